@@ -10,11 +10,17 @@ one hnswgpu_hnsw_search_dev launch.  With N > 1 every rank holds a replica of th
 own query batch (the 31k x 768 index fits one GPU, so the queries are what shard: "replicas", no
 collective on the data path); value = all ranks' queries / max-over-ranks time.  The row-sharded
 configurations (configs[3]: ONE IVF index whose lists are dealt to the GPUs; configs[4]: one HNSW
-sub-graph per GPU) run beside it for N > 1 and are reported in `sharded_ivf` / `sharded_hnsw`.
+sub-graph per GPU) run beside it for N > 1 with --full and are reported in `sharded_ivf` / `sharded_hnsw`.
 
 `python bench.py --gpus N` starts its N ranks itself (child processes with RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_* set; the parent never touches the GPU and relays rank 0's line); under
 torch.distributed.run the ranks are already there and it just runs as one of them.
+
+A plain run does what the headline needs and nothing else: data, index build, the ef sweep that fixes the operating
+point, `--warmup` steps, `--steps` timed steps.  `--full` adds every other measurement and check: the PMC passes, the
+latency and host-buffer figures, the HNSW / IVF rooflines, the other data sets and builders (by_distribution), the
+row-sharded legs, the reference protocol, the CPU baseline and the parity checks against the oracle.  The timed steps are
+the same in both.  `--dump-outputs DIR` writes what the last timed step returned (hnsw_ids.npy, hnsw_distances.npy).
 
 Prints ONE JSON line on rank 0.
 """
@@ -179,9 +185,18 @@ def main():
                     help="rows per GPU of the sharded 1536-d HNSW index (0 = skip that leg)")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 PMC passes that fill roofline.traffic")
     ap.add_argument("--no-dists", action="store_true", help="skip the gaussian / uniform / clustered operating points")
+    ap.add_argument("--full", action="store_true",
+                    help="every measurement and check beside the headline (PMC, rooflines, latencies, by_distribution, IVF, "
+                         "sharded legs, reference protocol, CPU baseline, oracle parity); the --no-* / --sharded options "
+                         "select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results to DIR/hnsw_ids.npy (float64) and DIR/hnsw_distances.npy "
+                         "(float32)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--launch-selftest", action="store_true", help=argparse.SUPPRESS)   # tests/: ranks report and exit
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not args.pmc_child:
         sys.exit(launch_ranks(args.gpus))
     if args.launch_selftest:     # no GPU needed: what a rank sees of the launcher's environment
@@ -202,12 +217,12 @@ def main():
     # PMC passes are child processes and start BEFORE this process touches the GPU.  Not under a profiler: its
     # preloaded library has already initialised the GPU here, and a profiler inside a profiler measures neither.
     profiled = any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "")
-    if world == 1 and not args.no_ivf and not args.no_pmc and not profiled:
+    if args.full and world == 1 and not args.no_ivf and not args.no_pmc and not profiled:
         traffic = pmc_traffic(args)
     ndev = max(torch.cuda.device_count(), 1)     # rehearsals may put several ranks on one GPU (local_rank >= ndev)
     torch.cuda.set_device(local_rank % ndev)
     dev = torch.device("cuda", local_rank % ndev)
-    if world > 1 or args.sharded:
+    if world > 1 or (args.full and args.sharded):
         if "MASTER_ADDR" not in os.environ:
             os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", "29517"
         backend = os.environ.get("HNSWGPU_BENCH_BACKEND", "nccl")   # "gloo": rehearse N ranks on fewer GPUs (RCCL refuses)
@@ -238,20 +253,23 @@ def main():
         t = torch.tensor([ef], device=dev)
         dist.broadcast(t, 0)
         ef = int(t.item())
-    # reference protocol: the first 100 base rows as queries (reproduce_02ms.clj:38)
-    Q100 = torch.from_numpy(base[:100]).to(dev)
-    t100, _ = idx.exact_knn_dev(Q100, K)
-    i100, _ = idx.hnsw_search_dev(Q100, K, ef)
-    rec100 = recall_at_k(i100, t100)
+    if args.full:
+        # reference protocol: the first 100 base rows as queries (reproduce_02ms.clj:38)
+        Q100 = torch.from_numpy(base[:100]).to(dev)
+        t100, _ = idx.exact_knn_dev(Q100, K)
+        i100, _ = idx.hnsw_search_dev(Q100, K, ef)
+        rec100 = recall_at_k(i100, t100)
 
     out_ids = torch.empty((args.nq, K), dtype=torch.int32, device=dev)
     out_d = torch.empty((args.nq, K), dtype=torch.float32, device=dev)
-    stats = torch.zeros((args.nq, 2), dtype=torch.int64, device=dev)
-    idx.hnsw_search_dev(Q, K, ef, out=(out_ids, out_d), stats=stats)
-    torch.cuda.synchronize()
-    evals = float(stats[:, 0].double().mean())
-    hops = float(stats[:, 1].double().mean())
+    if args.full:
+        stats = torch.zeros((args.nq, 2), dtype=torch.int64, device=dev)
+        idx.hnsw_search_dev(Q, K, ef, out=(out_ids, out_d), stats=stats)
+        torch.cuda.synchronize()
+        evals = float(stats[:, 0].double().mean())
+        hops = float(stats[:, 1].double().mean())
 
+    # the timed region is the same with and without --full (profiling on: roofline_hnsw's kernel time and f32 rows)
     for _ in range(args.warmup):
         idx.hnsw_search_dev(Q, K, ef, out=(out_ids, out_d))
     idx.set_profiling(True)
@@ -275,6 +293,74 @@ def main():
     kern_ms, kern_n = idx.get_profile(engine.PROF_HNSW, reset=True)
     idx.set_profiling(False)
     qps = world * args.nq * args.steps / elapsed
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out_ids, out_d, rank, world)
+
+    result = {
+        "metric": "QPS @ recall@10>=0.98 (31k x 768, k=10); IVF scan achieved HBM GB/s vs roofline",
+        "value": round(qps, 1),
+        "unit": "queries/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "full": args.full,
+        "config": {
+            "workload": "hnsw search-knn (ultra_fast.clj:346-374 = graph.clj:297-320), 31,173 x 768 f32 (%s, java.util.Random "
+                        "seed 42; queries: the same generator, seed 43), k=10, M=16 ef_construction=200, index built on the "
+                        "device by the %s builder, batched HIP traversal kernel" % (args.dist, args.builder),
+            "builder": args.builder,
+            "queries_per_step_per_gpu": args.nq,
+            "ef_search": ef,
+            "recall_at_10": round(rec, 4),
+            "ef_sweep": sweep,
+            "parallelism": "replicas x%d (index replicated, queries sharded, no collective)" % world,
+            "hnsw_build_s": round(build_s, 2),
+        },
+    }
+    if args.full:
+        full_run(args, engine, dev, rank, world, idx, base, queries, Q, ef, out_ids, out_d, traffic, result,
+                 rec100=rec100, evals=evals, hops=hops, f32_rows=f32_rows, neighbours=neighbours, kern_ms=kern_ms,
+                 kern_n=kern_n)
+    idx.close()
+    if dist.is_initialized():
+        dist.barrier()
+        dist.destroy_process_group()
+    if rank == 0:
+        os.write(real_stdout, (json.dumps(result) + "\n").encode())
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, ids, dists, rank, world):
+    """--dump-outputs: the (nq, k) ids and distances the last timed step returned, as out_dir/hnsw_ids.npy (float64: exact for
+    every id) and hnsw_distances.npy (float32); with N ranks every rank writes its own, suffixed _rank<r>.  Beyond 64 MB over
+    all ranks: a fixed sample of query rows (seed 0, ascending), their indices in hnsw_rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    ids, dists = ids.cpu().numpy(), dists.cpu().numpy()
+    arrays = {}
+    cap = (DUMP_BYTES - 4096) // ((ids.shape[1] * 12 + 8) * world)     # f64 id + f32 distance per result, f64 row index
+    if ids.shape[0] > cap:
+        rows = np.sort(np.random.default_rng(0).choice(ids.shape[0], cap, replace=False))
+        arrays["hnsw_rows"] = rows.astype(np.float64)
+        ids, dists = ids[rows], dists[rows]
+    arrays["hnsw_ids"] = ids.astype(np.float64)
+    arrays["hnsw_distances"] = dists.astype(np.float32)
+    sfx = "" if world == 1 else "_rank%d" % rank
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + sfx + ".npy"), a)
+
+
+def full_run(args, engine, dev, rank, world, idx, base, queries, Q, ef, out_ids, out_d, traffic, result, rec100, evals, hops,
+             f32_rows, neighbours, kern_ms, kern_n):
+    """--full: the measurements and checks that follow the timed steps, into `result` (main() runs the PMC passes, the
+    first-100-rows recall and the counters launch before them)."""
     # single-query latency (configs[1] "single-query latency"): one query per launch
     torch.cuda.synchronize()
     lat = []
@@ -305,43 +391,21 @@ def main():
     moved_q = (nb_q * (code_row + 16) if tested else 0.0) + f32_q * (4 * DIM + 4) + hops * 4 * (2 * M)
     hnsw_gbs = moved_q * args.nq / (hnsw_avg_ms * 1e-3) / 1e9
 
-    result = {
-        "metric": "QPS @ recall@10>=0.98 (31k x 768, k=10); IVF scan achieved HBM GB/s vs roofline",
-        "value": round(qps, 1),
-        "unit": "queries/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {
-            "workload": "hnsw search-knn (ultra_fast.clj:346-374 = graph.clj:297-320), 31,173 x 768 f32 (%s, java.util.Random "
-                        "seed 42; queries: the same generator, seed 43), k=10, M=16 ef_construction=200, index built on the "
-                        "device by the %s builder, batched HIP traversal kernel" % (args.dist, args.builder),
-            "builder": args.builder,
-            "queries_per_step_per_gpu": args.nq,
-            "ef_search": ef,
-            "recall_at_10": round(rec, 4),
-            "recall_at_10_first100_base_rows": round(rec100, 4),
-            "ef_sweep": sweep,
-            "parallelism": "replicas x%d (index replicated, queries sharded, no collective)" % world,
-            "hnsw_build_s": round(build_s, 2),
-            "dist_evals_per_query": round(evals, 1),
-            "expansions_per_query": round(hops, 1),
-            "single_query_latency_ms": {"p50": round(lat_h[len(lat_h) // 2], 4), "min": round(lat_h[0], 4),
-                                        "p95": round(lat_h[int(len(lat_h) * 0.95)], 4),
-                                        "path": "hnswgpu_hnsw_search, host buffers in and out (the reference's search-knn seam): "
-                                                "query and results in mapped pinned memory, one launch, host-polled completion"},
-            "launch_paths": {k: engine.debug_counter(k) for k in ("hnsw_wave", "hnsw_solo", "hnsw_helpers", "hnsw_rejection", "hnsw_plain")},
-            "hnsw_rejection_state": dict(zip(("state", "int8_test_off", "f32_rows_per_neighbour"), idx.hnsw_rejection_state())),
-            "single_query_latency_dev_ms": {"p50": round(lat[len(lat) // 2], 4), "min": round(lat[0], 4),
-                                            "p95": round(lat[int(len(lat) * 0.95)], 4),
-                                            "path": "hnswgpu_hnsw_search_dev on torch's stream + torch.cuda.synchronize()"},
-        },
+    result["config"].update({
+        "recall_at_10_first100_base_rows": round(rec100, 4),
+        "dist_evals_per_query": round(evals, 1),
+        "expansions_per_query": round(hops, 1),
+        "single_query_latency_ms": {"p50": round(lat_h[len(lat_h) // 2], 4), "min": round(lat_h[0], 4),
+                                    "p95": round(lat_h[int(len(lat_h) * 0.95)], 4),
+                                    "path": "hnswgpu_hnsw_search, host buffers in and out (the reference's search-knn seam): "
+                                            "query and results in mapped pinned memory, one launch, host-polled completion"},
+        "launch_paths": {k: engine.debug_counter(k) for k in ("hnsw_wave", "hnsw_solo", "hnsw_helpers", "hnsw_rejection", "hnsw_plain")},
+        "hnsw_rejection_state": dict(zip(("state", "int8_test_off", "f32_rows_per_neighbour"), idx.hnsw_rejection_state())),
+        "single_query_latency_dev_ms": {"p50": round(lat[len(lat) // 2], 4), "min": round(lat[0], 4),
+                                        "p95": round(lat[int(len(lat) * 0.95)], 4),
+                                        "path": "hnswgpu_hnsw_search_dev on torch's stream + torch.cuda.synchronize()"},
+    })
+    result.update({
         "roofline_hnsw": {"bound": "infinity-cache gather", "achieved": round(hnsw_gbs, 1), "peak": IC_GATHER_GBS[1],
                           "unit": "GB/s", "frac": round(hnsw_gbs / IC_GATHER_GBS[1], 4),
                           "traffic": (traffic or {}).get("hnsw", None) and traffic["hnsw"]["traffic"],
@@ -370,7 +434,7 @@ def main():
                                   "23.9 MB) are Infinity-Cache resident, so the bound is the guide's measured ceiling for "
                                   "random ~1 KB rows of a 38-151 MB table (7.4-8.6 TB/s), not HBM; the HBM-resident traversal "
                                   "(1.25M x 1536, configs[4]) is the sharded_hnsw leg / tests, against 5.5-5.8 TB/s"},
-    }
+    })
     result["config"]["qps_host_buffers"] = host_buffer_qps(idx, queries, ef, args.steps)
     if rank == 0 and world == 1 and not args.no_dists:
         result["config"]["by_distribution"] = by_distribution(engine, dev, args, not args.no_cpu)
@@ -405,12 +469,6 @@ def main():
     if not args.no_cpu and rank == 0 and world == 1:
         result["cpu_baseline"] = cpu_baseline(idx, base, queries, ef)
         result["config"]["parity_checked"] = parity_check(idx, base, queries, ef, out_ids, out_d)
-    idx.close()
-    if dist.is_initialized():
-        dist.barrier()
-        dist.destroy_process_group()
-    if rank == 0:
-        os.write(real_stdout, (json.dumps(result) + "\n").encode())
 
 
 def host_buffer_qps(idx, queries, ef, steps):

@@ -152,6 +152,34 @@ def test_bench_starts_its_own_ranks():
     assert r.returncode == 0 and r.stdout.strip() == ""
 
 
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: the last timed step's ids (float64, exact) and distances (float32) as .npy files; a batch
+    whose results pass 64 MB is written as a fixed, sorted sample of query rows (the same rows on every run), indices
+    beside it (no GPU needed: the tensors are the caller's)."""
+    import torch
+
+    import bench
+
+    ids = torch.arange(50, dtype=torch.int32).reshape(5, 10) + (1 << 30)
+    d = torch.linspace(0, 1, 50, dtype=torch.float32).reshape(5, 10)
+    bench.dump_outputs(str(tmp_path / "a"), ids, d, 0, 1)
+    got_i, got_d = np.load(tmp_path / "a" / "hnsw_ids.npy"), np.load(tmp_path / "a" / "hnsw_distances.npy")
+    assert got_i.dtype == np.float64 and got_d.dtype == np.float32
+    assert np.array_equal(got_i, ids.numpy()) and np.array_equal(got_d, d.numpy())
+    assert not (tmp_path / "a" / "hnsw_rows.npy").exists()
+    n = 600_000                                             # 600k x 10 results x 12 B = 72 MB
+    ids = torch.arange(n * 10, dtype=torch.int32).reshape(n, 10)
+    d = torch.zeros((n, 10), dtype=torch.float32)
+    for sub in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / sub), ids, d, 1, 2)
+    total = sum(f.stat().st_size for f in (tmp_path / "b").iterdir())
+    assert 2 * total <= 64 << 20                            # two ranks' files within the limit
+    rows = np.load(tmp_path / "b" / "hnsw_rows_rank1.npy")
+    assert rows.dtype == np.float64 and (np.diff(rows) > 0).all() and rows[-1] < n
+    assert np.array_equal(np.load(tmp_path / "b" / "hnsw_ids_rank1.npy"), ids.numpy()[rows.astype(np.int64)])
+    assert np.array_equal(rows, np.load(tmp_path / "c" / "hnsw_rows_rank1.npy"))
+
+
 def test_load_rejects_damaged_headers_before_touching_anything(native_lib, tmp_path):
     """hnswgpu_load validates the 64-byte header against the documented limits and against the file size BEFORE it
     sizes a single read from it (no GPU involved up to that point): garbage row counts, dims, degrees and list counts
