@@ -1107,8 +1107,9 @@ static int launch_route_tail_wave(const RouteArgs &a, int nch, hipStream_t st) {
     return 0;
 }
 
-int launch_ivf_route(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t nprobe, Pair *pairs, int32_t *probes,
-                     int32_t *qcnt, hipStream_t st, const RouteStream *rs, bool two_launches) {
+int launch_ivf_route(hnswgpu_index *idx, const IvfSearchPlan &p, const float *d_Q, Pair *pairs, int32_t *probes, int32_t *qcnt,
+                     hipStream_t st, const RouteStream *rs) {
+    const int32_t nq = p.nq, nprobe = p.nprobe;
     RouteArgs a;
     memset(&a, 0, sizeof(a));
     if (rs) {
@@ -1116,13 +1117,13 @@ int launch_ivf_route(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t n
         a.qscal = rs->qscal;
         a.tau = rs->tau;
         a.surv_cnt = rs->surv_cnt;
-        a.k = rs->k;
-        a.seed_rows = stream_seed_rows(nq, idx->ivf_n_global > 0 ? idx->ivf_n_global : idx->n, idx->nlist);
+        a.k = p.k;
+        a.seed_rows = p.seed_rows;
         a.bk_cnt = rs->bk_cnt;
         a.bk_mem = rs->bk_mem;
-        a.bk_cap = rs->bk_cap;
-        a.home = rs->home;
-        if (rs->wl && rs->bk_cnt) {
+        a.bk_cap = p.bk_cap;
+        a.home = p.home ? 1 : 0;
+        if (rs->wl) {
             a.wl = *rs->wl;
             a.wl_on = 1;
         }
@@ -1130,7 +1131,7 @@ int launch_ivf_route(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t n
     a.dbg = g_tile_dbg_buf;  // null outside diagnostic sessions
     a.rows = idx->d_lrows;
     a.row_norms = idx->d_lnorms;
-    if (idx->d_lhalf && tune(HNSWGPU_TUNE_SEED_HALF, 1) != 0) {
+    if (p.seed_half) {
         a.half = idx->d_lhalf;
         a.hmeta = idx->d_lhmeta;
     }
@@ -1163,25 +1164,16 @@ int launch_ivf_route(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t n
     a.pairs = pairs;
     a.probes = probes;
     a.qcnt = qcnt;
-    const size_t lds = std::max<size_t>(sizeof(uint64_t) * ((nprobe <= kWave ? 2 * kNWave : kNWave) + 1) * nprobe, sizeof(float) * kSeedMax);
-    HG_REQUIRE(lds <= 48 * 1024, HNSWGPU_ELIMIT, "nprobe too large for the fused routing kernel");
+    const size_t lds = p.route_lds;
     const bool l2 = a.metric == METRIC_L2;
-    // the tail with a wave per query: large home-list batches (a query whose nearest list is shorter than k seeds its threshold itself)
-    const int64_t pqw = tune(HNSWGPU_TUNE_QUERY_WAVES, -1);
-    const bool wave_tail = two_launches && rs && rs->home && !a.wl_on && a.bk_cnt && a.tau && a.probes && a.surv_cnt && nprobe <= kWave &&
-                           rs->k <= kWave && idx->nlist <= 12 * 1024 && pqw != 0 && (pqw > 0 || nq >= 2048);
-    if (two_launches) {
+    if (p.route == IvfRoute::DistTail) {
         // larger batches: the distances by workgroups that share their centroid rows among a group of queries, then the tail
         // as a launch of its own (plain loads: the distances come from an earlier launch)
         // (the group's queries are staged in LDS: 1 KB x NCH each, 48 KB at most)
-        // cosine / dot, rows of 256 / 512 / 768 elements, from 256 queries: the GEMV-order distances on the f32 matrix cores
-        // (1M x 768 / 1024 centroids, VALU vs matrix cores: 32 queries 6.7 vs 11.8 us, 64: 8.6 vs 11.8, 128: 12.4 vs 11.9, 256:
-        // 20 vs 13, 1024: 54 vs 33, 4096: 150 vs 99)
-        const int64_t rm = tune(HNSWGPU_TUNE_ROUTE_MFMA, -1);  // -1 that rule, 0 never, 1 whenever possible, > 1: slices per query group
-        if (!l2 && idx->nch <= 3 && idx->ld == 256 * idx->nch && rm != 0 && (rm > 0 || nq >= 256)) {
+        if (p.route_mfma) {  // cosine / dot: the GEMV-order distances on the f32 matrix cores
             const int64_t ngroups = (nq + kRoute16Q - 1) / kRoute16Q, tiles = (idx->nlist + 15) / 16;
             int64_t split = std::max<int64_t>(1, std::min<int64_t>((tiles + kNWave - 1) / kNWave, (1024 + ngroups - 1) / ngroups));
-            if (rm > 1) split = std::max<int64_t>(1, std::min<int64_t>(rm, tiles));  // (tuning: slices per query group)
+            if (p.route_mfma_slices > 1) split = std::max<int64_t>(1, std::min<int64_t>(p.route_mfma_slices, tiles));  // (tuning: slices per query group)
             const int64_t tps = (tiles + split - 1) / split;
             a.rows_per_block = static_cast<int32_t>(tps * 16);
             a.blocks_per_query = static_cast<int32_t>((tiles + tps - 1) / tps);
@@ -1201,33 +1193,22 @@ do {                                                                            
             }
 #undef CALLM
             HG_HIP(hipGetLastError());
-            if (wave_tail) {
-                a.defer_file = 1;
-                HG_TRY(launch_route_tail_wave(a, idx->nch, st));
-                HG_TRY(launch_bucket_fill(a, st));
-                return 0;
-            }
-#define CALL(N, R, L) hipLaunchKernelGGL((ivf_route_tail_kernel<N, R, L>), dim3(static_cast<unsigned>(nq) + extra), dim3(kWG), lds, st, a)
+        } else {
+            a.qgroup = static_cast<int32_t>(std::max(2, std::min(std::min(16, 48 / idx->nch), nq / 16)));
+            const int64_t ngroups = (nq + a.qgroup - 1) / a.qgroup;
+            int64_t wb = std::max<int64_t>(1, p.route_wgs / ngroups);
+            int64_t rp = (idx->nlist + wb - 1) / wb;
+            rp = std::max<int64_t>(per_iter, (rp + per_iter - 1) / per_iter * per_iter);
+            a.rows_per_block = static_cast<int32_t>(rp);
+            a.blocks_per_query = static_cast<int32_t>((idx->nlist + rp - 1) / rp);
+            const int64_t dblocks = ngroups * a.blocks_per_query;
+            const size_t qlds = sizeof(float4) * kWave * idx->nch * a.qgroup;
+#define CALL(N, R, L) hipLaunchKernelGGL((ivf_route_dist_kernel<N, R, L>), dim3(static_cast<unsigned>(dblocks)), dim3(kWG), qlds, st, a)
             HG_DISPATCH(idx->nch, l2, CALL);
 #undef CALL
             HG_HIP(hipGetLastError());
-            return 0;
         }
-        a.qgroup = static_cast<int32_t>(std::max(2, std::min(std::min(16, 48 / idx->nch), nq / 16)));
-        const int64_t ngroups = (nq + a.qgroup - 1) / a.qgroup;
-        const int64_t route_wgs = tune(HNSWGPU_TUNE_ROUTE_WGS, 2048);
-        int64_t wb = std::max<int64_t>(1, route_wgs / ngroups);
-        int64_t rp = (idx->nlist + wb - 1) / wb;
-        rp = std::max<int64_t>(per_iter, (rp + per_iter - 1) / per_iter * per_iter);
-        a.rows_per_block = static_cast<int32_t>(rp);
-        a.blocks_per_query = static_cast<int32_t>((idx->nlist + rp - 1) / rp);
-        const int64_t dblocks = ngroups * a.blocks_per_query;
-        const size_t qlds = sizeof(float4) * kWave * idx->nch * a.qgroup;
-#define CALL(N, R, L) hipLaunchKernelGGL((ivf_route_dist_kernel<N, R, L>), dim3(static_cast<unsigned>(dblocks)), dim3(kWG), qlds, st, a)
-        HG_DISPATCH(idx->nch, l2, CALL);
-#undef CALL
-        HG_HIP(hipGetLastError());
-        if (wave_tail) {
+        if (p.route_tail_wave) {  // large home-list batches (a query whose nearest list is shorter than k seeds its threshold itself)
             a.defer_file = 1;
             HG_TRY(launch_route_tail_wave(a, idx->nch, st));
             HG_TRY(launch_bucket_fill(a, st));

@@ -283,21 +283,77 @@ int combine_search(hnswgpu_index::Combiner &c, hnswgpu_index::SearchReq &me,
 // pinned staging block of a combined batch (grown on demand)
 int ensure_pinned(hnswgpu_index *idx, size_t bytes);
 int scan_dense_topk(hnswgpu_index *idx, ScanArgs a, int32_t nq, int64_t nrows, hipStream_t st);
-// small IVF batches: routing in one launch, list scan with the merge / decode folded into its last workgroups
-// what the routing step prepares for the survivor stream of the list scan (stream_kernels.hpp), or null
+// Everything one IVF search decides, computed once before its first launch (ivf.hip: ivf_search_plan, where every rule and its
+// measured reason live) from the handle's state and ONE reading of the tuning table.  The stages of ivf_search_enqueue and
+// launch_ivf_route fill their arguments from it and decide nothing themselves.
+enum class IvfScan {
+    Tile,    // MFMA tile scan (cosine / dot: the k-ordered summation; Euclidean: l2_group_kernel)
+    Group,   // register-row group kernel: the GEMV order, a list fetched once per group of queries
+    Stream,  // survivor stream: int8 bounds -> survivors -> f32 distances in the GEMV order
+    Fused,   // one GEMV per pair, merge / decode / copy in the scan's last workgroups
+    Gemv     // one GEMV per pair, merge and decode launches behind it
+};
+enum class IvfRoute {
+    Given,      // the caller's lists
+    OneLaunch,  // ivf_route_kernel: distances, choice, probe table (and the stream's query set-up) in one launch
+    DistTail,   // a distance pass that shares centroid rows among queries, then the tail as a launch of its own
+    TileTopk,   // the centroid table through the tile kernel
+    GroupTopk,  // ... through the register-row group kernel (GEMV order)
+    Dense,      // dense [nq][nlist] distances + select
+    Scan        // partial lists + merge
+};
+struct IvfSearchPlan {
+    int32_t nq, k, nprobe;  // nprobe: clamped to the number of lists unless the caller chose them
+    int64_t npairs;         // nq * nprobe
+    int64_t cand_stride;    // candidates per query, upper bound (a multiple of 4)
+    IvfScan scan;
+    bool list_order;        // Fused / Gemv: the pairs in list order (pair_order_kernel), in runs of order_run
+    int32_t order_run;
+    int64_t tile_wgs, tile_ptiles;  // Tile / Group: workgroups the items are sized for; tiles per item of the persistent kernel (0: an item per workgroup)
+    IvfRoute route;
+    bool query_prep;        // Stream behind a routing without the stream's set-up: ivf_query_prep_kernel
+    int32_t seed_rows;      // OneLaunch / DistTail / query_prep: rows of the nearest list the first threshold is taken from ...
+    bool seed_half;         // ... in half precision
+    size_t route_lds;       // OneLaunch / DistTail: the tail's selection lists
+    bool route_tail_wave;   // DistTail: the tail with a wave per query (+ ivf_bucket_fill_kernel)
+    bool route_mfma;        // DistTail: the distances on the f32 matrix cores, route_mfma_slices (0: automatic) slices per query group;
+    int64_t route_mfma_slices, route_wgs;  // otherwise on the VALU, cut for route_wgs workgroups
+    // Stream only, in the order of its stages
+    bool grouped;           // the pairs filed by list (buckets of bk_cap members), a work list of up to wbound items
+    bool ordered;           // the queries served in the order of their nearest list
+    bool folded;            // the work list by extra workgroups of the routing tail's launch
+    bool home;              // the home-list pass (implies grouped and ordered): items of home_chunk rows, up to home_bound of them
+    bool mid;               // the half-precision pass
+    bool heavy;             // the heavy list (queries one workgroup cannot serve)
+    bool narrow;            // the bounds pass: the lane = row epilogue;
+    int qblocks;            // 32-query column blocks per group;
+    int64_t chunk_rows;     // rows per work item (whole tiles);
+    int32_t nchunks;        // items per list at most
+    int64_t wbound;
+    int32_t bk_cap;
+    int64_t surv_cap;       // survivors per query that fit
+    int64_t home_chunk, home_bound, home_stride, home_strays;  // home_stride: floats per query of the home list's bounds
+    bool home_select_wave;  // a wave per query selects the home list's survivors
+    uint32_t heavy_times_mean, heavy_thr;
+    int32_t mid_slices_auto;  // workgroups per query of the half-precision pass by the rule (what `heavy` goes by) ...
+    int32_t mid_slices;       // ... and as launched (HNSWGPU_TUNE_MID_SLICES overrides)
+    int32_t mid_compact;      // entries up to which the pass compacts a survivor list (0: it does not)
+    int32_t finish_slices, finish_span, finish_adapt, finish_bisect, finish_direct;
+    int64_t finish_pstride;   // keys per query handed to its last workgroup
+    bool flag_in_finish;      // a flagged synchronous call: the finish kernel's last workgroup tells the caller
+};
+// the survivor stream's buffers that the routing step prepares (stream_kernels.hpp), or null
 struct RouteStream {
     uint32_t *qcodes;
     QueryScal *qscal;
     uint32_t *tau, *surv_cnt;
-    int32_t k;
     uint32_t *bk_cnt;  // per-list buckets of (query, list) pairs, or null (ungrouped bounds pass)
     uint2 *bk_mem;
-    int32_t bk_cap;
-    int32_t home;  // the home-list pass follows (stream_kernels.hpp, step 1a): a query whose nearest list holds k rows gets its threshold there
-    const struct WorklistArgs *wl;  // optional: the bounds pass's work list by extra workgroups of the tail's launch (filed: set by the launch)
+    const struct WorklistArgs *wl;  // the plan's `folded`: the bounds pass's work list by extra workgroups of the tail's launch (filed: set by the launch)
 };
-int launch_ivf_route(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t nprobe, Pair *pairs, int32_t *probes,
-                     int32_t *qcnt, hipStream_t st, const RouteStream *rs = nullptr, bool two_launches = false);
+// small IVF batches: routing in one launch (IvfRoute::OneLaunch); larger stream batches: distance pass + tail (DistTail)
+int launch_ivf_route(hnswgpu_index *idx, const IvfSearchPlan &p, const float *d_Q, Pair *pairs, int32_t *probes, int32_t *qcnt,
+                     hipStream_t st, const RouteStream *rs);
 // the survivor stream of the IVF list scan (stream_kernels.hpp)
 struct StreamArgs;
 struct FinishArgs;

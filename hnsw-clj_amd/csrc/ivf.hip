@@ -656,9 +656,10 @@ struct GroupPlan {
 // ptiles > 0: persistent workgroups pulling items of up to `ptiles` tiles off a queue (tile_scan_kernel); 0 = one
 // workgroup per item, items sized to fill the chip.  member_stride: a member's output base is q * member_stride + the
 // pair's offset in the query's candidate stream (0 = the offset alone: the survivor stream's order keys).
-static int plan_groups(hnswgpu_index *idx, int32_t nq, int32_t nprobe, const int32_t *d_probes, int64_t ptiles,
-                       int64_t member_stride, hipStream_t st, GroupPlan &g) {
-    const int64_t npairs = static_cast<int64_t>(nq) * nprobe;
+static int plan_groups(hnswgpu_index *idx, const IvfSearchPlan &p, const int32_t *d_probes, int64_t member_stride, hipStream_t st,
+                       GroupPlan &g) {
+    const int32_t nprobe = p.nprobe;
+    const int64_t npairs = p.npairs, ptiles = p.tile_ptiles;
     const int nlist = idx->nlist;
     // a multiple of 4 so that every query's array is 16-B aligned (float4 select)
     g.stride = (static_cast<int64_t>(nprobe) * idx->max_list_len + 3) / 4 * 4;
@@ -668,7 +669,7 @@ static int plan_groups(hnswgpu_index *idx, int32_t nq, int32_t nprobe, const int
     const int64_t mean = std::max<int64_t>(1, idx->n / std::max(nlist, 1));
     const int64_t est_groups = std::max<int64_t>(1, npairs / tq + nlist / 2);
     const int64_t mean_tiles = (mean + kTileRows - 1) / kTileRows;
-    const int64_t tgt = tune(HNSWGPU_TUNE_TILE_WGS, 2048);
+    const int64_t tgt = p.tile_wgs;
     const int64_t want = std::max<int64_t>(1, std::min<int64_t>(mean_tiles, (tgt + est_groups - 1) / est_groups));
     int64_t cr = ((mean_tiles + want - 1) / want) * kTileRows;
     if (ptiles > 0) cr = std::max<int64_t>(1, std::min<int64_t>(ptiles, mean_tiles)) * kTileRows;
@@ -715,19 +716,13 @@ static int plan_groups(hnswgpu_index *idx, int32_t nq, int32_t nprobe, const int
 // and stream the list through the MFMA tile kernel once per group; distances land in a dense
 // per-query candidate array (position = the pair's order key), then one select pass per query.
 // gemv_order: the register-row group kernel (GEMV summation order) instead of the MFMA tiles.
-static int ivf_tile_scan(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t nprobe,
-                         const int32_t *d_probes, const int32_t *d_qcnt, hipStream_t st, bool gemv_order) {
-    const int64_t npairs = static_cast<int64_t>(nq) * nprobe;
-    const int tq = tile_tq(idx->dim);
-    // persistent workgroups pulling items off a queue (tile_scan_kernel): items of up to `ptiles` tiles, however many
-    // there are -- the queue balances them.  0 = one workgroup per item, items sized to fill the chip (round 1)
-    const int64_t ptiles_env = tune(HNSWGPU_TUNE_TILE_PERSIST, 4);
-    // the L2 group kernel takes one item per workgroup; few groups: shorter items, so that every CU has several
-    const int64_t est_groups = std::max<int64_t>(1, npairs / tq + idx->nlist / 2);
-    const int64_t ptiles = idx->metric == METRIC_L2 || gemv_order ? 0 : (ptiles_env == 4 && est_groups < 1200 ? 2 : ptiles_env);
+static int ivf_tile_scan(hnswgpu_index *idx, const IvfSearchPlan &p, const float *d_Q, const int32_t *d_probes, const int32_t *d_qcnt,
+                         hipStream_t st) {
+    const int32_t nq = p.nq, k = p.k;
+    const bool gemv_order = p.scan == IvfScan::Group;
+    const int64_t ptiles = p.tile_ptiles;
     GroupPlan g;
-    const int64_t stride0 = (static_cast<int64_t>(nprobe) * idx->max_list_len + 3) / 4 * 4;
-    HG_TRY(plan_groups(idx, nq, nprobe, d_probes, ptiles, stride0, st, g));
+    HG_TRY(plan_groups(idx, p, d_probes, p.cand_stride, st, g));
     const int64_t stride = g.stride;
     HG_TRY(idx->s_tile.ensure(sizeof(float) * static_cast<size_t>(nq) * stride));  // queries already padded
     TileArgs t;
@@ -772,47 +767,30 @@ static int ivf_tile_scan(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32
     return launch_select(s, st);
 }
 
-// scratch of the survivor stream, carved out of s_qn: [QueryScal x nq | tau x nq | survivor count x nq]
-// The tuning values ONE search decides its passes by, read once (ivf_search_enqueue): the table is process-wide and another
-// thread may change it between the routing and the scan of the same search -- with the home-list decision flipping in between
-// the routing would seed no threshold for a scan that expects one (every query through the overflow fallback).
-struct StreamTune {
-    int64_t stream_mid, finish_order, stream_home, mid_slices, mid_compact, home_strays;
-    void read() {
-        stream_mid = tune(HNSWGPU_TUNE_STREAM_MID, -1);
-        finish_order = tune(HNSWGPU_TUNE_FINISH_ORDER, 512);  // 0 = never (A/B)
-        stream_home = tune(HNSWGPU_TUNE_STREAM_HOME, -1);
-        mid_slices = tune(HNSWGPU_TUNE_MID_SLICES, 0);
-        mid_compact = tune(HNSWGPU_TUNE_MID_COMPACT, 1);
-        home_strays = tune(HNSWGPU_TUNE_HOME_STRAYS, 32);
-    }
-};
-
+// buffers of the survivor stream's stages.  The first four are carved out of s_qn: [QueryScal x nq | tau x nq | survivor count x nq]
 struct StreamScratch {
-    StreamTune tn;
     uint32_t *qcodes;
     QueryScal *qscal;
     uint32_t *tau, *surv_cnt;
     // the (query, list) pairs filed by list for the grouped bounds pass (s_misc): counters [nlist], members [nlist][bk_cap]
     uint32_t *bk_cnt;
     uint2 *bk_mem;
-    int32_t bk_cap;
-    bool wl_folded;  // the routing tail's launch has built the bounds pass's work list (worklist_part_wg)
+    WorkDesc *desc;  // the grouped bounds pass's work list (s_misc2) and its item count
+    int32_t *nitems;
+    HomeDesc *home_desc;  // the home-list pass's work list (s_home) and its item count
+    int32_t *home_nit;
+    uint32_t *home_first;  // [nq] entries of a query's list behind the home-list launch
+    const int32_t *qorder;  // large batches: the queries in the order of their nearest list (s_stats)
+    uint4 *surv;            // [nq][surv_cap] survivor lists (s_tile)
+    uint32_t *heavy_cnt;    // the heavy list (s_heavy), when the plan has one
+    int32_t *heavy_list;
 };
 
-// Buckets for the pairs of a batch: room for the whole batch under every list (a list may be probed by every query) as
-// long as that stays under 256 MB -- 32M / nlist members per list otherwise.  A hotter list files what fits; the queries
-// beyond take the finish kernel's fallback (exact, just slower).
-static int stream_buckets(hnswgpu_index *idx, int32_t nq, int32_t nprobe, StreamScratch &s, hipStream_t st) {
-    const int64_t npairs = static_cast<int64_t>(nq) * nprobe;
-    (void)npairs;
-    int64_t cap = std::max<int64_t>(64, (32LL << 20) / std::max(idx->nlist, 1) / 32 * 32);  // <= 256 MB of members
-    cap = std::min<int64_t>(cap, (static_cast<int64_t>(nq) + 31) / 32 * 32);
-    const int64_t cap_env = tune(HNSWGPU_TUNE_STREAM_BUCKET, 0);  // tests: tiny buckets force the fallback
-    if (cap_env > 0) cap = cap_env;
+// The buckets for the pairs of a batch (capacity: IvfSearchPlan::bk_cap).
+static int stream_buckets(hnswgpu_index *idx, const IvfSearchPlan &p, StreamScratch &s, hipStream_t st) {
     // members in s_misc; the counters in a buffer of their own that is zero between searches (a 4 KB memset is a 6 us
     // launch: a thirtieth of a batch-32 search)
-    HG_TRY(idx->s_misc.ensure(sizeof(uint2) * static_cast<size_t>(idx->nlist) * cap));
+    HG_TRY(idx->s_misc.ensure(sizeof(uint2) * static_cast<size_t>(idx->nlist) * p.bk_cap));
     const size_t cnt_bytes = sizeof(uint32_t) * static_cast<size_t>(idx->nlist);
     if (idx->s_bk.cap < cnt_bytes) {
         HG_TRY(idx->s_bk.ensure(cnt_bytes));
@@ -822,7 +800,6 @@ static int stream_buckets(hnswgpu_index *idx, int32_t nq, int32_t nprobe, Stream
     idx->bk_dirty = true;  // until the work-list kernel of this search has been enqueued
     s.bk_cnt = idx->s_bk.as<uint32_t>();
     s.bk_mem = idx->s_misc.as<uint2>();
-    s.bk_cap = static_cast<int32_t>(cap);
     return 0;
 }
 static int stream_scratch(hnswgpu_index *idx, int32_t nq, StreamScratch &s) {
@@ -833,377 +810,6 @@ static int stream_scratch(hnswgpu_index *idx, int32_t nq, StreamScratch &s) {
     s.tau = reinterpret_cast<uint32_t *>(s.qscal + nq);
     s.surv_cnt = s.tau + nq;
     return 0;
-}
-
-// The half-precision pass of a batch (stream_kernels.hpp, step 1b).  Once the exact pass would be the largest kernel (its
-// rows are 3 KB each and every query fetches its own) the survivors first meet their half-precision rows.  The survivors
-// are a few per cent of the candidates: from ~1.5 M candidates per batch (48 queries x 32 lists x 977 rows; 5 queries at 10 M
-// rows) the pass saves more than its launch costs -- measured at 1M x 768: batch 32 0.183 ms without vs 0.195 with, 64:
-// 0.250 vs 0.243, 128: 0.298 vs 0.277.  HNSWGPU_TUNE_STREAM_MID=<queries> overrides (tests: 1 = always; 0 = never).
-static bool ivf_mid_mode(const hnswgpu_index *idx, int32_t nq, int32_t nprobe, const StreamTune &tn) {
-    const int64_t mid_env = tn.stream_mid;
-    const int64_t cand = static_cast<int64_t>(nq) * nprobe * ivf_mean_len(idx);
-    return idx->d_lhalf != nullptr && !idx->ivf_calibrating && (mid_env >= 0 ? (mid_env > 0 && nq >= mid_env) : cand >= 1500000);
-}
-// are the queries of a batch served in the order of their nearest list (grouped bounds pass, large batches)?
-static bool ivf_ordered_mode(const hnswgpu_index *idx, int32_t nq, bool grouped, const StreamTune &tn) {
-    const int64_t order_min = tn.finish_order;
-    return grouped && order_min > 0 && nq >= order_min && idx->nlist <= kOrderMaxLists;
-}
-// The home-list pass (stream_kernels.hpp, step 1a): batches in which the lists are home to about a query each or more --
-// every home list once through the matrix cores in half precision for all of its queries (ivf_home_kernel) instead of a
-// half row per (query, survivor), and the queries' thresholds from there instead of from 64 sampled f32 rows.  Rows of whole
-// 128-element steps; from 512 queries and half a query per list (measured on the bench index, on / off: batch
-// 128 0.265 / 0.266 ms, 256 0.321 / 0.318, 512 0.383 / 0.399, 1024 0.480 / 0.558); HNSWGPU_TUNE_STREAM_HOME: -1 this rule, 0
-// never, 1 whenever the queries are ordered.  Decided BEFORE the routing (whose tail then skips the threshold seed) and again by the scan: one rule.
-static bool ivf_home_mode(const hnswgpu_index *idx, int32_t nq, int32_t nprobe, bool grouped, const StreamTune &tn) {
-    const int64_t home_env = tn.stream_home;
-    const int64_t hstride = (idx->max_list_len + 15) / 16 * 16;
-    return ivf_mid_mode(idx, nq, nprobe, tn) && ivf_ordered_mode(idx, nq, grouped, tn) && idx->ld % 128 == 0 &&
-           home_env != 0 && tn.mid_slices <= 1 && tn.mid_compact != 0 &&
-           (home_env > 0 || (nq >= 512 && 2LL * nq >= idx->nlist)) && static_cast<int64_t>(nq) * hstride * 8 <= (2LL << 30) &&
-           (static_cast<int64_t>(nq) / home_group(idx->nch) + std::min<int64_t>(nq, idx->nlist)) * ((idx->max_list_len + 4095) / 4096) < (1LL << 30);
-}
-
-// The bounds pass's cut of the lists into work items -- by the routing (which builds the work list of a small batch inside
-// its tail's launch) and by the scan: one rule.
-struct WorkPlan {
-    int64_t chunk_rows;  // rows per work item: whole tiles; enough working workgroups to fill the chip a few times over
-    int32_t nchunks;
-    bool narrow;         // which epilogue: few queries per probed list -> lane = row
-    int qblocks;         // 32-query column blocks per group
-    int64_t wbound;      // grouped: items <= sum over lists of ceil(members / 32) * chunks <= (npairs / 32 + nlist) * nchunks
-};
-static WorkPlan stream_work_plan(const hnswgpu_index *idx, int32_t nq, int32_t nprobe, bool grouped, const StreamTune &tn) {
-    WorkPlan p;
-    const int64_t npairs = static_cast<int64_t>(nq) * nprobe;
-    const bool mid = ivf_mid_mode(idx, nq, nprobe, tn);
-    // The largest batches (a list probed by 256 queries and more on average, entries appended without bounds): two 32-query
-    // column blocks per group -- every staged row operand meets 64 queries, the lists leave L2 half as often
-    const int64_t wide2 = tune(HNSWGPU_TUNE_STREAM_WIDE2, -1);  // -1 that rule, 0 never, 1 whenever the epilogue allows
-    const int64_t narrow_env = tune(HNSWGPU_TUNE_STREAM_NARROW, -1);  // A/B: 0 / 1 force
-    p.narrow = narrow_env >= 0 ? narrow_env != 0 : npairs < 6LL * idx->nlist;
-    // (round 5 built FOUR blocks as well -- the list's rows out of the L2 once per 128 members -- and measured them slower at every
-    // batch size, 4096: 0.324 vs 0.281 ms, 16384: 0.862 vs 0.800 (two) / 0.864 (one): it is not the re-streamed rows that bound the
-    // pass at these sizes but a matrix instruction's 1 KB query operand out of LDS -- four SIMDs at one instruction per 32 cycles
-    // ARE the LDS's 128 bytes per cycle.  1 forces two blocks, 4 four, wherever the wide deferring epilogue runs.)
-    p.qblocks = 1;
-    if (grouped && mid && !p.narrow && idx->nch <= 4 /* (128 queries' codes of 1024 bytes: 128 KB of LDS) */ && wide2 != 0) {
-        if (wide2 == 4) p.qblocks = 4;
-        else if (wide2 > 0 || npairs >= 256LL * idx->nlist) p.qblocks = 2;
-    }
-    // (Also built in round 5 and removed again: the members' codes in REGISTERS -- a 32-member column block per wave, four or
-    // eight waves walking the same rows, no LDS operand at all -- on the hope that the CU's L1 would serve the second to eighth
-    // reader of a row operand: it does not (batch 4096: 0.386 vs 0.241 ms, 16384: 1.02 vs 0.67).)
-    const int64_t mean = ivf_mean_len(idx);
-    const int64_t mean_tiles = (mean + kTileRows - 1) / kTileRows, max_tiles = (idx->max_list_len + kTileRows - 1) / kTileRows;
-    // (grouped small batches -- a query or two per probed list -- in finer items: batch 32 on the bench index, target 1024 /
-    // 2048 / 4096 / 8192: 145.3 / 144.7 / 142.3 / 142.5 us per search)
-    const int64_t tgt = tune(HNSWGPU_TUNE_STREAM_WGS, grouped && npairs < 6LL * idx->nlist ? 4096 : 2048);
-    // units of work the target is spread over: the lists (or pairs) that have work -- times the GROUPS a list's members form (round
-    // 5: a list probed by 128 queries is four items per chunk already; cut into two chunks as well, every item staged its 24 KB of
-    // query codes for two row blocks per wave -- whole lists: batch 4096 0.389 -> 0.313 ms, 16384 0.819 -> 0.655 in the diagnostic build)
-    int64_t units = grouped ? std::min<int64_t>(npairs, idx->nlist) : npairs;
-    if (grouped) {  // (rounded up: 48 members per list are two groups -- batch 1536: 0.169 -> 0.155 ms with whole lists)
-        const int64_t per_group = std::max<int64_t>(units, 1) * kTileQ * p.qblocks;
-        units *= std::max<int64_t>(1, (npairs + per_group - 1) / per_group);
-    }
-    const int64_t want = std::max<int64_t>(1, std::min<int64_t>(mean_tiles, (tgt + units - 1) / std::max<int64_t>(units, 1)));
-    const int64_t cr = ((mean_tiles + want - 1) / want) * kTileRows, tpc = cr / kTileRows;
-    p.chunk_rows = cr;
-    p.nchunks = static_cast<int32_t>(std::max<int64_t>(1, (max_tiles + tpc / 2) / tpc));
-    p.wbound = (npairs / kTileQ + idx->nlist) * p.nchunks;
-    return p;
-}
-
-// The list scan as a survivor stream (stream_kernels.hpp): int8 bounds with a running threshold -> compact survivor
-// lists -> f32 distances (GEMV order), top-k, ids and distances written by the finish kernel.  The query codes, tau = none
-// and empty survivor lists are set up by the routing step.
-static int ivf_stream_scan(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t nprobe, const int32_t *d_qcnt,
-                           const int32_t *d_probes, int32_t *d_out_ids, float *d_out_dist, uint32_t *d_out_gord,
-                           const StreamScratch &sc, hipStream_t st) {
-    const int64_t npairs = static_cast<int64_t>(nq) * nprobe;
-    StreamArgs b;
-    memset(&b, 0, sizeof(b));
-    int64_t blocks;
-    const int32_t *qorder = nullptr;  // large batches: the queries in the order of their nearest list (below)
-    const int64_t stride = (static_cast<int64_t>(nprobe) * idx->max_list_len + 3) / 4 * 4;
-    const bool grouped = sc.bk_cnt != nullptr;
-    const StreamTune &tn = sc.tn;  // (one reading of the tuning table per search: the routing decided by the same values)
-    const WorkPlan plan = stream_work_plan(idx, nq, nprobe, grouped, tn);
-    const int64_t cr = plan.chunk_rows;
-    b.chunk_rows = static_cast<int32_t>(cr);
-    b.nchunks = plan.nchunks;
-    const bool mid = ivf_mid_mode(idx, nq, nprobe, tn);
-    const int64_t order_min = tn.finish_order;
-    const bool ordered = d_probes != nullptr && ivf_ordered_mode(idx, nq, grouped, tn);
-    const int64_t hstride = (idx->max_list_len + 15) / 16 * 16;
-    const int home_gq = home_group(idx->nch);
-    bool home = d_probes != nullptr && ivf_home_mode(idx, nq, nprobe, grouped, tn);  // (the routing took the same decision)
-    int64_t home_chunk = 256, home_bound = 0;
-    if (const int64_t hc = tune(HNSWGPU_TUNE_HOME_CHUNK, 0); hc >= 64) home_chunk = hc / 64 * 64;
-    if (home) {
-        const int64_t groups = nq / home_gq + std::min<int64_t>(nq, idx->nlist);
-        while (home_chunk < 4096 && groups * ((idx->max_list_len + home_chunk - 1) / home_chunk) > 16384) home_chunk *= 2;
-        home_bound = groups * ((idx->max_list_len + home_chunk - 1) / home_chunk);
-        HG_REQUIRE(home_bound < 2147483647LL, HNSWGPU_ELIMIT, "home-list pass: work list too large");
-    }
-    HomeDesc *home_desc = nullptr;
-    int32_t *home_nit = nullptr;
-    uint32_t *home_first = nullptr;  // [nq] entries of a query's list behind the home-list launch
-    if (home) {
-        HG_TRY(idx->s_home.ensure(sizeof(HomeDesc) * static_cast<size_t>(home_bound) + 64 + sizeof(uint32_t) * static_cast<size_t>(nq)));
-        HG_TRY(idx->s_dh.ensure(sizeof(float2) * static_cast<size_t>(nq) * hstride));
-        home_desc = idx->s_home.as<HomeDesc>();
-        home_nit = reinterpret_cast<int32_t *>(home_desc + home_bound);
-        home_first = reinterpret_cast<uint32_t *>(home_nit + 16);
-    }
-    const bool narrow = plan.narrow;
-    const int qblocks = plan.qblocks;
-    if (grouped) {
-        const int64_t wbound = plan.wbound;
-        HG_REQUIRE(wbound < 2147483647LL, HNSWGPU_ELIMIT, "bounds pass work list too large");
-        HG_TRY(idx->s_misc2.ensure(sizeof(WorkDesc) * static_cast<size_t>(wbound) + 64));
-        WorkDesc *desc = idx->s_misc2.as<WorkDesc>();
-        int32_t *nit = reinterpret_cast<int32_t *>(desc + wbound);
-        // (large batches: the query order of the half-precision pass and the finish kernel by a second workgroup of this launch)
-        size_t olds = 0;
-        if (ordered) {
-            HG_TRY(idx->s_stats.ensure(sizeof(int32_t) * static_cast<size_t>(nq)));  // (s_ids / s_outd may be the caller's outputs)
-            olds = sizeof(int32_t) * (idx->nlist + 1 + 1024);
-            if (olds > 32 * 1024) {  // (+ the work list's static 4 KB)
-                static bool attr_done[64] = {};
-                if (attr_needed(attr_done))
-                    HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ivf_worklist_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               static_cast<int>(sizeof(int32_t) * (kOrderMaxLists + 1 + 1024))));
-            }
-            qorder = idx->s_stats.as<int32_t>();
-        }
-        if (!sc.wl_folded) {  // (a small batch's list was built inside the routing tail's launch: worklist_part_wg)
-            hipLaunchKernelGGL(ivf_worklist_kernel, dim3(qorder ? 2 : 1), dim3(1024), olds, st, sc.bk_cnt, sc.bk_cap, idx->nlist,
-                               idx->d_listoff, cr, b.nchunks, desc, nit, d_probes, nq, idx->s_stats.as<int32_t>(), nprobe,
-                               home_desc, home_nit, home_gq, static_cast<int>(home_chunk), kTileQ * qblocks);
-            HG_HIP(hipGetLastError());
-        }
-        idx->bk_dirty = false;  // (the kernel leaves the counters zero)
-        b.wi_desc = desc;
-        b.nitems = nit;
-        b.bk_mem = sc.bk_mem;
-        b.bk_cap = sc.bk_cap;
-        blocks = (wbound + 7) & ~7LL;
-    } else {  // a handful of queries: every (query, list) pair is its own item
-        b.pairs = idx->s_pairs.as<Pair>();
-        b.npairs = static_cast<int32_t>(npairs);
-        blocks = npairs * b.nchunks;
-    }
-    // survivors per query that fit; a query with more takes the finish kernel's fallback (the plain f32 scan)
-    const int64_t cap_env = tune(HNSWGPU_TUNE_STREAM_CAP, 0);  // tests: a tiny list forces the fallback
-    int64_t cap = std::min<int64_t>(stride, std::max<int64_t>(4096, 4 * idx->max_list_len));
-    if (cap_env > 0) cap = cap_env;
-    cap = std::max<int64_t>(cap, 1);
-    HG_TRY(idx->s_tile.ensure(sizeof(uint4) * static_cast<size_t>(nq) * cap));
-    b.metric = idx->metric;
-    b.k = k;
-    b.ctile = idx->d_lctile;
-    b.cmeta = idx->d_lcmeta;
-    b.qcodes = sc.qcodes;
-    b.qscal = sc.qscal;
-    b.tau = sc.tau;
-    b.surv_cnt = sc.surv_cnt;
-    b.surv = idx->s_tile.as<uint4>();
-    b.cap = cap;
-#ifdef HG_DIAG
-    b.dbg = g_stream_dbg;  // ablation timing only (results are wrong on purpose): hnswgpu_debug_set_ablation
-#else
-    b.dbg = 0;
-#endif
-    b.stamps = g_tile_dbg_buf;  // null outside diagnostic sessions
-    b.defer = mid ? 1 : 0;
-    if (home) {
-        // the home lists first: every row of a query's nearest list through the matrix cores in half precision
-        // (ivf_home_kernel), then one workgroup per query takes the k-th smallest upper bound found there as the query's
-        // threshold and starts its survivor list with the rows it does not exclude (ivf_home_select_kernel).  The
-        // bounds pass below appends nothing for a (query, home list) pair and meets every other list with that threshold;
-        // what survives there (the part of a query's cluster that k-means put into a second list, above all) goes through the
-        // per-survivor half-precision pass behind it, held against the same threshold.
-        HG_REQUIRE(qorder != nullptr, HNSWGPU_EINVAL, "home-list pass without the query order");
-        b.home_pairs = idx->s_pairs.as<Pair>();
-        b.home_nprobe = nprobe;
-        HomeArgs ho;
-        memset(&ho, 0, sizeof(ho));
-        ho.items = home_desc;
-        ho.nitems = home_nit;
-        ho.qorder = qorder;
-        ho.half = idx->d_lhalf;
-        ho.hmeta = idx->d_lhmeta;
-        ho.ld = idx->ld;
-        ho.Q = d_Q;
-        ho.qld = idx->dim;
-        ho.dim = idx->dim;
-        ho.metric = idx->metric;
-        ho.dh = idx->s_dh.as<float2>();
-        ho.hstride = hstride;
-        HG_TRY(launch_home(ho, home_bound, idx->nch, st));
-        HomeSelectArgs hs;
-        memset(&hs, 0, sizeof(hs));
-        hs.dh = ho.dh;
-        hs.hstride = hstride;
-        hs.pairs = idx->s_pairs.as<Pair>();
-        hs.nq = nq;
-        hs.nprobe = nprobe;
-        hs.k = k;
-        hs.surv = b.surv;
-        hs.cap = cap;
-        hs.surv_cnt = b.surv_cnt;
-        hs.first = home_first;
-        hs.tau = b.tau;
-        // (large batches: a wave per query, four queries per workgroup -- the per-query chain four times as often per CU)
-        const int64_t pqw = tune(HNSWGPU_TUNE_QUERY_WAVES, -1);  // -1 from 2048 queries, 0 never, 1 wherever a wave can serve a query
-        if (k <= kWave && pqw != 0 && (pqw > 0 || nq >= 2048))
-            hipLaunchKernelGGL(ivf_home_select_wave_kernel, dim3((nq + kNWave - 1) / kNWave), dim3(kWG), 0, st, hs);
-        else
-            hipLaunchKernelGGL(ivf_home_select_kernel, dim3(nq), dim3(kWG), 0, st, hs);
-        HG_HIP(hipGetLastError());
-    }
-    hipEvent_t e0;
-    prof_begin(idx, PROF_IVF_SCAN, st, &e0);
-    // which epilogue: few queries per probed list -> lane = row (a list probed by more takes several passes); many -> lane = query
-    HG_TRY(launch_stream_bounds(b, blocks, idx->nch, narrow, st, qblocks));
-    prof_end(idx, PROF_IVF_SCAN, st, e0);
-    // Large batches: a query's survivors are, above all, its nearest list -- and several queries share one.  The queries are
-    // taken in the order of their nearest list, a contiguous eighth of that order per XCD, so that the queries which read
-    // the same rows run side by side on ONE L2 (each XCD otherwise fetches the list for itself).
-    if (!qorder && d_probes && order_min > 0 && nq >= order_min && idx->nlist <= kOrderMaxLists) {  // (ungrouped launches)
-        HG_TRY(idx->s_stats.ensure(sizeof(int32_t) * static_cast<size_t>(nq)));  // (s_ids / s_outd may be the caller's outputs)
-        const size_t olds = sizeof(int32_t) * (idx->nlist + 1 + 1024);
-        if (olds > 48 * 1024) {
-            static bool attr_done[64] = {};
-            if (attr_needed(attr_done))
-                HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pair_order_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           static_cast<int>(sizeof(int32_t) * (kOrderMaxLists + 1 + 1024))));
-        }
-        hipLaunchKernelGGL(pair_order_kernel, dim3(1), dim3(1024), olds, st, d_probes, nq, idx->nlist, idx->s_stats.as<int32_t>(), nprobe);
-        HG_HIP(hipGetLastError());
-        qorder = idx->s_stats.as<int32_t>();
-    }
-    FinishArgs f;
-    memset(&f, 0, sizeof(f));
-    f.prepass = mid ? 1 : 0;  // (lists of more than 128 entries only: what a compacting pass has left is evaluated in one step)
-    f.adapt = static_cast<int32_t>(tune(HNSWGPU_TUNE_FINISH_ADAPT, 1));        // A/B
-    f.bisect_min = static_cast<int32_t>(tune(HNSWGPU_TUNE_FINISH_BISECT, 1));  // A/B
-    f.dbg = g_tile_dbg_buf;
-    f.surv = b.surv;
-    f.surv_cnt = b.surv_cnt;
-    f.tau = b.tau;
-    f.cap = cap;
-    f.q_cnt = d_qcnt;
-    f.pairs = idx->s_pairs.as<Pair>();
-    f.nq = nq;
-    f.nprobe = nprobe;
-    f.k = k;
-    // workgroups per query: the chip filled a few times over for small batches; one or two for large ones
-    // (behind the half-precision pass a query has little more than k rows left to fetch: fewer workgroups, each of which
-    // reads the whole survivor list for the threshold)
-    // (measured at batch 32, slices 16 / 32 / 64 / 128: 0.176 / 0.169 / 0.176 / 0.184 ms; one query: 64 is best)
-    f.slices = static_cast<int32_t>(std::max<int64_t>(1, std::min<int64_t>(64, (mid ? 512 : (nq <= 64 ? 1024 : 2048)) / nq)));
-    f.span = nq <= 32 ? 16 : 64;
-    if (const int64_t sl = tune(HNSWGPU_TUNE_FINISH_SLICES, 0)) f.slices = static_cast<int32_t>(std::max<int64_t>(1, std::min<int64_t>(sl, 256)));  // tuning
-    if (const int64_t sp = tune(HNSWGPU_TUNE_FINISH_SPAN, 0)) f.span = sp >= 64 ? 64 : (sp >= 32 ? 32 : 16);
-    f.rows = idx->d_lrows;
-    f.row_norms = idx->d_lnorms;
-    f.ld = idx->ld;
-    f.Q = d_Q;
-    f.qld = idx->dim;
-    f.dim = idx->dim;
-    f.metric = idx->metric;
-    // Queries one workgroup cannot serve (see ivf_heavy_kernel): when the half-precision pass or the finish kernel gives a
-    // query fewer than eight, the queries with more than 4096 survivors -- and the overflowed ones, whose finish is the
-    // plain f32 scan of every candidate -- are listed, and 32 x 64 extra workgroups per launch take them in 64 slices.
-    const int64_t mid_slices = !mid ? 0 : (qorder ? 1 : std::max<int64_t>(1, std::min<int64_t>(16, 4096 / nq)));
-    const bool heavy = tune(HNSWGPU_TUNE_STREAM_HEAVY, 1) != 0 && ((mid && mid_slices < 8) || f.slices < 8);
-    constexpr int kHeavySlices = 64;
-    // keys per query handed to its last workgroup: the slices' lists -- or, for a short survivor list spread over many
-    // workgroups (small batches), a key per survivor (FinishArgs::direct; measured at batch 32: see DESIGN)
-    f.direct = f.slices >= 16 && !heavy && k <= kWave ? static_cast<int32_t>(std::max<int64_t>(0, std::min<int64_t>(1024, tune(HNSWGPU_TUNE_FINISH_DIRECT, 1024)))) : 0;
-    f.pstride = std::max<int64_t>(static_cast<int64_t>(heavy ? std::max(f.slices, kHeavySlices) : f.slices) * (k <= kWave ? 1 : kNWave) * k, f.direct);
-    const size_t keys = static_cast<size_t>(nq) * f.pstride;
-    HG_TRY(idx->s_partial.ensure(sizeof(uint64_t) * keys));
-    if (heavy) {
-        HG_TRY(idx->s_heavy.ensure(sizeof(int32_t) * (2 * static_cast<size_t>(nq) + 4)));
-        HeavyArgs ha;
-        memset(&ha, 0, sizeof(ha));
-        ha.surv_cnt = b.surv_cnt;
-        ha.nq = nq;
-        ha.cap = static_cast<uint32_t>(cap);
-        ha.times_mean = static_cast<uint32_t>(tune(HNSWGPU_TUNE_STREAM_HEAVY_MEAN, 4));
-        ha.thr = static_cast<uint32_t>(std::min<int64_t>(cap, tune(HNSWGPU_TUNE_STREAM_HEAVY_MIN, 4096)));
-        ha.cnt = idx->s_heavy.as<uint32_t>();
-        ha.list = idx->s_heavy.as<int32_t>() + 4;
-        if (home) {  // ... and the queries the bounds pass appended more than a few candidates to
-            ha.first = home_first;
-            ha.few = static_cast<uint32_t>(std::max<int64_t>(0, tn.home_strays));
-            ha.todo_cnt = idx->s_heavy.as<uint32_t>() + 1;
-            ha.todo = ha.list + nq;
-        }
-        HG_TRY(launch_heavy(ha, st));
-        f.heavy_cnt = ha.cnt;
-        f.heavy_list = ha.list;
-        f.heavy_slices = kHeavySlices;
-    }
-    HG_TRY(ensure_counters(idx, nq, st));
-    f.partial = idx->s_partial.as<uint64_t>();
-    f.done = idx->s_done.as<uint32_t>();
-    f.listids = idx->d_listids;
-    f.out_ids = d_out_ids;
-    f.out_dist = d_out_dist;
-    f.out_gord = d_out_gord;
-    f.stats = (idx->prof || idx->ivf_calibrating) ? idx->d_rej_stats : nullptr;
-    if (idx->zc_flag && !heavy && !idx->ivf_calibrating) {  // a flagged synchronous call: the last query's workgroup tells the caller
-        f.host_flag = idx->zc_flag;
-        f.flag_val = idx->zc_val;
-        f.done_q = idx->s_done.as<uint32_t>() + 2 * idx->s_done_n + 2;
-        idx->zc_taken = true;
-    }
-    f.qorder = f.slices == 1 ? qorder : nullptr;
-    f.main_blocks = static_cast<int32_t>(f.qorder ? (static_cast<int64_t>(nq) + 7) / 8 * 8 : static_cast<int64_t>(nq) * f.slices);
-    if (mid) {
-        MidArgs ma;
-        memset(&ma, 0, sizeof(ma));
-        ma.surv = b.surv;
-        ma.surv_cnt = b.surv_cnt;
-        ma.cap = cap;
-        ma.nq = nq;
-        ma.slices = qorder ? 1 : static_cast<int32_t>(std::max<int64_t>(1, std::min<int64_t>(16, 4096 / nq)));
-        if (const int64_t sl = tn.mid_slices) ma.slices = static_cast<int32_t>(std::max<int64_t>(1, std::min<int64_t>(sl, 64)));  // tuning
-        ma.qorder = ma.slices == 1 ? qorder : nullptr;
-        // one workgroup per query sees the whole list: it also applies the threshold of the upper bounds and compacts the
-        // list (up to 4096 entries: 16 KB of LDS -- more would cost the kernel its occupancy; a longer list is left to the finish kernel's own pass)
-        ma.tau = b.tau;
-        ma.k = k;
-        ma.compact = ma.slices == 1 && tn.mid_compact ? static_cast<int32_t>(std::min<int64_t>(cap, 4096)) : 0;
-        ma.half = idx->d_lhalf;
-        ma.hmeta = idx->d_lhmeta;
-        ma.ld = idx->ld;
-        ma.Q = d_Q;
-        ma.qld = idx->dim;
-        ma.dim = idx->dim;
-        ma.metric = idx->metric;
-        if (heavy) {
-            ma.heavy_cnt = f.heavy_cnt;
-            ma.heavy_list = f.heavy_list;
-            ma.heavy_slices = kHeavySlices;
-            ma.main_blocks = static_cast<int32_t>(ma.qorder ? (static_cast<int64_t>(nq) + 7) / 8 * 8 : static_cast<int64_t>(nq) * ma.slices);
-        }
-        ma.first = home_first;  // (home-list batches: half rows only for what the bounds pass appended)
-        if (home && heavy) {
-            ma.todo_cnt = idx->s_heavy.as<uint32_t>() + 1;
-            ma.todo = f.heavy_list + nq;
-            ma.todo_slices = 8;
-        }
-        ma.first_few = static_cast<int32_t>(tn.home_strays);
-        HG_TRY(launch_mid(ma, idx->nch, st));
-    }
-    return launch_finish(f, idx->nch, st);
 }
 
 // (query, list) pairs per list from which the MFMA tile scan serves a cosine / dot batch -- and with it the k-ordered
@@ -1233,18 +839,574 @@ static int32_t ivf_stream_max_k(const hnswgpu_index *idx) {
     return static_cast<int32_t>(kStreamMaxK / scale);
 }
 // can this search go through the survivor stream at all (int8 list rows present and switched on, k within its range)?
-static bool ivf_codes_usable(const hnswgpu_index *idx, int32_t k) {
+// tm: HNSWGPU_TUNE_TILE; codes_from: HNSWGPU_TUNE_IVF_CODES (a batch also needs that many queries)
+static bool ivf_codes_usable(const hnswgpu_index *idx, int32_t k, int tm, int64_t codes_from) {
     return idx->d_lctile != nullptr &&
            (idx->rejection_mode == 2 || (idx->rejection_mode == 1 && idx->dim >= 128 && !idx->ivf_stream_off)) &&
-           tile_mode() != 0 && k <= ivf_stream_max_k(idx) && tune(HNSWGPU_TUNE_IVF_CODES, 1) > 0;
+           tm != 0 && k <= ivf_stream_max_k(idx) && codes_from > 0;
 }
+// Which summation order does a search of this handle get -- the MFMA tile scan's or the GEMV order?  The one predicate of
+// ivf_search_plan and of the call combiner (hnswgpu_ivf_search), built from ONE reading of TILE, IVF_CODES and TILE_PAIRS.
+struct TileRule {
+    bool possible, always;   // tile_path_ok and TILE != 0; TILE == 1 (whenever possible)
+    int64_t pairs_per_list;  // otherwise: beyond this many (query, list) pairs per list
+    bool tiled(const hnswgpu_index *idx, int64_t npairs) const { return possible && (always || npairs > pairs_per_list * idx->nlist); }
+};
 // the boundary of the two summation orders for this handle and k (HNSWGPU_TILE_PAIRS overrides: the parity suite pins it
 // at 12 so that its small indexes still reach the tile path)
-static int64_t ivf_tile_pairs(const hnswgpu_index *idx, int32_t k) {
-    const int64_t e = tune(HNSWGPU_TUNE_TILE_PAIRS, 0);
-    if (e > 0) return e;
-    if (!ivf_codes_usable(idx, k)) return kTilePairs;
-    return idx->d_lhalf ? kTilePairsNever : kTilePairsCoded;
+static TileRule ivf_tile_rule(const hnswgpu_index *idx, int32_t k, int tm, int64_t codes_from, int64_t tile_pairs_env) {
+    TileRule r;
+    r.possible = tile_path_ok(idx) && tm != 0;
+    r.always = tm == 1;
+    if (tile_pairs_env > 0) r.pairs_per_list = tile_pairs_env;
+    else if (!ivf_codes_usable(idx, k, tm, codes_from)) r.pairs_per_list = kTilePairs;
+    else r.pairs_per_list = idx->d_lhalf ? kTilePairsNever : kTilePairsCoded;
+    return r;
+}
+
+constexpr int kHeavySlices = 64;
+
+// Everything ONE search decides (IvfSearchPlan, engine.hpp), before its first launch: a pure function of the handle's state and
+// of one reading of the tuning table -- every key at most once, every rule evaluated once, here.  The table is process-wide and
+// another thread may change it while a search is being enqueued: with the home-list decision flipping between the routing and
+// the scan the routing would seed no threshold for a scan that expects one (every query through the overflow fallback), with
+// the chunking changing the folded work list would be built for another cut of the lists than the bounds kernel walks.  The
+// limits a search can exceed are found here as well, with nothing enqueued yet.
+static int ivf_search_plan(const hnswgpu_index *idx, int32_t nq, int32_t k, int32_t nprobe, bool given_probes, IvfSearchPlan &p) {
+    memset(&p, 0, sizeof(p));
+    if (nprobe > idx->nlist && !given_probes) nprobe = idx->nlist;
+    const int64_t npairs = static_cast<int64_t>(nq) * nprobe;
+    p.nq = nq;
+    p.k = k;
+    p.nprobe = nprobe;
+    p.npairs = npairs;
+    // a multiple of 4 so that every query's array is 16-B aligned (float4 select)
+    p.cand_stride = (static_cast<int64_t>(nprobe) * idx->max_list_len + 3) / 4 * 4;
+    const bool dense_fits = static_cast<int64_t>(nq) * idx->nlist <= (64LL << 20);  // [nq][nlist] centroid distances
+    const bool l2 = idx->metric == METRIC_L2;
+
+    // ---- the scan path
+    // tiled (MFMA) list scan once the batch holds more than kTilePairs (query, list) pairs per list: the GEMV scan streams a
+    // list once per pair (pairs of one list side by side on one L2, see ScanArgs::order), the tile scan once per
+    // group of <= 32 pairs but at ~5 TB/s.  Measured on 1M x 768 / 1024 lists / nprobe 32 (tools/ivf_batch_time.py,
+    // GEMV vs tiled, end to end): batch 32: 0.42 vs 0.56 ms; 48: 0.54 vs 0.61; 64: 0.64 vs 0.64; 80: 0.72 vs 0.65;
+    // 96: 0.82 vs 0.71; 128: 1.03 vs 0.71.
+    const int tm = tile_mode();
+    const int code_env = static_cast<int>(tune(HNSWGPU_TUNE_IVF_CODES, 1));  // 0 = never (A/B), N > 0 = from N queries per batch
+    // the survivor stream (stream_kernels.hpp): k up to a tile chunk's rows can get a threshold from one chunk
+    const bool codes_ok = ivf_codes_usable(idx, k, tm, code_env) && nq >= code_env;
+    // (Euclidean has one arithmetic at every batch size -- its "tile" path is the register-row group kernel -- so the
+    // bounds pipeline below serves all its batches: batch 1024 at 1M x 768: 4.8 -> 2.8 ms)
+    const TileRule tile_rule = ivf_tile_rule(idx, k, tm, code_env, tune(HNSWGPU_TUNE_TILE_PAIRS, 0));
+    const bool use_tile = tile_rule.tiled(idx, npairs) && !(l2 && codes_ok && tm != 1);
+    // Between the fused small-batch path and the tile scan: bounds on the int8 list rows first, f32 distances -- the
+    // GEMV order, so the bits of this regime are unchanged -- only for the candidates that can still be among the k
+    // nearest (code_kernels.hpp).  Without the int8 rows (hnswgpu_set_rejection_test mode 0) the same bits come from
+    // the f32 scans below: one GEMV per pair, or the register-row group kernel from 1.5 pairs per list.
+    const bool use_code = !use_tile && codes_ok;
+    // A handful of queries: the launches around the list scan (select, probe table, merge, decode, copy) cost as much as
+    // the scan, so their work is folded into the routing and scan kernels' last workgroups (two launches instead of
+    // seven; 1M x 768, one query: 99 -> 88 us per call, 78 -> 74 us back to back).  Larger batches keep the separate
+    // launches: their merge runs one workgroup per query in parallel, and a tail would only lengthen the scan kernel.
+    const int fused_env = static_cast<int>(tune(HNSWGPU_TUNE_IVF_FUSED, 1));  // 0 = never, 1 = small batches (default), 2 = every GEMV-path batch
+    const bool fused_mode = !use_tile && !use_code && (fused_env == 2 || (fused_env == 1 && nq <= 8));
+    // Without int8 rows, from 1.5 pairs per list up to that boundary: the register-row group kernel (l2_kernels.hpp) fetches a list once for
+    // all the queries probing it and keeps the GEMV summation order, so the results stay bit-identical to the GEMV
+    // scan's (the contract up to kTilePairs pairs per list) while the second and third readers of a list cost no traffic.
+    // Same index, GEMV vs group, list-scan kernel / end to end: batch 32: 0.356 / 0.423 vs 0.331 / 0.423 ms;
+    // 48: 0.464 / 0.531 vs 0.431 / 0.527; 64: 0.572 / 0.643 vs 0.488 / 0.589 (about 885 distinct lists x 3 MB at
+    // ~5.5 TB/s).  The three extra launches (histogram, plan, scatter) cost what the kernel gains below 1.5 pairs per list.
+    const int group_env = static_cast<int>(tune(HNSWGPU_TUNE_IVF_GROUP, 1));  // 0 = never (A/B), 2 = from half a pair per list
+    const bool use_group = !use_tile && !use_code && !fused_mode && group_env && tm != 0 && idx->dim <= kL2MaxDim &&
+                           (group_env == 2 ? npairs * 2 >= idx->nlist : npairs * 2 >= 3LL * idx->nlist);
+    p.scan = use_tile ? IvfScan::Tile : use_code ? IvfScan::Stream : use_group ? IvfScan::Group : fused_mode ? IvfScan::Fused : IvfScan::Gemv;
+    // GEMV scan with enough pairs for lists to be probed twice: run the pairs in list order (see ScanArgs::order).
+    // Below half a pair per list there is next to nothing to share and the sort's ~10 us would be all cost.
+    const int order_mode = static_cast<int>(tune(HNSWGPU_TUNE_SCAN_ORDER, 1));  // 0 = never (A/B)
+    p.list_order = !use_tile && !use_group && !use_code && order_mode && idx->nlist <= kOrderMaxLists && npairs * 2 >= idx->nlist &&
+                   npairs <= (1 << 22);
+    if (p.list_order) {
+        // all the pairs of a list in one run (one XCD) while a run stays a small part of an XCD's share
+        p.order_run = 8;
+        while (p.order_run < 64 && static_cast<int64_t>(p.order_run) * idx->nlist < npairs) p.order_run *= 2;
+    }
+    if (use_tile || use_group) {
+        // persistent workgroups pulling items off a queue (tile_scan_kernel): items of up to `ptiles` tiles, however many
+        // there are -- the queue balances them.  0 = one workgroup per item, items sized to fill the chip (round 1)
+        const int64_t ptiles_env = tune(HNSWGPU_TUNE_TILE_PERSIST, 4);
+        // the L2 group kernel takes one item per workgroup; few groups: shorter items, so that every CU has several
+        const int64_t est_groups = std::max<int64_t>(1, npairs / tile_tq(idx->dim) + idx->nlist / 2);
+        p.tile_ptiles = l2 || use_group ? 0 : (ptiles_env == 4 && est_groups < 1200 ? 2 : ptiles_env);
+        p.tile_wgs = tune(HNSWGPU_TUNE_TILE_WGS, 2048);  // workgroups the items of a batch are sized for (plan_groups)
+    }
+
+    // ---- the survivor stream's passes
+    if (use_code) {
+        const int stream_group_min = static_cast<int>(tune(HNSWGPU_TUNE_STREAM_GROUP, 5));  // queries from which the bounds pass groups the pairs by list
+        p.grouped = nq >= stream_group_min;
+        const int64_t mean = ivf_mean_len(idx);
+        // The half-precision pass of a batch (stream_kernels.hpp, step 1b).  Once the exact pass would be the largest kernel (its
+        // rows are 3 KB each and every query fetches its own) the survivors first meet their half-precision rows.  The survivors
+        // are a few per cent of the candidates: from ~1.5 M candidates per batch (48 queries x 32 lists x 977 rows; 5 queries at 10 M
+        // rows) the pass saves more than its launch costs -- measured at 1M x 768: batch 32 0.183 ms without vs 0.195 with, 64:
+        // 0.250 vs 0.243, 128: 0.298 vs 0.277.  HNSWGPU_TUNE_STREAM_MID=<queries> overrides (tests: 1 = always; 0 = never).
+        const int64_t mid_env = tune(HNSWGPU_TUNE_STREAM_MID, -1);
+        const int64_t cand = npairs * mean;
+        p.mid = idx->d_lhalf != nullptr && !idx->ivf_calibrating && (mid_env >= 0 ? (mid_env > 0 && nq >= mid_env) : cand >= 1500000);
+        // are the queries of a batch served in the order of their nearest list (large batches)?  Grouped: by a second workgroup
+        // of the work-list launch; ungrouped: by a launch of pair_order_kernel behind the bounds pass
+        const int64_t order_min = tune(HNSWGPU_TUNE_FINISH_ORDER, 512);  // 0 = never (A/B)
+        p.ordered = order_min > 0 && nq >= order_min && idx->nlist <= kOrderMaxLists;
+        // The home-list pass (stream_kernels.hpp, step 1a): batches in which the lists are home to about a query each or more --
+        // every home list once through the matrix cores in half precision for all of its queries (ivf_home_kernel) instead of a
+        // half row per (query, survivor), and the queries' thresholds from there instead of from 64 sampled f32 rows.  Rows of whole
+        // 128-element steps; from 512 queries and half a query per list (measured on the bench index, on / off: batch
+        // 128 0.265 / 0.266 ms, 256 0.321 / 0.318, 512 0.383 / 0.399, 1024 0.480 / 0.558); HNSWGPU_TUNE_STREAM_HOME: -1 this rule, 0
+        // never, 1 whenever the queries are ordered.  Decided here, BEFORE the routing (whose tail then skips the threshold seed): the
+        // scan's stages read the same field.  home implies ordered and grouped.
+        const int64_t home_env = tune(HNSWGPU_TUNE_STREAM_HOME, -1);
+        const int64_t mid_slices_env = tune(HNSWGPU_TUNE_MID_SLICES, 0), mid_compact_env = tune(HNSWGPU_TUNE_MID_COMPACT, 1);
+        const int home_gq = home_group(idx->nch);
+        p.home_stride = (idx->max_list_len + 15) / 16 * 16;
+        p.home = p.mid && p.grouped && p.ordered && idx->ld % 128 == 0 && home_env != 0 && mid_slices_env <= 1 && mid_compact_env != 0 &&
+                 (home_env > 0 || (nq >= 512 && 2LL * nq >= idx->nlist)) && static_cast<int64_t>(nq) * p.home_stride * 8 <= (2LL << 30) &&
+                 (static_cast<int64_t>(nq) / home_gq + std::min<int64_t>(nq, idx->nlist)) * ((idx->max_list_len + 4095) / 4096) < (1LL << 30);
+        p.home_strays = tune(HNSWGPU_TUNE_HOME_STRAYS, 32);
+        p.home_chunk = 256;
+        if (const int64_t hc = tune(HNSWGPU_TUNE_HOME_CHUNK, 0); hc >= 64) p.home_chunk = hc / 64 * 64;
+        if (p.home) {
+            const int64_t groups = nq / home_gq + std::min<int64_t>(nq, idx->nlist);
+            while (p.home_chunk < 4096 && groups * ((idx->max_list_len + p.home_chunk - 1) / p.home_chunk) > 16384) p.home_chunk *= 2;
+            p.home_bound = groups * ((idx->max_list_len + p.home_chunk - 1) / p.home_chunk);
+            HG_REQUIRE(p.home_bound < 2147483647LL, HNSWGPU_ELIMIT, "home-list pass: work list too large");
+        }
+        // small grouped batches: the bounds pass's work list by extra workgroups of the routing tail's launch (larger ones order
+        // their queries in a second workgroup of ivf_worklist_kernel: they keep that launch)
+        p.folded = p.grouped && !given_probes && !p.ordered && tune(HNSWGPU_TUNE_WORKLIST_FOLD, 1) != 0 && dense_fits;
+
+        // The bounds pass's cut of the lists into work items -- for the routing (which builds the work list of a small batch
+        // inside its tail's launch) and for the scan: one cut.
+        //   chunk_rows: rows per work item: whole tiles; enough working workgroups to fill the chip a few times over
+        //   narrow:     which epilogue: few queries per probed list -> lane = row
+        //   qblocks:    32-query column blocks per group
+        //   wbound:     grouped: items <= sum over lists of ceil(members / 32) * chunks <= (npairs / 32 + nlist) * nchunks
+        // The largest batches (a list probed by 256 queries and more on average, entries appended without bounds): two 32-query
+        // column blocks per group -- every staged row operand meets 64 queries, the lists leave L2 half as often
+        const int64_t wide2 = tune(HNSWGPU_TUNE_STREAM_WIDE2, -1);  // -1 that rule, 0 never, 1 whenever the epilogue allows
+        const int64_t narrow_env = tune(HNSWGPU_TUNE_STREAM_NARROW, -1);  // A/B: 0 / 1 force
+        p.narrow = narrow_env >= 0 ? narrow_env != 0 : npairs < 6LL * idx->nlist;
+        // (round 5 built FOUR blocks as well -- the list's rows out of the L2 once per 128 members -- and measured them slower at every
+        // batch size, 4096: 0.324 vs 0.281 ms, 16384: 0.862 vs 0.800 (two) / 0.864 (one): it is not the re-streamed rows that bound the
+        // pass at these sizes but a matrix instruction's 1 KB query operand out of LDS -- four SIMDs at one instruction per 32 cycles
+        // ARE the LDS's 128 bytes per cycle.  1 forces two blocks, 4 four, wherever the wide deferring epilogue runs.)
+        p.qblocks = 1;
+        if (p.grouped && p.mid && !p.narrow && idx->nch <= 4 /* (128 queries' codes of 1024 bytes: 128 KB of LDS) */ && wide2 != 0) {
+            if (wide2 == 4) p.qblocks = 4;
+            else if (wide2 > 0 || npairs >= 256LL * idx->nlist) p.qblocks = 2;
+        }
+        // (Also built in round 5 and removed again: the members' codes in REGISTERS -- a 32-member column block per wave, four or
+        // eight waves walking the same rows, no LDS operand at all -- on the hope that the CU's L1 would serve the second to eighth
+        // reader of a row operand: it does not (batch 4096: 0.386 vs 0.241 ms, 16384: 1.02 vs 0.67).)
+        const int64_t mean_tiles = (mean + kTileRows - 1) / kTileRows, max_tiles = (idx->max_list_len + kTileRows - 1) / kTileRows;
+        // (grouped small batches -- a query or two per probed list -- in finer items: batch 32 on the bench index, target 1024 /
+        // 2048 / 4096 / 8192: 145.3 / 144.7 / 142.3 / 142.5 us per search)
+        const int64_t tgt = tune(HNSWGPU_TUNE_STREAM_WGS, p.grouped && npairs < 6LL * idx->nlist ? 4096 : 2048);
+        // units of work the target is spread over: the lists (or pairs) that have work -- times the GROUPS a list's members form (round
+        // 5: a list probed by 128 queries is four items per chunk already; cut into two chunks as well, every item staged its 24 KB of
+        // query codes for two row blocks per wave -- whole lists: batch 4096 0.389 -> 0.313 ms, 16384 0.819 -> 0.655 in the diagnostic build)
+        int64_t units = p.grouped ? std::min<int64_t>(npairs, idx->nlist) : npairs;
+        if (p.grouped) {  // (rounded up: 48 members per list are two groups -- batch 1536: 0.169 -> 0.155 ms with whole lists)
+            const int64_t per_group = std::max<int64_t>(units, 1) * kTileQ * p.qblocks;
+            units *= std::max<int64_t>(1, (npairs + per_group - 1) / per_group);
+        }
+        const int64_t want = std::max<int64_t>(1, std::min<int64_t>(mean_tiles, (tgt + units - 1) / std::max<int64_t>(units, 1)));
+        const int64_t cr = ((mean_tiles + want - 1) / want) * kTileRows, tpc = cr / kTileRows;
+        p.chunk_rows = cr;
+        p.nchunks = static_cast<int32_t>(std::max<int64_t>(1, (max_tiles + tpc / 2) / tpc));
+        p.wbound = (npairs / kTileQ + idx->nlist) * p.nchunks;
+        HG_REQUIRE(!p.grouped || p.wbound < 2147483647LL, HNSWGPU_ELIMIT, "bounds pass work list too large");
+
+        if (p.grouped) {
+            // Buckets for the pairs of a batch: room for the whole batch under every list (a list may be probed by every query) as
+            // long as that stays under 256 MB -- 32M / nlist members per list otherwise.  A hotter list files what fits; the queries
+            // beyond take the finish kernel's fallback (exact, just slower).
+            int64_t bk_cap = std::max<int64_t>(64, (32LL << 20) / std::max(idx->nlist, 1) / 32 * 32);  // <= 256 MB of members
+            bk_cap = std::min<int64_t>(bk_cap, (static_cast<int64_t>(nq) + 31) / 32 * 32);
+            const int64_t bk_env = tune(HNSWGPU_TUNE_STREAM_BUCKET, 0);  // tests: tiny buckets force the fallback
+            p.bk_cap = static_cast<int32_t>(bk_env > 0 ? bk_env : bk_cap);
+        }
+        // survivors per query that fit; a query with more takes the finish kernel's fallback (the plain f32 scan)
+        const int64_t cap_env = tune(HNSWGPU_TUNE_STREAM_CAP, 0);  // tests: a tiny list forces the fallback
+        p.surv_cap = std::min<int64_t>(p.cand_stride, std::max<int64_t>(4096, 4 * idx->max_list_len));
+        if (cap_env > 0) p.surv_cap = cap_env;
+        p.surv_cap = std::max<int64_t>(p.surv_cap, 1);
+
+        p.finish_adapt = static_cast<int32_t>(tune(HNSWGPU_TUNE_FINISH_ADAPT, 1));    // A/B
+        p.finish_bisect = static_cast<int32_t>(tune(HNSWGPU_TUNE_FINISH_BISECT, 1));  // A/B
+        // workgroups per query: the chip filled a few times over for small batches; one or two for large ones
+        // (behind the half-precision pass a query has little more than k rows left to fetch: fewer workgroups, each of which
+        // reads the whole survivor list for the threshold)
+        // (measured at batch 32, slices 16 / 32 / 64 / 128: 0.176 / 0.169 / 0.176 / 0.184 ms; one query: 64 is best)
+        p.finish_slices = static_cast<int32_t>(std::max<int64_t>(1, std::min<int64_t>(64, (p.mid ? 512 : (nq <= 64 ? 1024 : 2048)) / nq)));
+        p.finish_span = nq <= 32 ? 16 : 64;
+        if (const int64_t sl = tune(HNSWGPU_TUNE_FINISH_SLICES, 0)) p.finish_slices = static_cast<int32_t>(std::max<int64_t>(1, std::min<int64_t>(sl, 256)));  // tuning
+        if (const int64_t sp = tune(HNSWGPU_TUNE_FINISH_SPAN, 0)) p.finish_span = sp >= 64 ? 64 : (sp >= 32 ? 32 : 16);
+        // Queries one workgroup cannot serve (see ivf_heavy_kernel): when the half-precision pass or the finish kernel gives a
+        // query fewer than eight, the queries with more than 4096 survivors -- and the overflowed ones, whose finish is the
+        // plain f32 scan of every candidate -- are listed, and 32 x 64 extra workgroups per launch take them in 64 slices.
+        // (carried over as it is: `heavy` goes by the AUTOMATIC slice count of the half-precision pass, mid_slices_auto, while the
+        // pass itself is launched with mid_slices, which HNSWGPU_TUNE_MID_SLICES overrides)
+        p.mid_slices_auto = !p.mid ? 0 : (p.ordered ? 1 : static_cast<int32_t>(std::max<int64_t>(1, std::min<int64_t>(16, 4096 / nq))));
+        p.heavy = tune(HNSWGPU_TUNE_STREAM_HEAVY, 1) != 0 && ((p.mid && p.mid_slices_auto < 8) || p.finish_slices < 8);
+        if (p.heavy) {
+            p.heavy_times_mean = static_cast<uint32_t>(tune(HNSWGPU_TUNE_STREAM_HEAVY_MEAN, 4));
+            p.heavy_thr = static_cast<uint32_t>(std::min<int64_t>(p.surv_cap, tune(HNSWGPU_TUNE_STREAM_HEAVY_MIN, 4096)));
+        }
+        // keys per query handed to its last workgroup: the slices' lists -- or, for a short survivor list spread over many
+        // workgroups (small batches), a key per survivor (FinishArgs::direct; measured at batch 32: see DESIGN)
+        p.finish_direct = p.finish_slices >= 16 && !p.heavy && k <= kWave ? static_cast<int32_t>(std::max<int64_t>(0, std::min<int64_t>(1024, tune(HNSWGPU_TUNE_FINISH_DIRECT, 1024)))) : 0;
+        p.finish_pstride = std::max<int64_t>(static_cast<int64_t>(p.heavy ? std::max(p.finish_slices, kHeavySlices) : p.finish_slices) * (k <= kWave ? 1 : kNWave) * k, p.finish_direct);
+        if (p.mid) {
+            p.mid_slices = p.mid_slices_auto;
+            if (mid_slices_env) p.mid_slices = static_cast<int32_t>(std::max<int64_t>(1, std::min<int64_t>(mid_slices_env, 64)));  // tuning
+            // one workgroup per query sees the whole list: it also applies the threshold of the upper bounds and compacts the
+            // list (up to 4096 entries: 16 KB of LDS -- more would cost the kernel its occupancy; a longer list is left to the finish kernel's own pass)
+            p.mid_compact = p.mid_slices == 1 && mid_compact_env ? static_cast<int32_t>(std::min<int64_t>(p.surv_cap, 4096)) : 0;
+        }
+        // a flagged synchronous call: the last query's workgroup of the finish kernel tells the caller
+        p.flag_in_finish = idx->zc_flag && !p.heavy && !idx->ivf_calibrating;
+    }
+
+    // ---- the routing
+    const int stream_route_max = static_cast<int>(tune(HNSWGPU_TUNE_STREAM_ROUTE, 12));  // largest batch routed by the one-launch routing kernel
+    // queries from which a GEMV-order batch routes through the group kernel
+    // (Euclidean 1M x 768: 512 queries 0.85 vs 0.87 ms (GEMV vs group), 1024: 1.50 vs 1.43, 4096: 5.08 vs 4.70)
+    const int route_group_min = static_cast<int>(tune(HNSWGPU_TUNE_ROUTE_GROUP, 1024));
+    if (given_probes)  // caller-chosen lists (the :turbo mode's random partitions, :271-272); -1 = none
+        p.route = IvfRoute::Given;
+    else if (!use_tile && (fused_mode || (use_code && nq <= stream_route_max)) && dense_fits)
+        // small batches: distances to the centroids, the choice of the nprobe nearest and the probe table in ONE launch
+        // (for the survivor stream also the query codes, tau = none and the empty survivor lists)
+        p.route = IvfRoute::OneLaunch;
+    else if (use_code && dense_fits)
+        // survivor stream, larger batches: the centroid distances by a pass that serves a group of queries per fetch of a
+        // centroid row (the GEMV order, same bits), then ONE launch for everything else of the routing -- select, probe
+        // table, pairs filed by list, query codes, first thresholds
+        p.route = IvfRoute::DistTail;
+    else if (use_tile)  // every query against the centroid table on the tile kernel as well
+        p.route = IvfRoute::TileTopk;
+    else if (nq >= route_group_min && idx->dim <= kL2MaxDim && tm != 0)
+        // a large batch in the GEMV order (Euclidean): the centroid table once per group of 32 queries (register-row group
+        // kernel) instead of once per query, the same bits
+        p.route = IvfRoute::GroupTopk;
+    else if (dense_fits)  // dense [nq][nlist] distances + select
+        p.route = IvfRoute::Dense;
+    else
+        p.route = IvfRoute::Scan;
+    const bool stream_route = p.route == IvfRoute::OneLaunch || p.route == IvfRoute::DistTail;
+    // what the routing kernels do in their tail -- codes, empty survivor lists, first thresholds -- by a launch of its own
+    p.query_prep = use_code && !stream_route;
+    if (stream_route || p.query_prep) {
+        p.seed_rows = stream_seed_rows(nq, idx->ivf_n_global > 0 ? idx->ivf_n_global : idx->n, idx->nlist);
+        p.seed_half = idx->d_lhalf && tune(HNSWGPU_TUNE_SEED_HALF, 1) != 0;  // the first thresholds from half-precision rows
+    }
+    if (stream_route) {
+        p.route_lds = std::max<size_t>(sizeof(uint64_t) * ((nprobe <= kWave ? 2 * kNWave : kNWave) + 1) * nprobe, sizeof(float) * kSeedMax);
+        HG_REQUIRE(p.route_lds <= 48 * 1024, HNSWGPU_ELIMIT, "nprobe too large for the fused routing kernel");
+    }
+    // (large batches: a wave per query, four queries per workgroup -- the per-query chain four times as often per CU)
+    const int64_t pqw = use_code ? tune(HNSWGPU_TUNE_QUERY_WAVES, -1) : 0;  // -1 from 2048 queries, 0 never, 1 wherever a wave can serve a query
+    const bool query_waves = pqw != 0 && (pqw > 0 || nq >= 2048);
+    p.home_select_wave = p.home && k <= kWave && query_waves;
+    if (p.route == IvfRoute::DistTail) {
+        // the tail with a wave per query: large home-list batches (a query whose nearest list is shorter than k seeds its threshold itself)
+        p.route_tail_wave = p.home && nprobe <= kWave && k <= kWave && idx->nlist <= 12 * 1024 && query_waves;
+        // cosine / dot, rows of 256 / 512 / 768 elements, from 256 queries: the GEMV-order distances on the f32 matrix cores
+        // (1M x 768 / 1024 centroids, VALU vs matrix cores: 32 queries 6.7 vs 11.8 us, 64: 8.6 vs 11.8, 128: 12.4 vs 11.9, 256:
+        // 20 vs 13, 1024: 54 vs 33, 4096: 150 vs 99)
+        const int64_t rm = tune(HNSWGPU_TUNE_ROUTE_MFMA, -1);  // -1 that rule, 0 never, 1 whenever possible, > 1: slices per query group
+        p.route_mfma = !l2 && idx->nch <= 3 && idx->ld == 256 * idx->nch && rm != 0 && (rm > 0 || nq >= 256);
+        p.route_mfma_slices = rm > 1 ? rm : 0;
+        p.route_wgs = tune(HNSWGPU_TUNE_ROUTE_WGS, 2048);  // workgroups the VALU distance pass is cut for
+    }
+    return 0;
+}
+
+// The dynamic LDS of the query-order histogram (pair_order_kernel, and the second workgroup of ivf_worklist_kernel -- behind its
+// static 4 KB): [nlist + 1 + 1024] ints.  Beyond the default limit: raised once per device, for the largest histogram the kernels support.
+static int order_lds(bool worklist, int nlist, size_t *lds) {
+    static bool attr_done[2][64] = {};
+    *lds = sizeof(int32_t) * (nlist + 1 + 1024);
+    if (*lds > (worklist ? 32 : 48) * 1024 && attr_needed(attr_done[worklist]))
+        HG_HIP(hipFuncSetAttribute(worklist ? reinterpret_cast<const void *>(&ivf_worklist_kernel) : reinterpret_cast<const void *>(&pair_order_kernel),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sizeof(int32_t) * (kOrderMaxLists + 1 + 1024))));
+    return 0;
+}
+
+// ---- The list scan as a survivor stream (stream_kernels.hpp): int8 bounds with a running threshold -> compact survivor
+// lists -> f32 distances (GEMV order), top-k, ids and distances written by the finish kernel.  The query codes, tau = none
+// and empty survivor lists are set up by the routing step.  One function per launch, in the order of ivf_stream_scan; each
+// fills its arguments from the plan, the handle and the scratch and decides nothing.
+
+// grouped batches: the bounds pass's work list (and, for ordered batches, the query order by a second workgroup of the launch)
+static int stream_worklist(hnswgpu_index *idx, const IvfSearchPlan &p, StreamScratch &sc, const int32_t *d_probes, hipStream_t st) {
+    HG_TRY(idx->s_misc2.ensure(sizeof(WorkDesc) * static_cast<size_t>(p.wbound) + 64));
+    sc.desc = idx->s_misc2.as<WorkDesc>();
+    sc.nitems = reinterpret_cast<int32_t *>(sc.desc + p.wbound);
+    // (large batches: the query order of the half-precision pass and the finish kernel by a second workgroup of this launch)
+    size_t olds = 0;
+    if (p.ordered) {
+        HG_TRY(idx->s_stats.ensure(sizeof(int32_t) * static_cast<size_t>(p.nq)));  // (s_ids / s_outd may be the caller's outputs)
+        HG_TRY(order_lds(true, idx->nlist, &olds));
+        sc.qorder = idx->s_stats.as<int32_t>();
+    }
+    if (!p.folded) {  // (a small batch's list was built inside the routing tail's launch: worklist_part_wg)
+        hipLaunchKernelGGL(ivf_worklist_kernel, dim3(sc.qorder ? 2 : 1), dim3(1024), olds, st, sc.bk_cnt, p.bk_cap, idx->nlist,
+                           idx->d_listoff, p.chunk_rows, p.nchunks, sc.desc, sc.nitems, d_probes, p.nq, idx->s_stats.as<int32_t>(), p.nprobe,
+                           sc.home_desc, sc.home_nit, home_group(idx->nch), static_cast<int>(p.home_chunk), kTileQ * p.qblocks);
+        HG_HIP(hipGetLastError());
+    }
+    idx->bk_dirty = false;  // (the kernel leaves the counters zero)
+    return 0;
+}
+
+// the home lists first: every row of a query's nearest list through the matrix cores in half precision
+// (ivf_home_kernel), then one workgroup per query takes the k-th smallest upper bound found there as the query's
+// threshold and starts its survivor list with the rows it does not exclude (ivf_home_select_kernel).  The
+// bounds pass below appends nothing for a (query, home list) pair and meets every other list with that threshold;
+// what survives there (the part of a query's cluster that k-means put into a second list, above all) goes through the
+// per-survivor half-precision pass behind it, held against the same threshold.
+static int stream_home_pass(hnswgpu_index *idx, const IvfSearchPlan &p, const StreamScratch &sc, const float *d_Q, hipStream_t st) {
+    HomeArgs ho;
+    memset(&ho, 0, sizeof(ho));
+    ho.items = sc.home_desc;
+    ho.nitems = sc.home_nit;
+    ho.qorder = sc.qorder;
+    ho.half = idx->d_lhalf;
+    ho.hmeta = idx->d_lhmeta;
+    ho.ld = idx->ld;
+    ho.Q = d_Q;
+    ho.qld = idx->dim;
+    ho.dim = idx->dim;
+    ho.metric = idx->metric;
+    ho.dh = idx->s_dh.as<float2>();
+    ho.hstride = p.home_stride;
+    HG_TRY(launch_home(ho, p.home_bound, idx->nch, st));
+    HomeSelectArgs hs;
+    memset(&hs, 0, sizeof(hs));
+    hs.dh = ho.dh;
+    hs.hstride = p.home_stride;
+    hs.pairs = idx->s_pairs.as<Pair>();
+    hs.nq = p.nq;
+    hs.nprobe = p.nprobe;
+    hs.k = p.k;
+    hs.surv = sc.surv;
+    hs.cap = p.surv_cap;
+    hs.surv_cnt = sc.surv_cnt;
+    hs.first = sc.home_first;
+    hs.tau = sc.tau;
+    if (p.home_select_wave)
+        hipLaunchKernelGGL(ivf_home_select_wave_kernel, dim3((p.nq + kNWave - 1) / kNWave), dim3(kWG), 0, st, hs);
+    else
+        hipLaunchKernelGGL(ivf_home_select_kernel, dim3(p.nq), dim3(kWG), 0, st, hs);
+    HG_HIP(hipGetLastError());
+    return 0;
+}
+
+// the bounds on the int8 rows: what a query's running threshold does not exclude is appended to its survivor list
+static int stream_bounds_pass(hnswgpu_index *idx, const IvfSearchPlan &p, const StreamScratch &sc, hipStream_t st) {
+    StreamArgs b;
+    memset(&b, 0, sizeof(b));
+    int64_t blocks;
+    b.chunk_rows = static_cast<int32_t>(p.chunk_rows);
+    b.nchunks = p.nchunks;
+    if (p.grouped) {
+        b.wi_desc = sc.desc;
+        b.nitems = sc.nitems;
+        b.bk_mem = sc.bk_mem;
+        b.bk_cap = p.bk_cap;
+        blocks = (p.wbound + 7) & ~7LL;
+    } else {  // a handful of queries: every (query, list) pair is its own item
+        b.pairs = idx->s_pairs.as<Pair>();
+        b.npairs = static_cast<int32_t>(p.npairs);
+        blocks = p.npairs * b.nchunks;
+    }
+    b.metric = idx->metric;
+    b.k = p.k;
+    b.ctile = idx->d_lctile;
+    b.cmeta = idx->d_lcmeta;
+    b.qcodes = sc.qcodes;
+    b.qscal = sc.qscal;
+    b.tau = sc.tau;
+    b.surv_cnt = sc.surv_cnt;
+    b.surv = sc.surv;
+    b.cap = p.surv_cap;
+#ifdef HG_DIAG
+    b.dbg = g_stream_dbg;  // ablation timing only (results are wrong on purpose): hnswgpu_debug_set_ablation
+#else
+    b.dbg = 0;
+#endif
+    b.stamps = g_tile_dbg_buf;  // null outside diagnostic sessions
+    b.defer = p.mid ? 1 : 0;
+    if (p.home) {  // (nothing is appended for a (query, home list) pair)
+        b.home_pairs = idx->s_pairs.as<Pair>();
+        b.home_nprobe = p.nprobe;
+    }
+    hipEvent_t e0;
+    prof_begin(idx, PROF_IVF_SCAN, st, &e0);
+    // which epilogue: few queries per probed list -> lane = row (a list probed by more takes several passes); many -> lane = query
+    HG_TRY(launch_stream_bounds(b, blocks, idx->nch, p.narrow, st, p.qblocks));
+    prof_end(idx, PROF_IVF_SCAN, st, e0);
+    return 0;
+}
+
+// Large batches: a query's survivors are, above all, its nearest list -- and several queries share one.  The queries are
+// taken in the order of their nearest list, a contiguous eighth of that order per XCD, so that the queries which read
+// the same rows run side by side on ONE L2 (each XCD otherwise fetches the list for itself).
+// (ungrouped launches: the grouped ones get the order from their work-list launch)
+static int stream_query_order(hnswgpu_index *idx, const IvfSearchPlan &p, StreamScratch &sc, const int32_t *d_probes, hipStream_t st) {
+    HG_TRY(idx->s_stats.ensure(sizeof(int32_t) * static_cast<size_t>(p.nq)));  // (s_ids / s_outd may be the caller's outputs)
+    size_t olds;
+    HG_TRY(order_lds(false, idx->nlist, &olds));
+    hipLaunchKernelGGL(pair_order_kernel, dim3(1), dim3(1024), olds, st, d_probes, p.nq, idx->nlist, idx->s_stats.as<int32_t>(), p.nprobe);
+    HG_HIP(hipGetLastError());
+    sc.qorder = idx->s_stats.as<int32_t>();
+    return 0;
+}
+
+// the queries one workgroup cannot serve (the plan's `heavy`), listed for the extra workgroups of the two passes behind
+static int stream_heavy_list(hnswgpu_index *idx, const IvfSearchPlan &p, StreamScratch &sc, hipStream_t st) {
+    HG_TRY(idx->s_heavy.ensure(sizeof(int32_t) * (2 * static_cast<size_t>(p.nq) + 4)));
+    HeavyArgs ha;
+    memset(&ha, 0, sizeof(ha));
+    ha.surv_cnt = sc.surv_cnt;
+    ha.nq = p.nq;
+    ha.cap = static_cast<uint32_t>(p.surv_cap);
+    ha.times_mean = p.heavy_times_mean;
+    ha.thr = p.heavy_thr;
+    ha.cnt = idx->s_heavy.as<uint32_t>();
+    ha.list = idx->s_heavy.as<int32_t>() + 4;
+    if (p.home) {  // ... and the queries the bounds pass appended more than a few candidates to
+        ha.first = sc.home_first;
+        ha.few = static_cast<uint32_t>(std::max<int64_t>(0, p.home_strays));
+        ha.todo_cnt = idx->s_heavy.as<uint32_t>() + 1;
+        ha.todo = ha.list + p.nq;
+    }
+    HG_TRY(launch_heavy(ha, st));
+    sc.heavy_cnt = ha.cnt;
+    sc.heavy_list = ha.list;
+    return 0;
+}
+
+// the survivors against their half-precision rows (stream_kernels.hpp, step 1b)
+static int stream_mid_pass(hnswgpu_index *idx, const IvfSearchPlan &p, const StreamScratch &sc, const float *d_Q, hipStream_t st) {
+    MidArgs ma;
+    memset(&ma, 0, sizeof(ma));
+    ma.surv = sc.surv;
+    ma.surv_cnt = sc.surv_cnt;
+    ma.cap = p.surv_cap;
+    ma.nq = p.nq;
+    ma.slices = p.mid_slices;
+    ma.qorder = ma.slices == 1 ? sc.qorder : nullptr;
+    ma.tau = sc.tau;
+    ma.k = p.k;
+    ma.compact = p.mid_compact;
+    ma.half = idx->d_lhalf;
+    ma.hmeta = idx->d_lhmeta;
+    ma.ld = idx->ld;
+    ma.Q = d_Q;
+    ma.qld = idx->dim;
+    ma.dim = idx->dim;
+    ma.metric = idx->metric;
+    if (p.heavy) {
+        ma.heavy_cnt = sc.heavy_cnt;
+        ma.heavy_list = sc.heavy_list;
+        ma.heavy_slices = kHeavySlices;
+        ma.main_blocks = static_cast<int32_t>(ma.qorder ? (static_cast<int64_t>(p.nq) + 7) / 8 * 8 : static_cast<int64_t>(p.nq) * ma.slices);
+    }
+    ma.first = sc.home_first;  // (home-list batches: half rows only for what the bounds pass appended)
+    if (p.home && p.heavy) {
+        ma.todo_cnt = sc.heavy_cnt + 1;
+        ma.todo = sc.heavy_list + p.nq;
+        ma.todo_slices = 8;
+    }
+    ma.first_few = static_cast<int32_t>(p.home_strays);
+    return launch_mid(ma, idx->nch, st);
+}
+
+// f32 distances of the survivors in the GEMV order, top-k, ids and distances
+static int stream_finish(hnswgpu_index *idx, const IvfSearchPlan &p, const StreamScratch &sc, const float *d_Q, const int32_t *d_qcnt,
+                         int32_t *d_out_ids, float *d_out_dist, uint32_t *d_out_gord, hipStream_t st) {
+    FinishArgs f;
+    memset(&f, 0, sizeof(f));
+    f.prepass = p.mid ? 1 : 0;  // (lists of more than 128 entries only: what a compacting pass has left is evaluated in one step)
+    f.adapt = p.finish_adapt;
+    f.bisect_min = p.finish_bisect;
+    f.dbg = g_tile_dbg_buf;
+    f.surv = sc.surv;
+    f.surv_cnt = sc.surv_cnt;
+    f.tau = sc.tau;
+    f.cap = p.surv_cap;
+    f.q_cnt = d_qcnt;
+    f.pairs = idx->s_pairs.as<Pair>();
+    f.nq = p.nq;
+    f.nprobe = p.nprobe;
+    f.k = p.k;
+    f.slices = p.finish_slices;
+    f.span = p.finish_span;
+    f.rows = idx->d_lrows;
+    f.row_norms = idx->d_lnorms;
+    f.ld = idx->ld;
+    f.Q = d_Q;
+    f.qld = idx->dim;
+    f.dim = idx->dim;
+    f.metric = idx->metric;
+    f.direct = p.finish_direct;
+    f.pstride = p.finish_pstride;
+    if (p.heavy) {
+        f.heavy_cnt = sc.heavy_cnt;
+        f.heavy_list = sc.heavy_list;
+        f.heavy_slices = kHeavySlices;
+    }
+    f.partial = idx->s_partial.as<uint64_t>();
+    f.done = idx->s_done.as<uint32_t>();
+    f.listids = idx->d_listids;
+    f.out_ids = d_out_ids;
+    f.out_dist = d_out_dist;
+    f.out_gord = d_out_gord;
+    f.stats = (idx->prof || idx->ivf_calibrating) ? idx->d_rej_stats : nullptr;
+    if (p.flag_in_finish) {
+        f.host_flag = idx->zc_flag;
+        f.flag_val = idx->zc_val;
+        f.done_q = idx->s_done.as<uint32_t>() + 2 * idx->s_done_n + 2;
+        idx->zc_taken = true;
+    }
+    f.qorder = f.slices == 1 ? sc.qorder : nullptr;
+    f.main_blocks = static_cast<int32_t>(f.qorder ? (static_cast<int64_t>(p.nq) + 7) / 8 * 8 : static_cast<int64_t>(p.nq) * f.slices);
+    return launch_finish(f, idx->nch, st);
+}
+
+static int ivf_stream_scan(hnswgpu_index *idx, const IvfSearchPlan &p, StreamScratch &sc, const float *d_Q, const int32_t *d_qcnt,
+                           const int32_t *d_probes, int32_t *d_out_ids, float *d_out_dist, uint32_t *d_out_gord, hipStream_t st) {
+    if (p.home) {
+        HG_TRY(idx->s_home.ensure(sizeof(HomeDesc) * static_cast<size_t>(p.home_bound) + 64 + sizeof(uint32_t) * static_cast<size_t>(p.nq)));
+        HG_TRY(idx->s_dh.ensure(sizeof(float2) * static_cast<size_t>(p.nq) * p.home_stride));
+        sc.home_desc = idx->s_home.as<HomeDesc>();
+        sc.home_nit = reinterpret_cast<int32_t *>(sc.home_desc + p.home_bound);
+        sc.home_first = reinterpret_cast<uint32_t *>(sc.home_nit + 16);
+    }
+    if (p.grouped) HG_TRY(stream_worklist(idx, p, sc, d_probes, st));
+    // (s_tile held the routing's centroid distances up to here)
+    HG_TRY(idx->s_tile.ensure(sizeof(uint4) * static_cast<size_t>(p.nq) * p.surv_cap));
+    sc.surv = idx->s_tile.as<uint4>();
+    if (p.home) HG_TRY(stream_home_pass(idx, p, sc, d_Q, st));
+    HG_TRY(stream_bounds_pass(idx, p, sc, st));
+    if (p.ordered && !p.grouped) HG_TRY(stream_query_order(idx, p, sc, d_probes, st));
+    HG_TRY(idx->s_partial.ensure(sizeof(uint64_t) * static_cast<size_t>(p.nq) * p.finish_pstride));
+    if (p.heavy) HG_TRY(stream_heavy_list(idx, p, sc, st));
+    HG_TRY(ensure_counters(idx, p.nq, st));
+    if (p.mid) HG_TRY(stream_mid_pass(idx, p, sc, d_Q, st));
+    return stream_finish(idx, p, sc, d_Q, d_qcnt, d_out_ids, d_out_dist, d_out_gord, st);
 }
 
 static int ivf_search_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t nprobe,
@@ -1303,192 +1465,108 @@ static int ivf_calibrate(hnswgpu_index *idx, hipStream_t st) {
     return 0;
 }
 
-static int ivf_search_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t nprobe,
-                              int32_t *d_out_ids, float *d_out_dist, int32_t *d_out_probes, hipStream_t st,
-                              const int32_t *d_given_probes, uint32_t *d_out_gord) {
-    if (!idx->ivf_calibrated && !idx->ivf_calibrating) HG_TRY(ivf_calibrate(idx, st));
-    const int64_t *glistoff = idx->d_glistoff ? idx->d_glistoff : idx->d_listoff;
-    if (nprobe > idx->nlist && !d_given_probes) nprobe = idx->nlist;
-    // 1. centroid routing (:261-269): top-nprobe of the centroid table, stable on the centroid index
-    ScanArgs a;
-    memset(&a, 0, sizeof(a));
-    HG_TRY(idx->s_pairs.ensure(sizeof(Pair) * static_cast<size_t>(nq) * nprobe));
-    const int64_t npairs = static_cast<int64_t>(nq) * nprobe;
-    // tiled (MFMA) list scan once the batch holds more than kTilePairs (query, list) pairs per list: the GEMV scan streams a
-    // list once per pair (pairs of one list side by side on one L2, see ScanArgs::order), the tile scan once per
-    // group of <= 32 pairs but at ~5 TB/s.  Measured on 1M x 768 / 1024 lists / nprobe 32 (tools/ivf_batch_time.py,
-    // GEMV vs tiled, end to end): batch 32: 0.42 vs 0.56 ms; 48: 0.54 vs 0.61; 64: 0.64 vs 0.64; 80: 0.72 vs 0.65;
-    // 96: 0.82 vs 0.71; 128: 1.03 vs 0.71.
-    const int tm = tile_mode();
-    const int code_env = static_cast<int>(tune(HNSWGPU_TUNE_IVF_CODES, 1));  // 0 = never (A/B), N > 0 = from N queries per batch
-    // the survivor stream (stream_kernels.hpp): k up to a tile chunk's rows can get a threshold from one chunk
-    const bool codes_ok = idx->d_lctile != nullptr &&
-                          (idx->rejection_mode == 2 || (idx->rejection_mode == 1 && idx->dim >= 128 && !idx->ivf_stream_off)) &&
-                          code_env > 0 && nq >= code_env && tm != 0 && k <= ivf_stream_max_k(idx);
-    // (Euclidean has one arithmetic at every batch size -- its "tile" path is the register-row group kernel -- so the
-    // bounds pipeline below serves all its batches: batch 1024 at 1M x 768: 4.8 -> 2.8 ms)
-    const int64_t tile_pairs = ivf_tile_pairs(idx, k);
-    const bool use_tile = tile_path_ok(idx) && tm != 0 && (tm == 1 || npairs > tile_pairs * idx->nlist) &&
-                          !(idx->metric == METRIC_L2 && codes_ok && tm != 1);
-    // Between the fused small-batch path and the tile scan: bounds on the int8 list rows first, f32 distances -- the
-    // GEMV order, so the bits of this regime are unchanged -- only for the candidates that can still be among the k
-    // nearest (code_kernels.hpp).  Without the int8 rows (hnswgpu_set_rejection_test mode 0) the same bits come from
-    // the f32 scans below: one GEMV per pair, or the register-row group kernel from 1.5 pairs per list.
-    const bool use_code = !use_tile && codes_ok;
-    int32_t *probes_buf = d_out_probes;
-    int32_t *qcnt_buf = nullptr;
-    // GEMV scan with enough pairs for lists to be probed twice: run the pairs in list order (see ScanArgs::order).
-    // Below half a pair per list there is next to nothing to share and the sort's ~10 us would be all cost.
-    const int order_mode = static_cast<int>(tune(HNSWGPU_TUNE_SCAN_ORDER, 1));  // 0 = never (A/B)
-    // A handful of queries: the launches around the list scan (select, probe table, merge, decode, copy) cost as much as
-    // the scan, so their work is folded into the routing and scan kernels' last workgroups (two launches instead of
-    // seven; 1M x 768, one query: 99 -> 88 us per call, 78 -> 74 us back to back).  Larger batches keep the separate
-    // launches: their merge runs one workgroup per query in parallel, and a tail would only lengthen the scan kernel.
-    const int fused_env = static_cast<int>(tune(HNSWGPU_TUNE_IVF_FUSED, 1));  // 0 = never, 1 = small batches (default), 2 = every GEMV-path batch
-    const bool fused_mode = !use_code && (fused_env == 2 || (fused_env == 1 && nq <= 8));
-    // Without int8 rows, from 1.5 pairs per list up to that boundary: the register-row group kernel (l2_kernels.hpp) fetches a list once for
-    // all the queries probing it and keeps the GEMV summation order, so the results stay bit-identical to the GEMV
-    // scan's (the contract up to kTilePairs pairs per list) while the second and third readers of a list cost no traffic.
-    // Same index, GEMV vs group, list-scan kernel / end to end: batch 32: 0.356 / 0.423 vs 0.331 / 0.423 ms;
-    // 48: 0.464 / 0.531 vs 0.431 / 0.527; 64: 0.572 / 0.643 vs 0.488 / 0.589 (about 885 distinct lists x 3 MB at
-    // ~5.5 TB/s).  The three extra launches (histogram, plan, scatter) cost what the kernel gains below 1.5 pairs per list.
-    const int group_env = static_cast<int>(tune(HNSWGPU_TUNE_IVF_GROUP, 1));  // 0 = never (A/B), 2 = from half a pair per list
-    const bool use_group = !use_tile && !use_code && !fused_mode && group_env && tm != 0 && idx->dim <= kL2MaxDim &&
-                           (group_env == 2 ? npairs * 2 >= idx->nlist : npairs * 2 >= 3LL * idx->nlist);
-    const bool use_order = !use_tile && !use_group && !use_code && order_mode && idx->nlist <= kOrderMaxLists &&
-                           npairs * 2 >= idx->nlist && npairs <= (1 << 22);
-    int32_t *order_buf = nullptr;
-    if (use_tile || use_group || use_code || use_order) {
-        HG_TRY(idx->s_grp.ensure(sizeof(int32_t) * (2 * npairs + nq + 16)));
-        if (!probes_buf) probes_buf = idx->s_grp.as<int32_t>();
-        qcnt_buf = use_tile || use_group || use_code ? idx->s_grp.as<int32_t>() + npairs : nullptr;
-        order_buf = idx->s_grp.as<int32_t>() + npairs + nq + 16;
-    }
-    if (use_tile || use_group) HG_TRY(pad_queries(idx, d_Q, idx->dim, nq, st));
-    // survivor stream: query codes, thresholds and survivor counters live in s_qp / s_qn (sized here: the routing below may
-    // still use both for padded queries and norms, and must not move s_qn afterwards)
-    StreamScratch sc;
-    memset(&sc, 0, sizeof(sc));
-    sc.tn.read();
-    const int stream_route_max = static_cast<int>(tune(HNSWGPU_TUNE_STREAM_ROUTE, 12));  // largest batch routed by the one-launch routing kernel
-    const int stream_group_min = static_cast<int>(tune(HNSWGPU_TUNE_STREAM_GROUP, 5));    // queries from which the bounds pass groups the pairs by list
-    if (use_code) {
-        HG_TRY(stream_scratch(idx, nq, sc));
-        if (nq >= stream_group_min) HG_TRY(stream_buckets(idx, nq, nprobe, sc, st));  // (zeroes the per-list counters)
-    }
-    bool codes_done = false;
-    // the home-list pass of large batches (ivf_home_mode): the routing's tail leaves the thresholds to it
-    const bool home_mode = use_code && sc.bk_cnt != nullptr && probes_buf != nullptr && ivf_home_mode(idx, nq, nprobe, true, sc.tn);
-    // small grouped batches: the bounds pass's work list by extra workgroups of the routing tail's launch (larger ones order
-    // their queries in a second workgroup of ivf_worklist_kernel: they keep that launch)
-    WorklistArgs wl;
-    memset(&wl, 0, sizeof(wl));
-    const bool fold_wl = use_code && sc.bk_cnt != nullptr && !d_given_probes && !ivf_ordered_mode(idx, nq, true, sc.tn) &&
-                         tune(HNSWGPU_TUNE_WORKLIST_FOLD, 1) != 0 && static_cast<int64_t>(nq) * idx->nlist <= (64LL << 20);
-    if (fold_wl) {
-        const WorkPlan plan = stream_work_plan(idx, nq, nprobe, true, sc.tn);
-        HG_REQUIRE(plan.wbound < 2147483647LL, HNSWGPU_ELIMIT, "bounds pass work list too large");
-        HG_TRY(idx->s_misc2.ensure(sizeof(WorkDesc) * static_cast<size_t>(plan.wbound) + 64));
-        HG_TRY(ensure_counters(idx, nq, st));
-        wl.bk_cnt = sc.bk_cnt;
-        wl.bk_cap = sc.bk_cap;
-        wl.nlist = idx->nlist;
-        wl.list_off = idx->d_listoff;
-        wl.chunk_rows = plan.chunk_rows;
-        wl.max_chunks = plan.nchunks;
-        wl.tq = kTileQ * plan.qblocks;
-        wl.desc = idx->s_misc2.as<WorkDesc>();
-        wl.nitems = reinterpret_cast<int32_t *>(wl.desc + plan.wbound);
-        wl.surv_cnt = sc.surv_cnt;
-        wl.nq = nq;
-    }
-    // queries from which a GEMV-order batch routes through the group kernel
-    // (Euclidean 1M x 768: 512 queries 0.85 vs 0.87 ms (GEMV vs group), 1024: 1.50 vs 1.43, 4096: 5.08 vs 4.70)
-    const int route_group_min = static_cast<int>(tune(HNSWGPU_TUNE_ROUTE_GROUP, 1024));
-    if (d_given_probes) {  // caller-chosen lists (the :turbo mode's random partitions, :271-272); -1 = none
-        hipLaunchKernelGGL(probe_pairs_kernel, dim3((nq + kNWave - 1) / kNWave), dim3(kWG), 0, st,
-                           reinterpret_cast<const uint32_t *>(d_given_probes), nq, nprobe, idx->d_listoff, glistoff,
-                           idx->s_pairs.as<Pair>(), probes_buf, qcnt_buf, sc.bk_cnt, sc.bk_mem, sc.bk_cap, sc.surv_cnt);
-        HG_HIP(hipGetLastError());
-    } else {
-    a.rows = idx->d_cent;
-    a.row_norms = idx->d_cnorms;
-    a.ld = idx->ld;
-    a.nrows_all = idx->nlist;
-    a.Q = d_Q;
-    a.qld = idx->dim;
-    a.dim = idx->dim;
-    a.metric = idx->metric;
-    a.k = nprobe;
-    a.role = ROLE_ROUTE;
-    if (!use_tile && (fused_mode || (use_code && nq <= stream_route_max)) && static_cast<int64_t>(nq) * idx->nlist <= (64LL << 20)) {
-        // small batches: distances to the centroids, the choice of the nprobe nearest and the probe table in ONE launch
-        // (for the survivor stream also the query codes, tau = none and the empty survivor lists)
-        RouteStream rs = {sc.qcodes, sc.qscal, sc.tau, sc.surv_cnt, k, sc.bk_cnt, sc.bk_mem, sc.bk_cap, home_mode ? 1 : 0, fold_wl ? &wl : nullptr};
-        HG_TRY(launch_ivf_route(idx, d_Q, nq, nprobe, idx->s_pairs.as<Pair>(), probes_buf, qcnt_buf, st, use_code ? &rs : nullptr));
-        codes_done = use_code;
-        sc.wl_folded = use_code && fold_wl;
-    } else if (use_code && static_cast<int64_t>(nq) * idx->nlist <= (64LL << 20)) {
-        // survivor stream, larger batches: the centroid distances by a pass that serves a group of queries per fetch of a
-        // centroid row (the GEMV order, same bits), then ONE launch for everything else of the routing -- select, probe
-        // table, pairs filed by list, query codes, first thresholds
-        RouteStream rs = {sc.qcodes, sc.qscal, sc.tau, sc.surv_cnt, k, sc.bk_cnt, sc.bk_mem, sc.bk_cap, home_mode ? 1 : 0, fold_wl ? &wl : nullptr};
-        HG_TRY(launch_ivf_route(idx, d_Q, nq, nprobe, idx->s_pairs.as<Pair>(), probes_buf, qcnt_buf, st, &rs, true));
-        codes_done = true;
-        sc.wl_folded = fold_wl;
-    } else {
-    if (use_tile)  // every query against the centroid table on the tile kernel as well
-        HG_TRY(tile_topk_all(idx, idx->s_qp.as<float>(), idx->s_qn.as<float>(), nq, idx->d_cent, idx->d_cnorms, idx->nlist,
-                             nprobe, st, -1));
-    else if (nq >= route_group_min && idx->dim <= kL2MaxDim && tm != 0) {
-        // a large batch in the GEMV order (Euclidean): the centroid table once per group of 32 queries (register-row group
-        // kernel) instead of once per query, the same bits
-        if (!use_group) HG_TRY(pad_queries(idx, d_Q, idx->dim, nq, st));
-        HG_TRY(tile_topk_all(idx, idx->s_qp.as<float>(), idx->s_qn.as<float>(), nq, idx->d_cent, idx->d_cnorms, idx->nlist,
-                             nprobe, st, -1, true));
-    } else if (static_cast<int64_t>(nq) * idx->nlist <= (64LL << 20))  // dense [nq][nlist] distances + select
-        HG_TRY(scan_dense_topk(idx, a, nq, idx->nlist, st));
-    else
-        HG_TRY(scan_topk(idx, a, nq, 1, idx->nlist, st, -1));
-    hipLaunchKernelGGL(probe_pairs_kernel, dim3((nq + kNWave - 1) / kNWave), dim3(kWG), 0, st, idx->s_ord.as<uint32_t>(), nq,
-                       nprobe, idx->d_listoff, glistoff, idx->s_pairs.as<Pair>(), probes_buf, qcnt_buf, sc.bk_cnt, sc.bk_mem, sc.bk_cap,
-                       sc.surv_cnt);
-    HG_HIP(hipGetLastError());
-    }
-    }
-    if (use_code) {
-        // bounds on the int8 list rows with a running threshold, f32 distances -- the GEMV order, so the bits of this regime
-        // are unchanged -- only for the survivors; the finish kernel writes ids and distances
-        if (!codes_done) {  // what the fused routing kernel does in its tail: codes, empty survivor lists, first thresholds
-            HG_TRY(stream_scratch(idx, nq, sc));  // (s_qp may have moved under the padded queries of the routing)
-            PrepArgs pa;
-            memset(&pa, 0, sizeof(pa));
-            pa.Q = d_Q;
-            pa.qld = idx->dim;
-            pa.dim = idx->dim;
-            pa.metric = idx->metric;
-            pa.nq = nq;
-            pa.nprobe = nprobe;
-            pa.k = k;
-            pa.seed_rows = stream_seed_rows(nq, idx->ivf_n_global > 0 ? idx->ivf_n_global : idx->n, idx->nlist);
-            pa.home = home_mode ? 1 : 0;
-            pa.pairs = idx->s_pairs.as<Pair>();
-            pa.qcnt = qcnt_buf;
-            pa.rows = idx->d_lrows;
-            pa.row_norms = idx->d_lnorms;
-            pa.ld = idx->ld;
-            if (idx->d_lhalf && tune(HNSWGPU_TUNE_SEED_HALF, 1) != 0) {
-                pa.half = idx->d_lhalf;
-                pa.hmeta = idx->d_lhmeta;
+// 1. centroid routing (:261-269): top-nprobe of the centroid table, stable on the centroid index
+static int ivf_route(hnswgpu_index *idx, const IvfSearchPlan &p, const float *d_Q, const int32_t *d_given_probes, int32_t *probes_buf,
+                     int32_t *qcnt_buf, const StreamScratch &sc, hipStream_t st) {
+    const int32_t nq = p.nq;
+    const uint32_t *chosen = nullptr;
+    switch (p.route) {
+        case IvfRoute::Given: chosen = reinterpret_cast<const uint32_t *>(d_given_probes); break;
+        case IvfRoute::OneLaunch:
+        case IvfRoute::DistTail: {
+            WorklistArgs wl;
+            memset(&wl, 0, sizeof(wl));
+            if (p.folded) {
+                HG_TRY(idx->s_misc2.ensure(sizeof(WorkDesc) * static_cast<size_t>(p.wbound) + 64));
+                HG_TRY(ensure_counters(idx, nq, st));
+                wl.bk_cnt = sc.bk_cnt;
+                wl.bk_cap = p.bk_cap;
+                wl.nlist = idx->nlist;
+                wl.list_off = idx->d_listoff;
+                wl.chunk_rows = p.chunk_rows;
+                wl.max_chunks = p.nchunks;
+                wl.tq = kTileQ * p.qblocks;
+                wl.desc = idx->s_misc2.as<WorkDesc>();
+                wl.nitems = reinterpret_cast<int32_t *>(wl.desc + p.wbound);
+                wl.surv_cnt = sc.surv_cnt;
+                wl.nq = nq;
             }
-            pa.qcodes = sc.qcodes;
-            pa.qscal = sc.qscal;
-            pa.tau = sc.tau;
-            HG_TRY(launch_query_prep(pa, idx->nch, st));
+            const RouteStream rs = {sc.qcodes, sc.qscal, sc.tau, sc.surv_cnt, sc.bk_cnt, sc.bk_mem, p.folded ? &wl : nullptr};
+            return launch_ivf_route(idx, p, d_Q, idx->s_pairs.as<Pair>(), probes_buf, qcnt_buf, st, p.scan == IvfScan::Stream ? &rs : nullptr);
         }
-        return ivf_stream_scan(idx, d_Q, nq, k, nprobe, qcnt_buf, probes_buf, d_out_ids, d_out_dist, d_out_gord, sc, st);
+        case IvfRoute::TileTopk:
+            HG_TRY(tile_topk_all(idx, idx->s_qp.as<float>(), idx->s_qn.as<float>(), nq, idx->d_cent, idx->d_cnorms, idx->nlist,
+                                 p.nprobe, st, -1));
+            break;
+        case IvfRoute::GroupTopk:
+            if (p.scan != IvfScan::Group) HG_TRY(pad_queries(idx, d_Q, idx->dim, nq, st));
+            HG_TRY(tile_topk_all(idx, idx->s_qp.as<float>(), idx->s_qn.as<float>(), nq, idx->d_cent, idx->d_cnorms, idx->nlist,
+                                 p.nprobe, st, -1, true));
+            break;
+        case IvfRoute::Dense:
+        case IvfRoute::Scan: {
+            ScanArgs a;
+            memset(&a, 0, sizeof(a));
+            a.rows = idx->d_cent;
+            a.row_norms = idx->d_cnorms;
+            a.ld = idx->ld;
+            a.nrows_all = idx->nlist;
+            a.Q = d_Q;
+            a.qld = idx->dim;
+            a.dim = idx->dim;
+            a.metric = idx->metric;
+            a.k = p.nprobe;
+            a.role = ROLE_ROUTE;
+            if (p.route == IvfRoute::Dense) HG_TRY(scan_dense_topk(idx, a, nq, idx->nlist, st));
+            else HG_TRY(scan_topk(idx, a, nq, 1, idx->nlist, st, -1));
+            break;
+        }
     }
-    // 2. scan the probed lists (:217-234) and merge (:291-294)
+    // the probe table from the chosen lists: pairs, probes, per-query counts, and for the stream the pairs filed by list
+    if (!chosen) chosen = idx->s_ord.as<uint32_t>();  // (the top-k passes above have sized it)
+    hipLaunchKernelGGL(probe_pairs_kernel, dim3((nq + kNWave - 1) / kNWave), dim3(kWG), 0, st, chosen, nq, p.nprobe, idx->d_listoff,
+                       idx->d_glistoff ? idx->d_glistoff : idx->d_listoff, idx->s_pairs.as<Pair>(), probes_buf, qcnt_buf, sc.bk_cnt,
+                       sc.bk_mem, p.bk_cap, sc.surv_cnt);
+    HG_HIP(hipGetLastError());
+    return 0;
+}
+
+// what the fused routing kernels do in their tail, for a stream search that was routed otherwise: codes, empty survivor lists, first thresholds
+static int stream_query_prep(hnswgpu_index *idx, const IvfSearchPlan &p, StreamScratch &sc, const float *d_Q, const int32_t *d_qcnt,
+                             hipStream_t st) {
+    HG_TRY(stream_scratch(idx, p.nq, sc));  // (s_qp may have moved under the padded queries of the routing)
+    PrepArgs pa;
+    memset(&pa, 0, sizeof(pa));
+    pa.Q = d_Q;
+    pa.qld = idx->dim;
+    pa.dim = idx->dim;
+    pa.metric = idx->metric;
+    pa.nq = p.nq;
+    pa.nprobe = p.nprobe;
+    pa.k = p.k;
+    pa.seed_rows = p.seed_rows;
+    pa.home = p.home ? 1 : 0;
+    pa.pairs = idx->s_pairs.as<Pair>();
+    pa.qcnt = d_qcnt;
+    pa.rows = idx->d_lrows;
+    pa.row_norms = idx->d_lnorms;
+    pa.ld = idx->ld;
+    if (p.seed_half) {
+        pa.half = idx->d_lhalf;
+        pa.hmeta = idx->d_lhmeta;
+    }
+    pa.qcodes = sc.qcodes;
+    pa.qscal = sc.qscal;
+    pa.tau = sc.tau;
+    return launch_query_prep(pa, idx->nch, st);
+}
+
+// 2. scan the probed lists (:217-234) and merge (:291-294): one GEMV per pair.  Fused: ids and distances are written by the
+// scan's tail; otherwise the winners' order keys are left in s_ord / s_dist for ivf_decode.
+static int ivf_gemv_scan(hnswgpu_index *idx, const IvfSearchPlan &p, const float *d_Q, const int32_t *d_probes, int32_t *order_buf,
+                         int32_t *d_out_ids, float *d_out_dist, uint32_t *d_out_gord, hipStream_t st) {
+    const int32_t nq = p.nq, k = p.k, nprobe = p.nprobe;
+    ScanArgs a;
     memset(&a, 0, sizeof(a));
     a.rows = idx->d_lrows;
     a.row_norms = idx->d_lnorms;
@@ -1500,46 +1578,76 @@ static int ivf_search_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, 
     a.pairs = idx->s_pairs.as<Pair>();
     a.k = k;
     a.role = ROLE_LIST_SCAN;
-    if (use_tile || use_group) {
-        HG_TRY(ivf_tile_scan(idx, d_Q, nq, k, nprobe, probes_buf, qcnt_buf, st, use_group));
-    } else {
-        if (use_order) {
-            const size_t olds = sizeof(int32_t) * (idx->nlist + 1 + 1024);
-            if (olds > 48 * 1024) {  // once per device, for the largest histogram the kernel supports
-                static bool attr_done[64] = {};
-                if (attr_needed(attr_done))
-                    HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pair_order_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               static_cast<int>(sizeof(int32_t) * (kOrderMaxLists + 1 + 1024))));
-            }
-            hipLaunchKernelGGL(pair_order_kernel, dim3(1), dim3(1024), olds, st, probes_buf, static_cast<int>(npairs),
-                               idx->nlist, order_buf);
-            HG_HIP(hipGetLastError());
-            a.order = order_buf;
-            // all the pairs of a list in one run (one XCD) while a run stays a small part of an XCD's share
-            a.run = 8;
-            while (a.run < 64 && static_cast<int64_t>(a.run) * idx->nlist < npairs) a.run *= 2;
-        }
-        if (fused_mode) {
-            // the scan's last workgroup per query merges the partial lists, maps the winners to row ids and writes the
-            // results: no merge, decode or copy launch behind the scan
-            a.listids = idx->d_listids;
-            a.out_ids = d_out_ids;
-            a.out_dist = d_out_dist;
-            a.out_gord = d_out_gord;
-            return scan_fused(idx, a, nq, nprobe, idx->max_list_len, ivf_mean_len(idx), st,
-                              PROF_IVF_SCAN);
-        }
-        HG_TRY(scan_topk(idx, a, nq, nprobe, idx->max_list_len, st, PROF_IVF_SCAN,
-                         ivf_mean_len(idx)));
+    if (p.list_order) {
+        size_t olds;
+        HG_TRY(order_lds(false, idx->nlist, &olds));
+        hipLaunchKernelGGL(pair_order_kernel, dim3(1), dim3(1024), olds, st, d_probes, static_cast<int>(p.npairs), idx->nlist, order_buf);
+        HG_HIP(hipGetLastError());
+        a.order = order_buf;
+        a.run = p.order_run;
     }
-    int64_t cnt = static_cast<int64_t>(nq) * k;
+    if (p.scan == IvfScan::Fused) {
+        // the scan's last workgroup per query merges the partial lists, maps the winners to row ids and writes the
+        // results: no merge, decode or copy launch behind the scan
+        a.listids = idx->d_listids;
+        a.out_ids = d_out_ids;
+        a.out_dist = d_out_dist;
+        a.out_gord = d_out_gord;
+        return scan_fused(idx, a, nq, nprobe, idx->max_list_len, ivf_mean_len(idx), st,
+                          PROF_IVF_SCAN);
+    }
+    return scan_topk(idx, a, p.nq, p.nprobe, idx->max_list_len, st, PROF_IVF_SCAN, ivf_mean_len(idx));
+}
+
+// the winners' order keys (s_ord) to row ids, the distances (s_dist) to the caller's array
+static int ivf_decode(hnswgpu_index *idx, const IvfSearchPlan &p, int32_t *d_out_ids, float *d_out_dist, uint32_t *d_out_gord, hipStream_t st) {
+    const int64_t cnt = static_cast<int64_t>(p.nq) * p.k;
     hipLaunchKernelGGL(ivf_decode_kernel, dim3(static_cast<unsigned>((cnt + 255) / 256)), dim3(256), 0, st,
-                       idx->s_ord.as<uint32_t>(), nq, k, idx->s_pairs.as<Pair>(), nprobe, idx->d_listids, d_out_ids,
+                       idx->s_ord.as<uint32_t>(), p.nq, p.k, idx->s_pairs.as<Pair>(), p.nprobe, idx->d_listids, d_out_ids,
                        d_out_gord);
     HG_HIP(hipGetLastError());
     HG_HIP(hipMemcpyAsync(d_out_dist, idx->s_dist.p, sizeof(float) * cnt, hipMemcpyDeviceToDevice, st));
     return 0;
+}
+
+// One search: calibrate if needed, plan, size the scratch the plan names, route, scan.
+static int ivf_search_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t nprobe,
+                              int32_t *d_out_ids, float *d_out_dist, int32_t *d_out_probes, hipStream_t st,
+                              const int32_t *d_given_probes, uint32_t *d_out_gord) {
+    if (!idx->ivf_calibrated && !idx->ivf_calibrating) HG_TRY(ivf_calibrate(idx, st));
+    IvfSearchPlan p;
+    HG_TRY(ivf_search_plan(idx, nq, k, nprobe, d_given_probes != nullptr, p));
+    const bool stream = p.scan == IvfScan::Stream, grouped_rows = p.scan == IvfScan::Tile || p.scan == IvfScan::Group;
+    HG_TRY(idx->s_pairs.ensure(sizeof(Pair) * static_cast<size_t>(p.npairs)));
+    int32_t *probes_buf = d_out_probes, *qcnt_buf = nullptr, *order_buf = nullptr;
+    if (grouped_rows || stream || p.list_order) {
+        HG_TRY(idx->s_grp.ensure(sizeof(int32_t) * (2 * p.npairs + nq + 16)));
+        if (!probes_buf) probes_buf = idx->s_grp.as<int32_t>();
+        qcnt_buf = grouped_rows || stream ? idx->s_grp.as<int32_t>() + p.npairs : nullptr;
+        order_buf = idx->s_grp.as<int32_t>() + p.npairs + nq + 16;
+    }
+    if (grouped_rows) HG_TRY(pad_queries(idx, d_Q, idx->dim, nq, st));
+    // survivor stream: query codes, thresholds and survivor counters live in s_qp / s_qn (sized here: the routing below may
+    // still use both for padded queries and norms, and must not move s_qn afterwards)
+    StreamScratch sc;
+    memset(&sc, 0, sizeof(sc));
+    if (stream) {
+        HG_TRY(stream_scratch(idx, nq, sc));
+        if (p.grouped) HG_TRY(stream_buckets(idx, p, sc, st));  // (zeroes the per-list counters)
+    }
+    HG_TRY(ivf_route(idx, p, d_Q, d_given_probes, probes_buf, qcnt_buf, sc, st));
+    switch (p.scan) {
+        case IvfScan::Stream:
+            // bounds on the int8 list rows with a running threshold, f32 distances -- the GEMV order, so the bits of this regime
+            // are unchanged -- only for the survivors; the finish kernel writes ids and distances
+            if (p.query_prep) HG_TRY(stream_query_prep(idx, p, sc, d_Q, qcnt_buf, st));
+            return ivf_stream_scan(idx, p, sc, d_Q, qcnt_buf, probes_buf, d_out_ids, d_out_dist, d_out_gord, st);
+        case IvfScan::Tile:
+        case IvfScan::Group: HG_TRY(ivf_tile_scan(idx, p, d_Q, probes_buf, qcnt_buf, st)); break;
+        case IvfScan::Fused: return ivf_gemv_scan(idx, p, d_Q, probes_buf, order_buf, d_out_ids, d_out_dist, d_out_gord, st);
+        case IvfScan::Gemv: HG_TRY(ivf_gemv_scan(idx, p, d_Q, probes_buf, order_buf, d_out_ids, d_out_dist, d_out_gord, st)); break;
+    }
+    return ivf_decode(idx, p, d_out_ids, d_out_dist, d_out_gord, st);
 }
 
 }  // namespace hg
@@ -1954,7 +2062,7 @@ int hnswgpu_ivf_search(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k
         me.out_ids = out_ids;
         me.out_dist = out_dist;
         me.stats = nullptr;
-        // (the handle's one-off measurement of what the int8 bounds separate decides ivf_tile_pairs: it runs here, under
+        // (the handle's one-off measurement of what the int8 bounds separate decides ivf_tile_rule: it runs here, under
         // the index lock, before the predicate is built -- concurrent first calls would otherwise combine by the
         // pre-calibration boundary and run on the post-calibration kernel)
         {
@@ -1966,13 +2074,13 @@ int hnswgpu_ivf_search(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k
                 HG_TRY(end_call(idx, idx->stream));
             }
         }
-        const bool one_arith = idx->metric == METRIC_L2 || !tile_path_ok(idx) || tile_mode() == 0;
-        // the kernel a batch of `total` queries gets: ivf_search_enqueue's own predicate, on the BATCH's nprobe (the
-        // leader that evaluates this may have asked for another one)
-        const int64_t tile_pairs = ivf_tile_pairs(idx, k);  // (requests of one batch share k)
-        auto tiled = [idx, tile_pairs](int64_t total, int32_t nprobe_req) {
-            const int64_t nl = idx->nlist;
-            return total * std::min<int64_t>(nprobe_req, nl) > tile_pairs * nl;
+        // the summation order a batch of `total` queries gets: the predicate ivf_search_plan itself decides by (TileRule), on the
+        // BATCH's nprobe (the leader that evaluates this may have asked for another one); requests of one batch share k.
+        // (This is off the search path: the table is read here, once per call, and the rule is carried into the combiner.)
+        const TileRule rule = ivf_tile_rule(idx, k, tile_mode(), tune(HNSWGPU_TUNE_IVF_CODES, 1), tune(HNSWGPU_TUNE_TILE_PAIRS, 0));
+        const bool one_arith = idx->metric == METRIC_L2 || !rule.possible;
+        auto tiled = [idx, rule](int64_t total, int32_t nprobe_req) {
+            return rule.tiled(idx, total * std::min<int64_t>(nprobe_req, idx->nlist));
         };
         return combine_search(
             idx->cmb_ivf, me,
