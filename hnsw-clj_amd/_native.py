@@ -82,6 +82,7 @@ _SIGS = {
     "hnswgpu_set_profiling": ["p", "i32"],
     "hnswgpu_get_profile": ["p", "i32", "p", "p", "i32"],
     "hnswgpu_rejection_bounds": ["p", "p", "p", "i32", "p"],
+    "hnswgpu_hnsw_rejection_bounds": ["p", "p", "p", "i32", "p"],
     "hnswgpu_distance_bounds": ["p", "p", "p", "i32", "p", "p"],
     "hnswgpu_ivf_half_bounds": ["p", "p", "p", "i32", "p", "p"],
     "hnswgpu_ivf_home_bounds": ["p", "p", "i32", "i64", "i64", "p", "p"],

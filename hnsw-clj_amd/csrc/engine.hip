@@ -2364,14 +2364,11 @@ int hnswgpu_dense_distances(hnswgpu_index *idx, const float *Q, int32_t nq, floa
     return 0;
 }
 
-// Measurement / test entry: the lower bounds the HNSW traversal's rejection test (kernels.hpp: quantize_rows_kernel)
-// computes for query q against rows ids[0..m), by the traversal's own device functions.  NaN = "no bound".
-int hnswgpu_rejection_bounds(hnswgpu_index *idx, const float *q, const int32_t *ids, int32_t m, float *out) {
-    return hnswgpu_distance_bounds(idx, q, ids, m, out, nullptr);
-}
-
-int hnswgpu_distance_bounds(hnswgpu_index *idx, const float *q, const int32_t *ids, int32_t m, float *out,
-                            float *out_ub) {
+// Measurement / test entries: the bounds of query q against rows ids[0..m) from the int8 rows, by the searches' own device
+// functions (kernels.hpp: code_bound_kernel).  q16 = the HNSW traversals' form, the query in the 16-bit code (Query16);
+// else the query in int8 as well, the IVF bounds pass's form.  NaN = "no bound".
+static int code_bounds_call(hnswgpu_index *idx, const float *q, const int32_t *ids, int32_t m, float *out, float *out_ub,
+                            bool q16) {
     HG_REQUIRE(idx && q && ids && out && m >= 1, HNSWGPU_EINVAL, "null argument");
     for (int32_t i = 0; i < m; i++) HG_REQUIRE(ids[i] >= 0 && ids[i] < idx->n, HNSWGPU_EINVAL, "id out of range");
     std::lock_guard<std::mutex> lk(idx->mu);
@@ -2386,17 +2383,34 @@ int hnswgpu_distance_bounds(hnswgpu_index *idx, const float *q, const int32_t *i
     HG_TRY(idx->s_outd.ensure(sizeof(float) * 2 * static_cast<size_t>(m)));
     HG_HIP(hipMemcpyAsync(idx->s_ids.p, ids, sizeof(int32_t) * m, hipMemcpyHostToDevice, st));
     float *d_ub = out_ub ? idx->s_outd.as<float>() + m : nullptr;
-#define CALL(N, R, L)                                                                                                \
-    hipLaunchKernelGGL((code_bound_kernel<N>), dim3((m + 7) / 8), dim3(kWave), 0, st, idx->s_q.as<float>(), idx->dim, \
+#define CALL_QC(N, Q16)                                                                                                  \
+    hipLaunchKernelGGL((code_bound_kernel<N, Q16>), dim3((m + 7) / 8), dim3(kWave), 0, st, idx->s_q.as<float>(), idx->dim, \
                        idx->metric, idx->d_qrows, idx->d_qmeta, idx->s_ids.as<int32_t>(), m, idx->s_outd.as<float>(), d_ub)
+#define CALL(N, R, L)                \
+    if (q16) CALL_QC(N, true);       \
+    else CALL_QC(N, false)
     HG_DISPATCH(idx->nch, false, CALL);
 #undef CALL
+#undef CALL_QC
     HG_HIP(hipGetLastError());
     HG_HIP(hipMemcpyAsync(out, idx->s_outd.p, sizeof(float) * m, hipMemcpyDeviceToHost, st));
     if (out_ub) HG_HIP(hipMemcpyAsync(out_ub, d_ub, sizeof(float) * m, hipMemcpyDeviceToHost, st));
     HG_TRY(end_call(idx, st));
     HG_HIP(hipStreamSynchronize(st));
     return 0;
+}
+
+int hnswgpu_rejection_bounds(hnswgpu_index *idx, const float *q, const int32_t *ids, int32_t m, float *out) {
+    return code_bounds_call(idx, q, ids, m, out, nullptr, false);
+}
+
+int hnswgpu_distance_bounds(hnswgpu_index *idx, const float *q, const int32_t *ids, int32_t m, float *out,
+                            float *out_ub) {
+    return code_bounds_call(idx, q, ids, m, out, out_ub, false);
+}
+
+int hnswgpu_hnsw_rejection_bounds(hnswgpu_index *idx, const float *q, const int32_t *ids, int32_t m, float *out_lb) {
+    return code_bounds_call(idx, q, ids, m, out_lb, nullptr, true);
 }
 
 // Diagnostic / test entry: the half-precision bounds (stream_kernels.hpp, step 1b) of `m` LIST rows -- positions in list

@@ -1223,6 +1223,77 @@ __device__ __forceinline__ int code_dot(const uint32_t (&a)[NCH], const uint32_t
     return acc;
 }
 
+// The HNSW traversals' query code: 16 bits per element instead of 8.  Half of the rejection test's slack
+// W = E_v + E_q (1 + E_v) came from coding the QUERY in int8 (E_q ~ E_v ~ 0.0078 on the bench's rows), yet the query
+// sits in registers and costs no memory traffic at any width: with a = round(q / s_q), |a| <= A (s_q = max|q| / A),
+// E_q falls by A / 127 (0.0078 / 128 = 6e-5 at A = 16255) and the rows that pass the test with a full list from 1,375 to 1,159 per query at the headline's
+// ef 640 (tools/bound_width_study.py).  The code is held as two int8 planes in the row layout, a = 256 h + l with
+// l in [-128, 127] and |h| <= 63, so a . c stays v_dot4_i32_i8 work: two per dword, 256 (h . c) + (l . c) per lane.
+// A is the 15-bit 16255 = 63 * 256 + 127 where the WAVE total fits int32, and smaller beyond: a wave covers 256 NCH
+// elements and |c| <= 127, so |a . c| <= 256 NCH * 127 * A <= 2^31 - 1 with A = min(16255, (2^31 - 1) / (127 * 256 * NCH))
+// (16255 up to dim 1024, 11008 / 8256 / 5504 at NCH 6 / 8 / 12) -- ONE wave_sum8_int, as for the int8 query.  So "16-bit"
+// names the storage: the code has 15.0 bits with its sign up to dim 1024 and 14.4 / 14.0 / 13.4 at dims 1536 / 2048 / 3072,
+// E_q = 0.0078 * 127 / A = 6e-5 ... 1.8e-4, in every case under 3 % of E_v.  A query whose largest component is below
+// 1e-18 gets no code (r_q = NaN: every neighbour takes the exact path): s_q = max|q| / A, its reciprocal and s_q^2 a.a
+// stay clear of the subnormal range and of infinity for every query that is coded.  The IVF bounds kernels feed the int8
+// matrix cores and keep QueryCode / encode_query.
+template <int NCH>
+struct Query16 {
+    static constexpr int kFit = 0x7fffffff / (127 * 256 * NCH);
+    static constexpr int kMax = kFit < 16255 ? kFit : 16255;  // A
+    uint32_t hi[NCH], lo[NCH];
+    QueryScal sc;
+};
+
+template <int NCH>
+__device__ __forceinline__ void encode_query16(const float4 (&q)[NCH], Query16<NCH> &qc) {
+    constexpr float A = static_cast<float>(Query16<NCH>::kMax);
+    bool bad;
+    const float mx = wave_absmax<NCH>(q, bad);
+    bad = bad || (mx > 0.0f && mx < 1.0e-18f);  // (see above: no code for a query this small)
+    const float sc = mx / A, inv = mx > 0.0f ? A / mx : 0.0f;
+    float res = 0.0f;
+    unsigned long long c2 = 0;  // a . a reaches 256 NCH * A^2 > 2^39: 64 bits
+#pragma unroll
+    for (int c = 0; c < NCH; c++) {
+        const float e[4] = {q[c].x, q[c].y, q[c].z, q[c].w};
+        qc.hi[c] = qc.lo[c] = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            float t = __builtin_rintf(e[j] * inv);
+            t = t > A ? A : (t < -A ? -A : t);
+            const int code = bad ? 0 : static_cast<int>(t);
+            const float d = e[j] - sc * static_cast<float>(code);  // against the value the test reconstructs
+            res = __builtin_fmaf(d, d, res);
+            c2 += static_cast<unsigned long long>(code * code);
+            const int l = ((code + 128) & 255) - 128, h = (code - l) >> 8;  // code = 256 h + l exactly
+            qc.lo[c] |= (static_cast<uint32_t>(l) & 0xffu) << (8 * j);
+            qc.hi[c] |= (static_cast<uint32_t>(h) & 0xffu) << (8 * j);
+        }
+    }
+    for (int off = 1; off < kWave; off <<= 1) c2 += __shfl_xor(c2, off, kWave);
+    qc.sc.s = sc;
+    qc.sc.qn = __builtin_sqrtf(wave_sum(lane_partial<NCH, false>(q, q)));
+    qc.sc.rq = bad ? __uint_as_float(0x7fc00000u) : 1.01f * __builtin_sqrtf(wave_sum(res));
+    qc.sc.eq = qc.sc.rq / qc.sc.qn;
+    const float an = sc * __builtin_sqrtf(static_cast<float>(c2));  // |q'| first: s_q^2 alone may be subnormal
+    qc.sc.a2 = an * an;
+    qc.sc.iqn = 1.0f / qc.sc.qn;
+    qc.sc.pad[0] = qc.sc.pad[1] = 0.0f;
+}
+
+// a . c over this lane's elements for the two-plane query code (exact; <= 4 NCH * 127 * A per lane)
+template <int NCH>
+__device__ __forceinline__ int code_dot16(const Query16<NCH> &qc, const uint32_t (&w)[NCH]) {
+    int ah = 0, al = 0;
+#pragma unroll
+    for (int c = 0; c < NCH; c++) {
+        ah = __builtin_amdgcn_sdot4(static_cast<int>(qc.hi[c]), static_cast<int>(w[c]), ah, false);
+        al = __builtin_amdgcn_sdot4(static_cast<int>(qc.lo[c]), static_cast<int>(w[c]), al, false);
+    }
+    return ah * 256 + al;
+}
+
 // Eight per-lane integers -> their eight wave totals, one per group of eight lanes: lane l ends up with the total of
 // x[(l >> 3) & 7].  Halving exchange: v_permlane32_swap / v_permlane16_swap trade the half a lane does not keep for
 // the half it does (4 + 2 swaps), one row_ror:8 DPP add, then three DPP adds inside the group of eight -- 17
@@ -1252,7 +1323,21 @@ __device__ __forceinline__ int wave_sum8_int(const int (&x)[8], int lane) {
 __device__ __forceinline__ int wave_sum8_row(int lane) { return (lane >> 3) & 7; }
 
 // the bounds of d(q, v) from the exact code dot product (see above): lb <= the f32 distance of the exact path <= ub;
-// NaN when nothing can be said
+// NaN when nothing can be said.  One function for both query codes (QueryScal is filled by encode_query or
+// encode_query16; `dot` is a . c with |dot| < 2^31 either way).  What the allowances have to cover, u = 2^-24:
+//   * the exact path's own rounding: < 1.2e-6 |q||v| (above);
+//   * dh: float(dot) rounds by u RELATIVE whatever the magnitude (the int8 query's totals passed 2^24 from dim 1040 on
+//     as well), s_q s_v and the product add u each: |dh - q'.v'| <= 3 u |q'||v'| < 1.9e-7 |q||v|;
+//   * the query's residual r_q is measured against fl(s_q a), the test uses s_q a: off by <= u |q|, under the 1 % only
+//     while r_q > 6e-6 |q| -- a query that its 16-bit code represents (almost) exactly relies on the allowances
+//     (as a constant query did with the int8 code);
+//   cosine: all of it is relative to |q||v|, i.e. absolute in the distance: 1.2e-6 + 1.9e-7 + 6e-8 + the two
+//     reciprocals' 2 u << 1e-4 (E carries it);
+//   dot: (1.2e-6 + 1.9e-7) |q||v| + u |q| |v'| << 2e-5 |q||v| (E carries 2e-5 |v|, times |q| here);
+//   L2: d2 sums three terms of <= a2 + v2 + 2 |dh| <= 2 (a2 + v2): a2 = fl(fl(s_q sqrt(float(a.a)))^2) is 8 u relative, v2 3 u,
+//     2 dh 3 u (a2 + v2), two additions 2 u * 2 (a2 + v2): < 9e-7 (a2 + v2) < dl = 2e-6 (a2 + v2); behind the
+//     square root the exact path's rounding and the residual's u |q| go against 4e-6 (|q| + |v|) in W.
+// None of these terms depends on the width of the query code: the constants are the int8 code's.
 __device__ __forceinline__ void code_bounds(int metric, int dot, const QueryScal &qc, float4 meta, float irn, float &lb, float &ub) {
     const float dh = static_cast<float>(dot) * (qc.s * meta.x);  // q' . v'
     if (metric == METRIC_L2) {
@@ -1279,17 +1364,27 @@ __device__ __forceinline__ float code_lower_bound(int metric, int dot, const Que
     return lb;
 }
 
-// Diagnostic / test entry (hnswgpu_rejection_bounds): the bound of every listed row against one query, by the very
-// functions the traversal uses.  One wave per eight rows.
+// Diagnostic / test entries: the bound of every listed row against one query, by the very functions the searches use.
+// Q16 = false: the query in int8 (hnswgpu_distance_bounds / hnswgpu_rejection_bounds, the IVF bounds pass's form);
+// Q16 = true: the HNSW traversals' form (hnswgpu_hnsw_rejection_bounds).  One wave per eight rows.
 template <int NCH>
+__device__ __forceinline__ void encode_code(const float4 (&q)[NCH], QueryCode<NCH> &qc) { encode_query<NCH>(q, qc); }
+template <int NCH>
+__device__ __forceinline__ void encode_code(const float4 (&q)[NCH], Query16<NCH> &qc) { encode_query16<NCH>(q, qc); }
+template <int NCH>
+__device__ __forceinline__ int code_dot_of(const QueryCode<NCH> &qc, const uint32_t (&w)[NCH]) { return code_dot<NCH>(qc.a, w); }
+template <int NCH>
+__device__ __forceinline__ int code_dot_of(const Query16<NCH> &qc, const uint32_t (&w)[NCH]) { return code_dot16<NCH>(qc, w); }
+
+template <int NCH, bool Q16>
 __global__ __launch_bounds__(kWave) void code_bound_kernel(const float *Q, int dim, int metric, const uint32_t *qrows,
                                                            const float4 *qmeta, const int32_t *ids, int m, float *out,
                                                            float *out_ub) {
     const int lane = threadIdx.x;
     float4 q[NCH];
     load_query<NCH>(q, Q, dim, lane);
-    QueryCode<NCH> qc;
-    encode_query<NCH>(q, qc);
+    typename std::conditional<Q16, Query16<NCH>, QueryCode<NCH>>::type qc;
+    encode_code<NCH>(q, qc);
     const int j0 = blockIdx.x * 8;
     int acc[8];
 #pragma unroll
@@ -1299,7 +1394,7 @@ __global__ __launch_bounds__(kWave) void code_bound_kernel(const float *Q, int d
         const uint32_t *rp = qrows + (static_cast<int64_t>(rid) * kWave + lane) * NCH;
 #pragma unroll
         for (int c = 0; c < NCH; c++) w[c] = rp[c];
-        acc[b] = code_dot<NCH>(qc.a, w);
+        acc[b] = code_dot_of<NCH>(qc, w);
     }
     const int tot = wave_sum8_int(acc, lane);
     const int j = j0 + wave_sum8_row(lane);
@@ -1617,8 +1712,8 @@ __global__ __launch_bounds__(NW * kWave) void hnsw_search_kernel(HnswArgs a) {
         float4 q[NCH];
         load_query<NCH>(q, qptr, a.dim, lane);
         float qn = a.metric == METRIC_COS ? query_norm<NCH>(q) : 0.0f;
-        QueryCode<NCH> qc;  // the query's side of the rejection test
-        if (a.qrows != nullptr) encode_query<NCH>(q, qc);
+        Query16<NCH> qc;  // the query's side of the rejection test
+        if (a.qrows != nullptr) encode_query16<NCH>(q, qc);
         const int qlevel = a.q_levels ? a.q_levels[qi] : -1;
 
         int64_t n_eval = 0, n_hop = 0, n_exact = 0;
@@ -1780,7 +1875,7 @@ __global__ __launch_bounds__(NW * kWave) void hnsw_search_kernel(HnswArgs a) {
                         }
                         int acc[8];
 #pragma unroll
-                        for (int b = 0; b < 8; b++) acc[b] = code_dot<NCH>(qc.a, w[b]);
+                        for (int b = 0; b < 8; b++) acc[b] = code_dot16<NCH>(qc, w[b]);
                         const int tot = wave_sum8_int(acc, lane);
                         const float lb = code_lower_bound(a.metric, tot, qc.sc, mymeta, mymeta.w);
                         const bool need = ok && !(lb >= worst0);  // NaN: needs the exact distance

@@ -5,8 +5,11 @@
 // expansion's admitted neighbours into ONE sorted list by rank and scatter: every list entry is compared with every admitted
 // neighbour, every expansion.  With one wave per query (the shape of every launch that fills the chip) that is the traversal's
 // largest compute phase -- at the headline's ef 640 the merge took 2.9 of the 8.2 us an expansion takes per wave, the same again
-// went into selecting the next candidate from LDS, and the launch runs no faster with the int8 rejection test than without
-// (24 % fewer bytes, same time): it is bound by instructions, not by memory.  The list here is the one solo_kernels.hpp's
+// went into selecting the next candidate from LDS, and the launch ran no faster with the int8 rejection test than without
+// (24 % fewer bytes, same time): THAT kernel is bound by instructions, not by memory.  This one is bound by memory: the
+// headline launch requests 9.8 MB per query, 7.6 TB/s, 28-29 GB/s per CU past L2 -- what a CU's path to memory carries for
+// random ~1 KB rows -- and 4,096 queries already run at the QPS of 10,000, so its time follows the bytes that leave L2
+// (hence the 16-bit query code of the rejection test, kernels.hpp: Query16).  The list here is the one solo_kernels.hpp's
 // sequencer keeps (round 5): `nearest` = main[0, pm) + buffer[0, pb), an admitted neighbour enters the buffer by a ballot and a
 // lane shift (several at once: one pass decides them exactly as the reference's loop would), what leaves `nearest` is a pointer
 // move, the next candidate comes out of two register windows, and every 63 admissions the buffer is merged into the main list
@@ -305,8 +308,8 @@ __global__ __launch_bounds__(kWave) void hnsw_wave_kernel(HnswArgs a) {
         float4 q[NCH];
         load_query<NCH>(q, qptr, a.dim, lane);
         const float qn = a.metric == METRIC_COS ? query_norm<NCH>(q) : 0.0f;
-        QueryCode<NCH> qc;  // the query's side of the rejection test
-        if (a.qrows != nullptr) encode_query<NCH>(q, qc);
+        Query16<NCH> qc;  // the query's side of the rejection test
+        if (a.qrows != nullptr) encode_query16<NCH>(q, qc);
         const int qlevel = a.q_levels ? a.q_levels[qi] : -1;
         int64_t n_eval = 0, n_hop = 0, n_exact = 0;
         int len = 0;
@@ -394,7 +397,7 @@ __global__ __launch_bounds__(kWave) void hnsw_wave_kernel(HnswArgs a) {
                         }
                         int acc[8];
 #pragma unroll
-                        for (int b = 0; b < 8; b++) acc[b] = code_dot<NCH>(qc.a, w[b]);
+                        for (int b = 0; b < 8; b++) acc[b] = code_dot16<NCH>(qc, w[b]);
                         const int tot = wave_sum8_int(acc, lane);
                         const float lb = code_lower_bound(a.metric, tot, qc.sc, mymeta, mymeta.w);
                         const bool need = ok && !(lb >= worst0);  // NaN: needs the exact distance

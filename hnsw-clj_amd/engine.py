@@ -143,8 +143,20 @@ class Index:
         check(lib().hnswgpu_get_rejection_stats(self._h, C.byref(a), C.byref(b), 1 if reset else 0))
         return a.value, b.value
 
+    def hnsw_rejection_bounds(self, q, ids):
+        """Lower bounds of d(q, row) as the HNSW traversals' rejection test computes them: int8 rows against the 16-bit
+        query code (NaN = no bound)."""
+        q = _f32(q).reshape(-1)
+        if len(q) != self.dim:
+            raise ValueError("query has %d elements, index dim is %d" % (len(q), self.dim))
+        ids = np.ascontiguousarray(ids, np.int32)
+        out = np.empty(len(ids), np.float32)
+        check(lib().hnswgpu_hnsw_rejection_bounds(self._h, _p(q), _p(ids), len(ids), _p(out)))
+        return out
+
     def rejection_bounds(self, q, ids):
-        """Lower bounds of d(q, row) from the int8 rows of the HNSW traversal's rejection test (NaN = no bound)."""
+        """Lower bounds of d(q, row) from the int8 rows with the query in int8 as well: the lower side of distance_bounds
+        (NaN = no bound).  The HNSW traversals' own bounds: hnsw_rejection_bounds."""
         q = _f32(q).reshape(-1)
         if len(q) != self.dim:
             raise ValueError("query has %d elements, index dim is %d" % (len(q), self.dim))

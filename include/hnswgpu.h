@@ -283,9 +283,12 @@ int hnswgpu_set_profiling(hnswgpu_index *idx, int32_t on);
 int hnswgpu_launch_count(int32_t which, int64_t *out);
 /* The HNSW traversal decides most neighbours (those that cannot enter a full result list, ultra_fast.clj:195-198) from
  * an int8 copy of the rows: a lower bound of the distance that is already >= the list's worst needs no f32 row
- * (hnsw-clj_amd/csrc/kernels.hpp: quantize_rows_kernel; results and counters are unchanged by construction).  This
- * entry returns those bounds for query q[dim] against rows ids[0..m) -- out[i] <= the distance hnswgpu_batch_distances
- * reports for the same pair, NaN where the test abstains -- so the property can be checked from outside.
+ * (hnsw-clj_amd/csrc/kernels.hpp: quantize_rows_kernel; results and counters are unchanged by construction).  The
+ * traversals code the QUERY in 16 bits (it sits in registers; kernels.hpp: Query16): hnswgpu_hnsw_rejection_bounds, below,
+ * returns THEIR bounds.  This entry returns the bounds of the same rows with the query in int8 as well -- the form the
+ * IVF bounds pass uses, and the lower side of hnswgpu_distance_bounds bit for bit -- for query q[dim] against rows
+ * ids[0..m): out[i] <= the distance hnswgpu_batch_distances reports for the same pair, NaN where the test abstains -- so
+ * the property can be checked from outside.
  * hnswgpu_set_rejection_test: mode 0 = off (no int8 copy is made: saves n * dim bytes; the bounds entry then fails),
  * 1 = launches of at least two queries per CU, where the traversal is bandwidth-bound, and only for dim >= 128 (an int8
  * row of a shorter vector saves no cache line) (default), 2 = every launch, every dim.  The same setting decides whether
@@ -296,6 +299,14 @@ int hnswgpu_launch_count(int32_t which, int64_t *out);
  * (every batch size; k <= 256, fewer on very long lists: see hnswgpu_ivf_search).
  * HNSWGPU_PREFILTER=<mode> in the environment sets the default of new handles.  Results never depend on the mode. */
 int hnswgpu_rejection_bounds(hnswgpu_index *idx, const float *q, const int32_t *ids, int32_t m, float *out);
+/* The bounds the HNSW traversals' own test computes: int8 rows against the 16-bit query code, by the device functions
+ * hnsw_wave_kernel and hnsw_search_kernel call.  out_lb[i] <= the distance hnswgpu_batch_distances reports, NaN where the
+ * test abstains; tighter than hnswgpu_rejection_bounds by the query's share of the slack (about half of it on rows and
+ * queries of similar spread).  "16-bit" is the code's storage, two int8 planes: its range is +-16255 (15 bits with the
+ * sign) up to dim 1024 and +-11008 / 8256 / 5504 at dims up to 1536 / 2048 / 3072, so that the integer dot product of a
+ * whole row fits 32 bits; the query's share of the slack is 1 / 128 ... 1 / 43 of the int8 code's.  A query whose largest
+ * component is below 1e-18 gets no bounds (NaN). */
+int hnswgpu_hnsw_rejection_bounds(hnswgpu_index *idx, const float *q, const int32_t *ids, int32_t m, float *out_lb);
 /* The same with the UPPER bounds beside them (out_ub, may be NULL): out_lb[i] <= distance <= out_ub[i].  The IVF search's
  * bounds pass (hnsw-clj_amd/csrc/stream_kernels.hpp) derives a query's threshold from upper bounds -- k candidates whose
  * upper bound is at most tau put the k-th nearest distance at or below tau -- and drops candidates whose lower bound is
