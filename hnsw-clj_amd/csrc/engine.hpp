@@ -98,9 +98,9 @@ struct hnswgpu_index {
     uint2 *d_lhalf = nullptr;    // list rows in fp16, row-major (four halves per element), + per-row (scale, E, 0, 1/|v|)
     float4 *d_lhmeta = nullptr;
     unsigned long long *d_rej_stats = nullptr;  // [2], counted by the traversal while profiling is on
-    int rejection_mode = 1;  // 0 = off, 1 = batches that fill the chip (launch_hnsw_idx), 2 = every launch
+    int rejection_mode = 1;  // 0 = off, 1 = batches that fill the chip (hnsw_launch_plan), 2 = every launch
     // HNSW, mode 1: the first large launch on a graph counts what the int8 test decides (f32 rows fetched / neighbours
-    // evaluated, launch_hnsw_idx); where it rejects too little to pay for its own bytes -- rows whose neighbours all lie
+    // evaluated, hnsw_launch_plan); where it rejects too little to pay for its own bytes -- rows whose neighbours all lie
     // within the bounds' width of the list's worst -- the later large launches evaluate every neighbour in f32.  0 = not
     // measured, 1 = measured (the counters are on their way to hnsw_cal_host), 2 = decided; reset with the graph.
     int hnsw_cal_state = 0;
@@ -207,7 +207,7 @@ struct hnswgpu_index {
     // them behind its last read); bk_dirty = a search was enqueued past the point that fills them but not past the
     // work-list kernel (an error in between): the next search clears them itself
     bool bk_dirty = false;
-    uint32_t pf_seq = 0;  // launch number of the last prefetch-helper launch (24 bits, never 0)
+    uint32_t pf_seq = 0;  // number of the last small launch, helper or several-CU kernel (hnsw.hip: hnsw_number_launch is its one owner)
     size_t s_done_n = 0;  // counters per half of s_done (scan tails | route tails)
     uint32_t vis_gen = 0;  // last generation number handed to an HBM visited slab
 
@@ -257,11 +257,62 @@ bool attr_needed(bool (&done)[64]);
         }                                                                 \
     } while (0)
 
-// small HNSW launches, one query over several CUs (solo.hip)
-bool solo_enabled(int ef);
-int launch_hnsw_solo(hnswgpu_index *idx, HnswArgs a, hipStream_t st);
-// large HNSW launches, one wave per query on a main list + admission buffer (wave.hip)
-int launch_hnsw_wave(hnswgpu_index *idx, const HnswArgs &a, int grid, size_t lds, bool vg, hipStream_t st);
+// Everything one HNSW traversal launch decides, computed once before anything is allocated, numbered, synchronised or enqueued
+// (hnsw.hip: hnsw_launch_plan, where every rule and its measured reason live) from the handle's state, the launch's shape and ONE
+// reading of the tuning table.  The stages behind it (hnsw_launch_resources, hnsw_dispatch) fill arguments from it and decide nothing.
+enum class HnswKernel {
+    Search,         // hnsw_search_kernel (kernels.hpp): a workgroup of nw waves per query
+    SearchHelpers,  // ... with helper workgroups that evaluate ahead of it: a handful of queries, short lists
+    Solo,           // hnsw_solo_kernel (solo_kernels.hpp): a handful of queries, each over several CUs
+    Wave            // hnsw_wave_kernel (wave_kernels.hpp): one wave per query, main list + admission buffer
+};
+using HnswKernelFn = void (*)(HnswArgs);
+struct HnswLaunchPlan {
+    HnswKernel kernel;
+    HnswKernelFn fn;      // its instantiation for (nch, metric, rejection, nw, vis_global)
+    int nch;              // 256-float chunks per row
+    bool rejection;       // the int8 rejection test is on
+    bool calibrate;       // rejection mode 1: this launch counts what the test decides (hnswgpu_index::hnsw_cal_state 0 -> 1)
+    bool vis_global;      // the visited set as generation stamps in HBM: a slab of n stamps per workgroup of `grid`,
+    int64_t gens;         // `gens` generation numbers per launch;
+    int32_t nwords;       // otherwise a bitset of nwords words in LDS
+    int nw;               // Search: waves per query
+    int grid, block;
+    size_t lds;
+    // SearchHelpers / Solo: helper workgroups per query, list entries looked at ahead, and the parts of one of the four regions
+    // of s_pf / s_solo: [mailboxes: mail_bytes][pf_res / solo_claim: table_bytes][solo_rec: rec_bytes]
+    int32_t pf_groups, pf_hints;
+    bool pf_eval;         // SearchHelpers: the helpers publish distances (false: they only warm the L2)
+    int32_t solo_chase, solo_log2s;
+    size_t mail_bytes, table_bytes, rec_bytes, region;
+    int32_t repeat_cap;   // list capacity of the repeat pass behind this launch, beside the SAME visited set (0: no repeat pass)
+};
+// Row width -> CALL(NCH, R, RF): f32 rows in flight per wave without / with the int8 rejection test -- the one table of the three
+// traversal kernels.  With the test a hop fetches f32 rows for a handful of neighbours only, half or a quarter of them in flight
+// are plenty, and the kernel then holds more waves per SIMD (dim 768, one wave per query: 159 -> 99 VGPRs, five waves instead of
+// three: 10,000 queries 2.24M -> 2.43M QPS, 4,096 queries 1.89M -> 2.39M, 1,024 queries 0.75 -> 0.68 ms).  Longer rows keep their
+// count: at dim 1536 (HBM-resident, 1.25M rows) two rows in flight instead of four cost 7 % although a third wave fits per SIMD.
+// RF3, the cell of nch 3: 2 for hnsw_search_kernel and hnsw_wave_kernel (the measurement above); hnsw_solo_kernel, whose third
+// argument is the rows in flight of a HELPER wave (it never runs the test), takes 4 there -- kept as found, the history names no
+// measurement for it, and each cell is an instantiation, hence a register count.
+#define HG_HNSW_ROWS(nch, RF3, CALL)       \
+    switch (nch) {                         \
+        case 1: CALL(1, 8, 4);             \
+        case 2: CALL(2, 8, 4);             \
+        case 3: CALL(3, 8, RF3);           \
+        case 4: CALL(4, 4, 4);             \
+        case 6: CALL(6, 4, 4);             \
+        case 8: CALL(8, 2, 2);             \
+        case 12: CALL(12, 2, 2);           \
+        default: return nullptr;           \
+    }
+// CALL for a kernel family F<NCH, rows in flight, L2>(plan) that runs the test: returns its instance for (p.rejection, l2)
+#define HG_HNSW_ROWS_IN_FLIGHT(F, N, R, RF) \
+    return p.rejection ? (l2 ? F<N, RF, true>(p) : F<N, RF, false>(p)) : (l2 ? F<N, R, true>(p) : F<N, R, false>(p))
+// the instantiation a plan names, or null for an unsupported row length (solo.hip / wave.hip: the three kernel families are
+// translation units of their own so that they compile side by side)
+HnswKernelFn hnsw_solo_kernel_for(const HnswLaunchPlan &p, const HnswArgs &a);
+HnswKernelFn hnsw_wave_kernel_for(const HnswLaunchPlan &p, const HnswArgs &a);
 int launch_norms(int nch, const float *rows, int64_t ld, int64_t n, float *out, hipStream_t st);
 int ensure_qrows(hnswgpu_index *idx, hipStream_t st);
 // int8 codes + per-row bound terms of `n` rows into freshly allocated *crows / *cmeta (the caller owns them)

@@ -15,164 +15,300 @@
 #include "build_kernels.hpp"
 #include "engine.hpp"
 #include "javarandom.hpp"
+#include "solo_kernels.hpp"  // solo_lds_bytes and the sizes of the several-CU kernel's mailboxes, for hnsw_launch_plan
 
 namespace hg {
 
+constexpr size_t kMaxLds = 160 * 1024;  // the LDS of a CU
+
+// The dynamic LDS of the three traversal kernels (solo_lds_bytes: solo_kernels.hpp, beside the layout it sizes)
 static size_t hnsw_lds_bytes(int cap, int nwords, int nw) {
     // kernels.hpp: hnsw_search_kernel's layout -- ONE list of 8-byte entries + a 16-bit merged position per slot
     return sizeof(uint2) * cap + sizeof(int32_t) * 3 * kMaxDeg + sizeof(int32_t) * 16 + sizeof(int32_t) * nw * kWave +
            sizeof(uint2) * kPfRing + sizeof(uint32_t) * nwords + sizeof(uint16_t) * cap + 16;
 }
 
-constexpr size_t kMaxLds = 160 * 1024;
-
 static size_t wave_lds_bytes(int cap, int nwords) {
     // wave_kernels.hpp: hnsw_wave_kernel's layout -- the main list, the buffer's image, the expansion's candidates, the visited set
     return sizeof(uint2) * cap + sizeof(uint2) * kWave + 2 * sizeof(int32_t) * kMaxDeg + sizeof(uint32_t) * nwords + 16;
 }
 
-// tuning override (HNSWGPU_TUNE_HNSW_NW = 1 | 2 | 4); 0 = choose by batch size
-static int hnsw_nw() {
-    const int64_t v = tune(HNSWGPU_TUNE_HNSW_NW, 0);
-    return (v == 1 || v == 2 || v == 4) ? static_cast<int>(v) : 0;
-}
-
 // Visited-set placement: an LDS bitset while it leaves room for several workgroups per CU, otherwise
 // generation stamps in HBM (4 B per row per resident workgroup; 288 GB makes that cheap).
 constexpr int64_t kLdsVisitedMaxRows = 262144;  // 32 KiB bitset
-static bool force_vg() { return tune(HNSWGPU_TUNE_VIS_GLOBAL, 0) != 0; }  // testing override: the HBM stamps at every size
+// (the several-CU kernel serves launches with the LDS bitset only, and its tags keep 18 bits of a node: solo_kernels.hpp, solo_tag)
+static_assert(kLdsVisitedMaxRows <= (1 << 18), "solo_tag holds 18 bits of a node id");
+// The one predicate of hnsw_launch_plan and of the call combiner (hnsw_search_batch); vis_global_env: HNSWGPU_TUNE_VIS_GLOBAL, the
+// testing override (the HBM stamps at every size)
+static bool hnsw_vis_global(int64_t n, int64_t vis_global_env) { return vis_global_env != 0 || n > kLdsVisitedMaxRows; }
 
-// helper workgroups per query that prefetch neighbour rows into the query's XCD L2 (kernels.hpp, HnswArgs::pf_mail);
-// HNSWGPU_TUNE_PREFETCH = <G> overrides (0 = off)
-static int pf_groups() {
-    const int64_t v = tune(HNSWGPU_TUNE_PREFETCH, 4);
-    return v < 0 ? 0 : (v > 16 ? 16 : static_cast<int>(v));
-}
 constexpr int kPfMaxQueries = 128;  // up to half a CU count of queries: every traversal and at least one helper per query get a CU
+static_assert(kPfMaxQueries == kSoloMaxQueries, "one bound for both kinds of small launch");
+constexpr int kSoloMinEf = 96;      // (hnsw_launch_plan: the several-CU kernel by default from this ef -- 96, not 200)
 
-int launch_hnsw_idx(hnswgpu_index *idx, HnswArgs a, hipStream_t st) {
-    a.dbg = g_tile_dbg_buf;  // null outside diagnostic sessions
-    a.rej_stats = idx->prof ? idx->d_rej_stats : nullptr;
-    if (a.nq <= 0) return 0;
-    const int nch = idx->nch;
+// Stage 1 of a launch.  Rejection mode 1 MEASURES (once per graph, on its first large launch: HnswLaunchPlan::calibrate): the
+// counters travel to pinned host memory behind an event, and the first launch that finds the event complete turns them into the
+// verdict hnsw_launch_plan reads as plain state.  Nothing here blocks.
+static void hnsw_calibration_absorb(hnswgpu_index *idx) {
+    if (idx->hnsw_cal_state != 1 || !idx->ev_hnsw_cal || hipEventQuery(idx->ev_hnsw_cal) != hipSuccess) return;
+    const double f32_rows = static_cast<double>(idx->hnsw_cal_host[0]), nb = static_cast<double>(idx->hnsw_cal_host[1]);
+    idx->hnsw_cal_frac = nb > 0 ? f32_rows / nb : 0.0;
+    const double keep = static_cast<double>(tune(HNSWGPU_TUNE_HNSW_CALIBRATE_PCT, 65)) / 100.0;
+    idx->hnsw_rej_off = nb > 0 && idx->hnsw_cal_frac > keep;  // the test leaves more than that of the rows to fetch
+    idx->hnsw_cal_state = 2;
+}
+
+// The instantiation of hnsw_search_kernel a plan names (wave.hip and solo.hip hold the other two families' tables: the three
+// compile side by side)
+template <int N, int R, bool L>
+static HnswKernelFn search_kernel(const HnswLaunchPlan &p) {
+    if (p.kernel == HnswKernel::SearchHelpers) return &hnsw_search_kernel<N, R, L, 4, false, true>;
+    if (p.vis_global) return p.nw == 1 ? &hnsw_search_kernel<N, R, L, 1, true> : (p.nw == 2 ? &hnsw_search_kernel<N, R, L, 2, true> : &hnsw_search_kernel<N, R, L, 4, true>);
+    return p.nw == 1 ? &hnsw_search_kernel<N, R, L, 1, false> : (p.nw == 2 ? &hnsw_search_kernel<N, R, L, 2, false> : &hnsw_search_kernel<N, R, L, 4, false>);
+}
+
+static HnswKernelFn hnsw_search_kernel_for(const HnswLaunchPlan &p, const HnswArgs &a) {
+    const bool l2 = a.metric == METRIC_L2;
+#define PICK(N, R, RF) HG_HNSW_ROWS_IN_FLIGHT(search_kernel, N, R, RF)
+    HG_HNSW_ROWS(p.nch, 2, PICK);
+#undef PICK
+}
+
+// Stage 2: everything ONE launch decides (HnswLaunchPlan, engine.hpp) -- a pure function of the handle's state, of the launch's
+// shape (a: nq, ef, cap, n, M0, max_level, metric; build mode = q_rows, repeat pass = q_index) and of one reading of the tuning
+// table: every key at most once, every rule evaluated once, here.  The table is process-wide and another thread may change it
+// while a search is being enqueued: a repeat pass is planned from its first pass's plan (`first`) and reads no key at all, so that
+// its list is sized for the visited set it then runs with.  Nothing is allocated, numbered, synchronised or enqueued before this
+// has returned 0: the limits a launch can exceed are found here.
+static int hnsw_launch_plan(const hnswgpu_index *idx, const HnswArgs &a, const HnswLaunchPlan *first, HnswLaunchPlan &p) {
+    memset(&p, 0, sizeof(p));
+    const bool build = a.q_rows != nullptr, repeat = a.q_index != nullptr;
+    p.nch = idx->nch;
     // The rejection test on int8 rows (kernels.hpp: quantize_rows_kernel) turns one memory round trip per hop into two
     // shorter ones: 2.2x the throughput once the chip is bandwidth-bound, ~5 % slower while a launch is latency-bound.
     // 31k x 768, ef 100, ms per launch without / with: 256 queries 0.537 / 0.571, 512: 0.607 / 0.590, 768: 0.817 /
     // 0.611, 1024: 1.05 / 0.74, 10000: 9.9 / 4.4 (tools/hnsw_batch_sweep.py) -- on from two queries per CU.
-    if (!(idx->rejection_mode == 2 || (idx->rejection_mode == 1 && a.nq >= 2 * idx->cus && idx->dim >= 128))) a.qrows = nullptr;
+    p.rejection = a.qrows && (idx->rejection_mode == 2 || (idx->rejection_mode == 1 && a.nq >= 2 * idx->cus && idx->dim >= 128));
     // Mode 1 also MEASURES (once per graph, on its first large launch): the int8 stage pays while it keeps enough f32 rows
     // from being fetched -- 31k x 768 clustered, ef 640: half of them; 1.25M x 1536 clustered, ef 256: a tenth, and the
     // launch then requests 1.15x the bytes of the plain traversal (profiles/r04_config5_hnsw_shard.txt).  Results never
-    // depend on it.  Nothing here blocks: the counters travel to pinned host memory behind an event a later launch looks at.
-    bool calibrate = false;
-    if (a.qrows && idx->rejection_mode == 1 && !a.q_rows && !a.q_index && tune(HNSWGPU_TUNE_HNSW_CALIBRATE, 1) != 0) {
-        if (idx->hnsw_cal_state == 1 && idx->ev_hnsw_cal && hipEventQuery(idx->ev_hnsw_cal) == hipSuccess) {
-            const double f32_rows = static_cast<double>(idx->hnsw_cal_host[0]), nb = static_cast<double>(idx->hnsw_cal_host[1]);
-            idx->hnsw_cal_frac = nb > 0 ? f32_rows / nb : 0.0;
-            const double keep = static_cast<double>(tune(HNSWGPU_TUNE_HNSW_CALIBRATE_PCT, 65)) / 100.0;
-            idx->hnsw_rej_off = nb > 0 && idx->hnsw_cal_frac > keep;  // the test leaves more than that of the rows to fetch
-            idx->hnsw_cal_state = 2;
-        }
-        if (idx->hnsw_cal_state == 2 && idx->hnsw_rej_off) a.qrows = nullptr;
-        calibrate = idx->hnsw_cal_state == 0 && !a.rej_stats;
+    // depend on it.  (A launch that counts for the profile does not measure: the kernel has one pair of counters.)
+    if (p.rejection && idx->rejection_mode == 1 && !build && !repeat && tune(HNSWGPU_TUNE_HNSW_CALIBRATE, 1) != 0) {
+        if (idx->hnsw_cal_state == 2 && idx->hnsw_rej_off) p.rejection = false;
+        p.calibrate = idx->hnsw_cal_state == 0 && !(idx->prof && idx->d_rej_stats);
     }
-    const bool vg = force_vg() || a.n > kLdsVisitedMaxRows;
-    const bool pf = pf_groups() > 0 && !vg && !a.q_rows && !a.q_index && a.nq <= kPfMaxQueries && hnsw_nw() == 0 &&
-                    a.n < (1LL << 31) && a.M0 <= kMaxDeg;
-    // waves per query.  Measured on 31k x 768, ef 128 (tools/tune_hnsw.py): a query takes 1.1 / 1.4 / 2.0 ms
-    // with 4 / 2 / 1 waves, and a CU holds 3 / 6 / 12 such workgroups (VGPR-limited), so once a batch
-    // exceeds one residency round fewer waves per query win: 10,000 queries run at 601k / 776k / 802k QPS.
-    int nw = hnsw_nw() > 0 ? hnsw_nw() : (a.nq > 1536 ? 1 : (a.nq > 768 ? 2 : 4));
-    // with the rejection test (fewer f32 rows in flight, below) a CU holds 4 / 8 / 20 such workgroups up to dim 768:
-    // 1,024 queries 0.60 / 0.68 / 0.96 ms with 4 / 2 / 1 waves, 2,048: 1.15 / 0.93 / 1.06, 3,072: 1.68 / 1.51 / 1.36
-    if (hnsw_nw() == 0 && a.qrows && nch <= 3) nw = a.nq > 2048 ? 1 : (a.nq > 1024 ? 2 : 4);
-    // a long candidate list (large ef) bounds the queries a CU holds by its LDS, not by registers: fewer than ~13 waves per
-    // CU cannot hide the hop's dependent round trips, so the queries that fit get more waves each (the int8 and f32 steps
-    // of a hop then run side by side).  31k x 768 clustered, 10,000 queries, QPS with 1 / 2 / 4 waves: ef 400 729k / 784k /
-    // 513k, ef 800 250k / 343k / 258k, ef 1600 60k / 89k / 116k, ef 3200 10.8k / 17.7k / 25.6k (tools/large_ef_nw.py).
-    // Launches that fill the chip with one wave per query, and every launch with a long list, take the kernel whose list is a
-    // main list + a register-resident admission buffer (wave_kernels.hpp: no positional merge per expansion, the next
-    // candidate out of register windows; 8 bytes of LDS per list slot).  31k x 768 clustered, QPS single-workgroup kernel /
-    // this one (tools/wave_sweep.py): 10,000 queries ef 50 4.55M / 4.80M, ef 640 516k / 778k, ef 1600 151k / 263k, ef 3200 51k /
-    // 91k; 2,048 queries ef 640 467k / 554k; 256 queries ef 50 459k / 418k (four waves per query are the better shape for a
-    // short list on a chip that is not full), ef 640 82k / 92k, ef 3200 13.9k / 22.7k.  HNSWGPU_TUNE_HNSW_WAVE = 0: never (A/B).
-    const size_t wlds = wave_lds_bytes(a.cap, vg ? 0 : a.nwords);
-    const int64_t wave_mode = tune(HNSWGPU_TUNE_HNSW_WAVE, 1);  // 2 = every launch it can serve (tests)
-    const bool use_wave = wave_mode != 0 && !pf && !a.q_index && hnsw_nw() == 0 && wlds <= kMaxLds && a.M0 <= kMaxDeg &&
+    if (repeat) {  // repeat pass: few (usually no) work items, one large-list workgroup per CU at most
+        p.kernel = HnswKernel::Search;
+        p.vis_global = first->vis_global;
+        p.nw = 4;
+        p.grid = std::min(a.nq, 256);
+    } else {
+        // tuning override (HNSWGPU_TUNE_HNSW_NW = 1 | 2 | 4); 0 = choose by batch size
+        const int64_t nw_raw = tune(HNSWGPU_TUNE_HNSW_NW, 0);
+        const int nw_env = (nw_raw == 1 || nw_raw == 2 || nw_raw == 4) ? static_cast<int>(nw_raw) : 0;
+        p.vis_global = hnsw_vis_global(a.n, tune(HNSWGPU_TUNE_VIS_GLOBAL, 0));
+        // helper workgroups per query that prefetch neighbour rows into the query's XCD L2 (kernels.hpp, HnswArgs::pf_mail):
+        // HNSWGPU_TUNE_PREFETCH = <G> overrides (0 = off, and the several-CU path with it).  ONE key, two intended defaults and
+        // clamps: 4 (at most 16) helpers for the round-2 helper kernel, 8 (at most 31) for the several-CU kernel.
+        const int64_t pf_env = tune(HNSWGPU_TUNE_PREFETCH, kTuneUnset);
+        const int helper_groups = pf_env == kTuneUnset ? 4 : static_cast<int>(std::max<int64_t>(0, std::min<int64_t>(16, pf_env)));
+        const int solo_groups = pf_env == kTuneUnset ? 8 : static_cast<int>(std::max<int64_t>(0, std::min<int64_t>(31, pf_env)));
+        const bool small = helper_groups > 0 && !p.vis_global && !build && a.nq <= kPfMaxQueries && nw_env == 0 && a.n < (1LL << 31) &&
+                           a.M0 <= kMaxDeg;
+        // HNSWGPU_TUNE_SOLO: 1 (default) = launches whose list is long enough for the split to pay (ef >= kSoloMinEf = 96: a search of
+        // a few dozen expansions is a descent whose every step waits for the step before it, and the round-2 helpers serve it as well --
+        // 31k x 768 clustered, one query, round-2 helpers / this kernel: ef 50 249 / 255 us, ef 100 378 / 350, ef 200 612 / 524, ef 640
+        // 1,900 / 1,210), 2 = every small launch, 0 = never
+        const int64_t solo_mode = tune(HNSWGPU_TUNE_SOLO, 1);
+        const bool solo = small && solo_groups > 0 && (solo_mode >= 2 || (solo_mode == 1 && a.ef >= kSoloMinEf));
+        const int64_t hints_env = tune(HNSWGPU_TUNE_PF_HINTS, kTuneUnset);
+        const auto hints = [hints_env](int dflt) {
+            return static_cast<int32_t>(std::max<int64_t>(1, std::min<int64_t>(32, hints_env == kTuneUnset ? dflt : hints_env)));
+        };
+        // waves per query.  Measured on 31k x 768, ef 128 (tools/tune_hnsw.py): a query takes 1.1 / 1.4 / 2.0 ms
+        // with 4 / 2 / 1 waves, and a CU holds 3 / 6 / 12 such workgroups (VGPR-limited), so once a batch
+        // exceeds one residency round fewer waves per query win: 10,000 queries run at 601k / 776k / 802k QPS.
+        int nw = nw_env > 0 ? nw_env : (a.nq > 1536 ? 1 : (a.nq > 768 ? 2 : 4));
+        // with the rejection test (fewer f32 rows in flight: HG_HNSW_ROWS) a CU holds 4 / 8 / 20 such workgroups up to dim 768:
+        // 1,024 queries 0.60 / 0.68 / 0.96 ms with 4 / 2 / 1 waves, 2,048: 1.15 / 0.93 / 1.06, 3,072: 1.68 / 1.51 / 1.36
+        if (nw_env == 0 && p.rejection && p.nch <= 3) nw = a.nq > 2048 ? 1 : (a.nq > 1024 ? 2 : 4);
+        // Launches that fill the chip with one wave per query, and every launch with a long list, take the kernel whose list is a
+        // main list + a register-resident admission buffer (wave_kernels.hpp: no positional merge per expansion, the next
+        // candidate out of register windows; 8 bytes of LDS per list slot).  31k x 768 clustered, QPS single-workgroup kernel /
+        // this one (tools/wave_sweep.py): 10,000 queries ef 50 4.55M / 4.80M, ef 640 516k / 778k, ef 1600 151k / 263k, ef 3200 51k /
+        // 91k; 2,048 queries ef 640 467k / 554k; 256 queries ef 50 459k / 418k (four waves per query are the better shape for a
+        // short list on a chip that is not full), ef 640 82k / 92k, ef 3200 13.9k / 22.7k.  HNSWGPU_TUNE_HNSW_WAVE = 0: never (A/B).
+        const int nwords = p.vis_global ? 0 : a.nwords;
+        const int64_t wave_mode = tune(HNSWGPU_TUNE_HNSW_WAVE, 1);  // 2 = every launch it can serve (tests)
+        const bool wave = wave_mode != 0 && !small && nw_env == 0 && wave_lds_bytes(a.cap, nwords) <= kMaxLds && a.M0 <= kMaxDeg &&
                           (wave_mode >= 2 || nw == 1 || a.ef >= 640);
-    if (hnsw_nw() == 0 && !use_wave)
-        while (nw < 4 && static_cast<int64_t>(kMaxLds / hnsw_lds_bytes(a.cap, vg ? 0 : a.nwords, nw)) * nw < 13) nw *= 2;
-    int grid = a.nq;
-    if (a.q_index) {  // repeat pass: few (usually no) work items, one large-list workgroup per CU at most
-        nw = 4;
-        grid = std::min(a.nq, 256);
-    }
-    if (pf && solo_enabled(a.ef)) {
-        a.nwords = static_cast<int32_t>((a.n + 31) / 32);
-        return launch_hnsw_solo(idx, a, st);  // one query over several CUs (solo_kernels.hpp)
-    }
-    if (pf) {
-        // one mailbox per query; four regions in rotation, so that launches in flight (two Slots) never share one
-        nw = 4;
-        // as many helper workgroups per query as find a CU of their own beside the traversals (at most the configured number)
-        a.pf_groups = std::max(1, std::min(pf_groups(), idx->cus / std::max(a.nq, 1) - 1));
-        a.pf_hints = static_cast<int32_t>(std::max<int64_t>(1, std::min<int64_t>(32, tune(HNSWGPU_TUNE_PF_HINTS, 4))));
-        grid = 8 * ((a.nq + 7) / 8) * (1 + a.pf_groups);
-        // per region: the mailboxes, then the helpers' published bounds [query][ring slot][neighbour slot]
-        const size_t mail_bytes = sizeof(uint32_t) * kPfMailWords * kPfMaxQueries;
-        const size_t res_bytes = sizeof(unsigned long long) * kPfMaxQueries * kPfRing * kMaxDeg;
-        const size_t region = mail_bytes + res_bytes;
-        // (both zero fills are waited for: the other slot's launch runs on ITS stream and would otherwise see the old bytes
-        // -- harmless for results, the words are tagged, but its helpers would poll until their timeout; once per handle
-        // and once per 2^24 launches)
-        if (idx->s_pf.cap < 4 * region) {
-            HG_TRY(idx->s_pf.ensure(4 * region));
-            HG_HIP(hipMemsetAsync(idx->s_pf.p, 0, idx->s_pf.cap, st));
-            HG_HIP(hipStreamSynchronize(st));
-        }
-        idx->pf_seq = (idx->pf_seq + 1) & 0xffffff;
-        if (idx->pf_seq == 0) {  // the launch numbers start over: no tag of the previous cycle may survive
-            for (auto &sl : idx->slots)
-                if (sl.st) HG_HIP(hipStreamSynchronize(sl.st));
-            HG_HIP(hipMemsetAsync(idx->s_pf.p, 0, idx->s_pf.cap, st));
-            HG_HIP(hipStreamSynchronize(st));
-            idx->pf_seq = 1;
-        }
-        a.pf_seq = idx->pf_seq;
-        char *reg = static_cast<char *>(idx->s_pf.p) + (idx->pf_seq & 3) * region;
-        a.pf_mail = reinterpret_cast<uint32_t *>(reg);
-        const bool pf_eval = tune(HNSWGPU_TUNE_PF_EVAL, 1) != 0;  // 0 = the helpers only warm the L2 (A/B)
-        if (pf_eval) {
+        // a long candidate list (large ef) bounds the queries a CU holds by its LDS, not by registers: fewer than ~13 waves per
+        // CU cannot hide the hop's dependent round trips, so the queries that fit get more waves each (the int8 and f32 steps
+        // of a hop then run side by side).  31k x 768 clustered, 10,000 queries, QPS with 1 / 2 / 4 waves: ef 400 729k / 784k /
+        // 513k, ef 800 250k / 343k / 258k, ef 1600 60k / 89k / 116k, ef 3200 10.8k / 17.7k / 25.6k (tools/large_ef_nw.py).
+        if (nw_env == 0 && !wave)
+            while (nw < 4 && static_cast<int64_t>(kMaxLds / hnsw_lds_bytes(a.cap, nwords, nw)) * nw < 13) nw *= 2;
+        p.grid = a.nq;
+        if (solo) {  // one query over several CUs (solo_kernels.hpp)
+            p.kernel = HnswKernel::Solo;
+            p.rejection = false;  // the owner's own int8 pass stays off: for a handful of queries it costs what it saves
+            p.pf_groups = std::max(1, std::min(solo_groups, idx->cus / std::max(a.nq, 1) - 1));
+            // the window the fetchers keep evaluated ahead of the sequencer: 8 entries for short searches (ef 100: 350 us against 382
+            // with 16), 16 from ef 256 (ef 640: 1.21 ms against 1.25 with 8, 1.28 with 32)
+            p.pf_hints = hints(a.ef < 256 ? 8 : 16);
+            p.solo_chase = tune(HNSWGPU_TUNE_SOLO_CHASE, 1) != 0 ? 1 : 0;
+            p.grid = 8 * ((a.nq + 7) / 8) * (1 + p.pf_groups);
+            // slots per query of the node-keyed tables: one per row while that stays small (no collisions), else ~32 per list
+            // entry (a search claims ~1.5 ef nodes; a record overwritten before the owner has used it costs the owner a gather),
+            // and the whole region within 512 MB
+            int log2s = static_cast<int>(tune(HNSWGPU_TUNE_SOLO_SLOTS, 0));
+            if (log2s <= 0) {
+                const int64_t want = std::min<int64_t>(a.n, 32LL * a.ef);
+                log2s = 11;
+                while ((1LL << log2s) < want && log2s < 18) log2s++;
+                while (log2s > 11 && (static_cast<int64_t>(a.nq) << log2s) * a.M0 * 8 > (512LL << 20)) log2s--;
+            }
+            p.solo_log2s = std::max(8, std::min(log2s, 18));
+            const size_t S = static_cast<size_t>(1) << p.solo_log2s;
+            // (the mailboxes at a fixed place whatever the batch: a word there never holds an older launch's table entry)
+            p.mail_bytes = (sizeof(uint32_t) * kSoloMailWords * kSoloMaxQueries + 255) & ~static_cast<size_t>(255);
+            p.table_bytes = (sizeof(uint32_t) * S * a.nq + 255) & ~static_cast<size_t>(255);
+            p.rec_bytes = sizeof(unsigned long long) * S * a.M0 * a.nq;
+        } else if (small) {  // the round-2 helper kernel
+            p.kernel = HnswKernel::SearchHelpers;
+            nw = 4;
+            // as many helper workgroups per query as find a CU of their own beside the traversals (at most the configured number)
+            p.pf_groups = std::max(1, std::min(helper_groups, idx->cus / std::max(a.nq, 1) - 1));
+            p.pf_hints = hints(4);
+            p.grid = 8 * ((a.nq + 7) / 8) * (1 + p.pf_groups);
+            // per region: the mailboxes, then the helpers' published bounds [query][ring slot][neighbour slot]
+            p.mail_bytes = sizeof(uint32_t) * kPfMailWords * kPfMaxQueries;
+            p.table_bytes = sizeof(unsigned long long) * kPfMaxQueries * kPfRing * kMaxDeg;
             // the helpers evaluate the neighbours of the hinted nodes and publish the distances (kernels.hpp: pf_res); the
             // traversal's own int8 bounds pass stays off: for a handful of queries it costs what it saves
-            a.pf_res = reinterpret_cast<unsigned long long *>(reg + mail_bytes);
-            a.qrows = nullptr;
+            p.pf_eval = tune(HNSWGPU_TUNE_PF_EVAL, 1) != 0;  // 0 = the helpers only warm the L2 (A/B)
+            if (p.pf_eval) p.rejection = false;
+        } else {
+            p.kernel = wave ? HnswKernel::Wave : HnswKernel::Search;
         }
+        p.region = p.mail_bytes + p.table_bytes + p.rec_bytes;
+        p.nw = nw;
     }
-    if (vg) {
-        a.nwords = 0;
+    p.nwords = p.vis_global ? 0 : a.nwords;
+    if (p.vis_global) {
         // one slab of n stamps per workgroup; a persistent grid bounds the slab count
         const int64_t budget = 16LL << 30;
         int64_t max_wg = budget / (4 * std::max<int64_t>(a.n, 1));
         max_wg = std::min<int64_t>(std::max<int64_t>(max_wg, 256), 256 * 12);
-        grid = static_cast<int>(std::min<int64_t>(a.nq, max_wg));
-        size_t need = sizeof(uint32_t) * static_cast<size_t>(a.n) * grid;
+        p.grid = static_cast<int>(std::min<int64_t>(a.nq, max_wg));
+        p.gens = (static_cast<int64_t>(a.nq) + p.grid - 1) / p.grid * (a.max_level + 1);
+    }
+    p.block = p.kernel == HnswKernel::Solo ? kWG : (p.kernel == HnswKernel::Wave ? kWave : p.nw * kWave);
+    p.lds = p.kernel == HnswKernel::Solo   ? solo_lds_bytes(a.cap, p.nwords)
+            : p.kernel == HnswKernel::Wave ? wave_lds_bytes(a.cap, p.nwords)
+                                           : hnsw_lds_bytes(a.cap, p.nwords, p.nw);
+    // No public call reaches this limit today: check_hnsw_args and both builders cap ef at 4096, so cap <= 4128, and the visited
+    // bits take 32 KiB at most (kLdsVisitedMaxRows).  The three size functions then give at most 10 B x 4128 + 2,384 + 32,768 =
+    // 76,432 B (hnsw_search_kernel, four waves), 8 B x 4128 + 1,040 + 32,768 = 66,832 B (hnsw_wave_kernel) and 8 B x 4128 +
+    // 36,248 + 32,768 = 102,040 B (hnsw_solo_kernel) of the 163,840; a repeat pass's list (repeat_cap, below) is cut to fit.
+    HG_REQUIRE(p.lds <= kMaxLds, HNSWGPU_ELIMIT, "HNSW search state (%zu B: ef=%d, n=%lld) exceeds the 160 KiB LDS of a CU", p.lds,
+               a.ef, (long long)a.n);
+    p.calibrate = p.calibrate && p.rejection;
+    if (!build && !repeat) {
+        // Queries that run out of ghost slots are repeated with the largest candidate list the LDS holds (search_enqueue) -- beside
+        // the visited set THIS plan chose
+        const size_t fixed = hnsw_lds_bytes(0, p.nwords, 4);
+        const int64_t cap_max = std::min<int64_t>(65000, static_cast<int64_t>((kMaxLds - fixed) / (sizeof(uint2) + sizeof(uint16_t))));
+        const int64_t big = std::min<int64_t>(cap_max - a.ef, a.n);
+        p.repeat_cap = big > kGhost ? static_cast<int32_t>(a.ef + big) : 0;
+    }
+    p.fn = p.kernel == HnswKernel::Solo   ? hnsw_solo_kernel_for(p, a)
+           : p.kernel == HnswKernel::Wave ? hnsw_wave_kernel_for(p, a)
+                                          : hnsw_search_kernel_for(p, a);
+    HG_REQUIRE(p.fn, HNSWGPU_ELIMIT, "unsupported row length");
+    return 0;
+}
+
+// every stream that may still run a launch that reads or writes s_pf / s_solo (the slot launches do not pass begin_call / end_call)
+static int hnsw_tables_idle(hnswgpu_index *idx, hipStream_t st) {
+    for (auto &sl : idx->slots)
+        if (sl.st) HG_HIP(hipStreamSynchronize(sl.st));
+    if (idx->stream) HG_HIP(hipStreamSynchronize(idx->stream));
+    HG_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+// The launch number of the small launches, the ONE owner of hnswgpu_index::pf_seq for the round-2 helper kernel and the several-CU
+// kernel alike.  Contract: a word written into s_pf or s_solo under launch number s can never be read by a launch whose tag
+// compares equal to s's (all 24 bits in the helper tables: (number << 8 | lap); the low 14 bits in solo_tag) unless it is that
+// launch -- whichever path took the launches in between.  One counter of 24 bits serves both tables: whenever it reaches a multiple
+// of 0x4000 (2^24 among them) the streams are waited for, every allocated table is cleared and the counter moves on, so two
+// launches whose numbers agree in the low 14 bits always have a clearing of both tables between them.  The number is never 0, in
+// either width (tag 0 is what fresh memory holds: nothing).  Four regions in rotation (number & 3), so that launches in flight
+// (two Slots) never share one.  Cost: one synchronise-and-clear per 16383 small launches.
+static int hnsw_number_launch(hnswgpu_index *idx, hipStream_t st) {
+    idx->pf_seq = (idx->pf_seq + 1) & 0xffffff;
+    if ((idx->pf_seq & 0x3fff) != 0) return 0;
+    HG_TRY(hnsw_tables_idle(idx, st));
+    for (DevBuf *t : {&idx->s_pf, &idx->s_solo})
+        if (t->p) HG_HIP(hipMemsetAsync(t->p, 0, t->cap, st));
+    HG_HIP(hipStreamSynchronize(st));
+    idx->pf_seq++;
+    return 0;
+}
+
+// Stage 3: everything that touches the handle or a stream before the kernel, and the plan's part of HnswArgs.  Decides nothing.
+static int hnsw_launch_resources(hnswgpu_index *idx, const HnswLaunchPlan &p, HnswArgs &a, hipStream_t st) {
+    a.dbg = g_tile_dbg_buf;  // null outside diagnostic sessions
+    a.rej_stats = idx->prof ? idx->d_rej_stats : nullptr;
+    if (!p.rejection) a.qrows = nullptr;
+    a.nwords = p.nwords;
+    if (p.kernel == HnswKernel::SearchHelpers || p.kernel == HnswKernel::Solo) {
+        const bool solo = p.kernel == HnswKernel::Solo;
+        DevBuf &tab = solo ? idx->s_solo : idx->s_pf;
+        // Growing the buffer frees the old one: every stream that may still run a launch on it is waited for first (s_pf has one
+        // size: it grows once, from nothing).  Fresh memory is zeroed (tag 0 = nothing), and the zero fill is waited for: the other
+        // slot's launch runs on ITS stream and would otherwise see the old bytes -- harmless for results, the words are tagged,
+        // but its helpers would poll until their timeout.
+        if (tab.cap < 4 * p.region) {
+            if (solo) HG_TRY(hnsw_tables_idle(idx, st));
+            HG_TRY(tab.ensure(4 * p.region));
+            HG_HIP(hipMemsetAsync(tab.p, 0, tab.cap, st));
+            HG_HIP(hipStreamSynchronize(st));
+        }
+        HG_TRY(hnsw_number_launch(idx, st));
+        a.pf_seq = idx->pf_seq;
+        a.pf_groups = p.pf_groups;
+        a.pf_hints = p.pf_hints;
+        // one mailbox per query at the head of the launch's region (the several-CU kernel's regions: a quarter of the buffer each)
+        char *reg = static_cast<char *>(tab.p) + (idx->pf_seq & 3) * (solo ? (tab.cap / 4 & ~static_cast<size_t>(255)) : p.region);
+        a.pf_mail = reinterpret_cast<uint32_t *>(reg);
+        if (solo) {
+            a.solo_chase = p.solo_chase;
+            a.solo_log2s = p.solo_log2s;
+            a.solo_claim = reinterpret_cast<uint32_t *>(reg + p.mail_bytes);
+            a.solo_rec = reinterpret_cast<unsigned long long *>(reg + p.mail_bytes + p.table_bytes);
+        } else if (p.pf_eval) {
+            a.pf_res = reinterpret_cast<unsigned long long *>(reg + p.mail_bytes);
+        }
+    }
+    if (p.vis_global) {
+        const size_t need = sizeof(uint32_t) * static_cast<size_t>(a.n) * p.grid;
         if (need > idx->s_vis.cap) {
             HG_TRY(idx->s_vis.ensure(need));
             HG_HIP(hipMemsetAsync(idx->s_vis.p, 0, idx->s_vis.cap, st));
             idx->vis_gen = 0;
         }
-        const int64_t gens = (static_cast<int64_t>(a.nq) + grid - 1) / grid * (a.max_level + 1);
-        if (static_cast<int64_t>(idx->vis_gen) + gens >= 0xfffffff0LL) {
+        if (static_cast<int64_t>(idx->vis_gen) + p.gens >= 0xfffffff0LL) {
             HG_HIP(hipMemsetAsync(idx->s_vis.p, 0, idx->s_vis.cap, st));
             idx->vis_gen = 0;
         }
         a.vis = idx->s_vis.as<uint32_t>();
         a.vis_stride = a.n;
         a.gen_base = idx->vis_gen;
-        idx->vis_gen += static_cast<uint32_t>(gens);
+        idx->vis_gen += static_cast<uint32_t>(p.gens);
     }
-    if (calibrate && a.qrows) {
+    if (p.calibrate) {
         if (!idx->d_hnsw_cal) {
             HG_HIP(hipMalloc(reinterpret_cast<void **>(&idx->d_hnsw_cal), 2 * sizeof(unsigned long long)));
             HG_HIP(hipHostMalloc(reinterpret_cast<void **>(&idx->hnsw_cal_host), 2 * sizeof(unsigned long long), hipHostMallocDefault));
@@ -180,89 +316,42 @@ int launch_hnsw_idx(hnswgpu_index *idx, HnswArgs a, hipStream_t st) {
         }
         HG_HIP(hipMemsetAsync(idx->d_hnsw_cal, 0, 2 * sizeof(unsigned long long), st));
         a.rej_stats = idx->d_hnsw_cal;
-    } else {
-        calibrate = false;
     }
-    size_t lds = use_wave ? wave_lds_bytes(a.cap, a.nwords) : hnsw_lds_bytes(a.cap, a.nwords, nw);
-    HG_REQUIRE(lds <= kMaxLds, HNSWGPU_ELIMIT,
-               "HNSW search state (%zu B: ef=%d, n=%lld) exceeds the 160 KiB LDS of a CU", lds, a.ef, (long long)a.n);
-    if (use_wave) {
-        HG_TRY(launch_hnsw_wave(idx, a, grid, lds, vg, st));
-        count_launch(a.qrows ? HNSWGPU_COUNT_HNSW_REJECTION : HNSWGPU_COUNT_HNSW_PLAIN);
-        count_launch(HNSWGPU_COUNT_HNSW_WAVE);
-        if (calibrate) {
-            HG_HIP(hipMemcpyAsync(idx->hnsw_cal_host, idx->d_hnsw_cal, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-            HG_HIP(hipEventRecord(idx->ev_hnsw_cal, st));
-            idx->hnsw_cal_state = 1;
-        }
-        return 0;
-    }
-    bool l2 = a.metric == METRIC_L2;
-#define CALL_K(N, R, L, W, V)                                                                                \
-    do {                                                                                                     \
-        if (lds > 48 * 1024)                                                                                 \
-            HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&hnsw_search_kernel<N, R, L, W, V>),  \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds))); \
-        hipLaunchKernelGGL((hnsw_search_kernel<N, R, L, W, V>), dim3(grid), dim3(W * kWave), lds, st, a);    \
-    } while (0)
-#define CALL_NW(N, R, L, W)          \
-    do {                             \
-        if (vg) CALL_K(N, R, L, W, true); \
-        else CALL_K(N, R, L, W, false);   \
-    } while (0)
-#define CALL_PF(N, R, L)                                                                                          \
-    do {                                                                                                         \
-        if (lds > 48 * 1024)                                                                                     \
-            HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&hnsw_search_kernel<N, R, L, 4, false, true>), \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));     \
-        hipLaunchKernelGGL((hnsw_search_kernel<N, R, L, 4, false, true>), dim3(grid), dim3(4 * kWave), lds, st, a); \
-    } while (0)
-#define CALL(N, R, L)                        \
-    do {                                     \
-        if (pf) CALL_PF(N, R, L);            \
-        else if (nw == 1) CALL_NW(N, R, L, 1);    \
-        else if (nw == 2) CALL_NW(N, R, L, 2); \
-        else CALL_NW(N, R, L, 4);            \
-    } while (0)
-    // f32 rows in flight per wave: with the rejection test a hop fetches f32 rows for a handful of neighbours only, half
-    // a quarter of them in flight are plenty, and the kernel then holds more waves per SIMD (dim 768, one wave per query:
-    // 159 -> 99 VGPRs, five waves instead of three: 10,000 queries 2.24M -> 2.43M QPS, 4,096 queries 1.89M -> 2.39M,
-    // 1,024 queries 0.75 -> 0.68 ms)
-#define CALLR(N, R, RF)                                   \
-    do {                                                  \
-        if (a.qrows) {                                    \
-            if (l2) CALL(N, RF, true);                    \
-            else CALL(N, RF, false);                      \
-        } else {                                          \
-            if (l2) CALL(N, R, true);                     \
-            else CALL(N, R, false);                       \
-        }                                                 \
-    } while (0)
-    switch (nch) {
-        case 1: CALLR(1, 8, 4); break;
-        case 2: CALLR(2, 8, 4); break;
-        case 3: CALLR(3, 8, 2); break;
-        // longer rows keep their count: at dim 1536 (HBM-resident, 1.25M rows) two rows in flight instead of four cost
-        // 7 % although a third wave fits per SIMD
-        case 4: CALLR(4, 4, 4); break;
-        case 6: CALLR(6, 4, 4); break;
-        case 8: CALLR(8, 2, 2); break;
-        case 12: CALLR(12, 2, 2); break;
-        default: set_error("unsupported row length"); return HNSWGPU_ELIMIT;
-    }
-#undef CALLR
-#undef CALL
-#undef CALL_PF
-#undef CALL_NW
-#undef CALL_K
+    return 0;
+}
+
+// Stage 4: the one launch block of the three kernel families (the limit of dynamic LDS is raised on every launch beyond 48 KiB)
+static int hnsw_dispatch(const HnswLaunchPlan &p, const HnswArgs &a, hipStream_t st) {
+    if (p.lds > 48 * 1024)
+        HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(p.fn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(p.lds)));
+    hipLaunchKernelGGL(p.fn, dim3(p.grid), dim3(p.block), p.lds, st, a);
     HG_HIP(hipGetLastError());
-    count_launch(pf ? HNSWGPU_COUNT_HNSW_HELPERS : (a.qrows ? HNSWGPU_COUNT_HNSW_REJECTION : HNSWGPU_COUNT_HNSW_PLAIN));
-    if (calibrate) {
+    return 0;
+}
+
+// Stages 3 to 5 of a planned launch; the tail: the launch counters, and a measuring launch sends its counters on their way
+static int hnsw_launch_planned(hnswgpu_index *idx, const HnswLaunchPlan &p, HnswArgs a, hipStream_t st) {
+    HG_TRY(hnsw_launch_resources(idx, p, a, st));
+    HG_TRY(hnsw_dispatch(p, a, st));
+    if (p.kernel == HnswKernel::Solo) count_launch(HNSWGPU_COUNT_HNSW_SOLO);
+    else if (p.kernel == HnswKernel::SearchHelpers) count_launch(HNSWGPU_COUNT_HNSW_HELPERS);
+    else count_launch(p.rejection ? HNSWGPU_COUNT_HNSW_REJECTION : HNSWGPU_COUNT_HNSW_PLAIN);
+    if (p.kernel == HnswKernel::Wave) count_launch(HNSWGPU_COUNT_HNSW_WAVE);
+    if (p.calibrate) {
         HG_HIP(hipMemcpyAsync(idx->hnsw_cal_host, idx->d_hnsw_cal, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
         HG_HIP(hipEventRecord(idx->ev_hnsw_cal, st));
         idx->hnsw_cal_state = 1;
     }
     return 0;
+}
+
+// One HNSW traversal launch, stages 1 to 5 (the builder's; search_enqueue keeps its plan for the repeat pass)
+static int launch_hnsw_idx(hnswgpu_index *idx, const HnswArgs &a, hipStream_t st) {
+    if (a.nq <= 0) return 0;
+    HnswLaunchPlan p;
+    hnsw_calibration_absorb(idx);
+    HG_TRY(hnsw_launch_plan(idx, a, nullptr, p));
+    return hnsw_launch_planned(idx, p, a, st);
 }
 
 static void free_graph(hnswgpu_index *idx) {
@@ -334,6 +423,11 @@ static int search_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, int3
     a.out_ids = d_ids;
     a.out_dist = d_dist;
     a.stats = d_stats;
+    if (nq <= 0) return 0;
+    // one plan -- one reading of the tuning table -- per call: the first pass's, which also sizes the repeat pass
+    HnswLaunchPlan p;
+    if (!repeat_only) hnsw_calibration_absorb(idx);
+    HG_TRY(hnsw_launch_plan(idx, a, nullptr, p));
     int32_t *again_cnt, *again;
     if (sig) {
         again_cnt = sig->again;
@@ -357,7 +451,7 @@ static int search_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, int3
         }
         hipEvent_t e0;
         prof_begin(idx, PROF_HNSW, st, &e0);
-        rc = launch_hnsw_idx(idx, a, st);
+        rc = hnsw_launch_planned(idx, p, a, st);
         prof_end(idx, PROF_HNSW, st, e0);
         if (rc || sig) return rc;
         a.done_cnt = nullptr;
@@ -366,17 +460,15 @@ static int search_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, int3
     // ... and are repeated, on the device and without a host round trip, with the largest candidate list the LDS
     // holds, so that every tie the reference would still expand (ultra_fast.clj:175-178, `<=`) is kept.  The pass
     // finds no work item on ordinary data (a few microseconds).
-    const int vgw = (force_vg() || idx->n > kLdsVisitedMaxRows) ? 0 : static_cast<int>((idx->n + 31) / 32);
-    const size_t fixed = hnsw_lds_bytes(0, vgw, 4);
-    const int64_t cap_max = std::min<int64_t>(65000, static_cast<int64_t>((kMaxLds - fixed) / (sizeof(uint2) + sizeof(uint16_t))));
-    const int32_t big = static_cast<int32_t>(std::min<int64_t>(cap_max - ef, idx->n));
-    if (big > kGhost) {
-        a.cap = ef + big;
+    if (p.repeat_cap) {
+        a.cap = p.repeat_cap;
         a.again = nullptr;
         a.again_cnt = nullptr;
         a.q_index = again;
         a.nq_dev = again_cnt;
-        rc = launch_hnsw_idx(idx, a, st);
+        HnswLaunchPlan r;
+        HG_TRY(hnsw_launch_plan(idx, a, &p, r));
+        rc = hnsw_launch_planned(idx, r, a, st);
     }
     if (repeat_only && rc == 0) HG_HIP(hipMemsetAsync(again_cnt, 0, sizeof(int32_t), st));  // zero between calls
     return rc;
@@ -860,7 +952,8 @@ static int hnsw_search_batch_slot(hnswgpu_index *idx, const std::vector<hnswgpu_
 // One launch for a set of queued synchronous requests with the same (k, ef): queries concatenated on the host,
 // results scattered back (see hnswgpu_index::SearchReq).
 static int hnsw_search_batch(hnswgpu_index *idx, const std::vector<hnswgpu_index::SearchReq *> &batch, int32_t total) {
-    if (zero_copy() && total <= kZcMaxQueries && !force_vg() && idx->n <= kLdsVisitedMaxRows)
+    // (the mapped-memory slot serves the LDS visited set: the plan's own predicate)
+    if (zero_copy() && total <= kZcMaxQueries && !hnsw_vis_global(idx->n, tune(HNSWGPU_TUNE_VIS_GLOBAL, 0)))
         return hnsw_search_batch_slot(idx, batch, total);
     const int32_t k = batch[0]->k, ef = batch[0]->ef;
     const int64_t cnt = static_cast<int64_t>(total) * k;
