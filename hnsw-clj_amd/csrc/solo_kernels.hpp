@@ -817,19 +817,58 @@ __global__ __launch_bounds__(kWG) void hnsw_solo_kernel(HnswArgs a) {
                     // ---- admission (:195-204), the reference's own loop: the fresh neighbours in adjacency order, each
                     //      against the worst of `nearest` as the ones before it have left it
                     const bool isfull = pm + pb >= ef_l;
-                    const uint64_t smask = __builtin_amdgcn_ballot_w64(fresh && (!isfull || dist < worst));  // (the worst only shrinks)
+                    uint64_t smask = __builtin_amdgcn_ballot_w64(fresh && (!isfull || dist < worst));  // (the worst only shrinks)
 #ifdef HG_SOLO_STAMPS
                     if (level == 0 && smask) {
                         dg[isfull ? 0 : 1]++;
                         dg[isfull ? 2 : 3] += __popcll(smask);
                     }
 #endif
-                    // (63 admissions at most between two merges: the buffer has 64 lanes, and the tail window of 64 main entries
-                    // covers every eviction)
+                    // ONE survivor (lane j): straight into its place
+                    auto admit_one = [&](int j) {
+                        const uint32_t djb = static_cast<uint32_t>(__builtin_amdgcn_readlane(__float_as_int(dist), j));
+                        const uint32_t idj = static_cast<uint32_t>(__builtin_amdgcn_readlane(nb_id, j));
+                        if (pm + pb >= ef_l && fkey(djb) >= worst_k) return;  // (:195-198, a strict <)
+                        // behind the buffer entries <= it (ties: admission order; lanes >= nb hold +inf)
+                        const float dj = __uint_as_float(djb);
+                        const int r0 = __popcll(__builtin_amdgcn_ballot_w64(bd <= dj));
+                        const int r = r0 < nb ? r0 : nb;  // (an infinite distance: behind everything)
+                        const float sd = __uint_as_float(wave_shr1(__float_as_uint(bd)));
+                        const uint32_t si = wave_shr1(bi);
+                        bd = lane > r ? sd : (lane == r ? dj : bd);
+                        bi = lane > r ? si : (lane == r ? idj : bi);
+                        const uint64_t lowm = (1ull << r) - 1ull;
+                        bun = (bun & lowm) | ((bun & ~lowm) << 1) | (1ull << r);
+                        nb++;
+                        pb++;
+                        // (:203-204) if `nearest` now holds ef + 1, its worst leaves it: the later of the two tails (a tie: the
+                        // buffer's, it is the younger).  Straight-line: integer selects on the keys, no branch.
+                        {
+                            const int over = pm + pb > ef_l ? 1 : 0;
+                            const int im = pm - 1 - tbase;
+                            const uint32_t wmb = static_cast<uint32_t>(__builtin_amdgcn_readlane(__float_as_int(td), im > 0 ? im : 0));
+                            const uint32_t wbb = static_cast<uint32_t>(__builtin_amdgcn_readlane(__float_as_int(bd), pb - 1));
+                            const int evm = (over && pm > 0 && fkey(wmb) > fkey(wbb)) ? 1 : 0;
+                            pm -= evm;
+                            pb -= over - evm;
+                        }
+                        top_worst();
+                        dirty = true;
+                    };
+                    // (63 admissions at most between two merges: the buffer has 64 lanes, and the tail window of 64 main entries shows
+                    // main[pm - 1] through 63 evictions.  64 survivors at once -- 64 layer-0 slots, all fresh -- could push 64 main
+                    // entries out: pm would arrive at tbase and the window's lane 0 be main[pm], an entry that has LEFT `nearest`, read
+                    // as its worst.  So the first of them goes alone and the window is loaded again behind it; the other 63 follow
+                    // together, and the buffer then holds 64)
                     SOLO_STAMP(5);
                     if (smask && nb + __popcll(smask) > kWave - 1) {
                         compact();
                         top_worst();
+                        if (smask == ~0ull) {
+                            admit_one(0);
+                            load_tail();
+                            smask &= smask - 1;
+                        }
                     }
                     SOLO_STAMP(6);
                     if (smask & (smask - 1)) {
@@ -918,38 +957,7 @@ __global__ __launch_bounds__(kWG) void hnsw_solo_kernel(HnswArgs a) {
                             dirty_sc = true;  // (the mirror IS the buffer now)
                         }
                     }
-#pragma unroll 1
-                    for (uint64_t mm = (smask & (smask - 1)) == 0 ? smask : 0; mm; mm &= mm - 1) {  // ONE survivor: straight into its place
-                        const int j = __ffsll(static_cast<unsigned long long>(mm)) - 1;
-                        const uint32_t djb = static_cast<uint32_t>(__builtin_amdgcn_readlane(__float_as_int(dist), j));
-                        const uint32_t idj = static_cast<uint32_t>(__builtin_amdgcn_readlane(nb_id, j));
-                        if (pm + pb >= ef_l && fkey(djb) >= worst_k) continue;  // (:195-198, a strict <)
-                        // behind the buffer entries <= it (ties: admission order; lanes >= nb hold +inf)
-                        const float dj = __uint_as_float(djb);
-                        const int r0 = __popcll(__builtin_amdgcn_ballot_w64(bd <= dj));
-                        const int r = r0 < nb ? r0 : nb;  // (an infinite distance: behind everything)
-                        const float sd = __uint_as_float(wave_shr1(__float_as_uint(bd)));
-                        const uint32_t si = wave_shr1(bi);
-                        bd = lane > r ? sd : (lane == r ? dj : bd);
-                        bi = lane > r ? si : (lane == r ? idj : bi);
-                        const uint64_t lowm = (1ull << r) - 1ull;
-                        bun = (bun & lowm) | ((bun & ~lowm) << 1) | (1ull << r);
-                        nb++;
-                        pb++;
-                        // (:203-204) if `nearest` now holds ef + 1, its worst leaves it: the later of the two tails (a tie: the
-                        // buffer's, it is the younger).  Straight-line: integer selects on the keys, no branch.
-                        {
-                            const int over = pm + pb > ef_l ? 1 : 0;
-                            const int im = pm - 1 - tbase;
-                            const uint32_t wmb = static_cast<uint32_t>(__builtin_amdgcn_readlane(__float_as_int(td), im > 0 ? im : 0));
-                            const uint32_t wbb = static_cast<uint32_t>(__builtin_amdgcn_readlane(__float_as_int(bd), pb - 1));
-                            const int evm = (over && pm > 0 && fkey(wmb) > fkey(wbb)) ? 1 : 0;
-                            pm -= evm;
-                            pb -= over - evm;
-                        }
-                        top_worst();
-                        dirty = true;
-                    }
+                    if (smask && (smask & (smask - 1)) == 0) admit_one(__ffsll(static_cast<unsigned long long>(smask)) - 1);
                     SOLO_STAMP(7);
                     if (dirty) Ls.bmir[lane] = make_uint2(__float_as_uint(bd), bi);  // the fetchers see the buffer through its mirror
                     if (dirty || dirty_sc) {

@@ -80,7 +80,7 @@ struct WaveList {
     }
     // Merge the buffer into the main list, in place: buffer entry k goes to k + (main entries <= it), main entry i to i + (buffer
     // entries < it) -- the main entries are the older ones.  Blocks from the tail down to the first position that changes; an
-    // entry moves towards the tail by at most 63, into blocks already read.
+    // entry moves towards the tail by at most 64, into blocks already read.
     __device__ __forceinline__ void compact() {
         if (nb == 0) return;
         if (lane < nb) img[lane] = make_uint2(__float_as_uint(bd), bi);
@@ -176,6 +176,15 @@ struct WaveList {
         if (nb + __popcll(smask) > kWave - 1) {  // (63 admissions at most between two merges)
             compact();
             top_worst();
+            // The tail window shows main[pm - 1] through 63 evictions, and 63 admissions cause no more.  64 survivors at once
+            // (64 layer-0 slots, all fresh) could push 64 main entries out: pm would arrive at tbase and the window's lane 0 be
+            // main[pm], an entry that has LEFT `nearest`, read as its worst.  So the first of them goes alone and the window is
+            // loaded again behind it; the other 63 follow together (the buffer then holds 64).
+            if (smask == ~0ull) {
+                admit_one(0, dist, id);
+                load_tail();
+                smask &= smask - 1;
+            }
         }
         if (smask & (smask - 1)) {
             // two or more: one pass in adjacency order decides every admission exactly as the sequential loop would -- a survivor
@@ -254,8 +263,10 @@ struct WaveList {
             top_worst();
             return;
         }
-        // ONE survivor: straight into its place
-        const int j = __ffsll(static_cast<unsigned long long>(smask)) - 1;
+        admit_one(__ffsll(static_cast<unsigned long long>(smask)) - 1, dist, id);
+    }
+    // ONE survivor (lane j): straight into its place
+    __device__ __forceinline__ void admit_one(int j, float dist, uint32_t id) {
         const uint32_t djb = static_cast<uint32_t>(__builtin_amdgcn_readlane(__float_as_int(dist), j));
         const uint32_t idj = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(id), j));
         if (full() && wl_key(djb) >= worst_k) return;  // (:195-198, a strict <)
