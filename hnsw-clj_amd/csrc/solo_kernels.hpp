@@ -25,22 +25,9 @@
 // waits for a helper (helpers leave on the owner's done word or after 20 ms), so ids, distance bits and both traversal
 // counters are the single-workgroup kernel's by construction -- the whole parity suite runs through this path.
 #pragma once
-#include "kernels.hpp"
+#include "hnsw_list.hpp"
 
 namespace hg {
-
-// LDS accesses that another wave of the workgroup must see in program order: volatile, and EXPLICITLY in the LDS address space
-// (a volatile access through a generic pointer is a flat instruction with a wait behind it: the compiler does not infer the
-// address space of volatile accesses)
-#define HG_LDS __attribute__((address_space(3)))
-template <class T>
-__device__ __forceinline__ volatile HG_LDS T *ldsv(T *p) {
-    return (volatile HG_LDS T *)p;
-}
-template <class T>
-__device__ __forceinline__ HG_LDS T *ldsp(T *p) {
-    return (HG_LDS T *)p;
-}
 
 constexpr int kSoloRing = 256;                      // ring entries (64-bit) per query
 constexpr int kSoloMailWords = 16 + 2 * kSoloRing;  // 32-bit words per query: [0..1] ring head (launch << 32 | count), [2] done, [4..5] tau (launch << 32 | float bits), [16..] ring
@@ -181,7 +168,7 @@ struct SoloLds {
     uint2 *win;                   // [kSoloFetchers][64] scratch of the fetchers' window compaction
     uint2 *bmir;                  // [64] mirror of the sequencer's admission buffer (the fetchers and the compaction read it)
     uint32_t *bits;               // [nwords] visited set
-    int32_t *sc;                  // [32] scalars: [0] first unexpanded index of the main list [1] its length [2] fin [3] buffer entries [6] ghost overflow [8] gather requests [9] gather answers [13] level done
+    int32_t *sc;                  // [32] scalars: [0] first unexpanded index of the main list [1] its length [2] fin [3] buffer entries [8] gather requests [9] gather answers [13] level done
     uint32_t *c_node;             // [kSoloSlots] node a slot holds (kSoloFree / kSoloBusy)
     uint32_t *c_done;             // [kSoloSlots] node the sequencer has consumed from the slot (written by the sequencer only)
     uint32_t *c_state;            // [kSoloSlots] 1 = c_id holds the node's adjacency row
@@ -492,15 +479,8 @@ __device__ __forceinline__ void solo_gather(const HnswArgs &a, const float4 (&q)
 }
 
 // ---- the kernel -----------------------------------------------------------------------------------------------------------
-// The sequencer's list is TWO sorted sequences: the main list in LDS and an admission buffer of up to 64 entries in its
-// registers (lane k = the k-th smallest; mirrored to LDS for the fetchers).  The reference's `nearest` (ultra_fast.clj:158)
-// is main[0, pm) + buffer[0, pb), pm + pb <= ef; its `candidates` are the unexpanded entries of both.  An admitted neighbour
-// (:195-198) enters the buffer by one ballot and one lane shift; the entry it pushes out of `nearest` (:203-204) is the
-// later of main[pm - 1] and buffer[pb - 1] -- a pointer moves, nothing else.  Evicted entries stay where they are: the
-// next candidate is the smaller of the first unexpanded entries of either sequence, and it is expanded iff it is still
-// <= the worst of `nearest` (:175-178) -- the reference's own loop, instead of the single-workgroup kernel's positional
-// merge of every expansion (one wave moved ~6 blocks of a 640-entry list per admission: 4 us per expansion).  Every 64
-// admissions, and when the layer is done, the buffer is merged into the main list in place (per-lane binary searches).
+// The owner's wave 0, the sequencer, keeps the candidate list of hnsw_list.hpp, MIRRORED: its fetchers look ahead through the
+// admission buffer's mirror (SoloLds::bmir) and the scalars it publishes in sc[].
 // RB: rows in flight per trip of the sequencer's own gathers; RBH: of a helper wave.
 template <int NCH, int RB, int RBH, bool L2>
 __global__ __launch_bounds__(kWG) void hnsw_solo_kernel(HnswArgs a) {
@@ -517,7 +497,6 @@ __global__ __launch_bounds__(kWG) void hnsw_solo_kernel(HnswArgs a) {
         uint2 *const curA = Ls.list;
         uint32_t *const bits = Ls.bits;
         volatile HG_LDS int32_t *sc = ldsv(Ls.sc);
-        volatile HG_LDS uint2 *const bm = ldsv(Ls.bmir);
         volatile HG_LDS uint32_t *const vnode = ldsv(Ls.c_node), *const vstate = ldsv(Ls.c_state), *const vdone = ldsv(Ls.c_done);
         volatile HG_LDS unsigned long long *const vvalid = ldsv(Ls.c_valid);
         volatile HG_LDS int32_t *const vcid = ldsv(Ls.c_id);
@@ -528,7 +507,8 @@ __global__ __launch_bounds__(kWG) void hnsw_solo_kernel(HnswArgs a) {
         const float qn = a.metric == METRIC_COS ? query_norm<NCH>(q) : 0.0f;
         int64_t n_eval = 0, n_hop = 0, n_exact = 0;
         unsigned long long h_cached = 0, h_full = 0, h_poll = 0, h_gather = 0, h_l0 = 0, h_compact = 0;
-        int lm = 0;  // entries of the main list
+        int len = 0;        // entries of the main list (the sequencer's)
+        bool over = false;  // ... and whether ties with its worst may have been cut off
         if (tid < 32) sc[tid] = 0;
         if (tid < kSoloSlots) {
             Ls.c_node[tid] = kSoloFree;
@@ -543,7 +523,7 @@ __global__ __launch_bounds__(kWG) void hnsw_solo_kernel(HnswArgs a) {
             const float s = wave_sum(lane_partial<NCH, L2>(q, r));
             const float d = finish_dist(a.metric, s, qn, a.metric == METRIC_COS ? a.row_norms[a.entry] : 0.0f);
             if (lane == 0) curA[0] = make_uint2(__float_as_uint(d + 0.0f), static_cast<uint32_t>(a.entry));
-            lm = 1;
+            len = 1;
             n_eval = 1;
         }
         const int64_t S = static_cast<int64_t>(1) << a.solo_log2s;
@@ -555,137 +535,26 @@ __global__ __launch_bounds__(kWG) void hnsw_solo_kernel(HnswArgs a) {
             __syncthreads();
             if (wave == 0) {
                 // ================= the sequencer: search-layer-ultra on this layer, one wave, no barrier =================
-                if (lm > ef_l) lm = ef_l;
+                if (len > ef_l) len = ef_l;
                 // the reference re-evaluates its entry points at every layer (:162-167); the values are reused here, but
                 // counted so that `evals` is the reference's number of distance calls
-                if (level != a.max_level) n_eval += lm;
-                for (int i = lane; i < lm; i += kWave) {
+                if (level != a.max_level) n_eval += len;
+                for (int i = lane; i < len; i += kWave) {
                     uint2 e = curA[i];
                     e.y &= ~kExpanded;
                     curA[i] = e;
                     atomicOr(&bits[e.y >> 5], 1u << (e.y & 31));
                 }
                 const int deg = level == 0 ? a.M0 : a.M;
-                // ---- the two sequences
-                float bd = __uint_as_float(0x7f800000u);  // buffer, lane k: distance (+inf behind the entries) ...
-                uint32_t bi = kExpanded;    // ... and node | expanded flag
-                int nb = 0, pb = 0;         // buffer entries; those of them in `nearest`
-                uint64_t bun = 0;           // bit k: buffer entry k is unexpanded
-                int pm = lm;                // main entries in `nearest`
-                float fd = 0.0f;            // front window of the main list, lane l: entry fbase + l
-                uint32_t fi = kExpanded;
-                int fbase = 0;
-                uint64_t fun = 0;           // bit l: entry fbase + l exists and is unexpanded
-                float td = 0.0f;            // tail window: distance of main entry tbase + l (the entries around pm)
-                int tbase = 0;
-                float worst = 0.0f;         // of `nearest`, while it holds ef entries
-                bool dirty = false;         // the buffer differs from its mirror
-                bool dirty_sc = false;      // ... only its entry count does
-                auto load_front = [&](int from) {
-                    fbase = from;
-                    const int i = fbase + lane;
-                    uint2 e = make_uint2(0u, kExpanded);
-                    if (i < lm) e = curA[i];
-                    fd = __uint_as_float(e.x);
-                    fi = e.y;
-                    fun = __builtin_amdgcn_ballot_w64(i < lm && !(e.y & kExpanded));
-                };
-                auto load_tail = [&]() {
-                    tbase = pm > kWave ? pm - kWave : 0;
-                    const int i = tbase + lane;
-                    td = i < lm ? __uint_as_float(curA[i].x) : 0.0f;
-                };
-                // (scalar decisions compare ORDERABLE KEYS of the distance bits with integer instructions: a float compare of two
-                // uniform values is a vector instruction whose result the scalar unit then waits ~25 cycles for)
-                auto fkey = [](uint32_t b) { return b ^ (static_cast<uint32_t>(static_cast<int32_t>(b) >> 31) | 0x80000000u); };
-                uint32_t worst_k = 0;
-                auto top_worst = [&]() {  // the later of main[pm - 1] and buffer[pb - 1]: the worst of `nearest`
-                    const int im = pm - 1 - tbase, ib = pb - 1;
-                    const uint32_t wmb = static_cast<uint32_t>(__builtin_amdgcn_readlane(__float_as_int(td), im > 0 ? im : 0));
-                    const uint32_t wbb = static_cast<uint32_t>(__builtin_amdgcn_readlane(__float_as_int(bd), ib > 0 ? ib : 0));
-                    const uint32_t km = pm > 0 ? fkey(wmb) : 0u, kb2 = pb > 0 ? fkey(wbb) : 0u;
-                    worst_k = kb2 >= km ? kb2 : km;
-                    worst = __uint_as_float(kb2 >= km ? wbb : wmb);
-                };
-                // Merge the buffer into the main list, in place: buffer entry k goes to k + (main entries <= it), main entry i
-                // to i + (buffer entries < it) -- the main entries are the older ones.  Blocks from the tail down to the first
-                // position that changes; an entry moves towards the tail by at most 64, into blocks already read.
-                auto compact = [&]() {
-                    if (nb == 0) return;
-                    h_compact++;
-                    if (lane < nb) {
-                        bm[lane].x = __float_as_uint(bd);
-                        bm[lane].y = bi;
-                    }
-                    // (the first unexpanded main entry, in the coordinates before the merge: nothing in front of it or of minP moves)
-                    const int first_un = fun ? fbase + __ffsll(static_cast<unsigned long long>(fun)) - 1 : fbase + kWave;
-                    int lo = 0, hi = lm;  // upper bound of bd in the main list
-                    for (int span = lm; span > 0; span >>= 1) {
-                        const int mid = (lo + hi) >> 1;
-                        const float v = __uint_as_float(curA[mid < lm ? mid : lm - 1].x);
-                        const bool act = lo < hi;
-                        const bool go = act && v <= bd;
-                        lo = go ? mid + 1 : lo;
-                        hi = (act && !go) ? mid : hi;
-                    }
-                    const int Pk = lane + lo;
-                    const int minP = __builtin_amdgcn_readlane(Pk, 0);
-                    const int total = lm + nb, top = pm + pb;
-                    const bool full = top >= ef_l;
-                    for (int base = ((lm - 1) / kWave) * kWave; base >= 0 && base + kWave > minP; base -= kWave) {
-                        const int i = base + lane;
-                        const bool valid_i = i < lm;
-                        uint2 e = make_uint2(0u, 0u);
-                        if (valid_i) e = curA[i];
-                        const float de = __uint_as_float(e.x);
-                        int l2 = 0, h2 = nb;  // lower bound of de in the buffer
-#pragma unroll
-                        for (int it = 0; it < 7; it++) {
-                            const int mid = (l2 + h2) >> 1;
-                            const float v = __uint_as_float(bm[mid < nb ? mid : nb - 1].x);
-                            const bool act = l2 < h2;
-                            const bool go = act && v < de;
-                            l2 = go ? mid + 1 : l2;
-                            h2 = (act && !go) ? mid : h2;
-                        }
-                        const int Pe = i + l2;
-                        if (valid_i && Pe < a.cap && Pe != i) curA[Pe] = e;
-                    }
-                    if (lane < nb && Pk < a.cap) curA[Pk] = make_uint2(__float_as_uint(bd), bi);
-                    if (full) {
-                        // behind `nearest` only what ties its worst can still be expanded (:175-178): that run stays (the
-                        // single-workgroup kernel's ghosts), as far as the list has room
-                        const uint32_t wbits = curA[ef_l - 1].x;
-                        int phys = (total < a.cap ? total : a.cap) - ef_l;
-                        const bool more = phys > kWave || total > a.cap;
-                        phys = phys > kWave ? kWave : phys;
-                        const bool tie = lane < phys && curA[ef_l + (lane < phys ? lane : 0)].x == wbits;
-                        const uint64_t nt = ~__builtin_amdgcn_ballot_w64(tie);
-                        const int run = nt ? __ffsll(static_cast<unsigned long long>(nt)) - 1 : kWave;
-                        if (run == phys && more && lane == 0) sc[6] = 1;  // ties may have been cut off: the query is repeated
-                        lm = ef_l + run;
-                        pm = ef_l;
-                    } else {
-                        lm = total;
-                        pm = total;
-                    }
-                    nb = 0;
-                    pb = 0;
-                    bun = 0;
-                    bi = kExpanded;
-                    bd = __uint_as_float(0x7f800000u);
-                    dirty = true;
-                    load_front(first_un < minP ? first_un : minP);
-                    load_tail();
-                };
-                load_front(0);
-                load_tail();
-                top_worst();
-                if (lane == 0) {
-                    sc[0] = 0;
-                    sc[1] = lm;
-                    sc[3] = 0;
-                }
+                HnswList<true> L;
+                L.main = curA;
+                L.img = ldsv(Ls.bmir);
+                L.sc = sc;
+                L.lane = lane;
+                L.cap = a.cap;
+                L.overflow = false;
+                L.merges = 0;
+                L.begin_level(len, ef_l);
 #ifdef HG_SOLO_STAMPS
                 unsigned long long st_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
                 unsigned long long dg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -693,33 +562,8 @@ __global__ __launch_bounds__(kWG) void hnsw_solo_kernel(HnswArgs a) {
 #endif
                 for (;;) {
                     SOLO_STAMP(9);
-                    // ---- next candidate: the smaller of the first unexpanded entries of the two sequences (a tie: the main
-                    //      list's, it is the older one)
-                    while (fun == 0 && fbase + kWave < lm) load_front(fbase + kWave);
-                    if ((fun | bun) == 0) break;
-                    const int lf = fun ? __ffsll(static_cast<unsigned long long>(fun)) - 1 : 0;
-                    const int kb = bun ? __ffsll(static_cast<unsigned long long>(bun)) - 1 : 0;
-                    const uint32_t dmk = fun ? fkey(static_cast<uint32_t>(__builtin_amdgcn_readlane(__float_as_int(fd), lf))) : 0xffffffffu;
-                    const uint32_t dbk = bun ? fkey(static_cast<uint32_t>(__builtin_amdgcn_readlane(__float_as_int(bd), kb))) : 0xffffffffu;
-                    const uint32_t nm = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(fi), lf));
-                    const uint32_t nbf = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(bi), kb));
-                    const bool take_main = fun != 0 && dmk <= dbk;
-                    if (pm + pb >= ef_l && (take_main ? dmk : dbk) > worst_k) break;  // (:175-178; nothing behind it can qualify either)
-                    const uint32_t node = take_main ? nm : nbf;
-                    if (take_main) {
-                        if (lane == lf) {
-                            fi |= kExpanded;
-                            curA[fbase + lf].y = fi;
-                        }
-                        fun &= fun - 1;
-                        if (lane == 0) sc[0] = fun ? fbase + __ffsll(static_cast<unsigned long long>(fun)) - 1 : fbase + kWave;
-                    } else {
-                        if (lane == kb) {
-                            bi |= kExpanded;
-                            bm[kb].y = bi;
-                        }
-                        bun &= bun - 1;
-                    }
+                    uint32_t node;
+                    if (!L.pop(node)) break;
                     SOLO_STAMP(0);
                     // ---- its neighbours and their distances: the LDS cache first
                     int32_t nb_id = -1;
@@ -814,165 +658,27 @@ __global__ __launch_bounds__(kWG) void hnsw_solo_kernel(HnswArgs a) {
                         }
                     }
                     SOLO_STAMP(4);
-                    // ---- admission (:195-204), the reference's own loop: the fresh neighbours in adjacency order, each
-                    //      against the worst of `nearest` as the ones before it have left it
-                    const bool isfull = pm + pb >= ef_l;
-                    uint64_t smask = __builtin_amdgcn_ballot_w64(fresh && (!isfull || dist < worst));  // (the worst only shrinks)
+                    // ---- admission (:195-204): the fresh neighbours in adjacency order (lane j = neighbour slot j), each against the
+                    //      worst of `nearest` as the ones before it have left it
+                    const bool isfull = L.full();
+                    uint64_t smask = __builtin_amdgcn_ballot_w64(fresh && (!isfull || dist < L.worst));  // (the worst only shrinks)
 #ifdef HG_SOLO_STAMPS
                     if (level == 0 && smask) {
                         dg[isfull ? 0 : 1]++;
                         dg[isfull ? 2 : 3] += __popcll(smask);
                     }
 #endif
-                    // ONE survivor (lane j): straight into its place
-                    auto admit_one = [&](int j) {
-                        const uint32_t djb = static_cast<uint32_t>(__builtin_amdgcn_readlane(__float_as_int(dist), j));
-                        const uint32_t idj = static_cast<uint32_t>(__builtin_amdgcn_readlane(nb_id, j));
-                        if (pm + pb >= ef_l && fkey(djb) >= worst_k) return;  // (:195-198, a strict <)
-                        // behind the buffer entries <= it (ties: admission order; lanes >= nb hold +inf)
-                        const float dj = __uint_as_float(djb);
-                        const int r0 = __popcll(__builtin_amdgcn_ballot_w64(bd <= dj));
-                        const int r = r0 < nb ? r0 : nb;  // (an infinite distance: behind everything)
-                        const float sd = __uint_as_float(wave_shr1(__float_as_uint(bd)));
-                        const uint32_t si = wave_shr1(bi);
-                        bd = lane > r ? sd : (lane == r ? dj : bd);
-                        bi = lane > r ? si : (lane == r ? idj : bi);
-                        const uint64_t lowm = (1ull << r) - 1ull;
-                        bun = (bun & lowm) | ((bun & ~lowm) << 1) | (1ull << r);
-                        nb++;
-                        pb++;
-                        // (:203-204) if `nearest` now holds ef + 1, its worst leaves it: the later of the two tails (a tie: the
-                        // buffer's, it is the younger).  Straight-line: integer selects on the keys, no branch.
-                        {
-                            const int over = pm + pb > ef_l ? 1 : 0;
-                            const int im = pm - 1 - tbase;
-                            const uint32_t wmb = static_cast<uint32_t>(__builtin_amdgcn_readlane(__float_as_int(td), im > 0 ? im : 0));
-                            const uint32_t wbb = static_cast<uint32_t>(__builtin_amdgcn_readlane(__float_as_int(bd), pb - 1));
-                            const int evm = (over && pm > 0 && fkey(wmb) > fkey(wbb)) ? 1 : 0;
-                            pm -= evm;
-                            pb -= over - evm;
-                        }
-                        top_worst();
-                        dirty = true;
-                    };
-                    // (63 admissions at most between two merges: the buffer has 64 lanes, and the tail window of 64 main entries shows
-                    // main[pm - 1] through 63 evictions.  64 survivors at once -- 64 layer-0 slots, all fresh -- could push 64 main
-                    // entries out: pm would arrive at tbase and the window's lane 0 be main[pm], an entry that has LEFT `nearest`, read
-                    // as its worst.  So the first of them goes alone and the window is loaded again behind it; the other 63 follow
-                    // together, and the buffer then holds 64)
                     SOLO_STAMP(5);
-                    if (smask && nb + __popcll(smask) > kWave - 1) {
-                        compact();
-                        top_worst();
-                        if (smask == ~0ull) {
-                            admit_one(0);
-                            load_tail();
-                            smask &= smask - 1;
-                        }
-                    }
+                    if (smask) L.make_room(smask, dist, static_cast<uint32_t>(nb_id));
                     SOLO_STAMP(6);
-                    if (smask & (smask - 1)) {
-                        // ---- two or more survivors: all of them at once.  One pass in adjacency order decides every admission
-                        //      exactly as the sequential loop would -- a survivor is admitted iff fewer than ef of {`nearest` as the
-                        //      expansion found it, the survivors before it} are <= it (the entries those have pushed out of
-                        //      `nearest` meanwhile were larger than it anyway) -- and collects the merge counts; the admitted ones
-                        //      then enter the buffer together (a scatter through its LDS mirror), and what they push out of `nearest`
-                        //      (:203-204) is the nev largest of its two tails, found by all lanes at once (a merge-path split).
-                        int before = 0, arank = 0, cball = 0, shb = 0;
-                        uint64_t am = 0;
-                        const bool tvalid = tbase + lane < pm;
-#pragma unroll 1
-                        for (uint64_t mm = smask; mm; mm &= mm - 1) {
-                            const int sv = __ffsll(static_cast<unsigned long long>(mm)) - 1;
-                            const float ds = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(dist), sv));
-                            const int cb = __popcll(__builtin_amdgcn_ballot_w64(lane < pb && bd <= ds));
-                            const int cw = __popcll(__builtin_amdgcn_ballot_w64(tvalid && td <= ds));
-                            const int bs = __builtin_amdgcn_readlane(before, sv);
-                            // (smaller than every main entry the tail window shows, and the window does not start at 0: at most
-                            // ef - 64 main + buffer entries are <= it, and fewer than 64 survivors precede it)
-                            const int tm = (cw == 0 && tbase > 0) ? 0 : tbase + cw;
-                            const bool adm = tm + cb + bs < ef_l;
-                            before += (lane > sv && ds <= dist) ? 1 : 0;
-                            if (adm) {
-                                am |= 1ull << sv;
-                                shb += (ds < bd) ? 1 : 0;
-                                arank += (ds < dist || (ds == dist && sv < lane)) ? 1 : 0;
-                                cball = lane == sv ? cb : cball;
-                            }
-                        }
-                        const int nadm = __popcll(am);
-                        if (nadm) {
-                            const bool isadm = (am >> lane) & 1ull;
-                            if (lane < nb) {
-                                bm[lane + shb].x = __float_as_uint(bd);
-                                bm[lane + shb].y = bi;
-                            }
-                            if (isadm) {
-                                bm[cball + arank].x = __float_as_uint(dist);
-                                bm[cball + arank].y = static_cast<uint32_t>(nb_id);
-                            }
-                            nb += nadm;
-                            {
-                                const uint32_t ex = bm[lane].x, ey = bm[lane].y;
-                                bd = lane < nb ? __uint_as_float(ex) : __uint_as_float(0x7f800000u);
-                                bi = lane < nb ? ey : kExpanded;
-                            }
-                            bun = __builtin_amdgcn_ballot_w64(lane < nb && !(bi & kExpanded));
-                            const int pbn = pb + nadm;
-                            const int nev = pm + pbn > ef_l ? pm + pbn - ef_l : 0;
-                            if (nev) {
-                                // lane e: e entries leave the main list's tail, nev - e the buffer's.  Right iff what stays is
-                                // before what leaves: main entries are the older ones (a tie: the buffer entry leaves)
-                                const int e = lane, eb = nev - lane;
-                                const bool feas = e <= nev && e <= pm && eb <= pbn;
-                                const int i_mk = pm - e - 1, i_me = pm - e, i_bk = pbn - eb - 1, i_be = pbn - eb;
-                                const float m_keep = __uint_as_float(curA[i_mk > 0 ? i_mk : 0].x);
-                                const float m_ev = __uint_as_float(curA[(feas && e > 0) ? i_me : 0].x);
-                                const float b_keep = __uint_as_float(bm[(feas && i_bk > 0) ? i_bk : 0].x);
-                                const float b_ev = __uint_as_float(bm[(feas && eb > 0) ? i_be : 0].x);
-                                const bool ca = i_mk < 0 || eb == 0 || m_keep <= b_ev;
-                                const bool cb2 = i_bk < 0 || e == 0 || b_keep < m_ev;
-                                const uint64_t okm = __builtin_amdgcn_ballot_w64(feas && ca && cb2);
-                                int em = okm ? __ffsll(static_cast<unsigned long long>(okm)) - 1 : -1;
-                                if (em < 0) {  // (cannot happen for comparable distances; NaNs: one at a time, the sequential rule)
-                                    em = 0;
-                                    int pmm = pm, pbb = pbn;
-                                    for (int t = 0; t < nev; t++) {
-                                        const uint32_t wmb = pmm > 0 ? curA[pmm - 1].x : 0u;
-                                        const uint32_t wbb = pbb > 0 ? bm[pbb - 1].x : 0u;
-                                        if (pmm > 0 && (pbb == 0 || fkey(wmb) > fkey(wbb))) {
-                                            pmm--;
-                                            em++;
-                                        } else {
-                                            pbb--;
-                                        }
-                                    }
-                                }
-                                pm -= em;
-                                pb = pbn - (nev - em);
-                            } else {
-                                pb = pbn;
-                            }
-                            top_worst();
-                            dirty_sc = true;  // (the mirror IS the buffer now)
-                        }
-                    }
-                    if (smask && (smask & (smask - 1)) == 0) admit_one(__ffsll(static_cast<unsigned long long>(smask)) - 1);
+                    if (smask) L.admit(smask, dist, static_cast<uint32_t>(nb_id));
                     SOLO_STAMP(7);
-                    if (dirty) Ls.bmir[lane] = make_uint2(__float_as_uint(bd), bi);  // the fetchers see the buffer through its mirror
-                    if (dirty || dirty_sc) {
-                        if (lane == 0) {  // (plain stores: hints, and the LDS takes a wave's stores in order)
-                            Ls.sc[3] = nb;
-                            Ls.sc[1] = lm;
-                            Ls.sc[0] = fun ? fbase + __ffsll(static_cast<unsigned long long>(fun)) - 1 : fbase + kWave;
-                        }
-                        asm volatile("" ::: "memory");
-                        dirty = false;
-                        dirty_sc = false;
-                    }
+                    L.publish();
                     SOLO_STAMP(8);
                 }
-                compact();
+                len = L.end_level();
+                over = over || L.overflow;
+                h_compact += L.merges;
                 if (lane == 0) {
                     sc[13] = level + 1;             // the assistant may go ...
                     if (level == 0) sc[2] = 1;      // ... and the fetchers
@@ -1005,14 +711,14 @@ __global__ __launch_bounds__(kWG) void hnsw_solo_kernel(HnswArgs a) {
         // ---- results: ascending, take k (:362-370; the distances are reused, not recomputed)
         if (wave == 0) {
             if (lane == 0) coherent_store(mail + 2, a.pf_seq);  // the helpers may go
-            const int real = lm < a.ef ? lm : a.ef;
+            const int real = len < a.ef ? len : a.ef;
             for (int i = lane; i < a.k; i += kWave) {
                 const bool ok = i < real;
                 a.out_ids[static_cast<int64_t>(qi) * a.k + i] = ok ? static_cast<int32_t>(curA[i].y & ~kExpanded) : -1;
                 a.out_dist[static_cast<int64_t>(qi) * a.k + i] = ok ? __uint_as_float(curA[i].x) : __uint_as_float(0x7f800000u);
             }
             if (lane == 0) {
-                if (a.again && sc[6]) a.again[atomicAdd(a.again_cnt, 1)] = qi;
+                if (a.again && over) a.again[atomicAdd(a.again_cnt, 1)] = qi;
                 if (a.stats) {
                     a.stats[2 * static_cast<int64_t>(qi)] = n_eval;
                     a.stats[2 * static_cast<int64_t>(qi) + 1] = n_hop;

@@ -3,7 +3,7 @@ plain restatement of search-layer-ultra that says which states a graph reaches.
 
 The parity tests search graphs a builder made from clustered or gaussian rows: an expansion finds a few fresh neighbours, one
 or two are admitted, the list moves a step at a time.  The wave and several-CU kernels keep that list as a main list in LDS, an
-admission buffer in registers and a 64-entry tail window (wave_kernels.hpp: WaveList); its hard states -- 64 fresh neighbours
+admission buffer in registers and a 64-entry tail window (hnsw_list.hpp: HnswList); its hard states -- 64 fresh neighbours
 all admitted, evictions that empty the tail window, evictions split between the two tails on a tie, a forced merge followed
 by a multi-admit, a fan-out wider than the list -- are reached here on purpose.
 

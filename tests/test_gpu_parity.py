@@ -625,7 +625,7 @@ def test_helpers_evaluate_small_launches(eng, oracle, tune, metric, dim, M, solo
     """Launches of a handful of queries: helper workgroups on idle CUs evaluate the neighbours of the candidates the
     traversal will expand next and publish the distances; the traversal gathers only what has not arrived.  solo = 2: one
     query over several CUs at every ef (solo_kernels.hpp: an owner workgroup keeps the reference's order -- its sequencer
-    wave holds the list as main list + admission buffer --, its fetcher waves copy published distances into an LDS cache,
+    wave holds the list as main list + admission buffer, hnsw_list.hpp --, its fetcher waves copy published distances into an LDS cache,
     the helpers evaluate and chase); 0: the round-2 helper kernel (kernels.hpp: pf_res); 1: the default rule (from ef 200).
     Timing decides WHICH distances arrive, never what they are: ids, distance bits and both counters equal the oracle's for
     1 / 3 / 20 / 64 queries, several times over, and the device counters show that published distances were used (the int8
@@ -661,7 +661,7 @@ def test_helpers_evaluate_small_launches(eng, oracle, tune, metric, dim, M, solo
 @pytest.mark.parametrize("metric,dim,M", [("cosine", 136, 16), ("l2", 72, 16), ("dot", 300, 32), ("cosine", 768, 8)])
 def test_wave_kernel_against_oracle(eng, oracle, tune, metric, dim, M, vis_global):
     """Large launches run one wave per query on a main list + a register-resident admission buffer (wave_kernels.hpp: the
-    list of solo_kernels.hpp's sequencer) instead of the single-workgroup kernel's positional merge; search-layer-ultra,
+    list of hnsw_list.hpp, solo_kernels.hpp's sequencer keeps the same) instead of the single-workgroup kernel's positional merge; search-layer-ultra,
     ultra_fast.clj:151-212.  Forced here for batches of 130 and 600 queries (HNSW_WAVE = 2; by default launches that fill the
     chip take it: test_timed_launch_configurations_against_oracle, test_full_size_31k_properties), with the int8 rejection
     test on and off, the visited set in LDS and in HBM stamps, duplicated rows (hundreds of exact ties at the list's worst:

@@ -1,7 +1,8 @@
 """Scripted graphs through every HNSW traversal kernel (tests/scripted_graphs.py has the graphs and says which state of the
 candidate list each one reaches; tests/test_scripted_graph_traces.py proves on the CPU that it does).
 
-The wave kernel and the several-CU kernel keep the list as main list + admission buffer + 64-entry tail window, the
+The wave kernel and the several-CU kernel keep the list as main list + admission buffer + 64-entry tail window (ONE
+implementation, hnsw_list.hpp: HnswList, with and without the mirror the several-CU kernel's fetchers read), the
 single-workgroup kernel and the round-2 helper kernel merge by position: each runs scenario S (a full fan-out of 64 fresh
 neighbours that are all admitted and push 64 main entries out -- the tail window is empty afterwards -- followed by a stop that
 depends on the right worst), its ef variants, S-tie, S-tie-many (64 evicted entries that all tie the worst, twice the ghost
