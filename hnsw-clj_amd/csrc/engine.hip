@@ -1255,22 +1255,45 @@ int scan_dense_topk(hnswgpu_index *idx, ScanArgs a, int32_t nq, int64_t nrows, h
     return launch_select(s, st);
 }
 
-int begin_call(hnswgpu_index *idx, hipStream_t st) {
+int Call::open(hnswgpu_index *idx, hipStream_t st) {
+    lk_ = std::unique_lock<std::mutex>(idx->mu);
+    HG_HIP(hipSetDevice(idx->device));
     if (idx->ev_valid && idx->ev_stream != st) HG_HIP(hipStreamWaitEvent(st, idx->ev_last, 0));
+    idx_ = idx;
+    st_ = st;
     return 0;
 }
-int quiesce(hnswgpu_index *idx, hipStream_t st) {
-    HG_TRY(begin_call(idx, st));
-    HG_HIP(hipStreamSynchronize(st));
-    for (auto &sl : idx->slots)
+int Call::quiesce() {
+    HG_HIP(hipStreamSynchronize(st_));
+    for (auto &sl : idx_->slots)
         if (sl.st) HG_HIP(hipStreamSynchronize(sl.st));
     return 0;
 }
-int end_call(hnswgpu_index *idx, hipStream_t st) {
-    if (!idx->ev_last) HG_HIP(hipEventCreateWithFlags(&idx->ev_last, hipEventDisableTiming));
-    HG_HIP(hipEventRecord(idx->ev_last, st));
-    idx->ev_stream = st;
-    idx->ev_valid = true;
+int Call::sync() {
+    HG_HIP(hipStreamSynchronize(st_));
+    idle_ = true;
+    return 0;
+}
+hipError_t Call::leave() {
+    hnswgpu_index *idx = idx_;
+    idx_ = nullptr;
+    if (idle_) {
+        idx->ev_valid = false;
+        return hipSuccess;
+    }
+    hipError_t e = idx->ev_last ? hipSuccess : hipEventCreateWithFlags(&idx->ev_last, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventRecord(idx->ev_last, st_);
+    if (e == hipSuccess) {
+        idx->ev_stream = st_;
+        idx->ev_valid = true;
+    } else if (hipStreamSynchronize(st_) == hipSuccess) {  // no event to wait for: nothing left in flight instead
+        idx->ev_valid = false;
+    }
+    return e;
+}
+int Call::close() {
+    const hipError_t e = leave();
+    HG_REQUIRE(e == hipSuccess, HNSWGPU_EHIP, "hipEventRecord behind a call failed: %s", hipGetErrorString(e));
     return 0;
 }
 
@@ -1321,7 +1344,8 @@ static double now_us() {
     return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-int slot_prepare(hnswgpu_index::Slot &s, size_t bytes) {
+int slot_prepare(hnswgpu_index::Slot &s, size_t bytes, int device) {
+    if (!s.d_again || bytes > s.cap) HG_HIP(hipSetDevice(device));
     if (!s.st) HG_HIP(hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
     if (!s.d_again) {
         HG_HIP(hipMalloc(reinterpret_cast<void **>(&s.d_again), sizeof(int32_t) * (kZcMaxQueries + 1)));
@@ -1358,6 +1382,46 @@ int slot_wait(hnswgpu_index::Slot &s, volatile uint32_t *flag, uint32_t seq) {
     HG_HIP(hipStreamSynchronize(s.st));  // surfaces a kernel fault; a healthy launch has set the flag by now
     HG_REQUIRE(__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq, HNSWGPU_EHIP, "search kernel finished without publishing its results");
     return 0;
+}
+
+BatchBlock::BatchBlock(int32_t dim_, int32_t total, int32_t k_, bool stats) : k(k_), dim(dim_) {
+    const auto up = [](size_t v) { return (v + 63) & ~size_t(63); };
+    const size_t cnt = static_cast<size_t>(total) * k;
+    o_q = 64;
+    o_i = up(o_q + sizeof(float) * static_cast<size_t>(total) * dim);
+    o_s = stats ? o_i : 0;
+    if (stats) o_i = up(o_s + sizeof(int64_t) * 2 * total);
+    o_d = up(o_i + sizeof(int32_t) * cnt);
+    bytes = o_d + sizeof(float) * cnt;
+}
+void BatchBlock::pack(void *host, const std::vector<hnswgpu_index::SearchReq *> &batch) const {
+    float *hq = queries(host);
+    for (auto *r : batch) {
+        const size_t c = static_cast<size_t>(r->nq) * dim;
+        memcpy(hq, r->Q, sizeof(float) * c);
+        hq += c;
+    }
+}
+void BatchBlock::scatter(void *host, const std::vector<hnswgpu_index::SearchReq *> &batch) const {
+    const int32_t *hi = ids(host);
+    const float *hd = dist(host);
+    const int64_t *hs = stats(host);
+    int64_t q0 = 0;
+    for (auto *r : batch) {
+        const size_t c = static_cast<size_t>(r->nq) * k;
+        memcpy(r->out_ids, hi + q0 * k, sizeof(int32_t) * c);
+        memcpy(r->out_dist, hd + q0 * k, sizeof(float) * c);
+        if (hs && r->stats) memcpy(r->stats, hs + 2 * q0, sizeof(int64_t) * 2 * r->nq);
+        q0 += r->nq;
+    }
+}
+hnswgpu_index::Slot *BatchBlock::acquire_slot(hnswgpu_index *idx, std::unique_lock<std::mutex> &lk) {
+    for (auto &s : idx->slots) {
+        lk = std::unique_lock<std::mutex>(s.mu, std::try_to_lock);
+        if (lk.owns_lock()) return &s;
+    }
+    lk = std::unique_lock<std::mutex>(idx->slots[0].mu);
+    return &idx->slots[0];
 }
 
 // Serve `me` through combiner `c`.  At any time at most ONE thread is the collector: it waits a moment for the callers
@@ -1751,6 +1815,23 @@ int upload_queries(hnswgpu_index *idx, const float *Q, int32_t nq, hipStream_t s
     return 0;
 }
 
+int Call::stage_in(const float *Q, int32_t nq, int32_t k) {
+    HG_TRY(upload_queries(idx_, Q, nq, st_));
+    HG_TRY(idx_->s_ids.ensure(sizeof(int32_t) * static_cast<size_t>(nq) * k));
+    return idx_->s_outd.ensure(sizeof(float) * static_cast<size_t>(nq) * k);
+}
+int Call::stage_out(int32_t *out_ids, float *out_dist, int64_t cnt) {
+    HG_HIP(hipMemcpyAsync(out_ids, idx_->s_ids.p, sizeof(int32_t) * cnt, hipMemcpyDeviceToHost, st_));
+    HG_HIP(hipMemcpyAsync(out_dist, idx_->s_outd.p, sizeof(float) * cnt, hipMemcpyDeviceToHost, st_));
+    return sync();
+}
+void fill_empty(int32_t *ids, float *dist, int64_t cnt) {
+    for (int64_t i = 0; i < cnt; i++) {
+        ids[i] = -1;
+        dist[i] = __builtin_inff();
+    }
+}
+
 __global__ void ord_to_ids_kernel(const uint32_t *ord, int64_t cnt, int32_t *ids) {
     int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i < cnt) ids[i] = ord[i] == 0xffffffffu ? -1 : static_cast<int32_t>(ord[i]);
@@ -2023,10 +2104,9 @@ int hnswgpu_batch_distances(hnswgpu_index *idx, const float *q, const int32_t *i
     HG_REQUIRE(m >= 0, HNSWGPU_EINVAL, "m < 0");
     if (m == 0) return 0;
     HG_REQUIRE(ids || m <= idx->n, HNSWGPU_EINVAL, "m > n with implicit ids");
-    std::lock_guard<std::mutex> lk(idx->mu);
-    HG_HIP(hipSetDevice(idx->device));
     hipStream_t st = idx->stream;
-    HG_TRY(begin_call(idx, st));
+    Call call;
+    HG_TRY(call.open(idx, st));
     HG_TRY(upload_queries(idx, q, 1, st));
     HG_TRY(idx->s_outd.ensure(sizeof(float) * m));
     GatherArgs g;
@@ -2048,19 +2128,18 @@ int hnswgpu_batch_distances(hnswgpu_index *idx, const float *q, const int32_t *i
     g.out = idx->s_outd.as<float>();
     HG_TRY(launch_gather(idx->nch, g, 1, st));
     HG_HIP(hipMemcpyAsync(out, g.out, sizeof(float) * m, hipMemcpyDeviceToHost, st));
-    HG_TRY(end_call(idx, st));
-    HG_HIP(hipStreamSynchronize(st));
-    return 0;
+    HG_TRY(call.sync());
+    return call.close();
 }
 
 int hnswgpu_norms(hnswgpu_index *idx, float *out_norms) {
     HG_REQUIRE(idx && (out_norms || idx->n == 0), HNSWGPU_EINVAL, "null argument");
     if (idx->n == 0) return 0;
-    std::lock_guard<std::mutex> lk(idx->mu);
-    HG_HIP(hipSetDevice(idx->device));
+    Call call;
+    HG_TRY(call.open(idx, idx->stream));
     HG_HIP(hipMemcpyAsync(out_norms, idx->d_norms, sizeof(float) * idx->n, hipMemcpyDeviceToHost, idx->stream));
-    HG_HIP(hipStreamSynchronize(idx->stream));
-    return 0;
+    HG_TRY(call.sync());
+    return call.close();
 }
 
 static int exact_knn_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t *d_ids,
@@ -2110,24 +2189,16 @@ static int check_search_args(const hnswgpu_index *idx, const void *Q, int32_t nq
     return 0;
 }
 
-static void fill_empty(int32_t *ids, float *dist, int64_t cnt) {
-    for (int64_t i = 0; i < cnt; i++) {
-        ids[i] = -1;
-        dist[i] = __builtin_inff();
-    }
-}
-
 int hnswgpu_exact_knn_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t *d_out_ids,
                           float *d_out_dist, void *stream) {
     HG_TRY(check_search_args(idx, d_Q, nq, k, d_out_ids, d_out_dist));
     if (nq == 0) return 0;
     HG_REQUIRE(idx->n > 0, HNSWGPU_ESTATE, "empty index: use the host entry point");
-    std::lock_guard<std::mutex> lk(idx->mu);
-    HG_HIP(hipSetDevice(idx->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    HG_TRY(begin_call(idx, st));
+    Call call;
+    HG_TRY(call.open(idx, st));
     HG_TRY(exact_knn_enqueue(idx, d_Q, nq, k, d_out_ids, d_out_dist, st));
-    return end_call(idx, st);
+    return call.close();
 }
 
 int hnswgpu_exact_knn(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t *out_ids,
@@ -2139,19 +2210,13 @@ int hnswgpu_exact_knn(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k,
         fill_empty(out_ids, out_dist, cnt);
         return 0;
     }
-    std::lock_guard<std::mutex> lk(idx->mu);
-    HG_HIP(hipSetDevice(idx->device));
     hipStream_t st = idx->stream;
-    HG_TRY(begin_call(idx, st));
-    HG_TRY(upload_queries(idx, Q, nq, st));
-    HG_TRY(idx->s_ids.ensure(sizeof(int32_t) * cnt));
-    HG_TRY(idx->s_outd.ensure(sizeof(float) * cnt));
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_TRY(call.stage_in(Q, nq, k));
     HG_TRY(exact_knn_enqueue(idx, idx->s_q.as<float>(), nq, k, idx->s_ids.as<int32_t>(), idx->s_outd.as<float>(), st));
-    HG_HIP(hipMemcpyAsync(out_ids, idx->s_ids.p, sizeof(int32_t) * cnt, hipMemcpyDeviceToHost, st));
-    HG_HIP(hipMemcpyAsync(out_dist, idx->s_outd.p, sizeof(float) * cnt, hipMemcpyDeviceToHost, st));
-    HG_TRY(end_call(idx, st));
-    HG_HIP(hipStreamSynchronize(st));
-    return 0;
+    HG_TRY(call.stage_out(out_ids, out_dist, cnt));
+    return call.close();
 }
 
 int hnswgpu_merge_lists_dev(int32_t device, const int32_t *d_ids, const float *d_dist, int32_t nshard, int32_t nq,
@@ -2246,12 +2311,11 @@ int hnswgpu_rerank_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, const i
     HG_TRY(check_rerank_args(idx, d_Q, nq, d_cand, m, k, d_out_ids, d_out_dist));
     if (nq == 0) return 0;
     HG_REQUIRE(idx->n > 0, HNSWGPU_ESTATE, "empty index: use the host entry point");
-    std::lock_guard<std::mutex> lk(idx->mu);
-    HG_HIP(hipSetDevice(idx->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    HG_TRY(begin_call(idx, st));
+    Call call;
+    HG_TRY(call.open(idx, st));
     HG_TRY(rerank_enqueue(idx, d_Q, nq, d_cand, m, k, d_out_ids, d_out_dist, st));
-    return end_call(idx, st);
+    return call.close();
 }
 
 int hnswgpu_rerank(hnswgpu_index *idx, const float *Q, int32_t nq, const int32_t *cand, int32_t m, int32_t k,
@@ -2263,23 +2327,17 @@ int hnswgpu_rerank(hnswgpu_index *idx, const float *Q, int32_t nq, const int32_t
         fill_empty(out_ids, out_dist, cnt);
         return 0;
     }
-    std::lock_guard<std::mutex> lk(idx->mu);
-    HG_HIP(hipSetDevice(idx->device));
     hipStream_t st = idx->stream;
-    HG_TRY(begin_call(idx, st));
-    HG_TRY(upload_queries(idx, Q, nq, st));
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_TRY(call.stage_in(Q, nq, k));
     const size_t cbytes = sizeof(int32_t) * static_cast<size_t>(nq) * m;
     HG_TRY(idx->s_misc.ensure(cbytes));
     HG_HIP(hipMemcpyAsync(idx->s_misc.p, cand, cbytes, hipMemcpyHostToDevice, st));
-    HG_TRY(idx->s_ids.ensure(sizeof(int32_t) * cnt));
-    HG_TRY(idx->s_outd.ensure(sizeof(float) * cnt));
     HG_TRY(rerank_enqueue(idx, idx->s_q.as<float>(), nq, idx->s_misc.as<int32_t>(), m, k, idx->s_ids.as<int32_t>(),
                           idx->s_outd.as<float>(), st));
-    HG_HIP(hipMemcpyAsync(out_ids, idx->s_ids.p, sizeof(int32_t) * cnt, hipMemcpyDeviceToHost, st));
-    HG_HIP(hipMemcpyAsync(out_dist, idx->s_outd.p, sizeof(float) * cnt, hipMemcpyDeviceToHost, st));
-    HG_TRY(end_call(idx, st));
-    HG_HIP(hipStreamSynchronize(st));
-    return 0;
+    HG_TRY(call.stage_out(out_ids, out_dist, cnt));
+    return call.close();
 }
 
 // ---- dense distances: every query against every row (batch-cosine-distances over a query batch) ----
@@ -2339,29 +2397,26 @@ static int check_dense_args(const hnswgpu_index *idx, const void *Q, int32_t nq,
 int hnswgpu_dense_distances_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, float *d_out, void *stream) {
     HG_TRY(check_dense_args(idx, d_Q, nq, d_out));
     if (nq == 0 || idx->n == 0) return 0;
-    std::lock_guard<std::mutex> lk(idx->mu);
-    HG_HIP(hipSetDevice(idx->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    HG_TRY(begin_call(idx, st));
+    Call call;
+    HG_TRY(call.open(idx, st));
     HG_TRY(dense_enqueue(idx, d_Q, nq, d_out, st));
-    return end_call(idx, st);
+    return call.close();
 }
 
 int hnswgpu_dense_distances(hnswgpu_index *idx, const float *Q, int32_t nq, float *out) {
     HG_TRY(check_dense_args(idx, Q, nq, out));
     if (nq == 0 || idx->n == 0) return 0;
-    std::lock_guard<std::mutex> lk(idx->mu);
-    HG_HIP(hipSetDevice(idx->device));
     hipStream_t st = idx->stream;
-    HG_TRY(begin_call(idx, st));
+    Call call;
+    HG_TRY(call.open(idx, st));
     HG_TRY(upload_queries(idx, Q, nq, st));
     const size_t bytes = sizeof(float) * static_cast<size_t>(nq) * idx->n;
     HG_TRY(idx->s_tile.ensure(bytes));
     HG_TRY(dense_enqueue(idx, idx->s_q.as<float>(), nq, idx->s_tile.as<float>(), st));
     HG_HIP(hipMemcpyAsync(out, idx->s_tile.p, bytes, hipMemcpyDeviceToHost, st));
-    HG_TRY(end_call(idx, st));
-    HG_HIP(hipStreamSynchronize(st));
-    return 0;
+    HG_TRY(call.sync());
+    return call.close();
 }
 
 // Measurement / test entries: the bounds of query q against rows ids[0..m) from the int8 rows, by the searches' own device
@@ -2371,10 +2426,9 @@ static int code_bounds_call(hnswgpu_index *idx, const float *q, const int32_t *i
                             bool q16) {
     HG_REQUIRE(idx && q && ids && out && m >= 1, HNSWGPU_EINVAL, "null argument");
     for (int32_t i = 0; i < m; i++) HG_REQUIRE(ids[i] >= 0 && ids[i] < idx->n, HNSWGPU_EINVAL, "id out of range");
-    std::lock_guard<std::mutex> lk(idx->mu);
-    HG_HIP(hipSetDevice(idx->device));
     hipStream_t st = idx->stream;
-    HG_TRY(begin_call(idx, st));
+    Call call;
+    HG_TRY(call.open(idx, st));
     HG_TRY(ensure_qrows(idx, st));
     HG_REQUIRE(idx->d_qrows, HNSWGPU_EINVAL,
                "this handle has no int8 rows (hnswgpu_set_rejection_test: mode 0, or mode 1 with dim < 128)");
@@ -2395,9 +2449,8 @@ static int code_bounds_call(hnswgpu_index *idx, const float *q, const int32_t *i
     HG_HIP(hipGetLastError());
     HG_HIP(hipMemcpyAsync(out, idx->s_outd.p, sizeof(float) * m, hipMemcpyDeviceToHost, st));
     if (out_ub) HG_HIP(hipMemcpyAsync(out_ub, d_ub, sizeof(float) * m, hipMemcpyDeviceToHost, st));
-    HG_TRY(end_call(idx, st));
-    HG_HIP(hipStreamSynchronize(st));
-    return 0;
+    HG_TRY(call.sync());
+    return call.close();
 }
 
 int hnswgpu_rejection_bounds(hnswgpu_index *idx, const float *q, const int32_t *ids, int32_t m, float *out) {
@@ -2419,11 +2472,10 @@ int hnswgpu_ivf_half_bounds(hnswgpu_index *idx, const float *q, const int32_t *l
                             float *out_ub) {
     HG_REQUIRE(idx && q && list_rows && out_lb && out_ub && m >= 1, HNSWGPU_EINVAL, "null argument");
     for (int32_t i = 0; i < m; i++) HG_REQUIRE(list_rows[i] >= 0 && list_rows[i] < idx->n, HNSWGPU_EINVAL, "row out of range");
-    std::lock_guard<std::mutex> lk(idx->mu);
-    HG_HIP(hipSetDevice(idx->device));
-    HG_REQUIRE(idx->d_lhalf, HNSWGPU_EINVAL, "this handle has no half-precision list rows (no lists, no int8 rows, or HNSWGPU_IVF_HALF=0)");
     hipStream_t st = idx->stream;
-    HG_TRY(begin_call(idx, st));
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_REQUIRE(idx->d_lhalf, HNSWGPU_EINVAL, "this handle has no half-precision list rows (no lists, no int8 rows, or HNSWGPU_IVF_HALF=0)");
     HG_TRY(upload_queries(idx, q, 1, st));
     HG_TRY(idx->s_tile.ensure(sizeof(uint4) * static_cast<size_t>(m) + sizeof(uint32_t)));
     std::vector<uint4> ent(m);
@@ -2449,13 +2501,12 @@ int hnswgpu_ivf_half_bounds(hnswgpu_index *idx, const float *q, const int32_t *l
     a.metric = idx->metric;
     HG_TRY(launch_mid(a, idx->nch, st));
     HG_HIP(hipMemcpyAsync(ent.data(), idx->s_tile.p, sizeof(uint4) * m, hipMemcpyDeviceToHost, st));
-    HG_TRY(end_call(idx, st));
-    HG_HIP(hipStreamSynchronize(st));
+    HG_TRY(call.sync());
     for (int32_t i = 0; i < m; i++) {
         memcpy(out_lb + i, &ent[i].z, sizeof(float));
         memcpy(out_ub + i, &ent[i].w, sizeof(float));
     }
-    return 0;
+    return call.close();
 }
 
 // Diagnostic / test entry: the matrix-core half-precision bounds (stream_kernels.hpp, step 1a: ivf_home_kernel) of the
@@ -2464,15 +2515,14 @@ int hnswgpu_ivf_half_bounds(hnswgpu_index *idx, const float *q, const int32_t *l
 int hnswgpu_ivf_home_bounds(hnswgpu_index *idx, const float *Q, int32_t nq, int64_t row_begin, int64_t row_end, float *out_lb,
                             float *out_ub) {
     HG_REQUIRE(idx && Q && out_lb && out_ub && nq >= 1, HNSWGPU_EINVAL, "null argument");
-    std::lock_guard<std::mutex> lk(idx->mu);
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
     // (under the lock: hnswgpu_hnsw_add grows idx->n)
     HG_REQUIRE(row_begin >= 0 && row_begin < row_end && row_end <= idx->n && row_end - row_begin < (1 << 24), HNSWGPU_EINVAL, "row range");
-    HG_HIP(hipSetDevice(idx->device));
     try {  // (the work lists and the staging below are host vectors: no exception crosses the C boundary)
     HG_REQUIRE(idx->d_lhalf, HNSWGPU_EINVAL, "this handle has no half-precision list rows (no lists, no int8 rows, or HNSWGPU_IVF_HALF=0)");
     HG_REQUIRE(idx->ld % 128 == 0, HNSWGPU_EINVAL, "the home-list pass serves rows of whole 128-element steps");
-    hipStream_t st = idx->stream;
-    HG_TRY(begin_call(idx, st));
     HG_TRY(upload_queries(idx, Q, nq, st));
     const int64_t len = row_end - row_begin, hstride = (len + 15) / 16 * 16;
     const int gq = home_group(idx->nch);
@@ -2518,14 +2568,13 @@ int hnswgpu_ivf_home_bounds(hnswgpu_index *idx, const float *Q, int32_t nq, int6
     HG_TRY(launch_home(a, nit, idx->nch, st));
     std::vector<float2> host(static_cast<size_t>(nq) * hstride);
     HG_HIP(hipMemcpyAsync(host.data(), a.dh, sizeof(float2) * host.size(), hipMemcpyDeviceToHost, st));
-    HG_TRY(end_call(idx, st));
-    HG_HIP(hipStreamSynchronize(st));
+    HG_TRY(call.sync());
     for (int32_t i = 0; i < nq; i++)
         for (int64_t r = 0; r < len; r++) {
             out_lb[i * len + r] = host[i * hstride + r].x;
             out_ub[i * len + r] = host[i * hstride + r].y;
         }
-    return 0;
+    return call.close();
     } catch (const std::bad_alloc &) {
         set_error("host allocation failed in hnswgpu_ivf_home_bounds");
         return HNSWGPU_ENOMEM;
@@ -2535,23 +2584,21 @@ int hnswgpu_ivf_home_bounds(hnswgpu_index *idx, const float *Q, int32_t nq, int6
 int hnswgpu_set_rejection_test(hnswgpu_index *idx, int32_t mode) {
     HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
     HG_REQUIRE(mode >= 0 && mode <= 2, HNSWGPU_EINVAL, "mode must be 0 (off), 1 (large batches) or 2 (always)");
-    std::lock_guard<std::mutex> lk(idx->mu);
-    HG_HIP(hipSetDevice(idx->device));
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
     idx->rejection_mode = mode;
     // (mode 1 measures again at the next IVF search -- but not a SHARD of a larger index: its verdict is the whole index's
     // (hnswgpu_ivf_set_stream_state); measuring alone it could take another kernel path than its siblings, and the sharded
     // answer would no longer be the unsharded one bit for bit)
     if (idx->d_glistoff == nullptr) idx->ivf_calibrated = idx->ivf_stream_off = false;
     if (mode != 0 && (idx->has_graph || idx->nlist > 0)) {  // int8 rows now for what exists, else with the graph / lists
-        hipStream_t st = idx->stream;
-        HG_TRY(begin_call(idx, st));
         if (idx->has_graph) HG_TRY(ensure_qrows(idx, st));
         HG_TRY(ensure_list_codes(idx, st));
         HG_TRY(ensure_list_half(idx, st));
-        HG_TRY(end_call(idx, st));
-        HG_HIP(hipStreamSynchronize(st));
+        HG_TRY(call.sync());
     }
-    return 0;
+    return call.close();
 }
 
 int hnswgpu_hnsw_rejection_state(hnswgpu_index *idx, int32_t *state, int32_t *off, double *frac) {
@@ -2633,20 +2680,18 @@ int hnswgpu_get_profile(hnswgpu_index *idx, int32_t which, double *total_ms, int
 
 int hnswgpu_get_rejection_stats(hnswgpu_index *idx, int64_t *f32_rows, int64_t *neighbours, int32_t reset) {
     HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
-    std::lock_guard<std::mutex> lk(idx->mu);
-    HG_HIP(hipSetDevice(idx->device));
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));  // every earlier call on this handle, whatever its stream, is ordered before st
     unsigned long long v[2] = {0, 0};
     if (idx->d_rej_stats) {
-        hipStream_t st = idx->stream;
-        HG_TRY(begin_call(idx, st));  // every earlier call on this handle, whatever its stream, is ordered before st
         HG_HIP(hipMemcpyAsync(v, idx->d_rej_stats, sizeof(v), hipMemcpyDeviceToHost, st));
         if (reset) HG_HIP(hipMemsetAsync(idx->d_rej_stats, 0, sizeof(v), st));
-        HG_TRY(end_call(idx, st));
-        HG_HIP(hipStreamSynchronize(st));
+        HG_TRY(call.sync());
     }
     if (f32_rows) *f32_rows = static_cast<int64_t>(v[0]);
     if (neighbours) *neighbours = static_cast<int64_t>(v[1]);
-    return 0;
+    return call.close();
 }
 
 }  // extern "C"

@@ -158,11 +158,6 @@ struct hnswgpu_index {
         uint32_t seq = 0;              // value the flag takes when the current launch has finished
     };
     Slot slots[2];
-    // a small synchronous IVF call in flight (ivf.hip: ivf_search_batch_slot): the flag word its last kernel sets, taken by the
-    // finish kernel's launch when the search goes through it (zc_taken), by a one-thread launch behind the search otherwise
-    uint32_t *zc_flag = nullptr;
-    uint32_t zc_val = 0;
-    bool zc_taken = false;
     void *h_pin = nullptr;    // pinned host staging of a large combined batch (queries in, results out)
     size_t h_pin_cap = 0;
     // cross-stream ordering of the shared scratch buffers: the last call's completion event
@@ -325,7 +320,8 @@ int launch_merge(const MergeArgs &a, hipStream_t st);
 // says whether request r may join a batch that starts with `first` and already holds `total` queries; `run` launches
 // a batch and returns its error code.
 constexpr int kZcMaxQueries = 256;  // largest combined batch served through a Slot (one workgroup per query and CU)
-int slot_prepare(hnswgpu_index::Slot &s, size_t bytes);  // stream, counters, mapped block of at least `bytes`
+// stream, counters, mapped block of at least `bytes` (sets the device only where it has to allocate)
+int slot_prepare(hnswgpu_index::Slot &s, size_t bytes, int device);
 // Spin on the completion flag of a slot launch (value `seq`); falls back to hipStreamSynchronize if it does not show.
 int slot_wait(hnswgpu_index::Slot &s, volatile uint32_t *flag, uint32_t seq);
 int combine_search(hnswgpu_index::Combiner &c, hnswgpu_index::SearchReq &me,
@@ -335,8 +331,8 @@ int combine_search(hnswgpu_index::Combiner &c, hnswgpu_index::SearchReq &me,
 int ensure_pinned(hnswgpu_index *idx, size_t bytes);
 int scan_dense_topk(hnswgpu_index *idx, ScanArgs a, int32_t nq, int64_t nrows, hipStream_t st);
 // Everything one IVF search decides, computed once before its first launch (ivf.hip: ivf_search_plan, where every rule and its
-// measured reason live) from the handle's state and ONE reading of the tuning table.  The stages of ivf_search_enqueue and
-// launch_ivf_route fill their arguments from it and decide nothing themselves.
+// measured reason live) from the handle's state, the call's shape (whether a host flag is wanted among it) and ONE reading of the
+// tuning table.  The stages of ivf_search_enqueue and launch_ivf_route fill their arguments from it and decide nothing themselves.
 enum class IvfScan {
     Tile,    // MFMA tile scan (cosine / dot: the k-ordered summation; Euclidean: l2_group_kernel)
     Group,   // register-row group kernel: the GEMV order, a list fetched once per group of queries
@@ -392,6 +388,13 @@ struct IvfSearchPlan {
     int32_t finish_slices, finish_span, finish_adapt, finish_bisect, finish_direct;
     int64_t finish_pstride;   // keys per query handed to its last workgroup
     bool flag_in_finish;      // a flagged synchronous call: the finish kernel's last workgroup tells the caller
+};
+// The flag word a small synchronous IVF call spins on (ivf.hip: ivf_search_batch_slot): its device address and the value it takes.
+// taken: the search went through the finish kernel, whose last workgroup sets it; otherwise a one-thread launch behind the search does.
+struct IvfHostFlag {
+    uint32_t *flag;
+    uint32_t val;
+    bool taken;
 };
 // the survivor stream's buffers that the routing step prepares (stream_kernels.hpp), or null
 struct RouteStream {
@@ -454,13 +457,59 @@ int pad_queries(hnswgpu_index *idx, const float *d_Q, int64_t qld, int32_t nq, h
 int tile_topk_all(hnswgpu_index *idx, const float *Qp, const float *q_norms, int32_t nq, const float *rows,
                   const float *row_norms, int64_t nrows, int32_t k, hipStream_t st, int prof_slot, bool gemv_order = false);
 
-// Every entry point brackets its device work with these: a call on stream B waits for the previous
-// call's work on stream A before it may reuse the index's scratch buffers.
-int begin_call(hnswgpu_index *idx, hipStream_t st);
-int end_call(hnswgpu_index *idx, hipStream_t st);
-// Before device memory that searches read is freed (graph, lists, the handle itself): wait, under idx->mu, for the
-// main stream AND for the two slot streams -- the small synchronous searches launch on those without begin_call /
-// end_call and release idx->mu before their kernel has finished.
-int quiesce(hnswgpu_index *idx, hipStream_t st);
+// One call on a handle: the owner of idx->mu, the current device and the ordering of the handle's shared scratch buffers across
+// streams.  open() takes the lock, sets the device and makes `st` wait for the event of the call before (ev_last) when that one ran
+// on another stream.  However the scope is left -- close() on the success path, the destructor behind an early error return --
+// ev_last / ev_stream / ev_valid describe everything the call may have enqueued on `st`: an event recorded behind it, or, once
+// sync() has waited for `st` behind the call's last enqueue, nothing (`st` had waited for the event before: no work of this handle
+// is in flight).  The scope may be narrower than its function and may be opened on a slot stream (ivf.hip: ivf_search_batch_slot).
+// hnsw_search_batch_slot alone takes no part: it enqueues under a plain lock of idx->mu, works in its slot's own memory and in
+// tagged regions of s_pf / s_solo (hnsw.hip: hnsw_number_launch), and is waited for by quiesce().
+class Call {
+public:
+    Call() = default;
+    Call(const Call &) = delete;
+    Call &operator=(const Call &) = delete;
+    ~Call() {
+        if (idx_) (void)leave();  // an early return: raw HIP calls, the thread's error message stays the caller's
+    }
+    int open(hnswgpu_index *idx, hipStream_t st);
+    // Before device memory that searches read is freed (graph, lists): wait for `st` AND for the two slot streams -- the small
+    // synchronous HNSW searches launch on those outside the event ordering and release idx->mu before their kernel has finished.
+    int quiesce();
+    int sync();   // hipStreamSynchronize(st), behind the call's last enqueue
+    int close();  // reports a failing hipEventRecord; the lock is held to the end of the scope
+    // Host staging of a search through s_q / s_ids / s_outd: the queries up and room for nq * k results; the enqueue goes between
+    // the two; then ids and distances down and sync()
+    int stage_in(const float *Q, int32_t nq, int32_t k);
+    int stage_out(int32_t *out_ids, float *out_dist, int64_t cnt);
+private:
+    hipError_t leave();
+    hnswgpu_index *idx_ = nullptr;
+    hipStream_t st_ = nullptr;
+    bool idle_ = false;
+    std::unique_lock<std::mutex> lk_;
+};
+
+void fill_empty(int32_t *ids, float *dist, int64_t cnt);  // no rows: id -1 at distance +inf
+
+// The block of host memory of one combined batch -- a Slot's mapped block and the pinned staging block alike:
+// [64-byte header: flag word, repeat count][queries][stats, 2 x int64 per query, or absent][ids][distances], every section on a
+// 64-byte boundary.  The accessors take the block's host or device address.
+struct BatchBlock {
+    int32_t k, dim;
+    size_t o_q, o_s, o_i, o_d, bytes;  // o_s == 0: no stats
+    BatchBlock(int32_t dim, int32_t total, int32_t k, bool stats);
+    uint32_t *flag(void *b) const { return static_cast<uint32_t *>(b); }
+    int32_t *again(void *b) const { return static_cast<int32_t *>(b) + 1; }
+    float *queries(void *b) const { return reinterpret_cast<float *>(static_cast<char *>(b) + o_q); }
+    int64_t *stats(void *b) const { return o_s ? reinterpret_cast<int64_t *>(static_cast<char *>(b) + o_s) : nullptr; }
+    int32_t *ids(void *b) const { return reinterpret_cast<int32_t *>(static_cast<char *>(b) + o_i); }
+    float *dist(void *b) const { return reinterpret_cast<float *>(static_cast<char *>(b) + o_d); }
+    void pack(void *host, const std::vector<hnswgpu_index::SearchReq *> &batch) const;     // the callers' queries, one behind the other
+    void scatter(void *host, const std::vector<hnswgpu_index::SearchReq *> &batch) const;  // ids, distances and stats back to each caller
+    // a free Slot and its lock (both busy: more callers than the combiner's batches in flight -- cannot happen, but wait for the first)
+    static hnswgpu_index::Slot *acquire_slot(hnswgpu_index *idx, std::unique_lock<std::mutex> &lk);
+};
 
 }  // namespace hg

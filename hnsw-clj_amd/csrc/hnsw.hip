@@ -229,7 +229,7 @@ static int hnsw_launch_plan(const hnswgpu_index *idx, const HnswArgs &a, const H
     return 0;
 }
 
-// every stream that may still run a launch that reads or writes s_pf / s_solo (the slot launches do not pass begin_call / end_call)
+// every stream that may still run a launch that reads or writes s_pf / s_solo (the slot launches take no part in hg::Call's event ordering)
 static int hnsw_tables_idle(hnswgpu_index *idx, hipStream_t st) {
     for (auto &sl : idx->slots)
         if (sl.st) HG_HIP(hipStreamSynchronize(sl.st));
@@ -804,13 +804,13 @@ int hnswgpu_set_graph(hnswgpu_index *idx, const int32_t *levels, const int32_t *
                                "edge %lld->%d on layer %d: target has no such layer", (long long)i, nb, lv);
                 }
     }
-    std::lock_guard<std::mutex> lk(idx->mu);
-    HG_HIP(hipSetDevice(idx->device));
     hipStream_t st = idx->stream;
-    // every earlier call on this handle is ordered before `st` by begin_call, except the small synchronous searches on
+    Call call;
+    HG_TRY(call.open(idx, st));
+    // every earlier call on this handle is ordered before `st` by the scope, except the small synchronous searches on
     // the slot streams: once `st` and both slot streams are idle nothing can still be traversing the graph that is about
     // to be freed (and no other handle on this GPU is stalled)
-    HG_TRY(quiesce(idx, st));
+    HG_TRY(call.quiesce());
     free_graph(idx);
     HG_TRY(alloc_graph(idx, M, M0, blocks));
     HG_TRY(ensure_qrows(idx, st));
@@ -820,7 +820,7 @@ int hnswgpu_set_graph(hnswgpu_index *idx, const int32_t *levels, const int32_t *
         HG_HIP(hipMemcpyAsync(idx->d_upoff, up_off, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, st));
         if (blocks > 0)
             HG_HIP(hipMemcpyAsync(idx->d_upadj, up_adj, sizeof(int32_t) * blocks * M, hipMemcpyHostToDevice, st));
-        HG_HIP(hipStreamSynchronize(st));
+        HG_TRY(call.sync());
         idx->h_levels.assign(levels, levels + n);
         idx->h_l0.assign(l0_adj, l0_adj + n * M0);
         idx->h_upoff.assign(up_off, up_off + n + 1);
@@ -834,7 +834,7 @@ int hnswgpu_set_graph(hnswgpu_index *idx, const int32_t *levels, const int32_t *
     idx->entry = n > 0 ? entry : -1;
     idx->max_level = n > 0 ? max_level : 0;
     idx->has_graph = true;
-    return 0;
+    return call.close();
 }
 
 int hnswgpu_graph_sizes(const hnswgpu_index *idx, int32_t *M, int32_t *M0, int64_t *up_blocks, int32_t *entry,
@@ -881,71 +881,40 @@ static bool zero_copy() { return tune(HNSWGPU_TUNE_ZEROCOPY, 1) != 0; }  // 0 = 
 // single-query call for a 0.35 ms kernel).  Two such batches may be in flight (own stream, block and counters each).
 static int hnsw_search_batch_slot(hnswgpu_index *idx, const std::vector<hnswgpu_index::SearchReq *> &batch, int32_t total) {
     const int32_t k = batch[0]->k, ef = batch[0]->ef;
-    const size_t cnt = static_cast<size_t>(total) * k;
-    // block layout: [flag u32 | repeat count i32 | pad to 64 B][queries][ids][distances][stats]
-    const size_t qb = sizeof(float) * static_cast<size_t>(total) * idx->dim, ib = sizeof(int32_t) * cnt, db = sizeof(float) * cnt,
-                 sb = sizeof(int64_t) * 2 * total;
-    const size_t o_q = 64, o_s = (o_q + qb + 63) & ~size_t(63), o_i = o_s + sb, o_d = o_i + ib, bytes = o_d + db;
-    hnswgpu_index::Slot *slot = nullptr;
+    const BatchBlock b(idx->dim, total, k, true);
     std::unique_lock<std::mutex> sl;
-    for (auto &s : idx->slots) {
-        sl = std::unique_lock<std::mutex>(s.mu, std::try_to_lock);
-        if (sl.owns_lock()) {
-            slot = &s;
-            break;
-        }
-    }
-    if (!slot) {  // both busy (more callers than the combiner's two batches in flight: cannot happen, but be safe)
-        slot = &idx->slots[0];
-        sl = std::unique_lock<std::mutex>(slot->mu);
-    }
-    HG_HIP(hipSetDevice(idx->device));
-    HG_TRY(slot_prepare(*slot, bytes));
-    char *hp = static_cast<char *>(slot->h), *dp = static_cast<char *>(slot->d);
-    size_t o = 0;
-    float *hq = reinterpret_cast<float *>(hp + o_q);
-    for (auto *r : batch) {
-        memcpy(hq + o, r->Q, sizeof(float) * static_cast<size_t>(r->nq) * idx->dim);
-        o += static_cast<size_t>(r->nq) * idx->dim;
-    }
+    hnswgpu_index::Slot *slot = BatchBlock::acquire_slot(idx, sl);
+    HG_TRY(slot_prepare(*slot, b.bytes, idx->device));
+    void *hp = slot->h, *dp = slot->d;
+    b.pack(hp, batch);
     SlotSignal sig;
     sig.again = slot->d_again;
     sig.done_cnt = slot->d_done;
-    sig.host_flag = reinterpret_cast<uint32_t *>(dp);
-    sig.host_again = reinterpret_cast<int32_t *>(dp + 4);
+    sig.host_flag = b.flag(dp);
+    sig.host_again = b.again(dp);
     sig.flag_val = ++slot->seq;
-    volatile uint32_t *h_flag = reinterpret_cast<volatile uint32_t *>(hp);
     uint64_t gen;
+    HG_HIP(hipSetDevice(idx->device));
     {
-        std::lock_guard<std::mutex> lk(idx->mu);  // the index state is read (and the launch enqueued) under its lock
+        // the index state is read (and the launch enqueued) under its lock -- a plain one: this path takes no part in hg::Call's
+        // event ordering (engine.hpp)
+        std::lock_guard<std::mutex> lk(idx->mu);
         HG_REQUIRE(idx->has_graph && idx->n > 0, HNSWGPU_ESTATE, "index has no graph (call hnswgpu_hnsw_build / hnswgpu_set_graph)");
         gen = idx->graph_gen;
-        HG_TRY(search_enqueue(idx, reinterpret_cast<const float *>(dp + o_q), total, k, ef, reinterpret_cast<int32_t *>(dp + o_i),
-                              reinterpret_cast<float *>(dp + o_d), reinterpret_cast<int64_t *>(dp + o_s), slot->st, &sig));
+        HG_TRY(search_enqueue(idx, b.queries(dp), total, k, ef, b.ids(dp), b.dist(dp), b.stats(dp), slot->st, &sig));
     }
-    HG_TRY(slot_wait(*slot, h_flag, sig.flag_val));
-    if (*reinterpret_cast<volatile int32_t *>(hp + 4) != 0) {
+    HG_TRY(slot_wait(*slot, b.flag(hp), sig.flag_val));
+    if (*static_cast<volatile int32_t *>(b.again(hp)) != 0) {
         // some query met more tied candidates than the ghost slots hold (hundreds of duplicated rows): the repeat pass --
         // against the graph the first pass ran on, or not at all (set_graph / hnsw_build wait for this slot's stream
         // before they free the old graph, but may have installed a new one since the first pass finished)
         std::lock_guard<std::mutex> lk(idx->mu);
         HG_REQUIRE(idx->has_graph && idx->graph_gen == gen, HNSWGPU_ESTATE,
                    "the graph was replaced while a search on it was in flight");
-        HG_TRY(search_enqueue(idx, reinterpret_cast<const float *>(dp + o_q), total, k, ef, reinterpret_cast<int32_t *>(dp + o_i),
-                              reinterpret_cast<float *>(dp + o_d), reinterpret_cast<int64_t *>(dp + o_s), slot->st, &sig, true));
+        HG_TRY(search_enqueue(idx, b.queries(dp), total, k, ef, b.ids(dp), b.dist(dp), b.stats(dp), slot->st, &sig, true));
         HG_HIP(hipStreamSynchronize(slot->st));
     }
-    const int32_t *hi = reinterpret_cast<const int32_t *>(hp + o_i);
-    const float *hd = reinterpret_cast<const float *>(hp + o_d);
-    const int64_t *hs = reinterpret_cast<const int64_t *>(hp + o_s);
-    int64_t q0 = 0;
-    for (auto *r : batch) {
-        const size_t c = static_cast<size_t>(r->nq) * k;
-        memcpy(r->out_ids, hi + q0 * k, sizeof(int32_t) * c);
-        memcpy(r->out_dist, hd + q0 * k, sizeof(float) * c);
-        if (r->stats) memcpy(r->stats, hs + 2 * q0, sizeof(int64_t) * 2 * r->nq);
-        q0 += r->nq;
-    }
+    b.scatter(hp, batch);
     return 0;
 }
 
@@ -956,49 +925,26 @@ static int hnsw_search_batch(hnswgpu_index *idx, const std::vector<hnswgpu_index
     if (zero_copy() && total <= kZcMaxQueries && !hnsw_vis_global(idx->n, tune(HNSWGPU_TUNE_VIS_GLOBAL, 0)))
         return hnsw_search_batch_slot(idx, batch, total);
     const int32_t k = batch[0]->k, ef = batch[0]->ef;
-    const int64_t cnt = static_cast<int64_t>(total) * k;
-    std::lock_guard<std::mutex> lk(idx->mu);
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
     // under the lock: a concurrent set_graph / hnsw_build may have replaced the graph since the caller's argument check
     HG_REQUIRE(idx->has_graph && idx->n > 0, HNSWGPU_ESTATE, "index has no graph (call hnswgpu_hnsw_build / hnswgpu_set_graph)");
-    HG_HIP(hipSetDevice(idx->device));
-    hipStream_t st = idx->stream;
-    HG_TRY(begin_call(idx, st));
-    HG_TRY(idx->s_ids.ensure(sizeof(int32_t) * cnt));
-    HG_TRY(idx->s_outd.ensure(sizeof(float) * cnt));
+    // one pinned staging block, four transfers per batch whatever the number of callers in it.  (Replaying the single-query
+    // sequence -- upload, counter reset, two launches, downloads -- as one captured hipGraph was tried and changed nothing:
+    // 0.483 ms per call either way, the time is on the device.)
+    const BatchBlock b(idx->dim, total, k, true);
+    HG_TRY(ensure_pinned(idx, b.bytes));
+    void *hp = idx->h_pin;
+    b.pack(hp, batch);
+    HG_TRY(call.stage_in(b.queries(hp), total, k));
     HG_TRY(idx->s_stats.ensure(sizeof(int64_t) * 2 * total));
-    // one pinned staging block [queries | stats | ids | distances], four transfers per batch whatever the number of
-    // callers in it.  (Replaying the single-query sequence -- upload, counter reset, two launches, downloads -- as one
-    // captured hipGraph was tried and changed nothing: 0.483 ms per call either way, the time is on the device.)
-    const size_t qb = sizeof(float) * static_cast<size_t>(total) * idx->dim, ib = sizeof(int32_t) * cnt,
-                 db = sizeof(float) * cnt, sb = sizeof(int64_t) * 2 * total;
-    HG_TRY(ensure_pinned(idx, qb + ib + db + sb + 64));
-    char *hp = static_cast<char *>(idx->h_pin);
-    float *hq = reinterpret_cast<float *>(hp);
-    int64_t *hs = reinterpret_cast<int64_t *>(hp + ((qb + 7) & ~size_t(7)));
-    int32_t *hi = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(hs) + sb);
-    float *hd = reinterpret_cast<float *>(reinterpret_cast<char *>(hi) + ib);
-    size_t o = 0;
-    for (auto *r : batch) {
-        memcpy(hq + o, r->Q, sizeof(float) * static_cast<size_t>(r->nq) * idx->dim);
-        o += static_cast<size_t>(r->nq) * idx->dim;
-    }
-    HG_TRY(upload_queries(idx, hq, total, st));
     HG_TRY(search_enqueue(idx, idx->s_q.as<float>(), total, k, ef, idx->s_ids.as<int32_t>(), idx->s_outd.as<float>(),
                           idx->s_stats.as<int64_t>(), st));
-    HG_HIP(hipMemcpyAsync(hi, idx->s_ids.p, ib, hipMemcpyDeviceToHost, st));
-    HG_HIP(hipMemcpyAsync(hd, idx->s_outd.p, db, hipMemcpyDeviceToHost, st));
-    HG_HIP(hipMemcpyAsync(hs, idx->s_stats.p, sb, hipMemcpyDeviceToHost, st));
-    HG_TRY(end_call(idx, st));
-    HG_HIP(hipStreamSynchronize(st));
-    int64_t q0 = 0;
-    for (auto *r : batch) {
-        const size_t c = static_cast<size_t>(r->nq) * k;
-        memcpy(r->out_ids, hi + q0 * k, sizeof(int32_t) * c);
-        memcpy(r->out_dist, hd + q0 * k, sizeof(float) * c);
-        if (r->stats) memcpy(r->stats, hs + 2 * q0, sizeof(int64_t) * 2 * r->nq);
-        q0 += r->nq;
-    }
-    return 0;
+    HG_HIP(hipMemcpyAsync(b.stats(hp), idx->s_stats.p, sizeof(int64_t) * 2 * total, hipMemcpyDeviceToHost, st));
+    HG_TRY(call.stage_out(b.ids(hp), b.dist(hp), static_cast<int64_t>(total) * k));
+    b.scatter(hp, batch);
+    return call.close();
 }
 
 int hnswgpu_hnsw_search_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t ef,
@@ -1006,12 +952,11 @@ int hnswgpu_hnsw_search_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, in
     HG_TRY(check_hnsw_args(idx, d_Q, nq, k, &ef, d_out_ids, d_out_dist));
     if (nq == 0) return 0;
     HG_REQUIRE(idx->n > 0, HNSWGPU_ESTATE, "empty index: use the host entry point");
-    std::lock_guard<std::mutex> lk(idx->mu);
-    HG_HIP(hipSetDevice(idx->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    HG_TRY(begin_call(idx, st));
+    Call call;
+    HG_TRY(call.open(idx, st));
     HG_TRY(search_enqueue(idx, d_Q, nq, k, ef, d_out_ids, d_out_dist, d_stats, st));
-    return end_call(idx, st);
+    return call.close();
 }
 
 int hnswgpu_hnsw_search(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t ef, int32_t *out_ids,
@@ -1020,10 +965,7 @@ int hnswgpu_hnsw_search(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t 
     if (nq == 0) return 0;
     int64_t cnt = static_cast<int64_t>(nq) * k;
     if (idx->n == 0) {  // (if (or (nil? entry-point) (zero? size)) [] ...), ultra_fast.clj:349-351
-        for (int64_t i = 0; i < cnt; i++) {
-            out_ids[i] = -1;
-            out_dist[i] = __builtin_inff();
-        }
+        fill_empty(out_ids, out_dist, cnt);
         if (stats) memset(stats, 0, sizeof(int64_t) * 2 * nq);
         return 0;
     }
@@ -1646,9 +1588,9 @@ int hnswgpu_hnsw_build_ex(hnswgpu_index *idx, int32_t M, int32_t ef_construction
                "HNSWGPU_BUILD_SYMMETRIC / _EXTEND qualify HNSWGPU_BUILD_HEURISTIC");
     HG_REQUIRE(M >= 1 && 2 * M <= kMaxDeg, HNSWGPU_ELIMIT, "need 1 <= M <= %d", kMaxDeg / 2);
     HG_REQUIRE(ef_construction >= 1 && ef_construction <= 4096, HNSWGPU_ELIMIT, "need 1 <= ef_construction <= 4096");
-    std::lock_guard<std::mutex> lk(idx->mu);
-    HG_HIP(hipSetDevice(idx->device));
     hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
     const int64_t n = idx->n;
     const int M0 = 2 * M;
     HostGraph g;
@@ -1659,7 +1601,7 @@ int hnswgpu_hnsw_build_ex(hnswgpu_index *idx, int32_t M, int32_t ef_construction
     g.up_off.assign(n + 1, 0);
     draw_levels(seed, 0, n, g.levels, g.up_off);
     const int64_t blocks = n > 0 ? g.up_off[n] : 0;
-    HG_TRY(quiesce(idx, st));  // as in hnswgpu_set_graph
+    HG_TRY(call.quiesce());  // as in hnswgpu_set_graph
     free_graph(idx);
     HG_TRY(alloc_graph(idx, M, M0, blocks));
     HG_TRY(ensure_qrows(idx, st));
@@ -1671,7 +1613,7 @@ int hnswgpu_hnsw_build_ex(hnswgpu_index *idx, int32_t M, int32_t ef_construction
         idx->entry = -1;
         idx->max_level = 0;
         idx->has_graph = true;
-        return 0;
+        return call.close();
     }
     g.l0.assign(static_cast<size_t>(n) * (M0 + 1), -1);
     g.l0_d.assign(static_cast<size_t>(n) * (M0 + 1), 0.f);
@@ -1690,7 +1632,7 @@ int hnswgpu_hnsw_build_ex(hnswgpu_index *idx, int32_t M, int32_t ef_construction
     HG_TRY(insert_batches(idx, g, 1, ef_construction, st, flags));
     HG_TRY(publish_graph(idx, g, st));
     idx->build_flags = flags;  // (only a graph that stands carries its builder: hnswgpu_hnsw_add inserts the same way)
-    return 0;
+    return call.close();
 }
 
 // insert-single on a LIVE index (ultra_fast.clj:216-275, reached by add-vector! src/hnsw/api.clj:30-33 and add!
@@ -1705,16 +1647,16 @@ int hnswgpu_hnsw_add(hnswgpu_index *idx, const float *rows, int64_t m, int32_t e
     if (m == 0) return 0;
     HG_REQUIRE(rows, HNSWGPU_EINVAL, "rows is null");
     HG_REQUIRE(ef_construction >= 1 && ef_construction <= 4096, HNSWGPU_ELIMIT, "need 1 <= ef_construction <= 4096");
-    std::lock_guard<std::mutex> lk(idx->mu);
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
     HG_REQUIRE(idx->has_graph, HNSWGPU_ESTATE, "index has no graph (call hnswgpu_hnsw_build / hnswgpu_set_graph first)");
     HG_REQUIRE(idx->nlist == 0, HNSWGPU_ESTATE,
                "the index holds IVF lists over its present rows: add rows first, then build / install the lists");
     HG_REQUIRE(idx->M0 == 2 * idx->M, HNSWGPU_ESTATE, "hnswgpu_hnsw_add needs a graph with M0 = 2 M (as hnswgpu_hnsw_build makes)");
     const int64_t n0 = idx->n, n1 = n0 + m;
     HG_REQUIRE(n1 < 2147483647LL, HNSWGPU_ELIMIT, "the index must hold fewer than 2^31 rows");
-    HG_HIP(hipSetDevice(idx->device));
-    hipStream_t st = idx->stream;
-    HG_TRY(quiesce(idx, st));
+    HG_TRY(call.quiesce());
     const int M = idx->M, M0 = idx->M0;
     const int64_t ld = idx->ld;
     // Failure-atomic: everything the call makes -- the grown base, norms, int8 rows, device graph -- is STAGED; the handle's
@@ -1869,7 +1811,7 @@ int hnswgpu_hnsw_add(hnswgpu_index *idx, const float *rows, int64_t m, int32_t e
         return rc;
     }
     free_staged(old);
-    return 0;
+    return call.close();
 }
 
 }  // extern "C"

@@ -872,7 +872,8 @@ constexpr int kHeavySlices = 64;
 // the scan the routing would seed no threshold for a scan that expects one (every query through the overflow fallback), with
 // the chunking changing the folded work list would be built for another cut of the lists than the bounds kernel walks.  The
 // limits a search can exceed are found here as well, with nothing enqueued yet.
-static int ivf_search_plan(const hnswgpu_index *idx, int32_t nq, int32_t k, int32_t nprobe, bool given_probes, IvfSearchPlan &p) {
+static int ivf_search_plan(const hnswgpu_index *idx, int32_t nq, int32_t k, int32_t nprobe, bool given_probes, bool want_flag,
+                           IvfSearchPlan &p) {
     memset(&p, 0, sizeof(p));
     if (nprobe > idx->nlist && !given_probes) nprobe = idx->nlist;
     const int64_t npairs = static_cast<int64_t>(nq) * nprobe;
@@ -1074,7 +1075,7 @@ static int ivf_search_plan(const hnswgpu_index *idx, int32_t nq, int32_t k, int3
             p.mid_compact = p.mid_slices == 1 && mid_compact_env ? static_cast<int32_t>(std::min<int64_t>(p.surv_cap, 4096)) : 0;
         }
         // a flagged synchronous call: the last query's workgroup of the finish kernel tells the caller
-        p.flag_in_finish = idx->zc_flag && !p.heavy && !idx->ivf_calibrating;
+        p.flag_in_finish = want_flag && !p.heavy && !idx->ivf_calibrating;
     }
 
     // ---- the routing
@@ -1336,7 +1337,7 @@ static int stream_mid_pass(hnswgpu_index *idx, const IvfSearchPlan &p, const Str
 
 // f32 distances of the survivors in the GEMV order, top-k, ids and distances
 static int stream_finish(hnswgpu_index *idx, const IvfSearchPlan &p, const StreamScratch &sc, const float *d_Q, const int32_t *d_qcnt,
-                         int32_t *d_out_ids, float *d_out_dist, uint32_t *d_out_gord, hipStream_t st) {
+                         int32_t *d_out_ids, float *d_out_dist, uint32_t *d_out_gord, IvfHostFlag *hf, hipStream_t st) {
     FinishArgs f;
     memset(&f, 0, sizeof(f));
     f.prepass = p.mid ? 1 : 0;  // (lists of more than 128 entries only: what a compacting pass has left is evaluated in one step)
@@ -1376,10 +1377,10 @@ static int stream_finish(hnswgpu_index *idx, const IvfSearchPlan &p, const Strea
     f.out_gord = d_out_gord;
     f.stats = (idx->prof || idx->ivf_calibrating) ? idx->d_rej_stats : nullptr;
     if (p.flag_in_finish) {
-        f.host_flag = idx->zc_flag;
-        f.flag_val = idx->zc_val;
+        f.host_flag = hf->flag;
+        f.flag_val = hf->val;
         f.done_q = idx->s_done.as<uint32_t>() + 2 * idx->s_done_n + 2;
-        idx->zc_taken = true;
+        hf->taken = true;
     }
     f.qorder = f.slices == 1 ? sc.qorder : nullptr;
     f.main_blocks = static_cast<int32_t>(f.qorder ? (static_cast<int64_t>(p.nq) + 7) / 8 * 8 : static_cast<int64_t>(p.nq) * f.slices);
@@ -1387,7 +1388,8 @@ static int stream_finish(hnswgpu_index *idx, const IvfSearchPlan &p, const Strea
 }
 
 static int ivf_stream_scan(hnswgpu_index *idx, const IvfSearchPlan &p, StreamScratch &sc, const float *d_Q, const int32_t *d_qcnt,
-                           const int32_t *d_probes, int32_t *d_out_ids, float *d_out_dist, uint32_t *d_out_gord, hipStream_t st) {
+                           const int32_t *d_probes, int32_t *d_out_ids, float *d_out_dist, uint32_t *d_out_gord, IvfHostFlag *hf,
+                           hipStream_t st) {
     if (p.home) {
         HG_TRY(idx->s_home.ensure(sizeof(HomeDesc) * static_cast<size_t>(p.home_bound) + 64 + sizeof(uint32_t) * static_cast<size_t>(p.nq)));
         HG_TRY(idx->s_dh.ensure(sizeof(float2) * static_cast<size_t>(p.nq) * p.home_stride));
@@ -1406,12 +1408,12 @@ static int ivf_stream_scan(hnswgpu_index *idx, const IvfSearchPlan &p, StreamScr
     if (p.heavy) HG_TRY(stream_heavy_list(idx, p, sc, st));
     HG_TRY(ensure_counters(idx, p.nq, st));
     if (p.mid) HG_TRY(stream_mid_pass(idx, p, sc, d_Q, st));
-    return stream_finish(idx, p, sc, d_Q, d_qcnt, d_out_ids, d_out_dist, d_out_gord, st);
+    return stream_finish(idx, p, sc, d_Q, d_qcnt, d_out_ids, d_out_dist, d_out_gord, hf, st);
 }
 
 static int ivf_search_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t nprobe,
                               int32_t *d_out_ids, float *d_out_dist, int32_t *d_out_probes, hipStream_t st,
-                              const int32_t *d_given_probes = nullptr, uint32_t *d_out_gord = nullptr);
+                              const int32_t *d_given_probes = nullptr, uint32_t *d_out_gord = nullptr, IvfHostFlag *hf = nullptr);
 
 // What do the int8 bounds separate on THIS handle's rows?  On data with cluster structure they leave a query its home
 // cluster (3 % of the candidates on the bench index); on rows without any -- i.i.d. gaussian: distances concentrate, every
@@ -1613,10 +1615,10 @@ static int ivf_decode(hnswgpu_index *idx, const IvfSearchPlan &p, int32_t *d_out
 // One search: calibrate if needed, plan, size the scratch the plan names, route, scan.
 static int ivf_search_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t nprobe,
                               int32_t *d_out_ids, float *d_out_dist, int32_t *d_out_probes, hipStream_t st,
-                              const int32_t *d_given_probes, uint32_t *d_out_gord) {
+                              const int32_t *d_given_probes, uint32_t *d_out_gord, IvfHostFlag *hf) {
     if (!idx->ivf_calibrated && !idx->ivf_calibrating) HG_TRY(ivf_calibrate(idx, st));
     IvfSearchPlan p;
-    HG_TRY(ivf_search_plan(idx, nq, k, nprobe, d_given_probes != nullptr, p));
+    HG_TRY(ivf_search_plan(idx, nq, k, nprobe, d_given_probes != nullptr, hf != nullptr, p));
     const bool stream = p.scan == IvfScan::Stream, grouped_rows = p.scan == IvfScan::Tile || p.scan == IvfScan::Group;
     HG_TRY(idx->s_pairs.ensure(sizeof(Pair) * static_cast<size_t>(p.npairs)));
     int32_t *probes_buf = d_out_probes, *qcnt_buf = nullptr, *order_buf = nullptr;
@@ -1641,7 +1643,7 @@ static int ivf_search_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, 
             // bounds on the int8 list rows with a running threshold, f32 distances -- the GEMV order, so the bits of this regime
             // are unchanged -- only for the survivors; the finish kernel writes ids and distances
             if (p.query_prep) HG_TRY(stream_query_prep(idx, p, sc, d_Q, qcnt_buf, st));
-            return ivf_stream_scan(idx, p, sc, d_Q, qcnt_buf, probes_buf, d_out_ids, d_out_dist, d_out_gord, st);
+            return ivf_stream_scan(idx, p, sc, d_Q, qcnt_buf, probes_buf, d_out_ids, d_out_dist, d_out_gord, hf, st);
         case IvfScan::Tile:
         case IvfScan::Group: HG_TRY(ivf_tile_scan(idx, p, d_Q, probes_buf, qcnt_buf, st)); break;
         case IvfScan::Fused: return ivf_gemv_scan(idx, p, d_Q, probes_buf, order_buf, d_out_ids, d_out_dist, d_out_gord, st);
@@ -1672,13 +1674,13 @@ static int set_ivf_impl(hnswgpu_index *idx, const float *centroids, int32_t nlis
         }
         HG_REQUIRE(goff[nlist] < 0xffffffffLL, HNSWGPU_ELIMIT, "the whole index must hold fewer than 2^32 rows");
     }
-    std::lock_guard<std::mutex> lk(idx->mu);
-    HG_HIP(hipSetDevice(idx->device));
     hipStream_t st = idx->stream;
-    // every earlier call on this handle is ordered before `st` by begin_call (the small HNSW searches on the slot streams
+    Call call;
+    HG_TRY(call.open(idx, st));
+    // every earlier call on this handle is ordered before `st` by the scope (the small HNSW searches on the slot streams
     // are waited for as well: lists that alias the base rows share them with the traversal): nothing can still read the
     // lists about to be freed (no device-wide synchronisation: other handles keep running)
-    HG_TRY(quiesce(idx, st));
+    HG_TRY(call.quiesce());
     free_ivf(idx);
     HG_TRY(alloc_centroids(idx, nlist));
     HG_HIP(hipMemsetAsync(idx->d_cent, 0, sizeof(float) * nlist * idx->ld, st));
@@ -1696,7 +1698,7 @@ static int set_ivf_impl(hnswgpu_index *idx, const float *centroids, int32_t nlis
         idx->ivf_n_global = goff[nlist];
     }
     idx->h_cent.assign(centroids, centroids + static_cast<size_t>(nlist) * idx->dim);
-    return 0;
+    return call.close();
 }
 
 int hnswgpu_set_ivf(hnswgpu_index *idx, const float *centroids, int32_t nlist, const int64_t *list_off,
@@ -1725,10 +1727,9 @@ int hnswgpu_kmeans_assign(hnswgpu_index *idx, const float *centroids, int32_t nl
     HG_REQUIRE(idx && centroids && (out_assign || idx->n == 0), HNSWGPU_EINVAL, "null argument");
     HG_REQUIRE(nlist >= 1, HNSWGPU_EINVAL, "nlist must be >= 1");
     if (idx->n == 0) return 0;
-    std::lock_guard<std::mutex> lk(idx->mu);
-    HG_HIP(hipSetDevice(idx->device));
     hipStream_t st = idx->stream;
-    HG_TRY(begin_call(idx, st));
+    Call call;
+    HG_TRY(call.open(idx, st));
     HG_TRY(idx->s_misc.ensure(sizeof(float) * nlist * idx->ld));
     HG_TRY(idx->s_misc2.ensure(sizeof(float) * nlist));
     HG_HIP(hipMemsetAsync(idx->s_misc.p, 0, sizeof(float) * nlist * idx->ld, st));
@@ -1738,8 +1739,8 @@ int hnswgpu_kmeans_assign(hnswgpu_index *idx, const float *centroids, int32_t nl
     HG_TRY(assign_enqueue(idx, idx->s_misc.as<float>(), idx->s_misc2.as<float>(), nlist, st));
     HG_HIP(hipMemcpyAsync(out_assign, idx->s_ord.p, sizeof(int32_t) * idx->n, hipMemcpyDeviceToHost, st));
     if (out_dist) HG_HIP(hipMemcpyAsync(out_dist, idx->s_dist.p, sizeof(float) * idx->n, hipMemcpyDeviceToHost, st));
-    HG_HIP(hipStreamSynchronize(st));
-    return 0;
+    HG_TRY(call.sync());
+    return call.close();
 }
 
 int hnswgpu_list_means(hnswgpu_index *idx, int32_t nlist, const int64_t *list_off, const int32_t *list_ids,
@@ -1747,10 +1748,9 @@ int hnswgpu_list_means(hnswgpu_index *idx, int32_t nlist, const int64_t *list_of
     HG_REQUIRE(idx && list_off && (list_ids || idx->n == 0) && out_centroids, HNSWGPU_EINVAL, "null argument");
     HG_REQUIRE(nlist >= 1, HNSWGPU_EINVAL, "nlist must be >= 1");
     HG_TRY(validate_lists(idx->n, nlist, list_off, list_ids));
-    std::lock_guard<std::mutex> lk(idx->mu);
-    HG_HIP(hipSetDevice(idx->device));
     hipStream_t st = idx->stream;
-    HG_TRY(begin_call(idx, st));
+    Call call;
+    HG_TRY(call.open(idx, st));
     HG_TRY(idx->s_misc.ensure(sizeof(int64_t) * (nlist + 1)));
     HG_TRY(idx->s_misc2.ensure(sizeof(int32_t) * std::max<int64_t>(idx->n, 1)));
     HG_TRY(idx->s_tile.ensure(sizeof(float) * static_cast<size_t>(nlist) * idx->ld));
@@ -1763,9 +1763,8 @@ int hnswgpu_list_means(hnswgpu_index *idx, int32_t nlist, const int64_t *list_of
     HG_HIP(hipGetLastError());
     HG_HIP(hipMemcpy2DAsync(out_centroids, sizeof(float) * idx->dim, idx->s_tile.p, sizeof(float) * idx->ld,
                             sizeof(float) * idx->dim, nlist, hipMemcpyDeviceToHost, st));
-    HG_TRY(end_call(idx, st));
-    HG_HIP(hipStreamSynchronize(st));
-    return 0;
+    HG_TRY(call.sync());
+    return call.close();
 }
 
 int hnswgpu_list_sums(hnswgpu_index *idx, int32_t nlist, const int64_t *list_off, const int32_t *list_ids,
@@ -1773,10 +1772,9 @@ int hnswgpu_list_sums(hnswgpu_index *idx, int32_t nlist, const int64_t *list_off
     HG_REQUIRE(idx && list_off && (list_ids || idx->n == 0) && out_sums, HNSWGPU_EINVAL, "null argument");
     HG_REQUIRE(nlist >= 1, HNSWGPU_EINVAL, "nlist must be >= 1");
     HG_TRY(validate_lists(idx->n, nlist, list_off, list_ids));
-    std::lock_guard<std::mutex> lk(idx->mu);
-    HG_HIP(hipSetDevice(idx->device));
     hipStream_t st = idx->stream;
-    HG_TRY(begin_call(idx, st));
+    Call call;
+    HG_TRY(call.open(idx, st));
     const size_t sbytes = sizeof(double) * static_cast<size_t>(nlist) * idx->dim;
     HG_TRY(idx->s_misc.ensure(sizeof(int64_t) * (nlist + 1)));
     HG_TRY(idx->s_misc2.ensure(sizeof(int32_t) * std::max<int64_t>(idx->n, 1)));
@@ -1788,32 +1786,30 @@ int hnswgpu_list_sums(hnswgpu_index *idx, int32_t nlist, const int64_t *list_off
                        idx->s_misc.as<int64_t>(), idx->s_misc2.as<int32_t>(), idx->s_tile.as<double>());
     HG_HIP(hipGetLastError());
     HG_HIP(hipMemcpyAsync(out_sums, idx->s_tile.p, sbytes, hipMemcpyDeviceToHost, st));
-    HG_TRY(end_call(idx, st));
-    HG_HIP(hipStreamSynchronize(st));
-    return 0;
+    HG_TRY(call.sync());
+    return call.close();
 }
 
 int hnswgpu_kmeanspp(hnswgpu_index *idx, int32_t nlist, int64_t seed, int32_t *out_rows) {
     HG_REQUIRE(idx && out_rows, HNSWGPU_EINVAL, "null argument");
     HG_REQUIRE(nlist >= 1 && idx->n >= 1, HNSWGPU_EINVAL, "need nlist >= 1 and a non-empty index");
-    std::lock_guard<std::mutex> lk(idx->mu);
-    HG_HIP(hipSetDevice(idx->device));
+    Call call;
+    HG_TRY(call.open(idx, idx->stream));
     std::vector<int32_t> chosen;
-    HG_TRY(begin_call(idx, idx->stream));
     HG_TRY(kmeanspp_device(idx, nlist, seed, chosen, idx->stream));
     memcpy(out_rows, chosen.data(), sizeof(int32_t) * nlist);
-    return 0;
+    return call.close();
 }
 
 int hnswgpu_ivf_build(hnswgpu_index *idx, int32_t nlist, int32_t max_iter, int64_t seed) {
     HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
     HG_REQUIRE(nlist >= 1 && max_iter >= 0, HNSWGPU_EINVAL, "bad nlist / max_iter");
     HG_REQUIRE(idx->n >= 1, HNSWGPU_ESTATE, "cannot partition an empty index");
-    std::lock_guard<std::mutex> lk(idx->mu);
-    HG_HIP(hipSetDevice(idx->device));
     hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
     const int64_t n = idx->n;
-    HG_TRY(quiesce(idx, st));  // see set_ivf_impl: retires every earlier call on this handle, and only those
+    HG_TRY(call.quiesce());  // see set_ivf_impl: retires every earlier call on this handle, and only those
     free_ivf(idx);
     std::vector<int32_t> chosen;
     HG_TRY(kmeanspp_device(idx, nlist, seed, chosen, st));
@@ -1844,7 +1840,7 @@ int hnswgpu_ivf_build(hnswgpu_index *idx, int32_t nlist, int32_t max_iter, int64
     }
     HG_TRY(install_lists(idx, nlist, off.data(), ids.data(), st));
     HG_TRY(download_centroids(idx, st));
-    return 0;
+    return call.close();
 }
 
 static int check_ivf_args(const hnswgpu_index *idx, const void *Q, int32_t nq, int32_t k, int32_t nprobe,
@@ -1861,12 +1857,11 @@ int hnswgpu_ivf_search_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int
                            int32_t *d_out_ids, float *d_out_dist, void *stream) {
     HG_TRY(check_ivf_args(idx, d_Q, nq, k, nprobe, d_out_ids, d_out_dist));
     if (nq == 0) return 0;
-    std::lock_guard<std::mutex> lk(idx->mu);
-    HG_HIP(hipSetDevice(idx->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    HG_TRY(begin_call(idx, st));
+    Call call;
+    HG_TRY(call.open(idx, st));
     HG_TRY(ivf_search_enqueue(idx, d_Q, nq, k, nprobe, d_out_ids, d_out_dist, nullptr, st));
-    return end_call(idx, st);
+    return call.close();
 }
 
 int hnswgpu_ivf_search_shard_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t nprobe,
@@ -1874,12 +1869,11 @@ int hnswgpu_ivf_search_shard_dev(hnswgpu_index *idx, const float *d_Q, int32_t n
     HG_TRY(check_ivf_args(idx, d_Q, nq, k, nprobe, d_out_ids, d_out_dist));
     if (nq == 0) return 0;
     HG_REQUIRE(d_out_order, HNSWGPU_EINVAL, "d_out_order is null");
-    std::lock_guard<std::mutex> lk(idx->mu);
-    HG_HIP(hipSetDevice(idx->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    HG_TRY(begin_call(idx, st));
+    Call call;
+    HG_TRY(call.open(idx, st));
     HG_TRY(ivf_search_enqueue(idx, d_Q, nq, k, nprobe, d_out_ids, d_out_dist, nullptr, st, nullptr, d_out_order));
-    return end_call(idx, st);
+    return call.close();
 }
 
 int hnswgpu_ivf_search_lists(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t nprobe,
@@ -1889,23 +1883,17 @@ int hnswgpu_ivf_search_lists(hnswgpu_index *idx, const float *Q, int32_t nq, int
     HG_REQUIRE(probes, HNSWGPU_EINVAL, "probes is null");
     for (int64_t i = 0; i < static_cast<int64_t>(nq) * nprobe; i++)
         HG_REQUIRE(probes[i] >= -1 && probes[i] < idx->nlist, HNSWGPU_EINVAL, "probe list id out of range");
-    std::lock_guard<std::mutex> lk(idx->mu);
-    HG_HIP(hipSetDevice(idx->device));
     hipStream_t st = idx->stream;
-    HG_TRY(begin_call(idx, st));
-    int64_t cnt = static_cast<int64_t>(nq) * k;
-    HG_TRY(upload_queries(idx, Q, nq, st));
-    HG_TRY(idx->s_ids.ensure(sizeof(int32_t) * cnt));
-    HG_TRY(idx->s_outd.ensure(sizeof(float) * cnt));
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_TRY(call.stage_in(Q, nq, k));
     HG_TRY(idx->s_probes.ensure(sizeof(int32_t) * static_cast<size_t>(nq) * nprobe));
     HG_HIP(hipMemcpyAsync(idx->s_probes.p, probes, sizeof(int32_t) * static_cast<size_t>(nq) * nprobe,
                           hipMemcpyHostToDevice, st));
     HG_TRY(ivf_search_enqueue(idx, idx->s_q.as<float>(), nq, k, nprobe, idx->s_ids.as<int32_t>(),
                               idx->s_outd.as<float>(), nullptr, st, idx->s_probes.as<int32_t>()));
-    HG_HIP(hipMemcpyAsync(out_ids, idx->s_ids.p, sizeof(int32_t) * cnt, hipMemcpyDeviceToHost, st));
-    HG_HIP(hipMemcpyAsync(out_dist, idx->s_outd.p, sizeof(float) * cnt, hipMemcpyDeviceToHost, st));
-    HG_HIP(hipStreamSynchronize(st));
-    return 0;
+    HG_TRY(call.stage_out(out_ids, out_dist, static_cast<int64_t>(nq) * k));
+    return call.close();
 }
 
 // One launch for a set of queued synchronous IVF requests with the same (k, nprobe); see combine_search.
@@ -1923,117 +1911,73 @@ __global__ void slot_signal_kernel(uint32_t *flag, uint32_t val) {
 constexpr int32_t kIvfZcMaxQueries = 16;
 static int ivf_search_batch_slot(hnswgpu_index *idx, const std::vector<hnswgpu_index::SearchReq *> &batch, int32_t total) {
     const int32_t k = batch[0]->k;
-    const size_t cnt = static_cast<size_t>(total) * k;
-    const size_t qb = sizeof(float) * static_cast<size_t>(total) * idx->dim, ib = sizeof(int32_t) * cnt, db = sizeof(float) * cnt;
-    const size_t o_q = 64, o_i = (o_q + qb + 63) & ~size_t(63), o_d = o_i + ((ib + 63) & ~size_t(63)), bytes = o_d + db;
-    hnswgpu_index::Slot *slot = nullptr;
+    const BatchBlock b(idx->dim, total, k, false);
     std::unique_lock<std::mutex> sl;
-    for (auto &s : idx->slots) {
-        sl = std::unique_lock<std::mutex>(s.mu, std::try_to_lock);
-        if (sl.owns_lock()) {
-            slot = &s;
-            break;
-        }
-    }
-    if (!slot) {
-        slot = &idx->slots[0];
-        sl = std::unique_lock<std::mutex>(slot->mu);
-    }
-    HG_HIP(hipSetDevice(idx->device));
-    HG_TRY(slot_prepare(*slot, bytes));
-    char *hp = static_cast<char *>(slot->h), *dp = static_cast<char *>(slot->d);
-    float *hq = reinterpret_cast<float *>(hp + o_q);
-    size_t o = 0;
-    for (auto *r : batch) {
-        memcpy(hq + o, r->Q, sizeof(float) * static_cast<size_t>(r->nq) * idx->dim);
-        o += static_cast<size_t>(r->nq) * idx->dim;
-    }
-    const uint32_t flag_val = ++slot->seq;
-    volatile uint32_t *h_flag = reinterpret_cast<volatile uint32_t *>(hp);
+    hnswgpu_index::Slot *slot = BatchBlock::acquire_slot(idx, sl);
+    HG_TRY(slot_prepare(*slot, b.bytes, idx->device));
+    void *hp = slot->h, *dp = slot->d;
+    b.pack(hp, batch);
+    IvfHostFlag hf = {b.flag(dp), ++slot->seq, false};
     {
-        std::lock_guard<std::mutex> lk(idx->mu);  // the index state is read (and the launches enqueued) under its lock
+        Call call;  // the index state is read (and the launches enqueued) under its lock; the wait for the flag is outside
+        HG_TRY(call.open(idx, slot->st));
         HG_REQUIRE(idx->nlist > 0, HNSWGPU_ESTATE, "index has no IVF lists (call hnswgpu_ivf_build / hnswgpu_set_ivf)");
         const int32_t np = std::min(batch[0]->ef, idx->nlist);
-        HG_TRY(begin_call(idx, slot->st));
-        idx->zc_flag = reinterpret_cast<uint32_t *>(dp);
-        idx->zc_val = flag_val;
-        idx->zc_taken = false;
-        const int rc = ivf_search_enqueue(idx, reinterpret_cast<const float *>(dp + o_q), total, k, np, reinterpret_cast<int32_t *>(dp + o_i),
-                                          reinterpret_cast<float *>(dp + o_d), nullptr, slot->st);
-        idx->zc_flag = nullptr;
-        if (rc) return rc;
-        if (!idx->zc_taken) {  // (a path without the finish kernel: the flag by a launch of its own behind it)
-            hipLaunchKernelGGL(slot_signal_kernel, dim3(1), dim3(1), 0, slot->st, reinterpret_cast<uint32_t *>(dp), flag_val);
+        HG_TRY(ivf_search_enqueue(idx, b.queries(dp), total, k, np, b.ids(dp), b.dist(dp), nullptr, slot->st, nullptr, nullptr, &hf));
+        if (!hf.taken) {  // (a path without the finish kernel: the flag by a launch of its own behind it)
+            hipLaunchKernelGGL(slot_signal_kernel, dim3(1), dim3(1), 0, slot->st, hf.flag, hf.val);
             HG_HIP(hipGetLastError());
         }
-        HG_TRY(end_call(idx, slot->st));
+        HG_TRY(call.close());
     }
-    HG_TRY(slot_wait(*slot, h_flag, flag_val));
-    const int32_t *hi = reinterpret_cast<const int32_t *>(hp + o_i);
-    const float *hd = reinterpret_cast<const float *>(hp + o_d);
-    int64_t q0 = 0;
-    for (auto *r : batch) {
-        const size_t c = static_cast<size_t>(r->nq) * k;
-        memcpy(r->out_ids, hi + q0 * k, sizeof(int32_t) * c);
-        memcpy(r->out_dist, hd + q0 * k, sizeof(float) * c);
-        q0 += r->nq;
-    }
+    HG_TRY(slot_wait(*slot, b.flag(hp), hf.val));
+    b.scatter(hp, batch);
     return 0;
 }
 
 static int ivf_search_batch(hnswgpu_index *idx, const std::vector<hnswgpu_index::SearchReq *> &batch, int32_t total) {
     if (tune(HNSWGPU_TUNE_ZEROCOPY, 1) != 0 && total <= kIvfZcMaxQueries) return ivf_search_batch_slot(idx, batch, total);
     const int32_t k = batch[0]->k;
-    const int64_t cnt = static_cast<int64_t>(total) * k;
-    std::lock_guard<std::mutex> lk(idx->mu);
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
     // under the lock: a concurrent set_ivf / ivf_build may have replaced (or a failed one removed) the lists since the
     // caller's argument check
     HG_REQUIRE(idx->nlist > 0, HNSWGPU_ESTATE, "index has no IVF lists (call hnswgpu_ivf_build / hnswgpu_set_ivf)");
     const int32_t np = std::min(batch[0]->ef, idx->nlist);
-    HG_HIP(hipSetDevice(idx->device));
-    hipStream_t st = idx->stream;
-    HG_TRY(begin_call(idx, st));
-    HG_TRY(idx->s_ids.ensure(sizeof(int32_t) * cnt));
-    HG_TRY(idx->s_outd.ensure(sizeof(float) * cnt));
-    const size_t qb = sizeof(float) * static_cast<size_t>(total) * idx->dim, ib = sizeof(int32_t) * cnt, db = sizeof(float) * cnt;
-    HG_TRY(ensure_pinned(idx, qb + ib + db + 64));
-    char *hp = static_cast<char *>(idx->h_pin);
-    float *hq = reinterpret_cast<float *>(hp);
-    int32_t *hi = reinterpret_cast<int32_t *>(hp + qb);
-    float *hd = reinterpret_cast<float *>(hp + qb + ib);
-    size_t o = 0;
-    for (auto *r : batch) {
-        memcpy(hq + o, r->Q, sizeof(float) * static_cast<size_t>(r->nq) * idx->dim);
-        o += static_cast<size_t>(r->nq) * idx->dim;
-    }
-    HG_TRY(upload_queries(idx, hq, total, st));
+    const BatchBlock b(idx->dim, total, k, false);
+    HG_TRY(ensure_pinned(idx, b.bytes));
+    void *hp = idx->h_pin;
+    b.pack(hp, batch);
+    HG_TRY(call.stage_in(b.queries(hp), total, k));
     HG_TRY(ivf_search_enqueue(idx, idx->s_q.as<float>(), total, k, np, idx->s_ids.as<int32_t>(), idx->s_outd.as<float>(),
                               nullptr, st));
-    HG_HIP(hipMemcpyAsync(hi, idx->s_ids.p, ib, hipMemcpyDeviceToHost, st));
-    HG_HIP(hipMemcpyAsync(hd, idx->s_outd.p, db, hipMemcpyDeviceToHost, st));
-    HG_HIP(hipStreamSynchronize(st));
-    int64_t q0 = 0;
-    for (auto *r : batch) {
-        const size_t c = static_cast<size_t>(r->nq) * k;
-        memcpy(r->out_ids, hi + q0 * k, sizeof(int32_t) * c);
-        memcpy(r->out_dist, hd + q0 * k, sizeof(float) * c);
-        q0 += r->nq;
+    HG_TRY(call.stage_out(b.ids(hp), b.dist(hp), static_cast<int64_t>(total) * k));
+    b.scatter(hp, batch);
+    return call.close();
+}
+
+// The handle's one-off measurement as a call of its own; once it is made: a look under the lock, no runtime call (this is on the
+// path of every synchronous search).
+static int ivf_calibrate_once(hnswgpu_index *idx) {
+    {
+        std::lock_guard<std::mutex> lk(idx->mu);
+        if (idx->ivf_calibrated || idx->nlist == 0) return 0;
     }
-    return 0;
+    Call call;
+    HG_TRY(call.open(idx, idx->stream));
+    if (!idx->ivf_calibrated && idx->nlist > 0) HG_TRY(ivf_calibrate(idx, idx->stream));
+    return call.close();
 }
 
 int hnswgpu_ivf_stream_state(hnswgpu_index *idx, int32_t *off) {
     HG_REQUIRE(idx && off, HNSWGPU_EINVAL, "null argument");
-    std::lock_guard<std::mutex> lk(idx->mu);
+    Call call;
+    HG_TRY(call.open(idx, idx->stream));
     HG_REQUIRE(idx->nlist > 0, HNSWGPU_ESTATE, "index has no IVF lists");
-    if (!idx->ivf_calibrated) {
-        HG_HIP(hipSetDevice(idx->device));
-        HG_TRY(begin_call(idx, idx->stream));
-        HG_TRY(ivf_calibrate(idx, idx->stream));
-        HG_TRY(end_call(idx, idx->stream));
-    }
+    if (!idx->ivf_calibrated) HG_TRY(ivf_calibrate(idx, idx->stream));
     *off = idx->ivf_stream_off ? 1 : 0;
-    return 0;
+    return call.close();
 }
 
 int hnswgpu_ivf_set_stream_state(hnswgpu_index *idx, int32_t off) {
@@ -2065,15 +2009,7 @@ int hnswgpu_ivf_search(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k
         // (the handle's one-off measurement of what the int8 bounds separate decides ivf_tile_rule: it runs here, under
         // the index lock, before the predicate is built -- concurrent first calls would otherwise combine by the
         // pre-calibration boundary and run on the post-calibration kernel)
-        {
-            std::lock_guard<std::mutex> lk(idx->mu);
-            if (!idx->ivf_calibrated && idx->nlist > 0) {
-                HG_HIP(hipSetDevice(idx->device));
-                HG_TRY(begin_call(idx, idx->stream));
-                HG_TRY(ivf_calibrate(idx, idx->stream));
-                HG_TRY(end_call(idx, idx->stream));
-            }
-        }
+        HG_TRY(ivf_calibrate_once(idx));
         // the summation order a batch of `total` queries gets: the predicate ivf_search_plan itself decides by (TileRule), on the
         // BATCH's nprobe (the leader that evaluates this may have asked for another one); requests of one batch share k.
         // (This is off the search path: the table is read here, once per call, and the rule is carried into the combiner.)
@@ -2095,26 +2031,20 @@ int hnswgpu_ivf_search(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k
                 return ivf_search_batch(idx, batch, total);
             });
     }
-    std::lock_guard<std::mutex> lk(idx->mu);
-    HG_HIP(hipSetDevice(idx->device));
     hipStream_t st = idx->stream;
-    HG_TRY(begin_call(idx, st));
+    Call call;
+    HG_TRY(call.open(idx, st));
     int32_t np = std::min(nprobe, idx->nlist);
-    int64_t cnt = static_cast<int64_t>(nq) * k;
-    HG_TRY(upload_queries(idx, Q, nq, st));
-    HG_TRY(idx->s_ids.ensure(sizeof(int32_t) * cnt));
-    HG_TRY(idx->s_outd.ensure(sizeof(float) * cnt));
+    HG_TRY(call.stage_in(Q, nq, k));
     HG_TRY(idx->s_probes.ensure(sizeof(int32_t) * static_cast<size_t>(nq) * np));
     HG_TRY(ivf_search_enqueue(idx, idx->s_q.as<float>(), nq, k, np, idx->s_ids.as<int32_t>(), idx->s_outd.as<float>(),
                               idx->s_probes.as<int32_t>(), st));
-    HG_HIP(hipMemcpyAsync(out_ids, idx->s_ids.p, sizeof(int32_t) * cnt, hipMemcpyDeviceToHost, st));
-    HG_HIP(hipMemcpyAsync(out_dist, idx->s_outd.p, sizeof(float) * cnt, hipMemcpyDeviceToHost, st));
     if (np < nprobe)
         for (int64_t i = 0; i < static_cast<int64_t>(nq) * nprobe; i++) out_probes[i] = -1;
     HG_HIP(hipMemcpy2DAsync(out_probes, sizeof(int32_t) * nprobe, idx->s_probes.p, sizeof(int32_t) * np,
                             sizeof(int32_t) * np, nq, hipMemcpyDeviceToHost, st));
-    HG_HIP(hipStreamSynchronize(st));
-    return 0;
+    HG_TRY(call.stage_out(out_ids, out_dist, static_cast<int64_t>(nq) * k));
+    return call.close();
 }
 
 }  // extern "C"

@@ -54,7 +54,7 @@ static int get(FILE *f, std::vector<T> &v, size_t cnt) {
 }
 
 // Body of hnswgpu_save, writing to an already opened temporary file.
-static int save_to(hnswgpu_index *idx, FILE *f) {
+static int save_to(hnswgpu_index *idx, Call &call, FILE *f) {
     FileHeader h;
     memset(&h, 0, sizeof(h));
     memcpy(h.magic, "HNSWGPU1", 8);
@@ -72,10 +72,9 @@ static int save_to(hnswgpu_index *idx, FILE *f) {
     HG_TRY(put(f, &h, 1));
     if (idx->n > 0) {
         std::vector<float> base(static_cast<size_t>(idx->n) * idx->dim);
-        HG_TRY(begin_call(idx, idx->stream));
         HG_HIP(hipMemcpy2DAsync(base.data(), sizeof(float) * idx->dim, idx->d_base, sizeof(float) * idx->ld,
                                 sizeof(float) * idx->dim, idx->n, hipMemcpyDeviceToHost, idx->stream));
-        HG_HIP(hipStreamSynchronize(idx->stream));
+        HG_TRY(call.sync());
         HG_TRY(put(f, base.data(), base.size()));
     }
     if (idx->has_graph) {
@@ -114,12 +113,12 @@ extern "C" {
 
 int hnswgpu_save(hnswgpu_index *idx, const char *path) {
     HG_REQUIRE(idx && path, HNSWGPU_EINVAL, "null argument");
-    std::lock_guard<std::mutex> lk(idx->mu);
+    Call call;
+    HG_TRY(call.open(idx, idx->stream));
     // a shard of a larger IVF index (hnswgpu_set_ivf_shard) numbers its candidates by the WHOLE index's list lengths, which
     // the file format does not carry: loaded back it would silently be an ordinary index with another tie order
     HG_REQUIRE(idx->h_glistlen.empty(), HNSWGPU_ESTATE,
                "this handle holds a shard of a larger IVF index (hnswgpu_set_ivf_shard): save the whole index instead");
-    HG_HIP(hipSetDevice(idx->device));
     // written beside the target -- under a name of this process's and this call's own: two savers of one path never share
     // a temporary -- flushed to the disk, and renamed over the target once complete and closed: a reader never sees half a
     // file, a crash never leaves a renamed file with missing contents, a failed save leaves the previous file untouched
@@ -136,7 +135,7 @@ int hnswgpu_save(hnswgpu_index *idx, const char *path) {
     HG_REQUIRE(f, HNSWGPU_EINVAL, "cannot open %s for writing", tmp.c_str());
     int rc;
     try {
-        rc = save_to(idx, f);
+        rc = save_to(idx, call, f);
     } catch (const std::bad_alloc &) {
         set_error("host allocation failed while saving the index");
         rc = HNSWGPU_ENOMEM;
@@ -154,7 +153,7 @@ int hnswgpu_save(hnswgpu_index *idx, const char *path) {
         rc = HNSWGPU_EINVAL;
     }
     if (rc != 0) (void)remove(tmp.c_str());
-    return rc;
+    return rc != 0 ? rc : call.close();
 }
 
 static int load_from(FILE *fp, const char *path, int32_t device, hnswgpu_index **out) {

@@ -1,6 +1,6 @@
 """Developer tool: the reference's multi-thread protocol (helper/parallel_search.clj:15-49 -- T threads, each issuing
 single-query search-knn calls) against the synchronous C entry point, which combines concurrent callers into one
-launch.  usage: python tools/concurrent_callers.py [ef]"""
+launch.  usage: python tools/concurrent_callers.py [ef] [threads,threads,...]"""
 import os
 import sys
 import threading
@@ -18,7 +18,7 @@ queries = bench.make_31k("manifold", 43, 4096)
 idx = engine.Index(base, "cosine", 0)
 idx.hnsw_build(16, 200, 42)
 want, _ = idx.hnsw_search(queries, 10, ef)
-for T in (1, 5, 20, 64, 128):
+for T in [int(x) for x in (sys.argv[2] if len(sys.argv) > 2 else "1,5,20,64,128").split(",")]:
     per = 4096 // T if T > 1 else 512
     got = np.full((T * per, 10), -1, np.int32)
 

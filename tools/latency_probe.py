@@ -1,4 +1,5 @@
-"""Developer tool: single-query latency of the synchronous host entry points against the kernel time.
+"""Developer tool: single-query latency of the synchronous host entry points against the kernel time (HNSW), and of the
+host IVF entry point over the same rows (64 lists, nprobe 8: the mapped-block path of small synchronous batches).
 usage: [HNSWGPU_TUNE=ZEROCOPY=0] python tools/latency_probe.py [ef]"""
 import os
 import sys
@@ -53,3 +54,11 @@ for nq in [int(x) for x in os.environ.get("PROBE_NQ", "1,20,200").split(",")]:
         torch.cuda.synchronize()
         lat.append((time.perf_counter() - t) * 1e6)
     print("   _dev entry + torch sync: %s" % pct(lat[10:]))
+
+idx.ivf_build(64, 5, 42)
+lat = []
+for i in range(220):
+    t = time.perf_counter()
+    idx.ivf_search(queries[i:i + 1], 10, 8)
+    lat.append((time.perf_counter() - t) * 1e6)
+print("ivf host entry,   1 query  per call: %s" % pct(lat[20:]))
