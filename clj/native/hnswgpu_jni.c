@@ -167,3 +167,41 @@ JNIEXPORT jlong JNICALL Java_hnsw_gpu_Native_load(JNIEnv *env, jclass c, jstring
     if (rc != 0) throw_last(env);
     return (jlong)(intptr_t)idx;
 }
+
+/* ---- filtered search (FilterableIndex/search-knn-filtered*, src/hnsw/api/protocol.clj:34-41,97-102): `allow` is the call's
+ * mask, (n + 31) / 32 ints, row i passes iff bit (i & 31) of allow[i >> 5] is set ---- */
+JNIEXPORT jint JNICALL Java_hnsw_gpu_Native_exactKnnFiltered(JNIEnv *env, jclass c, jlong h, jfloatArray q, jint nq, jint k,
+                                                             jintArray allow, jintArray ids, jfloatArray dist) {
+    if (!q || !allow || !ids || !dist) return throw_iae(env, "exactKnnFiltered: null array");
+    jfloat *pq = (*env)->GetFloatArrayElements(env, q, NULL);
+    jint *pa = (*env)->GetIntArrayElements(env, allow, NULL);
+    jint *pi = (*env)->GetIntArrayElements(env, ids, NULL);
+    jfloat *pd = (*env)->GetFloatArrayElements(env, dist, NULL);
+    int rc = (pq && pa && pi && pd)
+                 ? hnswgpu_exact_knn_filtered((hnswgpu_index *)(intptr_t)h, pq, nq, k, (const uint32_t *)pa, (int32_t *)pi, pd)
+                 : HNSWGPU_ENOMEM; /* OutOfMemoryError is pending */
+    if (pq) (*env)->ReleaseFloatArrayElements(env, q, pq, JNI_ABORT);
+    if (pa) (*env)->ReleaseIntArrayElements(env, allow, pa, JNI_ABORT);
+    if (pi) (*env)->ReleaseIntArrayElements(env, ids, pi, 0);
+    if (pd) (*env)->ReleaseFloatArrayElements(env, dist, pd, 0);
+    if (rc != 0 && rc != HNSWGPU_ENOMEM) throw_last(env);
+    return rc;
+}
+
+JNIEXPORT jint JNICALL Java_hnsw_gpu_Native_hnswSearchFiltered(JNIEnv *env, jclass c, jlong h, jfloatArray q, jint nq, jint k,
+                                                               jint ef, jintArray allow, jintArray ids, jfloatArray dist) {
+    if (!q || !allow || !ids || !dist) return throw_iae(env, "hnswSearchFiltered: null array");
+    jfloat *pq = (*env)->GetFloatArrayElements(env, q, NULL);
+    jint *pa = (*env)->GetIntArrayElements(env, allow, NULL);
+    jint *pi = (*env)->GetIntArrayElements(env, ids, NULL);
+    jfloat *pd = (*env)->GetFloatArrayElements(env, dist, NULL);
+    int rc = (pq && pa && pi && pd) ? hnswgpu_hnsw_search_filtered((hnswgpu_index *)(intptr_t)h, pq, nq, k, ef, (const uint32_t *)pa,
+                                                                   (int32_t *)pi, pd, NULL)
+                                    : HNSWGPU_ENOMEM; /* OutOfMemoryError is pending */
+    if (pq) (*env)->ReleaseFloatArrayElements(env, q, pq, JNI_ABORT);
+    if (pa) (*env)->ReleaseIntArrayElements(env, allow, pa, JNI_ABORT);
+    if (pi) (*env)->ReleaseIntArrayElements(env, ids, pi, 0);
+    if (pd) (*env)->ReleaseFloatArrayElements(env, dist, pd, 0);
+    if (rc != 0 && rc != HNSWGPU_ENOMEM) throw_last(env);
+    return rc;
+}

@@ -20,7 +20,8 @@
      (from-ultra-graph graph)                                        ; a graph built by the reference's own insert-single
      (from-ivf-flat-index ivf)                                       ; an IVFFlatIndex built by the reference's own k-means
      (save idx path) / (load-index path ids)                         ; helper/index-io save-index / load-index
-   and, at the bottom, the extend-type that makes GpuIndex an ANNIndex / BatchSearchIndex / PersistableIndex next to the
+     (search-knn-filtered index query-vec k filter-fn)               ; FilterableIndex/search-knn-filtered*, on the device
+   and, at the bottom, the extend-type that makes GpuIndex an ANNIndex / BatchSearchIndex / FilterableIndex / PersistableIndex next to the
    records src/hnsw/api/unified.clj:30-95 extends."
   (:require [hnsw.api.protocol :as proto])
   (:import [java.lang.foreign Arena FunctionDescriptor Linker MemorySegment SymbolLookup ValueLayout]
@@ -163,6 +164,59 @@
             (check (.invokeWithArguments ^MethodHandle @h-exact [(:handle idx) qa (int nq) (int k) ia da]))
             (mapv #(results idx ia da % k) (range nq)))
           (search-batch idx queries k :ef ef))))))
+
+;; ---- filtered search (FilterableIndex/search-knn-filtered*, src/hnsw/api/protocol.clj:34-41,97-102) ----
+(def ^:private h-exact-filtered
+  (delay (fn-handle "hnswgpu_exact_knn_filtered" (FunctionDescriptor/of I (into-array [P P I I P P P])))))
+(def ^:private h-search-filtered
+  (delay (fn-handle "hnswgpu_hnsw_search_filtered" (FunctionDescriptor/of I (into-array [P P I I I P P P P])))))
+
+(defn filtered-plan
+  "[:scan | :graph, ef'] for n rows of which p pass (hnsw-clj_amd/ultra_fast.py: filtered_plan): the reference over-fetches by 3
+   (protocol.clj:101), so a result list must hold ef-need = ceil(3 k n / p) entries to expect 3k passing ones; the exact scan of
+   the passing rows serves the call when nothing passes, when ef-need exceeds the 1024 list entries the filtered traversal
+   looks at, or when p <= ef'."
+  [n p k ef]
+  (let [ef0 (if (pos? ef) ef (max k 50))]
+    (if (zero? p)
+      [:scan ef0]
+      (let [ef-need (quot (+ (* 3 k n) (dec p)) p)
+            ef2 (max ef0 ef-need)]
+        [(if (or (> ef-need 1024) (<= p ef2)) :scan :graph) ef2]))))
+
+(defn search-batch-filtered
+  "search-knn-filtered* for a batch with ONE predicate on the caller's ids, evaluated once per row here into the call's
+   allow-mask ((n + 31) / 32 words, bit (i & 31) of word i >> 5).  :graph walks the graph at ef' and keeps the first k passing
+   entries of every result list; :scan returns the EXACT k nearest passing rows."
+  [idx queries k filter-fn & {:keys [ef] :or {ef 0}}]
+  (with-open [arena (Arena/ofConfined)]
+    (let [n (count (:ids idx))
+          nq (count queries)
+          words (quot (+ n 31) 32)
+          mask (.allocate arena (* 4 (max words 1)) 4)
+          _ (.fill mask (byte 0))
+          p (reduce (fn [p i]
+                      (if (filter-fn (nth (:ids idx) i))
+                        (let [w (quot i 32)]
+                          (.setAtIndex mask I (long w) (unchecked-int (bit-or (.getAtIndex mask I (long w))
+                                                                               (bit-shift-left 1 (rem i 32)))))
+                          (inc p))
+                        p))
+                    0 (range n))
+          [plan ef2] (filtered-plan n p k ef)
+          q (floats-of arena (vec queries) (:dim idx))
+          ids (.allocate arena (* 4 nq k) 4)
+          ds (.allocate arena (* 4 nq k) 4)]
+      (if (= plan :scan)
+        (check (.invokeWithArguments ^MethodHandle @h-exact-filtered [(:handle idx) q (int nq) (int k) mask ids ds]))
+        (check (.invokeWithArguments ^MethodHandle @h-search-filtered
+                                     [(:handle idx) q (int nq) (int k) (int ef2) mask ids ds MemorySegment/NULL])))
+      (mapv #(results idx ids ds % k) (range nq)))))
+
+(defn search-knn-filtered
+  "One query through search-batch-filtered: seq of {:id :distance} ascending, fewer than k when fewer rows pass."
+  [idx ^doubles query-vec k filter-fn]
+  (first (search-batch-filtered idx [query-vec] k filter-fn)))
 
 (defn build-ivf-index
   "hnsw.ann.partition.ivf-flat/build-index (src/hnsw/ann/partition/ivf_flat.clj:137-211,300-303)."
@@ -398,5 +452,10 @@
     (if (= :ivf (:kind this))
       (search-ivf-batch this queries k :num-probes (mode->probes mode 4))
       (search-batch this queries k)))
+  proto/FilterableIndex
+  (search-knn-filtered* [this query k filter-fn mode]
+    (if (= :ivf (:kind this))
+      (proto/default-filtered-search this query k filter-fn mode)   ; IVF handles keep the post-filter of protocol.clj:97-102
+      (search-knn-filtered this query k filter-fn)))
   proto/PersistableIndex
   (save-index* [this filepath] (save this filepath)))

@@ -77,6 +77,10 @@ _SIGS = {
     "hnswgpu_rerank_dev": ["p", "p", "i32", "p", "i32", "i32", "p", "p", "p"],
     "hnswgpu_dense_distances": ["p", "p", "i32", "p"],
     "hnswgpu_dense_distances_dev": ["p", "p", "i32", "p", "p"],
+    "hnswgpu_exact_knn_filtered": ["p", "p", "i32", "i32", "p", "p", "p"],
+    "hnswgpu_exact_knn_filtered_dev": ["p", "p", "i32", "i32", "p", "p", "p", "p"],
+    "hnswgpu_hnsw_search_filtered": ["p", "p", "i32", "i32", "i32", "p", "p", "p", "p"],
+    "hnswgpu_hnsw_search_filtered_dev": ["p", "p", "i32", "i32", "i32", "p", "p", "p", "p", "p"],
     "hnswgpu_save": ["p", "p"],
     "hnswgpu_load": ["p", "i32", "p"],
     "hnswgpu_set_profiling": ["p", "i32"],

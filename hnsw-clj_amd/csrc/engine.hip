@@ -18,6 +18,7 @@
 #include "tile_kernels.hpp"
 #include "l2_kernels.hpp"
 #include "stream_kernels.hpp"
+#include "filter_kernels.hpp"
 
 namespace hg {
 
@@ -1927,6 +1928,156 @@ __global__ __launch_bounds__(kWave) void merge_keyed_kernel(const int32_t *ids, 
     }
 }
 
+// ---- filtered search: mask -> passing list -> gathered group scan -> select -> decode (filter_kernels.hpp) ----
+int64_t mask_popcount(const uint32_t *allow, int64_t n) {
+    const int64_t nwords = (n + 31) / 32;
+    int64_t p = 0;
+    for (int64_t w = 0; w + 1 < nwords; w++) p += __builtin_popcount(allow[w]);
+    if (nwords > 0) {
+        const int tail = static_cast<int>(n & 31);
+        p += __builtin_popcount(tail ? allow[nwords - 1] & ((1u << tail) - 1u) : allow[nwords - 1]);
+    }
+    return p;
+}
+
+// The ascending list of passing rows into s_fpass, their number into *p: three small launches (per-workgroup popcounts,
+// one-workgroup scan, scatter).  p_host >= 0: the caller counted on the host; otherwise the 8-byte total is read back
+// once, between the scan and the scatter (the list is sized by it), and the calling thread waits for `st` there.
+static int mask_compact(hnswgpu_index *idx, const uint32_t *d_allow, int64_t p_host, int64_t *p, hipStream_t st) {
+    *p = 0;
+    if (p_host == 0) return 0;
+    MaskArgs m;
+    memset(&m, 0, sizeof(m));
+    m.allow = d_allow;
+    m.n = idx->n;
+    m.nwords = (idx->n + 31) / 32;
+    const int64_t nblk = (m.nwords + kMaskWordsPerWG - 1) / kMaskWordsPerWG;
+    m.nblk = static_cast<int32_t>(nblk);
+    const size_t tot_off = (sizeof(uint32_t) * static_cast<size_t>(nblk) + 7) & ~static_cast<size_t>(7);
+    HG_TRY(idx->s_fblk.ensure(tot_off + sizeof(unsigned long long)));
+    m.blk = idx->s_fblk.as<uint32_t>();
+    m.total = reinterpret_cast<unsigned long long *>(idx->s_fblk.as<char>() + tot_off);
+    hipLaunchKernelGGL(mask_count_kernel, dim3(static_cast<unsigned>(nblk)), dim3(kMaskThreads), 0, st, m);
+    hipLaunchKernelGGL(mask_scan_kernel, dim3(1), dim3(kMaskScanThreads), 0, st, m);
+    HG_HIP(hipGetLastError());
+    int64_t cnt = p_host;
+    if (cnt < 0) {
+        HG_TRY(ensure_pinned(idx, sizeof(unsigned long long)));
+        HG_HIP(hipMemcpyAsync(idx->h_pin, m.total, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HG_HIP(hipStreamSynchronize(st));
+        cnt = static_cast<int64_t>(*static_cast<unsigned long long *>(idx->h_pin));
+    }
+    HG_REQUIRE(cnt >= 0 && cnt <= idx->n, HNSWGPU_EINVAL, "the mask counts %lld passing rows of %lld", (long long)cnt, (long long)idx->n);
+    *p = cnt;
+    if (cnt == 0) return 0;
+    HG_TRY(idx->s_fpass.ensure(sizeof(int32_t) * static_cast<size_t>(cnt)));
+    m.pass_ids = idx->s_fpass.as<int32_t>();
+    m.cap = cnt;
+    hipLaunchKernelGGL(mask_scatter_kernel, dim3(static_cast<unsigned>(nblk)), dim3(kMaskThreads), 0, st, m);
+    HG_HIP(hipGetLastError());
+    return 0;
+}
+
+static int launch_filtered_group(int nch, const FilteredArgs &a, int64_t blocks, hipStream_t st) {
+    HG_REQUIRE(blocks > 0 && blocks < 2147483647LL, HNSWGPU_ELIMIT, "filtered scan grid too large (%lld blocks)", (long long)blocks);
+    const size_t lds = filtered_group_lds_bytes(a.ld);
+    const bool l2 = a.metric == METRIC_L2;
+#define CALL(N, R, L)                                                                                               \
+    do {                                                                                                            \
+        static bool fg_attr_done[64] = {};                                                                          \
+        if (attr_needed(fg_attr_done))                                                                              \
+            HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&filtered_group_kernel<N, R, L>),            \
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                   \
+        hipLaunchKernelGGL((filtered_group_kernel<N, R, L>), dim3(static_cast<unsigned>(blocks)), dim3(kTileThreads), lds, st, a); \
+    } while (0)
+    HG_DISPATCH(nch, l2, CALL);
+#undef CALL
+    HG_HIP(hipGetLastError());
+    return 0;
+}
+
+static int fill_empty_dev(int32_t *d_ids, float *d_dist, int64_t cnt, hipStream_t st) {
+    hipLaunchKernelGGL(filter_fill_kernel, dim3(static_cast<unsigned>((cnt + 255) / 256)), dim3(256), 0, st, d_ids, d_dist, cnt);
+    HG_HIP(hipGetLastError());
+    return 0;
+}
+
+// k nearest of the passing rows for every query: exact, GEMV summation order at every batch size
+static int filtered_scan_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, const uint32_t *d_allow,
+                                 int64_t p_host, int32_t *d_ids, float *d_dist, hipStream_t st) {
+    const int64_t cnt = static_cast<int64_t>(nq) * k;
+    int64_t p = 0;
+    HG_TRY(mask_compact(idx, d_allow, p_host, &p, st));
+    if (p == 0) return fill_empty_dev(d_ids, d_dist, cnt, st);
+    HG_TRY(pad_queries(idx, d_Q, idx->dim, nq, st));
+    HG_TRY(idx->s_ord.ensure(sizeof(uint32_t) * static_cast<size_t>(cnt)));
+    HG_TRY(idx->s_dist.ensure(sizeof(float) * static_cast<size_t>(cnt)));
+    // dense scratch [qb][p]; bound it to ~2 GiB by slicing the queries (whole groups)
+    const int tq = filtered_group_queries(idx->ld);
+    int64_t qb = std::max<int64_t>(tq, ((2LL << 30) / (4 * p)) / tq * tq);
+    qb = std::min<int64_t>(qb, (static_cast<int64_t>(nq) + tq - 1) / tq * tq);
+    HG_TRY(idx->s_tile.ensure(sizeof(float) * static_cast<size_t>(qb) * p));
+    for (int64_t q0 = 0; q0 < nq; q0 += qb) {
+        const int32_t nb = static_cast<int32_t>(std::min<int64_t>(qb, nq - q0));
+        FilteredArgs f;
+        memset(&f, 0, sizeof(f));
+        f.rows = idx->d_base;
+        f.row_norms = idx->d_norms;
+        f.ld = idx->ld;
+        f.metric = idx->metric;
+        f.Qp = idx->s_qp.as<float>() + q0 * idx->ld;
+        f.q_norms = idx->s_qn.as<float>() + q0;
+        f.nq = nb;
+        f.tq = tq;
+        f.ngroups = (nb + tq - 1) / tq;
+        f.pass_ids = idx->s_fpass.as<int32_t>();
+        f.p = p;
+        // chunks of whole 256-position tiles, about 2048 workgroups in all: a workgroup stages its query group once per chunk
+        const int64_t tiles = (p + kTileRows - 1) / kTileRows;
+        const int64_t want = std::max<int64_t>(1, std::min<int64_t>(tiles, (2048 + f.ngroups - 1) / f.ngroups));
+        f.chunk_rows = (tiles + want - 1) / want * kTileRows;
+        const int64_t nchunks = (p + f.chunk_rows - 1) / f.chunk_rows;
+        f.out = idx->s_tile.as<float>();
+        hipEvent_t e0;
+        prof_begin(idx, PROF_IVF_SCAN, st, &e0);
+        HG_TRY(launch_filtered_group(idx->nch, f, nchunks * f.ngroups, st));
+        prof_end(idx, PROF_IVF_SCAN, st, e0);
+        SelectArgs s;
+        memset(&s, 0, sizeof(s));
+        s.dist = f.out;
+        s.stride = p;
+        s.cnt_all = p;
+        s.nq = nb;
+        s.k = k;
+        s.out_ord = idx->s_ord.as<uint32_t>() + q0 * k;
+        s.out_dist = idx->s_dist.as<float>() + q0 * k;
+        HG_TRY(launch_select(s, st));
+    }
+    hipLaunchKernelGGL(filter_decode_kernel, dim3(static_cast<unsigned>((cnt + 255) / 256)), dim3(256), 0, st,
+                       idx->s_ord.as<uint32_t>(), cnt, idx->s_fpass.as<int32_t>(), p, d_ids);
+    HG_HIP(hipGetLastError());
+    HG_HIP(hipMemcpyAsync(d_dist, idx->s_dist.p, sizeof(float) * cnt, hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+int launch_filter_take(const int32_t *ids_in, const float *dist_in, int32_t nq, int32_t kk, int32_t k, const uint32_t *d_allow,
+                       int64_t n, int32_t *d_out_ids, float *d_out_dist, hipStream_t st) {
+    if (nq <= 0) return 0;
+    TakeArgs t;
+    t.ids_in = ids_in;
+    t.dist_in = dist_in;
+    t.nq = nq;
+    t.kk = kk;
+    t.k = k;
+    t.allow = d_allow;
+    t.n = n;
+    t.out_ids = d_out_ids;
+    t.out_dist = d_out_dist;
+    hipLaunchKernelGGL(filter_take_kernel, dim3((nq + kNWave - 1) / kNWave), dim3(kWG), 0, st, t);
+    HG_HIP(hipGetLastError());
+    return 0;
+}
+
 }  // namespace hg
 
 using namespace hg;
@@ -2048,7 +2199,8 @@ int hnswgpu_destroy(hnswgpu_index *idx) {
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     DevBuf *bufs[] = {&idx->s_q,   &idx->s_partial, &idx->s_ord,   &idx->s_dist, &idx->s_pairs, &idx->s_ids,
-                      &idx->s_outd, &idx->s_probes,  &idx->s_stats, &idx->s_misc, &idx->s_misc2, &idx->s_vis, &idx->s_qp, &idx->s_qn, &idx->s_tile, &idx->s_grp, &idx->s_done, &idx->s_pf, &idx->s_solo, &idx->s_bk, &idx->s_heavy, &idx->s_home, &idx->s_dh};
+                      &idx->s_outd, &idx->s_probes,  &idx->s_stats, &idx->s_misc, &idx->s_misc2, &idx->s_vis, &idx->s_qp, &idx->s_qn, &idx->s_tile, &idx->s_grp, &idx->s_done, &idx->s_pf, &idx->s_solo, &idx->s_bk, &idx->s_heavy, &idx->s_home, &idx->s_dh,
+                      &idx->s_fmask, &idx->s_fpass, &idx->s_fblk, &idx->s_fids, &idx->s_fdist};
     for (DevBuf *b : bufs) b->release();
     for (int s = 0; s < PROF_N; s++)
         for (auto &pr : idx->prof_ev[s]) {
@@ -2215,6 +2367,48 @@ int hnswgpu_exact_knn(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k,
     HG_TRY(call.open(idx, st));
     HG_TRY(call.stage_in(Q, nq, k));
     HG_TRY(exact_knn_enqueue(idx, idx->s_q.as<float>(), nq, k, idx->s_ids.as<int32_t>(), idx->s_outd.as<float>(), st));
+    HG_TRY(call.stage_out(out_ids, out_dist, cnt));
+    return call.close();
+}
+
+int hnswgpu_exact_knn_filtered_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, const uint32_t *d_allow,
+                                   int32_t *d_out_ids, float *d_out_dist, void *stream) {
+    HG_TRY(check_search_args(idx, d_Q, nq, k, d_out_ids, d_out_dist));
+    HG_REQUIRE(d_allow, HNSWGPU_EINVAL, "allow is null");
+    if (nq == 0) return 0;
+    HG_REQUIRE(idx->n > 0, HNSWGPU_ESTATE, "empty index: use the host entry point");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_TRY(filtered_scan_enqueue(idx, d_Q, nq, k, d_allow, -1, d_out_ids, d_out_dist, st));
+    return call.close();
+}
+
+int hnswgpu_exact_knn_filtered(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, const uint32_t *allow,
+                               int32_t *out_ids, float *out_dist) {
+    HG_TRY(check_search_args(idx, Q, nq, k, out_ids, out_dist));
+    HG_REQUIRE(allow, HNSWGPU_EINVAL, "allow is null");
+    if (nq == 0) return 0;
+    const int64_t cnt = static_cast<int64_t>(nq) * k;
+    if (idx->n == 0) {
+        fill_empty(out_ids, out_dist, cnt);
+        return 0;
+    }
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_TRY(call.stage_in(Q, nq, k));
+    const size_t mbytes = sizeof(uint32_t) * static_cast<size_t>((idx->n + 31) / 32);
+    HG_TRY(idx->s_fmask.ensure(mbytes));
+    HG_HIP(hipMemcpyAsync(idx->s_fmask.p, allow, mbytes, hipMemcpyHostToDevice, st));
+    const int64_t p = mask_popcount(allow, idx->n);  // on the host, while the upload is in flight
+    if (p == 0) {
+        fill_empty(out_ids, out_dist, cnt);
+        HG_TRY(call.sync());
+        return call.close();
+    }
+    HG_TRY(filtered_scan_enqueue(idx, idx->s_q.as<float>(), nq, k, idx->s_fmask.as<uint32_t>(), p, idx->s_ids.as<int32_t>(),
+                                 idx->s_outd.as<float>(), st));
     HG_TRY(call.stage_out(out_ids, out_dist, cnt));
     return call.close();
 }

@@ -202,6 +202,9 @@ struct hnswgpu_index {
     // them behind its last read); bk_dirty = a search was enqueued past the point that fills them but not past the
     // work-list kernel (an error in between): the next search clears them itself
     bool bk_dirty = false;
+    // filtered search (filter_kernels.hpp): the call's mask on the device, the passing row ids, the compaction's block counts
+    // (+ the 8-byte total behind them), and the traversal's unfiltered result lists
+    hg::DevBuf s_fmask, s_fpass, s_fblk, s_fids, s_fdist;
     uint32_t pf_seq = 0;  // number of the last small launch, helper or several-CU kernel (hnsw.hip: hnsw_number_launch is its one owner)
     size_t s_done_n = 0;  // counters per half of s_done (scan tails | route tails)
     uint32_t vis_gen = 0;  // last generation number handed to an HBM visited slab
@@ -492,6 +495,12 @@ private:
 };
 
 void fill_empty(int32_t *ids, float *dist, int64_t cnt);  // no rows: id -1 at distance +inf
+
+// --- filtered search (filter_kernels.hpp; the allow-mask: include/hnswgpu.h) ---------------------------------------------
+int64_t mask_popcount(const uint32_t *allow, int64_t n);  // passing rows among the first n bits, on the host
+// the first k passing entries of every query's list ids_in / dist_in [nq][kk] (-1 padded), -1 / +inf padded (filter_take_kernel)
+int launch_filter_take(const int32_t *ids_in, const float *dist_in, int32_t nq, int32_t kk, int32_t k, const uint32_t *d_allow,
+                       int64_t n, int32_t *d_out_ids, float *d_out_dist, hipStream_t st);
 
 // The block of host memory of one combined batch -- a Slot's mapped block and the pinned staging block alike:
 // [64-byte header: flag word, repeat count][queries][stats, 2 x int64 per query, or absent][ids][distances], every section on a

@@ -1,0 +1,278 @@
+// filter_kernels.hpp -- filtered search (FilterableIndex/search-knn-filtered*, api/protocol.clj:34-41,97-102).
+//
+// One allow-mask per call, shared by its queries: (n + 31) / 32 words, row i may be returned iff bit (i & 31) of word
+// i >> 5 is set; bits at positions >= n are ignored.  Two services are built on it:
+//
+//   few rows pass -- mask_compact turns the mask into the ascending list of passing row ids (popcounts and a scan, no
+//   atomic: the list is the same on every run), filtered_group_kernel evaluates exactly those rows, each fetched once per
+//   query GROUP, into a dense [query][position in the passing list] array, and the dense top-k selection + a decode
+//   (position -> row id) finish the call.  The work per (row, query) pair is lane_partial + rows_sum_to_lane +
+//   finish_dist: the GEMV summation order at every batch size, the bits hnswgpu_rerank and scan_kernel produce.  Ties go
+//   to the lower position = the lower row id.
+//
+//   many rows pass -- the traversal runs untouched for min(ef, 1024) results and filter_take_kernel keeps the first k
+//   passing entries of each query's result list, in list order.
+#pragma once
+#include "kernels.hpp"
+#include "tile_args.hpp"
+
+namespace hg {
+
+// ---- mask -> ascending list of passing row ids -----------------------------------------------------------------
+constexpr int kMaskThreads = 256;
+constexpr int kMaskWordsPerThread = 4;  // consecutive words of one thread: its ids are consecutive in the list
+constexpr int kMaskWordsPerWG = kMaskThreads * kMaskWordsPerThread;
+constexpr int kMaskScanThreads = 1024;
+
+struct MaskArgs {
+    const uint32_t *allow;
+    int64_t n;       // rows (>= 1)
+    int64_t nwords;  // (n + 31) / 32
+    uint32_t *blk;   // [nblk]: passing rows per workgroup of the count pass, then their exclusive prefix sums
+    int32_t nblk;
+    int32_t *pass_ids;          // [cap]
+    int64_t cap;                // entries pass_ids holds (the count the scan produced)
+    unsigned long long *total;  // [1]: passing rows
+};
+
+// word w of the mask as the kernels see it: nothing past the mask, the last word trimmed to n
+__device__ __forceinline__ uint32_t mask_word(const MaskArgs &a, int64_t w) {
+    const uint32_t m = a.allow[w < a.nwords ? w : a.nwords - 1];  // clamped, unconditional
+    const int tail = static_cast<int>(a.n & 31);
+    const uint32_t keep = (w == a.nwords - 1 && tail) ? (1u << tail) - 1u : 0xffffffffu;
+    return w < a.nwords ? m & keep : 0u;
+}
+
+// exclusive prefix sum of v over the NW waves of the workgroup; *tot: the workgroup's sum.  ws: NW words of LDS, free
+// again on return.
+template <int NW>
+__device__ __forceinline__ uint32_t wg_exclusive_scan(uint32_t v, uint32_t *ws, uint32_t *tot) {
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    uint32_t inc = v;
+#pragma unroll
+    for (int off = 1; off < kWave; off <<= 1) {
+        const uint32_t t = __shfl_up(inc, off, kWave);
+        inc += lane >= off ? t : 0u;
+    }
+    if (lane == kWave - 1) ws[wave] = inc;
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < NW; w++) {
+        const uint32_t c = ws[w];
+        before += w < wave ? c : 0u;
+        all += c;
+    }
+    __syncthreads();
+    *tot = all;
+    return before + inc - v;
+}
+
+__global__ __launch_bounds__(kMaskThreads) void mask_count_kernel(MaskArgs a) {
+    __shared__ uint32_t ws[kMaskThreads / kWave];
+    const int64_t w0 = static_cast<int64_t>(blockIdx.x) * kMaskWordsPerWG + threadIdx.x * kMaskWordsPerThread;
+    uint32_t c = 0;
+#pragma unroll
+    for (int u = 0; u < kMaskWordsPerThread; u++) c += __popc(mask_word(a, w0 + u));
+    uint32_t tot;
+    (void)wg_exclusive_scan<kMaskThreads / kWave>(c, ws, &tot);
+    if (threadIdx.x == 0) a.blk[blockIdx.x] = tot;
+}
+
+// one workgroup: blk[] -> its exclusive prefix sums, *total = the sum
+__global__ __launch_bounds__(kMaskScanThreads) void mask_scan_kernel(MaskArgs a) {
+    __shared__ uint32_t ws[kMaskScanThreads / kWave];
+    unsigned long long carry = 0;
+    for (int i0 = 0; i0 < a.nblk; i0 += kMaskScanThreads) {
+        const int i = i0 + threadIdx.x;
+        const uint32_t v = i < a.nblk ? a.blk[i] : 0u;
+        uint32_t tot;
+        const uint32_t ex = wg_exclusive_scan<kMaskScanThreads / kWave>(v, ws, &tot);
+        if (i < a.nblk) a.blk[i] = static_cast<uint32_t>(carry) + ex;  // below 2^31: row ids are int32
+        carry += tot;
+    }
+    if (threadIdx.x == 0) *a.total = carry;
+}
+
+__global__ __launch_bounds__(kMaskThreads) void mask_scatter_kernel(MaskArgs a) {
+    __shared__ uint32_t ws[kMaskThreads / kWave];
+    const int64_t w0 = static_cast<int64_t>(blockIdx.x) * kMaskWordsPerWG + threadIdx.x * kMaskWordsPerThread;
+    uint32_t m[kMaskWordsPerThread];
+    uint32_t c = 0;
+#pragma unroll
+    for (int u = 0; u < kMaskWordsPerThread; u++) {
+        m[u] = mask_word(a, w0 + u);
+        c += __popc(m[u]);
+    }
+    uint32_t tot;
+    int64_t off = static_cast<int64_t>(a.blk[blockIdx.x]) + wg_exclusive_scan<kMaskThreads / kWave>(c, ws, &tot);
+#pragma unroll
+    for (int u = 0; u < kMaskWordsPerThread; u++) {
+        uint32_t x = m[u];
+        while (x) {
+            const int bit = __ffs(x) - 1;
+            x &= x - 1;
+            // (off < cap by construction; the check keeps a mask its owner rewrites during the call inside the list)
+            if (off < a.cap) a.pass_ids[off] = static_cast<int32_t>((w0 + u) * 32 + bit);
+            off++;
+        }
+    }
+}
+
+// no results: id -1 at distance +inf (what fill_empty writes on the host)
+__global__ void filter_fill_kernel(int32_t *ids, float *dist, int64_t cnt) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= cnt) return;
+    ids[i] = -1;
+    dist[i] = __uint_as_float(0x7f800000u);
+}
+
+// position in the passing list -> row id (rerank_decode_kernel's job for candidate lists)
+__global__ void filter_decode_kernel(const uint32_t *ord, int64_t cnt, const int32_t *pass_ids, int64_t p, int32_t *out_ids) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= cnt) return;
+    const uint32_t o = ord[i];
+    out_ids[i] = o < p ? pass_ids[o] : -1;  // 0xffffffff: padding
+}
+
+// ---- the gathered register-row group scan ------------------------------------------------------------------------
+// l2_group_kernel (l2_kernels.hpp) over the rows pass_ids names: a workgroup keeps a group of queries resident in LDS, every
+// wave holds RB rows in registers and walks the group's queries over them.  Row b of a step is pass_ids[base + b]; lane b
+// fetches that id, and with it the row's norm, so the distance is finished in the lane that stores it: RB consecutive
+// floats of dense[q][base ..], whose index IS the position in the passing list.
+struct FilteredArgs {
+    const float *rows;
+    const float *row_norms;
+    int64_t ld;
+    int32_t metric;
+    const float *Qp;       // queries padded to stride ld (zero filled)
+    const float *q_norms;  // cosine
+    int32_t nq;
+    int32_t tq;            // queries per group: what the LDS holds at this ld (filtered_group_queries)
+    int32_t ngroups;
+    const int32_t *pass_ids;
+    int64_t p;             // passing rows (>= 1)
+    int64_t chunk_rows;    // positions of the passing list per workgroup
+    float *out;            // dense[q * p + position]
+};
+
+// 32 queries up to ld 1024, 16 up to 2048, 8 up to 3072: 128 KiB / 128 KiB / 96 KiB of the CU's 160 KiB
+__host__ __device__ inline int filtered_group_queries(int64_t ld) { return ld <= 1024 ? 32 : (ld <= 2048 ? 16 : 8); }
+__host__ inline size_t filtered_group_lds_bytes(int64_t ld) {
+    const size_t tq = static_cast<size_t>(filtered_group_queries(ld));
+    return sizeof(float) * tq * static_cast<size_t>(ld) + sizeof(float) * tq;
+}
+
+template <int NCH, int RB, bool L2M>
+__global__ __launch_bounds__(kTileThreads) void filtered_group_kernel(FilteredArgs a) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int nvec = static_cast<int>(a.ld / 4);
+    float4 *Bs = reinterpret_cast<float4 *>(smem);            // [tq][nvec] resident query group
+    float *qn_s = reinterpret_cast<float *>(Bs + a.tq * nvec);  // [tq] query norms (cosine)
+    const int tid = threadIdx.x;
+    const int lane = tid & (kWave - 1);
+    const int wave = tid >> 6;
+    // chunk-major: the workgroups of one chunk of the passing list run side by side and share its rows in L2
+    const int g = blockIdx.x % a.ngroups;
+    const int64_t chunk = blockIdx.x / a.ngroups;
+    const int64_t r0 = chunk * a.chunk_rows;
+    const int64_t r1 = r0 + a.chunk_rows < a.p ? r0 + a.chunk_rows : a.p;
+    const int q0 = g * a.tq;
+    const int cnt = a.nq - q0 < a.tq ? a.nq - q0 : a.tq;
+    if (r0 >= r1 || cnt <= 0) return;
+
+    if (tid < cnt) qn_s[tid] = (!L2M && a.metric == METRIC_COS) ? a.q_norms[q0 + tid] : 0.0f;
+    {
+        constexpr int kQU = 16;  // 32 x 256 float4 at most = 16 per thread
+        const int total = cnt * nvec;
+        const float4 *src = reinterpret_cast<const float4 *>(a.Qp + static_cast<int64_t>(q0) * a.ld);  // the group's rows are contiguous
+        for (int f0 = tid; f0 < total; f0 += kTileThreads * kQU) {
+            float4 v[kQU];
+            int fc[kQU];
+#pragma unroll
+            for (int u = 0; u < kQU; u++) {  // clamped, unconditional: all loads of a thread in flight together
+                const int f = f0 + u * kTileThreads;
+                fc[u] = f < total ? f : total - 1;
+                v[u] = src[fc[u]];
+            }
+            // ... and unconditional stores: an index past the end re-writes element total - 1 with its own value
+#pragma unroll
+            for (int u = 0; u < kQU; u++) Bs[fc[u]] = v[u];
+        }
+    }
+    __syncthreads();
+
+    for (int64_t base = r0 + wave * RB; base < r1; base += kTileWaves * RB) {
+        float4 r[RB][NCH];
+        // lane b (and every lane beyond RB, as row RB - 1): the id of row b, clamped into the chunk, and its norm
+        const int64_t mypos = base + (lane < RB ? lane : RB - 1);
+        const int32_t myid = a.pass_ids[mypos < r1 ? mypos : r1 - 1];
+        const float myrn = (!L2M && a.metric == METRIC_COS) ? a.row_norms[myid] : 0.0f;
+#pragma unroll
+        for (int b = 0; b < RB; b++) {
+            const int64_t row = __builtin_amdgcn_readlane(myid, b);
+            load_row<NCH>(r[b], a.rows + row * a.ld, nvec, lane, true);
+        }
+        for (int q = 0; q < cnt; q++) {
+            const float qn = L2M ? 0.0f : qn_s[q];
+            float4 qv[NCH];
+#pragma unroll
+            for (int c = 0; c < NCH; c++) {
+                const int i = c * kWave + lane;
+                qv[c] = i < nvec ? Bs[q * nvec + i] : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+            float s[RB];
+#pragma unroll
+            for (int b = 0; b < RB; b++) s[b] = lane_partial<NCH, L2M>(qv, r[b]);
+            const float mine = rows_sum_to_lane<RB>(s, lane);  // lane b: row b's sum
+            if (lane < RB && base + lane < r1)
+                a.out[static_cast<int64_t>(q0 + q) * a.p + (base + lane)] = L2M ? __builtin_sqrtf(mine) : finish_dist(a.metric, mine, qn, myrn);
+        }
+    }
+}
+
+// ---- the first k passing entries of a traversal's result list ----------------------------------------------------------
+struct TakeArgs {
+    const int32_t *ids_in;  // [nq][kk], -1 padded
+    const float *dist_in;
+    int32_t nq, kk, k;
+    const uint32_t *allow;
+    int64_t n;
+    int32_t *out_ids;  // [nq][k]
+    float *out_dist;
+};
+
+// One wave per query, 64 entries of the list per step: `id >= 0 && bit` -> ballot -> the prefix popcount is the output slot.
+__global__ __launch_bounds__(kWG) void filter_take_kernel(TakeArgs a) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int q = blockIdx.x * kNWave + (threadIdx.x >> 6);
+    if (q >= a.nq) return;  // uniform over the wave
+    const int32_t *in = a.ids_in + static_cast<int64_t>(q) * a.kk;
+    const float *din = a.dist_in + static_cast<int64_t>(q) * a.kk;
+    int32_t *oi = a.out_ids + static_cast<int64_t>(q) * a.k;
+    float *od = a.out_dist + static_cast<int64_t>(q) * a.k;
+    int taken = 0;
+    for (int base = 0; base < a.kk && taken < a.k; base += kWave) {
+        const int i = base + lane;
+        const int ic = i < a.kk ? i : a.kk - 1;
+        const int32_t id = in[ic];
+        const float d = din[ic];
+        const bool valid = i < a.kk && id >= 0 && id < a.n;
+        const uint32_t w = a.allow[valid ? id >> 5 : 0];
+        const bool ok = valid && ((w >> (id & 31)) & 1u);
+        const unsigned long long m = __ballot(ok);
+        const int slot = taken + __popcll(m & ((1ull << lane) - 1ull));
+        if (ok && slot < a.k) {
+            oi[slot] = id;
+            od[slot] = d;
+        }
+        taken += __popcll(m);
+    }
+    if (taken > a.k) taken = a.k;
+    for (int i = taken + lane; i < a.k; i += kWave) {
+        oi[i] = -1;
+        od[i] = __uint_as_float(0x7f800000u);
+    }
+}
+
+}  // namespace hg

@@ -988,6 +988,65 @@ int hnswgpu_hnsw_search(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t 
         });
 }
 
+// Filtered search (api/protocol.clj:34-41,97-102): the unfiltered traversal at ef for kk = min(ef, 1024) results per query
+// into s_fids / s_fdist, then the first k passing entries of every list (filter_kernels.hpp: filter_take_kernel).
+static int hnsw_filtered_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t ef, const uint32_t *d_allow,
+                                 int32_t *d_ids, float *d_dist, int64_t *d_stats, hipStream_t st) {
+    const int32_t kk = ef < 1024 ? ef : 1024;
+    const size_t cnt = static_cast<size_t>(nq) * kk;
+    HG_TRY(idx->s_fids.ensure(sizeof(int32_t) * cnt));
+    HG_TRY(idx->s_fdist.ensure(sizeof(float) * cnt));
+    HG_TRY(search_enqueue(idx, d_Q, nq, kk, ef, idx->s_fids.as<int32_t>(), idx->s_fdist.as<float>(), d_stats, st));
+    return launch_filter_take(idx->s_fids.as<int32_t>(), idx->s_fdist.as<float>(), nq, kk, k, d_allow, idx->n, d_ids, d_dist, st);
+}
+
+int hnswgpu_hnsw_search_filtered_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t ef,
+                                     const uint32_t *d_allow, int32_t *d_out_ids, float *d_out_dist, int64_t *d_stats,
+                                     void *stream) {
+    HG_TRY(check_hnsw_args(idx, d_Q, nq, k, &ef, d_out_ids, d_out_dist));
+    HG_REQUIRE(d_allow, HNSWGPU_EINVAL, "allow is null");
+    if (nq == 0) return 0;
+    HG_REQUIRE(idx->n > 0, HNSWGPU_ESTATE, "empty index: use the host entry point");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_TRY(hnsw_filtered_enqueue(idx, d_Q, nq, k, ef, d_allow, d_out_ids, d_out_dist, d_stats, st));
+    return call.close();
+}
+
+// One caller's staged batch: masks differ between callers, so this entry takes no part in the call combiner.
+int hnswgpu_hnsw_search_filtered(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t ef, const uint32_t *allow,
+                                 int32_t *out_ids, float *out_dist, int64_t *stats) {
+    HG_TRY(check_hnsw_args(idx, Q, nq, k, &ef, out_ids, out_dist));
+    HG_REQUIRE(allow, HNSWGPU_EINVAL, "allow is null");
+    if (nq == 0) return 0;
+    const int64_t cnt = static_cast<int64_t>(nq) * k;
+    if (idx->n == 0) {
+        fill_empty(out_ids, out_dist, cnt);
+        if (stats) memset(stats, 0, sizeof(int64_t) * 2 * nq);
+        return 0;
+    }
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
+    // under the lock: a concurrent set_graph / hnsw_build may have replaced the graph since the argument check
+    HG_REQUIRE(idx->has_graph && idx->n > 0, HNSWGPU_ESTATE, "index has no graph (call hnswgpu_hnsw_build / hnswgpu_set_graph)");
+    HG_TRY(call.stage_in(Q, nq, k));
+    const size_t mbytes = sizeof(uint32_t) * static_cast<size_t>((idx->n + 31) / 32);
+    HG_TRY(idx->s_fmask.ensure(mbytes));
+    HG_HIP(hipMemcpyAsync(idx->s_fmask.p, allow, mbytes, hipMemcpyHostToDevice, st));
+    int64_t *d_stats = nullptr;
+    if (stats) {
+        HG_TRY(idx->s_stats.ensure(sizeof(int64_t) * 2 * nq));
+        d_stats = idx->s_stats.as<int64_t>();
+    }
+    HG_TRY(hnsw_filtered_enqueue(idx, idx->s_q.as<float>(), nq, k, ef, idx->s_fmask.as<uint32_t>(), idx->s_ids.as<int32_t>(),
+                                 idx->s_outd.as<float>(), d_stats, st));
+    if (stats) HG_HIP(hipMemcpyAsync(stats, d_stats, sizeof(int64_t) * 2 * nq, hipMemcpyDeviceToHost, st));
+    HG_TRY(call.stage_out(out_ids, out_dist, cnt));
+    return call.close();
+}
+
 }  // extern "C"
 
 namespace hg {

@@ -32,6 +32,37 @@ def _queries(Q, dim):
     return Q
 
 
+def pack_mask(allow, n):
+    """The allow-mask of a filtered search (include/hnswgpu.h): (n + 31) // 32 uint32 words, row i passes iff bit (i & 31) of
+    word i >> 5 is set (little-endian bit order, padded with zeros to whole words).  ``allow``: a bool array of length n, or
+    an iterable of row ids."""
+    n = int(n)
+    a = np.asarray(allow if hasattr(allow, "__len__") else list(allow))
+    if a.dtype == np.bool_:
+        if a.shape != (n,):
+            raise ValueError("a bool mask must have one entry per row (%d), got %s" % (n, a.shape))
+        bits = a
+    else:
+        ids = a.astype(np.int64).reshape(-1)
+        if len(ids) and (ids.min() < 0 or ids.max() >= n):
+            raise ValueError("row ids must lie in [0, %d)" % n)
+        bits = np.zeros(n, np.bool_)
+        bits[ids] = True
+    nwords = (n + 31) // 32
+    packed = np.zeros(nwords * 4, np.uint8)
+    b = np.packbits(bits, bitorder="little")
+    packed[:len(b)] = b
+    return packed.view("<u4").astype(np.uint32, copy=False)
+
+
+def _mask_words(allow, n):
+    """A packed mask (pack_mask) checked against the index size."""
+    a = np.ascontiguousarray(allow)
+    if a.dtype != np.uint32 or a.ndim != 1 or len(a) != (n + 31) // 32:
+        raise ValueError("allow must be the %d uint32 words of pack_mask(..., %d)" % ((n + 31) // 32, n))
+    return a
+
+
 class Graph:
     """Flat HNSW graph (layout documented in include/hnswgpu.h)."""
 
@@ -207,6 +238,16 @@ class Index:
         check(lib().hnswgpu_exact_knn(self._h, _p(Q), len(Q), k, _p(ids), _p(d)))
         return ids, d
 
+    def exact_knn_filtered(self, Q, k, allow):
+        """hnswgpu_exact_knn_filtered: the k nearest of the rows ``allow`` (pack_mask) lets pass -- exact, distances in the
+        gather order at every batch size, ties to the lower row id, -1 / +inf padded when fewer than k rows pass."""
+        Q = _queries(Q, self.dim)
+        allow = _mask_words(allow, self.n)
+        ids = np.empty((len(Q), k), np.int32)
+        d = np.empty((len(Q), k), np.float32)
+        check(lib().hnswgpu_exact_knn_filtered(self._h, _p(Q), len(Q), k, _p(allow), _p(ids), _p(d)))
+        return ids, d
+
     def rerank(self, Q, cand, k):
         """Per query: exact distances to its candidate rows cand[q] (-1 = skip), stable sort, first k."""
         Q = _queries(Q, self.dim)
@@ -266,6 +307,18 @@ class Index:
         d = np.empty((len(Q), k), np.float32)
         stats = np.zeros((len(Q), 2), np.int64) if want_stats else None
         check(lib().hnswgpu_hnsw_search(self._h, _p(Q), len(Q), k, int(ef or 0), _p(ids), _p(d), _p(stats)))
+        return (ids, d, stats) if want_stats else (ids, d)
+
+    def hnsw_search_filtered(self, Q, k, allow, ef=0, want_stats=False):
+        """hnswgpu_hnsw_search_filtered: hnsw_search's traversal at ef, then the first k entries of its result list (its
+        first min(ef, 1024) entries) that ``allow`` (pack_mask) lets pass; stats are the unfiltered traversal's."""
+        Q = _queries(Q, self.dim)
+        allow = _mask_words(allow, self.n)
+        ids = np.empty((len(Q), k), np.int32)
+        d = np.empty((len(Q), k), np.float32)
+        stats = np.zeros((len(Q), 2), np.int64) if want_stats else None
+        check(lib().hnswgpu_hnsw_search_filtered(self._h, _p(Q), len(Q), k, int(ef or 0), _p(allow), _p(ids), _p(d),
+                                                 _p(stats)))
         return (ids, d, stats) if want_stats else (ids, d)
 
     # -- IVF
@@ -394,6 +447,28 @@ class Index:
     def exact_knn_dev(self, Q, k, out=None):
         Q, ids, d, st = self._dev_args(Q, k, out)
         check(lib().hnswgpu_exact_knn_dev(self._h, Q.data_ptr(), Q.shape[0], k, ids.data_ptr(), d.data_ptr(), st))
+        return ids, d
+
+    def _dev_mask(self, allow, Q):
+        """The packed mask as a device tensor of 32-bit words (torch.from_numpy(pack_mask(...).view(np.int32)).to(device))."""
+        assert allow.is_cuda and allow.device == Q.device and allow.element_size() == 4 and allow.dim() == 1
+        assert allow.numel() == (self.n + 31) // 32, "allow must hold (n + 31) // 32 words"
+        return allow.contiguous()
+
+    def exact_knn_filtered_dev(self, Q, k, allow, out=None):
+        """hnswgpu_exact_knn_filtered_dev on torch's current stream (waits for it once, for the number of passing rows)."""
+        Q, ids, d, st = self._dev_args(Q, k, out)
+        allow = self._dev_mask(allow, Q)
+        check(lib().hnswgpu_exact_knn_filtered_dev(self._h, Q.data_ptr(), Q.shape[0], k, allow.data_ptr(), ids.data_ptr(),
+                                                   d.data_ptr(), st))
+        return ids, d
+
+    def hnsw_search_filtered_dev(self, Q, k, allow, ef=0, out=None, stats=None):
+        Q, ids, d, st = self._dev_args(Q, k, out)
+        allow = self._dev_mask(allow, Q)
+        check(lib().hnswgpu_hnsw_search_filtered_dev(self._h, Q.data_ptr(), Q.shape[0], k, int(ef or 0), allow.data_ptr(),
+                                                     ids.data_ptr(), d.data_ptr(),
+                                                     stats.data_ptr() if stats is not None else None, st))
         return ids, d
 
     def rerank_dev(self, Q, cand, k, out=None):

@@ -1,6 +1,7 @@
-"""Mirror of ``hnsw.api.protocol`` (src/hnsw/api/protocol.clj): ANNIndex, BatchSearchIndex, PersistableIndex and the
-default helpers (filtered search by post-filtering, :96-101; sequential batch search, :92-95) over the two GPU-served
-index types."""
+"""Mirror of ``hnsw.api.protocol`` (src/hnsw/api/protocol.clj): ANNIndex, BatchSearchIndex, PersistableIndex,
+FilterableIndex and the default helpers (filtered search by post-filtering, :96-101; sequential batch search, :92-95) over
+the two GPU-served index types.  The HNSW index filters on the device (ultra_fast.search_knn_filtered); the IVF index keeps
+the default helper."""
 from . import index_io, ivf_flat, ultra_fast
 
 
@@ -31,6 +32,13 @@ class PersistableIndex:
         raise NotImplementedError
 
 
+class FilterableIndex:
+    """protocol.clj:34-41"""
+
+    def search_knn_filtered_star(self, query, k, filter_fn, mode):
+        raise NotImplementedError
+
+
 def default_batch_search(index, queries, k, mode):
     """protocol.clj:92-95: one search-knn* per query (what an index without search-batch* gets)."""
     return [index.search_knn_star(q, k, mode) for q in queries]
@@ -41,9 +49,12 @@ def default_filtered_search(index, query, k, filter_fn, mode):
     return [r for r in index.search_knn_star(query, 3 * k, mode) if filter_fn(r["id"])][:k]
 
 
-class GpuHnswIndex(ANNIndex, BatchSearchIndex, PersistableIndex):
+class GpuHnswIndex(ANNIndex, BatchSearchIndex, PersistableIndex, FilterableIndex):
     def __init__(self, graph):
         self.graph = graph
+
+    def search_knn_filtered_star(self, query, k, filter_fn, mode=None):
+        return ultra_fast.search_knn_filtered(self.graph, query, k, filter_fn)
 
     def save_index_star(self, filepath):
         index_io.save_index(self.graph, filepath)
@@ -81,6 +92,11 @@ class GpuIvfFlatIndex(ANNIndex, BatchSearchIndex, PersistableIndex):
 
     def index_type_star(self):
         return "ivf-flat"
+
+
+def supports_filtering(index):
+    """protocol.clj:73-76 (an index without it is served by default_filtered_search)"""
+    return isinstance(index, FilterableIndex)
 
 
 def supports_batch_search(index):

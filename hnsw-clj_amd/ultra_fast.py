@@ -132,6 +132,65 @@ def search_batch(graph, queries, k, ef=None, route=False):
     return [_format(graph, ids[i], d[i]) for i in range(len(queries))]
 
 
+def filtered_plan(n, p, k, ef=None):
+    """How a filtered search over n rows, p of them passing, is served: ``("scan" | "graph", ef')`` -- a pure function of
+    counts the reference and the engine already fix.  The reference over-fetches by 3 (protocol.clj:101), and a result list
+    must hold 3k * n / p entries to expect 3k passing ones: ef_need = ceil(3 k n / p), ef' = max(ef or max(k, 50), ef_need).
+    The exact scan of the passing rows serves the call when nothing passes, when ef_need exceeds the 1024 list entries the
+    filtered traversal looks at, or when p <= ef' (the scan then evaluates no more rows than the list alone holds);
+    otherwise the graph is walked at ef'."""
+    n, p, k = int(n), int(p), int(k)
+    ef0 = int(ef) if ef else max(k, 50)
+    if p <= 0:
+        return "scan", ef0
+    ef_need = -(-3 * k * n // p)
+    ef2 = max(ef0, ef_need)
+    if ef_need > 1024 or p <= ef2:
+        return "scan", ef2
+    return "graph", ef2
+
+
+def _allow_bits(graph, filter_fn):
+    """The predicate on the caller's ids, evaluated once per row on the host (or a ready bool array of length n)."""
+    if callable(filter_fn):
+        return np.fromiter((bool(filter_fn(i)) for i in graph.ids), np.bool_, len(graph.ids))
+    bits = np.asarray(filter_fn)
+    if bits.dtype != np.bool_ or bits.shape != (graph.index.n,):
+        raise ValueError("filter_fn must be a predicate on ids or a bool array with one entry per row")
+    return bits
+
+
+def search_batch_filtered(graph, queries, k, filter_fn, ef=None):
+    """FilterableIndex/search-knn-filtered* (api/protocol.clj:34-41) for a batch, one predicate per call: ``filter_fn`` is
+    called once per row with ``graph.ids[i]`` (or is a bool array of length n).  filtered_plan chooses the path: "graph"
+    walks the graph at ef' and keeps the first k passing entries of each result list (protocol.clj:97-102 with a list
+    long enough to expect 3k passing entries); "scan" (not in the reference) evaluates exactly the passing rows -- the
+    neighbours are then the EXACT k nearest passing rows, at least as good as the graph's, not necessarily the same."""
+    queries = np.asarray(queries, np.float32)
+    if queries.ndim == 1:
+        queries = queries[None, :]
+    if len(queries) == 0:
+        return []
+    n = graph.index.n
+    if n == 0:
+        return [[] for _ in queries]
+    bits = _allow_bits(graph, filter_fn)
+    plan, ef2 = filtered_plan(n, int(bits.sum()), k, ef)
+    mask = engine.pack_mask(bits, n)
+    if plan == "scan":
+        ids, d = graph.index.exact_knn_filtered(queries, int(k), mask)
+    else:
+        ids, d = graph.index.hnsw_search_filtered(queries, int(k), mask, ef2)
+    return [_format(graph, ids[i], d[i]) for i in range(len(queries))]
+
+
+def search_knn_filtered(graph, query_vec, k, filter_fn, ef=None):
+    """search_batch_filtered for one query: a list of ``{"id", "distance"}`` ascending, fewer than k when fewer pass."""
+    if graph.index.n == 0:
+        return []
+    return search_batch_filtered(graph, np.asarray(query_vec, np.float32)[None, :], k, filter_fn, ef)[0]
+
+
 def graph_info(graph):
     """ultra_fast.clj:378-384"""
     g = graph.index.get_graph() if graph.index.n else None

@@ -257,6 +257,37 @@ int hnswgpu_rerank_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, const i
 int hnswgpu_dense_distances(hnswgpu_index *idx, const float *Q, int32_t nq, float *out);
 int hnswgpu_dense_distances_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, float *d_out, void *stream);
 
+/* ---- filtered search ----------------------------------------------------------------------------------------
+ * FilterableIndex/search-knn-filtered* (src/hnsw/api/protocol.clj:34-41) and its default, default-filtered-search
+ * (protocol.clj:97-102: search 3k, keep what passes the predicate, take k), with the predicate evaluated by the caller
+ * into ONE allow-mask per call, shared by the call's queries like the reference's one filter-fn per call:
+ *   allow: (n + 31) / 32 words; row i may be returned iff (allow[i >> 5] >> (i & 31)) & 1.  Bits at positions >= n are
+ *   ignored.  The mask is an argument, not handle state: nothing is kept or persisted, and after hnswgpu_hnsw_add the
+ *   next call simply brings a longer mask.  A null mask is an error (-1); n == 0: the host entry points behave as the
+ *   unfiltered ones do.
+ * hnswgpu_exact_knn_filtered (protocol.clj:34-41,97-102): the k nearest of the PASSING rows, exact, for every metric --
+ *   the mask is compacted into the ascending list of passing row ids and exactly those rows are scanned, each fetched
+ *   once per group of queries.  Distances in the gather order (wave-strided f32 fma chain + butterfly, the bits of
+ *   hnswgpu_rerank / hnswgpu_batch_distances) at EVERY batch size -- no matrix-core order: a query's bits never depend
+ *   on its batch.  Ties go to the lower row id; fewer than k passing rows: -1 / +inf padding.  k <= 1024.
+ *   The _dev entry reads the number of passing rows (8 bytes) back once, between the compaction's scan and its scatter,
+ *   and the calling thread waits for `stream` there: unlike the other _dev entry points it does synchronise, once.
+ * hnswgpu_hnsw_search_filtered (protocol.clj:34-41,97-102): the traversal of hnswgpu_hnsw_search, untouched -- same
+ *   list, expansions and stats.  With ef' the effective ef (ef <= 0: max(k, 50); at least k) and kk = min(ef', 1024), the
+ *   result is the first k passing entries among the first kk entries of the traversal's result list, in list order,
+ *   -1 / +inf padded.  ef' = 3k is default-filtered-search itself; a larger ef looks further; an all-ones mask returns
+ *   hnswgpu_hnsw_search's results bit for bit.  The host entry stages one caller's batch (it is not combined with
+ *   concurrent callers: their masks differ). */
+int hnswgpu_exact_knn_filtered(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, const uint32_t *allow,
+                               int32_t *out_ids, float *out_dist);
+int hnswgpu_exact_knn_filtered_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, const uint32_t *d_allow,
+                                   int32_t *d_out_ids, float *d_out_dist, void *stream);
+int hnswgpu_hnsw_search_filtered(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t ef, const uint32_t *allow,
+                                 int32_t *out_ids, float *out_dist, int64_t *stats);
+int hnswgpu_hnsw_search_filtered_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t ef,
+                                     const uint32_t *d_allow, int32_t *d_out_ids, float *d_out_dist, int64_t *d_stats,
+                                     void *stream);
+
 /* ---- persistence ------------------------------------------------------------------------------------------
  * One flat binary file (header + plain arrays; layout in hnsw-clj_amd/csrc/persist.hip) with the base
  * vectors, the graph and the IVF lists -- replaces helper/index-io's save-index / load-index, an EDN
