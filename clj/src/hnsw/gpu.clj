@@ -21,6 +21,7 @@
      (from-ivf-flat-index ivf)                                       ; an IVFFlatIndex built by the reference's own k-means
      (save idx path) / (load-index path ids)                         ; helper/index-io save-index / load-index
      (search-knn-filtered index query-vec k filter-fn)               ; FilterableIndex/search-knn-filtered*, on the device
+     (search-ivf-filtered index query-vec k filter-fn :num-probes 4)  ; ... through the IVF list scan: the k nearest passing rows
    and, at the bottom, the extend-type that makes GpuIndex an ANNIndex / BatchSearchIndex / FilterableIndex / PersistableIndex next to the
    records src/hnsw/api/unified.clj:30-95 extends."
   (:require [hnsw.api.protocol :as proto])
@@ -248,6 +249,36 @@
                                    [(:handle idx) q (int nq) (int k) (int num-probes) ids ds MemorySegment/NULL]))
       (mapv #(results idx ids ds % k) (range nq)))))
 
+;; ---- IVF-FLAT filtered search: the allow-mask through the list scan (hnswgpu_ivf_search_filtered) ----
+(def ^:private h-ivfsearch-filtered
+  (delay (fn-handle "hnswgpu_ivf_search_filtered" (FunctionDescriptor/of I (into-array [P P I I I P P P P])))))
+
+(defn search-ivf-batch-filtered
+  "search-knn-filtered* over the probed lists for a batch with ONE predicate on the caller's ids, evaluated once per row here
+   into the call's allow-mask ((n + 31) / 32 words, bit (i & 31) of word i >> 5, indexed by row).  The device scans exactly
+   the passing rows of the probed lists and returns the k nearest of them -- not protocol.clj:97-102's search 3k, drop, keep k."
+  [idx queries k filter-fn & {:keys [num-probes] :or {num-probes 4}}]
+  (with-open [arena (Arena/ofConfined)]
+    (let [n (count (:ids idx))
+          nq (count queries)
+          words (quot (+ n 31) 32)
+          mask (.allocate arena (* 4 (max words 1)) 4)
+          _ (.fill mask (byte 0))
+          _ (doseq [i (range n) :when (filter-fn (nth (:ids idx) i))]
+              (let [w (quot i 32)]
+                (.setAtIndex mask I (long w) (unchecked-int (bit-or (.getAtIndex mask I (long w)) (bit-shift-left 1 (rem i 32)))))))
+          q (floats-of arena (vec queries) (:dim idx))
+          ids (.allocate arena (* 4 nq k) 4)
+          ds (.allocate arena (* 4 nq k) 4)]
+      (check (.invokeWithArguments ^MethodHandle @h-ivfsearch-filtered
+                                   [(:handle idx) q (int nq) (int k) (int num-probes) mask ids ds MemorySegment/NULL]))
+      (mapv #(results idx ids ds % k) (range nq)))))
+
+(defn search-ivf-filtered
+  "One query through search-ivf-batch-filtered: seq of {:id :distance} ascending, fewer than k when fewer probed rows pass."
+  [idx ^doubles query-vec k filter-fn & {:keys [num-probes] :or {num-probes 4}}]
+  (first (search-ivf-batch-filtered idx [query-vec] k filter-fn :num-probes num-probes)))
+
 ;; ===== the simd-optimized batch seams =====
 
 (defn batch-distances
@@ -455,7 +486,7 @@
   proto/FilterableIndex
   (search-knn-filtered* [this query k filter-fn mode]
     (if (= :ivf (:kind this))
-      (proto/default-filtered-search this query k filter-fn mode)   ; IVF handles keep the post-filter of protocol.clj:97-102
+      (proto/default-filtered-search this query k filter-fn mode)   ; the reference's post-filter (protocol.clj:97-102); search-ivf-filtered filters in the list scan
       (search-knn-filtered this query k filter-fn)))
   proto/PersistableIndex
   (save-index* [this filepath] (save this filepath)))

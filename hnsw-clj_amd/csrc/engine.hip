@@ -1940,40 +1940,83 @@ int64_t mask_popcount(const uint32_t *allow, int64_t n) {
     return p;
 }
 
-// The ascending list of passing rows into s_fpass, their number into *p: three small launches (per-workgroup popcounts,
-// one-workgroup scan, scatter).  p_host >= 0: the caller counted on the host; otherwise the 8-byte total is read back
-// once, between the scan and the scatter (the list is sized by it), and the calling thread waits for `st` there.
-static int mask_compact(hnswgpu_index *idx, const uint32_t *d_allow, int64_t p_host, int64_t *p, hipStream_t st) {
+// The ascending list of the set bits of a mask of `len` bits into s_fpass, their number into *p: three small launches
+// (per-workgroup popcounts, one-workgroup scan, scatter).  p_host >= 0: the caller counted on the host; kMaskCountRead: the 8-byte
+// total is read back once, between the scan and the scatter (the list is sized by it), and the calling thread waits for `st`
+// there; kMaskCountDevice: nothing is read back -- the list is sized for `len` entries, *p = len is its capacity, and the total
+// stays on the device (*d_total: where) for kernels that read it there.
+int mask_compact(hnswgpu_index *idx, const uint32_t *d_allow, int64_t len, int64_t p_host, int64_t *p, hipStream_t st,
+                 const unsigned long long **d_total) {
     *p = 0;
+    if (d_total) *d_total = nullptr;
     if (p_host == 0) return 0;
     MaskArgs m;
     memset(&m, 0, sizeof(m));
     m.allow = d_allow;
-    m.n = idx->n;
-    m.nwords = (idx->n + 31) / 32;
+    m.n = len;
+    m.nwords = (len + 31) / 32;
     const int64_t nblk = (m.nwords + kMaskWordsPerWG - 1) / kMaskWordsPerWG;
     m.nblk = static_cast<int32_t>(nblk);
     const size_t tot_off = (sizeof(uint32_t) * static_cast<size_t>(nblk) + 7) & ~static_cast<size_t>(7);
     HG_TRY(idx->s_fblk.ensure(tot_off + sizeof(unsigned long long)));
     m.blk = idx->s_fblk.as<uint32_t>();
     m.total = reinterpret_cast<unsigned long long *>(idx->s_fblk.as<char>() + tot_off);
+    if (d_total) *d_total = m.total;
     hipLaunchKernelGGL(mask_count_kernel, dim3(static_cast<unsigned>(nblk)), dim3(kMaskThreads), 0, st, m);
     hipLaunchKernelGGL(mask_scan_kernel, dim3(1), dim3(kMaskScanThreads), 0, st, m);
     HG_HIP(hipGetLastError());
     int64_t cnt = p_host;
-    if (cnt < 0) {
+    if (cnt == kMaskCountDevice) {
+        cnt = len;
+    } else if (cnt < 0) {
         HG_TRY(ensure_pinned(idx, sizeof(unsigned long long)));
         HG_HIP(hipMemcpyAsync(idx->h_pin, m.total, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
         HG_HIP(hipStreamSynchronize(st));
         cnt = static_cast<int64_t>(*static_cast<unsigned long long *>(idx->h_pin));
     }
-    HG_REQUIRE(cnt >= 0 && cnt <= idx->n, HNSWGPU_EINVAL, "the mask counts %lld passing rows of %lld", (long long)cnt, (long long)idx->n);
+    HG_REQUIRE(cnt >= 0 && cnt <= len, HNSWGPU_EINVAL, "the mask counts %lld passing rows of %lld", (long long)cnt, (long long)len);
     *p = cnt;
     if (cnt == 0) return 0;
     HG_TRY(idx->s_fpass.ensure(sizeof(int32_t) * static_cast<size_t>(cnt)));
     m.pass_ids = idx->s_fpass.as<int32_t>();
     m.cap = cnt;
     hipLaunchKernelGGL(mask_scatter_kernel, dim3(static_cast<unsigned>(nblk)), dim3(kMaskThreads), 0, st, m);
+    HG_HIP(hipGetLastError());
+    return 0;
+}
+
+// IVF-FLAT filtered search (ivf.hip: ivf_filtered_enqueue): the mask in list order ...
+int launch_list_mask(hnswgpu_index *idx, const uint32_t *d_allow, uint32_t *d_lmask, hipStream_t st) {
+    const int64_t L = idx->n, lwords = (L + 31) / 32;
+    hipLaunchKernelGGL(list_mask_kernel, dim3(static_cast<unsigned>((L + kMaskThreads - 1) / kMaskThreads)), dim3(kMaskThreads), 0, st,
+                       d_allow, idx->d_listids, L, idx->n, d_lmask, lwords);
+    HG_HIP(hipGetLastError());
+    return 0;
+}
+// ... the passing positions below every list's first (cap: entries d_pass_pos holds) ...
+int launch_list_foff(hnswgpu_index *idx, const int32_t *d_pass_pos, const unsigned long long *d_total, int64_t cap, int32_t *d_foff,
+                     hipStream_t st) {
+    hipLaunchKernelGGL(list_foff_kernel, dim3((idx->nlist + 1 + 255) / 256), dim3(256), 0, st, d_pass_pos, d_total, cap, idx->d_listoff,
+                       idx->nlist, d_foff);
+    HG_HIP(hipGetLastError());
+    return 0;
+}
+// ... and the scan of the passing rows of the probed lists (launch_scan's grid: whole runs on every XCD when ordered)
+int launch_ivf_filtered_scan(int nch, const IvfFilteredArgs &a0, hipStream_t st) {
+    IvfFilteredArgs a = a0;
+    int64_t blocks = static_cast<int64_t>(a.npairs) * a.nchunks;
+    if (blocks <= 0) return 0;
+    if (a.order) {
+        if (a.run < 8) a.run = 8;
+        blocks = (blocks + 8 * a.run - 1) / (8 * a.run) * (8 * a.run);
+    }
+    HG_REQUIRE(blocks < 2147483647LL, HNSWGPU_ELIMIT, "filtered list scan grid too large (%lld blocks)", (long long)blocks);
+    const size_t lds = sizeof(uint64_t) * kNWave * a.k;
+    HG_REQUIRE(lds <= 64 * 1024, HNSWGPU_ELIMIT, "k too large for the scan kernel (k=%d)", a.k);
+    const bool l2 = a.metric == METRIC_L2;
+#define CALL(N, R, L) hipLaunchKernelGGL((ivf_filtered_scan_kernel<N, R, L>), dim3(static_cast<unsigned>(blocks)), dim3(kWG), lds, st, a)
+    HG_DISPATCH(nch, l2, CALL);
+#undef CALL
     HG_HIP(hipGetLastError());
     return 0;
 }
@@ -1996,7 +2039,7 @@ static int launch_filtered_group(int nch, const FilteredArgs &a, int64_t blocks,
     return 0;
 }
 
-static int fill_empty_dev(int32_t *d_ids, float *d_dist, int64_t cnt, hipStream_t st) {
+int fill_empty_dev(int32_t *d_ids, float *d_dist, int64_t cnt, hipStream_t st) {
     hipLaunchKernelGGL(filter_fill_kernel, dim3(static_cast<unsigned>((cnt + 255) / 256)), dim3(256), 0, st, d_ids, d_dist, cnt);
     HG_HIP(hipGetLastError());
     return 0;
@@ -2007,7 +2050,7 @@ static int filtered_scan_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t n
                                  int64_t p_host, int32_t *d_ids, float *d_dist, hipStream_t st) {
     const int64_t cnt = static_cast<int64_t>(nq) * k;
     int64_t p = 0;
-    HG_TRY(mask_compact(idx, d_allow, p_host, &p, st));
+    HG_TRY(mask_compact(idx, d_allow, idx->n, p_host, &p, st));  // (p_host < 0: kMaskCountRead)
     if (p == 0) return fill_empty_dev(d_ids, d_dist, cnt, st);
     HG_TRY(pad_queries(idx, d_Q, idx->dim, nq, st));
     HG_TRY(idx->s_ord.ensure(sizeof(uint32_t) * static_cast<size_t>(cnt)));
@@ -2200,7 +2243,7 @@ int hnswgpu_destroy(hnswgpu_index *idx) {
         if (p) (void)hipFree(p);
     DevBuf *bufs[] = {&idx->s_q,   &idx->s_partial, &idx->s_ord,   &idx->s_dist, &idx->s_pairs, &idx->s_ids,
                       &idx->s_outd, &idx->s_probes,  &idx->s_stats, &idx->s_misc, &idx->s_misc2, &idx->s_vis, &idx->s_qp, &idx->s_qn, &idx->s_tile, &idx->s_grp, &idx->s_done, &idx->s_pf, &idx->s_solo, &idx->s_bk, &idx->s_heavy, &idx->s_home, &idx->s_dh,
-                      &idx->s_fmask, &idx->s_fpass, &idx->s_fblk, &idx->s_fids, &idx->s_fdist};
+                      &idx->s_fmask, &idx->s_fpass, &idx->s_fblk, &idx->s_fids, &idx->s_fdist, &idx->s_flmask, &idx->s_ffoff};
     for (DevBuf *b : bufs) b->release();
     for (int s = 0; s < PROF_N; s++)
         for (auto &pr : idx->prof_ev[s]) {

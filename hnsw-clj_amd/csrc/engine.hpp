@@ -205,6 +205,8 @@ struct hnswgpu_index {
     // filtered search (filter_kernels.hpp): the call's mask on the device, the passing row ids, the compaction's block counts
     // (+ the 8-byte total behind them), and the traversal's unfiltered result lists
     hg::DevBuf s_fmask, s_fpass, s_fblk, s_fids, s_fdist;
+    // ... and for the IVF list scan: the mask in list order, the passing positions below every list's first
+    hg::DevBuf s_flmask, s_ffoff;
     uint32_t pf_seq = 0;  // number of the last small launch, helper or several-CU kernel (hnsw.hip: hnsw_number_launch is its one owner)
     size_t s_done_n = 0;  // counters per half of s_done (scan tails | route tails)
     uint32_t vis_gen = 0;  // last generation number handed to an HBM visited slab
@@ -501,6 +503,18 @@ int64_t mask_popcount(const uint32_t *allow, int64_t n);  // passing rows among 
 // the first k passing entries of every query's list ids_in / dist_in [nq][kk] (-1 padded), -1 / +inf padded (filter_take_kernel)
 int launch_filter_take(const int32_t *ids_in, const float *dist_in, int32_t nq, int32_t kk, int32_t k, const uint32_t *d_allow,
                        int64_t n, int32_t *d_out_ids, float *d_out_dist, hipStream_t st);
+
+// The set bits of a `len`-bit device mask as an ascending list in s_fpass (engine.hip).  p_host: the caller's count, or
+constexpr int64_t kMaskCountRead = -1;    // ... read the total back once (the calling thread waits for `st`)
+constexpr int64_t kMaskCountDevice = -2;  // ... no readback: the list holds `len` entries, the total stays at *d_total
+int mask_compact(hnswgpu_index *idx, const uint32_t *d_allow, int64_t len, int64_t p_host, int64_t *p, hipStream_t st,
+                 const unsigned long long **d_total = nullptr);
+int fill_empty_dev(int32_t *d_ids, float *d_dist, int64_t cnt, hipStream_t st);
+// IVF-FLAT filtered search (filter_kernels.hpp; driven by ivf.hip: ivf_filtered_enqueue)
+int launch_list_mask(hnswgpu_index *idx, const uint32_t *d_allow, uint32_t *d_lmask, hipStream_t st);
+int launch_list_foff(hnswgpu_index *idx, const int32_t *d_pass_pos, const unsigned long long *d_total, int64_t cap, int32_t *d_foff,
+                     hipStream_t st);
+int launch_ivf_filtered_scan(int nch, const IvfFilteredArgs &a, hipStream_t st);
 
 // The block of host memory of one combined batch -- a Slot's mapped block and the pinned staging block alike:
 // [64-byte header: flag word, repeat count][queries][stats, 2 x int64 per query, or absent][ids][distances], every section on a

@@ -12,6 +12,12 @@
 //
 //   many rows pass -- the traversal runs untouched for min(ef, 1024) results and filter_take_kernel keeps the first k
 //   passing entries of each query's result list, in list order.
+//
+//   IVF-FLAT (search-ivf-flat, ivf_flat.clj:261-294) -- the mask is turned round into LIST order (list_mask_kernel: bit pos
+//   = the bit of row list_ids[pos]), compacted by the same three launches into the ascending list of passing list
+//   POSITIONS, and cut at the list boundaries (list_foff_kernel).  A probed list's passing rows are then a segment of that
+//   list, and ivf_filtered_scan_kernel -- the gathered form of scan_kernel's top-k body -- reads exactly those rows.  Keys
+//   carry the position in the UNFILTERED candidate stream, so the merge and the decode of the unfiltered search finish it.
 #pragma once
 #include "kernels.hpp"
 #include "tile_args.hpp"
@@ -228,6 +234,125 @@ __global__ __launch_bounds__(kTileThreads) void filtered_group_kernel(FilteredAr
             if (lane < RB && base + lane < r1)
                 a.out[static_cast<int64_t>(q0 + q) * a.p + (base + lane)] = L2M ? __builtin_sqrtf(mine) : finish_dist(a.metric, mine, qn, myrn);
         }
+    }
+}
+
+// ---- IVF-FLAT: the mask in list order, the passing positions per list, the gathered list scan ----------------------------
+// lmask bit pos = allow bit of row list_ids[pos], for the L list positions; positions >= L are clear.  Lane i of a wave
+// takes position 64 * wave + i: one ballot is two words.  Row ids are install_lists' (in [0, n)); one outside reads as clear.
+__global__ __launch_bounds__(kMaskThreads) void list_mask_kernel(const uint32_t *allow, const int32_t *listids, int64_t L, int64_t n,
+                                                                 uint32_t *lmask, int64_t lwords) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t gw = (static_cast<int64_t>(blockIdx.x) * kMaskThreads + threadIdx.x) >> 6;
+    const int64_t pos = gw * kWave + lane;
+    const int64_t row = listids[pos < L ? pos : L - 1];  // clamped, unconditional (L >= 1)
+    const bool in = pos < L && row >= 0 && row < n;
+    const uint32_t w = allow[in ? row >> 5 : 0];
+    const unsigned long long m = __ballot(in && ((w >> (row & 31)) & 1u));
+    if (lane < 2 && 2 * gw + lane < lwords) lmask[2 * gw + lane] = static_cast<uint32_t>(m >> (32 * lane));
+}
+
+// foff[l] = passing positions below list_off[l], l = 0 .. nlist: a lower bound in the ascending pass_pos[0 .. total).
+// The total is read on the device (nobody has read it back) and trusted up to `cap`, the entries pass_pos holds.
+__global__ void list_foff_kernel(const int32_t *pass_pos, const unsigned long long *total, int64_t cap, const int64_t *list_off,
+                                 int nlist, int32_t *foff) {
+    const int l = blockIdx.x * blockDim.x + threadIdx.x;
+    if (l > nlist) return;
+    const unsigned long long t = *total;
+    int64_t lo = 0, hi = t < static_cast<unsigned long long>(cap) ? static_cast<int64_t>(t) : cap;
+    const int64_t at = list_off[l];
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (pass_pos[mid] < at) lo = mid + 1;
+        else hi = mid;
+    }
+    foff[l] = static_cast<int32_t>(lo);
+}
+
+// The list scan over the passing rows only.  A workgroup serves one (pair, chunk): the pair's list l comes from the probe
+// table (-1: none), its candidates are pass_pos[foff[l] .. foff[l + 1]) -- list positions, ascending, so the filtered
+// candidate stream is the unfiltered one with holes.  Nobody on the host knows a filtered list's length: workgroup c of a
+// pair takes the tiles c, c + nchunks, ... (chunk_rows positions each) of the segment, whatever its length; one with no
+// tile writes its all-ones lists and leaves.  Lane b fetches the position of row b (clamped into the segment) and its norm,
+// readlane makes the row address wave-uniform (filtered_group_kernel); lane_partial + rows_sum_to_lane + finish_dist are
+// scan_kernel's, in its order: the same bits.  Key: (distance, position in the UNFILTERED stream) -- monotone in the
+// filtered one, and what merge_topk_kernel and ivf_decode_kernel expect.  Partial lists: [pair][chunk][wave][k].
+// (IvfFilteredArgs: tile_args.hpp, beside the other launch arguments the host side fills)
+
+template <int NCH, int RB, bool L2M>
+__global__ __launch_bounds__(kWG) void ivf_filtered_scan_kernel(IvfFilteredArgs a) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    uint64_t *lists = reinterpret_cast<uint64_t *>(smem);  // [kNWave][k] (k > 64)
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x >> 6;
+    const int64_t bid = blockIdx.x;
+    int32_t pair, chunk;
+    if (a.order) {  // scan_kernel's dealing of the work items to the XCDs: pairs of one list side by side on one L2
+        const int64_t j = bid >> 3;
+        const int64_t item = ((j / a.run) * 8 + (bid & 7)) * a.run + j % a.run;
+        if (item >= static_cast<int64_t>(a.npairs) * a.nchunks) return;
+        pair = a.order[item % a.npairs];
+        chunk = static_cast<int32_t>(item / a.npairs);
+    } else {
+        pair = static_cast<int32_t>(bid % a.npairs);
+        chunk = static_cast<int32_t>(bid / a.npairs);
+    }
+    const Pair p = a.pairs[pair];
+    const int32_t l = a.probes[pair];
+    const int64_t s0 = l >= 0 ? a.foff[l] : 0, s1 = l >= 0 ? a.foff[l + 1] : 0;
+    uint64_t *mylist = lists + wave * a.k;
+    int cnt = 0;
+    uint64_t thr = ~0ull;
+    const bool regk = a.k <= kWave;
+    uint64_t mine = ~0ull;
+    if (s0 + static_cast<int64_t>(chunk) * a.chunk_rows < s1) {
+        float4 q[NCH];
+        load_query<NCH>(q, a.Q + p.q * a.qld, a.dim, lane);
+        const float qn = (!L2M && a.metric == METRIC_COS) ? query_norm<NCH>(q) : 0.0f;
+        const int nvec = static_cast<int>(a.ld / 4);
+        for (int64_t t0 = s0 + static_cast<int64_t>(chunk) * a.chunk_rows; t0 < s1; t0 += static_cast<int64_t>(a.nchunks) * a.chunk_rows) {
+            const int64_t t1 = t0 + a.chunk_rows < s1 ? t0 + a.chunk_rows : s1;
+            for (int64_t base = t0 + wave * RB; base < t1; base += kNWave * RB) {
+                float4 r[RB][NCH];
+                // lane b (and every lane beyond RB, as row RB - 1): the list position of row b, clamped into the tile, and its norm
+                const int64_t at = base + (lane < RB ? lane : RB - 1);
+                const int32_t mypos = a.pass_pos[at < t1 ? at : t1 - 1];
+                const float myrn = (!L2M && a.metric == METRIC_COS) ? a.row_norms[mypos] : 0.0f;
+#pragma unroll
+                for (int b = 0; b < RB; b++) {
+                    const int64_t row = __builtin_amdgcn_readlane(mypos, b);
+                    load_row<NCH>(r[b], a.rows + row * a.ld, nvec, lane, true);
+                }
+                float s[RB];
+#pragma unroll
+                for (int b = 0; b < RB; b++) s[b] = lane_partial<NCH, L2M>(q, r[b]);
+                const float tot = rows_sum_to_lane<RB>(s, lane);  // lane b: row b's sum
+                const float myd = L2M ? __builtin_sqrtf(tot) : finish_dist(a.metric, tot, qn, myrn);
+#pragma unroll
+                for (int b = 0; b < RB; b++) {
+                    if (base + b < t1) {  // wave-uniform
+                        const float d = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(myd), b));
+                        const int64_t pos = __builtin_amdgcn_readlane(mypos, b);
+                        const uint64_t key = make_key(d, p.ord_base + static_cast<uint32_t>(pos - p.row_begin));
+                        if (key < thr) {
+                            if (regk) {
+                                wave_insert_reg(mine, cnt, a.k, key, lane);
+                                thr = wave_kth_reg(mine, a.k);  // ~0 until the list is full
+                            } else {
+                                wave_insert(mylist, cnt, a.k, key, lane);
+                                thr = cnt == a.k ? mylist[a.k - 1] : ~0ull;
+                            }
+                        }
+                    }
+                }
+            }
+        }
+    }
+    uint64_t *dst = a.partial + ((static_cast<int64_t>(pair) * a.nchunks + chunk) * kNWave + wave) * a.k;
+    if (regk) {
+        if (lane < a.k) dst[lane] = mine;
+    } else {
+        for (int i = lane; i < a.k; i += kWave) dst[i] = i < cnt ? mylist[i] : ~0ull;
     }
 }
 

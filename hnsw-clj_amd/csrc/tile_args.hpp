@@ -116,4 +116,23 @@ struct SelectArgs {
     float *out_dist;
 };
 
+// The IVF list scan over the passing rows of an allow-mask (filter_kernels.hpp: ivf_filtered_scan_kernel).
+struct Pair;  // kernels.hpp
+struct IvfFilteredArgs {
+    const float *rows;       // list rows (list order) + norms
+    const float *row_norms;
+    int64_t ld;
+    const float *Q;
+    int64_t qld;
+    int32_t dim, metric;
+    const Pair *pairs;       // [npairs]
+    const int32_t *probes;   // [npairs]: the list a pair probes, -1 = none
+    const int32_t *pass_pos; // ascending passing list positions
+    const int32_t *foff;     // [nlist + 1]
+    const int32_t *order;    // optional execution order of the pairs (ScanArgs::order), in runs of `run`
+    int32_t run;
+    int32_t npairs, chunk_rows, nchunks, k;
+    uint64_t *partial;
+};
+
 }  // namespace hg

@@ -400,6 +400,17 @@ class Index:
         check(lib().hnswgpu_ivf_search(self._h, _p(Q), len(Q), k, nprobe, _p(ids), _p(d), _p(pr)))
         return (ids, d, pr) if want_probes else (ids, d)
 
+    def ivf_search_filtered(self, Q, k, nprobe, allow, want_probes=False):
+        """hnswgpu_ivf_search_filtered: ivf_search's routing, then the k nearest rows of the probed lists that ``allow``
+        (pack_mask, indexed by row id) lets pass -- only those rows are read; -1 / +inf where fewer than k pass."""
+        Q = _queries(Q, self.dim)
+        allow = _mask_words(allow, self.n)
+        ids = np.empty((len(Q), k), np.int32)
+        d = np.empty((len(Q), k), np.float32)
+        pr = np.empty((len(Q), nprobe), np.int32) if want_probes else None
+        check(lib().hnswgpu_ivf_search_filtered(self._h, _p(Q), len(Q), k, nprobe, _p(allow), _p(ids), _p(d), _p(pr)))
+        return (ids, d, pr) if want_probes else (ids, d)
+
     def ivf_search_lists(self, Q, k, probes):
         Q = _queries(Q, self.dim)
         probes = np.ascontiguousarray(probes, np.int32).reshape(len(Q), -1)
@@ -469,6 +480,14 @@ class Index:
         check(lib().hnswgpu_hnsw_search_filtered_dev(self._h, Q.data_ptr(), Q.shape[0], k, int(ef or 0), allow.data_ptr(),
                                                      ids.data_ptr(), d.data_ptr(),
                                                      stats.data_ptr() if stats is not None else None, st))
+        return ids, d
+
+    def ivf_search_filtered_dev(self, Q, k, nprobe, allow, out=None):
+        """hnswgpu_ivf_search_filtered_dev on torch's current stream: enqueues only, nothing is read back."""
+        Q, ids, d, st = self._dev_args(Q, k, out)
+        allow = self._dev_mask(allow, Q)
+        check(lib().hnswgpu_ivf_search_filtered_dev(self._h, Q.data_ptr(), Q.shape[0], k, nprobe, allow.data_ptr(),
+                                                    ids.data_ptr(), d.data_ptr(), st))
         return ids, d
 
     def rerank_dev(self, Q, cand, k, out=None):

@@ -2,7 +2,9 @@
 
 ``build_index(data, num_partitions=24, distance_fn=..., max_iterations=10)`` runs k-means++ /
 Lloyd on the device; ``search_knn(index, q, k, mode)`` / ``search_ivf_flat(index, q, k, mode=...,
-num_probes=...)`` scan the probed lists with the HIP scan kernel.
+num_probes=...)`` scan the probed lists with the HIP scan kernel;
+``search_knn_filtered`` / ``search_batch_filtered`` (not in the reference, whose IVF index has no
+FilterableIndex) scan only the rows of the probed lists that pass a predicate.
 """
 import random
 
@@ -84,6 +86,43 @@ def search_knn(index, query_vec, k, mode="balanced"):
 
 def search_batch(index, queries, k, mode="balanced", num_probes=None):
     return search_ivf_flat(index, np.asarray(queries, np.float32), k, mode=mode, num_probes=num_probes)
+
+
+def _allow_bits(index, filter_fn):
+    """The predicate on the caller's ids, evaluated once per row on the host (or a ready bool array of length n)."""
+    if callable(filter_fn):
+        return np.fromiter((bool(filter_fn(i)) for i in index.ids), np.bool_, len(index.ids))
+    bits = np.asarray(filter_fn)
+    if bits.dtype != np.bool_ or bits.shape != (index.index.n,):
+        raise ValueError("filter_fn must be a predicate on ids or a bool array with one entry per row")
+    return bits
+
+
+def search_batch_filtered(index, queries, k, filter_fn, mode="balanced", num_probes=None):
+    """FilterableIndex/search-knn-filtered* (api/protocol.clj:34-41) over the probed lists, one predicate per call:
+    ``filter_fn`` is called once per row with ``index.ids[i]`` (or is a bool array of length n) and packed into one
+    allow-mask; the device scans exactly the passing rows of the probed lists (hnswgpu_ivf_search_filtered) and returns the
+    k nearest of them -- not the reference's "search 3k, drop, keep k".  Mode presets as in search_ivf_flat.  A mode without
+    centroid routing (:turbo, ``use_centroids False``: random lists, :271-272) goes through the default helper's rule --
+    search_ivf_flat for 3k, keep what passes, take k."""
+    queries = np.asarray(queries, np.float32)
+    if queries.ndim == 1:
+        queries = queries[None, :]
+    if len(queries) == 0:
+        return []
+    cfg = MODE_CONFIGS.get(mode) or {"num_probes": num_probes or 4, "use_centroids": True}
+    bits = _allow_bits(index, filter_fn)
+    if not cfg["use_centroids"]:
+        res = search_ivf_flat(index, queries, 3 * int(k), mode=mode, num_probes=num_probes)
+        passing = {i for i, b in zip(index.ids, bits) if b}
+        return [[r for r in rs if r["id"] in passing][:int(k)] for rs in res]
+    ids, d = index.index.ivf_search_filtered(queries, int(k), int(cfg["num_probes"]), engine.pack_mask(bits, index.index.n))
+    return [_format(index, ids[i], d[i]) for i in range(len(queries))]
+
+
+def search_knn_filtered(index, query_vec, k, filter_fn, mode="balanced", num_probes=None):
+    """search_batch_filtered for one query: a list of ``{"id", "distance"}`` ascending, fewer than k when fewer pass."""
+    return search_batch_filtered(index, np.asarray(query_vec, np.float32)[None, :], k, filter_fn, mode, num_probes)[0]
 
 
 def index_info(index):

@@ -1,7 +1,8 @@
 """Mirror of ``hnsw.api.protocol`` (src/hnsw/api/protocol.clj): ANNIndex, BatchSearchIndex, PersistableIndex,
 FilterableIndex and the default helpers (filtered search by post-filtering, :96-101; sequential batch search, :92-95) over
-the two GPU-served index types.  The HNSW index filters on the device (ultra_fast.search_knn_filtered); the IVF index keeps
-the default helper."""
+the two GPU-served index types.  The HNSW index filters on the device (ultra_fast.search_knn_filtered).  GpuIvfFlatIndex is
+the reference's IVF index, which has no FilterableIndex and is served by the default helper; GpuFilterableIvfFlatIndex adds
+the protocol on top of it, filtering inside the list scan (ivf_flat.search_knn_filtered)."""
 from . import index_io, ivf_flat, ultra_fast
 
 
@@ -92,6 +93,13 @@ class GpuIvfFlatIndex(ANNIndex, BatchSearchIndex, PersistableIndex):
 
     def index_type_star(self):
         return "ivf-flat"
+
+
+class GpuFilterableIvfFlatIndex(GpuIvfFlatIndex, FilterableIndex):
+    """The IVF index with the allow-mask through its list scan: the k nearest PASSING rows of the probed lists."""
+
+    def search_knn_filtered_star(self, query, k, filter_fn, mode="balanced"):
+        return ivf_flat.search_knn_filtered(self.index, query, k, filter_fn, mode or "balanced")
 
 
 def supports_filtering(index):

@@ -287,6 +287,31 @@ int hnswgpu_hnsw_search_filtered(hnswgpu_index *idx, const float *Q, int32_t nq,
 int hnswgpu_hnsw_search_filtered_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t ef,
                                      const uint32_t *d_allow, int32_t *d_out_ids, float *d_out_dist, int64_t *d_stats,
                                      void *stream);
+/* hnswgpu_ivf_search_filtered (search-ivf-flat, src/hnsw/ann/partition/ivf_flat.clj:236-294, behind
+ *   FilterableIndex/search-knn-filtered*, protocol.clj:34-41): the allow-mask through the list scan, instead of
+ *   default-filtered-search's "search 3k, drop, keep k" (protocol.clj:97-102), which returns about 3k * p / n rows when p of n
+ *   rows pass and reads every row of every probed list whatever the mask says.  Routing is hnswgpu_ivf_search's
+ *   (ivf_flat.clj:261-269) and does not see the mask; out_probes (optional, [nq][nprobe], -1 padded) is what that call
+ *   reports.  Result: the query's candidate stream -- the probed lists concatenated in probe order, each in list order
+ *   (:281-288) -- with the rows whose bit is clear dropped, the k nearest of the rest ascending by (distance, position in
+ *   the stream), -1 / +inf padded when fewer than k pass.  Only the passing rows of the probed lists are read.  `allow` is
+ *   the mask above: indexed by ROW id, not by list position.  k, nprobe and nq are checked as hnswgpu_ivf_search checks
+ *   them; a handle without lists is -3.
+ *   Distances in the gather order (wave-strided f32 fma chain + butterfly: the bits of hnswgpu_rerank and
+ *   hnswgpu_exact_knn_filtered) at EVERY batch size and for every metric, behind a routing in the same order -- never the
+ *   matrix-core tile order: a query's bits depend neither on its batch nor on the rejection mode, the handle's first-search
+ *   measurement (not triggered, not read) or the presence of the int8 / half copies of the lists.  An all-ones mask returns
+ *   hnswgpu_ivf_search's ids and distance bits wherever that call runs in this order: Euclidean always, cosine / dot at
+ *   one query, and every batch on a handle with the compact copies.
+ *   The _dev entry enqueues only and does NOT synchronise: the list of passing positions is sized by the number of list
+ *   positions and nothing is read back.  The host entry stages one caller's batch (it is not combined with concurrent
+ *   callers: their masks differ).
+ *   One handle only.  hnswgpu_group_* and a set of hnswgpu_set_ivf_shard handles are out of scope: their members number
+ *   rows locally, and a mask over the rows of the whole index needs a split per member, which is the caller's to make. */
+int hnswgpu_ivf_search_filtered(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t nprobe,
+                                const uint32_t *allow, int32_t *out_ids, float *out_dist, int32_t *out_probes);
+int hnswgpu_ivf_search_filtered_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t nprobe,
+                                    const uint32_t *d_allow, int32_t *d_out_ids, float *d_out_dist, void *stream);
 
 /* ---- persistence ------------------------------------------------------------------------------------------
  * One flat binary file (header + plain arrays; layout in hnsw-clj_amd/csrc/persist.hip) with the base
