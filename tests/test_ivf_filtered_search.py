@@ -12,8 +12,8 @@ from util import assert_exact
 pytestmark = pytest.mark.gpu
 
 METRICS = ["cosine", "l2", "dot"]
-# (n, dim, nlist, nprobe): lists shorter than a wave's rows in flight / the ordinary case / every list probed / several mask
-# blocks and empty filtered lists / the widest row loaders
+# (n, dim, nlist, nprobe): lists shorter than a wave's rows in flight / the ordinary case / every list probed / 157 mask words
+# in ONE compaction block (of 1024 words; several blocks: test_filtered_scale.py) and empty filtered lists / the widest row loaders
 SHAPES = [(33, 7, 3, 2), (1000, 128, 16, 4), (300, 768, 7, 7), (5000, 96, 64, 8), (70, 1536, 4, 2), (70, 3072, 4, 2)]
 MASKS = ["ones", "zeros", "last", "every32", "half", "sparse", "one_list", "hand"]
 NQS = [1, 12, 70]
