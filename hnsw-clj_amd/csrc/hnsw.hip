@@ -787,7 +787,8 @@ int hnswgpu_set_graph(hnswgpu_index *idx, const int32_t *levels, const int32_t *
         HG_REQUIRE(max_level >= 0 && levels[entry] >= max_level, HNSWGPU_EINVAL, "entry level < max_level");
         HG_REQUIRE(up_off[0] == 0, HNSWGPU_EINVAL, "up_off[0] != 0");
         for (int64_t i = 0; i < n; i++) {
-            HG_REQUIRE(levels[i] >= 0 && up_off[i + 1] - up_off[i] == levels[i], HNSWGPU_EINVAL,
+            HG_REQUIRE(levels[i] >= 0, HNSWGPU_EINVAL, "node %lld has a negative level", (long long)i);
+            HG_REQUIRE(up_off[i + 1] - up_off[i] == levels[i], HNSWGPU_EINVAL,
                        "up_off is not the prefix sum of levels at node %lld", (long long)i);
             HG_REQUIRE(levels[i] <= max_level, HNSWGPU_EINVAL, "node %lld level > max_level", (long long)i);
         }
@@ -1672,6 +1673,7 @@ int hnswgpu_hnsw_build_ex(hnswgpu_index *idx, int32_t M, int32_t ef_construction
         idx->entry = -1;
         idx->max_level = 0;
         idx->has_graph = true;
+        idx->build_flags = flags;  // (rows added to the empty graph are linked by the builder that was asked for)
         return call.close();
     }
     g.l0.assign(static_cast<size_t>(n) * (M0 + 1), -1);
@@ -1791,7 +1793,7 @@ int hnswgpu_hnsw_add(hnswgpu_index *idx, const float *rows, int64_t m, int32_t e
             HG_HIP(hipMemcpyAsync(idx->s_ids.p, owner.data(), sizeof(int32_t) * owner.size(), hipMemcpyHostToDevice, st));
             HG_TRY(launch_edge_dist(idx, nullptr, idx->d_l0, M0, n0, dd0, st));
             HG_TRY(launch_edge_dist(idx, idx->s_ids.as<int32_t>(), idx->d_upadj, M, blocks0, ddu, st));
-            HG_HIP(hipMemcpyAsync(d0.data(), dd0, sizeof(float) * d0.size(), hipMemcpyDeviceToHost, st));
+            if (n0 > 0) HG_HIP(hipMemcpyAsync(d0.data(), dd0, sizeof(float) * d0.size(), hipMemcpyDeviceToHost, st));
             if (blocks0 > 0) HG_HIP(hipMemcpyAsync(du.data(), ddu, sizeof(float) * static_cast<size_t>(blocks0) * M, hipMemcpyDeviceToHost, st));
             HG_HIP(hipStreamSynchronize(st));
             // a full list whose distances ascend IS the pruned order (prune-connections-ultra's stable sort is the identity on

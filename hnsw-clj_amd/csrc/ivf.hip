@@ -1978,6 +1978,10 @@ int hnswgpu_ivf_search_lists(hnswgpu_index *idx, const float *Q, int32_t nq, int
     HG_REQUIRE(probes, HNSWGPU_EINVAL, "probes is null");
     for (int64_t i = 0; i < static_cast<int64_t>(nq) * nprobe; i++)
         HG_REQUIRE(probes[i] >= -1 && probes[i] < idx->nlist, HNSWGPU_EINVAL, "probe list id out of range");
+    if (idx->n == 0) {  // lists without rows (an empty index saved with its lists): nothing to scan, as hnswgpu_exact_knn
+        fill_empty(out_ids, out_dist, static_cast<int64_t>(nq) * k);
+        return 0;
+    }
     hipStream_t st = idx->stream;
     Call call;
     HG_TRY(call.open(idx, st));
@@ -2088,6 +2092,12 @@ int hnswgpu_ivf_search(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k
                        int32_t *out_ids, float *out_dist, int32_t *out_probes) {
     HG_TRY(check_ivf_args(idx, Q, nq, k, nprobe, out_ids, out_dist));
     if (nq == 0) return 0;
+    if (idx->n == 0) {  // lists without rows (an empty index saved with its lists): no list is scanned, none is reported
+        fill_empty(out_ids, out_dist, static_cast<int64_t>(nq) * k);
+        if (out_probes)
+            for (int64_t i = 0; i < static_cast<int64_t>(nq) * nprobe; i++) out_probes[i] = -1;
+        return 0;
+    }
     if (!out_probes) {
         // Concurrent callers are combined into one launch (see hnswgpu_index::SearchReq) -- but only while the
         // combined batch is served by the SAME kernel each request would get alone: the GEMV scan and the MFMA tile

@@ -2,6 +2,12 @@
 // (src/hnsw/helper/index_io.clj:10-80, one pr-str of every node: 492.9 MB for 31k vectors, README.md:22).
 // Layout (little endian): 64-byte header, then the sections that the flags announce, each a plain array that
 // can be mmap'ed by a JVM (FileChannel.map) or uploaded with one DMA:
+//   header    magic[8] "HNSWGPU1", version int32 (1), metric int32 (0 cosine, 1 L2, 2 dot), n int64, dim int32,
+//             flags int32 (bit 0: graph section, bit 1: ivf section; every other bit 0), M int32, M0 int32, entry int32,
+//             max_level int32, up_blocks int64, nlist int32, builder int32
+//             builder: the HNSWGPU_BUILD_* word hnswgpu_hnsw_build_ex made the graph with -- hnswgpu_hnsw_add on the loaded
+//             handle inserts the same way; 0 for a closest-m graph, for one installed by hnswgpu_set_graph, and in every
+//             file without a graph section (files written before the word had a meaning carry 0: they load as they did)
 //   base      n * dim        float32   (unpadded rows)
 //   graph     levels[n] int32, l0_adj[n * M0] int32, up_off[n + 1] int64, up_adj[up_blocks * M] int32
 //   ivf       centroids[nlist * dim] float32, list_off[nlist + 1] int64, list_ids[n] int32
@@ -31,7 +37,7 @@ struct FileHeader {
     int32_t M, M0, entry, max_level;
     int64_t up_blocks;
     int32_t nlist;
-    int32_t reserved;
+    int32_t builder;  // HNSWGPU_BUILD_* of the graph (0: closest-m, or a graph installed by hnswgpu_set_graph)
 };
 static_assert(sizeof(FileHeader) == 64, "header is 64 bytes");
 
@@ -69,6 +75,7 @@ static int save_to(hnswgpu_index *idx, Call &call, FILE *f) {
     h.max_level = idx->max_level;
     h.up_blocks = idx->up_blocks;
     h.nlist = idx->nlist;
+    h.builder = idx->has_graph ? idx->build_flags : 0;
     HG_TRY(put(f, &h, 1));
     if (idx->n > 0) {
         std::vector<float> base(static_cast<size_t>(idx->n) * idx->dim);
@@ -97,6 +104,10 @@ static int64_t expected_file_size(const FileHeader &h) {
     if (h.n < 0 || h.n >= 2147483647LL || h.dim < 1 || h.dim > 3072) return -1;
     if (h.M < 0 || h.M > kMaxDeg || h.M0 < 0 || h.M0 > kMaxDeg) return -1;
     if (h.nlist < 0 || h.up_blocks < 0 || h.up_blocks > h.n * 31) return -1;   // a node has at most 30 upper levels
+    if (h.flags & ~3) return -1;   // a section this version does not know: its bytes would be taken for another's
+    constexpr int32_t kBuilders = HNSWGPU_BUILD_SEQUENTIAL | HNSWGPU_BUILD_HEURISTIC | HNSWGPU_BUILD_SYMMETRIC | HNSWGPU_BUILD_EXTEND;
+    if ((h.builder & ~kBuilders) || (h.builder && !(h.flags & 1))) return -1;   // only a graph has a builder
+    if ((h.builder & (HNSWGPU_BUILD_SYMMETRIC | HNSWGPU_BUILD_EXTEND)) && !(h.builder & HNSWGPU_BUILD_HEURISTIC)) return -1;
     if ((h.flags & 2) && (h.nlist < 1)) return -1;
     if ((h.flags & 1) && (h.M < 1 || h.M0 < 1)) return -1;
     int64_t sz = sizeof(FileHeader) + h.n * h.dim * 4;   // < 2^31 * 3072 * 4: no overflow in int64
@@ -190,6 +201,7 @@ static int load_from(FILE *fp, const char *path, int32_t device, hnswgpu_index *
             // set_graph re-validates every level, offset and edge: a damaged file is rejected, never traversed
             HG_TRY(hnswgpu_set_graph(idx, levels.data(), l0.data(), h.M0, upoff.data(), up.data(), h.M, h.entry,
                                      h.max_level));
+            idx->build_flags = h.builder;  // set_graph installs a graph without a builder; this one comes with the file's
         }
         if (h.flags & 2) {
             std::vector<float> cent;

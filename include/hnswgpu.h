@@ -125,7 +125,9 @@ int hnswgpu_hnsw_build(hnswgpu_index *idx, int32_t M, int32_t ef_construction, i
  *   HNSWGPU_BUILD_SYMMETRIC   with HEURISTIC: an edge a pruning drops is removed from the other node's list as well
  *                             (graph.clj:226-231)
  *   HNSWGPU_BUILD_EXTEND      with HEURISTIC: extend-candidates? for the new node's own selection (graph.clj:191-195)
- * hnswgpu_hnsw_add inserts with the options the handle's graph was built with (batched). */
+ * hnswgpu_hnsw_add inserts with the options the handle's graph was built with (batched).  The index file carries them: a
+ * graph that came back through hnswgpu_load keeps its builder.  A graph installed by hnswgpu_set_graph has none: rows
+ * added to it are linked to their m closest candidates. */
 #define HNSWGPU_BUILD_SEQUENTIAL 1
 #define HNSWGPU_BUILD_HEURISTIC 2
 #define HNSWGPU_BUILD_SYMMETRIC 4
@@ -317,7 +319,12 @@ int hnswgpu_ivf_search_filtered_dev(hnswgpu_index *idx, const float *d_Q, int32_
  * One flat binary file (header + plain arrays; layout in hnsw-clj_amd/csrc/persist.hip) with the base
  * vectors, the graph and the IVF lists -- replaces helper/index-io's save-index / load-index, an EDN
  * pr-str of every node (src/hnsw/helper/index_io.clj:10-80) and api/save, api/load-index which throw
- * (src/hnsw/api.clj:40-50).  String ids are the caller's to store.  load re-validates the graph. */
+ * (src/hnsw/api.clj:40-50).  String ids are the caller's to store.  load judges the header against the documented limits
+ * and the size of the file before it reads the body (unknown flag or builder bits are a corrupt header, not ignored), and
+ * re-validates the graph and the lists: a damaged file is an error code, never a search over it.  The header's last word
+ * holds the HNSWGPU_BUILD_* flags of the graph, so a loaded graph grows (hnswgpu_hnsw_add) as the saved one would have;
+ * files from before the word had a meaning hold 0 there and load as they did (the version stays 1).  Saving what was loaded
+ * gives the same bytes. */
 int hnswgpu_save(hnswgpu_index *idx, const char *path);
 int hnswgpu_load(const char *path, int32_t device, hnswgpu_index **out);
 

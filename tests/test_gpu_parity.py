@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
+import index_file  # noqa: E402
 from util import assert_exact, assert_topk_parity, close, metric_scale  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -2020,8 +2021,10 @@ def test_persistence_and_lightning(eng, oracle, tmp_path):
     with pytest.raises(ValueError, match="metric"):
         index_io.load_index(path, ultra_fast.euclidean_distance_ultra)
     raw = bytearray(open(path, "rb").read())
-    raw[64 + 600 * 40 * 4 + 600 * 4 + 8] = 0x7f                                       # an edge pointing far outside
-    raw[64 + 600 * 40 * 4 + 600 * 4 + 11] = 0x7f
+    sec = index_file.section_offsets(index_file.unpack_header(raw))                    # the layout: tests/index_file.py
+    assert (sec["base"], sec["levels"], sec["l0_adj"]) == (64, 64 + 600 * 40 * 4, 64 + 600 * 40 * 4 + 600 * 4)
+    raw[sec["l0_adj"] + 8] = 0x7f                                                     # an edge pointing far outside
+    raw[sec["l0_adj"] + 11] = 0x7f
     open(str(tmp_path / "bad.bin"), "wb").write(raw)
     with pytest.raises(Exception, match="out of range"):
         eng.Index.load(str(tmp_path / "bad.bin"))
@@ -2030,7 +2033,8 @@ def test_persistence_and_lightning(eng, oracle, tmp_path):
         eng.Index.load(str(tmp_path / "short.bin"))
     # the header's up_blocks and the body's up_off must describe the same array (set_graph indexes one with the other)
     raw = bytearray(open(path, "rb").read())
-    upoff_end = 64 + 600 * 40 * 4 + 600 * 4 + 600 * 32 * 4 + 600 * 8
+    upoff_end = sec["up_adj"] - 8                                                     # up_off[n], the last of n + 1 offsets
+    assert upoff_end == 64 + 600 * 40 * 4 + 600 * 4 + 600 * 32 * 4 + 600 * 8
     raw[upoff_end:upoff_end + 8] = (10 ** 9).to_bytes(8, "little")
     open(str(tmp_path / "upoff.bin"), "wb").write(raw)
     with pytest.raises(Exception, match="up_off"):
@@ -2181,23 +2185,11 @@ def test_c_abi_from_plain_c(native_lib, oracle, tmp_path):
     assert out.returncode == 0, out.stdout + out.stderr
     assert "abi_demo ok" in out.stdout
     # the flat index file (layout: hnsw-clj_amd/csrc/persist.hip): header, base, levels, l0_adj, up_off, up_adj
-    raw = open(mig, "rb").read()
-    hdr = np.frombuffer(raw[:64], np.int32)
-    n, dim = int(np.frombuffer(raw[16:24], np.int64)[0]), int(hdr[6])
-    flags, M, M0, entry, max_level = int(hdr[7]), int(hdr[8]), int(hdr[9]), int(hdr[10]), int(hdr[11])
-    up_blocks = int(np.frombuffer(raw[48:56], np.int64)[0])
-    assert raw[:8] == b"HNSWGPU1" and flags == 1 and (n, dim, M, M0) == (2000, 96, 16, 32)
-    o = 64
-    base = np.frombuffer(raw, np.float32, n * dim, o).reshape(n, dim)
-    o += 4 * n * dim
-    levels = np.frombuffer(raw, np.int32, n, o)
-    o += 4 * n
-    l0 = np.frombuffer(raw, np.int32, n * M0, o).reshape(n, M0)
-    o += 4 * n * M0
-    up_off = np.frombuffer(raw, np.int64, n + 1, o)
-    o += 8 * (n + 1)
-    up = np.frombuffer(raw, np.int32, up_blocks * M, o)
-    assert o + 4 * up_blocks * M == len(raw)
+    f = index_file.read_index_file(mig)                       # (refuses a file whose size is not what its header implies)
+    n, dim, flags, M, M0, entry, max_level = (f[key] for key in ("n", "dim", "flags", "M", "M0", "entry", "max_level"))
+    assert f["magic"] == b"HNSWGPU1" and flags == 1 and (n, dim, M, M0) == (2000, 96, 16, 32)
+    base, levels, l0, up_off, up = (f[key] for key in ("base", "levels", "l0_adj", "up_off", "up_adj"))
+    assert f["size"] == 64 + 4 * n * dim + 4 * n + 4 * n * M0 + 8 * (n + 1) + 4 * f["up_blocks"] * M
     r = open(res, "rb").read()
     ids = np.frombuffer(r, np.int32, 40, 0).reshape(8, 5)
     d = np.frombuffer(r, np.float32, 40, 160).reshape(8, 5)
