@@ -143,7 +143,8 @@ __device__ __forceinline__ float query_norm(const float4 (&q)[NCH]) {
     return __builtin_sqrtf(wave_sum(lane_partial<NCH, false>(q, q)));
 }
 
-// total order on (distance, order) packed in 64 bits; -0 is canonicalised to +0, NaN sorts last
+// total order on (distance, order) packed in 64 bits; -0 is canonicalised to +0.  NaN is no part of any entry point's
+// contract: one with the sign bit clear sorts behind +inf, one with the sign bit set sorts before -inf
 __device__ __forceinline__ uint64_t make_key(float d, uint32_t ord) {
     d = d + 0.0f;
     uint32_t u = __float_as_uint(d);
