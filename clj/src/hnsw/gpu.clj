@@ -17,6 +17,7 @@
      (batch-distances index query-vec)                               ; simd-optimized/batch-cosine-distances
      (top-k-distances index query-vec k)                             ; simd-optimized/top-k-distances
      (add-vector! index new-data)                                    ; hnsw.api/add-vector!, insert-single on a live index
+     (add-ivf-vectors! index new-data)                               ; the same for a live IVF-FLAT index: hnswgpu_ivf_add
      (from-ultra-graph graph)                                        ; a graph built by the reference's own insert-single
      (from-ivf-flat-index ivf)                                       ; an IVFFlatIndex built by the reference's own k-means
      (save idx path) / (load-index path ids)                         ; helper/index-io save-index / load-index
@@ -114,6 +115,18 @@
     (check (.invokeWithArguments ^MethodHandle @h-add
                                  [(:handle idx) (floats-of arena (mapv second new-data) (:dim idx)) (long (count new-data))
                                   (int ef-construction) (long seed)])))
+  (update idx :ids into (map first new-data)))
+
+(def ^:private h-ivfadd (delay (fn-handle "hnswgpu_ivf_add" (FunctionDescriptor/of I (into-array [P P L])))))
+
+(defn add-ivf-vectors!
+  "add-vector! (src/hnsw/api.clj:30-33) for a live IVF-FLAT GpuIndex (the reference's IVFFlatIndex is an immutable record): the new
+   [id ^doubles vector] pairs join the base matrix, each behind the present members of its nearest partition (ivf_flat.clj:79-90);
+   the centroids stay.  Returns the index with their ids appended.  One call per batch of new vectors is the efficient shape."
+  [idx new-data]
+  (with-open [arena (Arena/ofConfined)]
+    (check (.invokeWithArguments ^MethodHandle @h-ivfadd
+                                 [(:handle idx) (floats-of arena (mapv second new-data) (:dim idx)) (long (count new-data))])))
   (update idx :ids into (map first new-data)))
 
 (defn- results [idx ^MemorySegment ids ^MemorySegment ds q k]

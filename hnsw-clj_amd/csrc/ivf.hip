@@ -8,6 +8,7 @@
 
 #include "engine.hpp"
 #include "stream_kernels.hpp"
+#include "ivf_add_kernels.hpp"
 #include "javarandom.hpp"
 
 namespace hg {
@@ -1935,6 +1936,190 @@ int hnswgpu_ivf_build(hnswgpu_index *idx, int32_t nlist, int32_t max_iter, int64
     }
     HG_TRY(install_lists(idx, nlist, off.data(), ids.data(), st));
     HG_TRY(download_centroids(idx, st));
+    return call.close();
+}
+
+// Rows join the lists of a live handle (include/hnswgpu.h).  The reference's IVFFlatIndex is an immutable record; what is
+// restated is its assignment rule (assign-to-nearest-centroid, ivf_flat.clj:79-90) and its "inverted lists in index order"
+// (:137-211): the grown handle holds what hnswgpu_create(all rows) + hnswgpu_set_ivf(same centroids, merged lists) holds.
+// One chain of launches on the handle's stream: base / norms / int8 rows grow as in hnswgpu_hnsw_add, the new rows are
+// the queries of a GEMV-order scan over the centroids, three integer kernels place them (ivf_add_kernels.hpp), one
+// kernel writes the grown list-order rows from the old ones and the new base rows, the int8 / half copies are made over
+// them as for a fresh set of lists, and ONE readback refreshes the host mirrors.
+int hnswgpu_ivf_add(hnswgpu_index *idx, const float *rows, int64_t m) {
+    HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
+    HG_REQUIRE(m >= 0, HNSWGPU_EINVAL, "m must be >= 0");
+    if (m == 0) return 0;
+    HG_REQUIRE(rows, HNSWGPU_EINVAL, "rows is null");
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_REQUIRE(idx->nlist > 0, HNSWGPU_ESTATE, "index has no IVF lists (call hnswgpu_ivf_build / hnswgpu_set_ivf first)");
+    HG_REQUIRE(!idx->has_graph, HNSWGPU_ESTATE,
+               "the index holds an HNSW graph: rows added to the IVF lists would be missing from the graph");
+    HG_REQUIRE(idx->d_glistoff == nullptr, HNSWGPU_ESTATE, "a shard of a larger IVF index (hnswgpu_set_ivf_shard) cannot grow alone");
+    const int64_t n0 = idx->n, n1 = n0 + m;
+    HG_REQUIRE(n1 < 2147483647LL, HNSWGPU_ELIMIT, "the index must hold fewer than 2^31 rows");
+    HG_TRY(call.quiesce());
+    const int64_t ld = idx->ld;
+    const int32_t nlist = idx->nlist;
+    // Failure-atomic, as hnswgpu_hnsw_add: every array the call makes is STAGED.  The handle's fields point at the staged
+    // arrays only for the last step (the int8 / half copies, made by the functions that make them for fresh lists; idx->mu
+    // is held and the streams are quiesced: no caller sees the intermediate state) and get their old values back, the
+    // staged arrays freed, if any step fails.  On success the old arrays are freed.
+    struct Arrays {
+        float *base = nullptr, *norms = nullptr, *lrows = nullptr, *lnorms = nullptr;
+        uint32_t *qrows = nullptr, *lctile = nullptr;
+        float4 *qmeta = nullptr, *lcmeta = nullptr, *lhmeta = nullptr;
+        uint2 *lhalf = nullptr;
+        int64_t *listoff = nullptr;
+        int32_t *listids = nullptr;
+        bool alias = false;
+    } nw, old;
+    auto of_handle = [&](Arrays &a) {
+        a.base = idx->d_base, a.norms = idx->d_norms, a.lrows = idx->d_lrows, a.lnorms = idx->d_lnorms;
+        a.qrows = idx->d_qrows, a.qmeta = idx->d_qmeta, a.lctile = idx->d_lctile, a.lcmeta = idx->d_lcmeta;
+        a.lhalf = idx->d_lhalf, a.lhmeta = idx->d_lhmeta, a.listoff = idx->d_listoff, a.listids = idx->d_listids;
+        a.alias = idx->lrows_alias;
+    };
+    auto to_handle = [&](const Arrays &a, int64_t n) {
+        idx->d_base = a.base, idx->d_norms = a.norms, idx->d_lrows = a.lrows, idx->d_lnorms = a.lnorms;
+        idx->d_qrows = a.qrows, idx->d_qmeta = a.qmeta, idx->d_lctile = a.lctile, idx->d_lcmeta = a.lcmeta;
+        idx->d_lhalf = a.lhalf, idx->d_lhmeta = a.lhmeta, idx->d_listoff = a.listoff, idx->d_listids = a.listids;
+        idx->lrows_alias = a.alias;
+        idx->n = n;
+    };
+    auto free_arrays = [](Arrays &a) {
+        if (a.alias) a.lrows = a.lnorms = nullptr;  // the base rows themselves: freed once
+        void *ptrs[] = {a.base, a.norms, a.lrows, a.lnorms, a.qrows, a.lctile, a.qmeta, a.lcmeta, a.lhmeta, a.lhalf, a.listoff, a.listids};
+        for (void *p : ptrs)
+            if (p) (void)hipFree(p);
+        a = Arrays();
+    };
+    of_handle(old);
+    bool installed = false;
+    std::vector<int64_t> h_off;
+    std::vector<int32_t> h_ids;
+    auto grow = [&]() -> int {
+        // ---- 1. the base matrix, its norms and base-order int8 rows grow (staged)
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.base), sizeof(float) * static_cast<size_t>(n1) * ld));
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.norms), sizeof(float) * static_cast<size_t>(n1)));
+        if (n0 > 0) {
+            HG_HIP(hipMemcpyAsync(nw.base, old.base, sizeof(float) * static_cast<size_t>(n0) * ld, hipMemcpyDeviceToDevice, st));
+            HG_HIP(hipMemcpyAsync(nw.norms, old.norms, sizeof(float) * static_cast<size_t>(n0), hipMemcpyDeviceToDevice, st));
+        }
+        if (ld != idx->dim) HG_HIP(hipMemsetAsync(nw.base + n0 * ld, 0, sizeof(float) * static_cast<size_t>(m) * ld, st));
+        HG_HIP(hipMemcpy2DAsync(nw.base + n0 * ld, sizeof(float) * ld, rows, sizeof(float) * idx->dim, sizeof(float) * idx->dim,
+                                static_cast<size_t>(m), hipMemcpyHostToDevice, st));
+        HG_TRY(launch_norms(idx->nch, nw.base + n0 * ld, ld, m, nw.norms + n0, st));
+        if (old.qrows) HG_TRY(quantize_rows(idx, nw.base, n1, &nw.qrows, &nw.qmeta, st));  // (all rows again: one pass over the base)
+        // ---- 2. the new rows' nearest centroids (ivf_flat.clj:79-90) -> s_ord [m].  Always the GEMV-order scan, never the
+        // MFMA tile path of assign_enqueue: a row's list must not depend on the size of the batch it arrived in.
+        ScanArgs sa;
+        memset(&sa, 0, sizeof(sa));
+        sa.rows = idx->d_cent;
+        sa.row_norms = idx->d_cnorms;
+        sa.ld = ld;
+        sa.nrows_all = nlist;
+        sa.Q = nw.base + n0 * ld;
+        sa.qld = ld;
+        sa.q_norms = nw.norms + n0;
+        sa.dim = idx->dim;
+        sa.metric = idx->metric;
+        sa.pairs = nullptr;
+        sa.k = 1;
+        sa.role = ROLE_ASSIGN;
+        HG_TRY(scan_topk(idx, sa, static_cast<int32_t>(m), 1, nlist, st, PROF_ASSIGN));
+        // ---- 3. placement: new rows per list, the grown offsets, every new row's position (its id goes there)
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.listoff), sizeof(int64_t) * (nlist + 1)));
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.listids), sizeof(int32_t) * static_cast<size_t>(n1)));
+        HG_TRY(idx->s_misc.ensure(sizeof(uint32_t) * (4 + static_cast<size_t>(nlist))));
+        HG_HIP(hipMemsetAsync(idx->s_misc.p, 0, sizeof(uint32_t) * (4 + static_cast<size_t>(nlist)), st));
+        IvfAddArgs a;
+        memset(&a, 0, sizeof(a));
+        a.assign = idx->s_ord.as<uint32_t>();
+        a.m = m;
+        a.n0 = n0;
+        a.nlist = nlist;
+        a.old_off = old.listoff;
+        a.new_off = nw.listoff;
+        a.flags = idx->s_misc.as<uint32_t>();
+        a.counts = a.flags + 4;
+        a.new_ids = nw.listids;
+        a.old_ids = old.listids;
+        a.old_lrows = old.lrows;
+        a.old_lnorms = old.lnorms;
+        a.base = nw.base;
+        a.norms = nw.norms;
+        a.ld = ld;
+        const unsigned count_wgs = static_cast<unsigned>(std::min<int64_t>((m + kWG - 1) / kWG, 2048));
+        hipLaunchKernelGGL(ivf_add_count_kernel, dim3(count_wgs), dim3(kWG), 0, st, a);
+        hipLaunchKernelGGL(ivf_add_offsets_kernel, dim3(1), dim3(kWG), 0, st, a);
+        hipLaunchKernelGGL(ivf_add_place_kernel, dim3(static_cast<unsigned>(nlist)), dim3(kWG), 0, st, a);
+        HG_HIP(hipGetLastError());
+        // ---- 4. splice: the grown list-order rows, norms and ids.  Lists that are the base rows in place (or no rows at
+        // all) stay so while every new row lands on the position of its own id -- one word read back says so.
+        uint32_t flags = kAddNotIdentity;
+        if (old.alias || n0 == 0) {
+            HG_HIP(hipMemcpyAsync(&flags, a.flags, sizeof(flags), hipMemcpyDeviceToHost, st));
+            HG_HIP(hipStreamSynchronize(st));
+            HG_REQUIRE(!(flags & kAddBadAssign), HNSWGPU_EINVAL, "a new row has no nearest centroid (NaN in rows?)");
+        }
+        if (!(flags & kAddNotIdentity)) {
+            nw.alias = true;
+            nw.lrows = nw.base;
+            nw.lnorms = nw.norms;
+            if (n0 > 0) HG_HIP(hipMemcpyAsync(nw.listids, old.listids, sizeof(int32_t) * static_cast<size_t>(n0), hipMemcpyDeviceToDevice, st));
+        } else {
+            HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.lrows), sizeof(float) * static_cast<size_t>(n1) * ld));
+            HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.lnorms), sizeof(float) * static_cast<size_t>(n1)));
+            a.new_lrows = nw.lrows;
+            a.new_lnorms = nw.lnorms;
+            hipLaunchKernelGGL(ivf_splice_kernel, dim3(static_cast<unsigned>((n1 + kNWave - 1) / kNWave)), dim3(kWG), 0, st, a);
+            HG_HIP(hipGetLastError());
+        }
+        // ---- the int8 tile codes and the half copy over the grown list rows: made as for a fresh set of lists, by the
+        // handle's rejection mode (ensure_list_codes / ensure_list_half read the handle)
+        to_handle(nw, n1);
+        installed = true;
+        HG_TRY(ensure_list_codes(idx, st));
+        HG_TRY(ensure_list_half(idx, st));
+        of_handle(nw);
+        // ---- 5. one readback: flags, offsets, ids
+        h_off.resize(static_cast<size_t>(nlist) + 1);
+        h_ids.resize(static_cast<size_t>(n1));
+        HG_HIP(hipMemcpyAsync(&flags, a.flags, sizeof(flags), hipMemcpyDeviceToHost, st));
+        HG_HIP(hipMemcpyAsync(h_off.data(), nw.listoff, sizeof(int64_t) * (nlist + 1), hipMemcpyDeviceToHost, st));
+        HG_HIP(hipMemcpyAsync(h_ids.data(), nw.listids, sizeof(int32_t) * static_cast<size_t>(n1), hipMemcpyDeviceToHost, st));
+        HG_HIP(hipStreamSynchronize(st));
+        HG_REQUIRE(!(flags & kAddBadAssign), HNSWGPU_EINVAL, "a new row has no nearest centroid (NaN in rows?)");
+        HG_REQUIRE(h_off[nlist] == n1, HNSWGPU_EHIP, "the grown lists hold %lld rows, not %lld", (long long)h_off[nlist], (long long)n1);
+        return 0;
+    };
+    int rc;
+    try {
+        rc = grow();
+    } catch (const std::bad_alloc &) {
+        set_error("host allocation failed in hnswgpu_ivf_add");
+        rc = HNSWGPU_ENOMEM;
+    }
+    if (rc != 0) {
+        (void)hipStreamSynchronize(st);
+        if (installed) of_handle(nw);  // (whatever the last step made is the staged set's)
+        to_handle(old, n0);
+        free_arrays(nw);
+        return rc;
+    }
+    idx->h_listoff.swap(h_off);
+    idx->h_listids.swap(h_ids);
+    idx->max_list_len = 0;
+    idx->min_list_len = idx->h_listoff[1] - idx->h_listoff[0];
+    for (int l = 0; l < nlist; l++) {
+        idx->max_list_len = std::max(idx->max_list_len, idx->h_listoff[l + 1] - idx->h_listoff[l]);
+        idx->min_list_len = std::min(idx->min_list_len, idx->h_listoff[l + 1] - idx->h_listoff[l]);
+    }
+    idx->ivf_n_global = n1;
+    free_arrays(old);  // (the first-search verdict of a mode-1 handle, ivf_calibrated / ivf_stream_off, stays: not measured again)
     return call.close();
 }
 

@@ -325,6 +325,15 @@ class Index:
     def ivf_build(self, nlist=24, max_iterations=10, seed=42):
         check(lib().hnswgpu_ivf_build(self._h, nlist, max_iterations, seed))
 
+    def ivf_add(self, rows):
+        """hnswgpu_ivf_add: `rows` join the base and the installed lists (each to its nearest centroid, behind the list's
+        present members); returns the row ids they got."""
+        rows = _queries(rows, self.dim)
+        first = self.n
+        check(lib().hnswgpu_ivf_add(self._h, _p(rows), len(rows)))
+        self.n += len(rows)
+        return np.arange(first, self.n, dtype=np.int32)
+
     def set_ivf(self, centroids, list_off, list_ids):
         cen = _f32(centroids)
         off = np.ascontiguousarray(list_off, np.int64)

@@ -3,7 +3,7 @@
 ``build_index(data, num_partitions=24, distance_fn=..., max_iterations=10)`` runs k-means++ /
 Lloyd on the device; ``search_knn(index, q, k, mode)`` / ``search_ivf_flat(index, q, k, mode=...,
 num_probes=...)`` scan the probed lists with the HIP scan kernel;
-``search_knn_filtered`` / ``search_batch_filtered`` (not in the reference, whose IVF index has no
+``add_vectors(index, data)`` grows a built index; ``search_knn_filtered`` / ``search_batch_filtered`` (not in the reference, whose IVF index has no
 FilterableIndex) scan only the rows of the probed lists that pass a predicate.
 """
 import random
@@ -54,6 +54,17 @@ def build_ivf_flat_index(data, num_partitions=24, distance_fn=cosine_distance_ul
 def build_index(data, **opts):
     """ivf_flat.clj:300-303"""
     return build_ivf_flat_index(data, **opts)
+
+
+def add_vectors(index, data):
+    """The IVF side of add-vector! (api.clj:30-33; the reference's IVFFlatIndex itself is immutable): ``data`` has the form
+    ``build_index`` takes; every vector joins its nearest partition behind the partition's present members
+    (hnswgpu_ivf_add), the centroids stay.  Returns the index."""
+    ids, rows = _split(data)
+    if ids:
+        index.index.ivf_add(rows)
+        index.ids.extend(ids)
+    return index
 
 
 def _format(index, ids_row, d_row):

@@ -140,7 +140,8 @@ int hnswgpu_hnsw_build_ex(hnswgpu_index *idx, int32_t M, int32_t ef_construction
  * the search kernel and the linker of hnswgpu_hnsw_build, against the CURRENT graph (any graph with M0 = 2 M:
  * hnswgpu_hnsw_build's, or one installed by hnswgpu_set_graph / hnswgpu_load -- its edge distances, which the reference's
  * pruning sorts by (:279-299), are recomputed on the device).  Not concurrent with searches on the same handle (they
- * wait); IVF lists must be built / installed AFTER the rows they cover have been added. */
+ * wait); IVF lists must be built / installed AFTER the rows they cover have been added (a handle that holds lists and
+ * no graph grows through hnswgpu_ivf_add). */
 int hnswgpu_hnsw_add(hnswgpu_index *idx, const float *rows, int64_t m, int32_t ef_construction, int64_t seed);
 int hnswgpu_graph_sizes(const hnswgpu_index *idx, int32_t *M, int32_t *M0, int64_t *up_blocks, int32_t *entry,
                         int32_t *max_level);
@@ -174,6 +175,34 @@ int hnswgpu_hnsw_search_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, in
  *   the order of candidates that tie within that) depend on which side of the boundary its batch falls.  Calls combined from
  *   concurrent host threads never change the kernel a call would get alone.  Euclidean: one arithmetic throughout. */
 int hnswgpu_ivf_build(hnswgpu_index *idx, int32_t nlist, int32_t max_iter, int64_t seed);
+/* Rows join the inverted lists of a LIVE handle (the IVF side of add-vector! src/hnsw/api.clj:30-33; the reference's
+ * IVFFlatIndex is an immutable record, so what is restated is its assignment rule and its list order).
+ * `rows` is m x dim float32 host memory; the rows join the base matrix as rows n, n + 1, ..., n + m - 1.  The norms grow
+ * with it, and so do the base-order int8 rows if the handle has them.
+ *   - Centroids do not move.  Each new row goes to its nearest centroid: strict <, lowest list index wins ties
+ *     (assign-to-nearest-centroid, ivf_flat.clj:79-90).  The arithmetic is ONE order at every m -- the GEMV-order scan,
+ *     never the MFMA tile path hnswgpu_kmeans_assign may take -- so a row's list never depends on the batch it came in.
+ *   - Each list keeps its old members in their old order and receives its new members behind them, ascending by row id
+ *     ("inverted lists in index order", :137-211).  m rows in one call or in any split of calls give the same lists.
+ *   - After the call everything a search reads equals, bit for bit, what hnswgpu_create(all rows) +
+ *     hnswgpu_set_rejection_test(same mode) + hnswgpu_set_ivf(same centroids, merged lists) holds: list offsets, ids,
+ *     rows and norms in list order, their int8 and half-precision copies, the list-length bookkeeping, and what
+ *     hnswgpu_get_ivf / hnswgpu_save export.  The first-search verdict of a mode-1 handle (hnswgpu_ivf_stream_state) is
+ *     kept, not measured again.  A handle whose lists are its base rows in place (identity list_ids) gets list-order
+ *     copies of its own once the merged lists are no longer the identity.
+ *   - Failure-atomic, like hnswgpu_hnsw_add: every new array is staged under the handle's lock with its streams
+ *     quiesced; on any failure the staged arrays are freed and the handle is what it was.  Searches from other threads
+ *     wait and then see either the old or the new index.  An allow-mask of a filtered search simply is longer at the
+ *     next call; scratch sized by n grows on demand.
+ *   - Cost: one pass over the base and the list rows on the device per CALL (copies and re-quantisation; no host pass
+ *     over the rows, no upload of old rows) plus nlist workgroups that each read the call's m assignments -- add rows
+ *     in batches.
+ * Returns (all checked before `rows` is read): HNSWGPU_EINVAL for a null handle, m < 0 or null rows; 0 for m == 0
+ * (nothing happens); HNSWGPU_ESTATE without lists, on a handle that holds an HNSW graph (the rows would be missing from
+ * the graph) and on a shard (hnswgpu_set_ivf_shard); HNSWGPU_ELIMIT for n + m >= 2^31.
+ * Out of scope: a handle with both a graph and lists, hnswgpu_group_*, and sharded.ShardedIVF (rebuild those).
+ * hnswgpu_hnsw_add still refuses a handle with lists. */
+int hnswgpu_ivf_add(hnswgpu_index *idx, const float *rows, int64_t m);
 int hnswgpu_set_ivf(hnswgpu_index *idx, const float *centroids, int32_t nlist, const int64_t *list_off,
                     const int32_t *list_ids);
 int hnswgpu_get_ivf(const hnswgpu_index *idx, float *centroids, int64_t *list_off, int32_t *list_ids);
