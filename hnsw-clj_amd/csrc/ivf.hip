@@ -368,9 +368,11 @@ __global__ __launch_bounds__(kWG) void permute_rows_kernel(const float *src, con
     if (lane == 0) dst_norms[pos] = src_norms[s];
 }
 
-// compute-centroid (ivf_flat.clj:66-77): f64 sum of the member rows in index order, divided by the
-// count, rounded to f32 for storage; an empty list keeps its previous centroid (:112-114).
-// One workgroup per list; thread t owns columns t, t+256, ...
+// compute-centroid (ivf_flat.clj:66-77): f64 sum of the member rows, one add at a time in LIST order (the order of
+// listids: index order for the lists hnswgpu_ivf_build makes, whatever the caller gave to hnswgpu_list_means), divided
+// by the count, rounded to f32 for storage.  An empty list is left alone: inside hnswgpu_ivf_build it keeps its
+// previous centroid (:112-114), hnswgpu_list_means zeroes the output first (lightning.clj:118-120).
+// One workgroup per list; thread t owns columns t, t+256, ...; `cent` has the rows' stride ld.
 __global__ __launch_bounds__(kWG) void centroid_mean_kernel(const float *rows, int64_t ld, int dim,
                                                             const int64_t *listoff, const int32_t *listids,
                                                             float *cent) {
@@ -385,7 +387,8 @@ __global__ __launch_bounds__(kWG) void centroid_mean_kernel(const float *rows, i
 }
 
 // The f64 column sums of compute-centroid (ivf_flat.clj:70-75) without the division: what one shard of a row-sharded
-// index contributes to a Lloyd update (the sums of all shards are added, then divided by the global count).
+// index contributes to a Lloyd update (the sums of all shards are added, then divided by the global count).  Same order
+// of addition as above; an empty list gives zeros; `sums` is dense (stride dim), unlike the rows and centroids (ld).
 __global__ __launch_bounds__(kWG) void list_sum_kernel(const float *rows, int64_t ld, int dim, const int64_t *listoff,
                                                        const int32_t *listids, double *sums) {
     int l = blockIdx.x;

@@ -387,14 +387,17 @@ def ivf_build(base, nlist=24, max_iterations=10, metric=COSINE, seed=42):
     return cen, a
 
 
-def ivf_build_dev(base, nlist=24, max_iterations=10, metric=COSINE, seed=42):
-    """The IVF build in the engine's own arithmetic (see orc_ivf_build_dev) -> (chosen rows, centroids f32, assign)."""
+def ivf_build_dev(base, nlist=24, max_iterations=10, metric=COSINE, seed=42, assign_mode=None):
+    """The IVF build in the engine's own arithmetic (see orc_ivf_build_dev) -> (chosen rows, centroids f32, assign).
+    assign_mode: the arithmetic of the assignment passes; None = what the engine takes by default (the MFMA tile kernel
+    for cosine / dot, the GEMV order for L2), MODE_DEV = the GEMV order (HNSWGPU_TUNE_TILE = 0)."""
     base = _f32(base)
     n, dim = base.shape
     chosen = np.zeros(nlist, np.int32)
     cen = np.zeros((nlist, dim), np.float32)
     a = np.zeros(n, np.int32)
-    assign_mode = MODE_DEV if metric == L2 else MODE_MFMA
+    if assign_mode is None:
+        assign_mode = MODE_DEV if metric == L2 else MODE_MFMA
     lib().orc_ivf_build_dev(_p(base), n, dim, int(metric), MODE_DEV, assign_mode, nlist, max_iterations, int(seed),
                             _p(chosen), _p(cen), _p(a))
     return chosen, cen, a
