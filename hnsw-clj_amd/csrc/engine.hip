@@ -1351,6 +1351,7 @@ int slot_prepare(hnswgpu_index::Slot &s, size_t bytes, int device) {
     if (!s.d_again) {
         HG_HIP(hipMalloc(reinterpret_cast<void **>(&s.d_again), sizeof(int32_t) * (kZcMaxQueries + 1)));
         HG_HIP(hipMalloc(reinterpret_cast<void **>(&s.d_done), sizeof(uint32_t) * 4));
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&s.d_order), sizeof(int32_t) * 2 * kZcMaxQueries));
         HG_HIP(hipMemsetAsync(s.d_again, 0, sizeof(int32_t) * (kZcMaxQueries + 1), s.st));
         HG_HIP(hipMemsetAsync(s.d_done, 0, sizeof(uint32_t) * 4, s.st));
         HG_HIP(hipStreamSynchronize(s.st));
@@ -2242,7 +2243,7 @@ int hnswgpu_destroy(hnswgpu_index *idx) {
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     DevBuf *bufs[] = {&idx->s_q,   &idx->s_partial, &idx->s_ord,   &idx->s_dist, &idx->s_pairs, &idx->s_ids,
-                      &idx->s_outd, &idx->s_probes,  &idx->s_stats, &idx->s_misc, &idx->s_misc2, &idx->s_vis, &idx->s_qp, &idx->s_qn, &idx->s_tile, &idx->s_grp, &idx->s_done, &idx->s_pf, &idx->s_solo, &idx->s_bk, &idx->s_heavy, &idx->s_home, &idx->s_dh,
+                      &idx->s_outd, &idx->s_probes,  &idx->s_stats, &idx->s_misc, &idx->s_misc2, &idx->s_vis, &idx->s_qp, &idx->s_qn, &idx->s_tile, &idx->s_grp, &idx->s_done, &idx->s_pf, &idx->s_solo, &idx->s_bk, &idx->s_heavy, &idx->s_home, &idx->s_dh, &idx->s_hord,
                       &idx->s_fmask, &idx->s_fpass, &idx->s_fblk, &idx->s_fids, &idx->s_fdist, &idx->s_flmask, &idx->s_ffoff};
     for (DevBuf *b : bufs) b->release();
     for (int s = 0; s < PROF_N; s++)
@@ -2261,6 +2262,7 @@ int hnswgpu_destroy(hnswgpu_index *idx) {
         if (sl.h) (void)hipHostFree(sl.h);
         if (sl.d_again) (void)hipFree(sl.d_again);
         if (sl.d_done) (void)hipFree(sl.d_done);
+        if (sl.d_order) (void)hipFree(sl.d_order);
         if (sl.st) (void)hipStreamDestroy(sl.st);
     }
     delete idx;

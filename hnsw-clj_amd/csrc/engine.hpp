@@ -155,6 +155,7 @@ struct hnswgpu_index {
         size_t cap = 0;
         int32_t *d_again = nullptr;    // [1 + kZcMaxQueries]: queries that ran out of ghost slots (see hnsw.hip)
         uint32_t *d_done = nullptr;    // workgroups that have finished the current launch
+        int32_t *d_order = nullptr;    // [2 x kZcMaxQueries]: order and keys of an ordered launch (order_kernels.hpp)
         uint32_t seq = 0;              // value the flag takes when the current launch has finished
     };
     Slot slots[2];
@@ -197,7 +198,10 @@ struct hnswgpu_index {
     std::vector<int32_t> h_listids;
 
     // scratch (grown on demand, reused across calls; calls are serialised by `mu`)
-    hg::DevBuf s_q, s_partial, s_ord, s_dist, s_pairs, s_ids, s_outd, s_probes, s_stats, s_misc, s_misc2, s_vis, s_qp, s_qn, s_tile, s_grp, s_done, s_pf, s_solo, s_bk, s_heavy, s_home, s_dh;
+    hg::DevBuf s_q, s_partial, s_ord, s_dist, s_pairs, s_ids, s_outd, s_probes, s_stats, s_misc, s_misc2, s_vis, s_qp, s_qn, s_tile, s_grp, s_done, s_pf, s_solo, s_bk, s_heavy, s_home, s_dh, s_hord;
+    // s_hord: order[nq] | keys[nq] of an ordered HNSW launch (order_kernels.hpp); the last such launch's, for hnswgpu_hnsw_last_order
+    const int32_t *hnsw_order_last = nullptr;
+    int32_t hnsw_order_nq = 0;
     // s_bk: the per-list pair counters of the IVF survivor stream -- zero between searches (the work-list kernel clears
     // them behind its last read); bk_dirty = a search was enqueued past the point that fills them but not past the
     // work-list kernel (an error in between): the next search clears them itself
@@ -286,6 +290,7 @@ struct HnswLaunchPlan {
     int32_t solo_chase, solo_log2s;
     size_t mail_bytes, table_bytes, rec_bytes, region;
     int32_t repeat_cap;   // list capacity of the repeat pass behind this launch, beside the SAME visited set (0: no repeat pass)
+    bool ordered;         // Wave: the queries dealt to the XCDs in the order of their nearest pivot row (order_kernels.hpp)
 };
 // Row width -> CALL(NCH, R, RF): f32 rows in flight per wave without / with the int8 rejection test -- the one table of the three
 // traversal kernels.  With the test a hop fetches f32 rows for a handful of neighbours only, half or a quarter of them in flight
@@ -313,6 +318,8 @@ struct HnswLaunchPlan {
 // translation units of their own so that they compile side by side)
 HnswKernelFn hnsw_solo_kernel_for(const HnswLaunchPlan &p, const HnswArgs &a);
 HnswKernelFn hnsw_wave_kernel_for(const HnswLaunchPlan &p, const HnswArgs &a);
+struct OrderArgs;
+int launch_hnsw_order(int nch, const OrderArgs &a, hipStream_t st);  // wave.hip: key pass + counting sort
 int launch_norms(int nch, const float *rows, int64_t ld, int64_t n, float *out, hipStream_t st);
 int ensure_qrows(hnswgpu_index *idx, hipStream_t st);
 // int8 codes + per-row bound terms of `n` rows into freshly allocated *crows / *cmeta (the caller owns them)

@@ -15,6 +15,7 @@
 #include "build_kernels.hpp"
 #include "engine.hpp"
 #include "javarandom.hpp"
+#include "order_kernels.hpp"  // OrderArgs, for hnsw_launch_resources
 #include "solo_kernels.hpp"  // solo_lds_bytes and the sizes of the several-CU kernel's mailboxes, for hnsw_launch_plan
 
 namespace hg {
@@ -45,6 +46,7 @@ static bool hnsw_vis_global(int64_t n, int64_t vis_global_env) { return vis_glob
 constexpr int kPfMaxQueries = 128;  // up to half a CU count of queries: every traversal and at least one helper per query get a CU
 static_assert(kPfMaxQueries == kSoloMaxQueries, "one bound for both kinds of small launch");
 constexpr int kSoloMinEf = 96;      // (hnsw_launch_plan: the several-CU kernel by default from this ef -- 96, not 200)
+constexpr int kOrderMinQueries = 10000;  // (hnsw_launch_plan: the wave kernel's queries in the order of their nearest pivot from this batch size)
 
 // Stage 1 of a launch.  Rejection mode 1 MEASURES (once per graph, on its first large launch: HnswLaunchPlan::calibrate): the
 // counters travel to pinned host memory behind an event, and the first launch that finds the event complete turns them into the
@@ -193,6 +195,22 @@ static int hnsw_launch_plan(const hnswgpu_index *idx, const HnswArgs &a, const H
         }
         p.region = p.mail_bytes + p.table_bytes + p.rec_bytes;
         p.nw = nw;
+        // The wave kernel's time follows the bytes that leave the XCD L2s, and queries near each other read largely the same
+        // rows: its search launches deal their queries to the XCDs in the order of their nearest pivot row (order_kernels.hpp:
+        // a key pass over the int8 rows + a counting sort in front of the traversal; results never depend on it).
+        // 31k x 768 clustered (the bench's index), ms per launch plain / ordered, medians of three rounds of ten launches, the
+        // two alternating (tools/hnsw_batch_sweep.py --order): ef 640: 2,048 queries 3.503 / 3.588, 4,096: 6.903 / 6.918, 10,000:
+        // 12.180 / 11.984; ef 100: 2,048: 1.193 / 1.194, 4,096: 1.486 / 1.628, 10,000: 3.060 / 3.066 (the rounds overlap).  Up to
+        // 4,096 queries the chip holds the whole batch at once (16 waves x 256 CUs): no query waits for a slot, so there is no
+        // "one XCD at one time" to arrange, and the order costs instead (why 4,096 at ef 100 loses 9.6 % was not looked into).
+        // On from 10,000 queries: the smallest measured batch at which ordered is faster at ef 640 and not apart from plain at
+        // ef 100.
+        // HNSWGPU_TUNE_HNSW_ORDER: 1 (default) = from kOrderMinQueries queries, 0 = never (A/B), 2 = every such launch (tests).
+        // (The int8 ROWS decide, not the rejection test: a handle whose test is calibrated off still has them.)
+        const int64_t order_mode = tune(HNSWGPU_TUNE_HNSW_ORDER, 1);
+        p.ordered = p.kernel == HnswKernel::Wave && !build && idx->d_qrows && idx->d_qmeta &&
+                    (order_mode >= 2 || (order_mode == 1 && a.nq >= kOrderMinQueries));
+        if (p.ordered) p.grid = 8 * ((a.nq + 7) / 8);  // slots: eight eighths of order[], the ragged end's surplus slots serve nobody
     }
     p.nwords = p.vis_global ? 0 : a.nwords;
     if (p.vis_global) {
@@ -200,8 +218,10 @@ static int hnsw_launch_plan(const hnswgpu_index *idx, const HnswArgs &a, const H
         const int64_t budget = 16LL << 30;
         int64_t max_wg = budget / (4 * std::max<int64_t>(a.n, 1));
         max_wg = std::min<int64_t>(std::max<int64_t>(max_wg, 256), 256 * 12);
-        p.grid = static_cast<int>(std::min<int64_t>(a.nq, max_wg));
-        p.gens = (static_cast<int64_t>(a.nq) + p.grid - 1) / p.grid * (a.max_level + 1);
+        const int64_t slots = p.ordered ? 8 * ((static_cast<int64_t>(a.nq) + 7) / 8) : a.nq;
+        p.grid = static_cast<int>(std::min<int64_t>(slots, max_wg));
+        if (p.ordered) p.grid = std::max(8, p.grid & ~7);  // a multiple of 8: workgroup b's slots b, b + grid, ... stay on its XCD
+        p.gens = (slots + p.grid - 1) / p.grid * (a.max_level + 1);
     }
     p.block = p.kernel == HnswKernel::Solo ? kWG : (p.kernel == HnswKernel::Wave ? kWave : p.nw * kWave);
     p.lds = p.kernel == HnswKernel::Solo   ? solo_lds_bytes(a.cap, p.nwords)
@@ -258,8 +278,29 @@ static int hnsw_number_launch(hnswgpu_index *idx, hipStream_t st) {
 }
 
 // Stage 3: everything that touches the handle or a stream before the kernel, and the plan's part of HnswArgs.  Decides nothing.
-static int hnsw_launch_resources(hnswgpu_index *idx, const HnswLaunchPlan &p, HnswArgs &a, hipStream_t st) {
+static int hnsw_launch_resources(hnswgpu_index *idx, const HnswLaunchPlan &p, HnswArgs &a, hipStream_t st, int32_t *order_mem) {
     a.dbg = g_tile_dbg_buf;  // null outside diagnostic sessions
+    if (p.ordered) {  // order_mem: a slot launch's own [order | keys] (two may be in flight); otherwise the handle's scratch
+        if (!order_mem) {
+            HG_TRY(idx->s_hord.ensure(sizeof(int32_t) * 2 * static_cast<size_t>(a.nq)));
+            order_mem = idx->s_hord.as<int32_t>();
+        }
+        OrderArgs o;
+        o.Q = a.Q;
+        o.qld = a.qld;
+        o.dim = a.dim;
+        o.metric = a.metric;
+        o.nq = a.nq;
+        o.n = a.n;
+        o.qrows = idx->d_qrows;
+        o.qmeta = idx->d_qmeta;
+        o.order = order_mem;
+        o.keys = order_mem + a.nq;
+        HG_TRY(launch_hnsw_order(p.nch, o, st));
+        a.q_order = o.order;
+        idx->hnsw_order_last = o.order;
+        idx->hnsw_order_nq = a.nq;
+    }
     a.rej_stats = idx->prof ? idx->d_rej_stats : nullptr;
     if (!p.rejection) a.qrows = nullptr;
     a.nwords = p.nwords;
@@ -330,13 +371,14 @@ static int hnsw_dispatch(const HnswLaunchPlan &p, const HnswArgs &a, hipStream_t
 }
 
 // Stages 3 to 5 of a planned launch; the tail: the launch counters, and a measuring launch sends its counters on their way
-static int hnsw_launch_planned(hnswgpu_index *idx, const HnswLaunchPlan &p, HnswArgs a, hipStream_t st) {
-    HG_TRY(hnsw_launch_resources(idx, p, a, st));
+static int hnsw_launch_planned(hnswgpu_index *idx, const HnswLaunchPlan &p, HnswArgs a, hipStream_t st, int32_t *order_mem = nullptr) {
+    HG_TRY(hnsw_launch_resources(idx, p, a, st, order_mem));
     HG_TRY(hnsw_dispatch(p, a, st));
     if (p.kernel == HnswKernel::Solo) count_launch(HNSWGPU_COUNT_HNSW_SOLO);
     else if (p.kernel == HnswKernel::SearchHelpers) count_launch(HNSWGPU_COUNT_HNSW_HELPERS);
     else count_launch(p.rejection ? HNSWGPU_COUNT_HNSW_REJECTION : HNSWGPU_COUNT_HNSW_PLAIN);
     if (p.kernel == HnswKernel::Wave) count_launch(HNSWGPU_COUNT_HNSW_WAVE);
+    if (p.ordered) count_launch(HNSWGPU_COUNT_HNSW_ORDERED);
     if (p.calibrate) {
         HG_HIP(hipMemcpyAsync(idx->hnsw_cal_host, idx->d_hnsw_cal, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
         HG_HIP(hipEventRecord(idx->ev_hnsw_cal, st));
@@ -407,6 +449,7 @@ struct SlotSignal {
     uint32_t *host_flag;   // device address of the flag word in the mapped block
     int32_t *host_again;   // device address of the repeat count in the mapped block
     uint32_t flag_val;
+    int32_t *order;        // device: [2 x kZcMaxQueries], order and keys of an ordered launch
 };
 
 static int search_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t ef,
@@ -451,7 +494,7 @@ static int search_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, int3
         }
         hipEvent_t e0;
         prof_begin(idx, PROF_HNSW, st, &e0);
-        rc = hnsw_launch_planned(idx, p, a, st);
+        rc = hnsw_launch_planned(idx, p, a, st, sig ? sig->order : nullptr);
         prof_end(idx, PROF_HNSW, st, e0);
         if (rc || sig) return rc;
         a.done_cnt = nullptr;
@@ -894,6 +937,7 @@ static int hnsw_search_batch_slot(hnswgpu_index *idx, const std::vector<hnswgpu_
     sig.host_flag = b.flag(dp);
     sig.host_again = b.again(dp);
     sig.flag_val = ++slot->seq;
+    sig.order = slot->d_order;
     uint64_t gen;
     HG_HIP(hipSetDevice(idx->device));
     {
@@ -987,6 +1031,19 @@ int hnswgpu_hnsw_search(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t 
         [idx](const std::vector<hnswgpu_index::SearchReq *> &batch, int32_t total) {
             return hnsw_search_batch(idx, batch, total);
         });
+}
+
+int hnswgpu_hnsw_last_order(hnswgpu_index *idx, int32_t *order, int32_t *keys, int32_t cap, int32_t *nq) {
+    HG_REQUIRE(idx && nq && cap >= 0, HNSWGPU_EINVAL, "need idx, nq and cap >= 0");
+    std::lock_guard<std::mutex> lk(idx->mu);
+    *nq = idx->hnsw_order_last ? idx->hnsw_order_nq : 0;
+    const size_t m = static_cast<size_t>(std::min(cap, *nq));
+    if (m == 0 || (!order && !keys)) return 0;
+    HG_HIP(hipSetDevice(idx->device));
+    HG_HIP(hipDeviceSynchronize());  // whichever stream the launch ran on
+    if (order) HG_HIP(hipMemcpy(order, idx->hnsw_order_last, sizeof(int32_t) * m, hipMemcpyDeviceToHost));
+    if (keys) HG_HIP(hipMemcpy(keys, idx->hnsw_order_last + *nq, sizeof(int32_t) * m, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 // Filtered search (api/protocol.clj:34-41,97-102): the unfiltered traversal at ef for kk = min(ef, 1024) results per query

@@ -1509,6 +1509,9 @@ struct HnswArgs {
     const uint32_t *qrows;
     const float4 *qmeta;
     unsigned long long *rej_stats;  // profiling: [0] += f32 rows fetched, [1] += neighbours evaluated (null otherwise)
+    // hnsw_wave_kernel, ordered launches (order_kernels.hpp): slot s serves query q_order[(s % 8) * ceil(nq / 8) + s / 8]; null =
+    // slot s serves query s.  Everything that is indexed by the query stays indexed by the query.
+    const int32_t *q_order;
     unsigned long long *dbg;  // -DHG_HNSW_STAMPS diagnostic builds only: per-phase s_memrealtime totals
 };
 

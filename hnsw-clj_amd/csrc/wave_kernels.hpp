@@ -17,7 +17,7 @@
 
 namespace hg {
 
-// One wave per query (workgroups of one wave; persistent: workgroup b serves queries b, b + gridDim.x, ...).  VG = visited set in
+// One wave per query (workgroups of one wave; persistent: workgroup b serves slots b, b + gridDim.x, ...; a slot is a query).  VG = visited set in
 // HBM stamps.  Build launches too (q_rows: the query is a base row, the best entry of every upper level <= the node's level is
 // emitted for the linker, all ef candidates of layer 0 are the result); the repeat pass stays with hnsw_search_kernel.
 template <int NCH, int RB, bool L2, bool VG>
@@ -33,7 +33,18 @@ __global__ __launch_bounds__(kWave) void hnsw_wave_kernel(HnswArgs a) {
     const int lane = threadIdx.x;
     const int nvec = static_cast<int>(a.ld / 4);
     uint32_t gen = a.gen_base;
-    for (int qi = blockIdx.x; qi < a.nq; qi += gridDim.x) {
+    // Ordered launches (order_kernels.hpp): the loop runs over SLOTS.  Workgroups b and b + 8 share an XCD (observed, and used for
+    // speed only), so the slots of one XCD, s % 8 = x, take the x-th eighth of q_order[] front to back: queries with neighbouring
+    // keys run on one XCD at one time.  The ragged end: the last eighths hold fewer than per8 queries, their surplus slots none.
+    const int per8 = (a.nq + 7) >> 3;
+    const int nslot = a.q_order ? 8 * per8 : a.nq;
+    for (int slot = blockIdx.x; slot < nslot; slot += gridDim.x) {
+        int qi = slot;
+        if (a.q_order) {
+            const int pos = (slot & 7) * per8 + (slot >> 3);
+            if (pos >= a.nq) continue;
+            qi = a.q_order[pos];
+        }
         const float *qptr = a.q_rows ? a.rows + static_cast<int64_t>(a.q_rows[qi]) * a.ld : a.Q + static_cast<int64_t>(qi) * a.qld;
         float4 q[NCH];
         load_query<NCH>(q, qptr, a.dim, lane);

@@ -162,6 +162,17 @@ class Index:
         """0 = off, 1 = large batches (default), 2 = every launch: int8 rejection test of the HNSW traversal."""
         check(lib().hnswgpu_set_rejection_test(self._h, int(mode)))
 
+    def hnsw_last_order(self):
+        """hnswgpu_hnsw_last_order: (order, keys) of the last ordered traversal launch on this handle -- the query indices sorted
+        by (key, index) and every query's key, the index of its nearest pivot row -- or None before the first such launch."""
+        nq = C.c_int32(0)
+        check(lib().hnswgpu_hnsw_last_order(self._h, None, None, 0, C.byref(nq)))
+        if nq.value == 0:
+            return None
+        order, keys = np.empty(nq.value, np.int32), np.empty(nq.value, np.int32)
+        check(lib().hnswgpu_hnsw_last_order(self._h, order.ctypes.data, keys.ctypes.data, nq.value, C.byref(nq)))
+        return order, keys
+
     def hnsw_rejection_state(self):
         """hnswgpu_hnsw_rejection_state: (state, off, frac) -- what rejection mode 1 has measured on this graph."""
         st, off, fr = C.c_int32(0), C.c_int32(0), C.c_double(0.0)

@@ -371,6 +371,7 @@ int hnswgpu_set_profiling(hnswgpu_index *idx, int32_t on);
 #define HNSWGPU_COUNT_HNSW_PLAIN 4        /* ... and with every neighbour evaluated in f32 */
 #define HNSWGPU_COUNT_HNSW_WAVE 5         /* large HNSW launches on the one-wave-per-query kernel with the admission buffer (wave_kernels.hpp) */
 #define HNSWGPU_COUNT_ROUTE_TAIL_WAVES 6   /* IVF routing tails launched with one wave per query (ivf_route_tail_wave_kernel) */
+#define HNSWGPU_COUNT_HNSW_ORDERED 7       /* ... of those, launches that dealt their queries in the order of their nearest pivot row (HNSWGPU_TUNE_HNSW_ORDER) */
 #define HNSWGPU_COUNT_N 8
 int hnswgpu_launch_count(int32_t which, int64_t *out);
 /* The HNSW traversal decides most neighbours (those that cannot enter a full result list, ultra_fast.clj:195-198) from
@@ -432,6 +433,10 @@ int hnswgpu_get_rejection_stats(hnswgpu_index *idx, int64_t *f32_rows, int64_t *
  * verdict; frac: f32 rows / neighbours of the measured launch.  Results never depend on it. */
 int hnswgpu_hnsw_rejection_state(hnswgpu_index *idx, int32_t *state, int32_t *off, double *frac);
 int hnswgpu_get_profile(hnswgpu_index *idx, int32_t which, double *total_ms, int64_t *launches, int32_t reset);
+/* Debug read-back of the last ORDERED traversal launch on this handle (HNSWGPU_TUNE_HNSW_ORDER): *nq = its queries (0: none
+ * yet), and the first min(cap, *nq) entries of its order[] (the query indices sorted by (key, index)) and of keys[] (per query:
+ * the index of its nearest pivot row).  Either array may be NULL.  Waits for the device. */
+int hnswgpu_hnsw_last_order(hnswgpu_index *idx, int32_t *order, int32_t *keys, int32_t cap, int32_t *nq);
 
 /* ---- tuning and test switches --------------------------------------------------------------------------------------
  * One process-wide table of 64-bit values.  NONE of them changes what a search returns within the contract of the path
@@ -504,7 +509,8 @@ int hnswgpu_get_profile(hnswgpu_index *idx, int32_t which, double *total_ms, int
 #define HNSWGPU_TUNE_SEED_HALF 58 /* 0 = a query's first threshold from f32 rows of its nearest list even where the half-precision copy exists (A/B; default 1: the k-th smallest upper bound of the sampled rows' half-precision copies, half the bytes) */
 #define HNSWGPU_TUNE_BUILD_KEEP_ROWS 59 /* 0 = the builder's heuristic selection fetches the already selected rows again for every candidate instead of keeping them in registers (A/B; the graph does not depend on it) */
 #define HNSWGPU_TUNE_QUERY_WAVES 60 /* the per-query kernels of large IVF batches (home-list selection) with one WAVE per query, four queries per workgroup, instead of a workgroup per query: -1 from 2048 queries, 0 never, 1 wherever a wave can serve a query (k <= 64) */
-#define HNSWGPU_TUNE_COUNT 61
+#define HNSWGPU_TUNE_HNSW_ORDER 61 /* launches of the one-wave-per-query kernel serve their queries in the order of their nearest pivot row (min(256, n) base rows at a fixed stride, judged on the int8 rows), dealt so that neighbouring queries run on one XCD at one time -- a hint for the L2s, results never depend on it: 1 = search launches on handles with int8 rows from a batch size (default), 0 = never (A/B), 2 = every such launch (tests) */
+#define HNSWGPU_TUNE_COUNT 62
 int hnswgpu_set_tuning(int32_t key, int64_t value);
 int hnswgpu_get_tuning(int32_t key, int64_t *value, int32_t *is_set);
 

@@ -1,5 +1,9 @@
 """Developer tool: HNSW batch-size sweep on the bench workload (31,173 x 768 manifold data, ef 100), for every
-waves-per-query setting the launcher can pick.  usage: python tools/hnsw_batch_sweep.py [ef]"""
+waves-per-query setting the launcher can pick.  usage: python tools/hnsw_batch_sweep.py [ef]
+
+python tools/hnsw_batch_sweep.py --order: the wave kernel's ordered launches (HNSW_ORDER 2) against plain ones (0) in ONE process
+on bench.py's own index (31,173 x 768 clustered, heuristic builder): 2,048 / 4,096 / 10,000 queries at ef 640 and ef 100, the two
+settings alternating, three rounds of 10 launches each; the table hnsw_launch_plan's threshold (kOrderMinQueries) is read from."""
 import os
 import subprocess
 import sys
@@ -7,7 +11,41 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-if len(sys.argv) > 1 and sys.argv[1] == "--child":
+if len(sys.argv) > 1 and sys.argv[1] == "--order":
+    import numpy as np
+    import torch
+
+    import bench
+    from hnsw_clj_amd import engine
+
+    base = bench.make_31k("clustered", 42, 31173)
+    queries = bench.make_31k("clustered", 43, 10000)
+    dev = torch.device("cuda", 0)
+    idx = engine.Index(base, "cosine", 0)
+    idx.hnsw_build(16, 200, 42, **bench.BUILDERS["heuristic"])
+    print("ef    nq      plain ms (3 rounds)        ordered ms (3 rounds)      ordered / plain (medians)", flush=True)
+    for ef in (640, 100):
+        for nq in (2048, 4096, 10000):
+            Q = torch.from_numpy(queries[:nq]).to(dev)
+            out = (torch.empty((nq, 10), dtype=torch.int32, device=dev), torch.empty((nq, 10), dtype=torch.float32, device=dev))
+            ms = {0: [], 2: []}
+            for rnd in range(4):                      # round 0 warms up
+                for mode in (0, 2):
+                    engine.set_tuning("HNSW_ORDER", mode)
+                    idx.hnsw_search_dev(Q, 10, ef, out=out)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for _ in range(10):
+                        idx.hnsw_search_dev(Q, 10, ef, out=out)
+                    torch.cuda.synchronize()
+                    if rnd:
+                        ms[mode].append((time.perf_counter() - t0) / 10 * 1e3)
+            med = {m: sorted(v)[1] for m, v in ms.items()}
+            print("%-5d %-7d %-26s %-26s %.4f" % (ef, nq, " ".join("%.4f" % v for v in ms[0]), " ".join("%.4f" % v for v in ms[2]),
+                                               med[2] / med[0]), flush=True)
+    engine.set_tuning("HNSW_ORDER", None)
+    print("launch counters: hnsw_wave %d, hnsw_ordered %d" % (engine.debug_counter("hnsw_wave"), engine.debug_counter("hnsw_ordered")))
+elif len(sys.argv) > 1 and sys.argv[1] == "--child":
     import numpy as np
     import torch
 
