@@ -79,6 +79,41 @@ JNIEXPORT jint JNICALL Java_hnsw_gpu_Native_ivfSearch(JNIEnv *env, jclass c, jlo
     return rc;
 }
 
+/* ---- a forest: several HNSW sub-graphs on one handle (include/hnswgpu.h: hnswgpu_hnsw_build_parts / hnswgpu_hnsw_search_parts) ---- */
+JNIEXPORT jint JNICALL Java_hnsw_gpu_Native_hnswBuildParts(JNIEnv *env, jclass c, jlong h, jlongArray partOff, jint M, jint efc,
+                                                           jlong seed, jint flags) {
+    if (!partOff) return throw_iae(env, "hnswBuildParts: null array");
+    jsize len = (*env)->GetArrayLength(env, partOff);
+    if (len < 2) return throw_iae(env, "hnswBuildParts: partOff holds nparts + 1 offsets");
+    jlong *po = (*env)->GetLongArrayElements(env, partOff, NULL);
+    if (!po) return HNSWGPU_ENOMEM; /* OutOfMemoryError is pending */
+    int rc = hnswgpu_hnsw_build_parts((hnswgpu_index *)(intptr_t)h, (int32_t)(len - 1), (const int64_t *)po, M, efc, seed, flags);
+    (*env)->ReleaseLongArrayElements(env, partOff, po, JNI_ABORT);
+    if (rc != 0) throw_last(env);
+    return rc;
+}
+
+/* probes: nq x nprobe part ids (-1 = skip), or null = every part in order (nprobe is then ignored) */
+JNIEXPORT jint JNICALL Java_hnsw_gpu_Native_hnswSearchParts(JNIEnv *env, jclass c, jlong h, jfloatArray q, jint nq, jint kPart,
+                                                            jint ef, jintArray probes, jint nprobe, jint k, jintArray ids,
+                                                            jfloatArray dist) {
+    if (!q || !ids || !dist) return throw_iae(env, "hnswSearchParts: null array");
+    if (probes && (jlong)(*env)->GetArrayLength(env, probes) < (jlong)nq * nprobe) return throw_iae(env, "hnswSearchParts: probes is shorter than nq x nprobe");
+    jfloat *pq = (*env)->GetFloatArrayElements(env, q, NULL);
+    jint *pp = probes ? (*env)->GetIntArrayElements(env, probes, NULL) : NULL;
+    jint *pi = (*env)->GetIntArrayElements(env, ids, NULL);
+    jfloat *pd = (*env)->GetFloatArrayElements(env, dist, NULL);
+    int rc = (pq && pi && pd && (pp || !probes))
+                 ? hnswgpu_hnsw_search_parts((hnswgpu_index *)(intptr_t)h, pq, nq, kPart, ef, (const int32_t *)pp, nprobe, k, (int32_t *)pi, pd, NULL)
+                 : HNSWGPU_ENOMEM;
+    if (pq) (*env)->ReleaseFloatArrayElements(env, q, pq, JNI_ABORT);
+    if (pp) (*env)->ReleaseIntArrayElements(env, probes, pp, JNI_ABORT);
+    if (pi) (*env)->ReleaseIntArrayElements(env, ids, pi, 0);
+    if (pd) (*env)->ReleaseFloatArrayElements(env, dist, pd, 0);
+    if (rc != 0 && rc != HNSWGPU_ENOMEM) throw_last(env);
+    return rc;
+}
+
 /* ---- INTEGRATION.md section 5 / the simd-optimized seams / persistence: the same mechanical shape ---- */
 
 JNIEXPORT jint JNICALL Java_hnsw_gpu_Native_setGraph(JNIEnv *env, jclass c, jlong h, jintArray levels, jintArray l0, jint M0,

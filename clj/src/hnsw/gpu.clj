@@ -153,6 +153,50 @@
   [idx ^doubles query-vec k]
   (first (search-batch idx [query-vec] k)))
 
+;; ---- a forest: several HNSW sub-graphs on one handle, searched in one launch (include/hnswgpu.h: hnswgpu_hnsw_build_parts) ----
+(def ^:private h-buildparts
+  (delay (fn-handle "hnswgpu_hnsw_build_parts" (FunctionDescriptor/of I (into-array [P I P I I L I])))))
+(def ^:private h-searchparts
+  (delay (fn-handle "hnswgpu_hnsw_search_parts" (FunctionDescriptor/of I (into-array [P P I I I P I I P P P])))))
+
+(defn build-forest
+  "hnsw.ann.partition.partitioned-hnsw/build-index (src/hnsw/ann/partition/partitioned_hnsw.clj:46-143) and the graphs of
+   hnsw.ann.hybrid.ivf-hnsw (src/hnsw/ann/hybrid/ivf_hnsw.clj:172-280) on ONE handle: `partitions` is a seq of partitions, each a
+   seq of [id ^doubles vector]; their rows are laid out one partition behind the other (the id table follows that order) and every
+   partition gets the graph build-index would give it alone.  An empty partition is allowed.  :select as in build-index."
+  [partitions & {:keys [M ef-construction metric seed select] :or {M 16 ef-construction 200 metric :cosine seed 42 select :closest}}]
+  (let [idx (create (vec (apply concat partitions)) metric :hnsw-forest)
+        offs (long-array (reductions + 0 (map count partitions)))]
+    (with-open [arena (Arena/ofConfined)]
+      (let [seg (.allocate arena (* 8 (alength offs)) 8)]
+        (dotimes [i (alength offs)] (.setAtIndex seg L (long i) (aget offs i)))
+        (check (.invokeWithArguments ^MethodHandle @h-buildparts
+                                     [(:handle idx) (int (count partitions)) seg (int M) (int ef-construction) (long seed)
+                                      (int (case select :closest 0 :heuristic 2 :graph-clj 6))]))))
+    (assoc idx :nparts (count partitions))))
+
+(defn search-forest-batch
+  "search-partitioned (partitioned_hnsw.clj:149-196) / search-ivf-hnsw (ivf_hnsw.clj:286-325) for a batch, in one traversal launch:
+   every probed partition's graph is searched for k-part results per query, the lists are merged in probe order (a stable sort of
+   the concatenation), take k.  :probes = per query a seq of partition numbers (-1 = none; all the same length), nil = every
+   partition in order."
+  [idx queries k-part k & {:keys [ef probes] :or {ef 0}}]
+  (with-open [arena (Arena/ofConfined)]
+    (let [nq (count queries)
+          q (floats-of arena (vec queries) (:dim idx))
+          nprobe (if probes (count (first probes)) (:nparts idx))
+          pr (if probes
+               (let [seg (.allocate arena (* 4 (long nq) (long nprobe)) 4)]
+                 (doseq [[i row] (map-indexed vector probes) [j p] (map-indexed vector row)]
+                   (.setAtIndex seg I (+ (* (long i) nprobe) (long j)) (int p)))
+                 seg)
+               MemorySegment/NULL)
+          ids (.allocate arena (* 4 nq k) 4)
+          ds (.allocate arena (* 4 nq k) 4)]
+      (check (.invokeWithArguments ^MethodHandle @h-searchparts
+                                   [(:handle idx) q (int nq) (int k-part) (int ef) pr (int nprobe) (int k) ids ds MemorySegment/NULL]))
+      (mapv #(results idx ids ds % k) (range nq)))))
+
 (defn search-batch-routed
   "search-batch with the crossover the device offers and the reference has no word for: the traversal evaluates E(ef) rows per
    query, gathered at random; the exact scan (hnswgpu_exact_knn: every row once per batch through the matrix cores) answers at

@@ -56,6 +56,11 @@ _SIGS = {
     "hnswgpu_get_graph": ["p", "p", "p", "p", "p"],
     "hnswgpu_hnsw_search": ["p", "p", "i32", "i32", "i32", "p", "p", "p"],
     "hnswgpu_hnsw_search_dev": ["p", "p", "i32", "i32", "i32", "p", "p", "p", "p"],
+    "hnswgpu_set_graph_parts": ["p", "p", "p", "i32", "p", "p", "i32", "i32", "p", "p", "p"],
+    "hnswgpu_hnsw_build_parts": ["p", "i32", "p", "i32", "i32", "i64", "i32"],
+    "hnswgpu_graph_parts": ["p", "p", "p", "p", "p"],
+    "hnswgpu_hnsw_search_parts": ["p", "p", "i32", "i32", "i32", "p", "i32", "i32", "p", "p", "p"],
+    "hnswgpu_hnsw_search_parts_dev": ["p", "p", "i32", "i32", "i32", "p", "i32", "i32", "p", "p", "p", "p"],
     "hnswgpu_ivf_build": ["p", "i32", "i32", "i64"],
     "hnswgpu_ivf_add": ["p", "p", "i64"],
     "hnswgpu_set_ivf": ["p", "p", "i32", "p", "p"],

@@ -177,6 +177,16 @@ struct hnswgpu_index {
     int64_t *d_upoff = nullptr;
     std::vector<int32_t> h_levels, h_l0, h_upadj;
     std::vector<int64_t> h_upoff;
+    // A FOREST (hnswgpu_set_graph_parts / hnswgpu_hnsw_build_parts): nparts > 0, the rows grouped by part -- part p is rows
+    // [h_part_off[p], h_part_off[p + 1]) with a sub-graph of its own (entry row or -1 for an empty part, top level); no edge leaves
+    // its part.  entry is -1 then and max_level the largest part's.  Searched by hnswgpu_hnsw_search_parts alone (hnsw.hip).
+    int nparts = 0;
+    int64_t max_part = 0;  // rows of the largest part: what the visited set of a forest launch is sized and placed by
+    std::vector<int64_t> h_part_off;
+    std::vector<int32_t> h_part_entry, h_part_level;
+    int4 *d_parts = nullptr;  // [nparts] (first row, entry, top level, rows): parts_kernels.hpp
+    // scratch of a forest search: the item table, the per-item result lists and counters, the host entry's probe table
+    hg::DevBuf s_pt_items, s_pt_ids, s_pt_dist, s_pt_stats, s_pt_probes;
 
     // IVF-FLAT (device: centroids + rows re-ordered so every list is contiguous)
     int nlist = 0;
@@ -318,6 +328,7 @@ struct HnswLaunchPlan {
 // translation units of their own so that they compile side by side)
 HnswKernelFn hnsw_solo_kernel_for(const HnswLaunchPlan &p, const HnswArgs &a);
 HnswKernelFn hnsw_wave_kernel_for(const HnswLaunchPlan &p, const HnswArgs &a);
+HnswKernelFn hnsw_parts_kernel_for(const HnswLaunchPlan &p, const HnswArgs &a);  // parts.hip: either family with the item table
 struct OrderArgs;
 int launch_hnsw_order(int nch, const OrderArgs &a, hipStream_t st);  // wave.hip: key pass + counting sort
 int launch_norms(int nch, const float *rows, int64_t ld, int64_t n, float *out, hipStream_t st);

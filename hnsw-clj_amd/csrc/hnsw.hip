@@ -16,6 +16,7 @@
 #include "engine.hpp"
 #include "javarandom.hpp"
 #include "order_kernels.hpp"  // OrderArgs, for hnsw_launch_resources
+#include "parts_kernels.hpp"  // the item table and the counters of a forest launch (hnsw_parts_enqueue)
 #include "solo_kernels.hpp"  // solo_lds_bytes and the sizes of the several-CU kernel's mailboxes, for hnsw_launch_plan
 
 namespace hg {
@@ -85,6 +86,12 @@ static HnswKernelFn hnsw_search_kernel_for(const HnswLaunchPlan &p, const HnswAr
 static int hnsw_launch_plan(const hnswgpu_index *idx, const HnswArgs &a, const HnswLaunchPlan *first, HnswLaunchPlan &p) {
     memset(&p, 0, sizeof(p));
     const bool build = a.q_rows != nullptr, repeat = a.q_index != nullptr;
+    // A forest launch (HnswArgs::items: a.nq counts items, a.nwords covers the largest part): a traversal never leaves its part,
+    // so the visited set is placed and sized by the LARGEST PART -- a 1M-row index of 24 parts keeps the LDS bitset its 24 handles
+    // had.  Such launches stay on hnsw_search_kernel and hnsw_wave_kernel, the two that read the item table: no helpers, no
+    // several-CU kernel, no ordered dealing (the pivot keys are per query, the slots per item).
+    const bool parts = a.items != nullptr;
+    const int64_t vis_rows = parts ? idx->max_part : a.n;
     p.nch = idx->nch;
     // The rejection test on int8 rows (kernels.hpp: quantize_rows_kernel) turns one memory round trip per hop into two
     // shorter ones: 2.2x the throughput once the chip is bandwidth-bound, ~5 % slower while a launch is latency-bound.
@@ -108,15 +115,15 @@ static int hnsw_launch_plan(const hnswgpu_index *idx, const HnswArgs &a, const H
         // tuning override (HNSWGPU_TUNE_HNSW_NW = 1 | 2 | 4); 0 = choose by batch size
         const int64_t nw_raw = tune(HNSWGPU_TUNE_HNSW_NW, 0);
         const int nw_env = (nw_raw == 1 || nw_raw == 2 || nw_raw == 4) ? static_cast<int>(nw_raw) : 0;
-        p.vis_global = hnsw_vis_global(a.n, tune(HNSWGPU_TUNE_VIS_GLOBAL, 0));
+        p.vis_global = hnsw_vis_global(vis_rows, tune(HNSWGPU_TUNE_VIS_GLOBAL, 0));
         // helper workgroups per query that prefetch neighbour rows into the query's XCD L2 (kernels.hpp, HnswArgs::pf_mail):
         // HNSWGPU_TUNE_PREFETCH = <G> overrides (0 = off, and the several-CU path with it).  ONE key, two intended defaults and
         // clamps: 4 (at most 16) helpers for the round-2 helper kernel, 8 (at most 31) for the several-CU kernel.
         const int64_t pf_env = tune(HNSWGPU_TUNE_PREFETCH, kTuneUnset);
         const int helper_groups = pf_env == kTuneUnset ? 4 : static_cast<int>(std::max<int64_t>(0, std::min<int64_t>(16, pf_env)));
         const int solo_groups = pf_env == kTuneUnset ? 8 : static_cast<int>(std::max<int64_t>(0, std::min<int64_t>(31, pf_env)));
-        const bool small = helper_groups > 0 && !p.vis_global && !build && a.nq <= kPfMaxQueries && nw_env == 0 && a.n < (1LL << 31) &&
-                           a.M0 <= kMaxDeg;
+        const bool small = helper_groups > 0 && !p.vis_global && !build && !parts && a.nq <= kPfMaxQueries && nw_env == 0 &&
+                           a.n < (1LL << 31) && a.M0 <= kMaxDeg;
         // HNSWGPU_TUNE_SOLO: 1 (default) = launches whose list is long enough for the split to pay (ef >= kSoloMinEf = 96: a search of
         // a few dozen expansions is a descent whose every step waits for the step before it, and the round-2 helpers serve it as well --
         // 31k x 768 clustered, one query, round-2 helpers / this kernel: ef 50 249 / 255 us, ef 100 378 / 350, ef 200 612 / 524, ef 640
@@ -208,7 +215,7 @@ static int hnsw_launch_plan(const hnswgpu_index *idx, const HnswArgs &a, const H
         // HNSWGPU_TUNE_HNSW_ORDER: 1 (default) = from kOrderMinQueries queries, 0 = never (A/B), 2 = every such launch (tests).
         // (The int8 ROWS decide, not the rejection test: a handle whose test is calibrated off still has them.)
         const int64_t order_mode = tune(HNSWGPU_TUNE_HNSW_ORDER, 1);
-        p.ordered = p.kernel == HnswKernel::Wave && !build && idx->d_qrows && idx->d_qmeta &&
+        p.ordered = p.kernel == HnswKernel::Wave && !build && !parts && idx->d_qrows && idx->d_qmeta &&
                     (order_mode >= 2 || (order_mode == 1 && a.nq >= kOrderMinQueries));
         if (p.ordered) p.grid = 8 * ((a.nq + 7) / 8);  // slots: eight eighths of order[], the ragged end's surplus slots serve nobody
     }
@@ -239,10 +246,11 @@ static int hnsw_launch_plan(const hnswgpu_index *idx, const HnswArgs &a, const H
         // the visited set THIS plan chose
         const size_t fixed = hnsw_lds_bytes(0, p.nwords, 4);
         const int64_t cap_max = std::min<int64_t>(65000, static_cast<int64_t>((kMaxLds - fixed) / (sizeof(uint2) + sizeof(uint16_t))));
-        const int64_t big = std::min<int64_t>(cap_max - a.ef, a.n);
+        const int64_t big = std::min<int64_t>(cap_max - a.ef, vis_rows);
         p.repeat_cap = big > kGhost ? static_cast<int32_t>(a.ef + big) : 0;
     }
-    p.fn = p.kernel == HnswKernel::Solo   ? hnsw_solo_kernel_for(p, a)
+    p.fn = parts                          ? hnsw_parts_kernel_for(p, a)
+           : p.kernel == HnswKernel::Solo ? hnsw_solo_kernel_for(p, a)
            : p.kernel == HnswKernel::Wave ? hnsw_wave_kernel_for(p, a)
                                           : hnsw_search_kernel_for(p, a);
     HG_REQUIRE(p.fn, HNSWGPU_ELIMIT, "unsupported row length");
@@ -407,6 +415,13 @@ static void free_graph(hnswgpu_index *idx) {
     idx->d_levels = idx->d_l0 = idx->d_upadj = nullptr;
     idx->d_upoff = nullptr;
     idx->has_graph = false;
+    if (idx->d_parts) (void)hipFree(idx->d_parts);  // a forest's part tables go with its graph
+    idx->d_parts = nullptr;
+    idx->nparts = 0;
+    idx->max_part = 0;
+    idx->h_part_off.clear();
+    idx->h_part_entry.clear();
+    idx->h_part_level.clear();
 }
 
 static int alloc_graph(hnswgpu_index *idx, int M, int M0, int64_t up_blocks) {
@@ -455,6 +470,9 @@ struct SlotSignal {
 static int search_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t ef,
                           int32_t *d_ids, float *d_dist, int64_t *d_stats, hipStream_t st,
                           const SlotSignal *sig = nullptr, bool repeat_only = false) {
+    // under the handle's lock: a forest has no entry point of its own (the one check behind every plain and filtered search)
+    HG_REQUIRE(idx->nparts == 0, HNSWGPU_ESTATE,
+               "the index holds a forest (hnswgpu_set_graph_parts / hnswgpu_hnsw_build_parts): search it with hnswgpu_hnsw_search_parts");
     HnswArgs a;
     fill_args(idx, a);
     a.Q = d_Q;
@@ -812,6 +830,226 @@ static int upload_graph(hnswgpu_index *idx, const HostGraph &g, hipStream_t st, 
     return 0;
 }
 
+// The part tables of a forest as the caller hands them over (hnswgpu_set_graph_parts); null = a plain graph
+struct PartTables {
+    int32_t nparts;
+    const int64_t *off;     // [nparts + 1]
+    const int32_t *entry;   // [nparts], -1 for an empty part
+    const int32_t *level;   // [nparts], the entry's level
+};
+
+// Everything hnswgpu_set_graph and hnswgpu_set_graph_parts require of their arrays, before anything on the handle changes.  The
+// kernels trust it: every edge points at a node that exists on that layer -- and, in a forest, inside the edge's own part (the
+// LDS visited set of a forest launch covers one part).
+static int check_graph(const hnswgpu_index *idx, const int32_t *levels, const int32_t *l0_adj, int32_t M0, const int64_t *up_off,
+                       const int32_t *up_adj, int32_t M, int32_t entry, int32_t max_level, const PartTables *pt) {
+    HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
+    const int64_t n = idx->n;
+    HG_REQUIRE(n == 0 || (levels && l0_adj && up_off), HNSWGPU_EINVAL, "null argument");
+    HG_REQUIRE(M >= 1 && M0 >= 1 && M0 <= kMaxDeg && M <= kMaxDeg, HNSWGPU_ELIMIT, "need 1 <= M, M0 <= %d", kMaxDeg);
+    if (pt) {
+        HG_REQUIRE(pt->nparts >= 1 && pt->off && pt->entry && pt->level, HNSWGPU_EINVAL, "need nparts >= 1 and the three part tables");
+        HG_REQUIRE(pt->off[0] == 0 && pt->off[pt->nparts] == n, HNSWGPU_EINVAL, "part_off must run from 0 to n");
+        for (int32_t p = 0; p < pt->nparts; p++) {
+            const int64_t lo = pt->off[p], hi = pt->off[p + 1];
+            HG_REQUIRE(lo <= hi && hi <= n, HNSWGPU_EINVAL, "part_off is not monotone at part %d", p);
+            if (lo == hi) {
+                HG_REQUIRE(pt->entry[p] == -1, HNSWGPU_EINVAL, "part %d is empty: its entry must be -1", p);
+                continue;
+            }
+            HG_REQUIRE(pt->entry[p] >= lo && pt->entry[p] < hi, HNSWGPU_EINVAL, "the entry of part %d lies outside the part", p);
+            HG_REQUIRE(pt->level[p] >= 0 && levels[pt->entry[p]] >= pt->level[p], HNSWGPU_EINVAL, "part %d: entry level < max_level", p);
+        }
+    } else if (n > 0) {
+        HG_REQUIRE(entry >= 0 && entry < n, HNSWGPU_EINVAL, "entry out of range");
+        HG_REQUIRE(max_level >= 0 && levels[entry] >= max_level, HNSWGPU_EINVAL, "entry level < max_level");
+    }
+    if (n == 0) return 0;
+    HG_REQUIRE(up_off[0] == 0, HNSWGPU_EINVAL, "up_off[0] != 0");
+    const int64_t whole[2] = {0, n};
+    const int32_t np = pt ? pt->nparts : 1;
+    for (int32_t p = 0; p < np; p++) {
+        const int64_t lo = pt ? pt->off[p] : whole[0], hi = pt ? pt->off[p + 1] : whole[1];
+        const int32_t top = pt ? pt->level[p] : max_level;
+        for (int64_t i = lo; i < hi; i++) {
+            HG_REQUIRE(levels[i] >= 0, HNSWGPU_EINVAL, "node %lld has a negative level", (long long)i);
+            HG_REQUIRE(up_off[i + 1] - up_off[i] == levels[i], HNSWGPU_EINVAL,
+                       "up_off is not the prefix sum of levels at node %lld", (long long)i);
+            HG_REQUIRE(levels[i] <= top, HNSWGPU_EINVAL, "node %lld level > max_level", (long long)i);
+        }
+    }
+    HG_REQUIRE(up_off[n] == 0 || up_adj, HNSWGPU_EINVAL, "up_adj is null");
+    for (int32_t p = 0; p < np; p++) {
+        const int64_t lo = pt ? pt->off[p] : whole[0], hi = pt ? pt->off[p + 1] : whole[1];
+        for (int64_t i = lo * M0; i < hi * M0; i++)
+            HG_REQUIRE(l0_adj[i] == -1 || (l0_adj[i] >= lo && l0_adj[i] < hi), HNSWGPU_EINVAL,
+                       pt ? "l0_adj entry leaves its part" : "l0_adj entry out of range");
+        for (int64_t i = lo; i < hi; i++)
+            for (int lv = 1; lv <= levels[i]; lv++)
+                for (int j = 0; j < M; j++) {
+                    int32_t nb = up_adj[(up_off[i] + lv - 1) * M + j];
+                    HG_REQUIRE(nb == -1 || (nb >= lo && nb < hi), HNSWGPU_EINVAL,
+                               pt ? "up_adj entry leaves its part" : "up_adj entry out of range");
+                    HG_REQUIRE(nb < 0 || levels[nb] >= lv, HNSWGPU_EINVAL,
+                               "edge %lld->%d on layer %d: target has no such layer", (long long)i, nb, lv);
+                }
+    }
+    return 0;
+}
+
+// Checked arrays -> the handle, inside the caller's call scope.  The device copies are made and filled BESIDE what the handle
+// holds; only when they stand is the old graph freed and the handle switched over, so a failing call leaves the handle as it was.
+static int install_graph(hnswgpu_index *idx, Call &call, hipStream_t st, const int32_t *levels, const int32_t *l0_adj, int32_t M0,
+                         const int64_t *up_off, const int32_t *up_adj, int32_t M, int32_t entry, int32_t max_level,
+                         const PartTables *pt) {
+    const int64_t n = idx->n, n1 = std::max<int64_t>(n, 1);
+    const int64_t blocks = n > 0 ? up_off[n] : 0;
+    std::vector<int4> parts;
+    int64_t max_part = 0;
+    int32_t top = n > 0 ? max_level : 0;
+    if (pt) {
+        parts.resize(pt->nparts);
+        top = 0;
+        for (int32_t p = 0; p < pt->nparts; p++) {
+            const int64_t rows = pt->off[p + 1] - pt->off[p];
+            parts[p] = make_int4(static_cast<int32_t>(pt->off[p]), rows > 0 ? pt->entry[p] : -1, rows > 0 ? pt->level[p] : 0,
+                                 static_cast<int32_t>(rows));
+            max_part = std::max(max_part, rows);
+            if (rows > 0) top = std::max(top, pt->level[p]);
+        }
+    }
+    struct Staged {
+        int32_t *levels = nullptr, *l0 = nullptr, *upadj = nullptr;
+        int64_t *upoff = nullptr;
+        int4 *parts = nullptr;
+        ~Staged() {
+            void *ptrs[] = {levels, l0, upadj, upoff, parts};
+            for (void *p : ptrs)
+                if (p) (void)hipFree(p);
+        }
+    } sg;
+    HG_HIP(hipMalloc(reinterpret_cast<void **>(&sg.levels), sizeof(int32_t) * n1));
+    HG_HIP(hipMalloc(reinterpret_cast<void **>(&sg.l0), sizeof(int32_t) * n1 * M0));
+    HG_HIP(hipMalloc(reinterpret_cast<void **>(&sg.upoff), sizeof(int64_t) * (n1 + 1)));
+    HG_HIP(hipMalloc(reinterpret_cast<void **>(&sg.upadj), sizeof(int32_t) * std::max<int64_t>(blocks, 1) * M));
+    if (pt) {
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&sg.parts), sizeof(int4) * parts.size()));
+        HG_HIP(hipMemcpyAsync(sg.parts, parts.data(), sizeof(int4) * parts.size(), hipMemcpyHostToDevice, st));
+    }
+    if (n > 0) {
+        HG_HIP(hipMemcpyAsync(sg.levels, levels, sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
+        HG_HIP(hipMemcpyAsync(sg.l0, l0_adj, sizeof(int32_t) * n * M0, hipMemcpyHostToDevice, st));
+        HG_HIP(hipMemcpyAsync(sg.upoff, up_off, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, st));
+        if (blocks > 0) HG_HIP(hipMemcpyAsync(sg.upadj, up_adj, sizeof(int32_t) * blocks * M, hipMemcpyHostToDevice, st));
+    }
+    HG_TRY(ensure_qrows(idx, st));  // (of the ROWS: nothing of the graph)
+    // host mirrors: built aside as well (an allocation failure throws nothing past here)
+    std::vector<int32_t> h_levels, h_l0, h_upadj;
+    std::vector<int64_t> h_upoff(1, 0), h_part_off;
+    std::vector<int32_t> h_part_entry, h_part_level;
+    if (n > 0) {
+        h_levels.assign(levels, levels + n);
+        h_l0.assign(l0_adj, l0_adj + n * M0);
+        h_upoff.assign(up_off, up_off + n + 1);
+        if (blocks > 0) h_upadj.assign(up_adj, up_adj + blocks * M);
+    }
+    if (pt) {
+        h_part_off.assign(pt->off, pt->off + pt->nparts + 1);
+        for (const int4 &q : parts) {
+            h_part_entry.push_back(q.y);
+            h_part_level.push_back(q.z);
+        }
+    }
+    // every earlier call on this handle is ordered before `st` by the scope, except the small synchronous searches on
+    // the slot streams: once `st` and both slot streams are idle nothing can still be traversing the graph that is about
+    // to be freed (and no other handle on this GPU is stalled) -- and the copies above have arrived
+    HG_TRY(call.quiesce());
+    free_graph(idx);
+    idx->d_levels = sg.levels;
+    idx->d_l0 = sg.l0;
+    idx->d_upoff = sg.upoff;
+    idx->d_upadj = sg.upadj;
+    idx->d_parts = sg.parts;
+    sg = Staged();
+    idx->M = M;
+    idx->M0 = M0;
+    idx->up_blocks = blocks;
+    idx->h_levels.swap(h_levels);
+    idx->h_l0.swap(h_l0);
+    idx->h_upoff.swap(h_upoff);
+    idx->h_upadj.swap(h_upadj);
+    idx->nparts = pt ? pt->nparts : 0;
+    idx->max_part = max_part;
+    idx->h_part_off.swap(h_part_off);
+    idx->h_part_entry.swap(h_part_entry);
+    idx->h_part_level.swap(h_part_level);
+    idx->entry = (n > 0 && !pt) ? entry : -1;
+    idx->max_level = top;
+    idx->has_graph = true;
+    return 0;
+}
+
+// One forest search of at most kPartsMaxItems items, enqueued on `st` inside the caller's call scope: the item table from the
+// probe table, ONE traversal launch over all (query, probe) items + its repeat pass (per item), the counters into the caller's
+// layout, the merge in probe order.
+constexpr int64_t kPartsMaxItems = 1 << 20;
+static int hnsw_parts_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k_part, int32_t ef, const int32_t *d_probes,
+                              int32_t nprobe, int32_t k, int32_t *d_ids, float *d_dist, int64_t *d_stats, hipStream_t st) {
+    const int64_t items = static_cast<int64_t>(nq) * nprobe;
+    if (items <= 0) return 0;
+    HG_REQUIRE(idx->nparts > 0 && idx->d_parts, HNSWGPU_ESTATE, "the index holds no forest (call hnswgpu_hnsw_build_parts / hnswgpu_set_graph_parts)");
+    HnswArgs a;
+    fill_args(idx, a);
+    a.Q = d_Q;
+    a.qld = idx->dim;
+    a.nq = static_cast<int32_t>(items);
+    a.ef = ef;
+    a.k = k_part;
+    a.cap = ef + kGhost;
+    a.nwords = static_cast<int32_t>((idx->max_part + 31) / 32);
+    HG_TRY(idx->s_pt_items.ensure(sizeof(int4) * items));
+    HG_TRY(idx->s_pt_ids.ensure(sizeof(int32_t) * items * k_part));
+    HG_TRY(idx->s_pt_dist.ensure(sizeof(float) * items * k_part));
+    if (d_stats) HG_TRY(idx->s_pt_stats.ensure(sizeof(int64_t) * 2 * items));
+    HG_TRY(idx->s_probes.ensure(sizeof(int32_t) * (static_cast<size_t>(items) + 1)));  // again[]: the items to repeat
+    a.items = idx->s_pt_items.as<int4>();
+    a.out_ids = idx->s_pt_ids.as<int32_t>();
+    a.out_dist = idx->s_pt_dist.as<float>();
+    a.stats = d_stats ? idx->s_pt_stats.as<int64_t>() : nullptr;
+    HnswLaunchPlan p;
+    hnsw_calibration_absorb(idx);
+    HG_TRY(hnsw_launch_plan(idx, a, nullptr, p));
+    const unsigned blocks = static_cast<unsigned>((items + 255) / 256);
+    hipLaunchKernelGGL(parts_items_kernel, dim3(blocks), dim3(256), 0, st, d_probes, nq, nprobe, idx->d_parts, idx->nparts,
+                       idx->s_pt_items.as<int4>());
+    HG_HIP(hipGetLastError());
+    int32_t *again_cnt = idx->s_probes.as<int32_t>(), *again = again_cnt + 1;
+    HG_HIP(hipMemsetAsync(again_cnt, 0, sizeof(int32_t), st));
+    a.again = again;
+    a.again_cnt = again_cnt;
+    hipEvent_t e0;
+    prof_begin(idx, PROF_HNSW, st, &e0);
+    int rc = hnsw_launch_planned(idx, p, a, st);
+    prof_end(idx, PROF_HNSW, st, e0);
+    HG_TRY(rc);
+    if (p.repeat_cap) {  // as search_enqueue's: the items that ran out of ghost slots, with the largest list the LDS holds
+        a.cap = p.repeat_cap;
+        a.again = nullptr;
+        a.again_cnt = nullptr;
+        a.q_index = again;
+        a.nq_dev = again_cnt;
+        HnswLaunchPlan r;
+        HG_TRY(hnsw_launch_plan(idx, a, &p, r));
+        HG_TRY(hnsw_launch_planned(idx, r, a, st));
+    }
+    if (d_stats) {
+        hipLaunchKernelGGL(parts_stats_kernel, dim3(blocks), dim3(256), 0, st, idx->s_pt_stats.as<int64_t>(), nq, nprobe, d_stats);
+        HG_HIP(hipGetLastError());
+    }
+    return hnswgpu_merge_lists_dev(idx->device, idx->s_pt_ids.as<int32_t>(), idx->s_pt_dist.as<float>(), nprobe, nq, k_part, k, d_ids,
+                                   d_dist, st);
+}
+
 }  // namespace hg
 
 using namespace hg;
@@ -820,65 +1058,34 @@ extern "C" {
 
 int hnswgpu_set_graph(hnswgpu_index *idx, const int32_t *levels, const int32_t *l0_adj, int32_t M0,
                       const int64_t *up_off, const int32_t *up_adj, int32_t M, int32_t entry, int32_t max_level) {
-    HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
-    const int64_t n = idx->n;
-    HG_REQUIRE(n == 0 || (levels && l0_adj && up_off), HNSWGPU_EINVAL, "null argument");
-    HG_REQUIRE(M >= 1 && M0 >= 1 && M0 <= kMaxDeg && M <= kMaxDeg, HNSWGPU_ELIMIT, "need 1 <= M, M0 <= %d", kMaxDeg);
-    int64_t blocks = n > 0 ? up_off[n] : 0;
-    if (n > 0) {
-        HG_REQUIRE(entry >= 0 && entry < n, HNSWGPU_EINVAL, "entry out of range");
-        HG_REQUIRE(max_level >= 0 && levels[entry] >= max_level, HNSWGPU_EINVAL, "entry level < max_level");
-        HG_REQUIRE(up_off[0] == 0, HNSWGPU_EINVAL, "up_off[0] != 0");
-        for (int64_t i = 0; i < n; i++) {
-            HG_REQUIRE(levels[i] >= 0, HNSWGPU_EINVAL, "node %lld has a negative level", (long long)i);
-            HG_REQUIRE(up_off[i + 1] - up_off[i] == levels[i], HNSWGPU_EINVAL,
-                       "up_off is not the prefix sum of levels at node %lld", (long long)i);
-            HG_REQUIRE(levels[i] <= max_level, HNSWGPU_EINVAL, "node %lld level > max_level", (long long)i);
-        }
-        HG_REQUIRE(blocks == 0 || up_adj, HNSWGPU_EINVAL, "up_adj is null");
-        // every edge must point at a node that exists on that layer: the kernel trusts this
-        for (int64_t i = 0; i < n * M0; i++)
-            HG_REQUIRE(l0_adj[i] >= -1 && l0_adj[i] < n, HNSWGPU_EINVAL, "l0_adj entry out of range");
-        for (int64_t i = 0; i < n; i++)
-            for (int lv = 1; lv <= levels[i]; lv++)
-                for (int j = 0; j < M; j++) {
-                    int32_t nb = up_adj[(up_off[i] + lv - 1) * M + j];
-                    HG_REQUIRE(nb >= -1 && nb < n, HNSWGPU_EINVAL, "up_adj entry out of range");
-                    HG_REQUIRE(nb < 0 || levels[nb] >= lv, HNSWGPU_EINVAL,
-                               "edge %lld->%d on layer %d: target has no such layer", (long long)i, nb, lv);
-                }
-    }
+    HG_TRY(check_graph(idx, levels, l0_adj, M0, up_off, up_adj, M, entry, max_level, nullptr));
     hipStream_t st = idx->stream;
     Call call;
     HG_TRY(call.open(idx, st));
-    // every earlier call on this handle is ordered before `st` by the scope, except the small synchronous searches on
-    // the slot streams: once `st` and both slot streams are idle nothing can still be traversing the graph that is about
-    // to be freed (and no other handle on this GPU is stalled)
-    HG_TRY(call.quiesce());
-    free_graph(idx);
-    HG_TRY(alloc_graph(idx, M, M0, blocks));
-    HG_TRY(ensure_qrows(idx, st));
-    if (n > 0) {
-        HG_HIP(hipMemcpyAsync(idx->d_levels, levels, sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
-        HG_HIP(hipMemcpyAsync(idx->d_l0, l0_adj, sizeof(int32_t) * n * M0, hipMemcpyHostToDevice, st));
-        HG_HIP(hipMemcpyAsync(idx->d_upoff, up_off, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, st));
-        if (blocks > 0)
-            HG_HIP(hipMemcpyAsync(idx->d_upadj, up_adj, sizeof(int32_t) * blocks * M, hipMemcpyHostToDevice, st));
-        HG_TRY(call.sync());
-        idx->h_levels.assign(levels, levels + n);
-        idx->h_l0.assign(l0_adj, l0_adj + n * M0);
-        idx->h_upoff.assign(up_off, up_off + n + 1);
-        idx->h_upadj.assign(up_adj, up_adj + blocks * M);
-    } else {
-        idx->h_levels.clear();
-        idx->h_l0.clear();
-        idx->h_upoff.assign(1, 0);
-        idx->h_upadj.clear();
-    }
-    idx->entry = n > 0 ? entry : -1;
-    idx->max_level = n > 0 ? max_level : 0;
-    idx->has_graph = true;
+    HG_TRY(install_graph(idx, call, st, levels, l0_adj, M0, up_off, up_adj, M, entry, max_level, nullptr));
     return call.close();
+}
+
+int hnswgpu_set_graph_parts(hnswgpu_index *idx, const int32_t *levels, const int32_t *l0_adj, int32_t M0, const int64_t *up_off,
+                            const int32_t *up_adj, int32_t M, int32_t nparts, const int64_t *part_off, const int32_t *part_entry,
+                            const int32_t *part_max_level) {
+    const PartTables pt = {nparts, part_off, part_entry, part_max_level};
+    HG_TRY(check_graph(idx, levels, l0_adj, M0, up_off, up_adj, M, -1, 0, &pt));
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_TRY(install_graph(idx, call, st, levels, l0_adj, M0, up_off, up_adj, M, -1, 0, &pt));
+    return call.close();
+}
+
+int hnswgpu_graph_parts(const hnswgpu_index *idx, int32_t *nparts, int64_t *part_off, int32_t *part_entry, int32_t *part_max_level) {
+    HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
+    HG_REQUIRE(idx->has_graph && idx->nparts > 0, HNSWGPU_ESTATE, "the index holds no forest (call hnswgpu_hnsw_build_parts / hnswgpu_set_graph_parts)");
+    if (nparts) *nparts = idx->nparts;
+    if (part_off) memcpy(part_off, idx->h_part_off.data(), sizeof(int64_t) * idx->h_part_off.size());
+    if (part_entry) memcpy(part_entry, idx->h_part_entry.data(), sizeof(int32_t) * idx->h_part_entry.size());
+    if (part_max_level) memcpy(part_max_level, idx->h_part_level.data(), sizeof(int32_t) * idx->h_part_level.size());
+    return 0;
 }
 
 int hnswgpu_graph_sizes(const hnswgpu_index *idx, int32_t *M, int32_t *M0, int64_t *up_blocks, int32_t *entry,
@@ -905,11 +1112,15 @@ int hnswgpu_get_graph(const hnswgpu_index *idx, int32_t *levels, int32_t *l0_adj
 }
 
 static int check_hnsw_args(const hnswgpu_index *idx, const void *Q, int32_t nq, int32_t k, int32_t *ef,
-                           const void *ids, const void *dist) {
+                           const void *ids, const void *dist, bool parts = false) {
     HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
     HG_REQUIRE(nq >= 0 && k >= 1, HNSWGPU_EINVAL, "need nq >= 0 and k >= 1");
     HG_REQUIRE(nq == 0 || (Q && ids && dist), HNSWGPU_EINVAL, "null argument");
     HG_REQUIRE(idx->has_graph, HNSWGPU_ESTATE, "index has no graph (call hnswgpu_hnsw_build / hnswgpu_set_graph)");
+    HG_REQUIRE(idx->nparts == 0 || parts, HNSWGPU_ESTATE,
+               "the index holds a forest (hnswgpu_set_graph_parts / hnswgpu_hnsw_build_parts): search it with hnswgpu_hnsw_search_parts");
+    HG_REQUIRE(idx->nparts > 0 || !parts, HNSWGPU_ESTATE,
+               "the index holds no forest (call hnswgpu_hnsw_build_parts / hnswgpu_set_graph_parts)");
     if (*ef <= 0) *ef = k > 50 ? k : 50;  // ef = (max k 50), ultra_fast.clj:355
     if (*ef < k) *ef = k;
     HG_REQUIRE(*ef <= 4096, HNSWGPU_ELIMIT, "ef > 4096 is not supported");
@@ -1031,6 +1242,76 @@ int hnswgpu_hnsw_search(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t 
         [idx](const std::vector<hnswgpu_index::SearchReq *> &batch, int32_t total) {
             return hnsw_search_batch(idx, batch, total);
         });
+}
+
+// the argument check of both forest search entries; nprobe: the caller's, or the number of parts without a probe table
+static int check_parts_args(const hnswgpu_index *idx, const void *Q, int32_t nq, int32_t k_part, int32_t *ef, const void *probes,
+                            int32_t *nprobe, int32_t k, const void *ids, const void *dist) {
+    HG_TRY(check_hnsw_args(idx, Q, nq, k_part, ef, ids, dist, true));
+    HG_REQUIRE(k >= 1, HNSWGPU_EINVAL, "need k >= 1");
+    HG_REQUIRE(k <= 1024, HNSWGPU_ELIMIT, "k > 1024 is not supported");
+    if (!probes) *nprobe = idx->nparts;
+    HG_REQUIRE(*nprobe >= 1, HNSWGPU_EINVAL, "need nprobe >= 1");
+    HG_REQUIRE(static_cast<int64_t>(*nprobe) * k_part < 2147483647LL && *nprobe <= kPartsMaxItems, HNSWGPU_ELIMIT,
+               "nprobe * k_part too large");
+    return 0;
+}
+
+// The reference's two indexes of many small graphs (partitioned_hnsw.clj:149-196, ivf_hnsw.clj:286-325) on one handle and in one
+// traversal launch: item (q, r) is hnswgpu_hnsw_search(k_part, ef) of query q on a handle over the rows of part probes[q][r] alone
+// -- ids (handle rows), distance bits and counters --, the result hnswgpu_merge_lists_dev of a query's items in probe order.
+int hnswgpu_hnsw_search_parts_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k_part, int32_t ef, const int32_t *d_probes,
+                                  int32_t nprobe, int32_t k, int32_t *d_out_ids, float *d_out_dist, int64_t *d_stats, void *stream) {
+    HG_TRY(check_parts_args(idx, d_Q, nq, k_part, &ef, d_probes, &nprobe, k, d_out_ids, d_out_dist));
+    if (nq == 0) return 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_REQUIRE(idx->nparts > 0 && (d_probes || nprobe == idx->nparts), HNSWGPU_ESTATE, "the forest was replaced while the call was on its way");
+    const int32_t step = static_cast<int32_t>(std::max<int64_t>(1, kPartsMaxItems / nprobe));
+    for (int32_t q0 = 0; q0 < nq; q0 += step) {
+        const int32_t m = std::min(step, nq - q0);
+        HG_TRY(hnsw_parts_enqueue(idx, d_Q + static_cast<int64_t>(q0) * idx->dim, m, k_part, ef,
+                                  d_probes ? d_probes + static_cast<int64_t>(q0) * nprobe : nullptr, nprobe, k,
+                                  d_out_ids + static_cast<int64_t>(q0) * k, d_out_dist + static_cast<int64_t>(q0) * k,
+                                  d_stats ? d_stats + 2 * static_cast<int64_t>(q0) * nprobe : nullptr, st));
+    }
+    return call.close();
+}
+
+// One caller's staged batch (probe tables differ between callers: no part in the call combiner or the mapped-memory slots), in
+// slices of at most kPartsMaxItems items.
+int hnswgpu_hnsw_search_parts(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k_part, int32_t ef, const int32_t *probes,
+                              int32_t nprobe, int32_t k, int32_t *out_ids, float *out_dist, int64_t *stats) {
+    HG_TRY(check_parts_args(idx, Q, nq, k_part, &ef, probes, &nprobe, k, out_ids, out_dist));
+    if (nq == 0) return 0;
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_REQUIRE(idx->nparts > 0 && (probes || nprobe == idx->nparts), HNSWGPU_ESTATE, "the forest was replaced while the call was on its way");
+    const int32_t step = static_cast<int32_t>(std::max<int64_t>(1, kPartsMaxItems / nprobe));
+    for (int32_t q0 = 0; q0 < nq; q0 += step) {
+        const int32_t m = std::min(step, nq - q0);
+        const int64_t items = static_cast<int64_t>(m) * nprobe;
+        HG_TRY(call.stage_in(Q + static_cast<int64_t>(q0) * idx->dim, m, k));
+        int32_t *d_probes = nullptr;
+        if (probes) {
+            HG_TRY(idx->s_pt_probes.ensure(sizeof(int32_t) * items));
+            d_probes = idx->s_pt_probes.as<int32_t>();
+            HG_HIP(hipMemcpyAsync(d_probes, probes + static_cast<int64_t>(q0) * nprobe, sizeof(int32_t) * items, hipMemcpyHostToDevice, st));
+        }
+        int64_t *d_stats = nullptr;
+        if (stats) {
+            HG_TRY(idx->s_stats.ensure(sizeof(int64_t) * 2 * items));
+            d_stats = idx->s_stats.as<int64_t>();
+        }
+        HG_TRY(hnsw_parts_enqueue(idx, idx->s_q.as<float>(), m, k_part, ef, d_probes, nprobe, k, idx->s_ids.as<int32_t>(),
+                                  idx->s_outd.as<float>(), d_stats, st));
+        if (stats)
+            HG_HIP(hipMemcpyAsync(stats + 2 * static_cast<int64_t>(q0) * nprobe, d_stats, sizeof(int64_t) * 2 * items, hipMemcpyDeviceToHost, st));
+        HG_TRY(call.stage_out(out_ids + static_cast<int64_t>(q0) * k, out_dist + static_cast<int64_t>(q0) * k, static_cast<int64_t>(m) * k));
+    }
+    return call.close();
 }
 
 int hnswgpu_hnsw_last_order(hnswgpu_index *idx, int32_t *order, int32_t *keys, int32_t cap, int32_t *nq) {
@@ -1753,6 +2034,61 @@ int hnswgpu_hnsw_build_ex(hnswgpu_index *idx, int32_t M, int32_t ef_construction
     return call.close();
 }
 
+// A forest built part by part: every non-empty part's rows -- contiguous in the handle's base matrix -- become a temporary handle
+// that hnswgpu_hnsw_build_ex builds exactly as a caller's handle over those rows alone (same seed: the part's rows draw levels as
+// rows 0, 1, ... of their own handle; same flags), its graph is exported and its ids shifted by the part's first row.  The forest
+// is installed once, when every part stands: on any error the handle keeps what it had.
+int hnswgpu_hnsw_build_parts(hnswgpu_index *idx, int32_t nparts, const int64_t *part_off, int32_t M, int32_t ef_construction,
+                             int64_t seed, int32_t flags) {
+    HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
+    HG_REQUIRE(nparts >= 1 && part_off, HNSWGPU_EINVAL, "need nparts >= 1 and part_off");
+    HG_REQUIRE((flags & ~(HNSWGPU_BUILD_SEQUENTIAL | HNSWGPU_BUILD_HEURISTIC | HNSWGPU_BUILD_SYMMETRIC | HNSWGPU_BUILD_EXTEND)) == 0,
+               HNSWGPU_EINVAL, "unknown build flags 0x%x", flags);
+    HG_REQUIRE(!(flags & (HNSWGPU_BUILD_SYMMETRIC | HNSWGPU_BUILD_EXTEND)) || (flags & HNSWGPU_BUILD_HEURISTIC), HNSWGPU_EINVAL,
+               "HNSWGPU_BUILD_SYMMETRIC / _EXTEND qualify HNSWGPU_BUILD_HEURISTIC");
+    HG_REQUIRE(M >= 1 && 2 * M <= kMaxDeg, HNSWGPU_ELIMIT, "need 1 <= M <= %d", kMaxDeg / 2);
+    HG_REQUIRE(ef_construction >= 1 && ef_construction <= 4096, HNSWGPU_ELIMIT, "need 1 <= ef_construction <= 4096");
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
+    const int64_t n = idx->n;
+    HG_REQUIRE(part_off[0] == 0 && part_off[nparts] == n, HNSWGPU_EINVAL, "part_off must run from 0 to n");
+    for (int32_t p = 0; p < nparts; p++)
+        HG_REQUIRE(part_off[p] <= part_off[p + 1] && part_off[p + 1] <= n, HNSWGPU_EINVAL, "part_off is not monotone at part %d", p);
+    const int M0 = 2 * M;
+    std::vector<int32_t> levels(n), l0(static_cast<size_t>(n) * M0, -1), up, entry(nparts, -1), top(nparts, 0);
+    std::vector<int64_t> up_off(n + 1, 0);
+    for (int32_t p = 0; p < nparts; p++) {
+        const int64_t lo = part_off[p], rows = part_off[p + 1] - lo;
+        if (rows == 0) continue;
+        hnswgpu_index *tmp = nullptr;
+        HG_TRY(hnswgpu_create_dev(idx->d_base + lo * idx->ld, rows, idx->dim, idx->ld, idx->metric, idx->device, st, &tmp));
+        const int rc = [&]() -> int {
+            tmp->rejection_mode = idx->rejection_mode;  // (the builder's searches decide as the caller's handle would: never a result)
+            HG_TRY(hnswgpu_hnsw_build_ex(tmp, M, ef_construction, seed, flags));
+            const int64_t blocks0 = up_off[lo], blocks = tmp->up_blocks;
+            up.resize(static_cast<size_t>(blocks0 + blocks) * M, -1);
+            std::vector<int64_t> off_p(rows + 1);
+            HG_TRY(hnswgpu_get_graph(tmp, levels.data() + lo, l0.data() + lo * M0, off_p.data(), up.data() + blocks0 * M));
+            for (int64_t i = 0; i <= rows; i++) up_off[lo + i] = blocks0 + off_p[i];
+            for (int64_t i = lo * M0; i < (lo + rows) * M0; i++)
+                if (l0[i] >= 0) l0[i] += static_cast<int32_t>(lo);
+            for (int64_t i = blocks0 * M; i < (blocks0 + blocks) * M; i++)
+                if (up[i] >= 0) up[i] += static_cast<int32_t>(lo);
+            entry[p] = tmp->entry + static_cast<int32_t>(lo);
+            top[p] = tmp->max_level;
+            return 0;
+        }();
+        (void)hnswgpu_destroy(tmp);
+        HG_HIP(hipSetDevice(idx->device));
+        HG_TRY(rc);
+    }
+    const PartTables pt = {nparts, part_off, entry.data(), top.data()};
+    HG_TRY(check_graph(idx, levels.data(), l0.data(), M0, up_off.data(), up.data(), M, -1, 0, &pt));
+    HG_TRY(install_graph(idx, call, st, levels.data(), l0.data(), M0, up_off.data(), up.data(), M, -1, 0, &pt));
+    return call.close();
+}
+
 // insert-single on a LIVE index (ultra_fast.clj:216-275, reached by add-vector! src/hnsw/api.clj:30-33 and add!
 // src/hnsw/api/simple.clj:31-42): `m` more rows join the base matrix and the graph that is installed.  The new rows'
 // levels continue the seeded java.util.Random sequence (row i takes its i-th draw), they are inserted in batches by the
@@ -1769,6 +2105,8 @@ int hnswgpu_hnsw_add(hnswgpu_index *idx, const float *rows, int64_t m, int32_t e
     Call call;
     HG_TRY(call.open(idx, st));
     HG_REQUIRE(idx->has_graph, HNSWGPU_ESTATE, "index has no graph (call hnswgpu_hnsw_build / hnswgpu_set_graph first)");
+    HG_REQUIRE(idx->nparts == 0, HNSWGPU_ESTATE,
+               "the index holds a forest: a new row has no part (rebuild with hnswgpu_hnsw_build_parts / hnswgpu_set_graph_parts)");
     HG_REQUIRE(idx->nlist == 0, HNSWGPU_ESTATE,
                "the index holds IVF lists over its present rows: add rows first, then build / install the lists");
     HG_REQUIRE(idx->M0 == 2 * idx->M, HNSWGPU_ESTATE, "hnswgpu_hnsw_add needs a graph with M0 = 2 M (as hnswgpu_hnsw_build makes)");

@@ -1512,6 +1512,12 @@ struct HnswArgs {
     // hnsw_wave_kernel, ordered launches (order_kernels.hpp): slot s serves query q_order[(s % 8) * ceil(nq / 8) + s / 8]; null =
     // slot s serves query s.  Everything that is indexed by the query stays indexed by the query.
     const int32_t *q_order;
+    // Forest launches (hnswgpu_hnsw_search_parts; parts_kernels.hpp fills the table): work item i serves query row items[i].x in
+    // the sub-graph whose entry row is items[i].y (-1: the item's outputs are padding) and whose top level is items[i].z; the
+    // LDS visited set is indexed by row - items[i].w, the first row of the part (HBM stamps stay indexed by row).  Outputs,
+    // counters, again[] and q_index are indexed by the ITEM.  Read by the PARTS instantiations of hnsw_search_kernel (no helpers)
+    // and hnsw_wave_kernel (parts.hip); null = every work item is a query of the one graph (entry, max_level).
+    const int4 *items;
     unsigned long long *dbg;  // -DHG_HNSW_STAMPS diagnostic builds only: per-phase s_memrealtime totals
 };
 
@@ -1539,6 +1545,18 @@ struct HnswArgs {
 #endif
 
 constexpr uint32_t kExpanded = 0x80000000u;
+
+// A forest launch's item without a sub-graph to search (HnswArgs::items, entry -1): k times (-1, +inf), both counters 0
+__device__ __forceinline__ void hnsw_item_padding(const HnswArgs &a, int item, int tid, int nthreads) {
+    for (int i = tid; i < a.k; i += nthreads) {
+        a.out_ids[static_cast<int64_t>(item) * a.k + i] = -1;
+        a.out_dist[static_cast<int64_t>(item) * a.k + i] = __uint_as_float(0x7f800000u);
+    }
+    if (a.stats && tid == 0) {
+        a.stats[2 * static_cast<int64_t>(item)] = 0;
+        a.stats[2 * static_cast<int64_t>(item) + 1] = 0;
+    }
+}
 
 // NW = waves per query: 4 for latency (few queries), 1-2 for throughput (more queries resident per CU;
 // with NW = 1 every barrier is wave-local).  VG = visited set in HBM (generation stamps) instead of
@@ -1674,7 +1692,9 @@ __device__ __forceinline__ void pf_post(const HnswArgs &a, uint32_t *mail, const
     }
 }
 
-template <int NCH, int RB, bool L2, int NW, bool VG, bool PF = false>
+// PARTS = a forest launch (HnswArgs::items; parts.hip holds those instantiations): a template parameter, not a test of the pointer
+// -- the kernels use every SGPR there is, and four more live scalars cost each instantiation 9 to 20 VGPRs (measured: DESIGN.md)
+template <int NCH, int RB, bool L2, int NW, bool VG, bool PF = false, bool PARTS = false>
 __global__ __launch_bounds__(NW * kWave) void hnsw_search_kernel(HnswArgs a) {
     constexpr int kThreads = NW * kWave;
     extern __shared__ __align__(16) unsigned char smem[];
@@ -1709,10 +1729,25 @@ __global__ __launch_bounds__(NW * kWave) void hnsw_search_kernel(HnswArgs a) {
         if (pf_role > 0) wi0 = nq_eff;  // helpers (and spare workgroups) take no query
     }
     for (int wi = wi0; wi < nq_eff; wi += wi_step) {
-        const int qi = a.q_index ? a.q_index[wi] : wi;  // the query this work item serves
+        const int qi = a.q_index ? a.q_index[wi] : wi;  // the query (forest launches: the item) this work item serves
         uint2 *const curA = listA;
         uint32_t pf_head = 0, pf_recent = 0xffffffffu;  // wave 1: entries posted so far; lane l: the l-th recent node
-        const float *qptr = a.q_rows ? a.rows + static_cast<int64_t>(a.q_rows[qi]) * a.ld : a.Q + qi * a.qld;
+        int64_t qrow = qi;
+        int32_t entry = a.entry, max_level = a.max_level;
+        uint32_t vis0 = 0;  // the row that owns bit 0 of the LDS visited set
+        if (PARTS) {
+            const int4 it = a.items[qi];
+            if (it.y < 0) {  // a skipped probe or an empty part (uniform in the workgroup: no barrier is left out on one side)
+                hnsw_item_padding(a, qi, tid, kThreads);
+                continue;
+            }
+            // (one item per workgroup: the four words into SGPRs, where entry and max_level of a plain launch live)
+            qrow = __builtin_amdgcn_readfirstlane(it.x);
+            entry = __builtin_amdgcn_readfirstlane(it.y);
+            max_level = __builtin_amdgcn_readfirstlane(it.z);
+            vis0 = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(it.w));
+        }
+        const float *qptr = a.q_rows ? a.rows + static_cast<int64_t>(a.q_rows[qi]) * a.ld : a.Q + qrow * a.qld;
         float4 q[NCH];
         load_query<NCH>(q, qptr, a.dim, lane);
         float qn = a.metric == METRIC_COS ? query_norm<NCH>(q) : 0.0f;
@@ -1733,14 +1768,14 @@ __global__ __launch_bounds__(NW * kWave) void hnsw_search_kernel(HnswArgs a) {
         // seed: the entry point (ultra_fast.clj:358-359)
         {
             float4 r[NCH];
-            load_row<NCH>(r, a.rows + static_cast<int64_t>(a.entry) * a.ld, nvec, lane, true);
+            load_row<NCH>(r, a.rows + static_cast<int64_t>(entry) * a.ld, nvec, lane, true);
             float s = wave_sum(lane_partial<NCH, L2>(q, r));
-            float d = finish_dist(a.metric, s, qn, a.metric == METRIC_COS ? a.row_norms[a.entry] : 0.0f);
-            if (tid == 0) curA[0] = make_uint2(__float_as_uint(d + 0.0f), static_cast<uint32_t>(a.entry));
+            float d = finish_dist(a.metric, s, qn, a.metric == METRIC_COS ? a.row_norms[entry] : 0.0f);
+            if (tid == 0) curA[0] = make_uint2(__float_as_uint(d + 0.0f), static_cast<uint32_t>(entry));
             len = 1;
             n_eval = 1;
         }
-        const int top_l = (a.ref_start && qlevel >= 0 && qlevel < a.max_level) ? qlevel : a.max_level;
+        const int top_l = (a.ref_start && qlevel >= 0 && qlevel < max_level) ? qlevel : max_level;
         for (int level = top_l; level >= 0; level--) {
             int ef_l = level > 0 ? 1 : a.ef;
             // fresh visited set per layer (:156); entries carried from the level above are marked
@@ -1759,7 +1794,7 @@ __global__ __launch_bounds__(NW * kWave) void hnsw_search_kernel(HnswArgs a) {
                 e.y &= ~kExpanded;
                 curA[i] = e;
                 if (VG) atomicExch(&stamps[e.y], gen);
-                else atomicOr(&bits[e.y >> 5], 1u << (e.y & 31));
+                else atomicOr(&bits[(PARTS ? e.y - vis0 : e.y) >> 5], 1u << ((PARTS ? e.y - vis0 : e.y) & 31));
             }
             __syncthreads();
             int cur_start = 0;
@@ -1810,8 +1845,9 @@ __global__ __launch_bounds__(NW * kWave) void hnsw_search_kernel(HnswArgs a) {
                             if (VG) {
                                 fresh = atomicExch(&stamps[nb], gen) != gen;
                             } else {
-                                uint32_t bit = 1u << (nb & 31);
-                                uint32_t old = atomicOr(&bits[nb >> 5], bit);
+                                const uint32_t vb = PARTS ? static_cast<uint32_t>(nb) - vis0 : static_cast<uint32_t>(nb);
+                                uint32_t bit = 1u << (vb & 31);
+                                uint32_t old = atomicOr(&bits[vb >> 5], bit);
                                 fresh = !(old & bit);
                             }
                         }

@@ -130,6 +130,10 @@ int hnswgpu_save(hnswgpu_index *idx, const char *path) {
     // the file format does not carry: loaded back it would silently be an ordinary index with another tie order
     HG_REQUIRE(idx->h_glistlen.empty(), HNSWGPU_ESTATE,
                "this handle holds a shard of a larger IVF index (hnswgpu_set_ivf_shard): save the whole index instead");
+    // the file format holds ONE entry point: a forest (hnswgpu_set_graph_parts / hnswgpu_hnsw_build_parts) would come back as a
+    // plain graph without one
+    HG_REQUIRE(idx->nparts == 0, HNSWGPU_ESTATE,
+               "this handle holds a forest: keep hnswgpu_get_graph + hnswgpu_graph_parts and install them with hnswgpu_set_graph_parts");
     // written beside the target -- under a name of this process's and this call's own: two savers of one path never share
     // a temporary -- flushed to the disk, and renamed over the target once complete and closed: a reader never sees half a
     // file, a crash never leaves a renamed file with missing contents, a failed save leaves the previous file untouched

@@ -20,7 +20,7 @@ namespace hg {
 // One wave per query (workgroups of one wave; persistent: workgroup b serves slots b, b + gridDim.x, ...; a slot is a query).  VG = visited set in
 // HBM stamps.  Build launches too (q_rows: the query is a base row, the best entry of every upper level <= the node's level is
 // emitted for the linker, all ef candidates of layer 0 are the result); the repeat pass stays with hnsw_search_kernel.
-template <int NCH, int RB, bool L2, bool VG>
+template <int NCH, int RB, bool L2, bool VG, bool PARTS = false>
 __global__ __launch_bounds__(kWave) void hnsw_wave_kernel(HnswArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     // LDS: [main: cap x 8] [img: 64 x 8] [cand_id | cand_d: kMaxDeg each] [bits: nwords]
@@ -45,7 +45,22 @@ __global__ __launch_bounds__(kWave) void hnsw_wave_kernel(HnswArgs a) {
             if (pos >= a.nq) continue;
             qi = a.q_order[pos];
         }
-        const float *qptr = a.q_rows ? a.rows + static_cast<int64_t>(a.q_rows[qi]) * a.ld : a.Q + static_cast<int64_t>(qi) * a.qld;
+        int64_t qrow = qi;
+        int32_t entry = a.entry, max_level = a.max_level;
+        uint32_t vis0 = 0;  // the row that owns bit 0 of the LDS visited set
+        if (PARTS) {  // a forest launch (kernels.hpp, HnswArgs::items): qi is an item
+            const int4 it = a.items[qi];
+            if (it.y < 0) {
+                hnsw_item_padding(a, qi, lane, kWave);
+                continue;
+            }
+            // (one item per workgroup: the four words into SGPRs, where entry and max_level of a plain launch live)
+            qrow = __builtin_amdgcn_readfirstlane(it.x);
+            entry = __builtin_amdgcn_readfirstlane(it.y);
+            max_level = __builtin_amdgcn_readfirstlane(it.z);
+            vis0 = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(it.w));
+        }
+        const float *qptr = a.q_rows ? a.rows + static_cast<int64_t>(a.q_rows[qi]) * a.ld : a.Q + qrow * a.qld;
         float4 q[NCH];
         load_query<NCH>(q, qptr, a.dim, lane);
         const float qn = a.metric == METRIC_COS ? query_norm<NCH>(q) : 0.0f;
@@ -57,14 +72,14 @@ __global__ __launch_bounds__(kWave) void hnsw_wave_kernel(HnswArgs a) {
         bool over = false;
         {  // seed: the entry point (ultra_fast.clj:358-359)
             float4 r[NCH];
-            load_row<NCH>(r, a.rows + static_cast<int64_t>(a.entry) * a.ld, nvec, lane, true);
+            load_row<NCH>(r, a.rows + static_cast<int64_t>(entry) * a.ld, nvec, lane, true);
             const float s = wave_sum(lane_partial<NCH, L2>(q, r));
-            const float d = finish_dist(a.metric, s, qn, a.metric == METRIC_COS ? a.row_norms[a.entry] : 0.0f);
-            if (lane == 0) curA[0] = make_uint2(__float_as_uint(d + 0.0f), static_cast<uint32_t>(a.entry));
+            const float d = finish_dist(a.metric, s, qn, a.metric == METRIC_COS ? a.row_norms[entry] : 0.0f);
+            if (lane == 0) curA[0] = make_uint2(__float_as_uint(d + 0.0f), static_cast<uint32_t>(entry));
             len = 1;
             n_eval = 1;
         }
-        const int top_l = (a.ref_start && qlevel >= 0 && qlevel < a.max_level) ? qlevel : a.max_level;
+        const int top_l = (a.ref_start && qlevel >= 0 && qlevel < max_level) ? qlevel : max_level;
         for (int level = top_l; level >= 0; level--) {
             const int ef_l = level > 0 ? 1 : a.ef;
             // fresh visited set per layer (:156); entries carried from the level above are marked
@@ -82,7 +97,7 @@ __global__ __launch_bounds__(kWave) void hnsw_wave_kernel(HnswArgs a) {
                 e.y &= ~kExpanded;
                 curA[i] = e;
                 if (VG) atomicExch(&stamps[e.y], gen);
-                else atomicOr(&bits[e.y >> 5], 1u << (e.y & 31));
+                else atomicOr(&bits[(PARTS ? e.y - vis0 : e.y) >> 5], 1u << ((PARTS ? e.y - vis0 : e.y) & 31));
             }
             const int deg = level == 0 ? a.M0 : a.M;
             HnswList<false> L;
@@ -103,8 +118,9 @@ __global__ __launch_bounds__(kWave) void hnsw_wave_kernel(HnswArgs a) {
                     if (VG) {
                         fresh = atomicExch(&stamps[nbr], gen) != gen;
                     } else {
-                        const uint32_t bit = 1u << (nbr & 31);
-                        const uint32_t old = atomicOr(&bits[nbr >> 5], bit);
+                        const uint32_t vb = PARTS ? static_cast<uint32_t>(nbr) - vis0 : static_cast<uint32_t>(nbr);
+                        const uint32_t bit = 1u << (vb & 31);
+                        const uint32_t old = atomicOr(&bits[vb >> 5], bit);
                         fresh = !(old & bit);
                     }
                 }

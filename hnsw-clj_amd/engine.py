@@ -63,6 +63,29 @@ def _mask_words(allow, n):
     return a
 
 
+def parts_layout(base, rows):
+    """Per-part row lists -> what a forest handle (Index.hnsw_build_parts / set_graph_parts) is made from: (the rows of
+    ``base`` grouped by part, part_off int64 [nparts + 1], the data position of every handle row int32).  Part p is the handle
+    rows [part_off[p], part_off[p + 1]), in the order of ``rows[p]``; an empty list is an empty part."""
+    rows = [np.asarray(r, np.int64).reshape(-1) for r in rows]
+    part_off = np.zeros(len(rows) + 1, np.int64)
+    np.cumsum([len(r) for r in rows], out=part_off[1:])
+    pos = np.concatenate(rows + [np.empty(0, np.int64)])
+    if len(pos) and (pos.min() < 0 or pos.max() >= len(base)):
+        raise ValueError("row lists must hold positions in [0, %d)" % len(base))
+    return np.ascontiguousarray(np.asarray(base, np.float32)[pos]), part_off, pos.astype(np.int32)
+
+
+class GraphParts:
+    """The part tables of a forest (include/hnswgpu.h: hnswgpu_set_graph_parts)."""
+
+    def __init__(self, part_off, part_entry, part_max_level):
+        self.part_off = np.ascontiguousarray(part_off, np.int64)
+        self.part_entry = np.ascontiguousarray(part_entry, np.int32)
+        self.part_max_level = np.ascontiguousarray(part_max_level, np.int32)
+        self.nparts = len(self.part_entry)
+
+
 class Graph:
     """Flat HNSW graph (layout documented in include/hnswgpu.h)."""
 
@@ -290,6 +313,64 @@ class Index:
         flags = (BUILD_SEQUENTIAL if sequential else 0) | (BUILD_HEURISTIC if heuristic else 0) | \
                 (BUILD_SYMMETRIC if symmetric else 0) | (BUILD_EXTEND if extend else 0)
         check(lib().hnswgpu_hnsw_build_ex(self._h, M, ef_construction, seed, flags))
+
+    # -- a forest: several sub-graphs on this handle, searched in one launch (include/hnswgpu.h)
+    def set_graph_parts(self, g, parts):
+        """hnswgpu_set_graph_parts: ``g`` as for set_graph (its entry / max_level are not used), ``parts`` a GraphParts."""
+        if len(parts.part_off) != parts.nparts + 1 or len(parts.part_max_level) != parts.nparts:
+            raise ValueError("part tables of %d parts must hold %d offsets and %d levels" % (parts.nparts, parts.nparts + 1, parts.nparts))
+        check(lib().hnswgpu_set_graph_parts(self._h, _p(g.levels), _p(g.l0_adj), g.M0, _p(g.up_off), _p(g.up_adj), g.M,
+                                            parts.nparts, _p(parts.part_off), _p(parts.part_entry), _p(parts.part_max_level)))
+
+    def hnsw_build_parts(self, part_off, M=16, ef_construction=200, seed=42, flags=0):
+        """hnswgpu_hnsw_build_parts: every part [part_off[p], part_off[p + 1]) built as hnsw_build builds a handle over its rows
+        alone (flags: BUILD_*)."""
+        part_off = np.ascontiguousarray(part_off, np.int64)
+        check(lib().hnswgpu_hnsw_build_parts(self._h, len(part_off) - 1, _p(part_off), M, ef_construction, seed, int(flags)))
+
+    def graph_parts(self):
+        n = C.c_int32()
+        check(lib().hnswgpu_graph_parts(self._h, C.byref(n), None, None, None))
+        off, ent, lv = np.zeros(n.value + 1, np.int64), np.zeros(n.value, np.int32), np.zeros(n.value, np.int32)
+        check(lib().hnswgpu_graph_parts(self._h, C.byref(n), _p(off), _p(ent), _p(lv)))
+        return GraphParts(off, ent, lv)
+
+    def _nprobe(self, probes, nq):
+        if probes is None:
+            n = C.c_int32()
+            check(lib().hnswgpu_graph_parts(self._h, C.byref(n), None, None, None))
+            return n.value
+        assert probes.ndim == 2 and probes.shape[0] == nq, "probes must be [nq, nprobe]"
+        return int(probes.shape[1])
+
+    def hnsw_search_parts(self, Q, k_part, k, ef=0, probes=None, want_stats=False):
+        """hnswgpu_hnsw_search_parts: probes [nq, nprobe] part ids (-1 = skip), None = every part; -> handle rows [nq, k]
+        (-1 padded), distances; stats [nq, nprobe, 2]."""
+        Q = _queries(Q, self.dim)
+        if probes is not None:
+            probes = np.ascontiguousarray(probes, np.int32)
+        nprobe = self._nprobe(probes, len(Q))
+        ids = np.empty((len(Q), k), np.int32)
+        d = np.empty((len(Q), k), np.float32)
+        stats = np.zeros((len(Q), nprobe, 2), np.int64) if want_stats else None
+        check(lib().hnswgpu_hnsw_search_parts(self._h, _p(Q), len(Q), k_part, int(ef or 0), _p(probes), nprobe, k, _p(ids), _p(d),
+                                              _p(stats)))
+        return (ids, d, stats) if want_stats else (ids, d)
+
+    def hnsw_search_parts_dev(self, Q, k_part, k, ef=0, probes=None, out=None, stats=None):
+        """hnswgpu_hnsw_search_parts_dev on torch's current stream: probes an int32 CUDA tensor [nq, nprobe] or None; stats an
+        int64 CUDA tensor [nq, nprobe, 2] or None."""
+        import torch
+
+        Q, ids, d, st = self._dev_args(Q, k, out)
+        if probes is not None:
+            assert probes.is_cuda and probes.dtype == torch.int32
+            probes = probes.contiguous()
+        nprobe = self._nprobe(probes, Q.shape[0])
+        check(lib().hnswgpu_hnsw_search_parts_dev(self._h, Q.data_ptr(), Q.shape[0], k_part, int(ef or 0),
+                                                  probes.data_ptr() if probes is not None else None, nprobe, k, ids.data_ptr(),
+                                                  d.data_ptr(), stats.data_ptr() if stats is not None else None, st))
+        return ids, d
 
     def hnsw_add(self, rows, ef_construction=200, seed=42):
         """insert-single on the live index (ultra_fast.clj:216-275): `rows` join the base and the installed graph; returns

@@ -10,6 +10,10 @@ order (a stable sort of the concatenation, like Collections/sort at :320-324).
 ``honour_modes``: the reference writes ``:ef-search`` into ``[:params :ef]`` (:316) but ``graph/search-knn`` never
 reads it and searches with (max 2k 50) (graph.clj:304).  False (default) reproduces that; True makes
 the presets effective.
+
+``one_handle=True`` builds the partitions as a FOREST on one handle (``hnswgpu_hnsw_build_parts``) and searches all
+(query, probe) pairs in one traversal launch: the centroid ranking IS the probe table of
+``hnswgpu_hnsw_search_parts_dev``, no host round trip and no per-partition launch; results are the composition's.
 """
 import numpy as np
 
@@ -37,16 +41,20 @@ class IVFHNSWIndex:
         self.distance_fn = distance_fn
         self.hnsw_params = hnsw_params
         self._dev_rows = None
+        self.handle = None                # one_handle: the forest handle (every entry of partitions is None then) ...
+        self.row_pos = None               # ... and the data position of each of its rows
 
     def close(self):
         for p in self.partitions:
             if p is not None:
                 p.close()
+        if self.handle is not None:
+            self.handle.close()
         self.cent_index.close()
 
 
 def build_ivf_hnsw_index(data, num_partitions=24, distance_fn=cosine_distance_ultra, show_progress=False, M=16,
-                         ef_construction=200, max_iterations=10, parallel_build=True, seed=42, device=0):
+                         ef_construction=200, max_iterations=10, parallel_build=True, seed=42, device=0, one_handle=False):
     """ivf_hnsw.clj:172-280 (``parallel_build`` is accepted for signature parity; the device build is batched)."""
     metric = ultra_fast._metric_of(distance_fn)
     ids, base = ultra_fast._split(data)
@@ -57,7 +65,7 @@ def build_ivf_hnsw_index(data, num_partitions=24, distance_fn=cosine_distance_ul
     for p in range(num_partitions):
         r = np.ascontiguousarray(lids[off[p]:off[p + 1]], np.int32)
         rows.append(r)
-        if len(r) == 0:
+        if len(r) == 0 or one_handle:
             parts.append(None)                                       # :162-163 empty graph
             continue
         idx = engine.Index(base[r], metric, device)
@@ -65,8 +73,13 @@ def build_ivf_hnsw_index(data, num_partitions=24, distance_fn=cosine_distance_ul
         parts.append(idx)
     if show_progress:
         print("IVF-HNSW: %d vectors in %d partitions" % (len(ids), num_partitions))
-    return IVFHNSWIndex(parts, rows, cent, engine.Index(cent, metric, device), ids, distance_fn,
-                        {"M": M, "ef-construction": ef_construction, "total-partitions": num_partitions})
+    index = IVFHNSWIndex(parts, rows, cent, engine.Index(cent, metric, device), ids, distance_fn,
+                         {"M": M, "ef-construction": ef_construction, "total-partitions": num_partitions})
+    if one_handle:
+        grouped, part_off, index.row_pos = engine.parts_layout(base, rows)
+        index.handle = engine.Index(grouped, metric, device)
+        index.handle.hnsw_build_parts(part_off, M, ef_construction, seed)
+    return index
 
 
 def search_batch_dev(index, Q, k, mode="balanced", num_probes=None, ef_search=None, honour_modes=False):
@@ -79,9 +92,14 @@ def search_batch_dev(index, Q, k, mode="balanced", num_probes=None, ef_search=No
     k2 = 2 * int(k)
     ef = max(int(cfg["ef-search"]), k2) if honour_modes else 0
     nq = Q.shape[0]
+    probes, _ = index.cent_index.exact_knn_dev(Q, nprobe)            # :302-309 centroid ranking, stable
+    if index.handle is not None:                                     # the ranking is the probe table: one launch + the merge
+        if index._dev_rows is None:
+            index._dev_rows = torch.from_numpy(index.row_pos).to(Q.device)
+        loc, d = index.handle.hnsw_search_parts_dev(Q, k2, int(k), ef, probes=probes)
+        return torch.where(loc >= 0, index._dev_rows[loc.clamp(min=0).to(torch.int64)], loc), d
     if index._dev_rows is None:
         index._dev_rows = [torch.from_numpy(r.astype(np.int64)).to(Q.device) for r in index.rows]
-    probes, _ = index.cent_index.exact_knn_dev(Q, nprobe)            # :302-309 centroid ranking, stable
     ids = torch.full((nprobe, nq, k2), -1, dtype=torch.int32, device=Q.device)
     d = torch.full((nprobe, nq, k2), float("inf"), dtype=torch.float32, device=Q.device)
     flat_ids, flat_d = ids.view(nprobe * nq, k2), d.view(nprobe * nq, k2)

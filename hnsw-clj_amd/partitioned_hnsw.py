@@ -7,6 +7,10 @@ partition by the traversal kernel and the P result lists are merged by ``hnswgpu
 sort of the concatenation, like Collections/sort at :187-196).  The same object row-shards across GPUs with
 ``sharded.ShardedSearcher`` (one sub-graph per GPU).
 
+``one_handle=True`` builds the same index as a FOREST on one handle (``hnswgpu_hnsw_build_parts``: the rows grouped by
+partition, every partition's graph edge for edge the one its own handle builds) and searches all partitions in one
+traversal launch (``hnswgpu_hnsw_search_parts_dev``); results are the composition's, bit for bit.
+
 Deviation: the reference shuffles with the unseeded ``clojure.core/shuffle`` (:82); here the permutation comes
 from ``numpy.random.default_rng(seed)`` so that a build is reproducible.
 """
@@ -30,15 +34,19 @@ class PartitionedHNSWIndex:
         self.search_mode = search_mode
         self.metadata = metadata
         self._dev_rows = None
+        self.handle = None                    # one_handle: the forest handle (partitions is empty then) ...
+        self.row_pos = None                   # ... and the data position of each of its rows (np.int32)
 
     def close(self):
         for p in self.partitions:
             p.close()
+        if self.handle is not None:
+            self.handle.close()
 
 
 def build_partitioned_hnsw(data, num_partitions=8, shuffle=True, show_progress=False, search_mode="lightning",
                            distance_fn=cosine_distance_ultra, max_connections=16, ef_construction=50, seed=42,
-                           device=0):
+                           device=0, one_handle=False):
     """partitioned_hnsw.clj:46-143"""
     import time
 
@@ -49,16 +57,23 @@ def build_partitioned_hnsw(data, num_partitions=8, shuffle=True, show_progress=F
     order = np.random.default_rng(seed).permutation(n).astype(np.int32) if shuffle else np.arange(n, dtype=np.int32)
     size = max(1, math.ceil(n / num_partitions))           # :87 partition-size, :88 partition-all
     rows = [order[i:i + size] for i in range(0, n, size)]
-    parts = []
-    for r in rows:
-        p = engine.Index(base[r], metric, device)
-        p.hnsw_build(max_connections, ef_construction, seed)
-        parts.append(p)
+    parts, handle, pos = [], None, None
+    if one_handle and rows:
+        grouped, part_off, pos = engine.parts_layout(base, rows)
+        handle = engine.Index(grouped, metric, device)
+        handle.hnsw_build_parts(part_off, max_connections, ef_construction, seed)
+    else:
+        for r in rows:
+            p = engine.Index(base[r], metric, device)
+            p.hnsw_build(max_connections, ef_construction, seed)
+            parts.append(p)
     if show_progress:
         print("All partitions built in %.2f seconds" % (time.time() - t0))
-    return PartitionedHNSWIndex(parts, rows, ids, num_partitions, shuffle, search_mode,
-                                {"build-time": (time.time() - t0) * 1e3, "total-vectors": n,
-                                 "distance-fn": distance_fn})
+    index = PartitionedHNSWIndex(parts, rows, ids, num_partitions, shuffle, search_mode,
+                                 {"build-time": (time.time() - t0) * 1e3, "total-vectors": n,
+                                  "distance-fn": distance_fn})
+    index.handle, index.row_pos = handle, pos
+    return index
 
 
 def k_per_partition(mode, num_partitions, k):
@@ -76,6 +91,11 @@ def search_batch_dev(index, Q, k, mode=None):
 
     mode = mode or index.search_mode
     kpp = k_per_partition(mode, index.num_partitions, k)
+    if index.handle is not None:
+        if index._dev_rows is None:
+            index._dev_rows = torch.from_numpy(index.row_pos).to(Q.device)
+        loc, d = index.handle.hnsw_search_parts_dev(Q, kpp, int(k))   # every partition, ef = (max k' 50): one launch + the merge
+        return torch.where(loc >= 0, index._dev_rows[loc.clamp(min=0).to(torch.int64)], loc), d
     nq, P = Q.shape[0], len(index.partitions)
     if index._dev_rows is None:
         index._dev_rows = [torch.from_numpy(r.astype(np.int64)).to(Q.device) for r in index.rows]
@@ -99,9 +119,9 @@ def search_batch(index, queries, k, mode=None):
     queries = np.ascontiguousarray(queries, np.float32)
     if len(queries) == 0:
         return []
-    if not index.partitions:
+    if not index.partitions and index.handle is None:
         return [[] for _ in queries]
-    dev = torch.device("cuda", index.partitions[0].device)
+    dev = torch.device("cuda", (index.handle or index.partitions[0]).device)
     ids, d = search_batch_dev(index, torch.from_numpy(queries).to(dev), k, mode)
     return _to_maps(index, ids.cpu(), d.cpu())
 

@@ -152,6 +152,45 @@ int hnswgpu_hnsw_search(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t 
 int hnswgpu_hnsw_search_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t ef,
                             int32_t *d_out_ids, float *d_out_dist, int64_t *d_stats, void *stream);
 
+/* ---- A forest: several HNSW sub-graphs on one handle, searched in one launch ------------------------
+ * The reference's indexes of many small graphs -- partitioned-hnsw (partitioned_hnsw.clj:149-196: every partition searched for
+ * k' results, concatenated, stable-sorted, take k) and ivf-hnsw (ivf_hnsw.clj:286-325: the num-probes nearest partitions'
+ * graphs searched for 2k each, merged) -- on ONE handle.  The handle's rows are grouped by part: part p is the contiguous
+ * range [part_off[p], part_off[p + 1]); the caller permutes its rows and keeps the row -> id table.
+ * hnswgpu_set_graph_parts: hnswgpu_set_graph's arrays (adjacency holds handle row ids) + the part tables.  Checked as
+ *   hnswgpu_set_graph checks, and: part_off[0] == 0, part_off[nparts] == n, part_off monotone; every edge stays inside its
+ *   part; an empty part has part_entry[p] == -1; otherwise part_entry[p] lies in the part, levels[part_entry[p]] >=
+ *   part_max_level[p], and no node of the part is above part_max_level[p].  Any violation: HNSWGPU_EINVAL, and the handle
+ *   keeps what it had.
+ * hnswgpu_hnsw_build_parts: every non-empty part built as hnswgpu_hnsw_build_ex(M, ef_construction, seed, flags) builds a
+ *   handle over that part's rows alone -- edge for edge, after the id shift by part_off[p].  The forest is installed once:
+ *   on any error the handle keeps what it had.
+ * hnswgpu_graph_parts: the part tables (arrays may be NULL to read only nparts); HNSWGPU_ESTATE without a forest.
+ * hnswgpu_hnsw_search_parts / _dev: probes is [nq][nprobe] part ids, -1 = skip (as hnswgpu_ivf_search_lists); NULL = every
+ *   part in order (nprobe is then the number of parts, the argument is ignored).  Item (q, r) -- query q, its r-th probe p --
+ *   holds bit for bit the ids (shifted by part_off[p]: handle rows), distances and stats pair that
+ *   hnswgpu_hnsw_search(k_part, ef) returns on a handle over part p's rows alone with part p's graph (ef <= 0: max(k_part,
+ *   50)); a skipped probe, an empty part or a part id out of range is an all-padding list (-1 / +inf, stats 0).  The result
+ *   is hnswgpu_merge_lists_dev of a query's items in probe order: stable, ties go to the earlier probe, take k (k <= 1024).
+ *   stats (optional): [nq][nprobe][2].  All items run in ONE traversal launch (+ the tie repeat pass, per item); the _dev
+ *   entry only enqueues on `stream`; the host entry stages one caller's batch (no call combining).
+ * On a handle that holds a forest: hnswgpu_get_graph works; hnswgpu_graph_sizes reports entry = -1 and the largest
+ *   max_level; hnswgpu_info has_graph = 1; hnswgpu_hnsw_search*, the filtered searches, hnswgpu_hnsw_add and hnswgpu_save
+ *   return HNSWGPU_ESTATE; hnswgpu_set_graph / hnswgpu_hnsw_build* replace the forest with a plain graph, and the other way
+ *   round.
+ * Out of scope: the several-CU kernel for forest launches (the single-query latency of the hybrid indexes: a handful of items
+ *   run one workgroup each); save / load, add, filtered search and groups on a forest; a device-side forest builder. */
+int hnswgpu_set_graph_parts(hnswgpu_index *idx, const int32_t *levels, const int32_t *l0_adj, int32_t M0, const int64_t *up_off,
+                            const int32_t *up_adj, int32_t M, int32_t nparts, const int64_t *part_off, const int32_t *part_entry,
+                            const int32_t *part_max_level);
+int hnswgpu_hnsw_build_parts(hnswgpu_index *idx, int32_t nparts, const int64_t *part_off, int32_t M, int32_t ef_construction,
+                             int64_t seed, int32_t flags);
+int hnswgpu_graph_parts(const hnswgpu_index *idx, int32_t *nparts, int64_t *part_off, int32_t *part_entry, int32_t *part_max_level);
+int hnswgpu_hnsw_search_parts(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k_part, int32_t ef, const int32_t *probes,
+                              int32_t nprobe, int32_t k, int32_t *out_ids, float *out_dist, int64_t *stats);
+int hnswgpu_hnsw_search_parts_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k_part, int32_t ef, const int32_t *d_probes,
+                                  int32_t nprobe, int32_t k, int32_t *d_out_ids, float *d_out_dist, int64_t *d_stats, void *stream);
+
 /* ---- IVF-FLAT -------------------------------------------------------------------------------------
  * hnswgpu_ivf_build: build-ivf-flat-index :partition-method :kmeans (ivf_flat.clj:137-211):
  *   k-means++ seeding with java.util.Random(seed) (:32-60), max_iter Lloyd iterations (:92-131),
