@@ -22,6 +22,7 @@
      (from-ivf-flat-index ivf)                                       ; an IVFFlatIndex built by the reference's own k-means
      (save idx path) / (load-index path ids)                         ; helper/index-io save-index / load-index
      (search-knn-filtered index query-vec k filter-fn)               ; FilterableIndex/search-knn-filtered*, on the device
+     (search-batch-filtered-each index queries k filter-fns)          ; ... for a batch, one predicate per query, in one chain of launches
      (search-ivf-filtered index query-vec k filter-fn :num-probes 4)  ; ... through the IVF list scan: the k nearest passing rows
    and, at the bottom, the extend-type that makes GpuIndex an ANNIndex / BatchSearchIndex / FilterableIndex / PersistableIndex next to the
    records src/hnsw/api/unified.clj:30-95 extends."
@@ -270,6 +271,56 @@
         (check (.invokeWithArguments ^MethodHandle @h-search-filtered
                                      [(:handle idx) q (int nq) (int k) (int ef2) mask ids ds MemorySegment/NULL])))
       (mapv #(results idx ids ds % k) (range nq)))))
+
+(def ^:private h-exact-filtered-each
+  (delay (fn-handle "hnswgpu_exact_knn_filtered_each" (FunctionDescriptor/of I (into-array [P P I I P P P])))))
+(def ^:private h-search-filtered-each
+  (delay (fn-handle "hnswgpu_hnsw_search_filtered_each" (FunctionDescriptor/of I (into-array [P P I I I P P P P])))))
+
+(defn search-batch-filtered-each
+  "search-knn-filtered* for a batch with one predicate PER QUERY (filter-fns: as many as queries): result q is
+   (search-knn-filtered idx (nth queries q) k (nth filter-fns q)).  An identical predicate is evaluated once.  filtered-plan is
+   applied per query; the :scan queries go in one hnswgpu_exact_knn_filtered_each call, ordered so that equal predicates are
+   adjacent (a query group then shares the rows it fetches), the :graph queries in one hnswgpu_hnsw_search_filtered_each call
+   per distinct ef'; the caller's order is restored.  One predicate for the whole batch: search-batch-filtered."
+  [idx queries k filter-fns & {:keys [ef] :or {ef 0}}]
+  (assert (= (count queries) (count filter-fns)) "one filter-fn per query")
+  (if (and (seq filter-fns) (every? #(identical? % (first filter-fns)) filter-fns))
+    (search-batch-filtered idx queries k (first filter-fns) :ef ef)
+    (let [n (count (:ids idx))
+          words (max 1 (quot (+ n 31) 32))
+          distinct-fns (vec (distinct filter-fns))
+          fn-no (into {} (map-indexed (fn [i f] [f i]) distinct-fns))
+          masks (mapv (fn [f]                                   ; per distinct predicate: its words and its passing count
+                        (let [m (int-array words)]
+                          [m (reduce (fn [p i]
+                                       (if (f (nth (:ids idx) i))
+                                         (do (aset m (quot i 32) (unchecked-int (bit-or (aget m (quot i 32)) (bit-shift-left 1 (rem i 32)))))
+                                             (inc p))
+                                         p))
+                                     0 (range n))]))
+                      distinct-fns)
+          call-of (fn [q] (let [[plan ef2] (filtered-plan n (second (masks (fn-no (nth filter-fns q)))) k ef)]
+                            (if (= plan :scan) [:scan 0] [:graph ef2])))
+          out (object-array (count queries))]
+      (doseq [[[plan ef2] qs] (group-by call-of (range (count queries)))]
+        (with-open [arena (Arena/ofConfined)]
+          (let [qs (vec (sort-by (fn [q] [(fn-no (nth filter-fns q)) q]) qs))
+                nq (count qs)
+                mask (.allocate arena (* 4 words nq) 4)
+                _ (doseq [[j q] (map-indexed vector qs)]
+                    (MemorySegment/copy (MemorySegment/ofArray ^ints (first (masks (fn-no (nth filter-fns q))))) 0
+                                        mask (* 4 words j) (* 4 words)))
+                qa (floats-of arena (mapv #(nth queries %) qs) (:dim idx))
+                ids (.allocate arena (* 4 nq k) 4)
+                ds (.allocate arena (* 4 nq k) 4)]
+            (if (= plan :scan)
+              (check (.invokeWithArguments ^MethodHandle @h-exact-filtered-each [(:handle idx) qa (int nq) (int k) mask ids ds]))
+              (check (.invokeWithArguments ^MethodHandle @h-search-filtered-each
+                                           [(:handle idx) qa (int nq) (int k) (int ef2) mask ids ds MemorySegment/NULL])))
+            (doseq [[j q] (map-indexed vector qs)]
+              (aset out q (results idx ids ds j k))))))
+      (vec out))))
 
 (defn search-knn-filtered
   "One query through search-batch-filtered: seq of {:id :distance} ascending, fewer than k when fewer rows pass."

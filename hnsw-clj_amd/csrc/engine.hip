@@ -2022,20 +2022,26 @@ int launch_ivf_filtered_scan(int nch, const IvfFilteredArgs &a0, hipStream_t st)
     return 0;
 }
 
-static int launch_filtered_group(int nch, const FilteredArgs &a, int64_t blocks, hipStream_t st) {
+static int launch_filtered_group(int nch, const FilteredArgs &a, int64_t blocks, hipStream_t st, bool each = false) {
     HG_REQUIRE(blocks > 0 && blocks < 2147483647LL, HNSWGPU_ELIMIT, "filtered scan grid too large (%lld blocks)", (long long)blocks);
     const size_t lds = filtered_group_lds_bytes(a.ld);
     const bool l2 = a.metric == METRIC_L2;
-#define CALL(N, R, L)                                                                                               \
+#define CALLE(N, R, L, E)                                                                                           \
     do {                                                                                                            \
         static bool fg_attr_done[64] = {};                                                                          \
         if (attr_needed(fg_attr_done))                                                                              \
-            HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&filtered_group_kernel<N, R, L>),            \
+            HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&filtered_group_kernel<N, R, L, E>),         \
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                   \
-        hipLaunchKernelGGL((filtered_group_kernel<N, R, L>), dim3(static_cast<unsigned>(blocks)), dim3(kTileThreads), lds, st, a); \
+        hipLaunchKernelGGL((filtered_group_kernel<N, R, L, E>), dim3(static_cast<unsigned>(blocks)), dim3(kTileThreads), lds, st, a); \
+    } while (0)
+#define CALL(N, R, L)                    \
+    do {                                 \
+        if (each) CALLE(N, R, L, true);  \
+        else CALLE(N, R, L, false);      \
     } while (0)
     HG_DISPATCH(nch, l2, CALL);
 #undef CALL
+#undef CALLE
     HG_HIP(hipGetLastError());
     return 0;
 }
@@ -2104,8 +2110,168 @@ static int filtered_scan_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t n
     return 0;
 }
 
+// One mask per query (d_allow_each: [nq][W]).  The chain of filtered_scan_enqueue over the UNION of every query group's
+// masks: unions, popcounts and scans of all groups in one launch each, the groups' counts read back in one copy (the calling
+// thread waits for `st` there, once), then slices of whole groups -- cut so that the dense array stays within
+// FILTER_EACH_MB, which bounds the slice's lists and words too (both are 1 / tq of it) -- scatter, words, group scan,
+// selection and decode.  A run of groups whose unions are empty is padding and launches nothing.
+static int filtered_each_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, const uint32_t *d_allow_each,
+                                 int32_t *d_ids, float *d_dist, hipStream_t st) {
+    const int64_t n = idx->n, W = (n + 31) / 32;
+    const int tq = filtered_group_queries(idx->ld);
+    const int64_t G = (static_cast<int64_t>(nq) + tq - 1) / tq;
+    HG_REQUIRE(G <= 65535, HNSWGPU_ELIMIT, "too many query groups for one call (%lld, at most 65535)", (long long)G);
+    const int64_t nblk = (W + kMaskWordsPerWG - 1) / kMaskWordsPerWG;
+    UnionArgs u;
+    memset(&u, 0, sizeof(u));
+    u.allow_each = d_allow_each;
+    u.n = n;
+    u.nwords = W;
+    u.nq = nq;
+    u.tq = tq;
+    HG_TRY(idx->s_feum.ensure(sizeof(uint32_t) * static_cast<size_t>(G * W)));
+    u.um = idx->s_feum.as<uint32_t>();
+    // s_fblk: [G][nblk] block counts, then the G totals
+    const size_t tot_off = (sizeof(uint32_t) * static_cast<size_t>(G * nblk) + 7) & ~static_cast<size_t>(7);
+    HG_TRY(idx->s_fblk.ensure(tot_off + sizeof(unsigned long long) * static_cast<size_t>(G)));
+    unsigned long long *d_up = reinterpret_cast<unsigned long long *>(idx->s_fblk.as<char>() + tot_off);
+    u.up = d_up;
+    MaskArgs m;
+    memset(&m, 0, sizeof(m));
+    m.allow = u.um;
+    m.n = n;
+    m.nwords = W;
+    m.blk = idx->s_fblk.as<uint32_t>();
+    m.nblk = static_cast<int32_t>(nblk);
+    m.total = d_up;
+    m.allow_stride = W;
+    m.blk_stride = nblk;
+    m.total_stride = 1;
+    const unsigned gy = static_cast<unsigned>(G);
+    hipLaunchKernelGGL(mask_union_kernel, dim3(static_cast<unsigned>((W + kMaskThreads - 1) / kMaskThreads), gy), dim3(kMaskThreads), 0, st, u);
+    hipLaunchKernelGGL(mask_count_kernel, dim3(static_cast<unsigned>(nblk), gy), dim3(kMaskThreads), 0, st, m);
+    hipLaunchKernelGGL(mask_scan_kernel, dim3(1, gy), dim3(kMaskScanThreads), 0, st, m);
+    HG_HIP(hipGetLastError());
+    std::vector<int64_t> up(static_cast<size_t>(G));
+    {
+        HG_TRY(ensure_pinned(idx, sizeof(unsigned long long) * static_cast<size_t>(G)));
+        HG_HIP(hipMemcpyAsync(idx->h_pin, d_up, sizeof(unsigned long long) * static_cast<size_t>(G), hipMemcpyDeviceToHost, st));
+        HG_HIP(hipStreamSynchronize(st));
+        const unsigned long long *h = static_cast<const unsigned long long *>(idx->h_pin);
+        for (int64_t g = 0; g < G; g++) {
+            HG_REQUIRE(h[g] <= static_cast<unsigned long long>(n), HNSWGPU_EINVAL, "a group's masks count %llu passing rows of %lld", h[g], (long long)n);
+            up[static_cast<size_t>(g)] = static_cast<int64_t>(h[g]);
+        }
+    }
+    const int64_t cap_bytes = std::max<int64_t>(1, tune(HNSWGPU_TUNE_FILTER_EACH_MB, 2048)) << 20;
+    struct Slice {
+        int64_t g0, g1, pmax;
+    };
+    std::vector<Slice> slices;
+    size_t list_max = 0, q_max = 0;  // the largest slice's list entries and queries: the scratch is sized once, before any launch reads it
+    for (int64_t g0 = 0; g0 < G;) {
+        int64_t g1 = g0 + 1, pmax = up[static_cast<size_t>(g0)];
+        if (pmax == 0) {
+            while (g1 < G && up[static_cast<size_t>(g1)] == 0) g1++;
+        } else {
+            for (; g1 < G && up[static_cast<size_t>(g1)] > 0; g1++) {
+                const int64_t pm = (std::max(pmax, up[static_cast<size_t>(g1)]) + 3) / 4 * 4;
+                if ((g1 + 1 - g0) * tq * pm * 4 > cap_bytes) break;
+                pmax = std::max(pmax, up[static_cast<size_t>(g1)]);
+            }
+            list_max = std::max(list_max, static_cast<size_t>((g1 - g0) * ((pmax + 3) / 4 * 4)));
+            q_max = std::max(q_max, static_cast<size_t>((g1 - g0) * tq));
+        }
+        slices.push_back({g0, g1, pmax});
+        g0 = g1;
+    }
+    if (list_max) {
+        HG_TRY(pad_queries(idx, d_Q, idx->dim, nq, st));
+        HG_TRY(idx->s_fpass.ensure(sizeof(int32_t) * list_max));
+        HG_TRY(idx->s_feuw.ensure(sizeof(uint32_t) * list_max));
+        HG_TRY(idx->s_feqc.ensure(sizeof(int32_t) * q_max));
+        HG_TRY(idx->s_tile.ensure(sizeof(float) * list_max * tq));
+        HG_TRY(idx->s_ord.ensure(sizeof(uint32_t) * q_max * k));
+        HG_TRY(idx->s_dist.ensure(sizeof(float) * q_max * k));
+    }
+    for (const Slice &sl : slices) {
+        const int64_t g1 = sl.g1, pmax = sl.pmax;
+        const int64_t q0 = sl.g0 * tq;
+        const int32_t nb = static_cast<int32_t>(std::min<int64_t>(g1 * tq, nq) - q0);
+        const int64_t cnt = static_cast<int64_t>(nb) * k;
+        const int32_t ng = static_cast<int32_t>(g1 - sl.g0);
+        if (pmax == 0) {
+            HG_TRY(fill_empty_dev(d_ids + q0 * k, d_dist + q0 * k, cnt, st));
+            continue;
+        }
+        const int64_t pstride = (pmax + 3) / 4 * 4;  // rows of the dense array 16-byte aligned (select_topk_kernel's float4 loads)
+        const int64_t gs = g1 - ng;  // the slice's first group
+        MaskArgs ms = m;
+        ms.allow = u.um + gs * W;
+        ms.blk = m.blk + gs * nblk;
+        ms.total = d_up + gs;
+        ms.pass_ids = idx->s_fpass.as<int32_t>();
+        ms.cap = pstride;
+        ms.pass_stride = pstride;
+        hipLaunchKernelGGL(mask_scatter_kernel, dim3(static_cast<unsigned>(nblk), static_cast<unsigned>(ng)), dim3(kMaskThreads), 0, st, ms);
+        UnionArgs us = u;  // the slice's queries and groups, numbered from 0
+        us.allow_each = d_allow_each + q0 * W;
+        us.nq = nb;
+        us.upass = idx->s_fpass.as<int32_t>();
+        us.up = d_up + gs;
+        us.uw = idx->s_feuw.as<uint32_t>();
+        us.pstride = pstride;
+        us.q_cnt = idx->s_feqc.as<int32_t>();
+        hipLaunchKernelGGL(union_words_kernel, dim3(static_cast<unsigned>((pmax + kMaskThreads - 1) / kMaskThreads), static_cast<unsigned>(ng)),
+                           dim3(kMaskThreads), 0, st, us);
+        hipLaunchKernelGGL(union_qcnt_kernel, dim3((nb + 255) / 256), dim3(256), 0, st, us);
+        HG_HIP(hipGetLastError());
+        FilteredArgs f;
+        memset(&f, 0, sizeof(f));
+        f.rows = idx->d_base;
+        f.row_norms = idx->d_norms;
+        f.ld = idx->ld;
+        f.metric = idx->metric;
+        f.Qp = idx->s_qp.as<float>() + q0 * idx->ld;
+        f.q_norms = idx->s_qn.as<float>() + q0;
+        f.nq = nb;
+        f.tq = tq;
+        f.ngroups = ng;
+        f.pass_ids = us.upass;
+        f.uw = us.uw;
+        f.up = us.up;
+        f.pstride = pstride;
+        // chunks of whole 256-position tiles of the longest list, about 2048 workgroups in all (filtered_scan_enqueue)
+        const int64_t tiles = (pmax + kTileRows - 1) / kTileRows;
+        const int64_t want = std::max<int64_t>(1, std::min<int64_t>(tiles, (2048 + ng - 1) / ng));
+        f.chunk_rows = (tiles + want - 1) / want * kTileRows;
+        const int64_t nchunks = (pmax + f.chunk_rows - 1) / f.chunk_rows;
+        f.out = idx->s_tile.as<float>();
+        hipEvent_t e0;
+        prof_begin(idx, PROF_IVF_SCAN, st, &e0);
+        HG_TRY(launch_filtered_group(idx->nch, f, nchunks * ng, st, true));
+        prof_end(idx, PROF_IVF_SCAN, st, e0);
+        g_launch_count[HNSWGPU_COUNT_FILTERED_EACH_GROUPS].fetch_add(ng, std::memory_order_relaxed);
+        SelectArgs s;
+        memset(&s, 0, sizeof(s));
+        s.dist = f.out;
+        s.q_cnt = us.q_cnt;
+        s.stride = pstride;
+        s.cnt_all = pstride;
+        s.nq = nb;
+        s.k = k;
+        s.out_ord = idx->s_ord.as<uint32_t>();
+        s.out_dist = idx->s_dist.as<float>();
+        HG_TRY(launch_select(s, st));
+        hipLaunchKernelGGL(filter_each_decode_kernel, dim3(static_cast<unsigned>((cnt + 255) / 256)), dim3(256), 0, st,
+                           idx->s_ord.as<uint32_t>(), idx->s_dist.as<float>(), cnt, k, us, d_ids + q0 * k, d_dist + q0 * k);
+        HG_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
 int launch_filter_take(const int32_t *ids_in, const float *dist_in, int32_t nq, int32_t kk, int32_t k, const uint32_t *d_allow,
-                       int64_t n, int32_t *d_out_ids, float *d_out_dist, hipStream_t st) {
+                       int64_t n, int32_t *d_out_ids, float *d_out_dist, hipStream_t st, int64_t allow_stride) {
     if (nq <= 0) return 0;
     TakeArgs t;
     t.ids_in = ids_in;
@@ -2114,6 +2280,7 @@ int launch_filter_take(const int32_t *ids_in, const float *dist_in, int32_t nq, 
     t.kk = kk;
     t.k = k;
     t.allow = d_allow;
+    t.allow_stride = allow_stride;
     t.n = n;
     t.out_ids = d_out_ids;
     t.out_dist = d_out_dist;
@@ -2244,7 +2411,7 @@ int hnswgpu_destroy(hnswgpu_index *idx) {
         if (p) (void)hipFree(p);
     DevBuf *bufs[] = {&idx->s_q,   &idx->s_partial, &idx->s_ord,   &idx->s_dist, &idx->s_pairs, &idx->s_ids,
                       &idx->s_outd, &idx->s_probes,  &idx->s_stats, &idx->s_misc, &idx->s_misc2, &idx->s_vis, &idx->s_qp, &idx->s_qn, &idx->s_tile, &idx->s_grp, &idx->s_done, &idx->s_pf, &idx->s_solo, &idx->s_bk, &idx->s_heavy, &idx->s_home, &idx->s_dh, &idx->s_hord,
-                      &idx->s_fmask, &idx->s_fpass, &idx->s_fblk, &idx->s_fids, &idx->s_fdist, &idx->s_flmask, &idx->s_ffoff,
+                      &idx->s_fmask, &idx->s_fpass, &idx->s_fblk, &idx->s_fids, &idx->s_fdist, &idx->s_flmask, &idx->s_ffoff, &idx->s_feum, &idx->s_feuw, &idx->s_feqc,
                       &idx->s_pt_items, &idx->s_pt_ids, &idx->s_pt_dist, &idx->s_pt_stats, &idx->s_pt_probes};
     for (DevBuf *b : bufs) b->release();
     for (int s = 0; s < PROF_N; s++)
@@ -2454,6 +2621,43 @@ int hnswgpu_exact_knn_filtered(hnswgpu_index *idx, const float *Q, int32_t nq, i
         return call.close();
     }
     HG_TRY(filtered_scan_enqueue(idx, idx->s_q.as<float>(), nq, k, idx->s_fmask.as<uint32_t>(), p, idx->s_ids.as<int32_t>(),
+                                 idx->s_outd.as<float>(), st));
+    HG_TRY(call.stage_out(out_ids, out_dist, cnt));
+    return call.close();
+}
+
+int hnswgpu_exact_knn_filtered_each_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, const uint32_t *d_allow_each,
+                                        int32_t *d_out_ids, float *d_out_dist, void *stream) {
+    HG_TRY(check_search_args(idx, d_Q, nq, k, d_out_ids, d_out_dist));
+    HG_REQUIRE(d_allow_each, HNSWGPU_EINVAL, "allow is null");
+    if (nq == 0) return 0;
+    HG_REQUIRE(idx->n > 0, HNSWGPU_ESTATE, "empty index: use the host entry point");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_TRY(filtered_each_enqueue(idx, d_Q, nq, k, d_allow_each, d_out_ids, d_out_dist, st));
+    return call.close();
+}
+
+// One caller's staged batch, as hnswgpu_exact_knn_filtered: no part in the call combiner.
+int hnswgpu_exact_knn_filtered_each(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, const uint32_t *allow_each,
+                                    int32_t *out_ids, float *out_dist) {
+    HG_TRY(check_search_args(idx, Q, nq, k, out_ids, out_dist));
+    HG_REQUIRE(allow_each, HNSWGPU_EINVAL, "allow is null");
+    if (nq == 0) return 0;
+    const int64_t cnt = static_cast<int64_t>(nq) * k;
+    if (idx->n == 0) {
+        fill_empty(out_ids, out_dist, cnt);
+        return 0;
+    }
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_TRY(call.stage_in(Q, nq, k));
+    const size_t mbytes = sizeof(uint32_t) * static_cast<size_t>((idx->n + 31) / 32) * static_cast<size_t>(nq);
+    HG_TRY(idx->s_fmask.ensure(mbytes));
+    HG_HIP(hipMemcpyAsync(idx->s_fmask.p, allow_each, mbytes, hipMemcpyHostToDevice, st));
+    HG_TRY(filtered_each_enqueue(idx, idx->s_q.as<float>(), nq, k, idx->s_fmask.as<uint32_t>(), idx->s_ids.as<int32_t>(),
                                  idx->s_outd.as<float>(), st));
     HG_TRY(call.stage_out(out_ids, out_dist, cnt));
     return call.close();

@@ -221,6 +221,9 @@ struct hnswgpu_index {
     hg::DevBuf s_fmask, s_fpass, s_fblk, s_fids, s_fdist;
     // ... and for the IVF list scan: the mask in list order, the passing positions below every list's first
     hg::DevBuf s_flmask, s_ffoff;
+    // ... and for one mask per query: the groups' union masks, the word per union row (who of the group allows it), the
+    // selection's per-query candidate counts.  (The lists live in s_fpass, the block counts and totals in s_fblk.)
+    hg::DevBuf s_feum, s_feuw, s_feqc;
     uint32_t pf_seq = 0;  // number of the last small launch, helper or several-CU kernel (hnsw.hip: hnsw_number_launch is its one owner)
     size_t s_done_n = 0;  // counters per half of s_done (scan tails | route tails)
     uint32_t vis_gen = 0;  // last generation number handed to an HBM visited slab
@@ -518,9 +521,10 @@ void fill_empty(int32_t *ids, float *dist, int64_t cnt);  // no rows: id -1 at d
 
 // --- filtered search (filter_kernels.hpp; the allow-mask: include/hnswgpu.h) ---------------------------------------------
 int64_t mask_popcount(const uint32_t *allow, int64_t n);  // passing rows among the first n bits, on the host
-// the first k passing entries of every query's list ids_in / dist_in [nq][kk] (-1 padded), -1 / +inf padded (filter_take_kernel)
+// the first k passing entries of every query's list ids_in / dist_in [nq][kk] (-1 padded), -1 / +inf padded (filter_take_kernel);
+// allow_stride: words between the masks of two queries, 0 = one mask shared by all
 int launch_filter_take(const int32_t *ids_in, const float *dist_in, int32_t nq, int32_t kk, int32_t k, const uint32_t *d_allow,
-                       int64_t n, int32_t *d_out_ids, float *d_out_dist, hipStream_t st);
+                       int64_t n, int32_t *d_out_ids, float *d_out_dist, hipStream_t st, int64_t allow_stride = 0);
 
 // The set bits of a `len`-bit device mask as an ascending list in s_fpass (engine.hip).  p_host: the caller's count, or
 constexpr int64_t kMaskCountRead = -1;    // ... read the total back once (the calling thread waits for `st`)

@@ -10,6 +10,13 @@
 //   finish_dist: the GEMV summation order at every batch size, the bits hnswgpu_rerank and scan_kernel produce.  Ties go
 //   to the lower position = the lower row id.
 //
+//   one mask per QUERY (the *_filtered_each entry points) -- the same chain over the UNION of a query group's masks:
+//   mask_union_kernel ORs the group's masks, the three compaction launches run once for all groups (group = blockIdx.y),
+//   union_words_kernel gives every union row one word with bit j = "query j of the group allows it", and the EACH form of
+//   filtered_group_kernel fetches a union row once for the group and finishes a distance only for the queries whose bit
+//   is set; every other (row, query) entry of the dense array holds kSkipDist, a key above +inf, and
+//   filter_each_decode_kernel turns whatever the selection kept of those into -1 / +inf BY THE BIT, not by the value.
+//
 //   many rows pass -- the traversal runs untouched for min(ef, 1024) results and filter_take_kernel keeps the first k
 //   passing entries of each query's result list, in list order.
 //
@@ -39,7 +46,22 @@ struct MaskArgs {
     int32_t *pass_ids;          // [cap]
     int64_t cap;                // entries pass_ids holds (the count the scan produced)
     unsigned long long *total;  // [1]: passing rows
+    // several masks in one launch, mask g = blockIdx.y (all 0: the one mask of today's callers)
+    int64_t allow_stride;  // words between two masks
+    int64_t blk_stride;    // entries of blk between two masks
+    int64_t pass_stride;   // entries of pass_ids between two lists
+    int64_t total_stride;  // entries of total between two masks (0 or 1)
 };
+
+// the arguments of mask blockIdx.y
+__device__ __forceinline__ MaskArgs mask_of_group(MaskArgs a) {
+    const int64_t g = blockIdx.y;
+    a.allow += g * a.allow_stride;
+    a.blk += g * a.blk_stride;
+    a.pass_ids += g * a.pass_stride;
+    a.total += g * a.total_stride;
+    return a;
+}
 
 // word w of the mask as the kernels see it: nothing past the mask, the last word trimmed to n
 __device__ __forceinline__ uint32_t mask_word(const MaskArgs &a, int64_t w) {
@@ -74,7 +96,8 @@ __device__ __forceinline__ uint32_t wg_exclusive_scan(uint32_t v, uint32_t *ws, 
     return before + inc - v;
 }
 
-__global__ __launch_bounds__(kMaskThreads) void mask_count_kernel(MaskArgs a) {
+__global__ __launch_bounds__(kMaskThreads) void mask_count_kernel(MaskArgs a0) {
+    const MaskArgs a = mask_of_group(a0);
     __shared__ uint32_t ws[kMaskThreads / kWave];
     const int64_t w0 = static_cast<int64_t>(blockIdx.x) * kMaskWordsPerWG + threadIdx.x * kMaskWordsPerThread;
     uint32_t c = 0;
@@ -86,7 +109,8 @@ __global__ __launch_bounds__(kMaskThreads) void mask_count_kernel(MaskArgs a) {
 }
 
 // one workgroup: blk[] -> its exclusive prefix sums, *total = the sum
-__global__ __launch_bounds__(kMaskScanThreads) void mask_scan_kernel(MaskArgs a) {
+__global__ __launch_bounds__(kMaskScanThreads) void mask_scan_kernel(MaskArgs a0) {
+    const MaskArgs a = mask_of_group(a0);
     __shared__ uint32_t ws[kMaskScanThreads / kWave];
     unsigned long long carry = 0;
     for (int i0 = 0; i0 < a.nblk; i0 += kMaskScanThreads) {
@@ -100,7 +124,8 @@ __global__ __launch_bounds__(kMaskScanThreads) void mask_scan_kernel(MaskArgs a)
     if (threadIdx.x == 0) *a.total = carry;
 }
 
-__global__ __launch_bounds__(kMaskThreads) void mask_scatter_kernel(MaskArgs a) {
+__global__ __launch_bounds__(kMaskThreads) void mask_scatter_kernel(MaskArgs a0) {
+    const MaskArgs a = mask_of_group(a0);
     __shared__ uint32_t ws[kMaskThreads / kWave];
     const int64_t w0 = static_cast<int64_t>(blockIdx.x) * kMaskWordsPerWG + threadIdx.x * kMaskWordsPerThread;
     uint32_t m[kMaskWordsPerThread];
@@ -141,6 +166,75 @@ __global__ void filter_decode_kernel(const uint32_t *ord, int64_t cnt, const int
     out_ids[i] = o < p ? pass_ids[o] : -1;  // 0xffffffff: padding
 }
 
+// ---- one mask per query: the union of a query group's masks, and who of the group allows a union row ----------------------
+// A dense entry of a (union row, query) pair whose bit is clear.  As a key (make_key) it lies above +inf, so it loses against
+// every passing entry of its query, one at distance +inf included; whether a selected entry IS one is decided by the bit.
+constexpr uint32_t kSkipDist = 0x7fffffffu;
+
+struct UnionArgs {
+    const uint32_t *allow_each;  // [nq][nwords]
+    int64_t n, nwords;
+    int32_t nq, tq;
+    uint32_t *um;                       // [ngroups][nwords]: OR of the group's masks, last word trimmed to n
+    const int32_t *upass;               // [ngroups][pstride]: ascending set bits of um[g] (mask_scatter_kernel)
+    const unsigned long long *up;       // [ngroups]: their number
+    uint32_t *uw;                       // [ngroups][pstride]: bit j = allow bit of query g * tq + j for row upass[g][i]
+    int64_t pstride;
+    int32_t *q_cnt;                     // [nq]: up[group of q], what select_topk_kernel walks
+};
+
+__global__ __launch_bounds__(kMaskThreads) void mask_union_kernel(UnionArgs a) {
+    const int64_t w = static_cast<int64_t>(blockIdx.x) * kMaskThreads + threadIdx.x;
+    const int g = blockIdx.y;
+    if (w >= a.nwords) return;
+    const int q0 = g * a.tq;
+    const int cnt = a.nq - q0 < a.tq ? a.nq - q0 : a.tq;
+    uint32_t m = 0;
+    for (int j = 0; j < cnt; j++) m |= a.allow_each[static_cast<int64_t>(q0 + j) * a.nwords + w];
+    const int tail = static_cast<int>(a.n & 31);
+    if (w == a.nwords - 1 && tail) m &= (1u << tail) - 1u;
+    a.um[static_cast<int64_t>(g) * a.nwords + w] = m;
+}
+
+// (neighbouring threads read neighbouring union rows: mostly the same word of every mask)
+__global__ __launch_bounds__(kMaskThreads) void union_words_kernel(UnionArgs a) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * kMaskThreads + threadIdx.x;
+    const int g = blockIdx.y;
+    const int64_t p = static_cast<int64_t>(a.up[g]) < a.pstride ? static_cast<int64_t>(a.up[g]) : a.pstride;
+    if (i >= p) return;
+    const int64_t row = a.upass[static_cast<int64_t>(g) * a.pstride + i];
+    const int q0 = g * a.tq;
+    const int cnt = a.nq - q0 < a.tq ? a.nq - q0 : a.tq;
+    uint32_t word = 0;
+    if (row >= 0 && row < a.n)
+        for (int j = 0; j < cnt; j++)
+            word |= ((a.allow_each[static_cast<int64_t>(q0 + j) * a.nwords + (row >> 5)] >> (row & 31)) & 1u) << j;
+    a.uw[static_cast<int64_t>(g) * a.pstride + i] = word;
+}
+
+__global__ void union_qcnt_kernel(UnionArgs a) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= a.nq) return;
+    const unsigned long long p = a.up[q / a.tq];
+    a.q_cnt[q] = static_cast<int32_t>(p < static_cast<unsigned long long>(a.pstride) ? p : a.pstride);
+}
+
+// position in the group's union list -> row id and distance, for the cnt = nq * k selected entries of a slice.  An entry
+// whose query does not allow the row (uw) is padding, whatever its distance reads.
+__global__ void filter_each_decode_kernel(const uint32_t *ord, const float *sel_dist, int64_t cnt, int32_t k, UnionArgs a,
+                                          int32_t *out_ids, float *out_dist) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= cnt) return;
+    const int q = static_cast<int>(i / k);
+    const int g = q / a.tq, j = q % a.tq;
+    const uint32_t o = ord[i];
+    const int64_t p = static_cast<int64_t>(a.up[g]) < a.pstride ? static_cast<int64_t>(a.up[g]) : a.pstride;
+    const int64_t at = static_cast<int64_t>(g) * a.pstride + (o < p ? o : 0);
+    const bool ok = o < p && ((a.uw[at] >> j) & 1u);
+    out_ids[i] = ok ? a.upass[at] : -1;
+    out_dist[i] = ok ? sel_dist[i] : __uint_as_float(0x7f800000u);
+}
+
 // ---- the gathered register-row group scan ------------------------------------------------------------------------
 // l2_group_kernel (l2_kernels.hpp) over the rows pass_ids names: a workgroup keeps a group of queries resident in LDS, every
 // wave holds RB rows in registers and walks the group's queries over them.  Row b of a step is pass_ids[base + b]; lane b
@@ -160,6 +254,10 @@ struct FilteredArgs {
     int64_t p;             // passing rows (>= 1)
     int64_t chunk_rows;    // positions of the passing list per workgroup
     float *out;            // dense[q * p + position]
+    // EACH (one mask per query): pass_ids is [ngroups][pstride], group g's union list; p is not used
+    const uint32_t *uw;            // [ngroups][pstride]: who of the group allows the row (union_words_kernel)
+    const unsigned long long *up;  // [ngroups]: entries of group g's list
+    int64_t pstride;               // also the row stride of `out`
 };
 
 // 32 queries up to ld 1024, 16 up to 2048, 8 up to 3072: 128 KiB / 128 KiB / 96 KiB of the CU's 160 KiB
@@ -169,7 +267,10 @@ __host__ inline size_t filtered_group_lds_bytes(int64_t ld) {
     return sizeof(float) * tq * static_cast<size_t>(ld) + sizeof(float) * tq;
 }
 
-template <int NCH, int RB, bool L2M>
+// EACH: the list is the group's own (the union of its queries' masks), lane b loads the row's word beside id and norm, and a
+// query is walked over a step's RB rows only if one of them carries its bit (anyw: wave-uniform); the store is the distance
+// where the row's bit is set and kSkipDist elsewhere, so every entry of dense[q][0 .. up[g]) is written.
+template <int NCH, int RB, bool L2M, bool EACH = false>
 __global__ __launch_bounds__(kTileThreads) void filtered_group_kernel(FilteredArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int nvec = static_cast<int>(a.ld / 4);
@@ -182,7 +283,17 @@ __global__ __launch_bounds__(kTileThreads) void filtered_group_kernel(FilteredAr
     const int g = blockIdx.x % a.ngroups;
     const int64_t chunk = blockIdx.x / a.ngroups;
     const int64_t r0 = chunk * a.chunk_rows;
-    const int64_t r1 = r0 + a.chunk_rows < a.p ? r0 + a.chunk_rows : a.p;
+    int64_t p = a.p, ostride = a.p;
+    const int32_t *pass = a.pass_ids;
+    const uint32_t *uw = nullptr;
+    if constexpr (EACH) {
+        const int64_t have = static_cast<int64_t>(a.up[g]);
+        p = have < a.pstride ? have : a.pstride;
+        ostride = a.pstride;
+        pass = a.pass_ids + g * a.pstride;
+        uw = a.uw + g * a.pstride;
+    }
+    const int64_t r1 = r0 + a.chunk_rows < p ? r0 + a.chunk_rows : p;
     const int q0 = g * a.tq;
     const int cnt = a.nq - q0 < a.tq ? a.nq - q0 : a.tq;
     if (r0 >= r1 || cnt <= 0) return;
@@ -212,14 +323,24 @@ __global__ __launch_bounds__(kTileThreads) void filtered_group_kernel(FilteredAr
         float4 r[RB][NCH];
         // lane b (and every lane beyond RB, as row RB - 1): the id of row b, clamped into the chunk, and its norm
         const int64_t mypos = base + (lane < RB ? lane : RB - 1);
-        const int32_t myid = a.pass_ids[mypos < r1 ? mypos : r1 - 1];
+        const int32_t myid = pass[mypos < r1 ? mypos : r1 - 1];
         const float myrn = (!L2M && a.metric == METRIC_COS) ? a.row_norms[myid] : 0.0f;
+        uint32_t myw = 0, anyw = 0;
+        if constexpr (EACH) myw = mypos < r1 ? uw[mypos] : 0u;  // (a row past the chunk's end: nobody's)
 #pragma unroll
         for (int b = 0; b < RB; b++) {
             const int64_t row = __builtin_amdgcn_readlane(myid, b);
             load_row<NCH>(r[b], a.rows + row * a.ld, nvec, lane, true);
+            if constexpr (EACH) anyw |= static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(myw), b));
         }
         for (int q = 0; q < cnt; q++) {
+            if constexpr (EACH) {
+                if (!((anyw >> q) & 1u)) {  // wave-uniform: none of the RB rows is this query's
+                    if (lane < RB && base + lane < r1)
+                        a.out[static_cast<int64_t>(q0 + q) * ostride + (base + lane)] = __uint_as_float(kSkipDist);
+                    continue;
+                }
+            }
             const float qn = L2M ? 0.0f : qn_s[q];
             float4 qv[NCH];
 #pragma unroll
@@ -231,8 +352,10 @@ __global__ __launch_bounds__(kTileThreads) void filtered_group_kernel(FilteredAr
 #pragma unroll
             for (int b = 0; b < RB; b++) s[b] = lane_partial<NCH, L2M>(qv, r[b]);
             const float mine = rows_sum_to_lane<RB>(s, lane);  // lane b: row b's sum
-            if (lane < RB && base + lane < r1)
-                a.out[static_cast<int64_t>(q0 + q) * a.p + (base + lane)] = L2M ? __builtin_sqrtf(mine) : finish_dist(a.metric, mine, qn, myrn);
+            if (lane < RB && base + lane < r1) {
+                const float d = L2M ? __builtin_sqrtf(mine) : finish_dist(a.metric, mine, qn, myrn);
+                a.out[static_cast<int64_t>(q0 + q) * ostride + (base + lane)] = (!EACH || ((myw >> q) & 1u)) ? d : __uint_as_float(kSkipDist);
+            }
         }
     }
 }
@@ -362,6 +485,7 @@ struct TakeArgs {
     const float *dist_in;
     int32_t nq, kk, k;
     const uint32_t *allow;
+    int64_t allow_stride;  // words between the masks of two queries; 0: one mask shared by all
     int64_t n;
     int32_t *out_ids;  // [nq][k]
     float *out_dist;
@@ -376,6 +500,7 @@ __global__ __launch_bounds__(kWG) void filter_take_kernel(TakeArgs a) {
     const float *din = a.dist_in + static_cast<int64_t>(q) * a.kk;
     int32_t *oi = a.out_ids + static_cast<int64_t>(q) * a.k;
     float *od = a.out_dist + static_cast<int64_t>(q) * a.k;
+    const uint32_t *allow = a.allow + static_cast<int64_t>(q) * a.allow_stride;
     int taken = 0;
     for (int base = 0; base < a.kk && taken < a.k; base += kWave) {
         const int i = base + lane;
@@ -383,7 +508,7 @@ __global__ __launch_bounds__(kWG) void filter_take_kernel(TakeArgs a) {
         const int32_t id = in[ic];
         const float d = din[ic];
         const bool valid = i < a.kk && id >= 0 && id < a.n;
-        const uint32_t w = a.allow[valid ? id >> 5 : 0];
+        const uint32_t w = allow[valid ? id >> 5 : 0];
         const bool ok = valid && ((w >> (id & 31)) & 1u);
         const unsigned long long m = __ballot(ok);
         const int slot = taken + __popcll(m & ((1ull << lane) - 1ull));

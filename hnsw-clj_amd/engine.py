@@ -55,6 +55,28 @@ def pack_mask(allow, n):
     return packed.view("<u4").astype(np.uint32, copy=False)
 
 
+def pack_masks(allows, n):
+    """One allow-mask per query (the *_filtered_each calls): ``allows`` is a sequence of what pack_mask takes -- bool arrays of
+    length n or iterables of row ids -- and the result is the [nq][(n + 31) // 32] uint32 array whose row q is
+    pack_mask(allows[q], n)."""
+    n = int(n)
+    if isinstance(allows, np.ndarray) and allows.dtype == np.bool_ and allows.ndim != 2:
+        raise ValueError("a bool array of masks must be (nq, %d), got %s" % (n, allows.shape))
+    rows = [pack_mask(a, n) for a in allows]
+    out = np.zeros((len(rows), (n + 31) // 32), np.uint32)
+    for q, r in enumerate(rows):
+        out[q] = r
+    return out
+
+
+def _mask_rows(allow_each, n, nq):
+    """Packed masks (pack_masks) checked against the index size and the batch."""
+    a = np.ascontiguousarray(allow_each)
+    if a.dtype != np.uint32 or a.shape != (nq, (n + 31) // 32):
+        raise ValueError("allow_each must be the (%d, %d) uint32 words of pack_masks(..., %d)" % (nq, (n + 31) // 32, n))
+    return a
+
+
 def _mask_words(allow, n):
     """A packed mask (pack_mask) checked against the index size."""
     a = np.ascontiguousarray(allow)
@@ -282,6 +304,16 @@ class Index:
         check(lib().hnswgpu_exact_knn_filtered(self._h, _p(Q), len(Q), k, _p(allow), _p(ids), _p(d)))
         return ids, d
 
+    def exact_knn_filtered_each(self, Q, k, allow_each):
+        """hnswgpu_exact_knn_filtered_each: row q is exact_knn_filtered(Q[q:q + 1], k, allow_each[q]) -- one mask per query
+        (pack_masks), one chain of launches for the batch; a group of queries fetches the union of its passing rows once."""
+        Q = _queries(Q, self.dim)
+        allow_each = _mask_rows(allow_each, self.n, len(Q))
+        ids = np.empty((len(Q), k), np.int32)
+        d = np.empty((len(Q), k), np.float32)
+        check(lib().hnswgpu_exact_knn_filtered_each(self._h, _p(Q), len(Q), k, _p(allow_each), _p(ids), _p(d)))
+        return ids, d
+
     def rerank(self, Q, cand, k):
         """Per query: exact distances to its candidate rows cand[q] (-1 = skip), stable sort, first k."""
         Q = _queries(Q, self.dim)
@@ -411,6 +443,17 @@ class Index:
         stats = np.zeros((len(Q), 2), np.int64) if want_stats else None
         check(lib().hnswgpu_hnsw_search_filtered(self._h, _p(Q), len(Q), k, int(ef or 0), _p(allow), _p(ids), _p(d),
                                                  _p(stats)))
+        return (ids, d, stats) if want_stats else (ids, d)
+
+    def hnsw_search_filtered_each(self, Q, k, allow_each, ef=0, want_stats=False):
+        """hnswgpu_hnsw_search_filtered_each: hnsw_search_filtered with one mask per query (pack_masks) in one launch."""
+        Q = _queries(Q, self.dim)
+        allow_each = _mask_rows(allow_each, self.n, len(Q))
+        ids = np.empty((len(Q), k), np.int32)
+        d = np.empty((len(Q), k), np.float32)
+        stats = np.zeros((len(Q), 2), np.int64) if want_stats else None
+        check(lib().hnswgpu_hnsw_search_filtered_each(self._h, _p(Q), len(Q), k, int(ef or 0), _p(allow_each), _p(ids), _p(d),
+                                                      _p(stats)))
         return (ids, d, stats) if want_stats else (ids, d)
 
     # -- IVF
@@ -581,6 +624,29 @@ class Index:
         check(lib().hnswgpu_hnsw_search_filtered_dev(self._h, Q.data_ptr(), Q.shape[0], k, int(ef or 0), allow.data_ptr(),
                                                      ids.data_ptr(), d.data_ptr(),
                                                      stats.data_ptr() if stats is not None else None, st))
+        return ids, d
+
+    def _dev_masks(self, allow_each, Q):
+        """Packed masks as a device tensor of [nq][(n + 31) // 32] 32-bit words (pack_masks(...).view(np.int32))."""
+        assert allow_each.is_cuda and allow_each.device == Q.device and allow_each.element_size() == 4
+        assert tuple(allow_each.shape) == (Q.shape[0], (self.n + 31) // 32), "allow_each must be (nq, (n + 31) // 32) words"
+        return allow_each.contiguous()
+
+    def exact_knn_filtered_each_dev(self, Q, k, allow_each, out=None):
+        """hnswgpu_exact_knn_filtered_each_dev on torch's current stream (waits for it once, for the groups' passing counts)."""
+        Q, ids, d, st = self._dev_args(Q, k, out)
+        allow_each = self._dev_masks(allow_each, Q)
+        check(lib().hnswgpu_exact_knn_filtered_each_dev(self._h, Q.data_ptr(), Q.shape[0], k, allow_each.data_ptr(),
+                                                        ids.data_ptr(), d.data_ptr(), st))
+        return ids, d
+
+    def hnsw_search_filtered_each_dev(self, Q, k, allow_each, ef=0, out=None, stats=None):
+        """hnswgpu_hnsw_search_filtered_each_dev on torch's current stream: enqueues only."""
+        Q, ids, d, st = self._dev_args(Q, k, out)
+        allow_each = self._dev_masks(allow_each, Q)
+        check(lib().hnswgpu_hnsw_search_filtered_each_dev(self._h, Q.data_ptr(), Q.shape[0], k, int(ef or 0),
+                                                          allow_each.data_ptr(), ids.data_ptr(), d.data_ptr(),
+                                                          stats.data_ptr() if stats is not None else None, st))
         return ids, d
 
     def ivf_search_filtered_dev(self, Q, k, nprobe, allow, out=None):

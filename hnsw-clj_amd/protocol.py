@@ -57,6 +57,10 @@ class GpuHnswIndex(ANNIndex, BatchSearchIndex, PersistableIndex, FilterableIndex
     def search_knn_filtered_star(self, query, k, filter_fn, mode=None):
         return ultra_fast.search_knn_filtered(self.graph, query, k, filter_fn)
 
+    def search_batch_filtered(self, queries, k, filter_fns, mode=None):
+        """search_knn_filtered_star for a batch, one predicate per query, in one chain of launches (not in the reference)."""
+        return ultra_fast.search_batch_filtered_each(self.graph, queries, k, filter_fns)
+
     def save_index_star(self, filepath):
         index_io.save_index(self.graph, filepath)
         return True

@@ -184,6 +184,55 @@ def search_batch_filtered(graph, queries, k, filter_fn, ef=None):
     return [_format(graph, ids[i], d[i]) for i in range(len(queries))]
 
 
+def search_batch_filtered_each(graph, queries, k, filter_fns, ef=None):
+    """search_batch_filtered with one predicate (or bool array) PER QUERY -- the reference's many threads, each with one
+    query and its own filter-fn, as one batch: row q equals ``search_knn_filtered(graph, queries[q], k, filter_fns[q], ef)``.
+    The same object, or equal bits, is evaluated and packed once.  filtered_plan is applied per query: the "scan" queries go
+    in one exact_knn_filtered_each call, ordered so that equal masks are adjacent (a query group then shares its rows), the
+    "graph" queries in one hnsw_search_filtered_each call per distinct ef' (never rounded); the original order is restored.
+    A batch whose filters are all one mask takes search_batch_filtered's single-mask call."""
+    queries = np.asarray(queries, np.float32)
+    if queries.ndim == 1:
+        queries = queries[None, :]
+    if len(filter_fns) != len(queries):
+        raise ValueError("one filter per query: %d filters for %d queries" % (len(filter_fns), len(queries)))
+    if len(queries) == 0:
+        return []
+    n = graph.index.n
+    if n == 0:
+        return [[] for _ in queries]
+    masks, by_obj, by_bits, which = [], {}, {}, []   # distinct masks: (bits, packed, p)
+    for f in filter_fns:
+        m = by_obj.get(id(f))
+        if m is None:
+            bits = _allow_bits(graph, f)
+            key = bits.tobytes()
+            m = by_bits.get(key)
+            if m is None:
+                m = by_bits[key] = len(masks)
+                masks.append((bits, engine.pack_mask(bits, n), int(bits.sum())))
+            by_obj[id(f)] = m
+        which.append(m)
+    if len(masks) == 1:
+        return search_batch_filtered(graph, queries, k, masks[0][0], ef)
+    plans = [filtered_plan(n, p, k, ef) for _, _, p in masks]
+    calls = {}                                       # ("scan",) or ("graph", ef') -> query numbers
+    for q, m in enumerate(which):
+        plan, ef2 = plans[m]
+        calls.setdefault(("scan",) if plan == "scan" else ("graph", ef2), []).append(q)
+    ids = np.empty((len(queries), int(k)), np.int32)
+    d = np.empty((len(queries), int(k)), np.float32)
+    for key, qs in sorted(calls.items()):
+        qs = sorted(qs, key=lambda q: (which[q], q))  # equal masks adjacent
+        rows = np.stack([masks[which[q]][1] for q in qs])
+        if key[0] == "scan":
+            gi, gd = graph.index.exact_knn_filtered_each(queries[qs], int(k), rows)
+        else:
+            gi, gd = graph.index.hnsw_search_filtered_each(queries[qs], int(k), rows, key[1])
+        ids[qs], d[qs] = gi, gd
+    return [_format(graph, ids[i], d[i]) for i in range(len(queries))]
+
+
 def search_knn_filtered(graph, query_vec, k, filter_fn, ef=None):
     """search_batch_filtered for one query: a list of ``{"id", "distance"}`` ascending, fewer than k when fewer pass."""
     if graph.index.n == 0:

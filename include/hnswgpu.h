@@ -357,6 +357,38 @@ int hnswgpu_hnsw_search_filtered(hnswgpu_index *idx, const float *Q, int32_t nq,
 int hnswgpu_hnsw_search_filtered_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t ef,
                                      const uint32_t *d_allow, int32_t *d_out_ids, float *d_out_dist, int64_t *d_stats,
                                      void *stream);
+/* One allow-mask per QUERY of a batch: the reference's callers are many threads, each with one query and its own filter-fn
+ *   (protocol.clj:34-41), and a service with per-user visibility brings one predicate per query.
+ *   allow_each: [nq][W] words, W = (n + 31) / 32, row-major; row q is query q's mask in exactly the format and meaning of
+ *   `allow` above (row i may be returned for q iff its bit is set in row q; bits at positions >= n are ignored; an argument,
+ *   never handle state).  A null mask is -1, nq == 0 is 0, n == 0: the host entries fill the padding; k <= 1024; a handle
+ *   that holds a forest is -3, as for every search.
+ * hnswgpu_exact_knn_filtered_each: result row q is, in ids and distance bits, what
+ *   hnswgpu_exact_knn_filtered(idx, Q + q * dim, 1, k, allow_each + q * W, ...) returns: gather order at every batch size,
+ *   ties to the lower row id, -1 / +inf padding where fewer than k of query q's OWN rows pass (however many pass for other
+ *   queries of the batch), and never a row whose bit is clear for q.  Queries are served in the groups of the single-mask
+ *   call (32 / 16 / 8 consecutive queries by row length); a group walks the UNION of its queries' passing rows, fetches a
+ *   union row once and finishes a distance only for the queries that allow it -- so callers that sort a batch by mask
+ *   (equal masks adjacent) get the single-mask call's cost, and no batch fetches more than nq single calls would.
+ *   The _dev entry reads the groups' passing counts (8 bytes per query group, one copy) back once and the calling thread
+ *   waits for `stream` there, as hnswgpu_exact_knn_filtered_dev does.  The dense scratch of a slice of groups is bounded
+ *   by HNSWGPU_TUNE_FILTER_EACH_MB.
+ * hnswgpu_hnsw_search_filtered_each: the traversal of hnswgpu_hnsw_search, untouched; result row q equals
+ *   hnswgpu_hnsw_search_filtered with mask q; stats are the unfiltered traversal's.  The _dev entry only enqueues.
+ * The host entries stage one caller's batch and take no part in the call combiner.
+ * Out of scope: one mask per query through the IVF list scan, an _each form of hnswgpu_ivf_search_filtered -- a list-order
+ *   mask per query is nq x n bits of scratch without a read-back, which needs its own design; combining concurrent
+ *   single-query filtered callers into one _each launch (it would change the path of the existing entry points); forests,
+ *   groups and shards. */
+int hnswgpu_exact_knn_filtered_each(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, const uint32_t *allow_each,
+                                    int32_t *out_ids, float *out_dist);
+int hnswgpu_exact_knn_filtered_each_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k,
+                                        const uint32_t *d_allow_each, int32_t *d_out_ids, float *d_out_dist, void *stream);
+int hnswgpu_hnsw_search_filtered_each(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t ef,
+                                      const uint32_t *allow_each, int32_t *out_ids, float *out_dist, int64_t *stats);
+int hnswgpu_hnsw_search_filtered_each_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t ef,
+                                          const uint32_t *d_allow_each, int32_t *d_out_ids, float *d_out_dist,
+                                          int64_t *d_stats, void *stream);
 /* hnswgpu_ivf_search_filtered (search-ivf-flat, src/hnsw/ann/partition/ivf_flat.clj:236-294, behind
  *   FilterableIndex/search-knn-filtered*, protocol.clj:34-41): the allow-mask through the list scan, instead of
  *   default-filtered-search's "search 3k, drop, keep k" (protocol.clj:97-102), which returns about 3k * p / n rows when p of n
@@ -411,7 +443,8 @@ int hnswgpu_set_profiling(hnswgpu_index *idx, int32_t on);
 #define HNSWGPU_COUNT_HNSW_WAVE 5         /* large HNSW launches on the one-wave-per-query kernel with the admission buffer (wave_kernels.hpp) */
 #define HNSWGPU_COUNT_ROUTE_TAIL_WAVES 6   /* IVF routing tails launched with one wave per query (ivf_route_tail_wave_kernel) */
 #define HNSWGPU_COUNT_HNSW_ORDERED 7       /* ... of those, launches that dealt their queries in the order of their nearest pivot row (HNSWGPU_TUNE_HNSW_ORDER) */
-#define HNSWGPU_COUNT_N 8
+#define HNSWGPU_COUNT_FILTERED_EACH_GROUPS 8 /* query groups served by the one-mask-per-query group scan (filtered_group_kernel<.., EACH>), added per launch */
+#define HNSWGPU_COUNT_N 9
 int hnswgpu_launch_count(int32_t which, int64_t *out);
 /* The HNSW traversal decides most neighbours (those that cannot enter a full result list, ultra_fast.clj:195-198) from
  * an int8 copy of the rows: a lower bound of the distance that is already >= the list's worst needs no f32 row
@@ -549,7 +582,8 @@ int hnswgpu_hnsw_last_order(hnswgpu_index *idx, int32_t *order, int32_t *keys, i
 #define HNSWGPU_TUNE_BUILD_KEEP_ROWS 59 /* 0 = the builder's heuristic selection fetches the already selected rows again for every candidate instead of keeping them in registers (A/B; the graph does not depend on it) */
 #define HNSWGPU_TUNE_QUERY_WAVES 60 /* the per-query kernels of large IVF batches (home-list selection) with one WAVE per query, four queries per workgroup, instead of a workgroup per query: -1 from 2048 queries, 0 never, 1 wherever a wave can serve a query (k <= 64) */
 #define HNSWGPU_TUNE_HNSW_ORDER 61 /* launches of the one-wave-per-query kernel serve their queries in the order of their nearest pivot row (min(256, n) base rows at a fixed stride, judged on the int8 rows), dealt so that neighbouring queries run on one XCD at one time -- a hint for the L2s, results never depend on it: 1 = search launches on handles with int8 rows from a batch size (default), 0 = never (A/B), 2 = every such launch (tests) */
-#define HNSWGPU_TUNE_COUNT 62
+#define HNSWGPU_TUNE_FILTER_EACH_MB 62 /* hnswgpu_exact_knn_filtered_each: bound of the dense distance scratch of one slice of query groups, in MiB (default 2048, the single-mask call's bound; at least one group per slice) */
+#define HNSWGPU_TUNE_COUNT 63
 int hnswgpu_set_tuning(int32_t key, int64_t value);
 int hnswgpu_get_tuning(int32_t key, int64_t *value, int32_t *is_set);
 
