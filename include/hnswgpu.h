@@ -563,7 +563,7 @@ int hnswgpu_hnsw_last_order(hnswgpu_index *idx, int32_t *order, int32_t *keys, i
 #define HNSWGPU_TUNE_PF_EVAL 40 /* 0 = the helpers only warm the L2 (A/B) */
 #define HNSWGPU_TUNE_ZEROCOPY 41 /* 0 = small synchronous HNSW calls stage through copies instead of mapped pinned memory (A/B) */
 #define HNSWGPU_TUNE_BUILD_TIMING 42 /* 1 = hnswgpu_hnsw_build prints where its time went to stderr */
-#define HNSWGPU_TUNE_BUILD_BATCH 43 /* largest insertion batch of hnswgpu_hnsw_build (default 16384; a batch never exceeds 1/8 of the graph it is searched against) */
+#define HNSWGPU_TUNE_BUILD_BATCH 43 /* largest insertion batch of hnswgpu_hnsw_build / hnswgpu_hnsw_add (default and cap 16384, at least 1).  The batch-size rule: with `done` rows in the graph the next batch holds min(BUILD_BATCH, max(1, done / 8), 2048 + done / 64, rows left) rows (integer divisions) -- never more than 1/8 of the graph it is searched against, and from 18,725 rows on 2048 + done / 64.  A build starts at done = 1 (row 0 is the entry point), hnswgpu_hnsw_add at the rows the index holds.  The rows of a batch are searched against the graph as it stood when the batch began, so the graph depends on this value (1 = one row per batch); HNSWGPU_BUILD_SEQUENTIAL ignores it */
 #define HNSWGPU_TUNE_STREAM_HOME 44 /* the home-list pass of large IVF batches (every list once through the matrix cores in half precision for all the queries it is nearest to): -1 from 512 queries and half a query per list, 0 never, 1 whenever the batch is served in the order of its nearest lists */
 #define HNSWGPU_TUNE_HOME_CHUNK 45 /* rows per work item of the home-list pass (a multiple of 64; 0 = auto) */
 #define HNSWGPU_TUNE_HOME_DEPTH 46 /* operand loads in flight per wave of the home-list pass: 4 / 8 / 12 / 16 / 24, the largest that divides the 32-element steps of a row and does not exceed this (default 12) */

@@ -898,6 +898,16 @@ static void list_remove(int32_t *a, int32_t *cnt, int32_t x) {
         }
 }
 
+/* a row's level: the next draw of the build's java.util.Random */
+static int draw_level(jrandom *rng) {
+    const double ml = 1.0 / log(2.0);
+    double u = jr_next_double(rng);
+    int lv = (int)(ml * (-log(u))); /* (long (* ml (- (Math/log U)))) :143-147 */
+    if (u == 0.0) lv = 64;
+    if (lv > 30) lv = 30; /* the engine's cap (hnsw.hip: draw_levels); 2^-31 per row */
+    return lv;
+}
+
 int orc_hnsw_build_ex(const float *base, int64_t n, int dim, int metric, int mode, int M, int efc, int64_t seed,
                       int flags, int32_t *levels_out, int32_t *l0_adj_out, int64_t *up_off_out, int32_t *up_adj_out,
                       int64_t up_adj_cap, int32_t *entry_out, int32_t *max_level_out, int64_t *counters) {
@@ -911,15 +921,11 @@ int orc_hnsw_build_ex(const float *base, int64_t n, int dim, int metric, int mod
     b.M0 = 2 * M;
     jrandom rng;
     jr_init(&rng, seed);
-    double ml = 1.0 / log(2.0);
     b.levels = levels_out;
     b.up_off = up_off_out;
     int64_t tot = 0;
     for (int64_t i = 0; i < n; i++) {
-        double u = jr_next_double(&rng);
-        int lv = (int)(ml * (-log(u))); /* (long (* ml (- (Math/log U)))) :143-147 */
-        if (u == 0.0) lv = 64;
-        if (lv > 30) lv = 30; /* the engine's cap (hnsw.hip: draw_levels); 2^-31 per row */
+        int lv = draw_level(&rng);
         b.levels[i] = lv;
         b.up_off[i] = tot;
         tot += lv;
@@ -1105,6 +1111,446 @@ int orc_hnsw_build(const float *base, int64_t n, int dim, int metric, int mode, 
                    int32_t *up_adj_out, int64_t up_adj_cap, int32_t *entry_out, int32_t *max_level_out) {
     return orc_hnsw_build_ex(base, n, dim, metric, mode, M, efc, seed, farthest_quirk ? ORC_BUILD_FARTHEST : 0, levels_out,
                              l0_adj_out, up_off_out, up_adj_out, up_adj_cap, entry_out, max_level_out, NULL);
+}
+
+/* ------------------------------------------------------------------------------------------ */
+/* 4a. The engine's BATCHED build, restated (hnsw-clj_amd/csrc/hnsw.hip: insert_batches).        */
+/*                                                                                              */
+/* Not the reference's order: the engine's own, stated in DESIGN.md.  Rows join in batches whose sizes the caller gives   */
+/* (tests/hnsw_build_model.py: batch_schedule restates the engine's rule).  Per batch:                                    */
+/*   1. every row of the batch is searched against the graph AS IT STOOD WHEN THE BATCH BEGAN (rows of a batch do not see  */
+/*      each other): the ORC_BUILD_DESCEND walk -- ef = 1 from the entry's level down to layer 1, the single nearest node  */
+/*      of each layer min(level, top) .. 1 kept --, then ef_construction at layer 0.  Closest-m takes the first            */
+/*      min(2M, ef) results, the heuristic selects 2M from all ef candidates (ORC_BUILD_EXTEND applies here only).         */
+/*   2. the batch is linked in row order, a row's layers top down, a layer's links in selection order.  Every edge carries */
+/*      the distance its search found (both directions: the arithmetic is symmetric).                                      */
+/*      closest-m (HostGraph::add_edge): a duplicate is ignored; an over-full list keeps its m closest by a stable sort on */
+/*      the stored distances.                                                                                              */
+/*      heuristic (append_edge + Pruner::run_batched): a reverse edge into a full list is PENDING; per (target, layer) the */
+/*      list as it stands after all appends plus its pending edges, ascending by (distance, id), is re-selected to at most */
+/*      m without extend; with ORC_BUILD_SYMMETRIC every candidate not kept loses its edge to the target, the removals     */
+/*      applied once every list of the batch has been replaced.                                                            */
+/*   3. entry point and top level move only now, row by row.                                                               */
+/* A start graph over the first n0 rows (levels0 != NULL) models hnswgpu_hnsw_add: its lists are adopted in their order,   */
+/* their edge distances recomputed as pair_dist(owner, neighbour).  Without one, row 0 is the first entry point and the     */
+/* batches cover rows 1 .. n - 1.                                                                                          */
+/* counters[0] prunings of over-full lists (closest-m) / selection tasks (heuristic)                                       */
+/*         [1] tasks with >= 2 pending edges          [2] symmetric removals that found their edge                         */
+/*         [3] rows whose level exceeded the top at batch start          [4] entry changes                                  */
+/*         [5] entry changes in batches of more than one row             [6] most prunings / tasks of one batch             */
+/*         [7] first prunings / tasks of lists adopted from the start graph                                                */
+/*         [8] ... of which the adopted list was full but not ascending by distance                                        */
+/* ------------------------------------------------------------------------------------------ */
+#define ORC_SEL_MAX_CAND 4096 /* build_kernels.hpp: kSelMaxCand */
+#define ORC_LEVEL_STRIDE 32   /* levels are capped at 30 */
+
+typedef struct {
+    int32_t target, lc, id;
+    double d;
+    int64_t seq;
+} pend_t;
+static int pend_cmp(const void *x, const void *y) {
+    const pend_t *a = (const pend_t *)x, *b = (const pend_t *)y;
+    if (a->target != b->target) return a->target < b->target ? -1 : 1;
+    if (a->lc != b->lc) return a->lc < b->lc ? -1 : 1;
+    return (a->seq > b->seq) - (a->seq < b->seq);
+}
+
+typedef struct {
+    build_t b;
+    double *l0_d, *up_d;       /* stored edge distances, laid out like l0_adj / up_adj */
+    uint8_t *adopt0, *adoptu;  /* start-graph lists not pruned yet: 1 = adopted, 2 = adopted full and not ascending */
+    int64_t *cnt;
+    int64_t batch_work;
+} bgraph_t;
+
+static int32_t *bg_adj(bgraph_t *g, int32_t node, int level, double **d, int32_t **cnt, int *m, uint8_t **adopted) {
+    int cap;
+    int32_t *a = bld_adj(&g->b, node, level, cnt, &cap);
+    *m = cap - 1;
+    if (level == 0) {
+        *d = g->l0_d + (int64_t)node * cap;
+        *adopted = &g->adopt0[node];
+    } else {
+        int64_t blk = g->b.up_off[node] + (level - 1);
+        *d = g->up_d + blk * cap;
+        *adopted = &g->adoptu[blk];
+    }
+    return a;
+}
+static void bg_first_touch(bgraph_t *g, uint8_t *adopted) {
+    if (*adopted) {
+        g->cnt[7]++;
+        if (*adopted == 2) g->cnt[8]++;
+        *adopted = 0;
+    }
+}
+/* HostGraph::add_edge */
+static void bg_add_edge(bgraph_t *g, int32_t from, int32_t to, int lc, double dist) {
+    double *d;
+    int32_t *cnt;
+    uint8_t *adopted;
+    int m;
+    int32_t *a = bg_adj(g, from, lc, &d, &cnt, &m, &adopted);
+    for (int i = 0; i < *cnt; i++)
+        if (a[i] == to) return;
+    a[*cnt] = to;
+    d[*cnt] = dist;
+    (*cnt)++;
+    if (*cnt <= m) return;
+    g->cnt[0]++;
+    g->batch_work++;
+    bg_first_touch(g, adopted);
+    prune_t pr[130];
+    for (int i = 0; i < *cnt; i++) {
+        pr[i].d = d[i];
+        pr[i].id = a[i];
+        pr[i].ord = i;
+    }
+    qsort(pr, (size_t)*cnt, sizeof(prune_t), prune_cmp);
+    for (int i = 0; i < m; i++) {
+        a[i] = pr[i].id;
+        d[i] = pr[i].d;
+    }
+    a[m] = -1;
+    *cnt = m;
+}
+/* HostGraph::append_edge: 0 = the list is full, the edge is pending */
+static int bg_append_edge(bgraph_t *g, int32_t from, int32_t to, int lc, double dist) {
+    double *d;
+    int32_t *cnt;
+    uint8_t *adopted;
+    int m;
+    int32_t *a = bg_adj(g, from, lc, &d, &cnt, &m, &adopted);
+    for (int i = 0; i < *cnt; i++)
+        if (a[i] == to) return 1;
+    if (*cnt >= m) return 0;
+    a[*cnt] = to;
+    d[*cnt] = dist;
+    (*cnt)++;
+    return 1;
+}
+/* HostGraph::remove_edge */
+static int bg_remove_edge(bgraph_t *g, int32_t from, int32_t to, int lc) {
+    double *d;
+    int32_t *cnt;
+    uint8_t *adopted;
+    int m;
+    int32_t *a = bg_adj(g, from, lc, &d, &cnt, &m, &adopted);
+    for (int i = 0; i < *cnt; i++)
+        if (a[i] == to) {
+            for (int t = i; t + 1 < *cnt; t++) {
+                a[t] = a[t + 1];
+                d[t] = d[t + 1];
+            }
+            a[--(*cnt)] = -1;
+            return 1;
+        }
+    return 0;
+}
+
+int orc_hnsw_build_batched(const float *base, int64_t n, int dim, int metric, int mode, int M, int efc, int64_t seed, int flags,
+                           const int64_t *batches, int64_t nbatches, int64_t n0, const int32_t *levels0,
+                           const int32_t *l0_adj0, const int64_t *up_off0, const int32_t *up_adj0, int32_t entry0,
+                           int32_t top0, int32_t *levels_out, int32_t *l0_adj_out, int64_t *up_off_out,
+                           int32_t *up_adj_out, int64_t up_adj_cap, int32_t *entry_out, int32_t *max_level_out,
+                           int64_t *counters) {
+    const int heur = flags & ORC_BUILD_HEURISTIC, extend = (flags & ORC_BUILD_EXTEND) != 0;
+    const int symmetric = heur && (flags & ORC_BUILD_SYMMETRIC);
+    const int M0 = 2 * M;
+    if (n < 1 || M < 1 || M0 > 128 || efc < 1) return -2;
+    if (!levels0) n0 = 0;
+    int64_t covered = levels0 ? n0 : 1, maxb = 1;
+    for (int64_t i = 0; i < nbatches; i++) {
+        if (batches[i] < 1) return -2;
+        covered += batches[i];
+        if (batches[i] > maxb) maxb = batches[i];
+    }
+    if (covered != n) return -2;
+    bgraph_t G;
+    memset(&G, 0, sizeof(G));
+    build_t *b = &G.b;
+    b->n = n;
+    b->dim = dim;
+    b->M = M;
+    b->M0 = M0;
+    b->levels = levels_out;
+    b->up_off = up_off_out;
+    jrandom rng;
+    jr_init(&rng, seed);
+    int64_t tot = 0;
+    for (int64_t i = 0; i < n; i++) { /* row i takes the i-th draw; rows of the start graph keep the level they have */
+        int lv = draw_level(&rng);
+        if (i < n0) lv = levels0[i];
+        b->levels[i] = lv;
+        b->up_off[i] = tot;
+        tot += lv;
+    }
+    b->up_off[n] = tot;
+    if (tot > up_adj_cap / M) return -1;
+    for (int64_t i = 0; i <= n0 && n0 > 0; i++)
+        if (up_off0[i] != b->up_off[i]) return -2; /* the start graph's layout follows from its levels */
+    b->l0_adj = (int32_t *)malloc(sizeof(int32_t) * (size_t)n * (M0 + 1));
+    b->l0_cnt = (int32_t *)calloc((size_t)n + 1, sizeof(int32_t));
+    b->up_adj = (int32_t *)malloc(sizeof(int32_t) * (size_t)(tot + 1) * (M + 1));
+    b->up_cnt = (int32_t *)calloc((size_t)tot + 1, sizeof(int32_t));
+    G.l0_d = (double *)calloc((size_t)n * (M0 + 1), sizeof(double));
+    G.up_d = (double *)calloc((size_t)(tot + 1) * (M + 1), sizeof(double));
+    G.adopt0 = (uint8_t *)calloc((size_t)n + 1, 1);
+    G.adoptu = (uint8_t *)calloc((size_t)tot + 1, 1);
+    int64_t cnt9[9] = {0};
+    G.cnt = cnt9;
+    for (int64_t i = 0; i < n * (M0 + 1); i++) b->l0_adj[i] = -1;
+    for (int64_t i = 0; i < (tot + 1) * (M + 1); i++) b->up_adj[i] = -1;
+
+    dist_ctx c;
+    c.metric = metric;
+    c.mode = mode;
+    c.dim = dim;
+    c.base = base;
+    c.norms = NULL;
+    c.q = base;
+    c.qnorm = 0.0f;
+    float *bnorms = NULL;
+    if (mode != ORC_MODE_F64 && metric == ORC_COSINE) {
+        bnorms = (float *)malloc(sizeof(float) * (size_t)(n + 1));
+        orc_norms(base, n, dim, mode, bnorms);
+        c.norms = bnorms;
+    }
+    int entry = 0, top = b->levels[0];
+    if (n0 > 0) { /* adopt the start graph: lists in their order, distances owner -> neighbour */
+        for (int64_t i = 0; i < n0; i++)
+            for (int lc = 0; lc <= b->levels[i]; lc++) {
+                const int w = lc == 0 ? M0 : M;
+                const int32_t *src = lc == 0 ? l0_adj0 + i * M0 : up_adj0 + (up_off0[i] + (lc - 1)) * (int64_t)M;
+                double *d;
+                int32_t *cn;
+                uint8_t *adopted;
+                int m;
+                int32_t *a = bg_adj(&G, (int32_t)i, lc, &d, &cn, &m, &adopted);
+                int k = 0, asc = 1;
+                while (k < w && src[k] >= 0) {
+                    a[k] = src[k];
+                    d[k] = pair_dist(&c, (int32_t)i, src[k]);
+                    if (k > 0 && d[k] < d[k - 1]) asc = 0;
+                    k++;
+                }
+                *cn = k;
+                *adopted = (k == w && !asc) ? 2 : 1;
+            }
+        entry = entry0;
+        top = top0;
+    }
+
+    visited_t vis;
+    vis.bits = (uint64_t *)calloc((size_t)(n + 63) / 64 + 1, sizeof(uint64_t));
+    vis.touched = (int32_t *)malloc(sizeof(int32_t) * (size_t)(n + 1));
+    cand_t *buf = (cand_t *)malloc(sizeof(cand_t) * (size_t)(efc + 4));
+    int prcap = (efc > M0 ? efc : M0) + 4;
+    prune_t *pr = (prune_t *)malloc(sizeof(prune_t) * (size_t)prcap);
+    prune_t *disc = (prune_t *)malloc(sizeof(prune_t) * (size_t)prcap);
+    /* what phase 1 hands to phase 2, per row of the batch */
+    int32_t *up_id = (int32_t *)malloc(sizeof(int32_t) * (size_t)maxb * ORC_LEVEL_STRIDE);
+    double *up_dd = (double *)malloc(sizeof(double) * (size_t)maxb * ORC_LEVEL_STRIDE);
+    int32_t *sel_id = (int32_t *)malloc(sizeof(int32_t) * (size_t)maxb * M0);
+    double *sel_d = (double *)malloc(sizeof(double) * (size_t)maxb * M0);
+    int32_t *sel_cnt = (int32_t *)malloc(sizeof(int32_t) * (size_t)maxb);
+    pend_t *pend = NULL;
+    int64_t npend = 0, pend_cap = 0;
+    prune_t *tc = NULL, *tdisc = NULL; /* a task's candidates */
+    int64_t tc_cap = 0;
+    int32_t keep[130];
+    double keep_d[130];
+    typedef struct {
+        int32_t from, to, lc;
+    } removal_t;
+    removal_t *rem = NULL;
+    int64_t nrem = 0, rem_cap = 0;
+    int64_t ev = 0, hp = 0, hev = 0;
+
+    graph_view g;
+    g.n = n;
+    g.M = M + 1; /* strides of the build arrays, as in orc_hnsw_build_ex */
+    g.M0 = M0 + 1;
+    g.levels = b->levels;
+    g.l0_adj = b->l0_adj;
+    g.up_off = b->up_off;
+    g.up_adj = b->up_adj;
+
+    int64_t done = n0 > 0 ? n0 : 1;
+    for (int64_t bi = 0; bi < nbatches; bi++) {
+        const int64_t B = batches[bi];
+        const int top_at_start = top;
+        G.batch_work = 0;
+        /* ---- phase 1: the searches, against the graph of rows [0, done) */
+        g.max_level = top;
+        g.entry = entry;
+        for (int64_t r = 0; r < B; r++) {
+            const int32_t id = (int32_t)(done + r);
+            const int level = b->levels[id];
+            ctx_set_query(&c, base + (int64_t)id * dim);
+            int32_t ep = entry;
+            double epd = 0.0;
+            int use_d = 0;
+            for (int lc = top; lc >= 1; lc--) {
+                int cnt = search_layer(&g, &c, &ep, use_d ? &epd : NULL, 1, 1, lc, &vis, buf, &ev, &hp);
+                if (cnt > 0) {
+                    ep = buf[0].id;
+                    epd = buf[0].d;
+                    use_d = 1;
+                }
+                if (lc <= level) {
+                    up_id[r * ORC_LEVEL_STRIDE + lc - 1] = cnt > 0 ? ep : -1;
+                    up_dd[r * ORC_LEVEL_STRIDE + lc - 1] = epd;
+                }
+            }
+            int cnt = search_layer(&g, &c, &ep, use_d ? &epd : NULL, 1, efc, 0, &vis, buf, &ev, &hp);
+            if (heur) {
+                for (int t = 0; t < cnt; t++) {
+                    pr[t].d = buf[t].d;
+                    pr[t].id = buf[t].id;
+                    pr[t].ord = t;
+                }
+                sel_cnt[r] = select_heuristic(&c, pr, cnt, M0, extend, sel_id + r * M0, sel_d + r * M0, disc, &hev);
+            } else {
+                int take = cnt < M0 ? cnt : M0;
+                for (int t = 0; t < take; t++) {
+                    sel_id[r * M0 + t] = buf[t].id;
+                    sel_d[r * M0 + t] = buf[t].d;
+                }
+                sel_cnt[r] = take;
+            }
+            if (level > top_at_start) cnt9[3]++;
+        }
+        /* ---- phase 2: link in row order */
+        npend = 0;
+        int64_t seq = 0;
+        for (int64_t r = 0; r < B; r++) {
+            const int32_t id = (int32_t)(done + r);
+            const int level = b->levels[id];
+            for (int lc = (level < top_at_start ? level : top_at_start); lc >= 0; lc--) {
+                const int cntl = lc == 0 ? sel_cnt[r] : 1;
+                for (int t = 0; t < cntl; t++, seq++) {
+                    const int32_t nb = lc == 0 ? sel_id[r * M0 + t] : up_id[r * ORC_LEVEL_STRIDE + lc - 1];
+                    const double d = lc == 0 ? sel_d[r * M0 + t] : up_dd[r * ORC_LEVEL_STRIDE + lc - 1];
+                    if (nb < 0 || nb == id) continue;
+                    bg_add_edge(&G, id, nb, lc, d); /* the row's own list: never over-full (at most m links) */
+                    if (!heur) {
+                        bg_add_edge(&G, nb, id, lc, d);
+                    } else if (!bg_append_edge(&G, nb, id, lc, d)) {
+                        if (npend == pend_cap) {
+                            pend_cap = pend_cap ? pend_cap * 2 : 1024;
+                            pend = (pend_t *)realloc(pend, sizeof(pend_t) * (size_t)pend_cap);
+                        }
+                        pend_t p = {nb, lc, id, d, seq};
+                        pend[npend++] = p;
+                    }
+                }
+            }
+        }
+        if (heur && npend > 0) { /* Pruner::run_batched */
+            qsort(pend, (size_t)npend, sizeof(pend_t), pend_cmp);
+            nrem = 0;
+            for (int64_t i = 0; i < npend;) {
+                int64_t j = i;
+                while (j < npend && pend[j].target == pend[i].target && pend[j].lc == pend[i].lc) j++;
+                const int32_t target = pend[i].target;
+                const int lc = pend[i].lc;
+                double *d;
+                int32_t *cn;
+                uint8_t *adopted;
+                int m;
+                int32_t *a = bg_adj(&G, target, lc, &d, &cn, &m, &adopted);
+                int64_t nc = *cn + (j - i);
+                if (nc + 4 > tc_cap) {
+                    tc_cap = (nc + 4) * 2;
+                    tc = (prune_t *)realloc(tc, sizeof(prune_t) * (size_t)tc_cap);
+                    tdisc = (prune_t *)realloc(tdisc, sizeof(prune_t) * (size_t)tc_cap);
+                }
+                for (int t = 0; t < *cn; t++) {
+                    tc[t].d = d[t];
+                    tc[t].id = a[t];
+                    tc[t].ord = t;
+                }
+                for (int64_t t = i; t < j; t++) {
+                    tc[*cn + (t - i)].d = pend[t].d;
+                    tc[*cn + (t - i)].id = pend[t].id;
+                    tc[*cn + (t - i)].ord = (int32_t)(*cn + (t - i));
+                }
+                qsort(tc, (size_t)nc, sizeof(prune_t), heur_cmp);
+                if (nc > ORC_SEL_MAX_CAND) nc = ORC_SEL_MAX_CAND; /* longer lists: the closest */
+                cnt9[0]++;
+                G.batch_work++;
+                if (j - i >= 2) cnt9[1]++;
+                bg_first_touch(&G, adopted);
+                int nk = select_heuristic(&c, tc, (int)nc, m, 0, keep, keep_d, tdisc, &hev);
+                if (symmetric)
+                    for (int64_t t = 0; t < nc; t++) {
+                        int kept = 0;
+                        for (int r = 0; r < nk; r++) kept |= keep[r] == tc[t].id;
+                        if (kept) continue;
+                        if (nrem == rem_cap) {
+                            rem_cap = rem_cap ? rem_cap * 2 : 1024;
+                            rem = (removal_t *)realloc(rem, sizeof(removal_t) * (size_t)rem_cap);
+                        }
+                        removal_t rv = {tc[t].id, target, lc};
+                        rem[nrem++] = rv;
+                    }
+                for (int t = 0; t < nk; t++) {
+                    a[t] = keep[t];
+                    d[t] = keep_d[t];
+                }
+                for (int t = nk; t <= m; t++) a[t] = -1;
+                *cn = nk;
+                i = j;
+            }
+            for (int64_t t = 0; t < nrem; t++) /* after every list of the batch has been replaced */
+                if (bg_remove_edge(&G, rem[t].from, rem[t].to, rem[t].lc)) cnt9[2]++;
+        }
+        if (G.batch_work > cnt9[6]) cnt9[6] = G.batch_work;
+        /* ---- entry point and top: only now, row by row */
+        for (int64_t r = 0; r < B; r++) {
+            const int32_t id = (int32_t)(done + r);
+            if (b->levels[id] > top) {
+                entry = id;
+                top = b->levels[id];
+                cnt9[4]++;
+                if (B > 1) cnt9[5]++;
+            }
+        }
+        done += B;
+    }
+    for (int64_t i = 0; i < n; i++)
+        for (int j = 0; j < M0; j++) l0_adj_out[i * M0 + j] = b->l0_adj[i * (M0 + 1) + j];
+    for (int64_t blk = 0; blk < tot; blk++)
+        for (int j = 0; j < M; j++) up_adj_out[blk * M + j] = b->up_adj[blk * (M + 1) + j];
+    *entry_out = entry;
+    *max_level_out = top < 0 ? 0 : top;
+    if (counters) memcpy(counters, cnt9, sizeof(cnt9));
+    free(b->l0_adj);
+    free(b->l0_cnt);
+    free(b->up_adj);
+    free(b->up_cnt);
+    free(G.l0_d);
+    free(G.up_d);
+    free(G.adopt0);
+    free(G.adoptu);
+    free(vis.bits);
+    free(vis.touched);
+    free(buf);
+    free(pr);
+    free(disc);
+    free(up_id);
+    free(up_dd);
+    free(sel_id);
+    free(sel_d);
+    free(sel_cnt);
+    free(pend);
+    free(tc);
+    free(tdisc);
+    free(rem);
+    free(bnorms);
+    return 0;
 }
 
 /* ------------------------------------------------------------------------------------------ */

@@ -67,6 +67,9 @@ def lib():
         _lib.orc_hnsw_build.argtypes = [p, i64, i32, i32, i32, i32, i32, i64, i32, p, p, p, p, i64, p, p]
         _lib.orc_hnsw_build_ex.restype = i32
         _lib.orc_hnsw_build_ex.argtypes = [p, i64, i32, i32, i32, i32, i32, i64, i32, p, p, p, p, i64, p, p, p]
+        _lib.orc_hnsw_build_batched.restype = i32
+        _lib.orc_hnsw_build_batched.argtypes = [p, i64, i32, i32, i32, i32, i32, i64, i32, p, i64, i64, p, p, p, p, i32, i32,
+                                                p, p, p, p, i64, p, p, p]
         _lib.orc_exact_knn.restype = d
         _lib.orc_exact_knn.argtypes = [p, i64, i32, i32, i32, p, p, i32, i32, i32, p, p]
         _lib.orc_recall.restype = d
@@ -243,6 +246,41 @@ def hnsw_build_ex(base, metric=COSINE, M=16, ef_construction=200, seed=42, flags
     tot = int(up_off[n])
     g = Graph(levels, l0, up_off, up[: tot * M].copy(), M, entry.value, maxl.value)
     return (g, cnt) if want_counters else g
+
+
+def hnsw_build_batched(base, batches, metric=COSINE, M=16, ef_construction=200, seed=42, flags=0, mode=MODE_DEV, start=None):
+    """The engine's batched build restated (oracle.c: orc_hnsw_build_batched; hnsw.hip: insert_batches): rows join in
+    batches of the given sizes, a batch's rows searched against the graph as it stood when the batch began, linked in row
+    order, entry point and top moved after the batch.  `flags`: BUILD_HEURISTIC / _EXTEND / _SYMMETRIC.  Without `start`
+    row 0 is the first entry point and the batches cover rows 1 .. n - 1; with `start` (a Graph over the first rows of
+    `base`, M0 = 2 M) they cover the rows behind it -- hnswgpu_hnsw_add.  Returns (Graph, counters[9])."""
+    base = _f32(base)
+    n, dim = base.shape
+    batches = np.ascontiguousarray(batches, np.int64)
+    levels = np.zeros(n, np.int32)
+    l0 = np.full((n, 2 * M), -1, np.int32)
+    up_off = np.zeros(n + 1, np.int64)
+    cap = (n * 3 + 64) * M
+    up = np.full(cap, -1, np.int32)
+    entry = C.c_int32(-1)
+    maxl = C.c_int32(0)
+    cnt = np.zeros(9, np.int64)
+    if start is not None:
+        if start.M != M or start.M0 != 2 * M:
+            raise ValueError("the start graph must have the build's M and M0 = 2 M")
+        l0s = np.ascontiguousarray(start.l0_adj, np.int32)
+        s = (start.n, _p(start.levels), _p(l0s), _p(start.up_off), _p(start.up_adj), start.entry, start.max_level)
+    else:
+        s = (0, None, None, None, None, -1, 0)
+    rc = lib().orc_hnsw_build_batched(_p(base), n, dim, int(metric), int(mode), M, ef_construction, int(seed), int(flags),
+                                      _p(batches), len(batches), *s, _p(levels), _p(l0), _p(up_off), _p(up), cap,
+                                      C.byref(entry), C.byref(maxl), _p(cnt))
+    if rc == -1:
+        raise RuntimeError("oracle hnsw_build_batched: upper-level capacity exceeded")
+    if rc != 0:
+        raise ValueError("oracle hnsw_build_batched: the batches do not cover the rows, or the start graph does not fit")
+    tot = int(up_off[n])
+    return Graph(levels, l0, up_off, up[: tot * M].copy(), M, entry.value, maxl.value), cnt
 
 
 def hnsw_build(base, metric=COSINE, M=16, ef_construction=200, seed=42, farthest_quirk=False, mode=MODE_F64):
