@@ -296,3 +296,22 @@ JNIEXPORT jint JNICALL Java_hnsw_gpu_Native_ivfSearchFiltered(JNIEnv *env, jclas
     if (rc != 0 && rc != HNSWGPU_ENOMEM) throw_last(env);
     return rc;
 }
+
+/* ... with one mask per query: `allow` holds nq rows of (n + 31) / 32 ints, row q is query q's mask (hnswgpu_ivf_search_filtered_each) */
+JNIEXPORT jint JNICALL Java_hnsw_gpu_Native_ivfSearchFilteredEach(JNIEnv *env, jclass c, jlong h, jfloatArray q, jint nq, jint k,
+                                                                  jint nprobe, jintArray allow, jintArray ids, jfloatArray dist) {
+    if (!q || !allow || !ids || !dist) return throw_iae(env, "ivfSearchFilteredEach: null array");
+    jfloat *pq = (*env)->GetFloatArrayElements(env, q, NULL);
+    jint *pa = (*env)->GetIntArrayElements(env, allow, NULL);
+    jint *pi = (*env)->GetIntArrayElements(env, ids, NULL);
+    jfloat *pd = (*env)->GetFloatArrayElements(env, dist, NULL);
+    int rc = (pq && pa && pi && pd) ? hnswgpu_ivf_search_filtered_each((hnswgpu_index *)(intptr_t)h, pq, nq, k, nprobe, (const uint32_t *)pa,
+                                                                       (int32_t *)pi, pd, NULL)
+                                    : HNSWGPU_ENOMEM; /* OutOfMemoryError is pending */
+    if (pq) (*env)->ReleaseFloatArrayElements(env, q, pq, JNI_ABORT);
+    if (pa) (*env)->ReleaseIntArrayElements(env, allow, pa, JNI_ABORT);
+    if (pi) (*env)->ReleaseIntArrayElements(env, ids, pi, 0);
+    if (pd) (*env)->ReleaseFloatArrayElements(env, dist, pd, 0);
+    if (rc != 0 && rc != HNSWGPU_ENOMEM) throw_last(env);
+    return rc;
+}

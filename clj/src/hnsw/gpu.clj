@@ -24,6 +24,7 @@
      (search-knn-filtered index query-vec k filter-fn)               ; FilterableIndex/search-knn-filtered*, on the device
      (search-batch-filtered-each index queries k filter-fns)          ; ... for a batch, one predicate per query, in one chain of launches
      (search-ivf-filtered index query-vec k filter-fn :num-probes 4)  ; ... through the IVF list scan: the k nearest passing rows
+     (search-ivf-batch-filtered-each index queries k filter-fns)      ; ... for a batch, one predicate per query, in one chain of launches
    and, at the bottom, the extend-type that makes GpuIndex an ANNIndex / BatchSearchIndex / FilterableIndex / PersistableIndex next to the
    records src/hnsw/api/unified.clj:30-95 extends."
   (:require [hnsw.api.protocol :as proto])
@@ -386,6 +387,48 @@
   "One query through search-ivf-batch-filtered: seq of {:id :distance} ascending, fewer than k when fewer probed rows pass."
   [idx ^doubles query-vec k filter-fn & {:keys [num-probes] :or {num-probes 4}}]
   (first (search-ivf-batch-filtered idx [query-vec] k filter-fn :num-probes num-probes)))
+
+(def ^:private h-ivfsearch-filtered-each
+  (delay (fn-handle "hnswgpu_ivf_search_filtered_each" (FunctionDescriptor/of I (into-array [P P I I I P P P P])))))
+
+(defn search-ivf-batch-filtered-each
+  "search-ivf-batch-filtered with one predicate PER QUERY (filter-fns: as many as queries): result q is
+   (search-ivf-filtered idx (nth queries q) k (nth filter-fns q) :num-probes num-probes).  An identical predicate is evaluated
+   once; the batch goes through one hnswgpu_ivf_search_filtered_each call, equal predicates adjacent, and the caller's order is
+   restored.  One predicate for the whole batch: search-ivf-batch-filtered."
+  [idx queries k filter-fns & {:keys [num-probes] :or {num-probes 4}}]
+  (assert (= (count queries) (count filter-fns)) "one filter-fn per query")
+  (cond
+    (empty? queries) []
+    (every? #(identical? % (first filter-fns)) filter-fns)
+    (search-ivf-batch-filtered idx queries k (first filter-fns) :num-probes num-probes)
+    :else
+    (let [n (count (:ids idx))
+          words (max 1 (quot (+ n 31) 32))
+          distinct-fns (vec (distinct filter-fns))
+          fn-no (into {} (map-indexed (fn [i f] [f i]) distinct-fns))
+          masks (mapv (fn [f]
+                        (let [m (int-array words)]
+                          (doseq [i (range n) :when (f (nth (:ids idx) i))]
+                            (aset m (quot i 32) (unchecked-int (bit-or (aget m (quot i 32)) (bit-shift-left 1 (rem i 32))))))
+                          m))
+                      distinct-fns)
+          qs (vec (sort-by (fn [q] [(fn-no (nth filter-fns q)) q]) (range (count queries))))
+          nq (count qs)
+          out (object-array nq)]
+      (with-open [arena (Arena/ofConfined)]
+        (let [mask (.allocate arena (* 4 words nq) 4)
+              _ (doseq [[j q] (map-indexed vector qs)]
+                  (MemorySegment/copy (MemorySegment/ofArray ^ints (masks (fn-no (nth filter-fns q)))) 0
+                                      mask (* 4 words j) (* 4 words)))
+              qa (floats-of arena (mapv #(nth queries %) qs) (:dim idx))
+              ids (.allocate arena (* 4 nq k) 4)
+              ds (.allocate arena (* 4 nq k) 4)]
+          (check (.invokeWithArguments ^MethodHandle @h-ivfsearch-filtered-each
+                                       [(:handle idx) qa (int nq) (int k) (int num-probes) mask ids ds MemorySegment/NULL]))
+          (doseq [[j q] (map-indexed vector qs)]
+            (aset out q (results idx ids ds j k)))))
+      (vec out))))
 
 ;; ===== the simd-optimized batch seams =====
 

@@ -93,6 +93,8 @@ _SIGS = {
     "hnswgpu_hnsw_search_filtered_each_dev": ["p", "p", "i32", "i32", "i32", "p", "p", "p", "p", "p"],
     "hnswgpu_ivf_search_filtered": ["p", "p", "i32", "i32", "i32", "p", "p", "p", "p"],
     "hnswgpu_ivf_search_filtered_dev": ["p", "p", "i32", "i32", "i32", "p", "p", "p", "p"],
+    "hnswgpu_ivf_search_filtered_each": ["p", "p", "i32", "i32", "i32", "p", "p", "p", "p"],
+    "hnswgpu_ivf_search_filtered_each_dev": ["p", "p", "i32", "i32", "i32", "p", "p", "p", "p"],
     "hnswgpu_save": ["p", "p"],
     "hnswgpu_load": ["p", "i32", "p"],
     "hnswgpu_set_profiling": ["p", "i32"],

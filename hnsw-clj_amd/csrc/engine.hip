@@ -2022,6 +2022,28 @@ int launch_ivf_filtered_scan(int nch, const IvfFilteredArgs &a0, hipStream_t st)
     return 0;
 }
 
+// The list scan with one mask per query (ivf.hip: ivf_filtered_each_enqueue): the same grid over the chunks of the UNFILTERED
+// lists, the same register rows per width; the LDS holds the waves' queues of passing positions before their top-k lists.
+int launch_ivf_each_scan(int nch, const IvfEachArgs &a0, hipStream_t st) {
+    IvfEachArgs a = a0;
+    int64_t blocks = static_cast<int64_t>(a.npairs) * a.nchunks;
+    if (blocks <= 0) return 0;
+    if (a.order) {
+        if (a.run < 8) a.run = 8;
+        blocks = (blocks + 8 * a.run - 1) / (8 * a.run) * (8 * a.run);
+    }
+    HG_REQUIRE(blocks < 2147483647LL, HNSWGPU_ELIMIT, "filtered list scan grid too large (%lld blocks)", (long long)blocks);
+    const size_t klds = sizeof(uint64_t) * kNWave * a.k;
+    HG_REQUIRE(klds <= 60 * 1024, HNSWGPU_ELIMIT, "k too large for the scan kernel (k=%d)", a.k);
+    const bool l2 = a.metric == METRIC_L2;
+#define CALL(N, R, L) \
+    hipLaunchKernelGGL((ivf_each_scan_kernel<N, R, L>), dim3(static_cast<unsigned>(blocks)), dim3(kWG), ivf_each_queue_bytes(R) + klds, st, a)
+    HG_DISPATCH(nch, l2, CALL);
+#undef CALL
+    HG_HIP(hipGetLastError());
+    return 0;
+}
+
 static int launch_filtered_group(int nch, const FilteredArgs &a, int64_t blocks, hipStream_t st, bool each = false) {
     HG_REQUIRE(blocks > 0 && blocks < 2147483647LL, HNSWGPU_ELIMIT, "filtered scan grid too large (%lld blocks)", (long long)blocks);
     const size_t lds = filtered_group_lds_bytes(a.ld);

@@ -537,6 +537,8 @@ int launch_list_mask(hnswgpu_index *idx, const uint32_t *d_allow, uint32_t *d_lm
 int launch_list_foff(hnswgpu_index *idx, const int32_t *d_pass_pos, const unsigned long long *d_total, int64_t cap, int32_t *d_foff,
                      hipStream_t st);
 int launch_ivf_filtered_scan(int nch, const IvfFilteredArgs &a, hipStream_t st);
+// ... with one mask per query (ivf_filtered_each_enqueue)
+int launch_ivf_each_scan(int nch, const IvfEachArgs &a, hipStream_t st);
 
 // The block of host memory of one combined batch -- a Slot's mapped block and the pinned staging block alike:
 // [64-byte header: flag word, repeat count][queries][stats, 2 x int64 per query, or absent][ids][distances], every section on a

@@ -25,6 +25,11 @@
 //   POSITIONS, and cut at the list boundaries (list_foff_kernel).  A probed list's passing rows are then a segment of that
 //   list, and ivf_filtered_scan_kernel -- the gathered form of scan_kernel's top-k body -- reads exactly those rows.  Keys
 //   carry the position in the UNFILTERED candidate stream, so the merge and the decode of the unfiltered search finish it.
+//
+//   IVF-FLAT, one mask per QUERY (hnswgpu_ivf_search_filtered_each) -- no list-order mask (nq x L bits) and no compaction:
+//   ivf_each_scan_kernel walks the UNFILTERED probed lists in scan_kernel's chunks, tests a row's bit in its query's mask where
+//   it reads the list id (64 positions, one ballot), queues the passing positions per wave in LDS and runs RB of them at a time
+//   through ivf_filtered_scan_kernel's body.  Same keys, same merge, same decode: the single-mask call's ids and bits.
 #pragma once
 #include "kernels.hpp"
 #include "tile_args.hpp"
@@ -469,6 +474,137 @@ __global__ __launch_bounds__(kWG) void ivf_filtered_scan_kernel(IvfFilteredArgs 
                     }
                 }
             }
+        }
+    }
+    uint64_t *dst = a.partial + ((static_cast<int64_t>(pair) * a.nchunks + chunk) * kNWave + wave) * a.k;
+    if (regk) {
+        if (lane < a.k) dst[lane] = mine;
+    } else {
+        for (int i = lane; i < a.k; i += kWave) dst[i] = i < cnt ? mylist[i] : ~0ull;
+    }
+}
+
+// ---- IVF-FLAT, one mask per query: the bit tested where the list is read ------------------------------------------------------
+// A list-order mask per query would be nq x L bits of scratch and a compaction per query.  Instead a workgroup serves one
+// (pair, chunk) of the UNFILTERED list -- positions [row_begin + chunk * chunk_rows, ...), which the host can plan as it plans
+// scan_kernel's -- and wave w takes the chunk's blocks w, w + 4, ... of 64 positions.  Of a block, lane i reads
+// row = list_ids[pos] and the word of ITS QUERY's mask that holds the row's bit (list_mask_kernel's clamping, a row outside
+// [0, n) reads as clear), one ballot gives the block's passing lanes, and a passing lane's prefix popcount is its slot in the
+// wave's queue of passing positions in LDS (kWave + RB entries: fewer than RB left over, at most 64 new).  Whenever the queue
+// holds RB positions, RB of them go through ivf_filtered_scan_kernel's body (ivf_each_step); what is left moves to the front,
+// and the remainder after the last block is flushed with the clamped lane.  A row's distance is finished in its own lane from
+// its own sum, so its bits do not depend on which rows share its step; keys are (distance, position in the UNFILTERED stream),
+// the partial lists are [pair][chunk][wave][k]: the top k of a query's keys is the single-mask call's, whatever the chunking.
+// Per probed position: 4 B of list_ids and a gathered mask word; the f32 row only where the bit is set.
+// (IvfEachArgs: tile_args.hpp)
+
+// RB queued positions (nvalid <= RB of them real: the last step of a wave) -> distances -> the wave's top-k list
+template <int NCH, int RB, bool L2M>
+__device__ __forceinline__ void ivf_each_step(const IvfEachArgs &a, const float4 (&q)[NCH], float qn, const Pair &p, const int32_t *que,
+                                              int nvalid, int lane, bool regk, uint64_t &mine, uint64_t *mylist, int &cnt, uint64_t &thr) {
+    float4 r[RB][NCH];
+    const int nvec = static_cast<int>(a.ld / 4);
+    // lane b (and every lane beyond RB, as row RB - 1): the list position of row b, clamped into the step, and its norm
+    int at = lane < RB ? lane : RB - 1;
+    at = at < nvalid ? at : nvalid - 1;
+    const int32_t mypos = que[at];
+    const float myrn = (!L2M && a.metric == METRIC_COS) ? a.row_norms[mypos] : 0.0f;
+#pragma unroll
+    for (int b = 0; b < RB; b++) {
+        const int64_t row = __builtin_amdgcn_readlane(mypos, b);
+        load_row<NCH>(r[b], a.rows + row * a.ld, nvec, lane, true);
+    }
+    float s[RB];
+#pragma unroll
+    for (int b = 0; b < RB; b++) s[b] = lane_partial<NCH, L2M>(q, r[b]);
+    const float tot = rows_sum_to_lane<RB>(s, lane);  // lane b: row b's sum
+    const float myd = L2M ? __builtin_sqrtf(tot) : finish_dist(a.metric, tot, qn, myrn);
+#pragma unroll
+    for (int b = 0; b < RB; b++) {
+        if (b < nvalid) {  // wave-uniform
+            const float d = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(myd), b));
+            const int64_t pos = __builtin_amdgcn_readlane(mypos, b);
+            const uint64_t key = make_key(d, p.ord_base + static_cast<uint32_t>(pos - p.row_begin));
+            if (key < thr) {
+                if (regk) {
+                    wave_insert_reg(mine, cnt, a.k, key, lane);
+                    thr = wave_kth_reg(mine, a.k);  // ~0 until the list is full
+                } else {
+                    wave_insert(mylist, cnt, a.k, key, lane);
+                    thr = cnt == a.k ? mylist[a.k - 1] : ~0ull;
+                }
+            }
+        }
+    }
+}
+
+// LDS: [kNWave][kWave + RB] queued positions, then [kNWave][k] keys (k > 64)
+__host__ __device__ constexpr size_t ivf_each_queue_bytes(int rb) { return sizeof(int32_t) * kNWave * (kWave + rb); }
+
+template <int NCH, int RB, bool L2M>
+__global__ __launch_bounds__(kWG) void ivf_each_scan_kernel(IvfEachArgs a) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    constexpr int kQueue = kWave + RB;
+    int32_t *queues = reinterpret_cast<int32_t *>(smem);
+    uint64_t *lists = reinterpret_cast<uint64_t *>(smem + ivf_each_queue_bytes(RB));  // (16 * kQueue bytes in: aligned)
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x >> 6;
+    const int64_t bid = blockIdx.x;
+    int32_t pair, chunk;
+    if (a.order) {  // scan_kernel's dealing of the work items to the XCDs: pairs of one list side by side on one L2
+        const int64_t j = bid >> 3;
+        const int64_t item = ((j / a.run) * 8 + (bid & 7)) * a.run + j % a.run;
+        if (item >= static_cast<int64_t>(a.npairs) * a.nchunks) return;
+        pair = a.order[item % a.npairs];
+        chunk = static_cast<int32_t>(item / a.npairs);
+    } else {
+        pair = static_cast<int32_t>(bid % a.npairs);
+        chunk = static_cast<int32_t>(bid / a.npairs);
+    }
+    const Pair p = a.pairs[pair];
+    const int64_t r0 = p.row_begin + static_cast<int64_t>(chunk) * a.chunk_rows;
+    const int64_t r1 = r0 + a.chunk_rows < p.row_end ? r0 + a.chunk_rows : p.row_end;
+    uint64_t *mylist = lists + wave * a.k;
+    int32_t *que = queues + wave * kQueue;
+    int cnt = 0;
+    uint64_t thr = ~0ull;
+    const bool regk = a.k <= kWave;
+    uint64_t mine = ~0ull;
+    if (r0 < r1) {
+        if (r0 + static_cast<int64_t>(wave) * kWave < r1) {  // wave-uniform: this wave has a block
+            float4 q[NCH];
+            load_query<NCH>(q, a.Q + p.q * a.qld, a.dim, lane);
+            const float qn = (!L2M && a.metric == METRIC_COS) ? query_norm<NCH>(q) : 0.0f;
+            const uint32_t *allow = a.allow_each + static_cast<int64_t>(p.q) * a.nwords;
+            int have = 0;  // queued positions (wave-uniform), < RB between two blocks
+            // wave w walks the chunk's blocks w, w + kNWave, ... of 64 positions
+            for (int64_t base = r0 + static_cast<int64_t>(wave) * kWave; base < r1; base += kNWave * kWave) {
+                const int64_t pos = base + lane;
+                const int64_t row = a.listids[pos < r1 ? pos : r1 - 1];  // clamped, unconditional
+                const bool in = pos < r1 && row >= 0 && row < a.n;
+                const uint32_t w = allow[in ? row >> 5 : 0];
+                const bool ok = in && ((w >> (row & 31)) & 1u);
+                const unsigned long long m = __ballot(ok);
+                if (ok) que[have + __popcll(m & ((1ull << lane) - 1ull))] = static_cast<int32_t>(pos);
+                have += __popcll(m);
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                int head = 0;
+                for (; have - head >= RB; head += RB)
+                    ivf_each_step<NCH, RB, L2M>(a, q, qn, p, que + head, RB, lane, regk, mine, mylist, cnt, thr);
+                const int rem = have - head;  // < RB
+                if (head > 0 && rem > 0) {  // the leftovers to the front
+                    int32_t v = 0;
+                    if (lane < rem) v = que[head + lane];
+                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                    if (lane < rem) que[lane] = v;
+                }
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                have = rem;
+            }
+            if (have > 0) ivf_each_step<NCH, RB, L2M>(a, q, qn, p, que, have, lane, regk, mine, mylist, cnt, thr);
         }
     }
     uint64_t *dst = a.partial + ((static_cast<int64_t>(pair) * a.nchunks + chunk) * kNWave + wave) * a.k;

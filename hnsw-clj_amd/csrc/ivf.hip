@@ -1751,6 +1751,85 @@ static int ivf_filtered_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq
     return ivf_decode(idx, p, d_out_ids, d_out_dist, nullptr, st);
 }
 
+// One mask per query, d_allow_each [nq][(n + 31) / 32] in ROW-id space: row q of the result is ivf_filtered_enqueue's for query q
+// alone with mask q.  The same unfiltered GEMV-order routing; the scan tests a row's bit where it reads the list
+// (ivf_each_scan_kernel), so there is no list-order mask and no compaction: the scratch is the unfiltered GEMV scan's (pairs,
+// order, partial lists, winners) and does not grow with nq x n.  The host knows a pair's positions, so the chunks are
+// scan_kernel's (plan_chunks over the unfiltered list lengths).  Same keys, same merge, same decode: the top k of a query's keys
+// is the same set whatever the chunking, so the bits are the single-mask call's.  Nothing is read back.
+static int ivf_filtered_each_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t nprobe,
+                                     const uint32_t *d_allow_each, int32_t *d_out_ids, float *d_out_dist, int32_t *d_out_probes,
+                                     hipStream_t st) {
+    IvfSearchPlan p;
+    memset(&p, 0, sizeof(p));
+    p.nq = nq;
+    p.k = k;
+    p.nprobe = std::min(nprobe, idx->nlist);
+    p.npairs = static_cast<int64_t>(nq) * p.nprobe;
+    p.scan = IvfScan::Gemv;
+    p.route = static_cast<int64_t>(nq) * idx->nlist <= (64LL << 20) ? IvfRoute::Dense : IvfRoute::Scan;
+    p.list_order = tune(HNSWGPU_TUNE_SCAN_ORDER, 1) != 0 && idx->nlist <= kOrderMaxLists && p.npairs * 2 >= idx->nlist && p.npairs <= (1 << 22);
+    if (p.list_order) {
+        p.order_run = 8;
+        while (p.order_run < 64 && static_cast<int64_t>(p.order_run) * idx->nlist < p.npairs) p.order_run *= 2;
+    }
+    HG_REQUIRE(p.npairs < 2147483647LL, HNSWGPU_ELIMIT, "too many (query, list) pairs (%lld)", (long long)p.npairs);
+    int32_t chunk_rows = 0;
+    const int32_t nchunks = plan_chunks(idx->nch, idx->max_list_len, ivf_mean_len(idx), p.npairs, &chunk_rows, true);
+    const int64_t keys_per_query = static_cast<int64_t>(p.nprobe) * nchunks * kNWave * k;
+    const size_t nres = static_cast<size_t>(nq) * std::max(k, p.nprobe);  // the routing's choice, then the winners
+    HG_TRY(idx->s_pairs.ensure(sizeof(Pair) * static_cast<size_t>(p.npairs)));
+    HG_TRY(idx->s_grp.ensure(sizeof(int32_t) * (2 * p.npairs + nq + 16)));
+    HG_TRY(idx->s_ord.ensure(sizeof(uint32_t) * nres));
+    HG_TRY(idx->s_dist.ensure(sizeof(float) * nres));
+    HG_TRY(idx->s_partial.ensure(sizeof(uint64_t) * static_cast<size_t>(keys_per_query) * nq));
+    int32_t *probes_buf = d_out_probes ? d_out_probes : idx->s_grp.as<int32_t>();
+    int32_t *order_buf = idx->s_grp.as<int32_t>() + p.npairs + nq + 16;
+    StreamScratch sc;
+    memset(&sc, 0, sizeof(sc));
+    HG_TRY(ivf_route(idx, p, d_Q, nullptr, probes_buf, nullptr, sc, st));
+    IvfEachArgs a;
+    memset(&a, 0, sizeof(a));
+    a.rows = idx->d_lrows;
+    a.row_norms = idx->d_lnorms;
+    a.ld = idx->ld;
+    a.Q = d_Q;
+    a.qld = idx->dim;
+    a.dim = idx->dim;
+    a.metric = idx->metric;
+    a.pairs = idx->s_pairs.as<Pair>();
+    a.listids = idx->d_listids;
+    a.allow_each = d_allow_each;
+    a.n = idx->n;
+    a.nwords = (idx->n + 31) / 32;
+    a.npairs = static_cast<int32_t>(p.npairs);
+    a.chunk_rows = chunk_rows;
+    a.nchunks = nchunks;
+    a.k = k;
+    a.partial = idx->s_partial.as<uint64_t>();
+    if (p.list_order) {
+        size_t olds;
+        HG_TRY(order_lds(false, idx->nlist, &olds));
+        hipLaunchKernelGGL(pair_order_kernel, dim3(1), dim3(1024), olds, st, probes_buf, static_cast<int>(p.npairs), idx->nlist, order_buf);
+        HG_HIP(hipGetLastError());
+        a.order = order_buf;
+        a.run = p.order_run;
+    }
+    hipEvent_t e0;
+    prof_begin(idx, PROF_IVF_SCAN, st, &e0);
+    HG_TRY(launch_ivf_each_scan(idx->nch, a, st));
+    prof_end(idx, PROF_IVF_SCAN, st, e0);
+    MergeArgs m;
+    m.partial = a.partial;
+    m.keys_per_query = keys_per_query;
+    m.nq = nq;
+    m.k = k;
+    m.out_ord = idx->s_ord.as<uint32_t>();
+    m.out_dist = idx->s_dist.as<float>();
+    HG_TRY(launch_merge(m, st));
+    return ivf_decode(idx, p, d_out_ids, d_out_dist, nullptr, st);
+}
+
 }  // namespace hg
 
 using namespace hg;
@@ -2383,6 +2462,54 @@ int hnswgpu_ivf_search_filtered(hnswgpu_index *idx, const float *Q, int32_t nq, 
     if (out_probes) HG_TRY(idx->s_probes.ensure(sizeof(int32_t) * static_cast<size_t>(nq) * np));
     HG_TRY(ivf_filtered_enqueue(idx, idx->s_q.as<float>(), nq, k, np, idx->s_fmask.as<uint32_t>(), pass, idx->s_ids.as<int32_t>(),
                                 idx->s_outd.as<float>(), out_probes ? idx->s_probes.as<int32_t>() : nullptr, st));
+    if (out_probes) {
+        if (np < nprobe)
+            for (int64_t i = 0; i < static_cast<int64_t>(nq) * nprobe; i++) out_probes[i] = -1;
+        HG_HIP(hipMemcpy2DAsync(out_probes, sizeof(int32_t) * nprobe, idx->s_probes.p, sizeof(int32_t) * np, sizeof(int32_t) * np, nq,
+                                hipMemcpyDeviceToHost, st));
+    }
+    HG_TRY(call.stage_out(out_ids, out_dist, cnt));
+    return call.close();
+}
+
+// One mask per query through the list scan (ivf_filtered_each_enqueue): enqueues only, reads nothing back.
+int hnswgpu_ivf_search_filtered_each_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t nprobe,
+                                         const uint32_t *d_allow_each, int32_t *d_out_ids, float *d_out_dist, void *stream) {
+    HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
+    HG_REQUIRE(d_allow_each, HNSWGPU_EINVAL, "allow is null");
+    HG_TRY(check_ivf_args(idx, d_Q, nq, k, nprobe, d_out_ids, d_out_dist));
+    if (nq == 0) return 0;
+    if (idx->n == 0) return hnswgpu_ivf_search_dev(idx, d_Q, nq, k, nprobe, d_out_ids, d_out_dist, stream);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_REQUIRE(idx->nlist > 0 && idx->n > 0, HNSWGPU_ESTATE, "index has no IVF lists (call hnswgpu_ivf_build / hnswgpu_set_ivf)");
+    HG_TRY(ivf_filtered_each_enqueue(idx, d_Q, nq, k, nprobe, d_allow_each, d_out_ids, d_out_dist, nullptr, st));
+    return call.close();
+}
+
+// One caller's batch, its [nq][W] masks staged whole (as hnswgpu_exact_knn_filtered_each); not combined with concurrent calls.
+int hnswgpu_ivf_search_filtered_each(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t nprobe,
+                                     const uint32_t *allow_each, int32_t *out_ids, float *out_dist, int32_t *out_probes) {
+    HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
+    HG_REQUIRE(allow_each, HNSWGPU_EINVAL, "allow is null");
+    HG_TRY(check_ivf_args(idx, Q, nq, k, nprobe, out_ids, out_dist));
+    if (nq == 0) return 0;
+    if (idx->n == 0) return hnswgpu_ivf_search(idx, Q, nq, k, nprobe, out_ids, out_dist, out_probes);
+    const int64_t cnt = static_cast<int64_t>(nq) * k;
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
+    // under the lock: a concurrent set_ivf / ivf_build may have replaced (or a failed one removed) the lists since the check
+    HG_REQUIRE(idx->nlist > 0 && idx->n > 0, HNSWGPU_ESTATE, "index has no IVF lists (call hnswgpu_ivf_build / hnswgpu_set_ivf)");
+    const int32_t np = std::min(nprobe, idx->nlist);
+    HG_TRY(call.stage_in(Q, nq, k));
+    const size_t mbytes = sizeof(uint32_t) * static_cast<size_t>((idx->n + 31) / 32) * static_cast<size_t>(nq);
+    HG_TRY(idx->s_fmask.ensure(mbytes));
+    HG_HIP(hipMemcpyAsync(idx->s_fmask.p, allow_each, mbytes, hipMemcpyHostToDevice, st));
+    if (out_probes) HG_TRY(idx->s_probes.ensure(sizeof(int32_t) * static_cast<size_t>(nq) * np));
+    HG_TRY(ivf_filtered_each_enqueue(idx, idx->s_q.as<float>(), nq, k, np, idx->s_fmask.as<uint32_t>(), idx->s_ids.as<int32_t>(),
+                                     idx->s_outd.as<float>(), out_probes ? idx->s_probes.as<int32_t>() : nullptr, st));
     if (out_probes) {
         if (np < nprobe)
             for (int64_t i = 0; i < static_cast<int64_t>(nq) * nprobe; i++) out_probes[i] = -1;

@@ -135,4 +135,23 @@ struct IvfFilteredArgs {
     uint64_t *partial;
 };
 
+// The IVF list scan with one allow-mask per query (filter_kernels.hpp: ivf_each_scan_kernel): the bit is tested where the list
+// is read, so there is no list-order mask, no compaction and no per-list offsets -- a pair's positions are its Pair's.
+struct IvfEachArgs {
+    const float *rows;       // list rows (list order) + norms
+    const float *row_norms;
+    int64_t ld;
+    const float *Q;
+    int64_t qld;
+    int32_t dim, metric;
+    const Pair *pairs;       // [npairs]: positions [row_begin, row_end) of the probed list (empty: no list)
+    const int32_t *listids;  // [n]: row id of a list position
+    const uint32_t *allow_each;  // [nq][nwords], ROW-id space
+    int64_t n, nwords;
+    const int32_t *order;    // optional execution order of the pairs (ScanArgs::order), in runs of `run`
+    int32_t run;
+    int32_t npairs, chunk_rows, nchunks, k;  // chunk c of a pair: positions [row_begin + c * chunk_rows, + chunk_rows)
+    uint64_t *partial;
+};
+
 }  // namespace hg

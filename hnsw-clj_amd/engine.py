@@ -555,6 +555,17 @@ class Index:
         check(lib().hnswgpu_ivf_search_filtered(self._h, _p(Q), len(Q), k, nprobe, _p(allow), _p(ids), _p(d), _p(pr)))
         return (ids, d, pr) if want_probes else (ids, d)
 
+    def ivf_search_filtered_each(self, Q, k, nprobe, allow_each, want_probes=False):
+        """hnswgpu_ivf_search_filtered_each: row q is ivf_search_filtered(Q[q:q + 1], k, nprobe, allow_each[q]) -- one mask per
+        query (pack_masks) in one chain of launches; the bit is tested where the list is read."""
+        Q = _queries(Q, self.dim)
+        allow_each = _mask_rows(allow_each, self.n, len(Q))
+        ids = np.empty((len(Q), k), np.int32)
+        d = np.empty((len(Q), k), np.float32)
+        pr = np.empty((len(Q), nprobe), np.int32) if want_probes else None
+        check(lib().hnswgpu_ivf_search_filtered_each(self._h, _p(Q), len(Q), k, nprobe, _p(allow_each), _p(ids), _p(d), _p(pr)))
+        return (ids, d, pr) if want_probes else (ids, d)
+
     def ivf_search_lists(self, Q, k, probes):
         Q = _queries(Q, self.dim)
         probes = np.ascontiguousarray(probes, np.int32).reshape(len(Q), -1)
@@ -655,6 +666,14 @@ class Index:
         allow = self._dev_mask(allow, Q)
         check(lib().hnswgpu_ivf_search_filtered_dev(self._h, Q.data_ptr(), Q.shape[0], k, nprobe, allow.data_ptr(),
                                                     ids.data_ptr(), d.data_ptr(), st))
+        return ids, d
+
+    def ivf_search_filtered_each_dev(self, Q, k, nprobe, allow_each, out=None):
+        """hnswgpu_ivf_search_filtered_each_dev on torch's current stream: enqueues only, nothing is read back."""
+        Q, ids, d, st = self._dev_args(Q, k, out)
+        allow_each = self._dev_masks(allow_each, Q)
+        check(lib().hnswgpu_ivf_search_filtered_each_dev(self._h, Q.data_ptr(), Q.shape[0], k, nprobe, allow_each.data_ptr(),
+                                                         ids.data_ptr(), d.data_ptr(), st))
         return ids, d
 
     def rerank_dev(self, Q, cand, k, out=None):

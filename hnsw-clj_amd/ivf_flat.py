@@ -4,7 +4,8 @@
 Lloyd on the device; ``search_knn(index, q, k, mode)`` / ``search_ivf_flat(index, q, k, mode=...,
 num_probes=...)`` scan the probed lists with the HIP scan kernel;
 ``add_vectors(index, data)`` grows a built index; ``search_knn_filtered`` / ``search_batch_filtered`` (not in the reference, whose IVF index has no
-FilterableIndex) scan only the rows of the probed lists that pass a predicate.
+FilterableIndex) scan only the rows of the probed lists that pass a predicate; ``search_batch_filtered_each`` takes one
+predicate per query.
 """
 import random
 
@@ -128,6 +129,48 @@ def search_batch_filtered(index, queries, k, filter_fn, mode="balanced", num_pro
         passing = {i for i, b in zip(index.ids, bits) if b}
         return [[r for r in rs if r["id"] in passing][:int(k)] for rs in res]
     ids, d = index.index.ivf_search_filtered(queries, int(k), int(cfg["num_probes"]), engine.pack_mask(bits, index.index.n))
+    return [_format(index, ids[i], d[i]) for i in range(len(queries))]
+
+
+def search_batch_filtered_each(index, queries, k, filter_fns, mode="balanced", num_probes=None):
+    """search_batch_filtered with one predicate (or bool array) PER QUERY: row q equals
+    ``search_knn_filtered(index, queries[q], k, filter_fns[q], mode, num_probes)``.  The same object, or equal bits, is evaluated
+    and packed once; the batch goes through ONE hnswgpu_ivf_search_filtered_each call, equal masks adjacent (neighbouring
+    queries then read the same mask words), and the original order is restored.  A batch whose filters are all one mask takes
+    search_batch_filtered's single-mask call; a mode without centroid routing goes through its 3k post-filter rule, per query."""
+    queries = np.asarray(queries, np.float32)
+    if queries.ndim == 1:
+        queries = queries[None, :]
+    if len(filter_fns) != len(queries):
+        raise ValueError("one filter per query: %d filters for %d queries" % (len(filter_fns), len(queries)))
+    if len(queries) == 0:
+        return []
+    n = index.index.n
+    masks, by_obj, by_bits, which = [], {}, {}, []   # distinct masks: (bits, packed)
+    for f in filter_fns:
+        m = by_obj.get(id(f))
+        if m is None:
+            bits = _allow_bits(index, f)
+            key = bits.tobytes()
+            m = by_bits.get(key)
+            if m is None:
+                m = by_bits[key] = len(masks)
+                masks.append((bits, engine.pack_mask(bits, n)))
+            by_obj[id(f)] = m
+        which.append(m)
+    if len(masks) == 1:
+        return search_batch_filtered(index, queries, k, masks[0][0], mode, num_probes)
+    cfg = MODE_CONFIGS.get(mode) or {"num_probes": num_probes or 4, "use_centroids": True}
+    if not cfg["use_centroids"]:
+        res = search_ivf_flat(index, queries, 3 * int(k), mode=mode, num_probes=num_probes)
+        passing = [{i for i, b in zip(index.ids, bits) if b} for bits, _ in masks]
+        return [[r for r in rs if r["id"] in passing[m]][:int(k)] for rs, m in zip(res, which)]
+    qs = sorted(range(len(queries)), key=lambda q: (which[q], q))   # equal masks adjacent
+    rows = np.stack([masks[which[q]][1] for q in qs])
+    gi, gd = index.index.ivf_search_filtered_each(queries[qs], int(k), int(cfg["num_probes"]), rows)
+    ids = np.empty((len(queries), int(k)), np.int32)
+    d = np.empty((len(queries), int(k)), np.float32)
+    ids[qs], d[qs] = gi, gd
     return [_format(index, ids[i], d[i]) for i in range(len(queries))]
 
 

@@ -92,6 +92,10 @@ class GpuIvfFlatIndex(ANNIndex, BatchSearchIndex, PersistableIndex):
     def search_batch_star(self, queries, k, mode="balanced"):
         return ivf_flat.search_batch(self.index, queries, k, mode)
 
+    def search_batch_filtered(self, queries, k, filter_fns, mode="balanced"):
+        """ivf_flat.search_knn_filtered for a batch, one predicate per query, in one chain of launches (not in the reference)."""
+        return ivf_flat.search_batch_filtered_each(self.index, queries, k, filter_fns, mode or "balanced")
+
     def index_info_star(self):
         return ivf_flat.index_info(self.index)
 

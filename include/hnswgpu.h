@@ -376,10 +376,9 @@ int hnswgpu_hnsw_search_filtered_dev(hnswgpu_index *idx, const float *d_Q, int32
  * hnswgpu_hnsw_search_filtered_each: the traversal of hnswgpu_hnsw_search, untouched; result row q equals
  *   hnswgpu_hnsw_search_filtered with mask q; stats are the unfiltered traversal's.  The _dev entry only enqueues.
  * The host entries stage one caller's batch and take no part in the call combiner.
- * Out of scope: one mask per query through the IVF list scan, an _each form of hnswgpu_ivf_search_filtered -- a list-order
- *   mask per query is nq x n bits of scratch without a read-back, which needs its own design; combining concurrent
- *   single-query filtered callers into one _each launch (it would change the path of the existing entry points); forests,
- *   groups and shards. */
+ * Out of scope: combining concurrent single-query filtered callers into one _each launch (it would change the path of the
+ *   existing entry points); forests, groups and shards.  (The IVF list scan's _each form: below, behind
+ *   hnswgpu_ivf_search_filtered.) */
 int hnswgpu_exact_knn_filtered_each(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, const uint32_t *allow_each,
                                     int32_t *out_ids, float *out_dist);
 int hnswgpu_exact_knn_filtered_each_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k,
@@ -414,6 +413,26 @@ int hnswgpu_ivf_search_filtered(hnswgpu_index *idx, const float *Q, int32_t nq, 
                                 const uint32_t *allow, int32_t *out_ids, float *out_dist, int32_t *out_probes);
 int hnswgpu_ivf_search_filtered_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t nprobe,
                                     const uint32_t *d_allow, int32_t *d_out_ids, float *d_out_dist, void *stream);
+/* hnswgpu_ivf_search_filtered_each: one allow-mask per QUERY through the list scan.  allow_each is the [nq][W] array of the
+ *   _each calls above (W = (n + 31) / 32, row-major, row q is query q's mask in ROW-id space, bits at positions >= n are
+ *   ignored, an argument and never handle state).  Result row q is, in ids and distance bits, what
+ *   hnswgpu_ivf_search_filtered(idx, Q + q * dim, 1, k, nprobe, allow_each + q * W, ...) returns: the unfiltered routing
+ *   in the gather order, distances in the gather order, ascending by (distance, position in the UNFILTERED candidate
+ *   stream), -1 / +inf padded where fewer than k of query q's OWN rows pass, and never a row whose bit is clear for q.
+ *   out_probes (host entry, optional) is what the single-mask call reports, -1 padded when nprobe > nlist.  A null idx or a
+ *   null mask is -1, arguments are checked as hnswgpu_ivf_search checks them, nq == 0 is 0, n == 0 behaves as the
+ *   unfiltered call, a handle without lists is -3.
+ *   How: no list-order mask and no compaction.  The scan walks the UNFILTERED probed lists in chunks the host plans from
+ *   the list lengths; of every 64 list positions a wave reads the row ids, tests each row's bit in its query's mask, and
+ *   queues the passing positions; only their f32 rows are fetched.  Per probed position that is 4 bytes of list ids and
+ *   a gathered mask word -- the price of having no per-query compaction, where the single-mask call reads nothing for a
+ *   failing position.  The scratch is that of an unfiltered scan of the batch and does not grow with nq x n.
+ *   The _dev entry only enqueues: it does NOT synchronise and reads nothing back.  The host entry stages one caller's
+ *   batch, masks included, and takes no part in the call combiner.  One handle only, as the single-mask call. */
+int hnswgpu_ivf_search_filtered_each(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t nprobe,
+                                     const uint32_t *allow_each, int32_t *out_ids, float *out_dist, int32_t *out_probes);
+int hnswgpu_ivf_search_filtered_each_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t nprobe,
+                                         const uint32_t *d_allow_each, int32_t *d_out_ids, float *d_out_dist, void *stream);
 
 /* ---- persistence ------------------------------------------------------------------------------------------
  * One flat binary file (header + plain arrays; layout in hnsw-clj_amd/csrc/persist.hip) with the base
