@@ -261,15 +261,23 @@ int launch_query_prep(const PrepArgs &a, int nch, hipStream_t st) {
     return 0;
 }
 
+// The grid of a scan over (pair, chunk) work items (scan_work_item): a workgroup per item -- *blocks = 0: nothing to launch --
+// and, with the pairs in an order, runs of at least 8 items, whole runs on every XCD.  what: the scan, for the limit's message.
+static int scan_grid(const int32_t *order, int32_t &run, int32_t npairs, int32_t nchunks, const char *what, int64_t *blocks) {
+    *blocks = std::max<int64_t>(0, static_cast<int64_t>(npairs) * nchunks);
+    if (order && *blocks > 0) {
+        if (run < 8) run = 8;
+        *blocks = (*blocks + 8 * run - 1) / (8 * run) * (8 * run);
+    }
+    HG_REQUIRE(*blocks < 2147483647LL, HNSWGPU_ELIMIT, "%s grid too large (%lld blocks)", what, (long long)*blocks);
+    return 0;
+}
+
 int launch_scan(int nch, const ScanArgs &a0, hipStream_t st) {
     ScanArgs a = a0;
-    int64_t blocks = static_cast<int64_t>(a.npairs) * a.nchunks;
-    if (blocks <= 0) return 0;
-    if (a.order) {
-        if (a.run < 8) a.run = 8;
-        blocks = (blocks + 8 * a.run - 1) / (8 * a.run) * (8 * a.run);  // whole runs on every XCD
-    }
-    HG_REQUIRE(blocks < 2147483647LL, HNSWGPU_ELIMIT, "scan grid too large (%lld blocks)", (long long)blocks);
+    int64_t blocks;
+    HG_TRY(scan_grid(a.order, a.run, a.npairs, a.nchunks, "scan", &blocks));
+    if (blocks == 0) return 0;
     size_t lds = a.mode == MODE_TOPK ? sizeof(uint64_t) * kNWave * a.k : 0;
     if (a.done) lds = sizeof(uint64_t) * (kNWave + 2) * a.k;  // fused tail: W lists + final list + (ord, dist) of the result
     HG_REQUIRE(lds <= 64 * 1024, HNSWGPU_ELIMIT, "k too large for the scan kernel (k=%d)", a.k);
@@ -1986,7 +1994,7 @@ int mask_compact(hnswgpu_index *idx, const uint32_t *d_allow, int64_t len, int64
     return 0;
 }
 
-// IVF-FLAT filtered search (ivf.hip: ivf_filtered_enqueue): the mask in list order ...
+// IVF-FLAT filtered search (ivf.hip: ivf_filtered_chain): the mask in list order ...
 int launch_list_mask(hnswgpu_index *idx, const uint32_t *d_allow, uint32_t *d_lmask, hipStream_t st) {
     const int64_t L = idx->n, lwords = (L + 31) / 32;
     hipLaunchKernelGGL(list_mask_kernel, dim3(static_cast<unsigned>((L + kMaskThreads - 1) / kMaskThreads)), dim3(kMaskThreads), 0, st,
@@ -2005,13 +2013,9 @@ int launch_list_foff(hnswgpu_index *idx, const int32_t *d_pass_pos, const unsign
 // ... and the scan of the passing rows of the probed lists (launch_scan's grid: whole runs on every XCD when ordered)
 int launch_ivf_filtered_scan(int nch, const IvfFilteredArgs &a0, hipStream_t st) {
     IvfFilteredArgs a = a0;
-    int64_t blocks = static_cast<int64_t>(a.npairs) * a.nchunks;
-    if (blocks <= 0) return 0;
-    if (a.order) {
-        if (a.run < 8) a.run = 8;
-        blocks = (blocks + 8 * a.run - 1) / (8 * a.run) * (8 * a.run);
-    }
-    HG_REQUIRE(blocks < 2147483647LL, HNSWGPU_ELIMIT, "filtered list scan grid too large (%lld blocks)", (long long)blocks);
+    int64_t blocks;
+    HG_TRY(scan_grid(a.order, a.run, a.npairs, a.nchunks, "filtered list scan", &blocks));
+    if (blocks == 0) return 0;
     const size_t lds = sizeof(uint64_t) * kNWave * a.k;
     HG_REQUIRE(lds <= 64 * 1024, HNSWGPU_ELIMIT, "k too large for the scan kernel (k=%d)", a.k);
     const bool l2 = a.metric == METRIC_L2;
@@ -2022,17 +2026,13 @@ int launch_ivf_filtered_scan(int nch, const IvfFilteredArgs &a0, hipStream_t st)
     return 0;
 }
 
-// The list scan with one mask per query (ivf.hip: ivf_filtered_each_enqueue): the same grid over the chunks of the UNFILTERED
-// lists, the same register rows per width; the LDS holds the waves' queues of passing positions before their top-k lists.
+// The list scan with one mask per query: the same grid over the chunks of the UNFILTERED lists, the same register rows per
+// width; the LDS holds the waves' queues of passing positions before their top-k lists.
 int launch_ivf_each_scan(int nch, const IvfEachArgs &a0, hipStream_t st) {
     IvfEachArgs a = a0;
-    int64_t blocks = static_cast<int64_t>(a.npairs) * a.nchunks;
-    if (blocks <= 0) return 0;
-    if (a.order) {
-        if (a.run < 8) a.run = 8;
-        blocks = (blocks + 8 * a.run - 1) / (8 * a.run) * (8 * a.run);
-    }
-    HG_REQUIRE(blocks < 2147483647LL, HNSWGPU_ELIMIT, "filtered list scan grid too large (%lld blocks)", (long long)blocks);
+    int64_t blocks;
+    HG_TRY(scan_grid(a.order, a.run, a.npairs, a.nchunks, "filtered list scan", &blocks));
+    if (blocks == 0) return 0;
     const size_t klds = sizeof(uint64_t) * kNWave * a.k;
     HG_REQUIRE(klds <= 60 * 1024, HNSWGPU_ELIMIT, "k too large for the scan kernel (k=%d)", a.k);
     const bool l2 = a.metric == METRIC_L2;

@@ -532,12 +532,12 @@ constexpr int64_t kMaskCountDevice = -2;  // ... no readback: the list holds `le
 int mask_compact(hnswgpu_index *idx, const uint32_t *d_allow, int64_t len, int64_t p_host, int64_t *p, hipStream_t st,
                  const unsigned long long **d_total = nullptr);
 int fill_empty_dev(int32_t *d_ids, float *d_dist, int64_t cnt, hipStream_t st);
-// IVF-FLAT filtered search (filter_kernels.hpp; driven by ivf.hip: ivf_filtered_enqueue)
+// IVF-FLAT filtered search (filter_kernels.hpp; driven by ivf.hip: ivf_filtered_chain)
 int launch_list_mask(hnswgpu_index *idx, const uint32_t *d_allow, uint32_t *d_lmask, hipStream_t st);
 int launch_list_foff(hnswgpu_index *idx, const int32_t *d_pass_pos, const unsigned long long *d_total, int64_t cap, int32_t *d_foff,
                      hipStream_t st);
 int launch_ivf_filtered_scan(int nch, const IvfFilteredArgs &a, hipStream_t st);
-// ... with one mask per query (ivf_filtered_each_enqueue)
+// ... with one mask per query
 int launch_ivf_each_scan(int nch, const IvfEachArgs &a, hipStream_t st);
 
 // The block of host memory of one combined batch -- a Slot's mapped block and the pinned staging block alike:

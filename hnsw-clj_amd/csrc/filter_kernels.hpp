@@ -29,7 +29,7 @@
 //   IVF-FLAT, one mask per QUERY (hnswgpu_ivf_search_filtered_each) -- no list-order mask (nq x L bits) and no compaction:
 //   ivf_each_scan_kernel walks the UNFILTERED probed lists in scan_kernel's chunks, tests a row's bit in its query's mask where
 //   it reads the list id (64 positions, one ballot), queues the passing positions per wave in LDS and runs RB of them at a time
-//   through ivf_filtered_scan_kernel's body.  Same keys, same merge, same decode: the single-mask call's ids and bits.
+//   through ivf_filtered_scan_kernel's step (ivf_gathered_step: one for both).  Same keys, same merge, same decode: the single-mask call's ids and bits.
 #pragma once
 #include "kernels.hpp"
 #include "tile_args.hpp"
@@ -397,117 +397,17 @@ __global__ void list_foff_kernel(const int32_t *pass_pos, const unsigned long lo
     foff[l] = static_cast<int32_t>(lo);
 }
 
-// The list scan over the passing rows only.  A workgroup serves one (pair, chunk): the pair's list l comes from the probe
-// table (-1: none), its candidates are pass_pos[foff[l] .. foff[l + 1]) -- list positions, ascending, so the filtered
-// candidate stream is the unfiltered one with holes.  Nobody on the host knows a filtered list's length: workgroup c of a
-// pair takes the tiles c, c + nchunks, ... (chunk_rows positions each) of the segment, whatever its length; one with no
-// tile writes its all-ones lists and leaves.  Lane b fetches the position of row b (clamped into the segment) and its norm,
-// readlane makes the row address wave-uniform (filtered_group_kernel); lane_partial + rows_sum_to_lane + finish_dist are
-// scan_kernel's, in its order: the same bits.  Key: (distance, position in the UNFILTERED stream) -- monotone in the
-// filtered one, and what merge_topk_kernel and ivf_decode_kernel expect.  Partial lists: [pair][chunk][wave][k].
-// (IvfFilteredArgs: tile_args.hpp, beside the other launch arguments the host side fills)
-
+// The gathered step of both filtered list scans: RB list positions (nvalid of them real, the rest clamped copies: the last step
+// of a tile or of a wave's queue) -> distances -> the wave's top-k list.  Lane b (and every lane beyond RB, as row RB - 1)
+// brings the position of row b in `mypos` and fetches its norm here, readlane makes the row address wave-uniform
+// (filtered_group_kernel); lane_partial + rows_sum_to_lane + finish_dist are scan_kernel's, in its order, and a row's distance is
+// finished in its own lane from its own sum: the same bits, whichever rows share its step.  Key: (distance, position in the
+// UNFILTERED stream) -- monotone in the filtered one, and what merge_topk_kernel and ivf_decode_kernel expect.
 template <int NCH, int RB, bool L2M>
-__global__ __launch_bounds__(kWG) void ivf_filtered_scan_kernel(IvfFilteredArgs a) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    uint64_t *lists = reinterpret_cast<uint64_t *>(smem);  // [kNWave][k] (k > 64)
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = threadIdx.x >> 6;
-    const int64_t bid = blockIdx.x;
-    int32_t pair, chunk;
-    if (a.order) {  // scan_kernel's dealing of the work items to the XCDs: pairs of one list side by side on one L2
-        const int64_t j = bid >> 3;
-        const int64_t item = ((j / a.run) * 8 + (bid & 7)) * a.run + j % a.run;
-        if (item >= static_cast<int64_t>(a.npairs) * a.nchunks) return;
-        pair = a.order[item % a.npairs];
-        chunk = static_cast<int32_t>(item / a.npairs);
-    } else {
-        pair = static_cast<int32_t>(bid % a.npairs);
-        chunk = static_cast<int32_t>(bid / a.npairs);
-    }
-    const Pair p = a.pairs[pair];
-    const int32_t l = a.probes[pair];
-    const int64_t s0 = l >= 0 ? a.foff[l] : 0, s1 = l >= 0 ? a.foff[l + 1] : 0;
-    uint64_t *mylist = lists + wave * a.k;
-    int cnt = 0;
-    uint64_t thr = ~0ull;
-    const bool regk = a.k <= kWave;
-    uint64_t mine = ~0ull;
-    if (s0 + static_cast<int64_t>(chunk) * a.chunk_rows < s1) {
-        float4 q[NCH];
-        load_query<NCH>(q, a.Q + p.q * a.qld, a.dim, lane);
-        const float qn = (!L2M && a.metric == METRIC_COS) ? query_norm<NCH>(q) : 0.0f;
-        const int nvec = static_cast<int>(a.ld / 4);
-        for (int64_t t0 = s0 + static_cast<int64_t>(chunk) * a.chunk_rows; t0 < s1; t0 += static_cast<int64_t>(a.nchunks) * a.chunk_rows) {
-            const int64_t t1 = t0 + a.chunk_rows < s1 ? t0 + a.chunk_rows : s1;
-            for (int64_t base = t0 + wave * RB; base < t1; base += kNWave * RB) {
-                float4 r[RB][NCH];
-                // lane b (and every lane beyond RB, as row RB - 1): the list position of row b, clamped into the tile, and its norm
-                const int64_t at = base + (lane < RB ? lane : RB - 1);
-                const int32_t mypos = a.pass_pos[at < t1 ? at : t1 - 1];
-                const float myrn = (!L2M && a.metric == METRIC_COS) ? a.row_norms[mypos] : 0.0f;
-#pragma unroll
-                for (int b = 0; b < RB; b++) {
-                    const int64_t row = __builtin_amdgcn_readlane(mypos, b);
-                    load_row<NCH>(r[b], a.rows + row * a.ld, nvec, lane, true);
-                }
-                float s[RB];
-#pragma unroll
-                for (int b = 0; b < RB; b++) s[b] = lane_partial<NCH, L2M>(q, r[b]);
-                const float tot = rows_sum_to_lane<RB>(s, lane);  // lane b: row b's sum
-                const float myd = L2M ? __builtin_sqrtf(tot) : finish_dist(a.metric, tot, qn, myrn);
-#pragma unroll
-                for (int b = 0; b < RB; b++) {
-                    if (base + b < t1) {  // wave-uniform
-                        const float d = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(myd), b));
-                        const int64_t pos = __builtin_amdgcn_readlane(mypos, b);
-                        const uint64_t key = make_key(d, p.ord_base + static_cast<uint32_t>(pos - p.row_begin));
-                        if (key < thr) {
-                            if (regk) {
-                                wave_insert_reg(mine, cnt, a.k, key, lane);
-                                thr = wave_kth_reg(mine, a.k);  // ~0 until the list is full
-                            } else {
-                                wave_insert(mylist, cnt, a.k, key, lane);
-                                thr = cnt == a.k ? mylist[a.k - 1] : ~0ull;
-                            }
-                        }
-                    }
-                }
-            }
-        }
-    }
-    uint64_t *dst = a.partial + ((static_cast<int64_t>(pair) * a.nchunks + chunk) * kNWave + wave) * a.k;
-    if (regk) {
-        if (lane < a.k) dst[lane] = mine;
-    } else {
-        for (int i = lane; i < a.k; i += kWave) dst[i] = i < cnt ? mylist[i] : ~0ull;
-    }
-}
-
-// ---- IVF-FLAT, one mask per query: the bit tested where the list is read ------------------------------------------------------
-// A list-order mask per query would be nq x L bits of scratch and a compaction per query.  Instead a workgroup serves one
-// (pair, chunk) of the UNFILTERED list -- positions [row_begin + chunk * chunk_rows, ...), which the host can plan as it plans
-// scan_kernel's -- and wave w takes the chunk's blocks w, w + 4, ... of 64 positions.  Of a block, lane i reads
-// row = list_ids[pos] and the word of ITS QUERY's mask that holds the row's bit (list_mask_kernel's clamping, a row outside
-// [0, n) reads as clear), one ballot gives the block's passing lanes, and a passing lane's prefix popcount is its slot in the
-// wave's queue of passing positions in LDS (kWave + RB entries: fewer than RB left over, at most 64 new).  Whenever the queue
-// holds RB positions, RB of them go through ivf_filtered_scan_kernel's body (ivf_each_step); what is left moves to the front,
-// and the remainder after the last block is flushed with the clamped lane.  A row's distance is finished in its own lane from
-// its own sum, so its bits do not depend on which rows share its step; keys are (distance, position in the UNFILTERED stream),
-// the partial lists are [pair][chunk][wave][k]: the top k of a query's keys is the single-mask call's, whatever the chunking.
-// Per probed position: 4 B of list_ids and a gathered mask word; the f32 row only where the bit is set.
-// (IvfEachArgs: tile_args.hpp)
-
-// RB queued positions (nvalid <= RB of them real: the last step of a wave) -> distances -> the wave's top-k list
-template <int NCH, int RB, bool L2M>
-__device__ __forceinline__ void ivf_each_step(const IvfEachArgs &a, const float4 (&q)[NCH], float qn, const Pair &p, const int32_t *que,
-                                              int nvalid, int lane, bool regk, uint64_t &mine, uint64_t *mylist, int &cnt, uint64_t &thr) {
+__device__ __forceinline__ void ivf_gathered_step(const IvfGatherArgs &a, const float4 (&q)[NCH], float qn, const Pair &p, int32_t mypos,
+                                                  int nvalid, int lane, bool regk, uint64_t &mine, uint64_t *mylist, int &cnt, uint64_t &thr) {
     float4 r[RB][NCH];
     const int nvec = static_cast<int>(a.ld / 4);
-    // lane b (and every lane beyond RB, as row RB - 1): the list position of row b, clamped into the step, and its norm
-    int at = lane < RB ? lane : RB - 1;
-    at = at < nvalid ? at : nvalid - 1;
-    const int32_t mypos = que[at];
     const float myrn = (!L2M && a.metric == METRIC_COS) ? a.row_norms[mypos] : 0.0f;
 #pragma unroll
     for (int b = 0; b < RB; b++) {
@@ -538,8 +438,81 @@ __device__ __forceinline__ void ivf_each_step(const IvfEachArgs &a, const float4
     }
 }
 
+// ... and their epilogue: the wave's list to partial[pair][chunk][wave][k], from its registers (k <= 64) or from LDS
+__device__ __forceinline__ void ivf_store_partial(const IvfGatherArgs &a, int32_t pair, int32_t chunk, int wave, int lane, bool regk,
+                                                  uint64_t mine, const uint64_t *mylist, int cnt) {
+    uint64_t *dst = a.partial + ((static_cast<int64_t>(pair) * a.nchunks + chunk) * kNWave + wave) * a.k;
+    if (regk) {
+        if (lane < a.k) dst[lane] = mine;
+    } else {
+        for (int i = lane; i < a.k; i += kWave) dst[i] = i < cnt ? mylist[i] : ~0ull;
+    }
+}
+
+// The list scan over the passing rows only.  A workgroup serves one (pair, chunk): the pair's list l comes from the probe
+// table (-1: none), its candidates are pass_pos[foff[l] .. foff[l + 1]) -- list positions, ascending, so the filtered
+// candidate stream is the unfiltered one with holes.  Nobody on the host knows a filtered list's length: workgroup c of a
+// pair takes the tiles c, c + nchunks, ... (chunk_rows positions each) of the segment, whatever its length; one with no
+// tile writes its all-ones lists and leaves.  Lane b fetches the position of row b, clamped into the tile, and the step does
+// the rest.  (IvfFilteredArgs: tile_args.hpp, beside the other launch arguments the host side fills)
+template <int NCH, int RB, bool L2M>
+__global__ __launch_bounds__(kWG) void ivf_filtered_scan_kernel(IvfFilteredArgs a) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    uint64_t *lists = reinterpret_cast<uint64_t *>(smem);  // [kNWave][k] (k > 64)
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x >> 6;
+    int32_t pair, chunk;
+    if (!scan_work_item(a.order, a.run, a.npairs, a.nchunks, blockIdx.x, pair, chunk)) return;
+    const Pair p = a.pairs[pair];
+    const int32_t l = a.probes[pair];
+    const int64_t s0 = l >= 0 ? a.foff[l] : 0, s1 = l >= 0 ? a.foff[l + 1] : 0;
+    uint64_t *mylist = lists + wave * a.k;
+    int cnt = 0;
+    uint64_t thr = ~0ull;
+    const bool regk = a.k <= kWave;
+    uint64_t mine = ~0ull;
+    if (s0 + static_cast<int64_t>(chunk) * a.chunk_rows < s1) {
+        float4 q[NCH];
+        load_query<NCH>(q, a.Q + p.q * a.qld, a.dim, lane);
+        const float qn = (!L2M && a.metric == METRIC_COS) ? query_norm<NCH>(q) : 0.0f;
+        for (int64_t t0 = s0 + static_cast<int64_t>(chunk) * a.chunk_rows; t0 < s1; t0 += static_cast<int64_t>(a.nchunks) * a.chunk_rows) {
+            const int64_t t1 = t0 + a.chunk_rows < s1 ? t0 + a.chunk_rows : s1;
+            for (int64_t base = t0 + wave * RB; base < t1; base += kNWave * RB) {
+                const int64_t at = base + (lane < RB ? lane : RB - 1);
+                const int32_t mypos = a.pass_pos[at < t1 ? at : t1 - 1];
+                // (readfirstlane: the count is the same in every lane of the wave, and the step branches on it)
+                const int nvalid = __builtin_amdgcn_readfirstlane(static_cast<int>(t1 - base));
+                ivf_gathered_step<NCH, RB, L2M>(a, q, qn, p, mypos, nvalid, lane, regk, mine, mylist, cnt, thr);
+            }
+        }
+    }
+    ivf_store_partial(a, pair, chunk, wave, lane, regk, mine, mylist, cnt);
+}
+
+// ---- IVF-FLAT, one mask per query: the bit tested where the list is read ------------------------------------------------------
+// A list-order mask per query would be nq x L bits of scratch and a compaction per query.  Instead a workgroup serves one
+// (pair, chunk) of the UNFILTERED list -- positions [row_begin + chunk * chunk_rows, ...), which the host can plan as it plans
+// scan_kernel's -- and wave w takes the chunk's blocks w, w + 4, ... of 64 positions.  Of a block, lane i reads
+// row = list_ids[pos] and the word of ITS QUERY's mask that holds the row's bit (list_mask_kernel's clamping, a row outside
+// [0, n) reads as clear), one ballot gives the block's passing lanes, and a passing lane's prefix popcount is its slot in the
+// wave's queue of passing positions in LDS (kWave + RB entries: fewer than RB left over, at most 64 new).  Whenever the queue
+// holds RB positions, RB of them go through the single-mask kernel's step (ivf_gathered_step); what is left moves to the front,
+// and the remainder after the last block is flushed with the clamped lane.  A row's bits do not depend on which rows share its
+// step, the keys and the partial lists are the single-mask kernel's: the top k of a query's keys is the single-mask call's,
+// whatever the chunking.
+// Per probed position: 4 B of list_ids and a gathered mask word; the f32 row only where the bit is set.
+// (IvfEachArgs: tile_args.hpp)
+
 // LDS: [kNWave][kWave + RB] queued positions, then [kNWave][k] keys (k > 64)
 __host__ __device__ constexpr size_t ivf_each_queue_bytes(int rb) { return sizeof(int32_t) * kNWave * (kWave + rb); }
+
+// lane b's position of a step over que[0 .. nvalid): entry b, clamped into the step (every lane beyond RB as row RB - 1)
+template <int RB>
+__device__ __forceinline__ int32_t ivf_each_queued(const int32_t *que, int nvalid, int lane) {
+    int at = lane < RB ? lane : RB - 1;
+    at = at < nvalid ? at : nvalid - 1;
+    return que[at];
+}
 
 template <int NCH, int RB, bool L2M>
 __global__ __launch_bounds__(kWG) void ivf_each_scan_kernel(IvfEachArgs a) {
@@ -549,18 +522,8 @@ __global__ __launch_bounds__(kWG) void ivf_each_scan_kernel(IvfEachArgs a) {
     uint64_t *lists = reinterpret_cast<uint64_t *>(smem + ivf_each_queue_bytes(RB));  // (16 * kQueue bytes in: aligned)
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = threadIdx.x >> 6;
-    const int64_t bid = blockIdx.x;
     int32_t pair, chunk;
-    if (a.order) {  // scan_kernel's dealing of the work items to the XCDs: pairs of one list side by side on one L2
-        const int64_t j = bid >> 3;
-        const int64_t item = ((j / a.run) * 8 + (bid & 7)) * a.run + j % a.run;
-        if (item >= static_cast<int64_t>(a.npairs) * a.nchunks) return;
-        pair = a.order[item % a.npairs];
-        chunk = static_cast<int32_t>(item / a.npairs);
-    } else {
-        pair = static_cast<int32_t>(bid % a.npairs);
-        chunk = static_cast<int32_t>(bid / a.npairs);
-    }
+    if (!scan_work_item(a.order, a.run, a.npairs, a.nchunks, blockIdx.x, pair, chunk)) return;
     const Pair p = a.pairs[pair];
     const int64_t r0 = p.row_begin + static_cast<int64_t>(chunk) * a.chunk_rows;
     const int64_t r1 = r0 + a.chunk_rows < p.row_end ? r0 + a.chunk_rows : p.row_end;
@@ -591,7 +554,7 @@ __global__ __launch_bounds__(kWG) void ivf_each_scan_kernel(IvfEachArgs a) {
                 __builtin_amdgcn_wave_barrier();
                 int head = 0;
                 for (; have - head >= RB; head += RB)
-                    ivf_each_step<NCH, RB, L2M>(a, q, qn, p, que + head, RB, lane, regk, mine, mylist, cnt, thr);
+                    ivf_gathered_step<NCH, RB, L2M>(a, q, qn, p, ivf_each_queued<RB>(que + head, RB, lane), RB, lane, regk, mine, mylist, cnt, thr);
                 const int rem = have - head;  // < RB
                 if (head > 0 && rem > 0) {  // the leftovers to the front
                     int32_t v = 0;
@@ -604,15 +567,11 @@ __global__ __launch_bounds__(kWG) void ivf_each_scan_kernel(IvfEachArgs a) {
                 __builtin_amdgcn_wave_barrier();
                 have = rem;
             }
-            if (have > 0) ivf_each_step<NCH, RB, L2M>(a, q, qn, p, que, have, lane, regk, mine, mylist, cnt, thr);
+            if (have > 0)
+                ivf_gathered_step<NCH, RB, L2M>(a, q, qn, p, ivf_each_queued<RB>(que, have, lane), have, lane, regk, mine, mylist, cnt, thr);
         }
     }
-    uint64_t *dst = a.partial + ((static_cast<int64_t>(pair) * a.nchunks + chunk) * kNWave + wave) * a.k;
-    if (regk) {
-        if (lane < a.k) dst[lane] = mine;
-    } else {
-        for (int i = lane; i < a.k; i += kWave) dst[i] = i < cnt ? mylist[i] : ~0ull;
-    }
+    ivf_store_partial(a, pair, chunk, wave, lane, regk, mine, mylist, cnt);
 }
 
 // ---- the first k passing entries of a traversal's result list ----------------------------------------------------------

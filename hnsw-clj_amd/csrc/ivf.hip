@@ -870,6 +870,22 @@ static TileRule ivf_tile_rule(const hnswgpu_index *idx, int32_t k, int tm, int64
 
 constexpr int kHeavySlices = 64;
 
+// The two rules every GEMV-order search shares (ivf_search_plan, ivf_filtered_chain).
+// Routing by dense [nq][nlist] centroid distances + select while that array fits; partial lists + merge beyond.
+static bool ivf_dense_fits(const hnswgpu_index *idx, int32_t nq) { return static_cast<int64_t>(nq) * idx->nlist <= (64LL << 20); }
+static IvfRoute ivf_plain_route(const hnswgpu_index *idx, int32_t nq) { return ivf_dense_fits(idx, nq) ? IvfRoute::Dense : IvfRoute::Scan; }
+// GEMV scan with enough pairs for lists to be probed twice: run the pairs in list order (see ScanArgs::order), in runs of the
+// length returned; 0: as they come.  Below half a pair per list there is next to nothing to share and the sort's ~10 us would
+// be all cost.
+static int32_t ivf_order_run(const hnswgpu_index *idx, int64_t npairs) {
+    const int order_mode = static_cast<int>(tune(HNSWGPU_TUNE_SCAN_ORDER, 1));  // 0 = never (A/B)
+    if (!order_mode || idx->nlist > kOrderMaxLists || npairs * 2 < idx->nlist || npairs > (1 << 22)) return 0;
+    // all the pairs of a list in one run (one XCD) while a run stays a small part of an XCD's share
+    int32_t run = 8;
+    while (run < 64 && static_cast<int64_t>(run) * idx->nlist < npairs) run *= 2;
+    return run;
+}
+
 // Everything ONE search decides (IvfSearchPlan, engine.hpp), before its first launch: a pure function of the handle's state and
 // of one reading of the tuning table -- every key at most once, every rule evaluated once, here.  The table is process-wide and
 // another thread may change it while a search is being enqueued: with the home-list decision flipping between the routing and
@@ -887,7 +903,7 @@ static int ivf_search_plan(const hnswgpu_index *idx, int32_t nq, int32_t k, int3
     p.npairs = npairs;
     // a multiple of 4 so that every query's array is 16-B aligned (float4 select)
     p.cand_stride = (static_cast<int64_t>(nprobe) * idx->max_list_len + 3) / 4 * 4;
-    const bool dense_fits = static_cast<int64_t>(nq) * idx->nlist <= (64LL << 20);  // [nq][nlist] centroid distances
+    const bool dense_fits = ivf_dense_fits(idx, nq);
     const bool l2 = idx->metric == METRIC_L2;
 
     // ---- the scan path
@@ -925,16 +941,8 @@ static int ivf_search_plan(const hnswgpu_index *idx, int32_t nq, int32_t k, int3
     const bool use_group = !use_tile && !use_code && !fused_mode && group_env && tm != 0 && idx->dim <= kL2MaxDim &&
                            (group_env == 2 ? npairs * 2 >= idx->nlist : npairs * 2 >= 3LL * idx->nlist);
     p.scan = use_tile ? IvfScan::Tile : use_code ? IvfScan::Stream : use_group ? IvfScan::Group : fused_mode ? IvfScan::Fused : IvfScan::Gemv;
-    // GEMV scan with enough pairs for lists to be probed twice: run the pairs in list order (see ScanArgs::order).
-    // Below half a pair per list there is next to nothing to share and the sort's ~10 us would be all cost.
-    const int order_mode = static_cast<int>(tune(HNSWGPU_TUNE_SCAN_ORDER, 1));  // 0 = never (A/B)
-    p.list_order = !use_tile && !use_group && !use_code && order_mode && idx->nlist <= kOrderMaxLists && npairs * 2 >= idx->nlist &&
-                   npairs <= (1 << 22);
-    if (p.list_order) {
-        // all the pairs of a list in one run (one XCD) while a run stays a small part of an XCD's share
-        p.order_run = 8;
-        while (p.order_run < 64 && static_cast<int64_t>(p.order_run) * idx->nlist < npairs) p.order_run *= 2;
-    }
+    p.order_run = !use_tile && !use_group && !use_code ? ivf_order_run(idx, npairs) : 0;
+    p.list_order = p.order_run > 0;
     if (use_tile || use_group) {
         // persistent workgroups pulling items off a queue (tile_scan_kernel): items of up to `ptiles` tiles, however many
         // there are -- the queue balances them.  0 = one workgroup per item, items sized to fill the chip (round 1)
@@ -1104,10 +1112,8 @@ static int ivf_search_plan(const hnswgpu_index *idx, int32_t nq, int32_t k, int3
         // a large batch in the GEMV order (Euclidean): the centroid table once per group of 32 queries (register-row group
         // kernel) instead of once per query, the same bits
         p.route = IvfRoute::GroupTopk;
-    else if (dense_fits)  // dense [nq][nlist] distances + select
-        p.route = IvfRoute::Dense;
     else
-        p.route = IvfRoute::Scan;
+        p.route = ivf_plain_route(idx, nq);
     const bool stream_route = p.route == IvfRoute::OneLaunch || p.route == IvfRoute::DistTail;
     // what the routing kernels do in their tail -- codes, empty survivor lists, first thresholds -- by a launch of its own
     p.query_prep = use_code && !stream_route;
@@ -1661,10 +1667,20 @@ static int ivf_search_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, 
 // failing rows dropped.  The routing does not see the mask and is always a GEMV-order one (Dense / Scan: the bits of every
 // other GEMV-order route); the scan reads the passing rows only and is in the GEMV order at every batch size, so a query's bits
 // depend on nothing but the query, the lists and the mask -- not on the batch, the rejection mode, the calibration verdict
-// (never asked for here) or the compact copies.  Nothing is read back: the list of passing positions is sized by the number
-// of list positions and the kernels read its length on the device.  p_host: passing rows counted by the caller, or -1.
-static int ivf_filtered_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t nprobe, const uint32_t *d_allow,
-                                int64_t p_host, int32_t *d_out_ids, float *d_out_dist, int32_t *d_out_probes, hipStream_t st) {
+// (never asked for here) or the compact copies.  Nothing is read back.  One chain for both forms of the mask:
+//   Single -- d_allow is one mask of (n + 31) / 32 words for the call.  It is turned into the ascending list of passing list
+//   positions, sized by the number of list positions (the kernels read its length on the device), and
+//   ivf_filtered_scan_kernel reads a probed list's segment of it.  p_host: passing rows counted by the caller, or -1.
+//   Each -- d_allow is [nq][(n + 31) / 32] in ROW-id space, row q of the result is Single's for query q alone with mask q.
+//   The scan tests a row's bit where it reads the list (ivf_each_scan_kernel), so nothing is prepared and the scratch is the
+//   unfiltered GEMV scan's: it does not grow with nq x n.  The host knows a pair's positions, so the chunks are scan_kernel's.
+// Same step (ivf_gathered_step), same keys, same merge, same decode: the top k of a query's keys is the same set whatever the
+// chunking, so the two forms agree bit for bit.
+enum class IvfMasks { Single, Each };
+
+static int ivf_filtered_chain(hnswgpu_index *idx, IvfMasks form, const float *d_Q, int32_t nq, int32_t k, int32_t nprobe,
+                              const uint32_t *d_allow, int64_t p_host, int32_t *d_out_ids, float *d_out_dist, int32_t *d_out_probes,
+                              hipStream_t st) {
     const int64_t L = idx->n;  // list positions: list_off[nlist] (validate_lists)
     IvfSearchPlan p;
     memset(&p, 0, sizeof(p));
@@ -1673,20 +1689,21 @@ static int ivf_filtered_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq
     p.nprobe = std::min(nprobe, idx->nlist);
     p.npairs = static_cast<int64_t>(nq) * p.nprobe;
     p.scan = IvfScan::Gemv;
-    p.route = static_cast<int64_t>(nq) * idx->nlist <= (64LL << 20) ? IvfRoute::Dense : IvfRoute::Scan;
-    // pairs probing one list side by side on one L2, as the unfiltered GEMV scan orders them (ivf_search_plan)
-    p.list_order = tune(HNSWGPU_TUNE_SCAN_ORDER, 1) != 0 && idx->nlist <= kOrderMaxLists && p.npairs * 2 >= idx->nlist && p.npairs <= (1 << 22);
-    if (p.list_order) {
-        p.order_run = 8;
-        while (p.order_run < 64 && static_cast<int64_t>(p.order_run) * idx->nlist < p.npairs) p.order_run *= 2;
-    }
+    p.route = ivf_plain_route(idx, nq);
+    // pairs probing one list side by side on one L2, as the unfiltered GEMV scan orders them
+    p.order_run = ivf_order_run(idx, p.npairs);
+    p.list_order = p.order_run > 0;
     HG_REQUIRE(p.npairs < 2147483647LL, HNSWGPU_ELIMIT, "too many (query, list) pairs (%lld)", (long long)p.npairs);
-    // Chunking without the filtered list lengths: tiles of chunk_rows passing positions, workgroup c of a pair takes the tiles
-    // c, c + nchunks, ...; both from the mean list length, scaled by the selectivity where the caller has counted it
-    int64_t mean = ivf_mean_len(idx);
-    if (p_host >= 0) mean = std::max<int64_t>(1, mean * p_host / std::max<int64_t>(L, 1));
-    int32_t chunk_rows = 0;
-    const int32_t nchunks = plan_chunks(idx->nch, mean, mean, p.npairs, &chunk_rows, true);
+    int32_t chunk_rows = 0, nchunks = 0;
+    if (form == IvfMasks::Single) {
+        // Chunking without the filtered list lengths: tiles of chunk_rows passing positions, workgroup c of a pair takes the tiles
+        // c, c + nchunks, ...; both from the mean list length, scaled by the selectivity where the caller has counted it
+        int64_t mean = ivf_mean_len(idx);
+        if (p_host >= 0) mean = std::max<int64_t>(1, mean * p_host / std::max<int64_t>(L, 1));
+        nchunks = plan_chunks(idx->nch, mean, mean, p.npairs, &chunk_rows, true);
+    } else {
+        nchunks = plan_chunks(idx->nch, idx->max_list_len, ivf_mean_len(idx), p.npairs, &chunk_rows, true);
+    }
     const int64_t keys_per_query = static_cast<int64_t>(p.nprobe) * nchunks * kNWave * k;
     const size_t nres = static_cast<size_t>(nq) * std::max(k, p.nprobe);  // the routing's choice, then the winners
     HG_TRY(idx->s_pairs.ensure(sizeof(Pair) * static_cast<size_t>(p.npairs)));
@@ -1694,24 +1711,28 @@ static int ivf_filtered_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq
     HG_TRY(idx->s_ord.ensure(sizeof(uint32_t) * nres));
     HG_TRY(idx->s_dist.ensure(sizeof(float) * nres));
     HG_TRY(idx->s_partial.ensure(sizeof(uint64_t) * static_cast<size_t>(keys_per_query) * nq));
-    HG_TRY(idx->s_flmask.ensure(sizeof(uint32_t) * static_cast<size_t>((L + 31) / 32)));
-    HG_TRY(idx->s_ffoff.ensure(sizeof(int32_t) * (static_cast<size_t>(idx->nlist) + 1)));
     int32_t *probes_buf = d_out_probes ? d_out_probes : idx->s_grp.as<int32_t>();
     int32_t *order_buf = idx->s_grp.as<int32_t>() + p.npairs + nq + 16;
-
-    // 1. the mask in list order -> ascending passing positions -> their number below every list's first
-    int64_t cap = 0;
-    const unsigned long long *d_total = nullptr;
-    HG_TRY(launch_list_mask(idx, d_allow, idx->s_flmask.as<uint32_t>(), st));
-    HG_TRY(mask_compact(idx, idx->s_flmask.as<uint32_t>(), L, kMaskCountDevice, &cap, st, &d_total));
-    HG_TRY(launch_list_foff(idx, idx->s_fpass.as<int32_t>(), d_total, cap, idx->s_ffoff.as<int32_t>(), st));
+    if (form == IvfMasks::Single) {
+        // 1. the mask in list order -> ascending passing positions -> their number below every list's first
+        HG_TRY(idx->s_flmask.ensure(sizeof(uint32_t) * static_cast<size_t>((L + 31) / 32)));
+        HG_TRY(idx->s_ffoff.ensure(sizeof(int32_t) * (static_cast<size_t>(idx->nlist) + 1)));
+        int64_t cap = 0;
+        const unsigned long long *d_total = nullptr;
+        HG_TRY(launch_list_mask(idx, d_allow, idx->s_flmask.as<uint32_t>(), st));
+        HG_TRY(mask_compact(idx, idx->s_flmask.as<uint32_t>(), L, kMaskCountDevice, &cap, st, &d_total));
+        HG_TRY(launch_list_foff(idx, idx->s_fpass.as<int32_t>(), d_total, cap, idx->s_ffoff.as<int32_t>(), st));
+    }
     // 2. routing (:261-269) and the probe table
     StreamScratch sc;
     memset(&sc, 0, sizeof(sc));
     HG_TRY(ivf_route(idx, p, d_Q, nullptr, probes_buf, nullptr, sc, st));
     // 3. the passing rows of the probed lists (:217-234), partial lists, merge (:291-294), decode
-    IvfFilteredArgs a;
-    memset(&a, 0, sizeof(a));
+    IvfFilteredArgs single;
+    IvfEachArgs each;
+    memset(&single, 0, sizeof(single));
+    memset(&each, 0, sizeof(each));
+    IvfGatherArgs &a = form == IvfMasks::Single ? static_cast<IvfGatherArgs &>(single) : static_cast<IvfGatherArgs &>(each);
     a.rows = idx->d_lrows;
     a.row_norms = idx->d_lnorms;
     a.ld = idx->ld;
@@ -1720,9 +1741,6 @@ static int ivf_filtered_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq
     a.dim = idx->dim;
     a.metric = idx->metric;
     a.pairs = idx->s_pairs.as<Pair>();
-    a.probes = probes_buf;
-    a.pass_pos = idx->s_fpass.as<int32_t>();
-    a.foff = idx->s_ffoff.as<int32_t>();
     a.npairs = static_cast<int32_t>(p.npairs);
     a.chunk_rows = chunk_rows;
     a.nchunks = nchunks;
@@ -1738,86 +1756,18 @@ static int ivf_filtered_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq
     }
     hipEvent_t e0;
     prof_begin(idx, PROF_IVF_SCAN, st, &e0);
-    HG_TRY(launch_ivf_filtered_scan(idx->nch, a, st));
-    prof_end(idx, PROF_IVF_SCAN, st, e0);
-    MergeArgs m;
-    m.partial = a.partial;
-    m.keys_per_query = keys_per_query;
-    m.nq = nq;
-    m.k = k;
-    m.out_ord = idx->s_ord.as<uint32_t>();
-    m.out_dist = idx->s_dist.as<float>();
-    HG_TRY(launch_merge(m, st));
-    return ivf_decode(idx, p, d_out_ids, d_out_dist, nullptr, st);
-}
-
-// One mask per query, d_allow_each [nq][(n + 31) / 32] in ROW-id space: row q of the result is ivf_filtered_enqueue's for query q
-// alone with mask q.  The same unfiltered GEMV-order routing; the scan tests a row's bit where it reads the list
-// (ivf_each_scan_kernel), so there is no list-order mask and no compaction: the scratch is the unfiltered GEMV scan's (pairs,
-// order, partial lists, winners) and does not grow with nq x n.  The host knows a pair's positions, so the chunks are
-// scan_kernel's (plan_chunks over the unfiltered list lengths).  Same keys, same merge, same decode: the top k of a query's keys
-// is the same set whatever the chunking, so the bits are the single-mask call's.  Nothing is read back.
-static int ivf_filtered_each_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t nprobe,
-                                     const uint32_t *d_allow_each, int32_t *d_out_ids, float *d_out_dist, int32_t *d_out_probes,
-                                     hipStream_t st) {
-    IvfSearchPlan p;
-    memset(&p, 0, sizeof(p));
-    p.nq = nq;
-    p.k = k;
-    p.nprobe = std::min(nprobe, idx->nlist);
-    p.npairs = static_cast<int64_t>(nq) * p.nprobe;
-    p.scan = IvfScan::Gemv;
-    p.route = static_cast<int64_t>(nq) * idx->nlist <= (64LL << 20) ? IvfRoute::Dense : IvfRoute::Scan;
-    p.list_order = tune(HNSWGPU_TUNE_SCAN_ORDER, 1) != 0 && idx->nlist <= kOrderMaxLists && p.npairs * 2 >= idx->nlist && p.npairs <= (1 << 22);
-    if (p.list_order) {
-        p.order_run = 8;
-        while (p.order_run < 64 && static_cast<int64_t>(p.order_run) * idx->nlist < p.npairs) p.order_run *= 2;
+    if (form == IvfMasks::Single) {
+        single.probes = probes_buf;
+        single.pass_pos = idx->s_fpass.as<int32_t>();
+        single.foff = idx->s_ffoff.as<int32_t>();
+        HG_TRY(launch_ivf_filtered_scan(idx->nch, single, st));
+    } else {
+        each.listids = idx->d_listids;
+        each.allow_each = d_allow;
+        each.n = idx->n;
+        each.nwords = (idx->n + 31) / 32;
+        HG_TRY(launch_ivf_each_scan(idx->nch, each, st));
     }
-    HG_REQUIRE(p.npairs < 2147483647LL, HNSWGPU_ELIMIT, "too many (query, list) pairs (%lld)", (long long)p.npairs);
-    int32_t chunk_rows = 0;
-    const int32_t nchunks = plan_chunks(idx->nch, idx->max_list_len, ivf_mean_len(idx), p.npairs, &chunk_rows, true);
-    const int64_t keys_per_query = static_cast<int64_t>(p.nprobe) * nchunks * kNWave * k;
-    const size_t nres = static_cast<size_t>(nq) * std::max(k, p.nprobe);  // the routing's choice, then the winners
-    HG_TRY(idx->s_pairs.ensure(sizeof(Pair) * static_cast<size_t>(p.npairs)));
-    HG_TRY(idx->s_grp.ensure(sizeof(int32_t) * (2 * p.npairs + nq + 16)));
-    HG_TRY(idx->s_ord.ensure(sizeof(uint32_t) * nres));
-    HG_TRY(idx->s_dist.ensure(sizeof(float) * nres));
-    HG_TRY(idx->s_partial.ensure(sizeof(uint64_t) * static_cast<size_t>(keys_per_query) * nq));
-    int32_t *probes_buf = d_out_probes ? d_out_probes : idx->s_grp.as<int32_t>();
-    int32_t *order_buf = idx->s_grp.as<int32_t>() + p.npairs + nq + 16;
-    StreamScratch sc;
-    memset(&sc, 0, sizeof(sc));
-    HG_TRY(ivf_route(idx, p, d_Q, nullptr, probes_buf, nullptr, sc, st));
-    IvfEachArgs a;
-    memset(&a, 0, sizeof(a));
-    a.rows = idx->d_lrows;
-    a.row_norms = idx->d_lnorms;
-    a.ld = idx->ld;
-    a.Q = d_Q;
-    a.qld = idx->dim;
-    a.dim = idx->dim;
-    a.metric = idx->metric;
-    a.pairs = idx->s_pairs.as<Pair>();
-    a.listids = idx->d_listids;
-    a.allow_each = d_allow_each;
-    a.n = idx->n;
-    a.nwords = (idx->n + 31) / 32;
-    a.npairs = static_cast<int32_t>(p.npairs);
-    a.chunk_rows = chunk_rows;
-    a.nchunks = nchunks;
-    a.k = k;
-    a.partial = idx->s_partial.as<uint64_t>();
-    if (p.list_order) {
-        size_t olds;
-        HG_TRY(order_lds(false, idx->nlist, &olds));
-        hipLaunchKernelGGL(pair_order_kernel, dim3(1), dim3(1024), olds, st, probes_buf, static_cast<int>(p.npairs), idx->nlist, order_buf);
-        HG_HIP(hipGetLastError());
-        a.order = order_buf;
-        a.run = p.order_run;
-    }
-    hipEvent_t e0;
-    prof_begin(idx, PROF_IVF_SCAN, st, &e0);
-    HG_TRY(launch_ivf_each_scan(idx->nch, a, st));
     prof_end(idx, PROF_IVF_SCAN, st, e0);
     MergeArgs m;
     m.partial = a.partial;
@@ -2355,6 +2305,15 @@ int hnswgpu_ivf_set_stream_state(hnswgpu_index *idx, int32_t off) {
     return 0;
 }
 
+// The probe table of a host call, s_probes [nq][np], to the caller's [nq][nprobe]: -1 where the index has fewer lists than asked for
+static int copy_out_probes(hnswgpu_index *idx, int32_t *out_probes, int32_t nq, int32_t nprobe, int32_t np, hipStream_t st) {
+    if (np < nprobe)
+        for (int64_t i = 0; i < static_cast<int64_t>(nq) * nprobe; i++) out_probes[i] = -1;
+    HG_HIP(hipMemcpy2DAsync(out_probes, sizeof(int32_t) * nprobe, idx->s_probes.p, sizeof(int32_t) * np, sizeof(int32_t) * np, nq,
+                            hipMemcpyDeviceToHost, st));
+    return 0;
+}
+
 int hnswgpu_ivf_search(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t nprobe,
                        int32_t *out_ids, float *out_dist, int32_t *out_probes) {
     HG_TRY(check_ivf_args(idx, Q, nq, k, nprobe, out_ids, out_dist));
@@ -2411,18 +2370,15 @@ int hnswgpu_ivf_search(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k
     HG_TRY(idx->s_probes.ensure(sizeof(int32_t) * static_cast<size_t>(nq) * np));
     HG_TRY(ivf_search_enqueue(idx, idx->s_q.as<float>(), nq, k, np, idx->s_ids.as<int32_t>(), idx->s_outd.as<float>(),
                               idx->s_probes.as<int32_t>(), st));
-    if (np < nprobe)
-        for (int64_t i = 0; i < static_cast<int64_t>(nq) * nprobe; i++) out_probes[i] = -1;
-    HG_HIP(hipMemcpy2DAsync(out_probes, sizeof(int32_t) * nprobe, idx->s_probes.p, sizeof(int32_t) * np,
-                            sizeof(int32_t) * np, nq, hipMemcpyDeviceToHost, st));
+    HG_TRY(copy_out_probes(idx, out_probes, nq, nprobe, np, st));
     HG_TRY(call.stage_out(out_ids, out_dist, static_cast<int64_t>(nq) * k));
     return call.close();
 }
 
-// The allow-mask through the list scan (ivf_filtered_enqueue).  One caller's batch: masks differ between callers, so the host
-// entry is not combined with concurrent ones (as hnswgpu_hnsw_search_filtered).
-int hnswgpu_ivf_search_filtered_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t nprobe,
-                                    const uint32_t *d_allow, int32_t *d_out_ids, float *d_out_dist, void *stream) {
+// The allow-mask through the list scan (ivf_filtered_chain), one body for both forms of the mask.  Device arrays: enqueues only,
+// reads nothing back.
+static int ivf_filtered_dev(hnswgpu_index *idx, IvfMasks form, const float *d_Q, int32_t nq, int32_t k, int32_t nprobe,
+                            const uint32_t *d_allow, int32_t *d_out_ids, float *d_out_dist, void *stream) {
     HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
     HG_REQUIRE(d_allow, HNSWGPU_EINVAL, "allow is null");
     HG_TRY(check_ivf_args(idx, d_Q, nq, k, nprobe, d_out_ids, d_out_dist));
@@ -2432,19 +2388,21 @@ int hnswgpu_ivf_search_filtered_dev(hnswgpu_index *idx, const float *d_Q, int32_
     Call call;
     HG_TRY(call.open(idx, st));
     HG_REQUIRE(idx->nlist > 0 && idx->n > 0, HNSWGPU_ESTATE, "index has no IVF lists (call hnswgpu_ivf_build / hnswgpu_set_ivf)");
-    HG_TRY(ivf_filtered_enqueue(idx, d_Q, nq, k, nprobe, d_allow, -1, d_out_ids, d_out_dist, nullptr, st));
+    HG_TRY(ivf_filtered_chain(idx, form, d_Q, nq, k, nprobe, d_allow, -1, d_out_ids, d_out_dist, nullptr, st));
     return call.close();
 }
 
-int hnswgpu_ivf_search_filtered(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t nprobe,
-                                const uint32_t *allow, int32_t *out_ids, float *out_dist, int32_t *out_probes) {
+// Host arrays.  One caller's batch, its mask -- Each: its [nq][W] masks (as hnswgpu_exact_knn_filtered_each) -- staged whole:
+// masks differ between callers, so the call is not combined with concurrent ones (as hnswgpu_hnsw_search_filtered).
+static int ivf_filtered_host(hnswgpu_index *idx, IvfMasks form, const float *Q, int32_t nq, int32_t k, int32_t nprobe,
+                             const uint32_t *allow, int32_t *out_ids, float *out_dist, int32_t *out_probes) {
     HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
     HG_REQUIRE(allow, HNSWGPU_EINVAL, "allow is null");
     HG_TRY(check_ivf_args(idx, Q, nq, k, nprobe, out_ids, out_dist));
     if (nq == 0) return 0;
     if (idx->n == 0) return hnswgpu_ivf_search(idx, Q, nq, k, nprobe, out_ids, out_dist, out_probes);
     const int64_t cnt = static_cast<int64_t>(nq) * k;
-    const int64_t pass = mask_popcount(allow, idx->n);
+    const int64_t pass = form == IvfMasks::Single ? mask_popcount(allow, idx->n) : -1;
     if (pass == 0 && !out_probes) {  // nothing can be returned, and nobody asks where the queries were routed
         fill_empty(out_ids, out_dist, cnt);
         return 0;
@@ -2456,68 +2414,32 @@ int hnswgpu_ivf_search_filtered(hnswgpu_index *idx, const float *Q, int32_t nq, 
     HG_REQUIRE(idx->nlist > 0 && idx->n > 0, HNSWGPU_ESTATE, "index has no IVF lists (call hnswgpu_ivf_build / hnswgpu_set_ivf)");
     const int32_t np = std::min(nprobe, idx->nlist);
     HG_TRY(call.stage_in(Q, nq, k));
-    const size_t mbytes = sizeof(uint32_t) * static_cast<size_t>((idx->n + 31) / 32);
+    const size_t mbytes = sizeof(uint32_t) * static_cast<size_t>((idx->n + 31) / 32) * (form == IvfMasks::Single ? 1 : static_cast<size_t>(nq));
     HG_TRY(idx->s_fmask.ensure(mbytes));
     HG_HIP(hipMemcpyAsync(idx->s_fmask.p, allow, mbytes, hipMemcpyHostToDevice, st));
     if (out_probes) HG_TRY(idx->s_probes.ensure(sizeof(int32_t) * static_cast<size_t>(nq) * np));
-    HG_TRY(ivf_filtered_enqueue(idx, idx->s_q.as<float>(), nq, k, np, idx->s_fmask.as<uint32_t>(), pass, idx->s_ids.as<int32_t>(),
-                                idx->s_outd.as<float>(), out_probes ? idx->s_probes.as<int32_t>() : nullptr, st));
-    if (out_probes) {
-        if (np < nprobe)
-            for (int64_t i = 0; i < static_cast<int64_t>(nq) * nprobe; i++) out_probes[i] = -1;
-        HG_HIP(hipMemcpy2DAsync(out_probes, sizeof(int32_t) * nprobe, idx->s_probes.p, sizeof(int32_t) * np, sizeof(int32_t) * np, nq,
-                                hipMemcpyDeviceToHost, st));
-    }
+    HG_TRY(ivf_filtered_chain(idx, form, idx->s_q.as<float>(), nq, k, np, idx->s_fmask.as<uint32_t>(), pass, idx->s_ids.as<int32_t>(),
+                              idx->s_outd.as<float>(), out_probes ? idx->s_probes.as<int32_t>() : nullptr, st));
+    if (out_probes) HG_TRY(copy_out_probes(idx, out_probes, nq, nprobe, np, st));
     HG_TRY(call.stage_out(out_ids, out_dist, cnt));
     return call.close();
 }
 
-// One mask per query through the list scan (ivf_filtered_each_enqueue): enqueues only, reads nothing back.
+int hnswgpu_ivf_search_filtered_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t nprobe,
+                                    const uint32_t *d_allow, int32_t *d_out_ids, float *d_out_dist, void *stream) {
+    return ivf_filtered_dev(idx, IvfMasks::Single, d_Q, nq, k, nprobe, d_allow, d_out_ids, d_out_dist, stream);
+}
+int hnswgpu_ivf_search_filtered(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t nprobe,
+                                const uint32_t *allow, int32_t *out_ids, float *out_dist, int32_t *out_probes) {
+    return ivf_filtered_host(idx, IvfMasks::Single, Q, nq, k, nprobe, allow, out_ids, out_dist, out_probes);
+}
 int hnswgpu_ivf_search_filtered_each_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t nprobe,
                                          const uint32_t *d_allow_each, int32_t *d_out_ids, float *d_out_dist, void *stream) {
-    HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
-    HG_REQUIRE(d_allow_each, HNSWGPU_EINVAL, "allow is null");
-    HG_TRY(check_ivf_args(idx, d_Q, nq, k, nprobe, d_out_ids, d_out_dist));
-    if (nq == 0) return 0;
-    if (idx->n == 0) return hnswgpu_ivf_search_dev(idx, d_Q, nq, k, nprobe, d_out_ids, d_out_dist, stream);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    Call call;
-    HG_TRY(call.open(idx, st));
-    HG_REQUIRE(idx->nlist > 0 && idx->n > 0, HNSWGPU_ESTATE, "index has no IVF lists (call hnswgpu_ivf_build / hnswgpu_set_ivf)");
-    HG_TRY(ivf_filtered_each_enqueue(idx, d_Q, nq, k, nprobe, d_allow_each, d_out_ids, d_out_dist, nullptr, st));
-    return call.close();
+    return ivf_filtered_dev(idx, IvfMasks::Each, d_Q, nq, k, nprobe, d_allow_each, d_out_ids, d_out_dist, stream);
 }
-
-// One caller's batch, its [nq][W] masks staged whole (as hnswgpu_exact_knn_filtered_each); not combined with concurrent calls.
 int hnswgpu_ivf_search_filtered_each(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t nprobe,
                                      const uint32_t *allow_each, int32_t *out_ids, float *out_dist, int32_t *out_probes) {
-    HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
-    HG_REQUIRE(allow_each, HNSWGPU_EINVAL, "allow is null");
-    HG_TRY(check_ivf_args(idx, Q, nq, k, nprobe, out_ids, out_dist));
-    if (nq == 0) return 0;
-    if (idx->n == 0) return hnswgpu_ivf_search(idx, Q, nq, k, nprobe, out_ids, out_dist, out_probes);
-    const int64_t cnt = static_cast<int64_t>(nq) * k;
-    hipStream_t st = idx->stream;
-    Call call;
-    HG_TRY(call.open(idx, st));
-    // under the lock: a concurrent set_ivf / ivf_build may have replaced (or a failed one removed) the lists since the check
-    HG_REQUIRE(idx->nlist > 0 && idx->n > 0, HNSWGPU_ESTATE, "index has no IVF lists (call hnswgpu_ivf_build / hnswgpu_set_ivf)");
-    const int32_t np = std::min(nprobe, idx->nlist);
-    HG_TRY(call.stage_in(Q, nq, k));
-    const size_t mbytes = sizeof(uint32_t) * static_cast<size_t>((idx->n + 31) / 32) * static_cast<size_t>(nq);
-    HG_TRY(idx->s_fmask.ensure(mbytes));
-    HG_HIP(hipMemcpyAsync(idx->s_fmask.p, allow_each, mbytes, hipMemcpyHostToDevice, st));
-    if (out_probes) HG_TRY(idx->s_probes.ensure(sizeof(int32_t) * static_cast<size_t>(nq) * np));
-    HG_TRY(ivf_filtered_each_enqueue(idx, idx->s_q.as<float>(), nq, k, np, idx->s_fmask.as<uint32_t>(), idx->s_ids.as<int32_t>(),
-                                     idx->s_outd.as<float>(), out_probes ? idx->s_probes.as<int32_t>() : nullptr, st));
-    if (out_probes) {
-        if (np < nprobe)
-            for (int64_t i = 0; i < static_cast<int64_t>(nq) * nprobe; i++) out_probes[i] = -1;
-        HG_HIP(hipMemcpy2DAsync(out_probes, sizeof(int32_t) * nprobe, idx->s_probes.p, sizeof(int32_t) * np, sizeof(int32_t) * np, nq,
-                                hipMemcpyDeviceToHost, st));
-    }
-    HG_TRY(call.stage_out(out_ids, out_dist, cnt));
-    return call.close();
+    return ivf_filtered_host(idx, IvfMasks::Each, Q, nq, k, nprobe, allow_each, out_ids, out_dist, out_probes);
 }
 
 }  // extern "C"

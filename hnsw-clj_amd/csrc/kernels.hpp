@@ -838,29 +838,36 @@ struct ScanArgs {
 // code is identical for every role.
 constexpr int ROLE_LIST_SCAN = 0, ROLE_ROUTE = 1, ROLE_ASSIGN = 2, ROLE_SEED = 3, ROLE_EXACT = 4;
 
+// The work item (pair, chunk) of workgroup `bid`, for scan_kernel and the filtered list scans (filter_kernels.hpp); false: the
+// workgroup is padding of an ordered grid and has nothing to do.
+// chunk-major: every pair's chunk 0 first, then chunk 1, ...  Chunks past a short list's end are empty
+// workgroups; this order keeps them at the END of the dispatch instead of interleaved with working ones
+// (interleaved idle workgroups cost the tile kernel half its CU occupancy on k-means lists).
+__device__ __forceinline__ bool scan_work_item(const int32_t *order, int32_t run, int32_t npairs, int32_t nchunks, int64_t bid,
+                                               int32_t &pair, int32_t &chunk) {
+    if (order) {
+        // workgroup b runs on XCD b % 8: XCD x takes the runs x, x + 8, x + 16, ... of `run` work items each
+        // (work items stay chunk-major: [chunk][pair in list order])
+        const int64_t j = bid >> 3;
+        const int64_t item = ((j / run) * 8 + (bid & 7)) * run + j % run;
+        if (item >= static_cast<int64_t>(npairs) * nchunks) return false;
+        pair = order[item % npairs];
+        chunk = static_cast<int32_t>(item / npairs);
+    } else {
+        pair = static_cast<int32_t>(bid % npairs);
+        chunk = static_cast<int32_t>(bid / npairs);
+    }
+    return true;
+}
+
 template <int NCH, int RB, bool L2, int ROLE>
 __global__ __launch_bounds__(kWG) void scan_kernel(ScanArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     uint64_t *lists = reinterpret_cast<uint64_t *>(smem);  // [kNWave][k]
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = threadIdx.x >> 6;
-    const int64_t bid = blockIdx.x;
-    // chunk-major: every pair's chunk 0 first, then chunk 1, ...  Chunks past a short list's end are empty
-    // workgroups; this order keeps them at the END of the dispatch instead of interleaved with working ones
-    // (interleaved idle workgroups cost the tile kernel half its CU occupancy on k-means lists).
     int32_t pair, chunk;
-    if (a.order) {
-        // workgroup b runs on XCD b % 8: XCD x takes the runs x, x + 8, x + 16, ... of a.run work items each
-        // (work items stay chunk-major: [chunk][pair in list order])
-        const int64_t j = bid >> 3;
-        const int64_t item = ((j / a.run) * 8 + (bid & 7)) * a.run + j % a.run;
-        if (item >= static_cast<int64_t>(a.npairs) * a.nchunks) return;
-        pair = a.order[item % a.npairs];
-        chunk = static_cast<int32_t>(item / a.npairs);
-    } else {
-        pair = static_cast<int32_t>(bid % a.npairs);
-        chunk = static_cast<int32_t>(bid / a.npairs);
-    }
+    if (!scan_work_item(a.order, a.run, a.npairs, a.nchunks, blockIdx.x, pair, chunk)) return;
     int64_t rb0, rb1;
     int32_t qi;
     uint32_t ord_base;

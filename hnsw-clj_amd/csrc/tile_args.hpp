@@ -116,28 +116,10 @@ struct SelectArgs {
     float *out_dist;
 };
 
-// The IVF list scan over the passing rows of an allow-mask (filter_kernels.hpp: ivf_filtered_scan_kernel).
+// What the two filtered IVF list scans share (filter_kernels.hpp): the gathered step, the work-item decode and the partial-list
+// epilogue take this block, the chain on the host (ivf.hip: ivf_filtered_chain) fills it once for either form.
 struct Pair;  // kernels.hpp
-struct IvfFilteredArgs {
-    const float *rows;       // list rows (list order) + norms
-    const float *row_norms;
-    int64_t ld;
-    const float *Q;
-    int64_t qld;
-    int32_t dim, metric;
-    const Pair *pairs;       // [npairs]
-    const int32_t *probes;   // [npairs]: the list a pair probes, -1 = none
-    const int32_t *pass_pos; // ascending passing list positions
-    const int32_t *foff;     // [nlist + 1]
-    const int32_t *order;    // optional execution order of the pairs (ScanArgs::order), in runs of `run`
-    int32_t run;
-    int32_t npairs, chunk_rows, nchunks, k;
-    uint64_t *partial;
-};
-
-// The IVF list scan with one allow-mask per query (filter_kernels.hpp: ivf_each_scan_kernel): the bit is tested where the list
-// is read, so there is no list-order mask, no compaction and no per-list offsets -- a pair's positions are its Pair's.
-struct IvfEachArgs {
+struct IvfGatherArgs {
     const float *rows;       // list rows (list order) + norms
     const float *row_norms;
     int64_t ld;
@@ -145,13 +127,27 @@ struct IvfEachArgs {
     int64_t qld;
     int32_t dim, metric;
     const Pair *pairs;       // [npairs]: positions [row_begin, row_end) of the probed list (empty: no list)
+    const int32_t *order;    // optional execution order of the pairs (ScanArgs::order), in runs of `run`
+    int32_t run;
+    int32_t npairs, chunk_rows, nchunks, k;
+    uint64_t *partial;       // [pair][chunk][wave][k]
+};
+
+// The IVF list scan over the passing rows of an allow-mask (ivf_filtered_scan_kernel): workgroup c of a pair takes the tiles
+// c, c + nchunks, ... of chunk_rows passing positions each.
+struct IvfFilteredArgs : IvfGatherArgs {
+    const int32_t *probes;   // [npairs]: the list a pair probes, -1 = none
+    const int32_t *pass_pos; // ascending passing list positions
+    const int32_t *foff;     // [nlist + 1]
+};
+
+// The IVF list scan with one allow-mask per query (ivf_each_scan_kernel): the bit is tested where the list is read, so there
+// is no list-order mask, no compaction and no per-list offsets -- chunk c of a pair: positions [row_begin + c * chunk_rows,
+// + chunk_rows) of its Pair.
+struct IvfEachArgs : IvfGatherArgs {
     const int32_t *listids;  // [n]: row id of a list position
     const uint32_t *allow_each;  // [nq][nwords], ROW-id space
     int64_t n, nwords;
-    const int32_t *order;    // optional execution order of the pairs (ScanArgs::order), in runs of `run`
-    int32_t run;
-    int32_t npairs, chunk_rows, nchunks, k;  // chunk c of a pair: positions [row_begin + c * chunk_rows, + chunk_rows)
-    uint64_t *partial;
 };
 
 }  // namespace hg

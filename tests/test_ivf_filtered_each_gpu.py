@@ -122,13 +122,14 @@ def test_block_and_queue_edges(native_lib, oracle, tune, metric, case):
     Qd, rows_d = torch.from_numpy(E.Q).to(torch.device("cuda", 0)), _dev(torch, rows)
     with engine.Index(E.base, metric, 0) as idx:
         idx.set_ivf(E.cen, E.off, E.lids)
-        si, sd = _singles(idx, E.Q, E.k, E.nprobe, packed, E.which)
-        assert_exact(si, sd, ei, ed, "%s %s: the single-mask call per query" % (metric, case))
         for blocks in (1, None):                                     # one chunk per pair (whole 64-blocks, several per wave), the default chunks
             if blocks:
                 tune.set("SCAN_BLOCKS", blocks)
             else:
                 tune.unset("SCAN_BLOCKS")
+            # (one workgroup per pair: the single-mask kernel walks several tiles of a segment longer than the mean)
+            si, sd = _singles(idx, E.Q, E.k, E.nprobe, packed, E.which)
+            assert_exact(si, sd, ei, ed, "%s %s SCAN_BLOCKS %s: the single-mask call per query" % (metric, case, blocks))
             for k in (E.k, 10, 1):
                 what = "%s %s SCAN_BLOCKS %s k %d" % (metric, case, blocks, k)
                 gi, gd = idx.ivf_search_filtered_each(E.Q, k, E.nprobe, rows)
