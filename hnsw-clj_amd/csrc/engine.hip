@@ -1835,6 +1835,12 @@ int Call::stage_out(int32_t *out_ids, float *out_dist, int64_t cnt) {
     HG_HIP(hipMemcpyAsync(out_dist, idx_->s_outd.p, sizeof(float) * cnt, hipMemcpyDeviceToHost, st_));
     return sync();
 }
+int Call::stage_mask(const uint32_t *allow, MaskForm form, int32_t nq) {
+    const size_t bytes = sizeof(uint32_t) * static_cast<size_t>((idx_->n + 31) / 32) * (form == MaskForm::Each ? static_cast<size_t>(nq) : 1);
+    HG_TRY(idx_->s_fmask.ensure(bytes));
+    HG_HIP(hipMemcpyAsync(idx_->s_fmask.p, allow, bytes, hipMemcpyHostToDevice, st_));
+    return 0;
+}
 void fill_empty(int32_t *ids, float *dist, int64_t cnt) {
     for (int64_t i = 0; i < cnt; i++) {
         ids[i] = -1;
@@ -1949,6 +1955,43 @@ int64_t mask_popcount(const uint32_t *allow, int64_t n) {
     return p;
 }
 
+// MaskArgs of G >= 1 masks of `len` bits each, mask g at d_allow + g * nwords (mask = blockIdx.y), and their count and scan
+// launches.  s_fblk: [G][nblk] per-workgroup counts, then their prefix sums; behind them the G totals.
+static int mask_count_scan(hnswgpu_index *idx, const uint32_t *d_allow, int64_t len, int64_t G, hipStream_t st, MaskArgs *out) {
+    MaskArgs m;
+    memset(&m, 0, sizeof(m));
+    m.allow = d_allow;
+    m.n = len;
+    m.nwords = (len + 31) / 32;
+    const int64_t nblk = (m.nwords + kMaskWordsPerWG - 1) / kMaskWordsPerWG;
+    m.nblk = static_cast<int32_t>(nblk);
+    const size_t tot_off = (sizeof(uint32_t) * static_cast<size_t>(G * nblk) + 7) & ~static_cast<size_t>(7);
+    HG_TRY(idx->s_fblk.ensure(tot_off + sizeof(unsigned long long) * static_cast<size_t>(G)));
+    m.blk = idx->s_fblk.as<uint32_t>();
+    m.total = reinterpret_cast<unsigned long long *>(idx->s_fblk.as<char>() + tot_off);
+    m.allow_stride = m.nwords;
+    m.blk_stride = nblk;
+    m.total_stride = 1;
+    const unsigned gy = static_cast<unsigned>(G);
+    hipLaunchKernelGGL(mask_count_kernel, dim3(static_cast<unsigned>(nblk), gy), dim3(kMaskThreads), 0, st, m);
+    hipLaunchKernelGGL(mask_scan_kernel, dim3(1, gy), dim3(kMaskScanThreads), 0, st, m);
+    HG_HIP(hipGetLastError());
+    *out = m;
+    return 0;
+}
+// ... and the scatter of the masks g0 .. g0 + ng of them: list i at pass_ids + i * stride, at most `cap` entries of it written
+static int mask_scatter(MaskArgs m, int64_t g0, int32_t ng, int32_t *pass_ids, int64_t cap, int64_t stride, hipStream_t st) {
+    m.allow += g0 * m.allow_stride;
+    m.blk += g0 * m.blk_stride;
+    m.total += g0 * m.total_stride;
+    m.pass_ids = pass_ids;
+    m.cap = cap;
+    m.pass_stride = stride;
+    hipLaunchKernelGGL(mask_scatter_kernel, dim3(static_cast<unsigned>(m.nblk), static_cast<unsigned>(ng)), dim3(kMaskThreads), 0, st, m);
+    HG_HIP(hipGetLastError());
+    return 0;
+}
+
 // The ascending list of the set bits of a mask of `len` bits into s_fpass, their number into *p: three small launches
 // (per-workgroup popcounts, one-workgroup scan, scatter).  p_host >= 0: the caller counted on the host; kMaskCountRead: the 8-byte
 // total is read back once, between the scan and the scatter (the list is sized by it), and the calling thread waits for `st`
@@ -1960,20 +2003,8 @@ int mask_compact(hnswgpu_index *idx, const uint32_t *d_allow, int64_t len, int64
     if (d_total) *d_total = nullptr;
     if (p_host == 0) return 0;
     MaskArgs m;
-    memset(&m, 0, sizeof(m));
-    m.allow = d_allow;
-    m.n = len;
-    m.nwords = (len + 31) / 32;
-    const int64_t nblk = (m.nwords + kMaskWordsPerWG - 1) / kMaskWordsPerWG;
-    m.nblk = static_cast<int32_t>(nblk);
-    const size_t tot_off = (sizeof(uint32_t) * static_cast<size_t>(nblk) + 7) & ~static_cast<size_t>(7);
-    HG_TRY(idx->s_fblk.ensure(tot_off + sizeof(unsigned long long)));
-    m.blk = idx->s_fblk.as<uint32_t>();
-    m.total = reinterpret_cast<unsigned long long *>(idx->s_fblk.as<char>() + tot_off);
+    HG_TRY(mask_count_scan(idx, d_allow, len, 1, st, &m));
     if (d_total) *d_total = m.total;
-    hipLaunchKernelGGL(mask_count_kernel, dim3(static_cast<unsigned>(nblk)), dim3(kMaskThreads), 0, st, m);
-    hipLaunchKernelGGL(mask_scan_kernel, dim3(1), dim3(kMaskScanThreads), 0, st, m);
-    HG_HIP(hipGetLastError());
     int64_t cnt = p_host;
     if (cnt == kMaskCountDevice) {
         cnt = len;
@@ -1987,11 +2018,7 @@ int mask_compact(hnswgpu_index *idx, const uint32_t *d_allow, int64_t len, int64
     *p = cnt;
     if (cnt == 0) return 0;
     HG_TRY(idx->s_fpass.ensure(sizeof(int32_t) * static_cast<size_t>(cnt)));
-    m.pass_ids = idx->s_fpass.as<int32_t>();
-    m.cap = cnt;
-    hipLaunchKernelGGL(mask_scatter_kernel, dim3(static_cast<unsigned>(nblk)), dim3(kMaskThreads), 0, st, m);
-    HG_HIP(hipGetLastError());
-    return 0;
+    return mask_scatter(m, 0, 1, idx->s_fpass.as<int32_t>(), cnt, cnt, st);
 }
 
 // IVF-FLAT filtered search (ivf.hip: ivf_filtered_chain): the mask in list order ...
@@ -2044,7 +2071,7 @@ int launch_ivf_each_scan(int nch, const IvfEachArgs &a0, hipStream_t st) {
     return 0;
 }
 
-static int launch_filtered_group(int nch, const FilteredArgs &a, int64_t blocks, hipStream_t st, bool each = false) {
+static int launch_filtered_group(int nch, MaskForm form, const FilteredArgs &a, int64_t blocks, hipStream_t st) {
     HG_REQUIRE(blocks > 0 && blocks < 2147483647LL, HNSWGPU_ELIMIT, "filtered scan grid too large (%lld blocks)", (long long)blocks);
     const size_t lds = filtered_group_lds_bytes(a.ld);
     const bool l2 = a.metric == METRIC_L2;
@@ -2056,10 +2083,10 @@ static int launch_filtered_group(int nch, const FilteredArgs &a, int64_t blocks,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                   \
         hipLaunchKernelGGL((filtered_group_kernel<N, R, L, E>), dim3(static_cast<unsigned>(blocks)), dim3(kTileThreads), lds, st, a); \
     } while (0)
-#define CALL(N, R, L)                    \
-    do {                                 \
-        if (each) CALLE(N, R, L, true);  \
-        else CALLE(N, R, L, false);      \
+#define CALL(N, R, L)                                          \
+    do {                                                       \
+        if (form == MaskForm::Each) CALLE(N, R, L, true);      \
+        else CALLE(N, R, L, false);                            \
     } while (0)
     HG_DISPATCH(nch, l2, CALL);
 #undef CALL
@@ -2074,118 +2101,60 @@ int fill_empty_dev(int32_t *d_ids, float *d_dist, int64_t cnt, hipStream_t st) {
     return 0;
 }
 
-// k nearest of the passing rows for every query: exact, GEMV summation order at every batch size
-static int filtered_scan_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, const uint32_t *d_allow,
-                                 int64_t p_host, int32_t *d_ids, float *d_dist, hipStream_t st) {
-    const int64_t cnt = static_cast<int64_t>(nq) * k;
-    int64_t p = 0;
-    HG_TRY(mask_compact(idx, d_allow, idx->n, p_host, &p, st));  // (p_host < 0: kMaskCountRead)
-    if (p == 0) return fill_empty_dev(d_ids, d_dist, cnt, st);
-    HG_TRY(pad_queries(idx, d_Q, idx->dim, nq, st));
-    HG_TRY(idx->s_ord.ensure(sizeof(uint32_t) * static_cast<size_t>(cnt)));
-    HG_TRY(idx->s_dist.ensure(sizeof(float) * static_cast<size_t>(cnt)));
-    // dense scratch [qb][p]; bound it to ~2 GiB by slicing the queries (whole groups)
-    const int tq = filtered_group_queries(idx->ld);
-    int64_t qb = std::max<int64_t>(tq, ((2LL << 30) / (4 * p)) / tq * tq);
-    qb = std::min<int64_t>(qb, (static_cast<int64_t>(nq) + tq - 1) / tq * tq);
-    HG_TRY(idx->s_tile.ensure(sizeof(float) * static_cast<size_t>(qb) * p));
-    for (int64_t q0 = 0; q0 < nq; q0 += qb) {
-        const int32_t nb = static_cast<int32_t>(std::min<int64_t>(qb, nq - q0));
-        FilteredArgs f;
-        memset(&f, 0, sizeof(f));
-        f.rows = idx->d_base;
-        f.row_norms = idx->d_norms;
-        f.ld = idx->ld;
-        f.metric = idx->metric;
-        f.Qp = idx->s_qp.as<float>() + q0 * idx->ld;
-        f.q_norms = idx->s_qn.as<float>() + q0;
-        f.nq = nb;
-        f.tq = tq;
-        f.ngroups = (nb + tq - 1) / tq;
-        f.pass_ids = idx->s_fpass.as<int32_t>();
-        f.p = p;
-        // chunks of whole 256-position tiles, about 2048 workgroups in all: a workgroup stages its query group once per chunk
-        const int64_t tiles = (p + kTileRows - 1) / kTileRows;
-        const int64_t want = std::max<int64_t>(1, std::min<int64_t>(tiles, (2048 + f.ngroups - 1) / f.ngroups));
-        f.chunk_rows = (tiles + want - 1) / want * kTileRows;
-        const int64_t nchunks = (p + f.chunk_rows - 1) / f.chunk_rows;
-        f.out = idx->s_tile.as<float>();
-        hipEvent_t e0;
-        prof_begin(idx, PROF_IVF_SCAN, st, &e0);
-        HG_TRY(launch_filtered_group(idx->nch, f, nchunks * f.ngroups, st));
-        prof_end(idx, PROF_IVF_SCAN, st, e0);
-        SelectArgs s;
-        memset(&s, 0, sizeof(s));
-        s.dist = f.out;
-        s.stride = p;
-        s.cnt_all = p;
-        s.nq = nb;
-        s.k = k;
-        s.out_ord = idx->s_ord.as<uint32_t>() + q0 * k;
-        s.out_dist = idx->s_dist.as<float>() + q0 * k;
-        HG_TRY(launch_select(s, st));
-    }
-    hipLaunchKernelGGL(filter_decode_kernel, dim3(static_cast<unsigned>((cnt + 255) / 256)), dim3(256), 0, st,
-                       idx->s_ord.as<uint32_t>(), cnt, idx->s_fpass.as<int32_t>(), p, d_ids);
-    HG_HIP(hipGetLastError());
-    HG_HIP(hipMemcpyAsync(d_dist, idx->s_dist.p, sizeof(float) * cnt, hipMemcpyDeviceToDevice, st));
-    return 0;
-}
-
-// One mask per query (d_allow_each: [nq][W]).  The chain of filtered_scan_enqueue over the UNION of every query group's
-// masks: unions, popcounts and scans of all groups in one launch each, the groups' counts read back in one copy (the calling
-// thread waits for `st` there, once), then slices of whole groups -- cut so that the dense array stays within
-// FILTER_EACH_MB, which bounds the slice's lists and words too (both are 1 / tq of it) -- scatter, words, group scan,
-// selection and decode.  A run of groups whose unions are empty is padding and launches nothing.
-static int filtered_each_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, const uint32_t *d_allow_each,
-                                 int32_t *d_ids, float *d_dist, hipStream_t st) {
+// k nearest of the passing rows for every query: exact, GEMV summation order at every batch size.  One chain for both forms
+// of the mask: lists of passing rows, then slices of whole query groups -- group scan into a dense [query][position in the
+// list] array, selection, decode.
+//   Single -- d_allow is the call's one mask; every group walks its list (mask_compact).  p_host: passing rows counted by the
+//   caller, or kMaskCountRead (the calling thread waits for `st` there, once).  The dense array of a slice stays within 2 GiB.
+//   Each -- d_allow is [nq][W]; a group walks the UNION of its queries' masks: unions, popcounts and scans of all groups in one
+//   launch each, the groups' counts read back in one copy (the calling thread waits for `st` there, once); a slice's scatter
+//   and its words (who of the group allows a union row) come before its scan.  The dense array stays within FILTER_EACH_MB,
+//   which bounds the slice's lists and words too (both are 1 / tq of it).  A run of groups whose unions are empty is padding
+//   and launches nothing but the fill.
+static int filtered_chain(hnswgpu_index *idx, MaskForm form, const float *d_Q, int32_t nq, int32_t k, const uint32_t *d_allow,
+                          int64_t p_host, int32_t *d_ids, float *d_dist, hipStream_t st) {
+    const bool each = form == MaskForm::Each;
     const int64_t n = idx->n, W = (n + 31) / 32;
     const int tq = filtered_group_queries(idx->ld);
     const int64_t G = (static_cast<int64_t>(nq) + tq - 1) / tq;
-    HG_REQUIRE(G <= 65535, HNSWGPU_ELIMIT, "too many query groups for one call (%lld, at most 65535)", (long long)G);
-    const int64_t nblk = (W + kMaskWordsPerWG - 1) / kMaskWordsPerWG;
+    std::vector<int64_t> up;  // entries of every group's list
+    MaskArgs m;  // Each: of the G union masks
     UnionArgs u;
-    memset(&u, 0, sizeof(u));
-    u.allow_each = d_allow_each;
-    u.n = n;
-    u.nwords = W;
-    u.nq = nq;
-    u.tq = tq;
-    HG_TRY(idx->s_feum.ensure(sizeof(uint32_t) * static_cast<size_t>(G * W)));
-    u.um = idx->s_feum.as<uint32_t>();
-    // s_fblk: [G][nblk] block counts, then the G totals
-    const size_t tot_off = (sizeof(uint32_t) * static_cast<size_t>(G * nblk) + 7) & ~static_cast<size_t>(7);
-    HG_TRY(idx->s_fblk.ensure(tot_off + sizeof(unsigned long long) * static_cast<size_t>(G)));
-    unsigned long long *d_up = reinterpret_cast<unsigned long long *>(idx->s_fblk.as<char>() + tot_off);
-    u.up = d_up;
-    MaskArgs m;
     memset(&m, 0, sizeof(m));
-    m.allow = u.um;
-    m.n = n;
-    m.nwords = W;
-    m.blk = idx->s_fblk.as<uint32_t>();
-    m.nblk = static_cast<int32_t>(nblk);
-    m.total = d_up;
-    m.allow_stride = W;
-    m.blk_stride = nblk;
-    m.total_stride = 1;
-    const unsigned gy = static_cast<unsigned>(G);
-    hipLaunchKernelGGL(mask_union_kernel, dim3(static_cast<unsigned>((W + kMaskThreads - 1) / kMaskThreads), gy), dim3(kMaskThreads), 0, st, u);
-    hipLaunchKernelGGL(mask_count_kernel, dim3(static_cast<unsigned>(nblk), gy), dim3(kMaskThreads), 0, st, m);
-    hipLaunchKernelGGL(mask_scan_kernel, dim3(1, gy), dim3(kMaskScanThreads), 0, st, m);
-    HG_HIP(hipGetLastError());
-    std::vector<int64_t> up(static_cast<size_t>(G));
-    {
+    memset(&u, 0, sizeof(u));
+    if (!each) {
+        int64_t p = 0;
+        HG_TRY(mask_compact(idx, d_allow, n, p_host, &p, st));
+        if (p == 0) return fill_empty_dev(d_ids, d_dist, static_cast<int64_t>(nq) * k, st);
+        up.assign(static_cast<size_t>(G), p);
+    } else {
+        HG_REQUIRE(G <= 65535, HNSWGPU_ELIMIT, "too many query groups for one call (%lld, at most 65535)", (long long)G);
+        u.allow_each = d_allow;
+        u.n = n;
+        u.nwords = W;
+        u.nq = nq;
+        u.tq = tq;
+        HG_TRY(idx->s_feum.ensure(sizeof(uint32_t) * static_cast<size_t>(G * W)));
+        u.um = idx->s_feum.as<uint32_t>();
+        hipLaunchKernelGGL(mask_union_kernel, dim3(static_cast<unsigned>((W + kMaskThreads - 1) / kMaskThreads), static_cast<unsigned>(G)),
+                           dim3(kMaskThreads), 0, st, u);
+        HG_TRY(mask_count_scan(idx, u.um, n, G, st, &m));
+        u.up = m.total;
         HG_TRY(ensure_pinned(idx, sizeof(unsigned long long) * static_cast<size_t>(G)));
-        HG_HIP(hipMemcpyAsync(idx->h_pin, d_up, sizeof(unsigned long long) * static_cast<size_t>(G), hipMemcpyDeviceToHost, st));
+        HG_HIP(hipMemcpyAsync(idx->h_pin, m.total, sizeof(unsigned long long) * static_cast<size_t>(G), hipMemcpyDeviceToHost, st));
         HG_HIP(hipStreamSynchronize(st));
         const unsigned long long *h = static_cast<const unsigned long long *>(idx->h_pin);
         for (int64_t g = 0; g < G; g++) {
             HG_REQUIRE(h[g] <= static_cast<unsigned long long>(n), HNSWGPU_EINVAL, "a group's masks count %llu passing rows of %lld", h[g], (long long)n);
-            up[static_cast<size_t>(g)] = static_cast<int64_t>(h[g]);
+            up.push_back(static_cast<int64_t>(h[g]));
         }
     }
-    const int64_t cap_bytes = std::max<int64_t>(1, tune(HNSWGPU_TUNE_FILTER_EACH_MB, 2048)) << 20;
+    // Row stride of the dense array for lists of p entries.  Each: 16-byte aligned rows (select_topk_kernel's float4 loads).
+    // Single: p itself -- the EACH = false kernel reads its stride from FilteredArgs.p, and the selection takes its path by it.
+    const auto stride_of = [each](int64_t p) { return each ? (p + 3) / 4 * 4 : p; };
+    const int64_t cap_bytes = each ? std::max<int64_t>(1, tune(HNSWGPU_TUNE_FILTER_EACH_MB, 2048)) << 20 : 2LL << 30;
+    // slices: runs of whole groups [g0, g1) whose dense array [groups * tq][stride of the longest list] fits the cap (one group
+    // always does), or runs of empty groups
     struct Slice {
         int64_t g0, g1, pmax;
     };
@@ -2197,11 +2166,11 @@ static int filtered_each_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t n
             while (g1 < G && up[static_cast<size_t>(g1)] == 0) g1++;
         } else {
             for (; g1 < G && up[static_cast<size_t>(g1)] > 0; g1++) {
-                const int64_t pm = (std::max(pmax, up[static_cast<size_t>(g1)]) + 3) / 4 * 4;
+                const int64_t pm = stride_of(std::max(pmax, up[static_cast<size_t>(g1)]));
                 if ((g1 + 1 - g0) * tq * pm * 4 > cap_bytes) break;
                 pmax = std::max(pmax, up[static_cast<size_t>(g1)]);
             }
-            list_max = std::max(list_max, static_cast<size_t>((g1 - g0) * ((pmax + 3) / 4 * 4)));
+            list_max = std::max(list_max, static_cast<size_t>((g1 - g0) * stride_of(pmax)));
             q_max = std::max(q_max, static_cast<size_t>((g1 - g0) * tq));
         }
         slices.push_back({g0, g1, pmax});
@@ -2209,45 +2178,40 @@ static int filtered_each_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t n
     }
     if (list_max) {
         HG_TRY(pad_queries(idx, d_Q, idx->dim, nq, st));
-        HG_TRY(idx->s_fpass.ensure(sizeof(int32_t) * list_max));
-        HG_TRY(idx->s_feuw.ensure(sizeof(uint32_t) * list_max));
-        HG_TRY(idx->s_feqc.ensure(sizeof(int32_t) * q_max));
+        if (each) {  // (Single: s_fpass holds the call's list already)
+            HG_TRY(idx->s_fpass.ensure(sizeof(int32_t) * list_max));
+            HG_TRY(idx->s_feuw.ensure(sizeof(uint32_t) * list_max));
+            HG_TRY(idx->s_feqc.ensure(sizeof(int32_t) * q_max));
+        }
         HG_TRY(idx->s_tile.ensure(sizeof(float) * list_max * tq));
         HG_TRY(idx->s_ord.ensure(sizeof(uint32_t) * q_max * k));
         HG_TRY(idx->s_dist.ensure(sizeof(float) * q_max * k));
     }
     for (const Slice &sl : slices) {
-        const int64_t g1 = sl.g1, pmax = sl.pmax;
-        const int64_t q0 = sl.g0 * tq;
-        const int32_t nb = static_cast<int32_t>(std::min<int64_t>(g1 * tq, nq) - q0);
+        const int64_t pmax = sl.pmax, q0 = sl.g0 * tq;
+        const int32_t nb = static_cast<int32_t>(std::min<int64_t>(sl.g1 * tq, nq) - q0);
         const int64_t cnt = static_cast<int64_t>(nb) * k;
-        const int32_t ng = static_cast<int32_t>(g1 - sl.g0);
+        const int32_t ng = static_cast<int32_t>(sl.g1 - sl.g0);
         if (pmax == 0) {
             HG_TRY(fill_empty_dev(d_ids + q0 * k, d_dist + q0 * k, cnt, st));
             continue;
         }
-        const int64_t pstride = (pmax + 3) / 4 * 4;  // rows of the dense array 16-byte aligned (select_topk_kernel's float4 loads)
-        const int64_t gs = g1 - ng;  // the slice's first group
-        MaskArgs ms = m;
-        ms.allow = u.um + gs * W;
-        ms.blk = m.blk + gs * nblk;
-        ms.total = d_up + gs;
-        ms.pass_ids = idx->s_fpass.as<int32_t>();
-        ms.cap = pstride;
-        ms.pass_stride = pstride;
-        hipLaunchKernelGGL(mask_scatter_kernel, dim3(static_cast<unsigned>(nblk), static_cast<unsigned>(ng)), dim3(kMaskThreads), 0, st, ms);
-        UnionArgs us = u;  // the slice's queries and groups, numbered from 0
-        us.allow_each = d_allow_each + q0 * W;
-        us.nq = nb;
-        us.upass = idx->s_fpass.as<int32_t>();
-        us.up = d_up + gs;
-        us.uw = idx->s_feuw.as<uint32_t>();
-        us.pstride = pstride;
-        us.q_cnt = idx->s_feqc.as<int32_t>();
-        hipLaunchKernelGGL(union_words_kernel, dim3(static_cast<unsigned>((pmax + kMaskThreads - 1) / kMaskThreads), static_cast<unsigned>(ng)),
-                           dim3(kMaskThreads), 0, st, us);
-        hipLaunchKernelGGL(union_qcnt_kernel, dim3((nb + 255) / 256), dim3(256), 0, st, us);
-        HG_HIP(hipGetLastError());
+        const int64_t stride = stride_of(pmax);
+        UnionArgs us = u;  // Each: the slice's queries and groups, numbered from 0
+        if (each) {
+            HG_TRY(mask_scatter(m, sl.g0, ng, idx->s_fpass.as<int32_t>(), stride, stride, st));
+            us.allow_each = d_allow + q0 * W;
+            us.nq = nb;
+            us.upass = idx->s_fpass.as<int32_t>();
+            us.up = u.up + sl.g0;
+            us.uw = idx->s_feuw.as<uint32_t>();
+            us.pstride = stride;
+            us.q_cnt = idx->s_feqc.as<int32_t>();
+            hipLaunchKernelGGL(union_words_kernel, dim3(static_cast<unsigned>((pmax + kMaskThreads - 1) / kMaskThreads), static_cast<unsigned>(ng)),
+                               dim3(kMaskThreads), 0, st, us);
+            hipLaunchKernelGGL(union_qcnt_kernel, dim3((nb + 255) / 256), dim3(256), 0, st, us);
+            HG_HIP(hipGetLastError());
+        }
         FilteredArgs f;
         memset(&f, 0, sizeof(f));
         f.rows = idx->d_base;
@@ -2259,11 +2223,13 @@ static int filtered_each_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t n
         f.nq = nb;
         f.tq = tq;
         f.ngroups = ng;
-        f.pass_ids = us.upass;
+        f.pass_ids = idx->s_fpass.as<int32_t>();
+        f.p = pmax;
         f.uw = us.uw;
         f.up = us.up;
-        f.pstride = pstride;
-        // chunks of whole 256-position tiles of the longest list, about 2048 workgroups in all (filtered_scan_enqueue)
+        f.pstride = stride;
+        // chunks of whole 256-position tiles of the longest list, about 2048 workgroups in all: a workgroup stages its query
+        // group once per chunk
         const int64_t tiles = (pmax + kTileRows - 1) / kTileRows;
         const int64_t want = std::max<int64_t>(1, std::min<int64_t>(tiles, (2048 + ng - 1) / ng));
         f.chunk_rows = (tiles + want - 1) / want * kTileRows;
@@ -2271,22 +2237,28 @@ static int filtered_each_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t n
         f.out = idx->s_tile.as<float>();
         hipEvent_t e0;
         prof_begin(idx, PROF_IVF_SCAN, st, &e0);
-        HG_TRY(launch_filtered_group(idx->nch, f, nchunks * ng, st, true));
+        HG_TRY(launch_filtered_group(idx->nch, form, f, nchunks * ng, st));
         prof_end(idx, PROF_IVF_SCAN, st, e0);
-        g_launch_count[HNSWGPU_COUNT_FILTERED_EACH_GROUPS].fetch_add(ng, std::memory_order_relaxed);
+        if (each) g_launch_count[HNSWGPU_COUNT_FILTERED_EACH_GROUPS].fetch_add(ng, std::memory_order_relaxed);
         SelectArgs s;
         memset(&s, 0, sizeof(s));
         s.dist = f.out;
         s.q_cnt = us.q_cnt;
-        s.stride = pstride;
-        s.cnt_all = pstride;
+        s.stride = stride;
+        s.cnt_all = stride;
         s.nq = nb;
         s.k = k;
         s.out_ord = idx->s_ord.as<uint32_t>();
         s.out_dist = idx->s_dist.as<float>();
         HG_TRY(launch_select(s, st));
-        hipLaunchKernelGGL(filter_each_decode_kernel, dim3(static_cast<unsigned>((cnt + 255) / 256)), dim3(256), 0, st,
-                           idx->s_ord.as<uint32_t>(), idx->s_dist.as<float>(), cnt, k, us, d_ids + q0 * k, d_dist + q0 * k);
+        // position in the list -> row id; Each decides by the union word what is padding, and writes the distances with it
+        const dim3 dgrid(static_cast<unsigned>((cnt + 255) / 256));
+        if (each) {
+            hipLaunchKernelGGL(filter_each_decode_kernel, dgrid, dim3(256), 0, st, s.out_ord, s.out_dist, cnt, k, us, d_ids + q0 * k, d_dist + q0 * k);
+        } else {
+            hipLaunchKernelGGL(filter_decode_kernel, dgrid, dim3(256), 0, st, s.out_ord, cnt, f.pass_ids, pmax, d_ids + q0 * k);
+            HG_HIP(hipMemcpyAsync(d_dist + q0 * k, s.out_dist, sizeof(float) * cnt, hipMemcpyDeviceToDevice, st));
+        }
         HG_HIP(hipGetLastError());
     }
     return 0;
@@ -2536,29 +2508,24 @@ static int exact_knn_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, i
         HG_TRY(pad_queries(idx, d_Q, idx->dim, nq, st));
         HG_TRY(tile_topk_all(idx, idx->s_qp.as<float>(), idx->s_qn.as<float>(), nq, idx->d_base, idx->d_norms, idx->n, k,
                              st, PROF_IVF_SCAN));
-        int64_t cnt = static_cast<int64_t>(nq) * k;
-        hipLaunchKernelGGL(ord_to_ids_kernel, dim3(static_cast<unsigned>((cnt + 255) / 256)), dim3(256), 0, st,
-                           idx->s_ord.as<uint32_t>(), cnt, d_ids);
-        HG_HIP(hipGetLastError());
-        HG_HIP(hipMemcpyAsync(d_dist, idx->s_dist.p, sizeof(float) * cnt, hipMemcpyDeviceToDevice, st));
-        return 0;
+    } else {
+        ScanArgs a;
+        memset(&a, 0, sizeof(a));
+        a.rows = idx->d_base;
+        a.row_norms = idx->d_norms;
+        a.ld = idx->ld;
+        a.nrows_all = idx->n;
+        a.Q = d_Q;
+        a.qld = idx->dim;
+        a.q_norms = nullptr;
+        a.dim = idx->dim;
+        a.metric = idx->metric;
+        a.pairs = nullptr;
+        a.k = k;
+        a.role = ROLE_EXACT;
+        HG_TRY(scan_topk(idx, a, nq, 1, idx->n, st, PROF_IVF_SCAN));
     }
-    ScanArgs a;
-    memset(&a, 0, sizeof(a));
-    a.rows = idx->d_base;
-    a.row_norms = idx->d_norms;
-    a.ld = idx->ld;
-    a.nrows_all = idx->n;
-    a.Q = d_Q;
-    a.qld = idx->dim;
-    a.q_norms = nullptr;
-    a.dim = idx->dim;
-    a.metric = idx->metric;
-    a.pairs = nullptr;
-    a.k = k;
-    a.role = ROLE_EXACT;
-    HG_TRY(scan_topk(idx, a, nq, 1, idx->n, st, PROF_IVF_SCAN));
-    int64_t cnt = static_cast<int64_t>(nq) * k;
+    const int64_t cnt = static_cast<int64_t>(nq) * k;
     hipLaunchKernelGGL(ord_to_ids_kernel, dim3(static_cast<unsigned>((cnt + 255) / 256)), dim3(256), 0, st,
                        idx->s_ord.as<uint32_t>(), cnt, d_ids);
     HG_HIP(hipGetLastError());
@@ -2606,8 +2573,9 @@ int hnswgpu_exact_knn(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k,
     return call.close();
 }
 
-int hnswgpu_exact_knn_filtered_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, const uint32_t *d_allow,
-                                   int32_t *d_out_ids, float *d_out_dist, void *stream) {
+// The allow-mask through the exact scan (filtered_chain), one body for both forms of the mask.  Device arrays.
+static int exact_filtered_dev(hnswgpu_index *idx, MaskForm form, const float *d_Q, int32_t nq, int32_t k, const uint32_t *d_allow,
+                              int32_t *d_out_ids, float *d_out_dist, void *stream) {
     HG_TRY(check_search_args(idx, d_Q, nq, k, d_out_ids, d_out_dist));
     HG_REQUIRE(d_allow, HNSWGPU_EINVAL, "allow is null");
     if (nq == 0) return 0;
@@ -2615,11 +2583,12 @@ int hnswgpu_exact_knn_filtered_dev(hnswgpu_index *idx, const float *d_Q, int32_t
     hipStream_t st = static_cast<hipStream_t>(stream);
     Call call;
     HG_TRY(call.open(idx, st));
-    HG_TRY(filtered_scan_enqueue(idx, d_Q, nq, k, d_allow, -1, d_out_ids, d_out_dist, st));
+    HG_TRY(filtered_chain(idx, form, d_Q, nq, k, d_allow, kMaskCountRead, d_out_ids, d_out_dist, st));
     return call.close();
 }
 
-int hnswgpu_exact_knn_filtered(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, const uint32_t *allow,
+// Host arrays.  One caller's staged batch, its mask -- Each: its [nq][W] masks -- staged whole: no part in the call combiner.
+static int exact_filtered_host(hnswgpu_index *idx, MaskForm form, const float *Q, int32_t nq, int32_t k, const uint32_t *allow,
                                int32_t *out_ids, float *out_dist) {
     HG_TRY(check_search_args(idx, Q, nq, k, out_ids, out_dist));
     HG_REQUIRE(allow, HNSWGPU_EINVAL, "allow is null");
@@ -2633,56 +2602,35 @@ int hnswgpu_exact_knn_filtered(hnswgpu_index *idx, const float *Q, int32_t nq, i
     Call call;
     HG_TRY(call.open(idx, st));
     HG_TRY(call.stage_in(Q, nq, k));
-    const size_t mbytes = sizeof(uint32_t) * static_cast<size_t>((idx->n + 31) / 32);
-    HG_TRY(idx->s_fmask.ensure(mbytes));
-    HG_HIP(hipMemcpyAsync(idx->s_fmask.p, allow, mbytes, hipMemcpyHostToDevice, st));
-    const int64_t p = mask_popcount(allow, idx->n);  // on the host, while the upload is in flight
+    HG_TRY(call.stage_mask(allow, form, nq));
+    // Single: counted on the host, while the upload is in flight (Each: the chain reads the groups' counts back)
+    const int64_t p = form == MaskForm::Single ? mask_popcount(allow, idx->n) : kMaskCountRead;
     if (p == 0) {
         fill_empty(out_ids, out_dist, cnt);
         HG_TRY(call.sync());
         return call.close();
     }
-    HG_TRY(filtered_scan_enqueue(idx, idx->s_q.as<float>(), nq, k, idx->s_fmask.as<uint32_t>(), p, idx->s_ids.as<int32_t>(),
-                                 idx->s_outd.as<float>(), st));
+    HG_TRY(filtered_chain(idx, form, idx->s_q.as<float>(), nq, k, idx->s_fmask.as<uint32_t>(), p, idx->s_ids.as<int32_t>(),
+                          idx->s_outd.as<float>(), st));
     HG_TRY(call.stage_out(out_ids, out_dist, cnt));
     return call.close();
 }
 
+int hnswgpu_exact_knn_filtered_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, const uint32_t *d_allow,
+                                   int32_t *d_out_ids, float *d_out_dist, void *stream) {
+    return exact_filtered_dev(idx, MaskForm::Single, d_Q, nq, k, d_allow, d_out_ids, d_out_dist, stream);
+}
+int hnswgpu_exact_knn_filtered(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, const uint32_t *allow,
+                               int32_t *out_ids, float *out_dist) {
+    return exact_filtered_host(idx, MaskForm::Single, Q, nq, k, allow, out_ids, out_dist);
+}
 int hnswgpu_exact_knn_filtered_each_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, const uint32_t *d_allow_each,
                                         int32_t *d_out_ids, float *d_out_dist, void *stream) {
-    HG_TRY(check_search_args(idx, d_Q, nq, k, d_out_ids, d_out_dist));
-    HG_REQUIRE(d_allow_each, HNSWGPU_EINVAL, "allow is null");
-    if (nq == 0) return 0;
-    HG_REQUIRE(idx->n > 0, HNSWGPU_ESTATE, "empty index: use the host entry point");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    Call call;
-    HG_TRY(call.open(idx, st));
-    HG_TRY(filtered_each_enqueue(idx, d_Q, nq, k, d_allow_each, d_out_ids, d_out_dist, st));
-    return call.close();
+    return exact_filtered_dev(idx, MaskForm::Each, d_Q, nq, k, d_allow_each, d_out_ids, d_out_dist, stream);
 }
-
-// One caller's staged batch, as hnswgpu_exact_knn_filtered: no part in the call combiner.
 int hnswgpu_exact_knn_filtered_each(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, const uint32_t *allow_each,
                                     int32_t *out_ids, float *out_dist) {
-    HG_TRY(check_search_args(idx, Q, nq, k, out_ids, out_dist));
-    HG_REQUIRE(allow_each, HNSWGPU_EINVAL, "allow is null");
-    if (nq == 0) return 0;
-    const int64_t cnt = static_cast<int64_t>(nq) * k;
-    if (idx->n == 0) {
-        fill_empty(out_ids, out_dist, cnt);
-        return 0;
-    }
-    hipStream_t st = idx->stream;
-    Call call;
-    HG_TRY(call.open(idx, st));
-    HG_TRY(call.stage_in(Q, nq, k));
-    const size_t mbytes = sizeof(uint32_t) * static_cast<size_t>((idx->n + 31) / 32) * static_cast<size_t>(nq);
-    HG_TRY(idx->s_fmask.ensure(mbytes));
-    HG_HIP(hipMemcpyAsync(idx->s_fmask.p, allow_each, mbytes, hipMemcpyHostToDevice, st));
-    HG_TRY(filtered_each_enqueue(idx, idx->s_q.as<float>(), nq, k, idx->s_fmask.as<uint32_t>(), idx->s_ids.as<int32_t>(),
-                                 idx->s_outd.as<float>(), st));
-    HG_TRY(call.stage_out(out_ids, out_dist, cnt));
-    return call.close();
+    return exact_filtered_host(idx, MaskForm::Each, Q, nq, k, allow_each, out_ids, out_dist);
 }
 
 int hnswgpu_merge_lists_dev(int32_t device, const int32_t *d_ids, const float *d_dist, int32_t nshard, int32_t nq,

@@ -76,6 +76,10 @@ struct DevBuf {
 
 enum { PROF_IVF_SCAN = 0, PROF_HNSW = 1, PROF_ASSIGN = 2, PROF_N = 3 };
 
+// The form of a filtered call's allow-mask (include/hnswgpu.h), W = (n + 31) / 32 words: one mask shared by the call's queries,
+// or [nq][W], one per query
+enum class MaskForm { Single, Each };
+
 }  // namespace hg
 
 struct hnswgpu_index {
@@ -509,6 +513,8 @@ public:
     // the two; then ids and distances down and sync()
     int stage_in(const float *Q, int32_t nq, int32_t k);
     int stage_out(int32_t *out_ids, float *out_dist, int64_t cnt);
+    // ... and of a filtered one: the caller's mask words (W, or nq * W: one mask per query) up into s_fmask
+    int stage_mask(const uint32_t *allow, MaskForm form, int32_t nq);
 private:
     hipError_t leave();
     hnswgpu_index *idx_ = nullptr;
@@ -524,7 +530,7 @@ int64_t mask_popcount(const uint32_t *allow, int64_t n);  // passing rows among 
 // the first k passing entries of every query's list ids_in / dist_in [nq][kk] (-1 padded), -1 / +inf padded (filter_take_kernel);
 // allow_stride: words between the masks of two queries, 0 = one mask shared by all
 int launch_filter_take(const int32_t *ids_in, const float *dist_in, int32_t nq, int32_t kk, int32_t k, const uint32_t *d_allow,
-                       int64_t n, int32_t *d_out_ids, float *d_out_dist, hipStream_t st, int64_t allow_stride = 0);
+                       int64_t n, int32_t *d_out_ids, float *d_out_dist, hipStream_t st, int64_t allow_stride);
 
 // The set bits of a `len`-bit device mask as an ascending list in s_fpass (engine.hip).  p_host: the caller's count, or
 constexpr int64_t kMaskCountRead = -1;    // ... read the total back once (the calling thread waits for `st`)

@@ -51,7 +51,7 @@ struct MaskArgs {
     int32_t *pass_ids;          // [cap]
     int64_t cap;                // entries pass_ids holds (the count the scan produced)
     unsigned long long *total;  // [1]: passing rows
-    // several masks in one launch, mask g = blockIdx.y (all 0: the one mask of today's callers)
+    // several masks in one launch, mask g = blockIdx.y (engine.hip: mask_count_scan / mask_scatter; mask_compact is one mask)
     int64_t allow_stride;  // words between two masks
     int64_t blk_stride;    // entries of blk between two masks
     int64_t pass_stride;   // entries of pass_ids between two lists

@@ -1329,21 +1329,21 @@ int hnswgpu_hnsw_last_order(hnswgpu_index *idx, int32_t *order, int32_t *keys, i
 
 // Filtered search (api/protocol.clj:34-41,97-102): the unfiltered traversal at ef for kk = min(ef, 1024) results per query
 // into s_fids / s_fdist, then the first k passing entries of every list (filter_kernels.hpp: filter_take_kernel).
-// allow_stride: words between the masks of two queries (one mask per query), 0 = the call's one mask.
-static int hnsw_filtered_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t ef, const uint32_t *d_allow,
-                                 int32_t *d_ids, float *d_dist, int64_t *d_stats, hipStream_t st, int64_t allow_stride = 0) {
+// The take reads query q's mask at d_allow + q * W (Each), or the call's one mask (Single).
+static int hnsw_filtered_enqueue(hnswgpu_index *idx, MaskForm form, const float *d_Q, int32_t nq, int32_t k, int32_t ef,
+                                 const uint32_t *d_allow, int32_t *d_ids, float *d_dist, int64_t *d_stats, hipStream_t st) {
     const int32_t kk = ef < 1024 ? ef : 1024;
     const size_t cnt = static_cast<size_t>(nq) * kk;
     HG_TRY(idx->s_fids.ensure(sizeof(int32_t) * cnt));
     HG_TRY(idx->s_fdist.ensure(sizeof(float) * cnt));
     HG_TRY(search_enqueue(idx, d_Q, nq, kk, ef, idx->s_fids.as<int32_t>(), idx->s_fdist.as<float>(), d_stats, st));
     return launch_filter_take(idx->s_fids.as<int32_t>(), idx->s_fdist.as<float>(), nq, kk, k, d_allow, idx->n, d_ids, d_dist, st,
-                              allow_stride);
+                              form == MaskForm::Each ? (idx->n + 31) / 32 : 0);
 }
 
-// The two entry points of the filtered traversal; each: one mask per query ([nq][W] words) instead of the call's one mask.
-static int hnsw_filtered_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t ef, const uint32_t *d_allow,
-                             int32_t *d_out_ids, float *d_out_dist, int64_t *d_stats, void *stream, bool each) {
+// The two entry points of the filtered traversal, one body each for both forms of the mask.
+static int hnsw_filtered_dev(hnswgpu_index *idx, MaskForm form, const float *d_Q, int32_t nq, int32_t k, int32_t ef,
+                             const uint32_t *d_allow, int32_t *d_out_ids, float *d_out_dist, int64_t *d_stats, void *stream) {
     HG_TRY(check_hnsw_args(idx, d_Q, nq, k, &ef, d_out_ids, d_out_dist));
     HG_REQUIRE(d_allow, HNSWGPU_EINVAL, "allow is null");
     if (nq == 0) return 0;
@@ -1351,13 +1351,13 @@ static int hnsw_filtered_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, i
     hipStream_t st = static_cast<hipStream_t>(stream);
     Call call;
     HG_TRY(call.open(idx, st));
-    HG_TRY(hnsw_filtered_enqueue(idx, d_Q, nq, k, ef, d_allow, d_out_ids, d_out_dist, d_stats, st, each ? (idx->n + 31) / 32 : 0));
+    HG_TRY(hnsw_filtered_enqueue(idx, form, d_Q, nq, k, ef, d_allow, d_out_ids, d_out_dist, d_stats, st));
     return call.close();
 }
 
 // One caller's staged batch: masks differ between callers, so this entry takes no part in the call combiner.
-static int hnsw_filtered_host(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t ef, const uint32_t *allow,
-                              int32_t *out_ids, float *out_dist, int64_t *stats, bool each) {
+static int hnsw_filtered_host(hnswgpu_index *idx, MaskForm form, const float *Q, int32_t nq, int32_t k, int32_t ef,
+                              const uint32_t *allow, int32_t *out_ids, float *out_dist, int64_t *stats) {
     HG_TRY(check_hnsw_args(idx, Q, nq, k, &ef, out_ids, out_dist));
     HG_REQUIRE(allow, HNSWGPU_EINVAL, "allow is null");
     if (nq == 0) return 0;
@@ -1373,17 +1373,14 @@ static int hnsw_filtered_host(hnswgpu_index *idx, const float *Q, int32_t nq, in
     // under the lock: a concurrent set_graph / hnsw_build may have replaced the graph since the argument check
     HG_REQUIRE(idx->has_graph && idx->n > 0, HNSWGPU_ESTATE, "index has no graph (call hnswgpu_hnsw_build / hnswgpu_set_graph)");
     HG_TRY(call.stage_in(Q, nq, k));
-    const int64_t W = (idx->n + 31) / 32;
-    const size_t mbytes = sizeof(uint32_t) * static_cast<size_t>(W) * (each ? static_cast<size_t>(nq) : 1);
-    HG_TRY(idx->s_fmask.ensure(mbytes));
-    HG_HIP(hipMemcpyAsync(idx->s_fmask.p, allow, mbytes, hipMemcpyHostToDevice, st));
+    HG_TRY(call.stage_mask(allow, form, nq));
     int64_t *d_stats = nullptr;
     if (stats) {
         HG_TRY(idx->s_stats.ensure(sizeof(int64_t) * 2 * nq));
         d_stats = idx->s_stats.as<int64_t>();
     }
-    HG_TRY(hnsw_filtered_enqueue(idx, idx->s_q.as<float>(), nq, k, ef, idx->s_fmask.as<uint32_t>(), idx->s_ids.as<int32_t>(),
-                                 idx->s_outd.as<float>(), d_stats, st, each ? W : 0));
+    HG_TRY(hnsw_filtered_enqueue(idx, form, idx->s_q.as<float>(), nq, k, ef, idx->s_fmask.as<uint32_t>(), idx->s_ids.as<int32_t>(),
+                                 idx->s_outd.as<float>(), d_stats, st));
     if (stats) HG_HIP(hipMemcpyAsync(stats, d_stats, sizeof(int64_t) * 2 * nq, hipMemcpyDeviceToHost, st));
     HG_TRY(call.stage_out(out_ids, out_dist, cnt));
     return call.close();
@@ -1392,21 +1389,21 @@ static int hnsw_filtered_host(hnswgpu_index *idx, const float *Q, int32_t nq, in
 int hnswgpu_hnsw_search_filtered_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t ef,
                                      const uint32_t *d_allow, int32_t *d_out_ids, float *d_out_dist, int64_t *d_stats,
                                      void *stream) {
-    return hnsw_filtered_dev(idx, d_Q, nq, k, ef, d_allow, d_out_ids, d_out_dist, d_stats, stream, false);
+    return hnsw_filtered_dev(idx, MaskForm::Single, d_Q, nq, k, ef, d_allow, d_out_ids, d_out_dist, d_stats, stream);
 }
 int hnswgpu_hnsw_search_filtered(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t ef, const uint32_t *allow,
                                  int32_t *out_ids, float *out_dist, int64_t *stats) {
-    return hnsw_filtered_host(idx, Q, nq, k, ef, allow, out_ids, out_dist, stats, false);
+    return hnsw_filtered_host(idx, MaskForm::Single, Q, nq, k, ef, allow, out_ids, out_dist, stats);
 }
 // One mask per query (include/hnswgpu.h): the same traversal and take; the take reads allow_each + q * W.
 int hnswgpu_hnsw_search_filtered_each_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t ef,
                                           const uint32_t *d_allow_each, int32_t *d_out_ids, float *d_out_dist,
                                           int64_t *d_stats, void *stream) {
-    return hnsw_filtered_dev(idx, d_Q, nq, k, ef, d_allow_each, d_out_ids, d_out_dist, d_stats, stream, true);
+    return hnsw_filtered_dev(idx, MaskForm::Each, d_Q, nq, k, ef, d_allow_each, d_out_ids, d_out_dist, d_stats, stream);
 }
 int hnswgpu_hnsw_search_filtered_each(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t ef,
                                       const uint32_t *allow_each, int32_t *out_ids, float *out_dist, int64_t *stats) {
-    return hnsw_filtered_host(idx, Q, nq, k, ef, allow_each, out_ids, out_dist, stats, true);
+    return hnsw_filtered_host(idx, MaskForm::Each, Q, nq, k, ef, allow_each, out_ids, out_dist, stats);
 }
 
 }  // extern "C"

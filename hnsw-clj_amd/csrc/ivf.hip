@@ -1676,9 +1676,7 @@ static int ivf_search_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, 
 //   unfiltered GEMV scan's: it does not grow with nq x n.  The host knows a pair's positions, so the chunks are scan_kernel's.
 // Same step (ivf_gathered_step), same keys, same merge, same decode: the top k of a query's keys is the same set whatever the
 // chunking, so the two forms agree bit for bit.
-enum class IvfMasks { Single, Each };
-
-static int ivf_filtered_chain(hnswgpu_index *idx, IvfMasks form, const float *d_Q, int32_t nq, int32_t k, int32_t nprobe,
+static int ivf_filtered_chain(hnswgpu_index *idx, MaskForm form, const float *d_Q, int32_t nq, int32_t k, int32_t nprobe,
                               const uint32_t *d_allow, int64_t p_host, int32_t *d_out_ids, float *d_out_dist, int32_t *d_out_probes,
                               hipStream_t st) {
     const int64_t L = idx->n;  // list positions: list_off[nlist] (validate_lists)
@@ -1695,7 +1693,7 @@ static int ivf_filtered_chain(hnswgpu_index *idx, IvfMasks form, const float *d_
     p.list_order = p.order_run > 0;
     HG_REQUIRE(p.npairs < 2147483647LL, HNSWGPU_ELIMIT, "too many (query, list) pairs (%lld)", (long long)p.npairs);
     int32_t chunk_rows = 0, nchunks = 0;
-    if (form == IvfMasks::Single) {
+    if (form == MaskForm::Single) {
         // Chunking without the filtered list lengths: tiles of chunk_rows passing positions, workgroup c of a pair takes the tiles
         // c, c + nchunks, ...; both from the mean list length, scaled by the selectivity where the caller has counted it
         int64_t mean = ivf_mean_len(idx);
@@ -1713,7 +1711,7 @@ static int ivf_filtered_chain(hnswgpu_index *idx, IvfMasks form, const float *d_
     HG_TRY(idx->s_partial.ensure(sizeof(uint64_t) * static_cast<size_t>(keys_per_query) * nq));
     int32_t *probes_buf = d_out_probes ? d_out_probes : idx->s_grp.as<int32_t>();
     int32_t *order_buf = idx->s_grp.as<int32_t>() + p.npairs + nq + 16;
-    if (form == IvfMasks::Single) {
+    if (form == MaskForm::Single) {
         // 1. the mask in list order -> ascending passing positions -> their number below every list's first
         HG_TRY(idx->s_flmask.ensure(sizeof(uint32_t) * static_cast<size_t>((L + 31) / 32)));
         HG_TRY(idx->s_ffoff.ensure(sizeof(int32_t) * (static_cast<size_t>(idx->nlist) + 1)));
@@ -1732,7 +1730,7 @@ static int ivf_filtered_chain(hnswgpu_index *idx, IvfMasks form, const float *d_
     IvfEachArgs each;
     memset(&single, 0, sizeof(single));
     memset(&each, 0, sizeof(each));
-    IvfGatherArgs &a = form == IvfMasks::Single ? static_cast<IvfGatherArgs &>(single) : static_cast<IvfGatherArgs &>(each);
+    IvfGatherArgs &a = form == MaskForm::Single ? static_cast<IvfGatherArgs &>(single) : static_cast<IvfGatherArgs &>(each);
     a.rows = idx->d_lrows;
     a.row_norms = idx->d_lnorms;
     a.ld = idx->ld;
@@ -1756,7 +1754,7 @@ static int ivf_filtered_chain(hnswgpu_index *idx, IvfMasks form, const float *d_
     }
     hipEvent_t e0;
     prof_begin(idx, PROF_IVF_SCAN, st, &e0);
-    if (form == IvfMasks::Single) {
+    if (form == MaskForm::Single) {
         single.probes = probes_buf;
         single.pass_pos = idx->s_fpass.as<int32_t>();
         single.foff = idx->s_ffoff.as<int32_t>();
@@ -2377,7 +2375,7 @@ int hnswgpu_ivf_search(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k
 
 // The allow-mask through the list scan (ivf_filtered_chain), one body for both forms of the mask.  Device arrays: enqueues only,
 // reads nothing back.
-static int ivf_filtered_dev(hnswgpu_index *idx, IvfMasks form, const float *d_Q, int32_t nq, int32_t k, int32_t nprobe,
+static int ivf_filtered_dev(hnswgpu_index *idx, MaskForm form, const float *d_Q, int32_t nq, int32_t k, int32_t nprobe,
                             const uint32_t *d_allow, int32_t *d_out_ids, float *d_out_dist, void *stream) {
     HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
     HG_REQUIRE(d_allow, HNSWGPU_EINVAL, "allow is null");
@@ -2394,7 +2392,7 @@ static int ivf_filtered_dev(hnswgpu_index *idx, IvfMasks form, const float *d_Q,
 
 // Host arrays.  One caller's batch, its mask -- Each: its [nq][W] masks (as hnswgpu_exact_knn_filtered_each) -- staged whole:
 // masks differ between callers, so the call is not combined with concurrent ones (as hnswgpu_hnsw_search_filtered).
-static int ivf_filtered_host(hnswgpu_index *idx, IvfMasks form, const float *Q, int32_t nq, int32_t k, int32_t nprobe,
+static int ivf_filtered_host(hnswgpu_index *idx, MaskForm form, const float *Q, int32_t nq, int32_t k, int32_t nprobe,
                              const uint32_t *allow, int32_t *out_ids, float *out_dist, int32_t *out_probes) {
     HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
     HG_REQUIRE(allow, HNSWGPU_EINVAL, "allow is null");
@@ -2402,7 +2400,7 @@ static int ivf_filtered_host(hnswgpu_index *idx, IvfMasks form, const float *Q, 
     if (nq == 0) return 0;
     if (idx->n == 0) return hnswgpu_ivf_search(idx, Q, nq, k, nprobe, out_ids, out_dist, out_probes);
     const int64_t cnt = static_cast<int64_t>(nq) * k;
-    const int64_t pass = form == IvfMasks::Single ? mask_popcount(allow, idx->n) : -1;
+    const int64_t pass = form == MaskForm::Single ? mask_popcount(allow, idx->n) : -1;
     if (pass == 0 && !out_probes) {  // nothing can be returned, and nobody asks where the queries were routed
         fill_empty(out_ids, out_dist, cnt);
         return 0;
@@ -2414,9 +2412,7 @@ static int ivf_filtered_host(hnswgpu_index *idx, IvfMasks form, const float *Q, 
     HG_REQUIRE(idx->nlist > 0 && idx->n > 0, HNSWGPU_ESTATE, "index has no IVF lists (call hnswgpu_ivf_build / hnswgpu_set_ivf)");
     const int32_t np = std::min(nprobe, idx->nlist);
     HG_TRY(call.stage_in(Q, nq, k));
-    const size_t mbytes = sizeof(uint32_t) * static_cast<size_t>((idx->n + 31) / 32) * (form == IvfMasks::Single ? 1 : static_cast<size_t>(nq));
-    HG_TRY(idx->s_fmask.ensure(mbytes));
-    HG_HIP(hipMemcpyAsync(idx->s_fmask.p, allow, mbytes, hipMemcpyHostToDevice, st));
+    HG_TRY(call.stage_mask(allow, form, nq));
     if (out_probes) HG_TRY(idx->s_probes.ensure(sizeof(int32_t) * static_cast<size_t>(nq) * np));
     HG_TRY(ivf_filtered_chain(idx, form, idx->s_q.as<float>(), nq, k, np, idx->s_fmask.as<uint32_t>(), pass, idx->s_ids.as<int32_t>(),
                               idx->s_outd.as<float>(), out_probes ? idx->s_probes.as<int32_t>() : nullptr, st));
@@ -2427,19 +2423,19 @@ static int ivf_filtered_host(hnswgpu_index *idx, IvfMasks form, const float *Q, 
 
 int hnswgpu_ivf_search_filtered_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t nprobe,
                                     const uint32_t *d_allow, int32_t *d_out_ids, float *d_out_dist, void *stream) {
-    return ivf_filtered_dev(idx, IvfMasks::Single, d_Q, nq, k, nprobe, d_allow, d_out_ids, d_out_dist, stream);
+    return ivf_filtered_dev(idx, MaskForm::Single, d_Q, nq, k, nprobe, d_allow, d_out_ids, d_out_dist, stream);
 }
 int hnswgpu_ivf_search_filtered(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t nprobe,
                                 const uint32_t *allow, int32_t *out_ids, float *out_dist, int32_t *out_probes) {
-    return ivf_filtered_host(idx, IvfMasks::Single, Q, nq, k, nprobe, allow, out_ids, out_dist, out_probes);
+    return ivf_filtered_host(idx, MaskForm::Single, Q, nq, k, nprobe, allow, out_ids, out_dist, out_probes);
 }
 int hnswgpu_ivf_search_filtered_each_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t nprobe,
                                          const uint32_t *d_allow_each, int32_t *d_out_ids, float *d_out_dist, void *stream) {
-    return ivf_filtered_dev(idx, IvfMasks::Each, d_Q, nq, k, nprobe, d_allow_each, d_out_ids, d_out_dist, stream);
+    return ivf_filtered_dev(idx, MaskForm::Each, d_Q, nq, k, nprobe, d_allow_each, d_out_ids, d_out_dist, stream);
 }
 int hnswgpu_ivf_search_filtered_each(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t nprobe,
                                      const uint32_t *allow_each, int32_t *out_ids, float *out_dist, int32_t *out_probes) {
-    return ivf_filtered_host(idx, IvfMasks::Each, Q, nq, k, nprobe, allow_each, out_ids, out_dist, out_probes);
+    return ivf_filtered_host(idx, MaskForm::Each, Q, nq, k, nprobe, allow_each, out_ids, out_dist, out_probes);
 }
 
 }  // extern "C"

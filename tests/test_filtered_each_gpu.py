@@ -229,6 +229,69 @@ def test_each_slices_by_filter_each_mb(native_lib, oracle, tune, shape, min_slic
     assert_exact(gi[:3], gd[:3], ei, ed, "sliced")
 
 
+@pytest.mark.parametrize("shape", [(33, 7), (300, 768), (70, 3072)], ids=lambda s: "%dx%d" % s)
+@pytest.mark.parametrize("metric", ["cosine", "l2"])
+def test_single_mask_call_equals_each_call_with_that_mask_for_every_query(native_lib, metric, shape):
+    """Both forms of the mask run one chain, so they are pinned against each other directly: exact_knn_filtered(Q, k, m) and
+    exact_knn_filtered_each(Q, k, [m] * 70) agree in ids and distance bits, host and device entries.  32 / 32 / 8 queries per
+    group: 70 queries are 3 / 3 / 9 groups with a ragged last one.  Masks: p not a multiple of 4 (a dense stride that differs
+    between the forms), none, only row n - 1, all.  The single call moves no launch counter and times one scan (none at p = 0);
+    the each call counts its groups -- every one, since every group's union is m, and none at p = 0 -- and nothing else."""
+    import torch
+
+    from hnsw_clj_amd import datagen, engine
+
+    n, dim = shape
+    base = datagen.generate_dataset(n, dim)
+    Q = datagen.generate_dataset(NQ_MAX, dim, seed=43)
+    Qd = torch.from_numpy(Q).to(torch.device("cuda", 0))
+    tq = 32 if dim <= 1024 else (16 if dim <= 2048 else 8)
+    odd = np.random.default_rng(77).random(n) < 0.5
+    while odd.sum() % 4 == 0 or not odd.any():
+        odd[np.flatnonzero(~odd)[0]] = True
+    last = np.zeros(n, np.bool_)
+    last[n - 1] = True
+    counters = lambda: [native_lib.debug_counter(c) for c in native_lib.LAUNCH_COUNTERS]  # noqa: E731
+    at = native_lib.LAUNCH_COUNTERS.index("filtered_each_groups")
+    with engine.Index(base, metric, 0) as idx:
+        idx.set_profiling(True)
+        for name, bits in (("odd", odd), ("none", np.zeros(n, np.bool_)), ("last", last), ("all", np.ones(n, np.bool_))):
+            p = int(bits.sum())
+            assert name != "odd" or p % 4
+            m = _garbage_past_n(engine.pack_mask(bits, n)[None, :], n, 3)[0]
+            rows = np.repeat(m[None, :], NQ_MAX, axis=0)
+            md, rd = _dev(torch, m), _dev(torch, rows)
+            torch.cuda.synchronize()
+            for k in (1, 100):
+                what = "%s %dx%d mask %s (p %d) k %d" % (metric, n, dim, name, p, k)
+                idx.get_profile(engine.PROF_IVF_SCAN)
+                c0 = counters()
+                si, sd = idx.exact_knn_filtered(Q, k, m)
+                assert counters() == c0, what + ": the single-mask call moved a launch counter"
+                assert idx.get_profile(engine.PROF_IVF_SCAN)[1] == (1 if p else 0), what + ": scans of the single-mask call"
+                ei, ed = idx.exact_knn_filtered_each(Q, k, rows)
+                c1 = counters()
+                want = list(c0)
+                want[at] += -(-NQ_MAX // tq) if p else 0
+                assert c1 == want, what + ": launch counters of the each call"
+                assert np.array_equal(si, ei) and np.array_equal(sd.view(np.uint32), ed.view(np.uint32)), what + " host"
+                filled = min(p, k)
+                assert (si[:, :filled] >= 0).all() and (si[:, filled:] == -1).all() and np.isposinf(sd[:, filled:]).all(), what
+                if name == "last":
+                    assert (si[:, 0] == n - 1).all(), what
+                idx.get_profile(engine.PROF_IVF_SCAN)
+                di, dd = idx.exact_knn_filtered_dev(Qd, k, md)
+                torch.cuda.synchronize()
+                assert counters() == c1, what + ": the single-mask device call moved a launch counter"
+                assert idx.get_profile(engine.PROF_IVF_SCAN)[1] == (1 if p else 0), what + ": scans of the single-mask device call"
+                gi, gd = idx.exact_knn_filtered_each_dev(Qd, k, rd)
+                torch.cuda.synchronize()
+                want[at] += -(-NQ_MAX // tq) if p else 0
+                assert counters() == want, what + ": launch counters of the each device call"
+                assert torch.equal(di, gi) and torch.equal(dd.view(torch.int32), gd.view(torch.int32)), what + " dev"
+                assert np.array_equal(di.cpu().numpy(), si) and np.array_equal(dd.cpu().numpy().view(np.uint32), sd.view(np.uint32)), what
+
+
 # ---- the traversal path -----------------------------------------------------------------------------------------------------
 N, DIM, K, NQ_H = 1000, 128, 10, 70
 EFS = [50, 200]

@@ -255,7 +255,7 @@ def test_mask_scan_carries_past_1024_blocks(large, oracle):
 
 @pytest.mark.parametrize("metric", ["l2", "cosine"])
 def test_filtered_exact_scan_in_query_slices(large, oracle, metric):
-    """filtered_scan_enqueue bounds its dense [queries][passing rows] scratch to 2 GiB: with p >= 2^20 passing rows a slice
+    """filtered_chain bounds the single-mask form's dense [queries][passing rows] scratch to 2 GiB: with p >= 2^20 passing rows a slice
     holds at most 512 queries, so 513 queries run in more than one slice, and every slice offsets the padded queries, their
     norms and the result arrays by its first query.  The 513 queries are three distinct ones of three different norms: every
     result row equals the oracle's for the query it repeats, wherever the slices are cut.  Two orders: the three repeated
@@ -293,7 +293,7 @@ def test_filtered_exact_scan_in_query_slices(large, oracle, metric):
             Q = np.ascontiguousarray(Q3[rep])
             Qd = torch.from_numpy(Q).to(dev)
             torch.cuda.synchronize()
-            # The gathered scan is the only launch of this call timed under PROF_IVF_SCAN, once per slice (filtered_scan_enqueue):
+            # The gathered scan is the only launch of this call timed under PROF_IVF_SCAN, once per slice (filtered_chain):
             # the count of timed launches is the number of slices.  Should anything else come to be timed there, count anew.
             idx.set_profiling(True)
             idx.get_profile(engine.PROF_IVF_SCAN, reset=True)
