@@ -18,6 +18,9 @@
      (top-k-distances index query-vec k)                             ; simd-optimized/top-k-distances
      (add-vector! index new-data)                                    ; hnsw.api/add-vector!, insert-single on a live index
      (add-ivf-vectors! index new-data)                               ; the same for a live IVF-FLAT index: hnswgpu_ivf_add
+     (build-lsh-index data :metric :cosine)                          ; hnsw.ann.hash.hybrid-lsh/build-lsh-index: (Random. 42), 8 x 12 bits
+     (search-lsh index query-vec k :mode :balanced)                  ; hybrid-lsh/search-knn (search-hybrid-multiprobe)
+     (search-lsh-batch index queries k :mode :balanced)
      (from-ultra-graph graph)                                        ; a graph built by the reference's own insert-single
      (from-ivf-flat-index ivf)                                       ; an IVFFlatIndex built by the reference's own k-means
      (save idx path) / (load-index path ids)                         ; helper/index-io save-index / load-index
@@ -130,6 +133,55 @@
     (check (.invokeWithArguments ^MethodHandle @h-ivfadd
                                  [(:handle idx) (floats-of arena (mapv second new-data) (:dim idx)) (long (count new-data))])))
   (update idx :ids into (map first new-data)))
+
+;; ---- hybrid LSH (hnsw.ann.hash.hybrid-lsh): hnswgpu_lsh_build / hnswgpu_lsh_search ----
+(def ^:private h-lshbuild  (delay (fn-handle "hnswgpu_lsh_build" (FunctionDescriptor/of I (into-array [P I I I L])))))
+(def ^:private h-lshset    (delay (fn-handle "hnswgpu_set_lsh" (FunctionDescriptor/of I (into-array [P P I I])))))
+(def ^:private h-lshsearch (delay (fn-handle "hnswgpu_lsh_search" (FunctionDescriptor/of I (into-array [P P I I I I I I P P])))))
+
+(defn build-lsh-index
+  "hnsw.ann.hash.hybrid-lsh/build-lsh-index (src/hnsw/ann/hash/hybrid_lsh.clj:66-145): data = seq of [id ^doubles vector].  The
+   defaults are the reference's constants (:12-14) and its (Random. 42): the same hyperplanes, rounded to float.  :planes, a seq of
+   tables of `bits` ^doubles rows, installs the caller's matrices instead (hnswgpu_set_lsh).  The metric is the handle's (the
+   reference computes cosine whatever :distance-fn says)."
+  [data & {:keys [metric tables bits projection-dim seed planes]
+           :or {metric :cosine tables 8 bits 12 projection-dim 64 seed 42}}]
+  (let [idx (create data metric :hybrid-lsh)]
+    (if planes
+      (with-open [arena (Arena/ofConfined)]
+        (check (.invokeWithArguments ^MethodHandle @h-lshset
+                                     [(:handle idx) (floats-of arena (vec (apply concat planes)) (:dim idx))
+                                      (int (count planes)) (int (count (first planes)))])))
+      (check (.invokeWithArguments ^MethodHandle @h-lshbuild
+                                   [(:handle idx) (int tables) (int bits) (int projection-dim) (long seed)])))
+    idx))
+
+(def ^:private lsh-modes {:turbo [2 1] :fast [4 1] :balanced [6 2] :accurate [8 3] :precise [8 4]})   ; hybrid_lsh.clj:350-364
+
+(declare results)
+
+(defn search-lsh-batch
+  "search-hybrid-multiprobe (hybrid_lsh.clj:261-342, the order of its sequential branch) for a batch in one call: 2k rows of the own
+   bucket, k of every one-bit neighbour, per probed table; :mode as search-knn's (:350-364), or :num-probes / :probe-radius."
+  [idx queries k & {:keys [mode num-probes probe-radius]}]
+  (let [[p r] (lsh-modes mode (lsh-modes :balanced))
+        p (or num-probes p)
+        r (or probe-radius r)]
+    (if (empty? (:ids idx))
+      (mapv (constantly []) queries)
+      (with-open [arena (Arena/ofConfined)]
+        (let [nq (count queries)
+              q (floats-of arena (vec queries) (:dim idx))
+              ids (.allocate arena (* 4 nq k) 4)
+              ds (.allocate arena (* 4 nq k) 4)]
+          (check (.invokeWithArguments ^MethodHandle @h-lshsearch
+                                       [(:handle idx) q (int nq) (int k) (int p) (int r) (int (* 2 k)) (int k) ids ds]))
+          (mapv #(results idx ids ds % k) (range nq)))))))
+
+(defn search-lsh
+  "hybrid-lsh/search-knn (hybrid_lsh.clj:350-364) for one query."
+  [idx query-vec k & opts]
+  (first (apply search-lsh-batch idx [query-vec] k opts)))
 
 (defn- results [idx ^MemorySegment ids ^MemorySegment ds q k]
   (vec (for [i (range k)

@@ -95,6 +95,13 @@ _SIGS = {
     "hnswgpu_ivf_search_filtered_dev": ["p", "p", "i32", "i32", "i32", "p", "p", "p", "p"],
     "hnswgpu_ivf_search_filtered_each": ["p", "p", "i32", "i32", "i32", "p", "p", "p", "p"],
     "hnswgpu_ivf_search_filtered_each_dev": ["p", "p", "i32", "i32", "i32", "p", "p", "p", "p"],
+    "hnswgpu_lsh_build": ["p", "i32", "i32", "i32", "i64"],
+    "hnswgpu_set_lsh": ["p", "p", "i32", "i32"],
+    "hnswgpu_lsh_sizes": ["p", "p", "p"],
+    "hnswgpu_lsh_get": ["p", "p", "p", "p", "p"],
+    "hnswgpu_lsh_hash": ["p", "p", "i32", "p"],
+    "hnswgpu_lsh_search": ["p", "p", "i32", "i32", "i32", "i32", "i32", "i32", "p", "p"],
+    "hnswgpu_lsh_search_dev": ["p", "p", "i32", "i32", "i32", "i32", "i32", "i32", "p", "p", "p"],
     "hnswgpu_save": ["p", "p"],
     "hnswgpu_load": ["p", "i32", "p"],
     "hnswgpu_set_profiling": ["p", "i32"],

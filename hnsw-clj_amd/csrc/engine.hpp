@@ -211,6 +211,16 @@ struct hnswgpu_index {
     std::vector<int64_t> h_listoff, h_glistlen;
     std::vector<int32_t> h_listids;
 
+    // Hybrid LSH (lsh.hip, lsh_kernels.hpp): lsh_tables sign-projection hash tables of lsh_bits bits over the base rows, or none
+    // (lsh_tables == 0).  Planes [tables * bits][ld] zero padded, codes [n][tables], and per table the buckets as
+    // off[2^bits + 1] into ids[n] (rows ascending inside a bucket); the caller's planes [tables][bits][dim] for export.
+    int lsh_tables = 0, lsh_bits = 0;
+    float *d_lsh_planes = nullptr;
+    uint16_t *d_lsh_codes = nullptr;
+    int64_t *d_lsh_off = nullptr;
+    int32_t *d_lsh_ids = nullptr;
+    std::vector<float> h_lsh_planes;
+
     // scratch (grown on demand, reused across calls; calls are serialised by `mu`)
     hg::DevBuf s_q, s_partial, s_ord, s_dist, s_pairs, s_ids, s_outd, s_probes, s_stats, s_misc, s_misc2, s_vis, s_qp, s_qn, s_tile, s_grp, s_done, s_pf, s_solo, s_bk, s_heavy, s_home, s_dh, s_hord;
     // s_hord: order[nq] | keys[nq] of an ordered HNSW launch (order_kernels.hpp); the last such launch's, for hnswgpu_hnsw_last_order

@@ -2129,6 +2129,8 @@ int hnswgpu_hnsw_add(hnswgpu_index *idx, const float *rows, int64_t m, int32_t e
                "the index holds a forest: a new row has no part (rebuild with hnswgpu_hnsw_build_parts / hnswgpu_set_graph_parts)");
     HG_REQUIRE(idx->nlist == 0, HNSWGPU_ESTATE,
                "the index holds IVF lists over its present rows: add rows first, then build / install the lists");
+    HG_REQUIRE(idx->lsh_tables == 0, HNSWGPU_ESTATE,
+               "the index holds LSH tables over its present rows: add rows first, then build / install the tables");
     HG_REQUIRE(idx->M0 == 2 * idx->M, HNSWGPU_ESTATE, "hnswgpu_hnsw_add needs a graph with M0 = 2 M (as hnswgpu_hnsw_build makes)");
     const int64_t n0 = idx->n, n1 = n0 + m;
     HG_REQUIRE(n1 < 2147483647LL, HNSWGPU_ELIMIT, "the index must hold fewer than 2^31 rows");

@@ -1988,6 +1988,8 @@ int hnswgpu_ivf_add(hnswgpu_index *idx, const float *rows, int64_t m) {
     HG_REQUIRE(!idx->has_graph, HNSWGPU_ESTATE,
                "the index holds an HNSW graph: rows added to the IVF lists would be missing from the graph");
     HG_REQUIRE(idx->d_glistoff == nullptr, HNSWGPU_ESTATE, "a shard of a larger IVF index (hnswgpu_set_ivf_shard) cannot grow alone");
+    HG_REQUIRE(idx->lsh_tables == 0, HNSWGPU_ESTATE,
+               "the index holds LSH tables over its present rows: add rows first, then build / install the tables");
     const int64_t n0 = idx->n, n1 = n0 + m;
     HG_REQUIRE(n1 < 2147483647LL, HNSWGPU_ELIMIT, "the index must hold fewer than 2^31 rows");
     HG_TRY(call.quiesce());

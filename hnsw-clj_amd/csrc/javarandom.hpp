@@ -1,9 +1,12 @@
 // javarandom.hpp -- java.util.Random as the JDK documents it (48-bit LCG).  The reference seeds
 // k-means++ with (Random. 42) (src/hnsw/ann/partition/ivf_flat.clj:36) and draws HNSW levels from
-// (Random.) (src/hnsw/ultra_fast.clj:139-147); using the same generator keeps a JVM user's seeds
+// (Random.) (src/hnsw/ultra_fast.clj:139-147), and the LSH hyperplanes from (Random. 42)'s nextGaussian
+// (src/hnsw/ann/hash/hybrid_lsh.clj:24-31,80); using the same generator keeps a JVM user's seeds
 // meaningful on this engine.
 #pragma once
 #include <stdint.h>
+
+#include <cmath>
 
 namespace hg {
 
@@ -29,10 +32,30 @@ class JavaRandom {
         int64_t hi = next(26), lo = next(27);
         return static_cast<double>((hi << 27) + lo) * 0x1.0p-53;
     }
+    // nextGaussian as the JDK documents it: the polar method, two values per accepted point, the second one cached.  (The JDK
+    // takes StrictMath.log / sqrt; this is libm's -- sqrt is correctly rounded in both, the last bit of log may differ.)
+    double next_gaussian() {
+        if (have_gaussian_) {
+            have_gaussian_ = false;
+            return gaussian_;
+        }
+        double v1, v2, s;
+        do {
+            v1 = 2 * next_double() - 1;
+            v2 = 2 * next_double() - 1;
+            s = v1 * v1 + v2 * v2;
+        } while (s >= 1 || s == 0);
+        const double mul = std::sqrt(-2 * std::log(s) / s);
+        gaussian_ = v2 * mul;
+        have_gaussian_ = true;
+        return v1 * mul;
+    }
 
    private:
     static constexpr uint64_t kMask = (1ULL << 48) - 1;
     uint64_t seed_;
+    double gaussian_ = 0.0;
+    bool have_gaussian_ = false;
 };
 
 }  // namespace hg

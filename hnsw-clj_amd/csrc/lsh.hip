@@ -1,0 +1,303 @@
+// lsh.hip -- the hybrid LSH index (src/hnsw/ann/hash/hybrid_lsh.clj): hyperplanes, hash, buckets, multi-probe search
+// (C ABI: include/hnswgpu.h, "Hybrid LSH"; kernels: lsh_kernels.hpp).
+#include <string.h>
+
+#include <vector>
+
+#include "engine.hpp"
+#include "javarandom.hpp"
+#include "lsh_kernels.hpp"
+
+namespace hg {
+
+static int launch_lsh_hash(int nch, const LshHashArgs &a, hipStream_t st) {
+    if (a.n <= 0) return 0;
+#define CALL(N, R, L)                                                                                                          \
+    hipLaunchKernelGGL((lsh_hash_kernel<N, R>), dim3(static_cast<unsigned>((a.n + kNWave * R - 1) / (kNWave * R))), dim3(kWG), 0, st, a)
+    HG_DISPATCH(nch, false, CALL);
+#undef CALL
+    HG_HIP(hipGetLastError());
+    return 0;
+}
+
+static int launch_lsh_scan(int nch, const LshScanArgs &a, hipStream_t st) {
+    const size_t lds = a.take_max > kWave ? sizeof(uint64_t) * kNWave * a.take_max : 0;
+    const unsigned grid = static_cast<unsigned>((a.npairs + kNWave - 1) / kNWave);
+#define CALL(N, R, L) hipLaunchKernelGGL((lsh_bucket_scan_kernel<N, R, L>), dim3(grid), dim3(kWG), lds, st, a)
+    HG_DISPATCH(nch, a.metric == METRIC_L2, CALL);
+#undef CALL
+    HG_HIP(hipGetLastError());
+    return 0;
+}
+
+// The tables a build or an install stages: the handle takes them over only when every step has succeeded.
+struct LshStaged {
+    float *planes = nullptr;
+    uint16_t *codes = nullptr;
+    int64_t *off = nullptr;
+    int32_t *ids = nullptr;
+    ~LshStaged() {
+        void *ptrs[] = {planes, codes, off, ids};
+        for (void *p : ptrs)
+            if (p) (void)hipFree(p);
+    }
+};
+
+// planes: [tables][bits][dim] on the host.  Hash on the device; the buckets by a stable counting sort of the codes on the host
+// (one pass per table over n codes read back: rows ascending inside a bucket by construction, never by the order of atomics).
+static int lsh_install(hnswgpu_index *idx, Call &call, const float *planes, int32_t tables, int32_t bits, hipStream_t st) {
+    const int64_t n = idx->n, ld = idx->ld, np = static_cast<int64_t>(tables) * bits, nb = static_cast<int64_t>(1) << bits;
+    LshStaged s;
+    HG_HIP(hipMalloc(reinterpret_cast<void **>(&s.planes), sizeof(float) * np * ld));
+    if (ld != idx->dim) HG_HIP(hipMemsetAsync(s.planes, 0, sizeof(float) * np * ld, st));
+    HG_HIP(hipMemcpy2DAsync(s.planes, sizeof(float) * ld, planes, sizeof(float) * idx->dim, sizeof(float) * idx->dim, np,
+                            hipMemcpyHostToDevice, st));
+    HG_HIP(hipMalloc(reinterpret_cast<void **>(&s.off), sizeof(int64_t) * tables * (nb + 1)));
+    std::vector<int64_t> off(static_cast<size_t>(tables) * (nb + 1), 0);
+    std::vector<int32_t> ids(static_cast<size_t>(tables) * n);
+    if (n > 0) {
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&s.codes), sizeof(uint16_t) * n * tables));
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&s.ids), sizeof(int32_t) * n * tables));
+        LshHashArgs h;
+        h.planes = s.planes;
+        h.rows = idx->d_base;
+        h.ld = ld;
+        h.n = n;
+        h.tables = tables;
+        h.bits = bits;
+        h.codes = s.codes;
+        HG_TRY(launch_lsh_hash(idx->nch, h, st));
+        std::vector<uint16_t> codes(static_cast<size_t>(n) * tables);
+        HG_HIP(hipMemcpyAsync(codes.data(), s.codes, sizeof(uint16_t) * codes.size(), hipMemcpyDeviceToHost, st));
+        HG_HIP(hipStreamSynchronize(st));
+        for (int32_t t = 0; t < tables; t++) {
+            int64_t *o = off.data() + static_cast<size_t>(t) * (nb + 1);
+            for (int64_t r = 0; r < n; r++) o[codes[r * tables + t] + 1]++;
+            for (int64_t b = 0; b < nb; b++) o[b + 1] += o[b];
+            std::vector<int64_t> at(o, o + nb);
+            int32_t *dst = ids.data() + static_cast<size_t>(t) * n;
+            for (int64_t r = 0; r < n; r++) dst[at[codes[r * tables + t]]++] = static_cast<int32_t>(r);
+        }
+        HG_HIP(hipMemcpyAsync(s.ids, ids.data(), sizeof(int32_t) * ids.size(), hipMemcpyHostToDevice, st));
+    }
+    HG_HIP(hipMemcpyAsync(s.off, off.data(), sizeof(int64_t) * off.size(), hipMemcpyHostToDevice, st));
+    std::vector<float> keep(planes, planes + np * idx->dim);
+    HG_TRY(call.quiesce());  // the uploads are done (the host vectors go away), and no search reads the old tables any more
+    std::swap(idx->d_lsh_planes, s.planes);  // (what the handle had goes with `s`)
+    std::swap(idx->d_lsh_codes, s.codes);
+    std::swap(idx->d_lsh_off, s.off);
+    std::swap(idx->d_lsh_ids, s.ids);
+    idx->h_lsh_planes.swap(keep);
+    idx->lsh_tables = tables;
+    idx->lsh_bits = bits;
+    return 0;
+}
+
+static int check_lsh_shape(const hnswgpu_index *idx, int32_t tables, int32_t bits) {
+    HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
+    HG_REQUIRE(tables >= 1, HNSWGPU_EINVAL, "tables must be >= 1");
+    HG_REQUIRE(tables <= kLshMaxTables, HNSWGPU_ELIMIT, "more than %d hash tables are not supported", kLshMaxTables);
+    HG_REQUIRE(bits >= 1 && bits <= kLshMaxBits, HNSWGPU_ELIMIT, "need 1 <= bits <= %d", kLshMaxBits);
+    return 0;
+}
+
+// Everything hnswgpu_lsh_search* checks and clamps, before the lock
+static int check_lsh_search(const hnswgpu_index *idx, const void *Q, int32_t nq, int32_t k, int32_t num_probes, int32_t probe_radius,
+                            int32_t take_main, int32_t take_flip, const void *ids, const void *dist) {
+    HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
+    HG_REQUIRE(nq >= 0, HNSWGPU_EINVAL, "nq < 0");
+    HG_REQUIRE(k >= 1, HNSWGPU_EINVAL, "k must be >= 1");
+    HG_REQUIRE(take_main >= 1 && take_flip >= 1, HNSWGPU_EINVAL, "take_main and take_flip must be >= 1");
+    HG_REQUIRE(num_probes >= 1 && probe_radius >= 0, HNSWGPU_EINVAL, "need num_probes >= 1 and probe_radius >= 0");
+    HG_REQUIRE(nq == 0 || (Q && ids && dist), HNSWGPU_EINVAL, "null argument");
+    HG_REQUIRE(k <= kLshMaxK, HNSWGPU_ELIMIT, "k > %d is not supported by the LSH search", kLshMaxK);
+    HG_REQUIRE(take_main <= kLshMaxTake && take_flip <= kLshMaxTake, HNSWGPU_ELIMIT, "take_main / take_flip > %d is not supported",
+               kLshMaxTake);
+    return 0;
+}
+
+// d_Q [nq][dim] -> d_ids / d_dist [nq][k] on `st`; only enqueues.  The caller holds the handle's Call and has checked the arguments.
+static int lsh_search_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t num_probes, int32_t probe_radius,
+                              int32_t take_main, int32_t take_flip, int32_t *d_ids, float *d_dist, hipStream_t st) {
+    HG_REQUIRE(idx->lsh_tables > 0, HNSWGPU_ESTATE, "index has no LSH tables (call hnswgpu_lsh_build / hnswgpu_set_lsh first)");
+    const int32_t probes = std::min(num_probes, idx->lsh_tables), radius = std::min(probe_radius, idx->lsh_bits);
+    const int32_t pp = probes * (1 + radius), take_max = std::max(take_main, take_flip);
+    HG_REQUIRE(static_cast<int64_t>(pp) * idx->n < (static_cast<int64_t>(1) << 32), HNSWGPU_ELIMIT,
+               "the probe stream of one query (probes x (1 + radius) x n rows) must stay below 2^32");
+    if (idx->n == 0) return fill_empty_dev(d_ids, d_dist, static_cast<int64_t>(nq) * k, st);
+    // slices of queries: 12 bytes per key slot of a query's pairs, a GiB of them at a time
+    const int64_t per_query = static_cast<int64_t>(pp) * take_max;
+    const int32_t slice = static_cast<int32_t>(std::min<int64_t>(nq, std::max<int64_t>(1, (static_cast<int64_t>(1) << 30) / (12 * per_query))));
+    HG_TRY(idx->s_misc.ensure(sizeof(uint16_t) * static_cast<size_t>(slice) * idx->lsh_tables));
+    HG_TRY(idx->s_pairs.ensure(sizeof(LshPair) * static_cast<size_t>(slice) * pp));
+    HG_TRY(idx->s_partial.ensure(sizeof(uint64_t) * static_cast<size_t>(slice) * per_query));
+    HG_TRY(idx->s_ord.ensure(sizeof(int32_t) * static_cast<size_t>(slice) * per_query));
+    for (int32_t q0 = 0; q0 < nq; q0 += slice) {
+        const int32_t m = std::min(slice, nq - q0);
+        const float *Qs = d_Q + static_cast<int64_t>(q0) * idx->dim;
+        HG_TRY(pad_queries(idx, Qs, idx->dim, m, st));  // the hash kernel reads whole float4s of zero-padded rows
+        LshHashArgs h;
+        h.planes = idx->d_lsh_planes;
+        h.rows = idx->s_qp.as<float>();
+        h.ld = idx->ld;
+        h.n = m;
+        h.tables = idx->lsh_tables;
+        h.bits = idx->lsh_bits;
+        h.codes = idx->s_misc.as<uint16_t>();
+        HG_TRY(launch_lsh_hash(idx->nch, h, st));
+        LshProbeArgs p;
+        p.qcodes = h.codes;
+        p.off = idx->d_lsh_off;
+        p.n = idx->n;
+        p.nq = m;
+        p.tables = idx->lsh_tables;
+        p.bits = idx->lsh_bits;
+        p.probes = probes;
+        p.radius = radius;
+        p.take_main = take_main;
+        p.take_flip = take_flip;
+        p.pairs = idx->s_pairs.as<LshPair>();
+        hipLaunchKernelGGL(lsh_probe_kernel, dim3((m + 255) / 256), dim3(256), 0, st, p);
+        HG_HIP(hipGetLastError());
+        LshScanArgs a;
+        a.rows = idx->d_base;
+        a.row_norms = idx->d_norms;
+        a.ld = idx->ld;
+        a.Q = Qs;
+        a.qld = idx->dim;
+        a.dim = idx->dim;
+        a.metric = idx->metric;
+        a.pairs = p.pairs;
+        a.npairs = static_cast<int64_t>(m) * pp;
+        a.ids = idx->d_lsh_ids;
+        a.take_max = take_max;
+        a.keys = idx->s_partial.as<uint64_t>();
+        a.key_rows = idx->s_ord.as<int32_t>();
+        HG_TRY(launch_lsh_scan(idx->nch, a, st));
+        LshMergeArgs g;
+        g.keys = a.keys;
+        g.key_rows = a.key_rows;
+        g.nq = m;
+        g.pp = pp;
+        g.take_max = take_max;
+        g.k = k;
+        g.out_ids = d_ids + static_cast<int64_t>(q0) * k;
+        g.out_dist = d_dist + static_cast<int64_t>(q0) * k;
+        hipLaunchKernelGGL(lsh_merge_kernel, dim3(m), dim3(kWave), 0, st, g);
+        HG_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
+}  // namespace hg
+
+using namespace hg;
+
+extern "C" {
+
+int hnswgpu_lsh_build(hnswgpu_index *idx, int32_t tables, int32_t bits, int32_t proj_dim, int64_t seed) {
+    HG_TRY(check_lsh_shape(idx, tables, bits));
+    HG_REQUIRE(proj_dim >= bits, HNSWGPU_EINVAL, "proj_dim must be >= bits");
+    // (generate-random-matrix, :24-31: table by table, row by row, tables x proj_dim x dim draws; a table keeps its first `bits` rows)
+    std::vector<float> planes(static_cast<size_t>(tables) * bits * idx->dim);
+    JavaRandom rng(seed);
+    for (int32_t t = 0; t < tables; t++)
+        for (int32_t i = 0; i < proj_dim; i++)
+            for (int32_t d = 0; d < idx->dim; d++) {
+                const double g = rng.next_gaussian();
+                if (i < bits) planes[(static_cast<size_t>(t) * bits + i) * idx->dim + d] = static_cast<float>(g);
+            }
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_TRY(lsh_install(idx, call, planes.data(), tables, bits, st));
+    HG_TRY(call.sync());
+    return call.close();
+}
+
+int hnswgpu_set_lsh(hnswgpu_index *idx, const float *planes, int32_t tables, int32_t bits) {
+    HG_REQUIRE(idx && planes, HNSWGPU_EINVAL, "null argument");
+    HG_TRY(check_lsh_shape(idx, tables, bits));
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_TRY(lsh_install(idx, call, planes, tables, bits, st));
+    HG_TRY(call.sync());
+    return call.close();
+}
+
+int hnswgpu_lsh_sizes(hnswgpu_index *idx, int32_t *tables, int32_t *bits) {
+    HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (tables) *tables = idx->lsh_tables;
+    if (bits) *bits = idx->lsh_bits;
+    return 0;
+}
+
+int hnswgpu_lsh_get(hnswgpu_index *idx, float *planes, uint16_t *codes, int64_t *off, int32_t *ids) {
+    HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_REQUIRE(idx->lsh_tables > 0, HNSWGPU_ESTATE, "index has no LSH tables (call hnswgpu_lsh_build / hnswgpu_set_lsh first)");
+    const size_t T = idx->lsh_tables, n = idx->n, nb1 = (static_cast<size_t>(1) << idx->lsh_bits) + 1;
+    if (planes) memcpy(planes, idx->h_lsh_planes.data(), sizeof(float) * idx->h_lsh_planes.size());
+    if (codes && n) HG_HIP(hipMemcpyAsync(codes, idx->d_lsh_codes, sizeof(uint16_t) * n * T, hipMemcpyDeviceToHost, st));
+    if (off) HG_HIP(hipMemcpyAsync(off, idx->d_lsh_off, sizeof(int64_t) * T * nb1, hipMemcpyDeviceToHost, st));
+    if (ids && n) HG_HIP(hipMemcpyAsync(ids, idx->d_lsh_ids, sizeof(int32_t) * n * T, hipMemcpyDeviceToHost, st));
+    HG_TRY(call.sync());
+    return call.close();
+}
+
+int hnswgpu_lsh_hash(hnswgpu_index *idx, const float *Q, int32_t nq, uint16_t *codes) {
+    HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
+    HG_REQUIRE(nq >= 0, HNSWGPU_EINVAL, "nq < 0");
+    HG_REQUIRE(nq == 0 || (Q && codes), HNSWGPU_EINVAL, "null argument");
+    if (nq == 0) return 0;
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_REQUIRE(idx->lsh_tables > 0, HNSWGPU_ESTATE, "index has no LSH tables (call hnswgpu_lsh_build / hnswgpu_set_lsh first)");
+    HG_TRY(upload_queries(idx, Q, nq, st));
+    HG_TRY(pad_queries(idx, idx->s_q.as<float>(), idx->dim, nq, st));
+    HG_TRY(idx->s_misc.ensure(sizeof(uint16_t) * static_cast<size_t>(nq) * idx->lsh_tables));
+    LshHashArgs h;
+    h.planes = idx->d_lsh_planes;
+    h.rows = idx->s_qp.as<float>();
+    h.ld = idx->ld;
+    h.n = nq;
+    h.tables = idx->lsh_tables;
+    h.bits = idx->lsh_bits;
+    h.codes = idx->s_misc.as<uint16_t>();
+    HG_TRY(launch_lsh_hash(idx->nch, h, st));
+    HG_HIP(hipMemcpyAsync(codes, h.codes, sizeof(uint16_t) * static_cast<size_t>(nq) * idx->lsh_tables, hipMemcpyDeviceToHost, st));
+    HG_TRY(call.sync());
+    return call.close();
+}
+
+int hnswgpu_lsh_search_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t num_probes, int32_t probe_radius,
+                           int32_t take_main, int32_t take_flip, int32_t *d_out_ids, float *d_out_dist, void *stream) {
+    HG_TRY(check_lsh_search(idx, d_Q, nq, k, num_probes, probe_radius, take_main, take_flip, d_out_ids, d_out_dist));
+    if (nq == 0) return 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_TRY(lsh_search_enqueue(idx, d_Q, nq, k, num_probes, probe_radius, take_main, take_flip, d_out_ids, d_out_dist, st));
+    return call.close();
+}
+
+int hnswgpu_lsh_search(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t num_probes, int32_t probe_radius,
+                       int32_t take_main, int32_t take_flip, int32_t *out_ids, float *out_dist) {
+    HG_TRY(check_lsh_search(idx, Q, nq, k, num_probes, probe_radius, take_main, take_flip, out_ids, out_dist));
+    if (nq == 0) return 0;
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_TRY(call.stage_in(Q, nq, k));
+    HG_TRY(lsh_search_enqueue(idx, idx->s_q.as<float>(), nq, k, num_probes, probe_radius, take_main, take_flip, idx->s_ids.as<int32_t>(),
+                              idx->s_outd.as<float>(), st));
+    HG_TRY(call.stage_out(out_ids, out_dist, static_cast<int64_t>(nq) * k));
+    return call.close();
+}
+
+}  // extern "C"

@@ -574,6 +574,57 @@ class Index:
         check(lib().hnswgpu_ivf_search_lists(self._h, _p(Q), len(Q), k, probes.shape[1], _p(probes), _p(ids), _p(d)))
         return ids, d
 
+    # -- hybrid LSH (include/hnswgpu.h: "Hybrid LSH")
+    def lsh_build(self, tables=8, bits=12, proj_dim=64, seed=42):
+        """hnswgpu_lsh_build: hyperplanes from java.util.Random(seed) as the reference draws them, hash, buckets."""
+        check(lib().hnswgpu_lsh_build(self._h, tables, bits, proj_dim, seed))
+
+    def set_lsh(self, planes):
+        """hnswgpu_set_lsh: the caller's hyperplanes (tables, bits, dim)."""
+        planes = _f32(planes)
+        if planes.ndim != 3 or planes.shape[2] != self.dim:
+            raise ValueError("planes must be (tables, bits, %d), got %s" % (self.dim, planes.shape))
+        check(lib().hnswgpu_set_lsh(self._h, _p(planes), planes.shape[0], planes.shape[1]))
+
+    def lsh_sizes(self):
+        t, b = C.c_int32(), C.c_int32()
+        check(lib().hnswgpu_lsh_sizes(self._h, C.byref(t), C.byref(b)))
+        return t.value, b.value
+
+    def lsh_get(self):
+        """(planes (T, bits, dim), codes (n, T) uint16, off (T, 2^bits + 1), ids (T, n)): bucket b of table t is
+        ids[t, off[t, b]:off[t, b + 1]], rows ascending."""
+        t, b = self.lsh_sizes()
+        planes = np.empty((t, b, self.dim), np.float32)
+        codes = np.empty((self.n, t), np.uint16)
+        off = np.empty((t, (1 << b) + 1), np.int64)
+        ids = np.empty((t, self.n), np.int32)
+        check(lib().hnswgpu_lsh_get(self._h, _p(planes), _p(codes), _p(off), _p(ids)))
+        return planes, codes, off, ids
+
+    def lsh_hash(self, Q):
+        """Codes (nq, T) of arbitrary vectors under the handle's hyperplanes (the kernel that hashed the base rows)."""
+        Q = _queries(Q, self.dim)
+        codes = np.empty((len(Q), self.lsh_sizes()[0]), np.uint16)
+        check(lib().hnswgpu_lsh_hash(self._h, _p(Q), len(Q), _p(codes)))
+        return codes
+
+    def lsh_search(self, Q, k, num_probes=6, probe_radius=2, take_main=None, take_flip=None, out=None):
+        """hnswgpu_lsh_search (numpy queries) / hnswgpu_lsh_search_dev (a torch device tensor, torch's current stream):
+        multi-probe search; the takes default to the reference's 2 k and k."""
+        take_main = 2 * k if take_main is None else take_main
+        take_flip = k if take_flip is None else take_flip
+        if hasattr(Q, "is_cuda") and Q.is_cuda:
+            Q, ids, d, st = self._dev_args(Q, k, out)
+            check(lib().hnswgpu_lsh_search_dev(self._h, Q.data_ptr(), Q.shape[0], k, num_probes, probe_radius, take_main,
+                                               take_flip, ids.data_ptr(), d.data_ptr(), st))
+            return ids, d
+        Q = _queries(Q, self.dim)
+        ids = np.empty((len(Q), k), np.int32)
+        d = np.empty((len(Q), k), np.float32)
+        check(lib().hnswgpu_lsh_search(self._h, _p(Q), len(Q), k, num_probes, probe_radius, take_main, take_flip, _p(ids), _p(d)))
+        return ids, d
+
     # -- zero-copy device entry points (torch tensors, torch's current stream)
     def _dev_args(self, Q, k, out=None):
         import torch

@@ -1,0 +1,117 @@
+"""Mirror of ``hnsw.ann.hash.hybrid-lsh`` (src/hnsw/ann/hash/hybrid_lsh.clj).
+
+``build_lsh_index(data, distance_fn=...)`` draws the reference's hyperplanes (``Random(42)``, 8 tables of 64 Gaussian rows
+of which the first 12 form the bucket id), hashes every row on the device and files it in its buckets;
+``search_hybrid`` / ``search_hybrid_multiprobe`` / ``search_knn(index, q, k[, mode])`` probe the query's buckets and their
+one-bit neighbours with the HIP bucket scan (hnswgpu_lsh_search).  Queries may be one vector or a batch.
+
+One difference, on purpose: the reference computes cosine whatever ``:distance-fn`` says (its ``query-norm`` is never nil,
+:157-166); here the index's metric decides, as in every other mirror.
+"""
+import numpy as np
+
+from . import engine
+from .ultra_fast import _metric_of, _split, cosine_distance_ultra
+
+# hybrid_lsh.clj:12-14, :80
+NUM_HASH_TABLES = 8
+NUM_HASH_BITS = 12
+PROJECTION_DIM = 64
+SEED = 42
+
+# hybrid_lsh.clj:350-364: mode -> (num_probes, probe_radius); anything else is :balanced
+MODE_CONFIGS = {
+    "turbo": (2, 1),
+    "fast": (4, 1),
+    "balanced": (6, 2),
+    "accurate": (8, 3),
+    "precise": (8, 4),
+}
+DEFAULT_MODE = "balanced"
+
+
+def mode_config(mode=None):
+    """(num_probes, probe_radius) of a mode keyword; an unknown mode (and none) is :balanced (:363-364)."""
+    return MODE_CONFIGS.get(mode, MODE_CONFIGS[DEFAULT_MODE])
+
+
+def clamp_probes(num_probes, probe_radius, tables=NUM_HASH_TABLES, bits=NUM_HASH_BITS):
+    """What a search probes: min(num-probes, tables) tables (:269), min(probe-radius, bits) flipped bits each (:321)."""
+    return min(int(num_probes), int(tables)), min(int(probe_radius), int(bits))
+
+
+class HybridIndex:
+    """hybrid_lsh.clj:18-22: hash tables, matrices, rows and norms live on the device behind ``index``."""
+
+    def __init__(self, index, ids, distance_fn):
+        self.index = index
+        self.ids = ids
+        self.distance_fn = distance_fn
+
+    def close(self):
+        self.index.close()
+
+
+def build_lsh_index(data, distance_fn=cosine_distance_ultra, show_progress=True, num_threads=8, device=0):
+    """hybrid_lsh.clj:66-145 (``num_threads`` is the reference's pool size: the device hashes every row in one launch)"""
+    metric = _metric_of(distance_fn)
+    ids, base = _split(data)
+    idx = engine.Index(base, metric, device)
+    idx.lsh_build(NUM_HASH_TABLES, NUM_HASH_BITS, PROJECTION_DIM, SEED)
+    if show_progress:
+        print("LSH index built: %d vectors, %d hash tables, %d buckets per table" % (len(ids), NUM_HASH_TABLES, 1 << NUM_HASH_BITS))
+    return HybridIndex(idx, ids, distance_fn)
+
+
+def build_index(data, **opts):
+    """hybrid_lsh.clj:345-348"""
+    return build_lsh_index(data, **opts)
+
+
+def _format(index, ids_row, d_row):
+    return [{"id": index.ids[i], "distance": float(d)} for i, d in zip(ids_row, d_row) if i >= 0]
+
+
+def _search(index, query_vec, k, num_probes, probe_radius, take_main, take_flip):
+    q = np.asarray(query_vec, np.float32)
+    single = q.ndim == 1
+    Q = q[None, :] if single else q
+    if index.index.n == 0 or len(Q) == 0:
+        out = [[] for _ in range(len(Q))]
+    else:
+        ids, d = index.index.lsh_search(Q, int(k), int(num_probes), int(probe_radius), int(take_main), int(take_flip))
+        out = [_format(index, ids[i], d[i]) for i in range(len(Q))]
+    return out[0] if single else out
+
+
+def search_hybrid(index, query_vec, k, num_probes=2, parallel=True):
+    """hybrid_lsh.clj:195-259: the query's own bucket in the first ``num_probes`` tables; 3 k rows of each are kept in the
+    parallel form (the default), 2 k in the sequential one."""
+    return _search(index, query_vec, k, num_probes, 0, (3 if parallel else 2) * int(k), int(k))
+
+
+def search_hybrid_multiprobe(index, query_vec, k, num_probes=6, probe_radius=2, parallel=True):
+    """hybrid_lsh.clj:261-342, in the order of its sequential branch (``parallel`` changes the order of ties only there,
+    and nothing here): 2 k rows of the own bucket, k of every one-bit neighbour."""
+    return _search(index, query_vec, k, num_probes, probe_radius, 2 * int(k), int(k))
+
+
+def search_knn(index, query_vec, k, mode=None):
+    """hybrid_lsh.clj:350-364"""
+    probes, radius = mode_config(mode)
+    return search_hybrid_multiprobe(index, query_vec, k, num_probes=probes, probe_radius=radius)
+
+
+def search_batch(index, queries, k, mode=None):
+    q = np.asarray(queries, np.float32)
+    return search_knn(index, q[None, :] if q.ndim == 1 else q, k, mode)
+
+
+def index_info(index):
+    """hybrid_lsh.clj:366-379: total-buckets counts the non-empty buckets of all tables, as the reference's maps do"""
+    n = index.index.n
+    tables, bits = index.index.lsh_sizes()
+    _, _, off, _ = index.index.lsh_get()
+    total = int((np.diff(off, axis=1) > 0).sum())
+    return {"type": "Hybrid LSH Index", "vectors": n, "hash-tables": tables, "buckets-per-table": 1 << bits,
+            "total-buckets": total, "avg-bucket-size": n / total if total > 0 else 0}

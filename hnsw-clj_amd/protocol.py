@@ -3,7 +3,7 @@ FilterableIndex and the default helpers (filtered search by post-filtering, :96-
 the two GPU-served index types.  The HNSW index filters on the device (ultra_fast.search_knn_filtered).  GpuIvfFlatIndex is
 the reference's IVF index, which has no FilterableIndex and is served by the default helper; GpuFilterableIvfFlatIndex adds
 the protocol on top of it, filtering inside the list scan (ivf_flat.search_knn_filtered)."""
-from . import index_io, ivf_flat, ultra_fast
+from . import hybrid_lsh, index_io, ivf_flat, ultra_fast
 
 
 class ANNIndex:
@@ -108,6 +108,25 @@ class GpuFilterableIvfFlatIndex(GpuIvfFlatIndex, FilterableIndex):
 
     def search_knn_filtered_star(self, query, k, filter_fn, mode="balanced"):
         return ivf_flat.search_knn_filtered(self.index, query, k, filter_fn, mode or "balanced")
+
+
+class GpuHybridLshIndex(ANNIndex, BatchSearchIndex):
+    """hnsw.ann.hash.hybrid-lsh behind the protocol (unified.clj's :hybrid-lsh); not persistable, as in the reference."""
+
+    def __init__(self, index):
+        self.index = index
+
+    def search_knn_star(self, query, k, mode=None):
+        return hybrid_lsh.search_knn(self.index, query, k, mode)
+
+    def search_batch_star(self, queries, k, mode=None):
+        return hybrid_lsh.search_batch(self.index, queries, k, mode)
+
+    def index_info_star(self):
+        return hybrid_lsh.index_info(self.index)
+
+    def index_type_star(self):
+        return "hybrid-lsh"
 
 
 def supports_filtering(index):

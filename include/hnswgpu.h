@@ -606,6 +606,49 @@ int hnswgpu_hnsw_last_order(hnswgpu_index *idx, int32_t *order, int32_t *keys, i
 int hnswgpu_set_tuning(int32_t key, int64_t value);
 int hnswgpu_get_tuning(int32_t key, int64_t *value, int32_t *is_set);
 
+/* ---- Hybrid LSH (hnsw-clj_amd/csrc/lsh.hip, lsh_kernels.hpp) -------------------------------------------------------
+ * The reference's hnsw.ann.hash.hybrid-lsh (src/hnsw/ann/hash/hybrid_lsh.clj): `tables` hash tables of sign projections
+ * over the handle's rows.  Bit i of a row's code in table t is dot(row, plane[t][i]) >= 0.0 (:33-45), bit i at position i
+ * (:47-55); a bucket lists its rows in row order (:105-129).  The dot is the engine's GEMV-order dot with the plane in the
+ * query's role -- the sign of the negated distance hnswgpu_batch_distances returns on a DOT handle -- and ONE kernel hashes
+ * base rows and queries: a base row used as a query lands in its own buckets.
+ *   hnswgpu_lsh_build: the planes from java.util.Random(seed) as build-lsh-index consumes it (:24-31, :80-84): tables x
+ *     proj_dim x dim nextGaussian draws, table by table, row by row; a table keeps its first `bits` rows (NUM-HASH-BITS of
+ *     PROJECTION-DIM, :12-14, :117).  proj_dim (>= bits) only keeps a JVM user's seed on the same hyperplanes; the
+ *     reference's index is (8, 12, 64, 42).  The draws are rounded to float.  Replaces tables the handle has.  n == 0 is legal.
+ *   hnswgpu_set_lsh: the same from the caller's hyperplanes [tables][bits][dim].
+ *   hnswgpu_lsh_sizes: (0, 0) for a handle without tables.
+ *   hnswgpu_lsh_get: planes [tables][bits][dim], codes [n][tables], off [tables][2^bits + 1] (bucket b of table t is
+ *     ids[t][off[t][b] .. off[t][b + 1]), rows ascending), ids [tables][n]; every output may be null.
+ *   hnswgpu_lsh_hash: codes [nq][tables] of arbitrary vectors under the handle's planes.
+ *   hnswgpu_lsh_search / _dev: search-hybrid-multiprobe's sequential branch (:305-342; the parallel branch differs in the order
+ *     of ties only).  For table t = 0 .. min(num_probes, tables) - 1: the query's own bucket, of which the take_main nearest
+ *     rows are kept, then for j = 0 .. min(probe_radius, bits) - 1 the bucket with bit j flipped, take_flip rows each (a bucket
+ *     with no more rows than its take is kept whole, :153; otherwise a stable sort by distance, :188-193).  The pieces are
+ *     concatenated in probe order, a row's later occurrences dropped, the rest sorted stably by distance and cut to k
+ *     (:330-342).  The reference calls it with take_main = 2 k, take_flip = k; search-hybrid (:195-259) is radius 0 with
+ *     take_main = 3 k (parallel, the default) or 2 k.  Truncation per probe comes BEFORE the dedup.  out [nq][k] ascending,
+ *     padded with -1 / +inf where fewer than k distinct rows were found.  The metric is the handle's (the reference computes
+ *     cosine whatever :distance-fn says, :157-166: its query-norm is never nil); distances have the bits of every GEMV-order
+ *     scan.  _dev only enqueues on `stream` (device arrays, no synchronise, no readback); the host entry stages one caller's
+ *     batch and takes no part in the combining of concurrent callers.
+ * Errors: -1 null pointers, k < 1, take_* < 1, num_probes < 1, probe_radius < 0, tables < 1; nq == 0 returns 0; -3 a handle
+ * without tables; -5 tables > 16, bits outside 1 .. 16, k > 256, take_* > 256, or a probe stream of one query
+ * (probes x (1 + radius) x n rows) of 2^32 rows or more.
+ * hnswgpu_hnsw_add and hnswgpu_ivf_add return -3 on a handle with tables (the tables would miss the new rows).  The tables
+ * are NOT part of the index file: hnswgpu_save writes what it writes without them, a loaded handle has none (build them again
+ * from the seed, or install the exported planes).  Groups, shards and forests do not know them. */
+int hnswgpu_lsh_build(hnswgpu_index *idx, int32_t tables, int32_t bits, int32_t proj_dim, int64_t seed);
+int hnswgpu_set_lsh(hnswgpu_index *idx, const float *planes, int32_t tables, int32_t bits);
+int hnswgpu_lsh_sizes(hnswgpu_index *idx, int32_t *tables, int32_t *bits);
+int hnswgpu_lsh_get(hnswgpu_index *idx, float *planes, uint16_t *codes, int64_t *off, int32_t *ids);
+int hnswgpu_lsh_hash(hnswgpu_index *idx, const float *Q, int32_t nq, uint16_t *codes);
+int hnswgpu_lsh_search(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t num_probes, int32_t probe_radius,
+                       int32_t take_main, int32_t take_flip, int32_t *out_ids, float *out_dist);
+int hnswgpu_lsh_search_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t num_probes,
+                           int32_t probe_radius, int32_t take_main, int32_t take_flip, int32_t *d_out_ids, float *d_out_dist,
+                           void *stream);
+
 /* ---- ONE index over several GPUs (hnsw-clj_amd/csrc/group.hip) ---------------------------------------------------
  * The reference shards inside one process: search-partitioned scatters a query to its partitions, takes a top-k per
  * partition, concatenates, sorts and takes k (src/hnsw/ann/partition/partitioned_hnsw.clj:149-196).  A group gives the
