@@ -19,6 +19,7 @@
      (add-vector! index new-data)                                    ; hnsw.api/add-vector!, insert-single on a live index
      (add-ivf-vectors! index new-data)                               ; the same for a live IVF-FLAT index: hnswgpu_ivf_add
      (build-lsh-index data :metric :cosine)                          ; hnsw.ann.hash.hybrid-lsh/build-lsh-index: (Random. 42), 8 x 12 bits
+     (add-lsh-vectors! index new-data)                               ; rows join a live hybrid-LSH index: hnswgpu_lsh_add
      (search-lsh index query-vec k :mode :balanced)                  ; hybrid-lsh/search-knn (search-hybrid-multiprobe)
      (search-lsh-batch index queries k :mode :balanced)
      (from-ultra-graph graph)                                        ; a graph built by the reference's own insert-single
@@ -155,6 +156,19 @@
       (check (.invokeWithArguments ^MethodHandle @h-lshbuild
                                    [(:handle idx) (int tables) (int bits) (int projection-dim) (long seed)])))
     idx))
+
+(def ^:private h-lshadd (delay (fn-handle "hnswgpu_lsh_add" (FunctionDescriptor/of I (into-array [P P L])))))
+
+(defn add-lsh-vectors!
+  "add-vector! (src/hnsw/api.clj:30-33) for a live hybrid-LSH GpuIndex (the reference's index has no add; what is restated is its
+   bucket order, hybrid_lsh.clj:105-129): the new [id ^doubles vector] pairs join the base matrix and, hashed under the index's
+   hyperplanes, every table's buckets behind a bucket's present members.  Returns the index with their ids appended.  One call per
+   batch of new vectors is the efficient shape."
+  [idx new-data]
+  (with-open [arena (Arena/ofConfined)]
+    (check (.invokeWithArguments ^MethodHandle @h-lshadd
+                                 [(:handle idx) (floats-of arena (mapv second new-data) (:dim idx)) (long (count new-data))])))
+  (update idx :ids into (map first new-data)))
 
 (def ^:private lsh-modes {:turbo [2 1] :fast [4 1] :balanced [6 2] :accurate [8 3] :precise [8 4]})   ; hybrid_lsh.clj:350-364
 

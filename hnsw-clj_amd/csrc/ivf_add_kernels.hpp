@@ -53,26 +53,6 @@ __global__ __launch_bounds__(kWG) void ivf_add_count_kernel(IvfAddArgs a) {
     }
 }
 
-// exclusive sum over the workgroup of one value per thread; *total = the workgroup's sum.  `wsum`: kNWave words of LDS.
-__device__ inline uint32_t wg_exclusive_sum(uint32_t v, uint32_t *wsum, uint32_t *total) {
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-    uint32_t incl = v;
-    for (int off = 1; off < kWave; off <<= 1) {
-        const uint32_t o = __shfl_up(incl, off, kWave);
-        if (lane >= off) incl += o;
-    }
-    __syncthreads();  // (the words' readers of the round before are through)
-    if (lane == kWave - 1) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-    for (int w = 0; w < kNWave; w++) {
-        if (w < wave) before += wsum[w];
-        all += wsum[w];
-    }
-    *total = all;
-    return before + incl - v;
-}
-
 // new_off[l] = old_off[l] + new rows of the lists below l: a list's shift is new_off[l] - old_off[l].  One workgroup.
 __global__ __launch_bounds__(kWG) void ivf_add_offsets_kernel(IvfAddArgs a) {
     __shared__ uint32_t wsum[kNWave];

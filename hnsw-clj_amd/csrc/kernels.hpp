@@ -403,6 +403,27 @@ __device__ __forceinline__ int wave_scan_incl(int v) {
     return v;
 }
 
+// exclusive sum over the workgroup of one value per thread; *total = the workgroup's sum.  `wsum`: kNWave words of LDS.
+// (The grown offsets of hnswgpu_ivf_add and hnswgpu_lsh_add: ivf_add_kernels.hpp, lsh_add_kernels.hpp.)
+__device__ inline uint32_t wg_exclusive_sum(uint32_t v, uint32_t *wsum, uint32_t *total) {
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    uint32_t incl = v;
+    for (int off = 1; off < kWave; off <<= 1) {
+        const uint32_t o = __shfl_up(incl, off, kWave);
+        if (lane >= off) incl += o;
+    }
+    __syncthreads();  // (the words' readers of the round before are through)
+    if (lane == kWave - 1) wsum[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+    for (int w = 0; w < kNWave; w++) {
+        if (w < wave) before += wsum[w];
+        all += wsum[w];
+    }
+    *total = all;
+    return before + incl - v;
+}
+
 // The k <= 64 smallest of up to 1024 keys (four per thread of a 256-thread workgroup, all-ones = none, distinct), ascending
 // into fin[0, k) (all-ones padded) -- by HISTOGRAMS of the distance words instead of a bisection of the key space: a pass
 // bins every key of the current range into 256 bins (one LDS atomic each), one wave scans the counts and names the bin

@@ -1,11 +1,12 @@
 // lsh.hip -- the hybrid LSH index (src/hnsw/ann/hash/hybrid_lsh.clj): hyperplanes, hash, buckets, multi-probe search
-// (C ABI: include/hnswgpu.h, "Hybrid LSH"; kernels: lsh_kernels.hpp).
+// (C ABI: include/hnswgpu.h, "Hybrid LSH"; kernels: lsh_kernels.hpp, and lsh_add_kernels.hpp for rows that join live tables).
 #include <string.h>
 
 #include <vector>
 
 #include "engine.hpp"
 #include "javarandom.hpp"
+#include "lsh_add_kernels.hpp"
 #include "lsh_kernels.hpp"
 
 namespace hg {
@@ -272,6 +273,127 @@ int hnswgpu_lsh_hash(hnswgpu_index *idx, const float *Q, int32_t nq, uint16_t *c
     HG_TRY(launch_lsh_hash(idx->nch, h, st));
     HG_HIP(hipMemcpyAsync(codes, h.codes, sizeof(uint16_t) * static_cast<size_t>(nq) * idx->lsh_tables, hipMemcpyDeviceToHost, st));
     HG_TRY(call.sync());
+    return call.close();
+}
+
+// Rows join the tables of a live handle (include/hnswgpu.h).  The reference's HybridIndex has no add; what is restated is its
+// bucket order (hybrid_lsh.clj:105-129: insertion order, which is row order): the grown handle holds what hnswgpu_create(all
+// rows) + hnswgpu_set_lsh(the same planes) holds.  One chain on the handle's stream: base / norms / int8 rows grow as in
+// hnswgpu_ivf_add, lsh_hash_kernel hashes the new rows behind a device copy of the old codes, four integer kernels
+// (lsh_add_kernels.hpp) count, scan, place the new rows and move the old members; ONE readback of a word per table says that
+// every table's grown buckets hold all rows.
+int hnswgpu_lsh_add(hnswgpu_index *idx, const float *rows, int64_t m) {
+    HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
+    HG_REQUIRE(m >= 0, HNSWGPU_EINVAL, "m must be >= 0");
+    if (m == 0) return 0;
+    HG_REQUIRE(rows, HNSWGPU_EINVAL, "rows is null");
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_REQUIRE(idx->lsh_tables > 0, HNSWGPU_ESTATE, "index has no LSH tables (call hnswgpu_lsh_build / hnswgpu_set_lsh first)");
+    HG_REQUIRE(!idx->has_graph || idx->nparts > 0, HNSWGPU_ESTATE,
+               "the index holds an HNSW graph: rows added to the LSH tables would be missing from the graph");
+    HG_REQUIRE(idx->nparts == 0, HNSWGPU_ESTATE,
+               "the index holds a forest of HNSW sub-graphs: rows added to the LSH tables would be missing from its parts");
+    HG_REQUIRE(idx->nlist == 0 || idx->d_glistoff != nullptr, HNSWGPU_ESTATE,
+               "the index holds IVF lists: rows added to the LSH tables would be missing from the lists");
+    HG_REQUIRE(idx->d_glistoff == nullptr, HNSWGPU_ESTATE,
+               "a shard of a larger IVF index (hnswgpu_set_ivf_shard) cannot grow alone: its lists would miss the rows");
+    const int64_t n0 = idx->n, n1 = n0 + m;
+    HG_REQUIRE(n1 < 2147483647LL, HNSWGPU_ELIMIT, "the index must hold fewer than 2^31 rows");
+    HG_TRY(call.quiesce());
+    const int64_t ld = idx->ld, nb = static_cast<int64_t>(1) << idx->lsh_bits;
+    const int32_t tables = idx->lsh_tables;
+    // Failure-atomic, as hnswgpu_ivf_add: every array the call makes is STAGED and goes with `nw` on an early return; the handle's
+    // fields change only behind the last step (idx->mu is held and the streams are quiesced: no caller sees a state in between).
+    struct Grown {
+        float *base = nullptr, *norms = nullptr;
+        uint32_t *qrows = nullptr;
+        float4 *qmeta = nullptr;
+        LshStaged lsh;  // (the planes stay the handle's)
+        ~Grown() {
+            void *ptrs[] = {base, norms, qrows, qmeta};
+            for (void *p : ptrs)
+                if (p) (void)hipFree(p);
+        }
+    } nw;
+    auto grow = [&]() -> int {
+        // ---- 1. the base matrix, its norms and base-order int8 rows grow
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.base), sizeof(float) * static_cast<size_t>(n1) * ld));
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.norms), sizeof(float) * static_cast<size_t>(n1)));
+        if (n0 > 0) {
+            HG_HIP(hipMemcpyAsync(nw.base, idx->d_base, sizeof(float) * static_cast<size_t>(n0) * ld, hipMemcpyDeviceToDevice, st));
+            HG_HIP(hipMemcpyAsync(nw.norms, idx->d_norms, sizeof(float) * static_cast<size_t>(n0), hipMemcpyDeviceToDevice, st));
+        }
+        if (ld != idx->dim) HG_HIP(hipMemsetAsync(nw.base + n0 * ld, 0, sizeof(float) * static_cast<size_t>(m) * ld, st));
+        HG_HIP(hipMemcpy2DAsync(nw.base + n0 * ld, sizeof(float) * ld, rows, sizeof(float) * idx->dim, sizeof(float) * idx->dim,
+                                static_cast<size_t>(m), hipMemcpyHostToDevice, st));
+        HG_TRY(launch_norms(idx->nch, nw.base + n0 * ld, ld, m, nw.norms + n0, st));
+        if (idx->d_qrows) HG_TRY(quantize_rows(idx, nw.base, n1, &nw.qrows, &nw.qmeta, st));  // (all rows again: one pass over the base)
+        // ---- 2. the new rows' codes, by the kernel and under the planes that made the old ones, behind a copy of those
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.lsh.codes), sizeof(uint16_t) * static_cast<size_t>(n1) * tables));
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.lsh.off), sizeof(int64_t) * tables * (nb + 1)));
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.lsh.ids), sizeof(int32_t) * static_cast<size_t>(n1) * tables));
+        if (n0 > 0)
+            HG_HIP(hipMemcpyAsync(nw.lsh.codes, idx->d_lsh_codes, sizeof(uint16_t) * static_cast<size_t>(n0) * tables,
+                                  hipMemcpyDeviceToDevice, st));
+        LshHashArgs h;
+        h.planes = idx->d_lsh_planes;
+        h.rows = nw.base + n0 * ld;
+        h.ld = ld;
+        h.n = m;
+        h.tables = tables;
+        h.bits = idx->lsh_bits;
+        h.codes = nw.lsh.codes + n0 * tables;
+        HG_TRY(launch_lsh_hash(idx->nch, h, st));
+        // ---- 3. - 6. count, offsets, place, splice: launch boundaries are the only dependences
+        const size_t cbytes = sizeof(uint32_t) * static_cast<size_t>(tables) * nb;
+        HG_TRY(idx->s_misc.ensure(cbytes));
+        HG_HIP(hipMemsetAsync(idx->s_misc.p, 0, cbytes, st));
+        LshAddArgs a;
+        a.codes = nw.lsh.codes;
+        a.n0 = n0;
+        a.m = m;
+        a.tables = tables;
+        a.bits = idx->lsh_bits;
+        a.old_off = idx->d_lsh_off;
+        a.new_off = nw.lsh.off;
+        a.cursor = idx->s_misc.as<uint32_t>();
+        a.old_ids = idx->d_lsh_ids;
+        a.new_ids = nw.lsh.ids;
+        const unsigned count_wgs = static_cast<unsigned>(std::min<int64_t>((m + kWG - 1) / kWG, 256));
+        hipLaunchKernelGGL(lsh_add_count_kernel, dim3(count_wgs, static_cast<unsigned>(tables)), dim3(kWG), 0, st, a);
+        hipLaunchKernelGGL(lsh_add_offsets_kernel, dim3(static_cast<unsigned>(tables)), dim3(kWG), 0, st, a);
+        if (nb <= kLshAddLdsBuckets)
+            hipLaunchKernelGGL(lsh_add_place_kernel<true>, dim3(static_cast<unsigned>(tables)), dim3(kWave), 0, st, a);
+        else
+            hipLaunchKernelGGL(lsh_add_place_kernel<false>, dim3(static_cast<unsigned>(tables)), dim3(kWave), 0, st, a);
+        if (n0 > 0)
+            hipLaunchKernelGGL(lsh_add_splice_kernel, dim3(static_cast<unsigned>((n0 * tables + kWG - 1) / kWG)), dim3(kWG), 0, st, a);
+        HG_HIP(hipGetLastError());
+        // ---- the one readback: every table's last offset (the tables have no host mirrors besides the planes)
+        int64_t total[kLshMaxTables];
+        HG_HIP(hipMemcpy2DAsync(total, sizeof(int64_t), nw.lsh.off + nb, sizeof(int64_t) * (nb + 1), sizeof(int64_t),
+                                static_cast<size_t>(tables), hipMemcpyDeviceToHost, st));
+        HG_HIP(hipStreamSynchronize(st));
+        for (int32_t t = 0; t < tables; t++)
+            HG_REQUIRE(total[t] == n1, HNSWGPU_EHIP, "the grown buckets of table %d hold %lld rows, not %lld", t, (long long)total[t],
+                       (long long)n1);
+        return 0;
+    };
+    const int rc = grow();
+    if (rc != 0) {
+        (void)hipStreamSynchronize(st);  // (nothing of the chain is in flight when `nw` frees what it staged)
+        return rc;
+    }
+    std::swap(idx->d_base, nw.base);  // (what the handle had goes with `nw`)
+    std::swap(idx->d_norms, nw.norms);
+    std::swap(idx->d_qrows, nw.qrows);
+    std::swap(idx->d_qmeta, nw.qmeta);
+    std::swap(idx->d_lsh_codes, nw.lsh.codes);
+    std::swap(idx->d_lsh_off, nw.lsh.off);
+    std::swap(idx->d_lsh_ids, nw.lsh.ids);
+    idx->n = n1;
     return call.close();
 }
 

@@ -609,6 +609,15 @@ class Index:
         check(lib().hnswgpu_lsh_hash(self._h, _p(Q), len(Q), _p(codes)))
         return codes
 
+    def lsh_add(self, rows):
+        """hnswgpu_lsh_add: `rows` join the base and every hash table's buckets (behind a bucket's present members, in row
+        order); returns the row ids they got."""
+        rows = _queries(rows, self.dim)
+        first = self.n
+        check(lib().hnswgpu_lsh_add(self._h, _p(rows), len(rows)))
+        self.n += len(rows)
+        return np.arange(first, self.n, dtype=np.int32)
+
     def lsh_search(self, Q, k, num_probes=6, probe_radius=2, take_main=None, take_flip=None, out=None):
         """hnswgpu_lsh_search (numpy queries) / hnswgpu_lsh_search_dev (a torch device tensor, torch's current stream):
         multi-probe search; the takes default to the reference's 2 k and k."""

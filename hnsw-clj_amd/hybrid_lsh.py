@@ -68,6 +68,18 @@ def build_index(data, **opts):
     return build_lsh_index(data, **opts)
 
 
+def add_vectors(index, data):
+    """The reference's hybrid-lsh index has no add (build-lsh-index returns an immutable record); what is restated is its
+    bucket order (hybrid_lsh.clj:105-129: a bucket lists its rows in insertion order): ``data`` has the form ``build_index``
+    takes; every vector is hashed under the index's hyperplanes and joins its bucket of every table behind the bucket's
+    present members (hnswgpu_lsh_add).  Empty ``data`` does nothing.  Returns the index."""
+    ids, rows = _split(data)
+    if ids:
+        index.index.lsh_add(rows)
+        index.ids.extend(ids)
+    return index
+
+
 def _format(index, ids_row, d_row):
     return [{"id": index.ids[i], "distance": float(d)} for i, d in zip(ids_row, d_row) if i >= 0]
 

@@ -637,12 +637,36 @@ int hnswgpu_get_tuning(int32_t key, int64_t *value, int32_t *is_set);
  * (probes x (1 + radius) x n rows) of 2^32 rows or more.
  * hnswgpu_hnsw_add and hnswgpu_ivf_add return -3 on a handle with tables (the tables would miss the new rows).  The tables
  * are NOT part of the index file: hnswgpu_save writes what it writes without them, a loaded handle has none (build them again
- * from the seed, or install the exported planes).  Groups, shards and forests do not know them. */
+ * from the seed, or install the exported planes).  Groups, shards and forests do not know them.
+ *
+ *   hnswgpu_lsh_add: rows join a LIVE handle with tables (the reference's HybridIndex has no add; what is restated is its bucket
+ *     order, :105-129: a bucket lists its rows in insertion order, which is row order).  `rows` is m x dim float32 host memory;
+ *     the rows get ids n .. n + m - 1 and join the base matrix, the norms, the base-order int8 rows where the handle has them,
+ *     and every table's buckets behind a bucket's present members, in row order.  The planes do not change, and the new rows
+ *     are hashed by the kernel that hashed the old ones: a row's code does not depend on whether it came by build or by add,
+ *     and m rows in one call or in any split of calls give the same tables.
+ *     After the call the handle holds, bit for bit, what hnswgpu_create(all n + m rows) + hnswgpu_set_rejection_test(same
+ *     mode) + hnswgpu_set_lsh(the same planes) holds: what hnswgpu_lsh_get exports, the ids and distance bits of
+ *     hnswgpu_lsh_search / _dev, hnswgpu_exact_knn, hnswgpu_norms, hnswgpu_batch_distances, hnswgpu_lsh_hash, and the bytes
+ *     hnswgpu_save writes (still without the tables).
+ *     Everything happens on the device, in one chain on the handle's stream: no old row is uploaded, no code or bucket id is
+ *     read back, and the placement is deterministic by construction (a new row's place is its stable rank among the call's
+ *     rows of its bucket, never the order atomics arrive in).  Failure-atomic, like hnswgpu_ivf_add: every new array is staged
+ *     under the handle's lock with its streams quiesced; the handle takes them over only after the last step, and after one
+ *     small readback has shown that every table's grown buckets hold n + m rows (HNSWGPU_EHIP otherwise); on any failure the
+ *     staged arrays are freed and the handle is what it was.  Searches from other threads wait and see the old or the new index.
+ *     Cost: one device copy of the base, the codes and the bucket ids per CALL plus about m / 64 dependent steps of one wave per
+ *     table -- add rows in batches; a bulk load should build the tables instead.
+ *     Returns, checked in this order: -1 for a null handle or m < 0; 0 for m == 0 (nothing happens, whatever `rows` and the
+ *     handle are); -1 for null rows; -3 for a handle without tables, and for one that also holds an HNSW graph, a forest, IVF
+ *     lists or a shard's lists (those structures would miss the rows; the message names which); -5 for n + m >= 2^31 - 1,
+ *     before `rows` is read.  n == 0 is legal. */
 int hnswgpu_lsh_build(hnswgpu_index *idx, int32_t tables, int32_t bits, int32_t proj_dim, int64_t seed);
 int hnswgpu_set_lsh(hnswgpu_index *idx, const float *planes, int32_t tables, int32_t bits);
 int hnswgpu_lsh_sizes(hnswgpu_index *idx, int32_t *tables, int32_t *bits);
 int hnswgpu_lsh_get(hnswgpu_index *idx, float *planes, uint16_t *codes, int64_t *off, int32_t *ids);
 int hnswgpu_lsh_hash(hnswgpu_index *idx, const float *Q, int32_t nq, uint16_t *codes);
+int hnswgpu_lsh_add(hnswgpu_index *idx, const float *rows, int64_t m);
 int hnswgpu_lsh_search(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t num_probes, int32_t probe_radius,
                        int32_t take_main, int32_t take_flip, int32_t *out_ids, float *out_dist);
 int hnswgpu_lsh_search_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t num_probes,
