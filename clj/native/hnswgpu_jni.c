@@ -315,3 +315,43 @@ JNIEXPORT jint JNICALL Java_hnsw_gpu_Native_ivfSearchFilteredEach(JNIEnv *env, j
     if (rc != 0 && rc != HNSWGPU_ENOMEM) throw_last(env);
     return rc;
 }
+
+/* the allow-mask through the hybrid LSH bucket scan: every probed bucket keeps its nearest passing rows (hnswgpu_lsh_search_filtered) */
+JNIEXPORT jint JNICALL Java_hnsw_gpu_Native_lshSearchFiltered(JNIEnv *env, jclass c, jlong h, jfloatArray q, jint nq, jint k,
+                                                              jint probes, jint radius, jint take_main, jint take_flip, jintArray allow,
+                                                              jintArray ids, jfloatArray dist) {
+    if (!q || !allow || !ids || !dist) return throw_iae(env, "lshSearchFiltered: null array");
+    jfloat *pq = (*env)->GetFloatArrayElements(env, q, NULL);
+    jint *pa = (*env)->GetIntArrayElements(env, allow, NULL);
+    jint *pi = (*env)->GetIntArrayElements(env, ids, NULL);
+    jfloat *pd = (*env)->GetFloatArrayElements(env, dist, NULL);
+    int rc = (pq && pa && pi && pd) ? hnswgpu_lsh_search_filtered((hnswgpu_index *)(intptr_t)h, pq, nq, k, probes, radius, take_main, take_flip,
+                                                                  (const uint32_t *)pa, (int32_t *)pi, pd)
+                                    : HNSWGPU_ENOMEM; /* OutOfMemoryError is pending */
+    if (pq) (*env)->ReleaseFloatArrayElements(env, q, pq, JNI_ABORT);
+    if (pa) (*env)->ReleaseIntArrayElements(env, allow, pa, JNI_ABORT);
+    if (pi) (*env)->ReleaseIntArrayElements(env, ids, pi, 0);
+    if (pd) (*env)->ReleaseFloatArrayElements(env, dist, pd, 0);
+    if (rc != 0 && rc != HNSWGPU_ENOMEM) throw_last(env);
+    return rc;
+}
+
+/* ... with one mask per query: `allow` holds nq rows of (n + 31) / 32 ints, row q is query q's mask (hnswgpu_lsh_search_filtered_each) */
+JNIEXPORT jint JNICALL Java_hnsw_gpu_Native_lshSearchFilteredEach(JNIEnv *env, jclass c, jlong h, jfloatArray q, jint nq, jint k,
+                                                                  jint probes, jint radius, jint take_main, jint take_flip,
+                                                                  jintArray allow, jintArray ids, jfloatArray dist) {
+    if (!q || !allow || !ids || !dist) return throw_iae(env, "lshSearchFilteredEach: null array");
+    jfloat *pq = (*env)->GetFloatArrayElements(env, q, NULL);
+    jint *pa = (*env)->GetIntArrayElements(env, allow, NULL);
+    jint *pi = (*env)->GetIntArrayElements(env, ids, NULL);
+    jfloat *pd = (*env)->GetFloatArrayElements(env, dist, NULL);
+    int rc = (pq && pa && pi && pd) ? hnswgpu_lsh_search_filtered_each((hnswgpu_index *)(intptr_t)h, pq, nq, k, probes, radius, take_main,
+                                                                       take_flip, (const uint32_t *)pa, (int32_t *)pi, pd)
+                                    : HNSWGPU_ENOMEM; /* OutOfMemoryError is pending */
+    if (pq) (*env)->ReleaseFloatArrayElements(env, q, pq, JNI_ABORT);
+    if (pa) (*env)->ReleaseIntArrayElements(env, allow, pa, JNI_ABORT);
+    if (pi) (*env)->ReleaseIntArrayElements(env, ids, pi, 0);
+    if (pd) (*env)->ReleaseFloatArrayElements(env, dist, pd, 0);
+    if (rc != 0 && rc != HNSWGPU_ENOMEM) throw_last(env);
+    return rc;
+}

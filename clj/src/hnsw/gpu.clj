@@ -22,6 +22,8 @@
      (add-lsh-vectors! index new-data)                               ; rows join a live hybrid-LSH index: hnswgpu_lsh_add
      (search-lsh index query-vec k :mode :balanced)                  ; hybrid-lsh/search-knn (search-hybrid-multiprobe)
      (search-lsh-batch index queries k :mode :balanced)
+     (search-lsh-filtered index query-vec k filter-fn :mode :balanced) ; the allow-mask through the bucket scan: hnswgpu_lsh_search_filtered
+     (search-lsh-batch-filtered-each index queries k filter-fns)      ; one predicate per query: hnswgpu_lsh_search_filtered_each
      (from-ultra-graph graph)                                        ; a graph built by the reference's own insert-single
      (from-ivf-flat-index ivf)                                       ; an IVFFlatIndex built by the reference's own k-means
      (save idx path) / (load-index path ids)                         ; helper/index-io save-index / load-index
@@ -196,6 +198,85 @@
   "hybrid-lsh/search-knn (hybrid_lsh.clj:350-364) for one query."
   [idx query-vec k & opts]
   (first (apply search-lsh-batch idx [query-vec] k opts)))
+
+;; ---- hybrid LSH filtered search: the allow-mask through the bucket scan (hnswgpu_lsh_search_filtered / _each) ----
+(def ^:private h-lshsearch-filtered
+  (delay (fn-handle "hnswgpu_lsh_search_filtered" (FunctionDescriptor/of I (into-array [P P I I I I I I P P P])))))
+(def ^:private h-lshsearch-filtered-each
+  (delay (fn-handle "hnswgpu_lsh_search_filtered_each" (FunctionDescriptor/of I (into-array [P P I I I I I I P P P])))))
+
+(defn- lsh-mask-of
+  "filter-fn on the caller's ids -> the (n + 31) / 32 words of an allow-mask (bit (i & 31) of word i >> 5, indexed by row)."
+  ^ints [idx filter-fn words]
+  (let [m (int-array words)]
+    (doseq [i (range (count (:ids idx))) :when (filter-fn (nth (:ids idx) i))]
+      (aset m (quot i 32) (unchecked-int (bit-or (aget m (quot i 32)) (bit-shift-left 1 (rem i 32))))))
+    m))
+
+(defn search-lsh-batch-filtered
+  "search-knn-filtered* over the probed buckets for a batch with ONE predicate on the caller's ids, evaluated once per row here
+   into the call's allow-mask.  The device tests the bit where a bucket is read and keeps the 2k / k nearest PASSING rows of every
+   probed bucket: search-hybrid-multiprobe over buckets that list only the passing rows -- not protocol.clj:97-102's search 3k,
+   drop, keep k.  :mode / :num-probes / :probe-radius as search-lsh-batch."
+  [idx queries k filter-fn & {:keys [mode num-probes probe-radius]}]
+  (let [[p r] (lsh-modes mode (lsh-modes :balanced))
+        p (or num-probes p)
+        r (or probe-radius r)]
+    (if (or (empty? (:ids idx)) (empty? queries))
+      (mapv (constantly []) queries)
+      (with-open [arena (Arena/ofConfined)]
+        (let [nq (count queries)
+              words (quot (+ (count (:ids idx)) 31) 32)
+              mask (.allocate arena (* 4 words) 4)
+              _ (MemorySegment/copy (MemorySegment/ofArray (lsh-mask-of idx filter-fn words)) 0 mask 0 (* 4 words))
+              q (floats-of arena (vec queries) (:dim idx))
+              ids (.allocate arena (* 4 nq k) 4)
+              ds (.allocate arena (* 4 nq k) 4)]
+          (check (.invokeWithArguments ^MethodHandle @h-lshsearch-filtered
+                                       [(:handle idx) q (int nq) (int k) (int p) (int r) (int (* 2 k)) (int k) mask ids ds]))
+          (mapv #(results idx ids ds % k) (range nq)))))))
+
+(defn search-lsh-filtered
+  "One query through search-lsh-batch-filtered: seq of {:id :distance} ascending, fewer than k when fewer passing rows are found."
+  [idx query-vec k filter-fn & opts]
+  (first (apply search-lsh-batch-filtered idx [query-vec] k filter-fn opts)))
+
+(defn search-lsh-batch-filtered-each
+  "search-lsh-batch-filtered with one predicate PER QUERY (filter-fns: as many as queries): result q is
+   (search-lsh-filtered idx (nth queries q) k (nth filter-fns q) ...).  An identical predicate is evaluated once; the batch goes
+   through one hnswgpu_lsh_search_filtered_each call, equal predicates adjacent, and the caller's order is restored.  One
+   predicate for the whole batch: search-lsh-batch-filtered."
+  [idx queries k filter-fns & {:keys [mode num-probes probe-radius] :as opts}]
+  (assert (= (count queries) (count filter-fns)) "one filter-fn per query")
+  (cond
+    (empty? queries) []
+    (empty? (:ids idx)) (mapv (constantly []) queries)
+    (every? #(identical? % (first filter-fns)) filter-fns)
+    (apply search-lsh-batch-filtered idx queries k (first filter-fns) (mapcat identity opts))
+    :else
+    (let [[p r] (lsh-modes mode (lsh-modes :balanced))
+          p (or num-probes p)
+          r (or probe-radius r)
+          words (quot (+ (count (:ids idx)) 31) 32)
+          distinct-fns (vec (distinct filter-fns))
+          fn-no (into {} (map-indexed (fn [i f] [f i]) distinct-fns))
+          masks (mapv #(lsh-mask-of idx % words) distinct-fns)
+          qs (vec (sort-by (fn [q] [(fn-no (nth filter-fns q)) q]) (range (count queries))))
+          nq (count qs)
+          out (object-array nq)]
+      (with-open [arena (Arena/ofConfined)]
+        (let [mask (.allocate arena (* 4 words nq) 4)
+              _ (doseq [[j q] (map-indexed vector qs)]
+                  (MemorySegment/copy (MemorySegment/ofArray ^ints (masks (fn-no (nth filter-fns q)))) 0
+                                      mask (* 4 words j) (* 4 words)))
+              qa (floats-of arena (mapv #(nth queries %) qs) (:dim idx))
+              ids (.allocate arena (* 4 nq k) 4)
+              ds (.allocate arena (* 4 nq k) 4)]
+          (check (.invokeWithArguments ^MethodHandle @h-lshsearch-filtered-each
+                                       [(:handle idx) qa (int nq) (int k) (int p) (int r) (int (* 2 k)) (int k) mask ids ds]))
+          (doseq [[j q] (map-indexed vector qs)]
+            (aset out q (results idx ids ds j k)))))
+      (vec out))))
 
 (defn- results [idx ^MemorySegment ids ^MemorySegment ds q k]
   (vec (for [i (range k)

@@ -103,6 +103,10 @@ _SIGS = {
     "hnswgpu_lsh_add": ["p", "p", "i64"],
     "hnswgpu_lsh_search": ["p", "p", "i32", "i32", "i32", "i32", "i32", "i32", "p", "p"],
     "hnswgpu_lsh_search_dev": ["p", "p", "i32", "i32", "i32", "i32", "i32", "i32", "p", "p", "p"],
+    "hnswgpu_lsh_search_filtered": ["p", "p", "i32", "i32", "i32", "i32", "i32", "i32", "p", "p", "p"],
+    "hnswgpu_lsh_search_filtered_dev": ["p", "p", "i32", "i32", "i32", "i32", "i32", "i32", "p", "p", "p", "p"],
+    "hnswgpu_lsh_search_filtered_each": ["p", "p", "i32", "i32", "i32", "i32", "i32", "i32", "p", "p", "p"],
+    "hnswgpu_lsh_search_filtered_each_dev": ["p", "p", "i32", "i32", "i32", "i32", "i32", "i32", "p", "p", "p", "p"],
     "hnswgpu_save": ["p", "p"],
     "hnswgpu_load": ["p", "i32", "p"],
     "hnswgpu_set_profiling": ["p", "i32"],

@@ -31,6 +31,17 @@ static int launch_lsh_scan(int nch, const LshScanArgs &a, hipStream_t st) {
     return 0;
 }
 
+// (a.allow set) the same grid over lsh_filtered_scan_kernel: its queues come first in LDS
+static int launch_lsh_filtered_scan(int nch, const LshScanArgs &a, hipStream_t st) {
+    const size_t keys = a.take_max > kWave ? sizeof(uint64_t) * kNWave * a.take_max : 0;
+    const unsigned grid = static_cast<unsigned>((a.npairs + kNWave - 1) / kNWave);
+#define CALL(N, R, L) hipLaunchKernelGGL((lsh_filtered_scan_kernel<N, R, L>), dim3(grid), dim3(kWG), lsh_queue_bytes(R) + keys, st, a)
+    HG_DISPATCH(nch, a.metric == METRIC_L2, CALL);
+#undef CALL
+    HG_HIP(hipGetLastError());
+    return 0;
+}
+
 // The tables a build or an install stages: the handle takes them over only when every step has succeeded.
 struct LshStaged {
     float *planes = nullptr;
@@ -118,8 +129,11 @@ static int check_lsh_search(const hnswgpu_index *idx, const void *Q, int32_t nq,
 }
 
 // d_Q [nq][dim] -> d_ids / d_dist [nq][k] on `st`; only enqueues.  The caller holds the handle's Call and has checked the arguments.
+// d_allow: null -- the unfiltered search; else the mask of query q is d_allow + q * allow_stride ((n + 31) / 32 words; stride 0:
+// one mask for the call), and the bucket scan is the filtered one.  Hash, probe table, keys and merge are the same either way.
 static int lsh_search_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t num_probes, int32_t probe_radius,
-                              int32_t take_main, int32_t take_flip, int32_t *d_ids, float *d_dist, hipStream_t st) {
+                              int32_t take_main, int32_t take_flip, const uint32_t *d_allow, int64_t allow_stride, int32_t *d_ids,
+                              float *d_dist, hipStream_t st) {
     HG_REQUIRE(idx->lsh_tables > 0, HNSWGPU_ESTATE, "index has no LSH tables (call hnswgpu_lsh_build / hnswgpu_set_lsh first)");
     const int32_t probes = std::min(num_probes, idx->lsh_tables), radius = std::min(probe_radius, idx->lsh_bits);
     const int32_t pp = probes * (1 + radius), take_max = std::max(take_main, take_flip);
@@ -174,7 +188,10 @@ static int lsh_search_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, 
         a.take_max = take_max;
         a.keys = idx->s_partial.as<uint64_t>();
         a.key_rows = idx->s_ord.as<int32_t>();
-        HG_TRY(launch_lsh_scan(idx->nch, a, st));
+        a.allow = d_allow ? d_allow + static_cast<int64_t>(q0) * allow_stride : nullptr;  // (LshPair::q counts from the slice's first query)
+        a.allow_stride = allow_stride;
+        a.n = idx->n;
+        HG_TRY(d_allow ? launch_lsh_filtered_scan(idx->nch, a, st) : launch_lsh_scan(idx->nch, a, st));
         LshMergeArgs g;
         g.keys = a.keys;
         g.key_rows = a.key_rows;
@@ -404,7 +421,7 @@ int hnswgpu_lsh_search_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int
     hipStream_t st = static_cast<hipStream_t>(stream);
     Call call;
     HG_TRY(call.open(idx, st));
-    HG_TRY(lsh_search_enqueue(idx, d_Q, nq, k, num_probes, probe_radius, take_main, take_flip, d_out_ids, d_out_dist, st));
+    HG_TRY(lsh_search_enqueue(idx, d_Q, nq, k, num_probes, probe_radius, take_main, take_flip, nullptr, 0, d_out_ids, d_out_dist, st));
     return call.close();
 }
 
@@ -416,10 +433,68 @@ int hnswgpu_lsh_search(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k
     Call call;
     HG_TRY(call.open(idx, st));
     HG_TRY(call.stage_in(Q, nq, k));
-    HG_TRY(lsh_search_enqueue(idx, idx->s_q.as<float>(), nq, k, num_probes, probe_radius, take_main, take_flip, idx->s_ids.as<int32_t>(),
-                              idx->s_outd.as<float>(), st));
+    HG_TRY(lsh_search_enqueue(idx, idx->s_q.as<float>(), nq, k, num_probes, probe_radius, take_main, take_flip, nullptr, 0,
+                              idx->s_ids.as<int32_t>(), idx->s_outd.as<float>(), st));
     HG_TRY(call.stage_out(out_ids, out_dist, static_cast<int64_t>(nq) * k));
     return call.close();
+}
+
+// ---- filtered search: the allow-mask through the bucket scan (lsh_filtered_scan_kernel; the contract: include/hnswgpu.h) ----
+// One body for both forms of the mask: Single is stride 0, Each stride (n + 31) / 32.  Device arrays: enqueues only, reads
+// nothing back -- nothing needs a count, the wave that reads a bucket filters it.
+static int lsh_filtered_dev(hnswgpu_index *idx, MaskForm form, const float *d_Q, int32_t nq, int32_t k, int32_t num_probes,
+                            int32_t probe_radius, int32_t take_main, int32_t take_flip, const uint32_t *d_allow, int32_t *d_out_ids,
+                            float *d_out_dist, void *stream) {
+    HG_TRY(check_lsh_search(idx, d_Q, nq, k, num_probes, probe_radius, take_main, take_flip, d_out_ids, d_out_dist));
+    if (nq == 0) return 0;
+    HG_REQUIRE(d_allow, HNSWGPU_EINVAL, "allow is null");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Call call;
+    HG_TRY(call.open(idx, st));
+    const int64_t stride = form == MaskForm::Each ? (idx->n + 31) / 32 : 0;
+    HG_TRY(lsh_search_enqueue(idx, d_Q, nq, k, num_probes, probe_radius, take_main, take_flip, d_allow, stride, d_out_ids, d_out_dist, st));
+    return call.close();
+}
+
+// Host arrays.  One caller's batch, its mask -- Each: its [nq][W] masks -- staged whole as hnswgpu_ivf_search_filtered_each
+// stages its own: masks differ between callers, so the call takes no part in the call combiner.
+static int lsh_filtered_host(hnswgpu_index *idx, MaskForm form, const float *Q, int32_t nq, int32_t k, int32_t num_probes,
+                             int32_t probe_radius, int32_t take_main, int32_t take_flip, const uint32_t *allow, int32_t *out_ids,
+                             float *out_dist) {
+    HG_TRY(check_lsh_search(idx, Q, nq, k, num_probes, probe_radius, take_main, take_flip, out_ids, out_dist));
+    if (nq == 0) return 0;
+    HG_REQUIRE(allow, HNSWGPU_EINVAL, "allow is null");
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_TRY(call.stage_in(Q, nq, k));
+    if (idx->n > 0) HG_TRY(call.stage_mask(allow, form, nq));  // (an empty index has no mask words, and its search reads none)
+    const int64_t stride = form == MaskForm::Each ? (idx->n + 31) / 32 : 0;
+    HG_TRY(lsh_search_enqueue(idx, idx->s_q.as<float>(), nq, k, num_probes, probe_radius, take_main, take_flip,
+                              idx->s_fmask.as<uint32_t>(), stride, idx->s_ids.as<int32_t>(), idx->s_outd.as<float>(), st));
+    HG_TRY(call.stage_out(out_ids, out_dist, static_cast<int64_t>(nq) * k));
+    return call.close();
+}
+
+int hnswgpu_lsh_search_filtered_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t num_probes, int32_t probe_radius,
+                                    int32_t take_main, int32_t take_flip, const uint32_t *d_allow, int32_t *d_out_ids, float *d_out_dist,
+                                    void *stream) {
+    return lsh_filtered_dev(idx, MaskForm::Single, d_Q, nq, k, num_probes, probe_radius, take_main, take_flip, d_allow, d_out_ids,
+                            d_out_dist, stream);
+}
+int hnswgpu_lsh_search_filtered(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t num_probes, int32_t probe_radius,
+                                int32_t take_main, int32_t take_flip, const uint32_t *allow, int32_t *out_ids, float *out_dist) {
+    return lsh_filtered_host(idx, MaskForm::Single, Q, nq, k, num_probes, probe_radius, take_main, take_flip, allow, out_ids, out_dist);
+}
+int hnswgpu_lsh_search_filtered_each_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t num_probes,
+                                         int32_t probe_radius, int32_t take_main, int32_t take_flip, const uint32_t *d_allow_each,
+                                         int32_t *d_out_ids, float *d_out_dist, void *stream) {
+    return lsh_filtered_dev(idx, MaskForm::Each, d_Q, nq, k, num_probes, probe_radius, take_main, take_flip, d_allow_each, d_out_ids,
+                            d_out_dist, stream);
+}
+int hnswgpu_lsh_search_filtered_each(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t num_probes, int32_t probe_radius,
+                                     int32_t take_main, int32_t take_flip, const uint32_t *allow_each, int32_t *out_ids, float *out_dist) {
+    return lsh_filtered_host(idx, MaskForm::Each, Q, nq, k, num_probes, probe_radius, take_main, take_flip, allow_each, out_ids, out_dist);
 }
 
 }  // extern "C"

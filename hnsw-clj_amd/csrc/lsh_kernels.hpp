@@ -8,6 +8,7 @@
 //   lsh_hash_kernel         codes of base rows and of queries alike: bit i of table t = dot(plane[t][i], row) >= 0 in the GEMV order
 //   lsh_probe_kernel        query codes -> one LshPair per (query, probe): the bucket's slice of `ids`, ord_base, take
 //   lsh_bucket_scan_kernel  one wave per pair: the `take` smallest keys (distance, ord) of the bucket, and their rows
+//   lsh_filtered_scan_kernel  the same over the bucket's rows whose bit is set in the pair's allow-mask (one body for both mask forms)
 //   lsh_merge_kernel        one wave per query: the pairs' ascending lists merged by key, a row's later occurrences dropped, k out
 // Truncation per probe comes BEFORE the dedup, as in the reference; a row's distance does not depend on the rows that share its
 // step (finished in its own lane from its own sum), so equal rows have equal distance bits and the dedup only ever drops an
@@ -120,13 +121,19 @@ struct LshScanArgs {
     int32_t take_max;    // slots per pair of the outputs (the larger of the two takes)
     uint64_t *keys;      // [npairs][take_max] ascending, all-ones padded
     int32_t *key_rows;   // [npairs][take_max] the keys' rows, -1 padded
+    // lsh_filtered_scan_kernel only: the mask of pair p is allow + p.q * allow_stride, (n + 31) / 32 words indexed by row id
+    const uint32_t *allow;
+    int64_t allow_stride;  // words between the masks of two queries; 0: one mask shared by all
+    int64_t n;
 };
 
-// ivf_gathered_step (filter_kernels.hpp) for a bucket: lane b (and every lane beyond RB, as row RB - 1) brings the ROW of bucket
-// position pos0 + b in `myrow`; the same loads, sums and finish in the same order, so a row's distance has the bits it has in every
-// GEMV-order scan.  The key is built from the position in the probe stream, which here is not the row.
+// ivf_gathered_step (filter_kernels.hpp) for a bucket: lane b (and every lane beyond RB, as row RB - 1) brings the ROW of a bucket
+// position in `myrow` and that position's place in the probe stream in `myord`; the same loads, sums and finish in the same order,
+// so a row's distance has the bits it has in every GEMV-order scan.  The key is built from the position in the probe stream,
+// which here is not the row.  One step for both bucket scans: the unfiltered one brings consecutive positions, the filtered one
+// whatever its queue holds.
 template <int NCH, int RB, bool L2M>
-__device__ __forceinline__ void lsh_gathered_step(const LshScanArgs &a, const float4 (&q)[NCH], float qn, int32_t myrow, uint32_t ord0,
+__device__ __forceinline__ void lsh_gathered_step(const LshScanArgs &a, const float4 (&q)[NCH], float qn, int32_t myrow, uint32_t myord,
                                                   int nvalid, int take, int lane, bool regk, uint64_t &mine, uint64_t *mylist, int &cnt,
                                                   uint64_t &thr) {
     float4 r[RB][NCH];
@@ -146,7 +153,7 @@ __device__ __forceinline__ void lsh_gathered_step(const LshScanArgs &a, const fl
     for (int b = 0; b < RB; b++) {
         if (b < nvalid) {  // wave-uniform
             const float d = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(myd), b));
-            const uint64_t key = make_key(d, ord0 + static_cast<uint32_t>(b));
+            const uint64_t key = make_key(d, static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(myord), b)));
             if (key < thr) {
                 if (regk) {
                     wave_insert_reg(mine, cnt, take, key, lane);
@@ -157,6 +164,18 @@ __device__ __forceinline__ void lsh_gathered_step(const LshScanArgs &a, const fl
                 }
             }
         }
+    }
+}
+
+// The epilogue of both bucket scans: the wave's list to keys[pair][take_max], from its registers (take <= 64) or from LDS, and
+// each key's row beside it (the ord says where in the bucket it stands).
+__device__ __forceinline__ void lsh_store_keys(const LshScanArgs &a, int64_t pair, const LshPair &p, int lane, bool regk, uint64_t mine,
+                                               const uint64_t *mylist, int cnt) {
+    for (int i = lane; i < a.take_max; i += kWave) {
+        const uint64_t key = regk ? (i < kWave ? mine : ~0ull) : (i < cnt ? mylist[i] : ~0ull);
+        const int64_t at = pair * a.take_max + i;
+        a.keys[at] = key;
+        a.key_rows[at] = key != ~0ull ? a.ids[p.begin + (static_cast<uint32_t>(key) - p.ord_base)] : -1;
     }
 }
 
@@ -185,16 +204,95 @@ __global__ __launch_bounds__(kWG) void lsh_bucket_scan_kernel(LshScanArgs a) {
             const int32_t myrow = a.ids[at < p.end ? at : p.end - 1];
             const int64_t left = p.end - base;
             const int nvalid = __builtin_amdgcn_readfirstlane(static_cast<int>(left < RB ? left : RB));
-            lsh_gathered_step<NCH, RB, L2M>(a, q, qn, myrow, p.ord_base + static_cast<uint32_t>(base - p.begin), nvalid, take, lane, regk,
-                                            mine, mylist, cnt, thr);
+            lsh_gathered_step<NCH, RB, L2M>(a, q, qn, myrow, p.ord_base + static_cast<uint32_t>(base - p.begin) + lane, nvalid, take, lane,
+                                            regk, mine, mylist, cnt, thr);
         }
     }
-    for (int i = lane; i < a.take_max; i += kWave) {
-        const uint64_t key = regk ? (i < kWave ? mine : ~0ull) : (i < cnt ? mylist[i] : ~0ull);
-        const int64_t at = pair * a.take_max + i;
-        a.keys[at] = key;
-        a.key_rows[at] = key != ~0ull ? a.ids[p.begin + (static_cast<uint32_t>(key) - p.ord_base)] : -1;
+    lsh_store_keys(a, pair, p, lane, regk, mine, mylist, cnt);
+}
+
+// ---- the allow-mask through the bucket scan ------------------------------------------------------------------------------------
+// The reference's search over buckets that list only their passing rows, in bucket order: the bit is tested where the bucket is
+// read (ivf_each_scan_kernel's pattern, filter_kernels.hpp).  One wave per pair as above; of a block of 64 bucket positions,
+// lane i reads row = ids[pos] and the word of ITS PAIR's mask that holds the row's bit (a row outside [0, n) reads as clear), one
+// ballot gives the block's passing lanes, and a passing lane's prefix popcount is its slot in the wave's queue in LDS (kWave + RB
+// entries: fewer than RB left over, at most 64 new).  The queue holds positions RELATIVE to p.begin: the row is
+// ids[p.begin + rel], the key's ord p.ord_base + rel -- the position in the UNFILTERED probe stream, monotone in the filtered
+// one, so the epilogue and lsh_merge_kernel are the unfiltered search's.  Whenever RB positions are queued, RB go through
+// lsh_gathered_step; what is left moves to the front, and the remainder after the last block is flushed with the clamped lane.
+// No workgroup barrier (a wave without a pair has left): a wave's queue is its own, ordered by a wavefront fence + wave_barrier.
+// Per probed position: 4 B of ids and a gathered mask word (rows ascend inside a bucket: so do a block's words); the f32 row
+// only where the bit is set.
+// LDS: [kNWave][kWave + RB] queued positions, then [kNWave][take_max] keys (take_max > 64)
+__host__ __device__ constexpr size_t lsh_queue_bytes(int rb) { return sizeof(int32_t) * kNWave * (kWave + rb); }
+
+// lane b's queued position of a step over que[0 .. nvalid): entry b, clamped into the step (every lane beyond RB as row RB - 1)
+template <int RB>
+__device__ __forceinline__ int32_t lsh_queued(const int32_t *que, int nvalid, int lane) {
+    int at = lane < RB ? lane : RB - 1;
+    at = at < nvalid ? at : nvalid - 1;
+    return que[at];
+}
+
+template <int NCH, int RB, bool L2M>
+__global__ __launch_bounds__(kWG) void lsh_filtered_scan_kernel(LshScanArgs a) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    constexpr int kQueue = kWave + RB;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x >> 6;
+    const int64_t pair = static_cast<int64_t>(blockIdx.x) * kNWave + wave;
+    if (pair >= a.npairs) return;
+    const LshPair p = a.pairs[pair];
+    const int take = p.take;
+    const bool regk = take <= kWave;
+    int32_t *que = reinterpret_cast<int32_t *>(smem) + wave * kQueue;
+    uint64_t *mylist = reinterpret_cast<uint64_t *>(smem + lsh_queue_bytes(RB)) + static_cast<size_t>(wave) * a.take_max;  // (16 * kQueue bytes in: aligned)
+    uint64_t mine = ~0ull, thr = ~0ull;
+    int cnt = 0;
+    if (p.begin < p.end) {
+        float4 q[NCH];
+        load_query<NCH>(q, a.Q + p.q * a.qld, a.dim, lane);
+        const float qn = (!L2M && a.metric == METRIC_COS) ? query_norm<NCH>(q) : 0.0f;
+        const uint32_t *allow = a.allow + static_cast<int64_t>(p.q) * a.allow_stride;
+        const int32_t *bucket = a.ids + p.begin;
+        const int64_t len = p.end - p.begin;  // (a bucket holds n < 2^31 rows at the most: a queued position fits 32 bits)
+        int have = 0;  // queued positions (wave-uniform), < RB between two blocks
+        for (int64_t base = 0; base < len; base += kWave) {
+            const int64_t rel = base + lane;
+            const int64_t row = bucket[rel < len ? rel : len - 1];  // clamped, unconditional
+            const bool in = rel < len && row >= 0 && row < a.n;
+            const uint32_t w = allow[in ? row >> 5 : 0];
+            const bool ok = in && ((w >> (row & 31)) & 1u);
+            const unsigned long long m = __ballot(ok);
+            if (ok) que[have + __popcll(m & ((1ull << lane) - 1ull))] = static_cast<int32_t>(rel);
+            have += __popcll(m);
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            int head = 0;
+            for (; have - head >= RB; head += RB) {
+                const int32_t myrel = lsh_queued<RB>(que + head, RB, lane);
+                lsh_gathered_step<NCH, RB, L2M>(a, q, qn, bucket[myrel], p.ord_base + static_cast<uint32_t>(myrel), RB, take, lane, regk, mine,
+                                                mylist, cnt, thr);
+            }
+            const int rem = have - head;  // < RB
+            if (head > 0 && rem > 0) {  // the leftovers to the front
+                int32_t v = 0;
+                if (lane < rem) v = que[head + lane];
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                if (lane < rem) que[lane] = v;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            have = rem;
+        }
+        if (have > 0) {
+            const int32_t myrel = lsh_queued<RB>(que, have, lane);
+            lsh_gathered_step<NCH, RB, L2M>(a, q, qn, bucket[myrel], p.ord_base + static_cast<uint32_t>(myrel), have, take, lane, regk, mine,
+                                            mylist, cnt, thr);
+        }
     }
+    lsh_store_keys(a, pair, p, lane, regk, mine, mylist, cnt);
 }
 
 __device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {

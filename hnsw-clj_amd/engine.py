@@ -634,6 +634,46 @@ class Index:
         check(lib().hnswgpu_lsh_search(self._h, _p(Q), len(Q), k, num_probes, probe_radius, take_main, take_flip, _p(ids), _p(d)))
         return ids, d
 
+    def lsh_search_filtered(self, Q, k, allow, num_probes=6, probe_radius=2, take_main=None, take_flip=None, out=None):
+        """hnswgpu_lsh_search_filtered (numpy queries and pack_mask words) / _dev (torch device tensors for both, torch's
+        current stream: enqueues only): lsh_search over buckets that list only the rows ``allow`` lets pass -- the bit is
+        tested where the bucket is read, the takes apply to the passing rows; -1 / +inf where fewer than k are found."""
+        take_main = 2 * k if take_main is None else take_main
+        take_flip = k if take_flip is None else take_flip
+        if hasattr(Q, "is_cuda") and Q.is_cuda:
+            Q, ids, d, st = self._dev_args(Q, k, out)
+            allow = self._dev_mask(allow, Q)
+            check(lib().hnswgpu_lsh_search_filtered_dev(self._h, Q.data_ptr(), Q.shape[0], k, num_probes, probe_radius, take_main,
+                                                        take_flip, allow.data_ptr(), ids.data_ptr(), d.data_ptr(), st))
+            return ids, d
+        Q = _queries(Q, self.dim)
+        allow = _mask_words(allow, self.n)
+        ids = np.empty((len(Q), k), np.int32)
+        d = np.empty((len(Q), k), np.float32)
+        check(lib().hnswgpu_lsh_search_filtered(self._h, _p(Q), len(Q), k, num_probes, probe_radius, take_main, take_flip,
+                                                _p(allow), _p(ids), _p(d)))
+        return ids, d
+
+    def lsh_search_filtered_each(self, Q, k, allow_each, num_probes=6, probe_radius=2, take_main=None, take_flip=None, out=None):
+        """hnswgpu_lsh_search_filtered_each / _dev: row q is lsh_search_filtered(Q[q:q + 1], k, allow_each[q], ...) -- one mask
+        per query (pack_masks) in one chain of launches."""
+        take_main = 2 * k if take_main is None else take_main
+        take_flip = k if take_flip is None else take_flip
+        if hasattr(Q, "is_cuda") and Q.is_cuda:
+            Q, ids, d, st = self._dev_args(Q, k, out)
+            allow_each = self._dev_masks(allow_each, Q)
+            check(lib().hnswgpu_lsh_search_filtered_each_dev(self._h, Q.data_ptr(), Q.shape[0], k, num_probes, probe_radius,
+                                                             take_main, take_flip, allow_each.data_ptr(), ids.data_ptr(),
+                                                             d.data_ptr(), st))
+            return ids, d
+        Q = _queries(Q, self.dim)
+        allow_each = _mask_rows(allow_each, self.n, len(Q))
+        ids = np.empty((len(Q), k), np.int32)
+        d = np.empty((len(Q), k), np.float32)
+        check(lib().hnswgpu_lsh_search_filtered_each(self._h, _p(Q), len(Q), k, num_probes, probe_radius, take_main, take_flip,
+                                                     _p(allow_each), _p(ids), _p(d)))
+        return ids, d
+
     # -- zero-copy device entry points (torch tensors, torch's current stream)
     def _dev_args(self, Q, k, out=None):
         import torch

@@ -4,6 +4,8 @@
 of which the first 12 form the bucket id), hashes every row on the device and files it in its buckets;
 ``search_hybrid`` / ``search_hybrid_multiprobe`` / ``search_knn(index, q, k[, mode])`` probe the query's buckets and their
 one-bit neighbours with the HIP bucket scan (hnswgpu_lsh_search).  Queries may be one vector or a batch.
+``search_knn_filtered`` / ``search_batch_filtered`` / ``search_batch_filtered_each`` (not in the reference, whose index is served
+by the protocol's post-filter) carry a predicate on the ids into the bucket scan as an allow-mask (hnswgpu_lsh_search_filtered).
 
 One difference, on purpose: the reference computes cosine whatever ``:distance-fn`` says (its ``query-norm`` is never nil,
 :157-166); here the index's metric decides, as in every other mirror.
@@ -117,6 +119,81 @@ def search_knn(index, query_vec, k, mode=None):
 def search_batch(index, queries, k, mode=None):
     q = np.asarray(queries, np.float32)
     return search_knn(index, q[None, :] if q.ndim == 1 else q, k, mode)
+
+
+def _allow_bits(index, filter_fn):
+    """The predicate on the caller's ids, evaluated once per row on the host (or a ready bool array of length n)."""
+    if callable(filter_fn):
+        return np.fromiter((bool(filter_fn(i)) for i in index.ids), np.bool_, len(index.ids))
+    bits = np.asarray(filter_fn)
+    if bits.dtype != np.bool_ or bits.shape != (index.index.n,):
+        raise ValueError("filter_fn must be a predicate on ids or a bool array with one entry per row")
+    return bits
+
+
+def search_batch_filtered(index, queries, k, filter_fn, mode=None):
+    """FilterableIndex/search-knn-filtered* (api/protocol.clj:34-41) over the probed buckets, one predicate per call:
+    ``filter_fn`` is called once per row with ``index.ids[i]`` (or is a bool array of length n) and packed into one
+    allow-mask; the device tests the bit where a bucket is read and keeps the nearest 2 k / k PASSING rows of every probed
+    bucket (hnswgpu_lsh_search_filtered) -- search_hybrid_multiprobe over buckets that list only the passing rows, not the
+    reference's "search 3k, drop, keep k".  Modes map through mode_config."""
+    queries = np.asarray(queries, np.float32)
+    if queries.ndim == 1:
+        queries = queries[None, :]
+    if len(queries) == 0:
+        return []
+    probes, radius = mode_config(mode)
+    bits = _allow_bits(index, filter_fn)
+    if index.index.n == 0:
+        return [[] for _ in range(len(queries))]
+    ids, d = index.index.lsh_search_filtered(queries, int(k), engine.pack_mask(bits, index.index.n), probes, radius,
+                                             2 * int(k), int(k))
+    return [_format(index, ids[i], d[i]) for i in range(len(queries))]
+
+
+def search_batch_filtered_each(index, queries, k, filter_fns, mode=None):
+    """search_batch_filtered with one predicate (or bool array) PER QUERY: row q equals
+    ``search_knn_filtered(index, queries[q], k, filter_fns[q], mode)``.  The same object, or equal bits, is evaluated and
+    packed once; the batch goes through ONE hnswgpu_lsh_search_filtered_each call, equal masks adjacent (neighbouring waves
+    then read the same mask words), and the original order is restored.  A batch whose filters are all one mask takes
+    search_batch_filtered's single-mask call."""
+    queries = np.asarray(queries, np.float32)
+    if queries.ndim == 1:
+        queries = queries[None, :]
+    if len(filter_fns) != len(queries):
+        raise ValueError("one filter per query: %d filters for %d queries" % (len(filter_fns), len(queries)))
+    if len(queries) == 0:
+        return []
+    n = index.index.n
+    masks, by_obj, by_bits, which = [], {}, {}, []   # distinct masks: (bits, packed)
+    for f in filter_fns:
+        m = by_obj.get(id(f))
+        if m is None:
+            bits = _allow_bits(index, f)
+            key = bits.tobytes()
+            m = by_bits.get(key)
+            if m is None:
+                m = by_bits[key] = len(masks)
+                masks.append((bits, engine.pack_mask(bits, n)))
+            by_obj[id(f)] = m
+        which.append(m)
+    if len(masks) == 1:
+        return search_batch_filtered(index, queries, k, masks[0][0], mode)
+    if n == 0:
+        return [[] for _ in range(len(queries))]
+    probes, radius = mode_config(mode)
+    qs = sorted(range(len(queries)), key=lambda q: (which[q], q))   # equal masks adjacent
+    rows = np.stack([masks[which[q]][1] for q in qs])
+    gi, gd = index.index.lsh_search_filtered_each(queries[qs], int(k), rows, probes, radius, 2 * int(k), int(k))
+    ids = np.empty((len(queries), int(k)), np.int32)
+    d = np.empty((len(queries), int(k)), np.float32)
+    ids[qs], d[qs] = gi, gd
+    return [_format(index, ids[i], d[i]) for i in range(len(queries))]
+
+
+def search_knn_filtered(index, query_vec, k, filter_fn, mode=None):
+    """search_batch_filtered for one query: a list of ``{"id", "distance"}`` ascending, fewer than k when fewer are found."""
+    return search_batch_filtered(index, np.asarray(query_vec, np.float32)[None, :], k, filter_fn, mode)[0]
 
 
 def index_info(index):

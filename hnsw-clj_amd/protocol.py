@@ -2,7 +2,8 @@
 FilterableIndex and the default helpers (filtered search by post-filtering, :96-101; sequential batch search, :92-95) over
 the two GPU-served index types.  The HNSW index filters on the device (ultra_fast.search_knn_filtered).  GpuIvfFlatIndex is
 the reference's IVF index, which has no FilterableIndex and is served by the default helper; GpuFilterableIvfFlatIndex adds
-the protocol on top of it, filtering inside the list scan (ivf_flat.search_knn_filtered)."""
+the protocol on top of it, filtering inside the list scan (ivf_flat.search_knn_filtered); GpuHybridLshIndex and
+GpuFilterableHybridLshIndex are the same pair for the hybrid LSH index (hybrid_lsh.search_knn_filtered: inside the bucket scan)."""
 from . import hybrid_lsh, index_io, ivf_flat, ultra_fast
 
 
@@ -127,6 +128,17 @@ class GpuHybridLshIndex(ANNIndex, BatchSearchIndex):
 
     def index_type_star(self):
         return "hybrid-lsh"
+
+
+class GpuFilterableHybridLshIndex(GpuHybridLshIndex, FilterableIndex):
+    """The hybrid LSH index with the allow-mask through its bucket scan: every probed bucket keeps its nearest PASSING rows."""
+
+    def search_knn_filtered_star(self, query, k, filter_fn, mode=None):
+        return hybrid_lsh.search_knn_filtered(self.index, query, k, filter_fn, mode)
+
+    def search_batch_filtered(self, queries, k, filter_fns, mode=None):
+        """search_knn_filtered_star for a batch, one predicate per query, in one chain of launches (not in the reference)."""
+        return hybrid_lsh.search_batch_filtered_each(self.index, queries, k, filter_fns, mode)
 
 
 def supports_filtering(index):

@@ -673,6 +673,50 @@ int hnswgpu_lsh_search_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int
                            int32_t probe_radius, int32_t take_main, int32_t take_flip, int32_t *d_out_ids, float *d_out_dist,
                            void *stream);
 
+/* hnswgpu_lsh_search_filtered / _each / _dev: the allow-mask through the bucket scan (lsh_filtered_scan_kernel).  As for
+ * hnswgpu_ivf_search_filtered, post-filtering ("search 3 k, drop what fails, keep k") is the wrong rule here, and more so: the
+ * candidate set is already cut per probe, before the dedup, to take_main / take_flip rows of each bucket, so when a fraction
+ * p of the rows passes about 3 k p results survive, and every row of every probed bucket is read whatever the mask says.
+ * Instead the bit is tested where the bucket is read, and only the passing rows are fetched.
+ *   Semantics: search-hybrid-multiprobe (:305-342) run over buckets that list only their passing rows, in bucket order.  For
+ *     each probed bucket of a query, in the UNFILTERED probe order (table by table; own bucket, then bit 0, 1, ... flipped),
+ *     the rows whose bit is clear are dropped and the `take` nearest of the rest are kept (take_main for the own bucket,
+ *     take_flip for a neighbour; a bucket with no more passing rows than its take is kept whole, otherwise the order is by
+ *     (distance, position in the bucket)).  The pieces are concatenated in probe order, a row's later occurrences dropped,
+ *     the rest sorted stably by distance and cut to k; truncation still comes before the dedup; -1 / +inf padding.
+ *   Equivalence: the result is what hnswgpu_lsh_search returns on a handle created over the passing rows alone (in row
+ *     order) with hnswgpu_set_lsh(the same planes), with ids mapped back: ids and distance bits are equal.  "Filter first,
+ *     then take" is the point: it differs from post-filtering wherever a bucket has more than `take` rows.  An all-ones
+ *     mask returns hnswgpu_lsh_search's ids and distance bits.
+ *   Keys carry the position in the unfiltered probe stream, which is monotone in the filtered one, so ties resolve as in
+ *     the sub-index; the probe table, the key epilogue and the merge are the unfiltered search's.  Distances have the bits
+ *     of every GEMV-order scan: a row's bits depend neither on which rows share its step nor on the mask.
+ *   Mask: exactly that of the other filtered calls.  `allow` is (n + 31) / 32 words indexed by row id, bits at positions
+ *     >= n are ignored; it is an argument, never handle state: nothing is kept or persisted, and after hnswgpu_lsh_add the
+ *     next call brings a longer mask.  allow_each is [nq][W] row-major; result row q equals the single-mask call with query
+ *     q and mask q.
+ *   Cost per probed position: 4 B of bucket ids and a gathered mask word; the f32 row only where the bit is set.
+ *   _dev entries only enqueue on `stream`: no synchronise, no readback (nothing needs a count: the wave that reads a bucket
+ *     filters it).  Host entries stage one caller's batch, masks included (as hnswgpu_ivf_search_filtered_each stages its
+ *     own), and take no part in the combining of concurrent callers.
+ *   Errors: everything hnswgpu_lsh_search checks, in its order; nq == 0 returns 0; a null mask is -1 (when nq > 0); -3 a
+ *     handle without tables; n == 0 fills the padding as the unfiltered call does; the 2^32 probe-stream limit is unchanged
+ *     (it is about the unfiltered stream, which the keys still number).
+ *   Out of scope: groups, shards and forests (they do not know the tables); the tables in the index file; combining
+ *     concurrent filtered callers. */
+int hnswgpu_lsh_search_filtered(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t num_probes,
+                                int32_t probe_radius, int32_t take_main, int32_t take_flip, const uint32_t *allow,
+                                int32_t *out_ids, float *out_dist);
+int hnswgpu_lsh_search_filtered_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t num_probes,
+                                    int32_t probe_radius, int32_t take_main, int32_t take_flip, const uint32_t *d_allow,
+                                    int32_t *d_out_ids, float *d_out_dist, void *stream);
+int hnswgpu_lsh_search_filtered_each(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t num_probes,
+                                     int32_t probe_radius, int32_t take_main, int32_t take_flip, const uint32_t *allow_each,
+                                     int32_t *out_ids, float *out_dist);
+int hnswgpu_lsh_search_filtered_each_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t num_probes,
+                                         int32_t probe_radius, int32_t take_main, int32_t take_flip,
+                                         const uint32_t *d_allow_each, int32_t *d_out_ids, float *d_out_dist, void *stream);
+
 /* ---- ONE index over several GPUs (hnsw-clj_amd/csrc/group.hip) ---------------------------------------------------
  * The reference shards inside one process: search-partitioned scatters a query to its partitions, takes a top-k per
  * partition, concatenates, sorts and takes k (src/hnsw/ann/partition/partitioned_hnsw.clj:149-196).  A group gives the
