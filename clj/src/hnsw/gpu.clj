@@ -20,6 +20,7 @@
      (add-ivf-vectors! index new-data)                               ; the same for a live IVF-FLAT index: hnswgpu_ivf_add
      (build-lsh-index data :metric :cosine)                          ; hnsw.ann.hash.hybrid-lsh/build-lsh-index: (Random. 42), 8 x 12 bits
      (add-lsh-vectors! index new-data)                               ; rows join a live hybrid-LSH index: hnswgpu_lsh_add
+     (remove-lsh-vectors! index ids)                                 ; ... and leave it: hnswgpu_lsh_remove
      (search-lsh index query-vec k :mode :balanced)                  ; hybrid-lsh/search-knn (search-hybrid-multiprobe)
      (search-lsh-batch index queries k :mode :balanced)
      (search-lsh-filtered index query-vec k filter-fn :mode :balanced) ; the allow-mask through the bucket scan: hnswgpu_lsh_search_filtered
@@ -171,6 +172,32 @@
     (check (.invokeWithArguments ^MethodHandle @h-lshadd
                                  [(:handle idx) (floats-of arena (mapv second new-data) (:dim idx)) (long (count new-data))])))
   (update idx :ids into (map first new-data)))
+
+(def ^:private h-lshremove (delay (fn-handle "hnswgpu_lsh_remove" (FunctionDescriptor/of I (into-array [P P L P])))))
+
+(declare ints-of)
+
+(defn remove-lsh-vectors!
+  "The inverse of add-lsh-vectors! (the reference's index has no remove either; what is restated is its bucket order,
+   hybrid_lsh.clj:105-129): the vectors with the given ids leave the base matrix and every table's buckets, a bucket's kept members
+   stay in their order, and the kept rows are renumbered densely in their old order (hnswgpu_lsh_remove).  An unknown id throws
+   before the device is touched.  Returns the index with the ids removed.  One call per batch is the efficient shape: a call
+   copies the kept rows once, whatever it removes.  Unverified like the rest of this namespace: no JVM where the library is built."
+  [idx ids]
+  (let [gone (set ids)
+        known (set (:ids idx))]
+    (when-let [bad (first (remove known gone))]
+      (throw (ex-info "remove-lsh-vectors!: unknown id" {:id bad})))
+    (if (empty? gone)
+      idx
+      (let [rows (vec (keep-indexed (fn [i id] (when (gone id) i)) (:ids idx)))]
+        (with-open [arena (Arena/ofConfined)]
+          (let [n-after (.allocate arena 8 8)]
+            (check (.invokeWithArguments ^MethodHandle @h-lshremove
+                                         [(:handle idx) (ints-of arena rows) (long (count rows)) n-after]))
+            (let [kept (vec (remove gone (:ids idx)))]
+              (assert (= (count kept) (.getAtIndex n-after L 0)))
+              (assoc idx :ids kept))))))))
 
 (def ^:private lsh-modes {:turbo [2 1] :fast [4 1] :balanced [6 2] :accurate [8 3] :precise [8 4]})   ; hybrid_lsh.clj:350-364
 

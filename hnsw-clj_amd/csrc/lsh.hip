@@ -1,13 +1,17 @@
 // lsh.hip -- the hybrid LSH index (src/hnsw/ann/hash/hybrid_lsh.clj): hyperplanes, hash, buckets, multi-probe search
-// (C ABI: include/hnswgpu.h, "Hybrid LSH"; kernels: lsh_kernels.hpp, and lsh_add_kernels.hpp for rows that join live tables).
+// (C ABI: include/hnswgpu.h, "Hybrid LSH"; kernels: lsh_kernels.hpp, lsh_add_kernels.hpp for rows that join live tables and
+// lsh_remove_kernels.hpp for rows that leave them).
 #include <string.h>
 
+#include <new>
 #include <vector>
 
 #include "engine.hpp"
 #include "javarandom.hpp"
 #include "lsh_add_kernels.hpp"
 #include "lsh_kernels.hpp"
+#include "lsh_remove_ids.hpp"
+#include "lsh_remove_kernels.hpp"
 
 namespace hg {
 
@@ -52,6 +56,30 @@ struct LshStaged {
         void *ptrs[] = {planes, codes, off, ids};
         for (void *p : ptrs)
             if (p) (void)hipFree(p);
+    }
+};
+
+// The rows of a handle and their tables as hnswgpu_lsh_add / hnswgpu_lsh_remove stage them: what is left in it when it goes out
+// of scope is freed -- the staged arrays on an early return, the handle's old ones behind the swap.
+struct LshStagedRows {
+    float *base = nullptr, *norms = nullptr;
+    uint32_t *qrows = nullptr;
+    float4 *qmeta = nullptr;
+    LshStaged lsh;  // (the planes stay the handle's)
+    ~LshStagedRows() {
+        void *ptrs[] = {base, norms, qrows, qmeta};
+        for (void *p : ptrs)
+            if (p) (void)hipFree(p);
+    }
+    void swap_into(hnswgpu_index *idx, int64_t n) {
+        std::swap(idx->d_base, base);  // (what the handle had goes with this object)
+        std::swap(idx->d_norms, norms);
+        std::swap(idx->d_qrows, qrows);
+        std::swap(idx->d_qmeta, qmeta);
+        std::swap(idx->d_lsh_codes, lsh.codes);
+        std::swap(idx->d_lsh_off, lsh.off);
+        std::swap(idx->d_lsh_ids, lsh.ids);
+        idx->n = n;
     }
 };
 
@@ -323,17 +351,7 @@ int hnswgpu_lsh_add(hnswgpu_index *idx, const float *rows, int64_t m) {
     const int32_t tables = idx->lsh_tables;
     // Failure-atomic, as hnswgpu_ivf_add: every array the call makes is STAGED and goes with `nw` on an early return; the handle's
     // fields change only behind the last step (idx->mu is held and the streams are quiesced: no caller sees a state in between).
-    struct Grown {
-        float *base = nullptr, *norms = nullptr;
-        uint32_t *qrows = nullptr;
-        float4 *qmeta = nullptr;
-        LshStaged lsh;  // (the planes stay the handle's)
-        ~Grown() {
-            void *ptrs[] = {base, norms, qrows, qmeta};
-            for (void *p : ptrs)
-                if (p) (void)hipFree(p);
-        }
-    } nw;
+    LshStagedRows nw;
     auto grow = [&]() -> int {
         // ---- 1. the base matrix, its norms and base-order int8 rows grow
         HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.base), sizeof(float) * static_cast<size_t>(n1) * ld));
@@ -403,14 +421,126 @@ int hnswgpu_lsh_add(hnswgpu_index *idx, const float *rows, int64_t m) {
         (void)hipStreamSynchronize(st);  // (nothing of the chain is in flight when `nw` frees what it staged)
         return rc;
     }
-    std::swap(idx->d_base, nw.base);  // (what the handle had goes with `nw`)
-    std::swap(idx->d_norms, nw.norms);
-    std::swap(idx->d_qrows, nw.qrows);
-    std::swap(idx->d_qmeta, nw.qmeta);
-    std::swap(idx->d_lsh_codes, nw.lsh.codes);
-    std::swap(idx->d_lsh_off, nw.lsh.off);
-    std::swap(idx->d_lsh_ids, nw.lsh.ids);
-    idx->n = n1;
+    nw.swap_into(idx, n1);
+    return call.close();
+}
+
+// Rows leave the tables of a live handle (include/hnswgpu.h).  The reference's HybridIndex has no remove either; what is restated
+// is again its bucket order: the shrunken handle holds what hnswgpu_create(the kept rows in their old order) + hnswgpu_set_lsh(the
+// same planes) holds.  One chain on the handle's stream (lsh_remove_kernels.hpp): mark, rank, the kept rows / norms / codes to
+// their ranks, removed rows per bucket, offsets, and the bucket ids compacted and renumbered (chunk counts, their scan, the
+// scatter); ONE readback of 2 x tables + 1 words says that the rank scan, every table's last offset and every table's compacted
+// ids all hold n1 rows.  Norms and codes are copied, not computed again; the int8 rows are made over the new base as add does.
+int hnswgpu_lsh_remove(hnswgpu_index *idx, const int32_t *rows, int64_t m, int64_t *n_after) {
+    HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
+    HG_REQUIRE(m >= 0, HNSWGPU_EINVAL, "m must be >= 0");
+    HG_REQUIRE(rows || m == 0, HNSWGPU_EINVAL, "rows is null");
+    if (m == 0) {  // nothing to remove: nothing happens, whatever the handle holds
+        std::lock_guard<std::mutex> lk(idx->mu);
+        if (n_after) *n_after = idx->n;
+        return 0;
+    }
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_REQUIRE(idx->lsh_tables > 0, HNSWGPU_ESTATE, "index has no LSH tables (call hnswgpu_lsh_build / hnswgpu_set_lsh first)");
+    HG_REQUIRE(!idx->has_graph || idx->nparts > 0, HNSWGPU_ESTATE,
+               "the index holds an HNSW graph: it would keep the old numbering of the rows");
+    HG_REQUIRE(idx->nparts == 0, HNSWGPU_ESTATE,
+               "the index holds a forest of HNSW sub-graphs: its parts would keep the old numbering of the rows");
+    HG_REQUIRE(idx->nlist == 0 || idx->d_glistoff != nullptr, HNSWGPU_ESTATE,
+               "the index holds IVF lists: they would keep the old numbering of the rows");
+    HG_REQUIRE(idx->d_glistoff == nullptr, HNSWGPU_ESTATE,
+               "a shard of a larger IVF index (hnswgpu_set_ivf_shard) cannot shrink alone: its lists would keep the old numbering");
+    const int64_t n0 = idx->n;
+    int64_t distinct = 0, bad = -1;
+    try {
+        bad = lsh_remove_check_ids(rows, m, n0, &distinct);  // on the host array, before anything is enqueued
+    } catch (const std::bad_alloc &) {  // (its sorted copy of the ids)
+        set_error("host allocation failed");
+        return HNSWGPU_ENOMEM;
+    }
+    HG_REQUIRE(bad < 0, HNSWGPU_EINVAL, "rows[%lld] = %d is not a row of the index (n = %lld)", (long long)bad, rows[bad], (long long)n0);
+    const int64_t n1 = n0 - distinct;
+    HG_TRY(call.quiesce());
+    const int64_t ld = idx->ld, nb = static_cast<int64_t>(1) << idx->lsh_bits;
+    const int32_t tables = idx->lsh_tables;
+    LshStagedRows nw;  // failure-atomic, as hnswgpu_lsh_add: the handle's fields change only behind the last step
+    auto shrink = [&]() -> int {
+        if (n1 > 0) {
+            HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.base), sizeof(float) * static_cast<size_t>(n1) * ld));
+            HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.norms), sizeof(float) * static_cast<size_t>(n1)));
+            HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.lsh.codes), sizeof(uint16_t) * static_cast<size_t>(n1) * tables));
+            HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.lsh.ids), sizeof(int32_t) * static_cast<size_t>(n1) * tables));
+        }
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.lsh.off), sizeof(int64_t) * tables * (nb + 1)));
+        // scratch, 16-byte sections: [gate | keep | removed] zeroed, then word_rank, chunk_base, the call's ids
+        LshRemoveArgs a;
+        a.n0 = n0;
+        a.n1 = n1;
+        a.m = m;
+        a.W = (n0 + 31) / 32;
+        a.ld = ld;
+        a.tables = tables;
+        a.bits = idx->lsh_bits;
+        a.nchunks = (n0 + kWG - 1) / kWG;
+        auto sect = [](size_t bytes) { return (bytes + 15) / 16 * 16; };
+        const size_t o_keep = sect(sizeof(int64_t) * kLshRemoveGate), o_removed = o_keep + sect(sizeof(uint32_t) * a.W),
+                     o_rank = o_removed + sect(sizeof(uint32_t) * tables * nb), o_chunk = o_rank + sect(sizeof(uint32_t) * a.W),
+                     o_ids = o_chunk + sect(sizeof(uint32_t) * tables * a.nchunks), bytes = o_ids + sect(sizeof(int32_t) * m);
+        HG_TRY(idx->s_misc.ensure(bytes));
+        char *s = idx->s_misc.as<char>();
+        HG_HIP(hipMemsetAsync(s, 0, o_rank, st));
+        HG_HIP(hipMemcpyAsync(s + o_ids, rows, sizeof(int32_t) * static_cast<size_t>(m), hipMemcpyHostToDevice, st));
+        a.gate = reinterpret_cast<int64_t *>(s);
+        a.keep = reinterpret_cast<uint32_t *>(s + o_keep);
+        a.removed = reinterpret_cast<uint32_t *>(s + o_removed);
+        a.word_rank = reinterpret_cast<uint32_t *>(s + o_rank);
+        a.chunk_base = reinterpret_cast<uint32_t *>(s + o_chunk);
+        a.rows = reinterpret_cast<const int32_t *>(s + o_ids);
+        a.old_base = idx->d_base;
+        a.old_norms = idx->d_norms;
+        a.old_codes = idx->d_lsh_codes;
+        a.new_base = nw.base;
+        a.new_norms = nw.norms;
+        a.new_codes = nw.lsh.codes;
+        a.old_off = idx->d_lsh_off;
+        a.new_off = nw.lsh.off;
+        a.old_ids = idx->d_lsh_ids;
+        a.new_ids = nw.lsh.ids;
+        const unsigned T = static_cast<unsigned>(tables), chunks = static_cast<unsigned>(a.nchunks);
+        hipLaunchKernelGGL(lsh_remove_mark_kernel, dim3(static_cast<unsigned>((m + kWG - 1) / kWG)), dim3(kWG), 0, st, a);
+        hipLaunchKernelGGL(lsh_remove_rank_kernel, dim3(1), dim3(kWG), 0, st, a);
+        if (n1 > 0) hipLaunchKernelGGL(lsh_remove_rows_kernel, dim3(static_cast<unsigned>((n0 + kNWave - 1) / kNWave)), dim3(kWG), 0, st, a);
+        const unsigned count_wgs = static_cast<unsigned>(std::min<int64_t>((a.W + kWG - 1) / kWG, 256));
+        hipLaunchKernelGGL(lsh_remove_count_kernel, dim3(count_wgs, T), dim3(kWG), 0, st, a);
+        hipLaunchKernelGGL(lsh_remove_offsets_kernel, dim3(T), dim3(kWG), 0, st, a);
+        hipLaunchKernelGGL(lsh_remove_chunk_count_kernel, dim3(chunks, T), dim3(kWG), 0, st, a);
+        hipLaunchKernelGGL(lsh_remove_chunk_scan_kernel, dim3(T), dim3(kWG), 0, st, a);
+        if (n1 > 0) hipLaunchKernelGGL(lsh_remove_ids_kernel, dim3(chunks, T), dim3(kWG), 0, st, a);
+        HG_HIP(hipGetLastError());
+        if (idx->d_qrows && n1 > 0) HG_TRY(quantize_rows(idx, nw.base, n1, &nw.qrows, &nw.qmeta, st));  // (as add: one pass over the new base)
+        // ---- the one readback
+        int64_t gate[kLshRemoveGate];
+        HG_HIP(hipMemcpyAsync(gate, a.gate, sizeof(gate), hipMemcpyDeviceToHost, st));
+        HG_HIP(hipStreamSynchronize(st));
+        HG_REQUIRE(gate[2 * kLshMaxTables] == n1, HNSWGPU_EHIP, "the mask keeps %lld rows, not %lld", (long long)gate[2 * kLshMaxTables],
+                   (long long)n1);
+        for (int32_t t = 0; t < tables; t++) {
+            HG_REQUIRE(gate[t] == n1, HNSWGPU_EHIP, "the shrunken buckets of table %d hold %lld rows, not %lld", t, (long long)gate[t],
+                       (long long)n1);
+            HG_REQUIRE(gate[kLshMaxTables + t] == n1, HNSWGPU_EHIP, "the compacted ids of table %d hold %lld rows, not %lld", t,
+                       (long long)gate[kLshMaxTables + t], (long long)n1);
+        }
+        return 0;
+    };
+    const int rc = shrink();
+    if (rc != 0) {
+        (void)hipStreamSynchronize(st);  // (nothing of the chain is in flight when `nw` frees what it staged)
+        return rc;
+    }
+    nw.swap_into(idx, n1);  // (n1 == 0: no base, norms, codes or ids -- an empty handle with planes and all-zero offsets)
+    if (n_after) *n_after = n1;
     return call.close();
 }
 

@@ -618,6 +618,20 @@ class Index:
         self.n += len(rows)
         return np.arange(first, self.n, dtype=np.int32)
 
+    def lsh_remove(self, rows):
+        """hnswgpu_lsh_remove: the rows named by `rows` (row ids, any order, repeats count once) leave the base and every hash
+        table's buckets; the kept rows are renumbered densely in their old order.  Returns `kept`, the int64 array of the old
+        row ids that remain, ascending: the row now numbered i was kept[i]."""
+        rows = np.ascontiguousarray(rows, np.int32).reshape(-1)
+        n_after = C.c_int64(-1)
+        check(lib().hnswgpu_lsh_remove(self._h, _p(rows), len(rows), C.byref(n_after)))
+        keep = np.ones(self.n, np.bool_)
+        keep[rows] = False
+        kept = np.flatnonzero(keep).astype(np.int64)
+        assert len(kept) == n_after.value, "hnswgpu_lsh_remove left %d rows, the id list %d" % (n_after.value, len(kept))
+        self.n = int(n_after.value)
+        return kept
+
     def lsh_search(self, Q, k, num_probes=6, probe_radius=2, take_main=None, take_flip=None, out=None):
         """hnswgpu_lsh_search (numpy queries) / hnswgpu_lsh_search_dev (a torch device tensor, torch's current stream):
         multi-probe search; the takes default to the reference's 2 k and k."""

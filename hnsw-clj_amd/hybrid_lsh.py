@@ -6,6 +6,8 @@ of which the first 12 form the bucket id), hashes every row on the device and fi
 one-bit neighbours with the HIP bucket scan (hnswgpu_lsh_search).  Queries may be one vector or a batch.
 ``search_knn_filtered`` / ``search_batch_filtered`` / ``search_batch_filtered_each`` (not in the reference, whose index is served
 by the protocol's post-filter) carry a predicate on the ids into the bucket scan as an allow-mask (hnswgpu_lsh_search_filtered).
+``add_vectors`` / ``remove_vectors`` (not in the reference either) change a live index on the device (hnswgpu_lsh_add /
+hnswgpu_lsh_remove).
 
 One difference, on purpose: the reference computes cosine whatever ``:distance-fn`` says (its ``query-norm`` is never nil,
 :157-166); here the index's metric decides, as in every other mirror.
@@ -79,6 +81,28 @@ def add_vectors(index, data):
     if ids:
         index.index.lsh_add(rows)
         index.ids.extend(ids)
+    return index
+
+
+def remove_vectors(index, ids):
+    """The reference's hybrid-lsh index has no remove either (build-lsh-index returns an immutable record); what is restated
+    is its bucket order (hybrid_lsh.clj:105-129: a bucket lists its rows in insertion order): ``ids`` are the caller's ids, the
+    form ``index.ids`` holds; their vectors leave the base and every table's buckets, the kept members of a bucket stay in
+    their order (hnswgpu_lsh_remove), and ``index.ids`` follows.  An unknown id raises KeyError before the device is touched;
+    an id of several rows removes them all.  Empty ``ids`` does nothing.  Returns the index."""
+    ids = list(ids)
+    if not ids:
+        return index
+    rows_of = {}
+    for row, i in enumerate(index.ids):
+        rows_of.setdefault(i, []).append(row)
+    rows = []
+    for i in ids:
+        if i not in rows_of:
+            raise KeyError(i)
+        rows.extend(rows_of[i])
+    kept = index.index.lsh_remove(np.asarray(rows, np.int32))
+    index.ids = [index.ids[i] for i in kept]
     return index
 
 

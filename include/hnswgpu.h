@@ -660,13 +660,42 @@ int hnswgpu_get_tuning(int32_t key, int64_t *value, int32_t *is_set);
  *     Returns, checked in this order: -1 for a null handle or m < 0; 0 for m == 0 (nothing happens, whatever `rows` and the
  *     handle are); -1 for null rows; -3 for a handle without tables, and for one that also holds an HNSW graph, a forest, IVF
  *     lists or a shard's lists (those structures would miss the rows; the message names which); -5 for n + m >= 2^31 - 1,
- *     before `rows` is read.  n == 0 is legal. */
+ *     before `rows` is read.  n == 0 is legal.
+ *
+ *   hnswgpu_lsh_remove: rows leave a LIVE handle with tables (the reference's HybridIndex has no remove either; what is
+ *     restated is again its bucket order).  `rows` is m row ids of the handle in host memory, in any order; an id named twice
+ *     is removed once.  The kept rows are renumbered densely in their old order: the new id of a kept row r is the number of
+ *     kept rows below r.  *n_after (may be NULL) gets the rows the handle holds afterwards.
+ *     After the call the handle holds, bit for bit, what hnswgpu_create(the kept rows in their old order) +
+ *     hnswgpu_set_rejection_test(same mode) + hnswgpu_set_lsh(the same planes) holds: base, norms, the base-order int8 rows and
+ *     their meta where the handle has them, and what hnswgpu_lsh_get exports -- codes [n1][tables], per table off[2^bits + 1]
+ *     and ids[n1], rows ascending inside a bucket (a bucket's kept members stay in their order; the rank is monotone) -- hence
+ *     the ids and distance bits of hnswgpu_lsh_search / _dev, hnswgpu_exact_knn, hnswgpu_norms, hnswgpu_batch_distances,
+ *     hnswgpu_lsh_hash, and the bytes hnswgpu_save writes (still without the tables).  It is the permanent form of
+ *     hnswgpu_lsh_search_filtered: a search after the removal finds the rows, under their new ids, and the distance bits that
+ *     the filtered search found before it under the mask of the kept rows.
+ *     Everything happens on the device, in one chain on the handle's stream: only the m ids go up, norms and codes are copied
+ *     (not computed again), no code or bucket id is read back, and every entry's destination is a function of the mask and the
+ *     old arrays alone (prefix counts of kept entries), never of the order atomics arrive in.  Failure-atomic, like
+ *     hnswgpu_lsh_add: nothing is changed in place, every new array is staged under the handle's lock with its streams
+ *     quiesced, and the handle takes them over only after ONE small readback has shown that the rank scan, every table's last
+ *     offset and every table's compacted ids all count n - (distinct ids) rows (HNSWGPU_EHIP otherwise); on any failure the
+ *     staged arrays are freed and the handle is what it was.  Searches from other threads wait and see the old or the new
+ *     index.  Peak memory: the old plus the new arrays for the length of the call, as for add.  Cost: one device copy of the
+ *     kept rows, codes and bucket ids per CALL, whatever m is -- remove rows in batches.
+ *     Returns, checked in this order: -1 for a null handle (before m == 0 and before any HIP call), for m < 0, and for null
+ *     rows with m > 0; 0 for m == 0 (nothing happens, *n_after = n, whatever the handle holds); -3 for a handle without
+ *     tables, and for one that also holds an HNSW graph, a forest, IVF lists or a shard's lists (those structures would keep
+ *     the old numbering; the message names which); -1 for an id outside [0, n), checked on the host array before anything is
+ *     enqueued.  The handle is untouched in every one of these cases.  Removing every row is legal: it leaves an empty handle
+ *     with tables (planes, all-zero offsets), the state hnswgpu_lsh_add accepts, and that handle can be grown again. */
 int hnswgpu_lsh_build(hnswgpu_index *idx, int32_t tables, int32_t bits, int32_t proj_dim, int64_t seed);
 int hnswgpu_set_lsh(hnswgpu_index *idx, const float *planes, int32_t tables, int32_t bits);
 int hnswgpu_lsh_sizes(hnswgpu_index *idx, int32_t *tables, int32_t *bits);
 int hnswgpu_lsh_get(hnswgpu_index *idx, float *planes, uint16_t *codes, int64_t *off, int32_t *ids);
 int hnswgpu_lsh_hash(hnswgpu_index *idx, const float *Q, int32_t nq, uint16_t *codes);
 int hnswgpu_lsh_add(hnswgpu_index *idx, const float *rows, int64_t m);
+int hnswgpu_lsh_remove(hnswgpu_index *idx, const int32_t *rows, int64_t m, int64_t *n_after);
 int hnswgpu_lsh_search(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t num_probes, int32_t probe_radius,
                        int32_t take_main, int32_t take_flip, int32_t *out_ids, float *out_dist);
 int hnswgpu_lsh_search_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t num_probes,
