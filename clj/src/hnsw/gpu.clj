@@ -18,6 +18,7 @@
      (top-k-distances index query-vec k)                             ; simd-optimized/top-k-distances
      (add-vector! index new-data)                                    ; hnsw.api/add-vector!, insert-single on a live index
      (add-ivf-vectors! index new-data)                               ; the same for a live IVF-FLAT index: hnswgpu_ivf_add
+     (remove-ivf-vectors! index ids)                                 ; ... and leave it: hnswgpu_ivf_remove
      (build-lsh-index data :metric :cosine)                          ; hnsw.ann.hash.hybrid-lsh/build-lsh-index: (Random. 42), 8 x 12 bits
      (add-lsh-vectors! index new-data)                               ; rows join a live hybrid-LSH index: hnswgpu_lsh_add
      (remove-lsh-vectors! index ids)                                 ; ... and leave it: hnswgpu_lsh_remove
@@ -138,6 +139,33 @@
                                  [(:handle idx) (floats-of arena (mapv second new-data) (:dim idx)) (long (count new-data))])))
   (update idx :ids into (map first new-data)))
 
+(declare ints-of)
+
+(def ^:private h-ivfremove (delay (fn-handle "hnswgpu_ivf_remove" (FunctionDescriptor/of I (into-array [P P L P])))))
+
+(defn remove-ivf-vectors!
+  "The inverse of add-ivf-vectors! (the reference's IVFFlatIndex has no remove; what is restated is its list order,
+   ivf_flat.clj:137-211): the vectors with the given ids leave the base matrix and their partitions, a partition's kept members
+   stay in their order, the centroids stay, and the kept rows are renumbered densely in their old order (hnswgpu_ivf_remove).  An
+   unknown id throws before the device is touched.  Returns the index with the ids removed.  One call per batch is the efficient
+   shape: a call copies the kept rows once, whatever it removes.  Unverified like the rest of this namespace: no JVM where the
+   library is built."
+  [idx ids]
+  (let [gone (set ids)
+        known (set (:ids idx))]
+    (when-let [bad (first (remove known gone))]
+      (throw (ex-info "remove-ivf-vectors!: unknown id" {:id bad})))
+    (if (empty? gone)
+      idx
+      (let [rows (vec (keep-indexed (fn [i id] (when (gone id) i)) (:ids idx)))]
+        (with-open [arena (Arena/ofConfined)]
+          (let [n-after (.allocate arena 8 8)]
+            (check (.invokeWithArguments ^MethodHandle @h-ivfremove
+                                         [(:handle idx) (ints-of arena rows) (long (count rows)) n-after]))
+            (let [kept (vec (remove gone (:ids idx)))]
+              (assert (= (count kept) (.getAtIndex n-after L 0)))
+              (assoc idx :ids kept))))))))
+
 ;; ---- hybrid LSH (hnsw.ann.hash.hybrid-lsh): hnswgpu_lsh_build / hnswgpu_lsh_search ----
 (def ^:private h-lshbuild  (delay (fn-handle "hnswgpu_lsh_build" (FunctionDescriptor/of I (into-array [P I I I L])))))
 (def ^:private h-lshset    (delay (fn-handle "hnswgpu_set_lsh" (FunctionDescriptor/of I (into-array [P P I I])))))
@@ -174,8 +202,6 @@
   (update idx :ids into (map first new-data)))
 
 (def ^:private h-lshremove (delay (fn-handle "hnswgpu_lsh_remove" (FunctionDescriptor/of I (into-array [P P L P])))))
-
-(declare ints-of)
 
 (defn remove-lsh-vectors!
   "The inverse of add-lsh-vectors! (the reference's index has no remove either; what is restated is its bucket order,

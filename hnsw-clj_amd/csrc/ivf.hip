@@ -9,6 +9,8 @@
 #include "engine.hpp"
 #include "stream_kernels.hpp"
 #include "ivf_add_kernels.hpp"
+#include "ivf_remove_kernels.hpp"
+#include "lsh_remove_ids.hpp"
 #include "javarandom.hpp"
 
 namespace hg {
@@ -1969,6 +1971,51 @@ int hnswgpu_ivf_build(hnswgpu_index *idx, int32_t nlist, int32_t max_iter, int64
     return call.close();
 }
 
+// The device arrays of a handle with lists as hnswgpu_ivf_add / hnswgpu_ivf_remove stage them: the handle's own (of_handle), or
+// a staged set that the handle's fields point at for the last step and for good after the readback (to_handle).
+struct IvfArrays {
+    float *base = nullptr, *norms = nullptr, *lrows = nullptr, *lnorms = nullptr;
+    uint32_t *qrows = nullptr, *lctile = nullptr;
+    float4 *qmeta = nullptr, *lcmeta = nullptr, *lhmeta = nullptr;
+    uint2 *lhalf = nullptr;
+    int64_t *listoff = nullptr;
+    int32_t *listids = nullptr;
+    bool alias = false;
+    void of_handle(const hnswgpu_index *idx) {
+        base = idx->d_base, norms = idx->d_norms, lrows = idx->d_lrows, lnorms = idx->d_lnorms;
+        qrows = idx->d_qrows, qmeta = idx->d_qmeta, lctile = idx->d_lctile, lcmeta = idx->d_lcmeta;
+        lhalf = idx->d_lhalf, lhmeta = idx->d_lhmeta, listoff = idx->d_listoff, listids = idx->d_listids;
+        alias = idx->lrows_alias;
+    }
+    void to_handle(hnswgpu_index *idx, int64_t n) const {
+        idx->d_base = base, idx->d_norms = norms, idx->d_lrows = lrows, idx->d_lnorms = lnorms;
+        idx->d_qrows = qrows, idx->d_qmeta = qmeta, idx->d_lctile = lctile, idx->d_lcmeta = lcmeta;
+        idx->d_lhalf = lhalf, idx->d_lhmeta = lhmeta, idx->d_listoff = listoff, idx->d_listids = listids;
+        idx->lrows_alias = alias;
+        idx->n = n;
+    }
+    void release() {
+        if (alias) lrows = lnorms = nullptr;  // the base rows themselves: freed once
+        void *ptrs[] = {base, norms, lrows, lnorms, qrows, lctile, qmeta, lcmeta, lhmeta, lhalf, listoff, listids};
+        for (void *p : ptrs)
+            if (p) (void)hipFree(p);
+        *this = IvfArrays();
+    }
+};
+
+// the host mirrors and list-length bounds of lists that grew or shrank to n rows
+static void take_list_mirrors(hnswgpu_index *idx, std::vector<int64_t> &h_off, std::vector<int32_t> &h_ids, int64_t n) {
+    idx->h_listoff.swap(h_off);
+    idx->h_listids.swap(h_ids);
+    idx->max_list_len = 0;
+    idx->min_list_len = idx->h_listoff[1] - idx->h_listoff[0];
+    for (int l = 0; l < idx->nlist; l++) {
+        idx->max_list_len = std::max(idx->max_list_len, idx->h_listoff[l + 1] - idx->h_listoff[l]);
+        idx->min_list_len = std::min(idx->min_list_len, idx->h_listoff[l + 1] - idx->h_listoff[l]);
+    }
+    idx->ivf_n_global = n;
+}
+
 // Rows join the lists of a live handle (include/hnswgpu.h).  The reference's IVFFlatIndex is an immutable record; what is
 // restated is its assignment rule (assign-to-nearest-centroid, ivf_flat.clj:79-90) and its "inverted lists in index order"
 // (:137-211): the grown handle holds what hnswgpu_create(all rows) + hnswgpu_set_ivf(same centroids, merged lists) holds.
@@ -1999,36 +2046,8 @@ int hnswgpu_ivf_add(hnswgpu_index *idx, const float *rows, int64_t m) {
     // arrays only for the last step (the int8 / half copies, made by the functions that make them for fresh lists; idx->mu
     // is held and the streams are quiesced: no caller sees the intermediate state) and get their old values back, the
     // staged arrays freed, if any step fails.  On success the old arrays are freed.
-    struct Arrays {
-        float *base = nullptr, *norms = nullptr, *lrows = nullptr, *lnorms = nullptr;
-        uint32_t *qrows = nullptr, *lctile = nullptr;
-        float4 *qmeta = nullptr, *lcmeta = nullptr, *lhmeta = nullptr;
-        uint2 *lhalf = nullptr;
-        int64_t *listoff = nullptr;
-        int32_t *listids = nullptr;
-        bool alias = false;
-    } nw, old;
-    auto of_handle = [&](Arrays &a) {
-        a.base = idx->d_base, a.norms = idx->d_norms, a.lrows = idx->d_lrows, a.lnorms = idx->d_lnorms;
-        a.qrows = idx->d_qrows, a.qmeta = idx->d_qmeta, a.lctile = idx->d_lctile, a.lcmeta = idx->d_lcmeta;
-        a.lhalf = idx->d_lhalf, a.lhmeta = idx->d_lhmeta, a.listoff = idx->d_listoff, a.listids = idx->d_listids;
-        a.alias = idx->lrows_alias;
-    };
-    auto to_handle = [&](const Arrays &a, int64_t n) {
-        idx->d_base = a.base, idx->d_norms = a.norms, idx->d_lrows = a.lrows, idx->d_lnorms = a.lnorms;
-        idx->d_qrows = a.qrows, idx->d_qmeta = a.qmeta, idx->d_lctile = a.lctile, idx->d_lcmeta = a.lcmeta;
-        idx->d_lhalf = a.lhalf, idx->d_lhmeta = a.lhmeta, idx->d_listoff = a.listoff, idx->d_listids = a.listids;
-        idx->lrows_alias = a.alias;
-        idx->n = n;
-    };
-    auto free_arrays = [](Arrays &a) {
-        if (a.alias) a.lrows = a.lnorms = nullptr;  // the base rows themselves: freed once
-        void *ptrs[] = {a.base, a.norms, a.lrows, a.lnorms, a.qrows, a.lctile, a.qmeta, a.lcmeta, a.lhmeta, a.lhalf, a.listoff, a.listids};
-        for (void *p : ptrs)
-            if (p) (void)hipFree(p);
-        a = Arrays();
-    };
-    of_handle(old);
+    IvfArrays nw, old;
+    old.of_handle(idx);
     bool installed = false;
     std::vector<int64_t> h_off;
     std::vector<int32_t> h_ids;
@@ -2112,11 +2131,11 @@ int hnswgpu_ivf_add(hnswgpu_index *idx, const float *rows, int64_t m) {
         }
         // ---- the int8 tile codes and the half copy over the grown list rows: made as for a fresh set of lists, by the
         // handle's rejection mode (ensure_list_codes / ensure_list_half read the handle)
-        to_handle(nw, n1);
+        nw.to_handle(idx, n1);
         installed = true;
         HG_TRY(ensure_list_codes(idx, st));
         HG_TRY(ensure_list_half(idx, st));
-        of_handle(nw);
+        nw.of_handle(idx);
         // ---- 5. one readback: flags, offsets, ids
         h_off.resize(static_cast<size_t>(nlist) + 1);
         h_ids.resize(static_cast<size_t>(n1));
@@ -2137,21 +2156,166 @@ int hnswgpu_ivf_add(hnswgpu_index *idx, const float *rows, int64_t m) {
     }
     if (rc != 0) {
         (void)hipStreamSynchronize(st);
-        if (installed) of_handle(nw);  // (whatever the last step made is the staged set's)
-        to_handle(old, n0);
-        free_arrays(nw);
+        if (installed) nw.of_handle(idx);  // (whatever the last step made is the staged set's)
+        old.to_handle(idx, n0);
+        nw.release();
         return rc;
     }
-    idx->h_listoff.swap(h_off);
-    idx->h_listids.swap(h_ids);
-    idx->max_list_len = 0;
-    idx->min_list_len = idx->h_listoff[1] - idx->h_listoff[0];
-    for (int l = 0; l < nlist; l++) {
-        idx->max_list_len = std::max(idx->max_list_len, idx->h_listoff[l + 1] - idx->h_listoff[l]);
-        idx->min_list_len = std::min(idx->min_list_len, idx->h_listoff[l + 1] - idx->h_listoff[l]);
+    take_list_mirrors(idx, h_off, h_ids, n1);
+    old.release();  // (the first-search verdict of a mode-1 handle, ivf_calibrated / ivf_stream_off, stays: not measured again)
+    return call.close();
+}
+
+// Rows leave the lists of a live handle (include/hnswgpu.h).  The reference's IVFFlatIndex has no remove either; what is restated
+// is again its "inverted lists in index order" (ivf_flat.clj:137-211): the shrunken handle holds what hnswgpu_create(the kept
+// rows in their old order) + hnswgpu_set_ivf(same centroids, compacted lists) holds.  One chain on the handle's stream
+// (remove_kernels.hpp, ivf_remove_kernels.hpp): mark, rank, the kept base rows / norms to their ranks, kept list positions per
+// chunk, their scan, the list ids compacted and renumbered (recording every old position's destination), the shrunken offsets,
+// the list-order rows / norms to their destinations; the int8 rows, the int8 tiles and the half copy are made over the moved
+// rows as for fresh lists; ONE readback holds the three counts of the gate, the offsets and the ids for the host mirrors.
+int hnswgpu_ivf_remove(hnswgpu_index *idx, const int32_t *rows, int64_t m, int64_t *n_after) {
+    HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
+    HG_REQUIRE(m >= 0, HNSWGPU_EINVAL, "m must be >= 0");
+    HG_REQUIRE(rows || m == 0, HNSWGPU_EINVAL, "rows is null");
+    if (m == 0) {  // nothing to remove: nothing happens, whatever the handle holds
+        std::lock_guard<std::mutex> lk(idx->mu);
+        if (n_after) *n_after = idx->n;
+        return 0;
     }
-    idx->ivf_n_global = n1;
-    free_arrays(old);  // (the first-search verdict of a mode-1 handle, ivf_calibrated / ivf_stream_off, stays: not measured again)
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_REQUIRE(idx->nlist > 0, HNSWGPU_ESTATE, "index has no IVF lists (call hnswgpu_ivf_build / hnswgpu_set_ivf first)");
+    HG_REQUIRE(idx->nparts == 0, HNSWGPU_ESTATE,
+               "the index holds a forest of HNSW sub-graphs: its parts would keep the old numbering of the rows");
+    HG_REQUIRE(!idx->has_graph, HNSWGPU_ESTATE, "the index holds an HNSW graph: it would keep the old numbering of the rows");
+    HG_REQUIRE(idx->lsh_tables == 0, HNSWGPU_ESTATE, "the index holds LSH tables: they would keep the old numbering of the rows");
+    HG_REQUIRE(idx->d_glistoff == nullptr, HNSWGPU_ESTATE,
+               "a shard of a larger IVF index (hnswgpu_set_ivf_shard) cannot shrink alone: the other shards number its rows too");
+    const int64_t n0 = idx->n;
+    int64_t distinct = 0, bad = -1;
+    try {
+        bad = lsh_remove_check_ids(rows, m, n0, &distinct);  // on the host array, before anything is enqueued
+    } catch (const std::bad_alloc &) {  // (its sorted copy of the ids)
+        set_error("host allocation failed");
+        return HNSWGPU_ENOMEM;
+    }
+    HG_REQUIRE(bad < 0, HNSWGPU_EINVAL, "rows[%lld] = %d is not a row of the index (n = %lld)", (long long)bad, rows[bad], (long long)n0);
+    const int64_t n1 = n0 - distinct;
+    HG_TRY(call.quiesce());
+    const int64_t ld = idx->ld;
+    const int32_t nlist = idx->nlist;
+    // Failure-atomic, as hnswgpu_ivf_add: every array the call makes is STAGED; the handle's fields point at the staged arrays
+    // only for the int8 / half copies (idx->mu is held and the streams are quiesced) and for good behind the one readback.
+    IvfArrays nw, old;
+    old.of_handle(idx);
+    bool installed = false;
+    std::vector<int64_t> h_off;
+    std::vector<int32_t> h_ids;
+    auto shrink = [&]() -> int {
+        const size_t rows1 = static_cast<size_t>(std::max<int64_t>(n1, 1));
+        if (n1 > 0) {
+            HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.base), sizeof(float) * rows1 * ld));
+            HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.norms), sizeof(float) * rows1));
+        }
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.listoff), sizeof(int64_t) * (nlist + 1)));
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.listids), sizeof(int32_t) * rows1));
+        // lists that are the base rows in place stay so: list order is row order and the rank is monotone, the compacted ids
+        // are again the identity.  (No rows left: what hnswgpu_set_ivf makes over an empty base, lists of their own.)
+        nw.alias = old.alias && n1 > 0;
+        if (nw.alias) {
+            nw.lrows = nw.base;
+            nw.lnorms = nw.norms;
+        } else {
+            HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.lrows), sizeof(float) * rows1 * ld));
+            HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.lnorms), sizeof(float) * rows1));
+        }
+        // scratch, 16-byte sections: [gate | keep] zeroed, then word_rank, chunk_base, dest, the call's ids
+        IvfRemoveArgs a;
+        memset(&a, 0, sizeof(a));
+        a.r.n0 = n0;
+        a.r.n1 = n1;
+        a.r.m = m;
+        a.r.W = (n0 + 31) / 32;
+        a.r.ld = ld;
+        a.r.nchunks = (n0 + kWG - 1) / kWG;
+        auto sect = [](size_t bytes) { return (bytes + 15) / 16 * 16; };
+        const size_t o_keep = sect(sizeof(int64_t) * kLshRemoveGate), o_rank = o_keep + sect(sizeof(uint32_t) * a.r.W),
+                     o_chunk = o_rank + sect(sizeof(uint32_t) * a.r.W), o_dest = o_chunk + sect(sizeof(uint32_t) * a.r.nchunks),
+                     o_ids = o_dest + sect(sizeof(uint32_t) * n0), bytes = o_ids + sect(sizeof(int32_t) * m);
+        HG_TRY(idx->s_misc.ensure(bytes));
+        char *s = idx->s_misc.as<char>();
+        HG_HIP(hipMemsetAsync(s, 0, o_rank, st));
+        HG_HIP(hipMemcpyAsync(s + o_ids, rows, sizeof(int32_t) * static_cast<size_t>(m), hipMemcpyHostToDevice, st));
+        a.r.gate = reinterpret_cast<int64_t *>(s);
+        a.r.keep = reinterpret_cast<uint32_t *>(s + o_keep);
+        a.r.word_rank = reinterpret_cast<uint32_t *>(s + o_rank);
+        a.r.chunk_base = reinterpret_cast<uint32_t *>(s + o_chunk);
+        a.dest = reinterpret_cast<uint32_t *>(s + o_dest);
+        a.r.rows = reinterpret_cast<const int32_t *>(s + o_ids);
+        a.r.old_base = old.base;
+        a.r.old_norms = old.norms;
+        a.r.new_base = nw.base;
+        a.r.new_norms = nw.norms;
+        a.r.old_ids = old.listids;  // (tables == 0: no codes; the one id array of the chunk counts is the list ids)
+        a.nlist = nlist;
+        a.old_off = old.listoff;
+        a.new_off = nw.listoff;
+        a.new_ids = nw.listids;
+        a.old_lrows = old.lrows;
+        a.old_lnorms = old.lnorms;
+        a.new_lrows = nw.lrows;
+        a.new_lnorms = nw.lnorms;
+        const unsigned chunks = static_cast<unsigned>(a.r.nchunks), row_wgs = static_cast<unsigned>((n0 + kNWave - 1) / kNWave);
+        hipLaunchKernelGGL(lsh_remove_mark_kernel, dim3(static_cast<unsigned>((m + kWG - 1) / kWG)), dim3(kWG), 0, st, a.r);
+        hipLaunchKernelGGL(lsh_remove_rank_kernel, dim3(1), dim3(kWG), 0, st, a.r);
+        if (n1 > 0) hipLaunchKernelGGL(lsh_remove_rows_kernel, dim3(row_wgs), dim3(kWG), 0, st, a.r);
+        hipLaunchKernelGGL(lsh_remove_chunk_count_kernel, dim3(chunks, 1), dim3(kWG), 0, st, a.r);
+        hipLaunchKernelGGL(lsh_remove_chunk_scan_kernel, dim3(1), dim3(kWG), 0, st, a.r);
+        if (n1 > 0) hipLaunchKernelGGL(ivf_remove_ids_kernel, dim3(chunks), dim3(kWG), 0, st, a);
+        hipLaunchKernelGGL(ivf_remove_offsets_kernel, dim3(static_cast<unsigned>((nlist + 1 + kNWave - 1) / kNWave)), dim3(kWG), 0, st, a);
+        if (n1 > 0 && !nw.alias) hipLaunchKernelGGL(ivf_remove_lrows_kernel, dim3(row_wgs), dim3(kWG), 0, st, a);
+        HG_HIP(hipGetLastError());
+        if (old.qrows && n1 > 0) HG_TRY(quantize_rows(idx, nw.base, n1, &nw.qrows, &nw.qmeta, st));  // (as add: one pass over the new base)
+        // ---- the int8 tile codes and the half copy over the moved list rows: made as for a fresh set of lists, by the
+        // handle's rejection mode (ensure_list_codes / ensure_list_half read the handle)
+        nw.to_handle(idx, n1);
+        installed = true;
+        HG_TRY(ensure_list_codes(idx, st));
+        HG_TRY(ensure_list_half(idx, st));
+        nw.of_handle(idx);
+        // ---- the one readback: gate, offsets, ids
+        int64_t gate[kLshRemoveGate];
+        h_off.resize(static_cast<size_t>(nlist) + 1);
+        h_ids.resize(static_cast<size_t>(n1));
+        HG_HIP(hipMemcpyAsync(gate, a.r.gate, sizeof(gate), hipMemcpyDeviceToHost, st));
+        HG_HIP(hipMemcpyAsync(h_off.data(), nw.listoff, sizeof(int64_t) * (nlist + 1), hipMemcpyDeviceToHost, st));
+        if (n1 > 0) HG_HIP(hipMemcpyAsync(h_ids.data(), nw.listids, sizeof(int32_t) * static_cast<size_t>(n1), hipMemcpyDeviceToHost, st));
+        HG_HIP(hipStreamSynchronize(st));
+        HG_REQUIRE(gate[2 * kRemoveMaxTables] == n1, HNSWGPU_EHIP, "the mask keeps %lld rows, not %lld", (long long)gate[2 * kRemoveMaxTables],
+                   (long long)n1);
+        HG_REQUIRE(gate[0] == n1 && h_off[nlist] == n1, HNSWGPU_EHIP, "the shrunken lists hold %lld rows, not %lld", (long long)gate[0], (long long)n1);
+        HG_REQUIRE(gate[kRemoveMaxTables] == n1, HNSWGPU_EHIP, "the compacted list ids hold %lld rows, not %lld",
+                   (long long)gate[kRemoveMaxTables], (long long)n1);
+        return 0;
+    };
+    int rc;
+    try {
+        rc = shrink();
+    } catch (const std::bad_alloc &) {
+        set_error("host allocation failed in hnswgpu_ivf_remove");
+        rc = HNSWGPU_ENOMEM;
+    }
+    if (rc != 0) {
+        (void)hipStreamSynchronize(st);  // (nothing of the chain is in flight when the staged arrays are freed)
+        if (installed) nw.of_handle(idx);  // (whatever the last step made is the staged set's)
+        old.to_handle(idx, n0);
+        nw.release();
+        return rc;
+    }
+    take_list_mirrors(idx, h_off, h_ids, n1);
+    old.release();  // (the first-search verdict of a mode-1 handle, ivf_calibrated / ivf_stream_off, stays: not measured again)
+    if (n_after) *n_after = n1;
     return call.close();
 }
 

@@ -469,6 +469,20 @@ class Index:
         self.n += len(rows)
         return np.arange(first, self.n, dtype=np.int32)
 
+    def ivf_remove(self, rows):
+        """hnswgpu_ivf_remove: the rows named by `rows` (row ids, any order, repeats count once) leave the base and the installed
+        lists; the kept rows are renumbered densely in their old order, every list keeps its kept members in their order.
+        Returns `kept`, the int64 array of the old row ids that remain, ascending: the row now numbered i was kept[i]."""
+        rows = np.ascontiguousarray(rows, np.int32).reshape(-1)
+        n_after = C.c_int64(-1)
+        check(lib().hnswgpu_ivf_remove(self._h, _p(rows), len(rows), C.byref(n_after)))
+        keep = np.ones(self.n, np.bool_)
+        keep[rows] = False
+        kept = np.flatnonzero(keep).astype(np.int64)
+        assert len(kept) == n_after.value, "hnswgpu_ivf_remove left %d rows, the id list %d" % (n_after.value, len(kept))
+        self.n = int(n_after.value)
+        return kept
+
     def set_ivf(self, centroids, list_off, list_ids):
         cen = _f32(centroids)
         off = np.ascontiguousarray(list_off, np.int64)

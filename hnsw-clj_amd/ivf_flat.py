@@ -3,7 +3,7 @@
 ``build_index(data, num_partitions=24, distance_fn=..., max_iterations=10)`` runs k-means++ /
 Lloyd on the device; ``search_knn(index, q, k, mode)`` / ``search_ivf_flat(index, q, k, mode=...,
 num_probes=...)`` scan the probed lists with the HIP scan kernel;
-``add_vectors(index, data)`` grows a built index; ``search_knn_filtered`` / ``search_batch_filtered`` (not in the reference, whose IVF index has no
+``add_vectors(index, data)`` grows a built index, ``remove_vectors(index, ids)`` shrinks it; ``search_knn_filtered`` / ``search_batch_filtered`` (not in the reference, whose IVF index has no
 FilterableIndex) scan only the rows of the probed lists that pass a predicate; ``search_batch_filtered_each`` takes one
 predicate per query.
 """
@@ -65,6 +65,28 @@ def add_vectors(index, data):
     if ids:
         index.index.ivf_add(rows)
         index.ids.extend(ids)
+    return index
+
+
+def remove_vectors(index, ids):
+    """The reference's IVFFlatIndex has no remove (it is an immutable record); what is restated is its list order
+    (ivf_flat.clj:137-211, "inverted lists in index order"): ``ids`` are the caller's ids, the form ``index.ids`` holds; their
+    vectors leave the base and their partitions, the kept members of a partition stay in their order (hnswgpu_ivf_remove), the
+    centroids stay, and ``index.ids`` follows.  An unknown id raises KeyError before the device is touched; an id of several
+    rows removes them all.  Empty ``ids`` does nothing.  Returns the index."""
+    ids = list(ids)
+    if not ids:
+        return index
+    rows_of = {}
+    for row, i in enumerate(index.ids):
+        rows_of.setdefault(i, []).append(row)
+    rows = []
+    for i in ids:
+        if i not in rows_of:
+            raise KeyError(i)
+        rows.extend(rows_of[i])
+    kept = index.index.ivf_remove(np.asarray(rows, np.int32))
+    index.ids = [index.ids[i] for i in kept]
     return index
 
 

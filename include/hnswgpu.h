@@ -242,6 +242,46 @@ int hnswgpu_ivf_build(hnswgpu_index *idx, int32_t nlist, int32_t max_iter, int64
  * Out of scope: a handle with both a graph and lists, hnswgpu_group_*, and sharded.ShardedIVF (rebuild those).
  * hnswgpu_hnsw_add still refuses a handle with lists. */
 int hnswgpu_ivf_add(hnswgpu_index *idx, const float *rows, int64_t m);
+/* Rows leave the inverted lists of a LIVE handle (the reference's IVFFlatIndex has no remove either; what is restated is
+ * again its list order, "inverted lists in index order", ivf_flat.clj:137-211).  The contract is that of hnswgpu_lsh_remove,
+ * on lists instead of tables.  `rows` is m row ids of the handle in host memory, in any order; an id named twice is removed
+ * once.  The kept rows are renumbered densely in their old order: the new id of a kept row r is the number of kept rows
+ * below r.  *n_after (may be NULL) gets the rows the handle holds afterwards.
+ *   - Centroids do not move.  Every list keeps its kept members in their order under their new ids; an emptied list stays,
+ *     with two equal offsets.
+ *   - After the call the handle holds, bit for bit, what hnswgpu_create(the kept rows in their old order) +
+ *     hnswgpu_set_rejection_test(same mode) + hnswgpu_set_ivf(same centroids, compacted lists) holds: base, norms, the
+ *     base-order int8 rows and their meta where the handle has them, list offsets and ids, rows and norms in list order,
+ *     their int8 and half-precision copies, the list-length bookkeeping, and what hnswgpu_get_ivf / hnswgpu_save export.
+ *     The first-search verdict of a mode-1 handle (hnswgpu_ivf_stream_state) is kept, not measured again.  A handle whose
+ *     lists are its base rows in place (identity list_ids) stays that way: the compacted ids are again the identity.
+ *     It is the permanent form of hnswgpu_ivf_search_filtered: a search after the removal finds the rows, under their new
+ *     ids, and the distance bits that the filtered search found before it under the mask of the kept rows.
+ *   - Everything happens on the device, in one chain on the handle's stream: only the m ids go up, rows and norms are
+ *     copied (not computed again), the int8 rows, the int8 tiles and the half copy are made again over the moved rows by
+ *     what makes them for fresh lists (their layout depends on position), and every entry's destination is a function of
+ *     the mask and the old arrays alone (prefix counts of kept entries), never of the order atomics arrive in.
+ *   - Failure-atomic, like hnswgpu_ivf_add: nothing is changed in place, every new array is staged under the handle's
+ *     lock with its streams quiesced, and the handle takes them over only after ONE readback -- the new offsets and ids
+ *     for the host mirrors, and three counts that must all equal n - (distinct ids): the rank scan's total, the last new
+ *     offset and the compacted list entries (HNSWGPU_EHIP otherwise).  On any failure the staged arrays are freed and the
+ *     handle is what it was.  Searches from other threads wait and see the old or the new index.  Peak memory: the old
+ *     plus the new arrays for the length of the call, as for add.
+ *   - Cost: one device copy of the kept rows in base and in list order plus their re-quantisation per CALL, whatever m
+ *     is -- remove rows in batches.  Measured on one MI355X (profiles/ivf_remove.txt: 31,173 x 768, 24 lists, mode 1):
+ *     1.31 / 1.10 / 1.26 ms for m = 1 / 1,024 / 8,192 against 2.05 / 2.00 / 1.60 ms for the rebuild over the kept rows
+ *     from host memory -- faster at every m measured, by less the more rows leave (0.64, 0.55, 0.79 of the rebuild); the
+ *     kernels are 0.14 ms of a call, the rest is allocating and freeing the staged arrays and the readback.
+ * Returns, checked in this order: -1 for a null handle (before m == 0 and before any HIP call), for m < 0, and for null
+ * rows with m > 0; 0 for m == 0 (nothing happens, *n_after = n, whatever the handle holds); -3 for a handle without lists,
+ * and for one that also holds an HNSW graph, a forest or LSH tables, and for a shard (hnswgpu_set_ivf_shard) -- those
+ * would keep the old numbering; the message names which; -1 for an id outside [0, n), checked on the host array before
+ * anything is enqueued.  The handle is untouched in every one of these cases.  Removing every row is legal: it leaves the
+ * empty handle with lists that hnswgpu_ivf_search answers with padding, and hnswgpu_ivf_add can grow it again.
+ * Out of scope: hnswgpu_group_*, sharded.ShardedIVF and shards (rebuild those); handles with both a graph and lists, and
+ * forests; removing rows from an HNSW graph; moving centroids or re-clustering after heavy removal.
+ * hnswgpu_lsh_remove still refuses a handle with lists. */
+int hnswgpu_ivf_remove(hnswgpu_index *idx, const int32_t *rows, int64_t m, int64_t *n_after);
 int hnswgpu_set_ivf(hnswgpu_index *idx, const float *centroids, int32_t nlist, const int64_t *list_off,
                     const int32_t *list_ids);
 int hnswgpu_get_ivf(const hnswgpu_index *idx, float *centroids, int64_t *list_off, int32_t *list_ids);
