@@ -386,3 +386,19 @@ JNIEXPORT jlong JNICALL Java_hnsw_gpu_Native_ivfRemove(JNIEnv *env, jclass c, jl
     if (rc != 0 && rc != HNSWGPU_ENOMEM) throw_last(env);
     return rc != 0 ? (jlong)rc : (jlong)n_after;
 }
+
+/* rows leave a live HNSW graph (hnswgpu_hnsw_remove): `rows` holds m row ids in any order, repeats count once; the kept rows are
+ * renumbered densely in their old order, a neighbour list that loses a member is selected again from the old graph.  Returns the
+ * rows the handle holds afterwards, or the negative error code (the exception is pending).  Unverified like the rest of this
+ * file: no JVM where the library is built and tested. */
+JNIEXPORT jlong JNICALL Java_hnsw_gpu_Native_hnswRemove(JNIEnv *env, jclass c, jlong h, jintArray rows, jlong m) {
+    if (!rows) return throw_iae(env, "hnswRemove: null array");
+    if (m < 0 || m > (jlong)(*env)->GetArrayLength(env, rows)) return throw_iae(env, "hnswRemove: m outside the array");
+    jint *pr = (*env)->GetIntArrayElements(env, rows, NULL);
+    int64_t n_after = -1;
+    int rc = pr ? hnswgpu_hnsw_remove((hnswgpu_index *)(intptr_t)h, (const int32_t *)pr, (int64_t)m, &n_after)
+                : HNSWGPU_ENOMEM; /* OutOfMemoryError is pending */
+    if (pr) (*env)->ReleaseIntArrayElements(env, rows, pr, JNI_ABORT);
+    if (rc != 0 && rc != HNSWGPU_ENOMEM) throw_last(env);
+    return rc != 0 ? (jlong)rc : (jlong)n_after;
+}

@@ -17,6 +17,7 @@
      (batch-distances index query-vec)                               ; simd-optimized/batch-cosine-distances
      (top-k-distances index query-vec k)                             ; simd-optimized/top-k-distances
      (add-vector! index new-data)                                    ; hnsw.api/add-vector!, insert-single on a live index
+     (remove-vectors! index ids)                                     ; ... and leave the graph again: hnswgpu_hnsw_remove
      (add-ivf-vectors! index new-data)                               ; the same for a live IVF-FLAT index: hnswgpu_ivf_add
      (remove-ivf-vectors! index ids)                                 ; ... and leave it: hnswgpu_ivf_remove
      (build-lsh-index data :metric :cosine)                          ; hnsw.ann.hash.hybrid-lsh/build-lsh-index: (Random. 42), 8 x 12 bits
@@ -161,6 +162,32 @@
         (with-open [arena (Arena/ofConfined)]
           (let [n-after (.allocate arena 8 8)]
             (check (.invokeWithArguments ^MethodHandle @h-ivfremove
+                                         [(:handle idx) (ints-of arena rows) (long (count rows)) n-after]))
+            (let [kept (vec (remove gone (:ids idx)))]
+              (assert (= (count kept) (.getAtIndex n-after L 0)))
+              (assoc idx :ids kept))))))))
+
+(def ^:private h-hnswremove (delay (fn-handle "hnswgpu_hnsw_remove" (FunctionDescriptor/of I (into-array [P P L P])))))
+
+(defn remove-vectors!
+  "The inverse of add-vector! for a live HNSW GpuIndex (the reference has no delete: pure_hnsw.clj:16 is a todo; the repair rule
+   is the engine's own, hnswgpu_hnsw_remove): the vectors with the given ids leave the base matrix and the graph, the kept rows are
+   renumbered densely in their old order, a neighbour list that loses no member stays as it is, and a list that loses one is
+   selected again -- as the index's builder prunes an over-full list -- from its kept members and the kept members of the lists of
+   the members that left.  No back edges are added, and the result depends on how a removal is split over calls.  An unknown id
+   throws before the device is touched.  Returns the index with the ids removed.  One call per batch is the efficient shape.
+   Unverified like the rest of this namespace: no JVM where the library is built."
+  [idx ids]
+  (let [gone (set ids)
+        known (set (:ids idx))]
+    (when-let [bad (first (remove known gone))]
+      (throw (ex-info "remove-vectors!: unknown id" {:id bad})))
+    (if (empty? gone)
+      idx
+      (let [rows (vec (keep-indexed (fn [i id] (when (gone id) i)) (:ids idx)))]
+        (with-open [arena (Arena/ofConfined)]
+          (let [n-after (.allocate arena 8 8)]
+            (check (.invokeWithArguments ^MethodHandle @h-hnswremove
                                          [(:handle idx) (ints-of arena rows) (long (count rows)) n-after]))
             (let [kept (vec (remove gone (:ids idx)))]
               (assert (= (count kept) (.getAtIndex n-after L 0)))

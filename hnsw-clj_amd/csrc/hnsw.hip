@@ -14,6 +14,8 @@
 
 #include "build_kernels.hpp"
 #include "engine.hpp"
+#include "hnsw_remove_kernels.hpp"  // the graph side of hnswgpu_hnsw_remove
+#include "lsh_remove_ids.hpp"       // the id check every removal shares
 #include "javarandom.hpp"
 #include "order_kernels.hpp"  // OrderArgs, for hnsw_launch_resources
 #include "parts_kernels.hpp"  // the item table and the counters of a forest launch (hnsw_parts_enqueue)
@@ -1478,6 +1480,19 @@ static int launch_heur(hnswgpu_index *idx, HeurArgs a, hipStream_t st) {
     return 0;
 }
 
+// d(u, c) over the tasks' candidate ranges (hnsw_remove_kernels.hpp): edge_dist_kernel's arithmetic and dispatch
+static int launch_remove_dist(hnswgpu_index *idx, const HnswRemoveArgs &a, hipStream_t st) {
+    if (a.ntasks <= 0) return 0;
+    const unsigned grid = static_cast<unsigned>((a.ntasks + kNWave - 1) / kNWave);
+    const bool l2 = idx->metric == METRIC_L2;
+#define CALL(N, R, L) \
+    hipLaunchKernelGGL((hnsw_remove_dist_kernel<N, R, L>), dim3(grid), dim3(kWG), 0, st, a, idx->d_base, idx->d_norms, idx->dim, idx->metric)
+    HG_DISPATCH(idx->nch, l2, CALL);
+#undef CALL
+    HG_HIP(hipGetLastError());
+    return 0;
+}
+
 // A pending reverse edge of graph.clj's builder: `id` wants into the FULL list of `target` on layer `lc`.
 struct PendingEdge {
     int32_t target, lc, id;
@@ -2289,6 +2304,250 @@ int hnswgpu_hnsw_add(hnswgpu_index *idx, const float *rows, int64_t m, int32_t e
         return rc;
     }
     free_staged(old);
+    return call.close();
+}
+
+// Rows leave a live graph (include/hnswgpu.h).  The reference has no delete (pure_hnsw.clj:16 is a todo); what is restated is the
+// list layout, the repair rule is this project's own: the kept rows are renumbered densely in their old order, a list that loses
+// no member keeps its members in their order, a list that loses one is selected again -- as the handle's builder prunes an
+// over-full list -- from its kept members and the kept members of the same-layer lists of the members that left, all read from
+// the graph as it stood when the call began.  One chain on the handle's stream (remove_kernels.hpp, hnsw_remove_kernels.hpp):
+// mark, rank, the kept base rows / norms to their ranks, levels and up_off, the list pass, the scan of the candidate counts (its
+// two totals are read to size the candidate arrays), gather, distances, sort, selection, scatter; the int8 rows are made again
+// over the moved rows.  Everything is staged; the handle takes the staged arrays over behind ONE readback: the gate's three
+// counts and the new graph for the host mirrors.  The traversal's rejection-test verdict (hnsw_cal_state) is reset, as free_graph
+// resets it wherever a graph is replaced: the next large launch measures the new graph.
+int hnswgpu_hnsw_remove(hnswgpu_index *idx, const int32_t *rows, int64_t m, int64_t *n_after) {
+    HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
+    HG_REQUIRE(m >= 0, HNSWGPU_EINVAL, "m must be >= 0");
+    HG_REQUIRE(rows || m == 0, HNSWGPU_EINVAL, "rows is null");
+    if (m == 0) {  // nothing to remove: nothing happens, whatever the handle holds
+        std::lock_guard<std::mutex> lk(idx->mu);
+        if (n_after) *n_after = idx->n;
+        return 0;
+    }
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_REQUIRE(idx->has_graph, HNSWGPU_ESTATE, "index has no graph (call hnswgpu_hnsw_build / hnswgpu_set_graph first)");
+    HG_REQUIRE(idx->nparts == 0, HNSWGPU_ESTATE,
+               "the index holds a forest of HNSW sub-graphs: its part tables would keep the old numbering of the rows");
+    HG_REQUIRE(idx->nlist == 0, HNSWGPU_ESTATE, "the index holds IVF lists: they would keep the old numbering of the rows");
+    HG_REQUIRE(idx->lsh_tables == 0, HNSWGPU_ESTATE, "the index holds LSH tables: they would keep the old numbering of the rows");
+    const int64_t n0 = idx->n;
+    int64_t distinct = 0, bad = -1;
+    try {
+        bad = lsh_remove_check_ids(rows, m, n0, &distinct);  // on the host array, before anything is enqueued
+    } catch (const std::bad_alloc &) {  // (its sorted copy of the ids)
+        set_error("host allocation failed");
+        return HNSWGPU_ENOMEM;
+    }
+    HG_REQUIRE(bad < 0, HNSWGPU_EINVAL, "rows[%lld] = %d is not a row of the index (n = %lld)", (long long)bad, rows[bad], (long long)n0);
+    const int64_t n1 = n0 - distinct;
+    HG_TRY(call.quiesce());
+    const int M = idx->M, M0 = idx->M0;
+    const int64_t ld = idx->ld, blocks0 = idx->up_blocks;
+    struct Staged {
+        float *base = nullptr, *norms = nullptr;
+        uint32_t *qrows = nullptr;
+        float4 *qmeta = nullptr;
+        int32_t *levels = nullptr, *l0 = nullptr, *upadj = nullptr;
+        int64_t *upoff = nullptr;
+        void release() {
+            void *ptrs[] = {base, norms, qrows, qmeta, levels, l0, upadj, upoff};
+            for (void *p : ptrs)
+                if (p) (void)hipFree(p);
+            *this = Staged();
+        }
+    } nw, old;
+    old.base = idx->d_base, old.norms = idx->d_norms, old.qrows = idx->d_qrows, old.qmeta = idx->d_qmeta;
+    old.levels = idx->d_levels, old.l0 = idx->d_l0, old.upadj = idx->d_upadj, old.upoff = idx->d_upoff;
+    std::vector<int32_t> h_levels, h_l0, h_upadj;
+    std::vector<int64_t> h_upoff;
+    int64_t blocks1 = 0;
+    int32_t entry1 = -1, top1 = 0;
+    auto shrink = [&]() -> int {
+        // what the host knows before the device does: the kept rows' levels summed (the staged upper layer's size and the
+        // gate's second count) and where a kept entry point lands
+        std::vector<uint8_t> gone(static_cast<size_t>(n0), 0);
+        for (int64_t i = 0; i < m; i++) gone[rows[i]] = 1;
+        int64_t below_entry = 0;
+        for (int64_t r = 0; r < n0; r++) {
+            if (gone[r]) continue;
+            blocks1 += idx->h_levels[r];
+            if (r < idx->entry) below_entry++;
+        }
+        const bool entry_kept = idx->entry >= 0 && idx->entry < n0 && !gone[idx->entry];
+        const size_t rows1 = static_cast<size_t>(std::max<int64_t>(n1, 1)), ub1 = static_cast<size_t>(std::max<int64_t>(blocks1, 1));
+        if (n1 > 0) {
+            HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.base), sizeof(float) * rows1 * ld));
+            HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.norms), sizeof(float) * rows1));
+        }
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.levels), sizeof(int32_t) * rows1));
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.l0), sizeof(int32_t) * rows1 * M0));
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.upoff), sizeof(int64_t) * (rows1 + 1)));
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.upadj), sizeof(int32_t) * ub1 * M));
+        HG_HIP(hipMemsetAsync(nw.l0, 0xff, sizeof(int32_t) * rows1 * M0, st));
+        HG_HIP(hipMemsetAsync(nw.upadj, 0xff, sizeof(int32_t) * ub1 * M, st));
+        // scratch, 16-byte sections: [gate | keep | cnt] zeroed, [owner] -1, then word_rank, the call's ids, the task tables
+        HnswRemoveArgs a;
+        memset(&a, 0, sizeof(a));
+        a.r.n0 = n0;
+        a.r.n1 = n1;
+        a.r.m = m;
+        a.r.W = (n0 + 31) / 32;
+        a.r.ld = ld;
+        a.M = M;
+        a.M0 = M0;
+        a.blocks0 = blocks0;
+        a.blocks1 = blocks1;
+        a.nlists = n0 + blocks0;
+        auto sect = [](size_t bytes) { return (bytes + 15) / 16 * 16; };
+        const size_t o_keep = sect(sizeof(int64_t) * kLshRemoveGate), o_cnt = o_keep + sect(sizeof(uint32_t) * a.r.W),
+                     o_owner = o_cnt + sect(sizeof(uint32_t) * a.nlists), o_rank = o_owner + sect(sizeof(int32_t) * blocks0),
+                     o_ids = o_rank + sect(sizeof(uint32_t) * a.r.W), o_tlist = o_ids + sect(sizeof(int32_t) * m),
+                     o_tm = o_tlist + sect(sizeof(int32_t) * a.nlists), o_toff = o_tm + sect(sizeof(int32_t) * a.nlists),
+                     bytes = o_toff + sect(sizeof(int64_t) * (a.nlists + 1));
+        HG_TRY(idx->s_misc.ensure(bytes));
+        char *s = idx->s_misc.as<char>();
+        HG_HIP(hipMemsetAsync(s, 0, o_owner, st));
+        if (blocks0 > 0) HG_HIP(hipMemsetAsync(s + o_owner, 0xff, sizeof(int32_t) * blocks0, st));
+        HG_HIP(hipMemcpyAsync(s + o_ids, rows, sizeof(int32_t) * static_cast<size_t>(m), hipMemcpyHostToDevice, st));
+        a.r.gate = reinterpret_cast<int64_t *>(s);
+        a.r.keep = reinterpret_cast<uint32_t *>(s + o_keep);
+        a.cnt = reinterpret_cast<uint32_t *>(s + o_cnt);
+        a.owner = reinterpret_cast<int32_t *>(s + o_owner);
+        a.r.word_rank = reinterpret_cast<uint32_t *>(s + o_rank);
+        a.r.rows = reinterpret_cast<const int32_t *>(s + o_ids);
+        a.task_list = reinterpret_cast<int32_t *>(s + o_tlist);
+        a.task_m = reinterpret_cast<int32_t *>(s + o_tm);
+        a.task_off = reinterpret_cast<int64_t *>(s + o_toff);
+        a.r.old_base = old.base;
+        a.r.old_norms = old.norms;
+        a.r.new_base = nw.base;
+        a.r.new_norms = nw.norms;
+        a.old_levels = old.levels;
+        a.old_l0 = old.l0;
+        a.old_upadj = old.upadj;
+        a.old_upoff = old.upoff;
+        a.new_levels = nw.levels;
+        a.new_l0 = nw.l0;
+        a.new_upadj = nw.upadj;
+        a.new_upoff = nw.upoff;
+        const unsigned row_wgs = static_cast<unsigned>((n0 + kNWave - 1) / kNWave), list_wgs = static_cast<unsigned>((a.nlists + kNWave - 1) / kNWave);
+        hipLaunchKernelGGL(lsh_remove_mark_kernel, dim3(static_cast<unsigned>((m + kWG - 1) / kWG)), dim3(kWG), 0, st, a.r);
+        hipLaunchKernelGGL(lsh_remove_rank_kernel, dim3(1), dim3(kWG), 0, st, a.r);
+        if (n1 > 0) hipLaunchKernelGGL(lsh_remove_rows_kernel, dim3(row_wgs), dim3(kWG), 0, st, a.r);
+        hipLaunchKernelGGL(hnsw_remove_levels_kernel, dim3(1), dim3(kWG), 0, st, a);
+        hipLaunchKernelGGL(hnsw_remove_owner_kernel, dim3(static_cast<unsigned>((n0 + kWG - 1) / kWG)), dim3(kWG), 0, st, a);
+        hipLaunchKernelGGL(hnsw_remove_lists_kernel, dim3(list_wgs), dim3(kWG), 0, st, a);
+        hipLaunchKernelGGL(hnsw_remove_scan_kernel, dim3(1), dim3(kWG), 0, st, a);
+        HG_HIP(hipGetLastError());
+        if (old.qrows && n1 > 0) HG_TRY(quantize_rows(idx, nw.base, n1, &nw.qrows, &nw.qmeta, st));  // (as add: one pass over the new base)
+        // the two totals of the scan: what the candidate arrays are sized by (no cap to overflow)
+        int64_t totals[2] = {0, 0};
+        HG_HIP(hipMemcpyAsync(totals, a.r.gate + kHnswRemoveGateCand, sizeof(totals), hipMemcpyDeviceToHost, st));
+        HG_HIP(hipStreamSynchronize(st));
+        a.ncand = totals[0];
+        a.ntasks = totals[1];
+        HG_REQUIRE(a.ntasks >= 0 && a.ntasks <= a.nlists && a.ncand >= a.ntasks &&
+                       a.ncand <= a.ntasks * static_cast<int64_t>(kSelMaxCand) && a.ntasks < 2147483647LL,
+                   HNSWGPU_EHIP, "the candidate scan counts %lld candidates of %lld lists", (long long)a.ncand, (long long)a.ntasks);
+        if (a.ntasks > 0) {
+            const bool heuristic = (idx->build_flags & HNSWGPU_BUILD_HEURISTIC) != 0;
+            HG_TRY(idx->s_ids.ensure(sizeof(int32_t) * static_cast<size_t>(a.ncand)));
+            HG_TRY(idx->s_outd.ensure(sizeof(float) * static_cast<size_t>(a.ncand)));
+            a.cand_id = idx->s_ids.as<int32_t>();
+            a.cand_d = idx->s_outd.as<float>();
+            const unsigned task_wgs = static_cast<unsigned>((a.ntasks + kNWave - 1) / kNWave);
+            hipLaunchKernelGGL(hnsw_remove_gather_kernel, dim3(task_wgs), dim3(kWG), 0, st, a);
+            HG_HIP(hipGetLastError());
+            HG_TRY(launch_remove_dist(idx, a, st));  // (the handle still holds the old rows: the candidates are old ids)
+            hipLaunchKernelGGL(hnsw_remove_sort_kernel, dim3(static_cast<unsigned>(a.ntasks)), dim3(kWG), 0, st, a);
+            HG_HIP(hipGetLastError());
+            if (heuristic) {
+                const size_t slots = static_cast<size_t>(a.ntasks) * M0;
+                const size_t o_d = sect(sizeof(int32_t) * slots), o_c = o_d + sect(sizeof(float) * slots);
+                HG_TRY(idx->s_misc2.ensure(o_c + sect(sizeof(int32_t) * static_cast<size_t>(a.ntasks))));
+                char *h = idx->s_misc2.as<char>();
+                HeurArgs ha;
+                memset(&ha, 0, sizeof(ha));
+                ha.ntasks = static_cast<int32_t>(a.ntasks);
+                ha.off = a.task_off;
+                ha.cand_id = a.cand_id;
+                ha.cand_d = a.cand_d;
+                ha.m = a.task_m;
+                ha.extend = 0;
+                ha.out_stride = M0;
+                ha.out_id = reinterpret_cast<int32_t *>(h);
+                ha.out_d = reinterpret_cast<float *>(h + o_d);
+                ha.out_cnt = reinterpret_cast<int32_t *>(h + o_c);
+                HG_TRY(launch_heur(idx, ha, st));
+                a.sel = ha.out_id;
+            }
+            hipLaunchKernelGGL(hnsw_remove_scatter_kernel, dim3(task_wgs), dim3(kWG), 0, st, a);
+            HG_HIP(hipGetLastError());
+        }
+        // ---- the one readback: gate, levels, up_off, both adjacency arrays
+        int64_t gate[kLshRemoveGate];
+        h_levels.resize(static_cast<size_t>(n1));
+        h_l0.resize(static_cast<size_t>(n1) * M0);
+        h_upoff.assign(static_cast<size_t>(n1) + 1, 0);
+        h_upadj.resize(static_cast<size_t>(blocks1) * M);
+        HG_HIP(hipMemcpyAsync(gate, a.r.gate, sizeof(gate), hipMemcpyDeviceToHost, st));
+        HG_HIP(hipMemcpyAsync(h_upoff.data(), nw.upoff, sizeof(int64_t) * (n1 + 1), hipMemcpyDeviceToHost, st));
+        if (n1 > 0) {
+            HG_HIP(hipMemcpyAsync(h_levels.data(), nw.levels, sizeof(int32_t) * n1, hipMemcpyDeviceToHost, st));
+            HG_HIP(hipMemcpyAsync(h_l0.data(), nw.l0, sizeof(int32_t) * n1 * M0, hipMemcpyDeviceToHost, st));
+        }
+        if (blocks1 > 0) HG_HIP(hipMemcpyAsync(h_upadj.data(), nw.upadj, sizeof(int32_t) * blocks1 * M, hipMemcpyDeviceToHost, st));
+        HG_HIP(hipStreamSynchronize(st));
+        HG_REQUIRE(gate[2 * kRemoveMaxTables] == n1, HNSWGPU_EHIP, "the mask keeps %lld rows, not %lld", (long long)gate[2 * kRemoveMaxTables],
+                   (long long)n1);
+        HG_REQUIRE(gate[kHnswRemoveGateOff] == blocks1 && h_upoff[n1] == blocks1, HNSWGPU_EHIP,
+                   "the shrunken graph holds %lld upper-layer lists, not %lld", (long long)gate[kHnswRemoveGateOff], (long long)blocks1);
+        HG_REQUIRE(gate[kHnswRemoveGateRows] == n1, HNSWGPU_EHIP, "the list pass moved %lld layer-0 lists, not %lld",
+                   (long long)gate[kHnswRemoveGateRows], (long long)n1);
+        // the entry point, from the mirrors: kept -> its new id; gone -> the kept row of the highest level, the lowest id among equals
+        if (n1 == 0) {
+            entry1 = -1, top1 = 0;
+        } else if (entry_kept) {
+            entry1 = static_cast<int32_t>(below_entry), top1 = idx->max_level;
+        } else {
+            entry1 = 0;
+            for (int64_t r = 1; r < n1; r++)
+                if (h_levels[r] > h_levels[entry1]) entry1 = static_cast<int32_t>(r);
+            top1 = h_levels[entry1];
+        }
+        return 0;
+    };
+    int rc;
+    try {
+        rc = shrink();
+    } catch (const std::bad_alloc &) {
+        set_error("host allocation failed in hnswgpu_hnsw_remove");
+        rc = HNSWGPU_ENOMEM;
+    }
+    if (rc != 0) {
+        (void)hipStreamSynchronize(st);  // (nothing of the chain is in flight when the staged arrays are freed)
+        nw.release();
+        return rc;
+    }
+    idx->d_base = nw.base, idx->d_norms = nw.norms, idx->d_qrows = nw.qrows, idx->d_qmeta = nw.qmeta;
+    idx->d_levels = nw.levels, idx->d_l0 = nw.l0, idx->d_upadj = nw.upadj, idx->d_upoff = nw.upoff;
+    idx->n = n1;
+    idx->up_blocks = blocks1;
+    idx->h_levels.swap(h_levels);
+    idx->h_l0.swap(h_l0);
+    idx->h_upoff.swap(h_upoff);
+    idx->h_upadj.swap(h_upadj);
+    idx->entry = entry1;
+    idx->max_level = top1;
+    idx->graph_gen++;
+    idx->hnsw_cal_state = 0;  // as free_graph: the shrunken graph is measured afresh
+    idx->hnsw_rej_off = false;
+    old.release();
+    if (n_after) *n_after = n1;
     return call.close();
 }
 

@@ -413,6 +413,21 @@ class Index:
         self.n += len(rows)
         return np.arange(first, self.n, dtype=np.int32)
 
+    def hnsw_remove(self, rows):
+        """hnswgpu_hnsw_remove: the rows named by `rows` (row ids, any order, repeats count once) leave the base and the installed
+        graph; the kept rows are renumbered densely in their old order, a list that loses no member keeps its members, a list that
+        loses one is selected again from the old graph (include/hnswgpu.h).  Returns `kept`, the int64 array of the old row ids
+        that remain, ascending: the row now numbered i was kept[i]."""
+        rows = np.ascontiguousarray(rows, np.int32).reshape(-1)
+        n_after = C.c_int64(-1)
+        check(lib().hnswgpu_hnsw_remove(self._h, _p(rows), len(rows), C.byref(n_after)))
+        keep = np.ones(self.n, np.bool_)
+        keep[rows] = False
+        kept = np.flatnonzero(keep).astype(np.int64)
+        assert len(kept) == n_after.value, "hnswgpu_hnsw_remove left %d rows, the id list %d" % (n_after.value, len(kept))
+        self.n = int(n_after.value)
+        return kept
+
     def get_graph(self):
         M, M0, ent, mx = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
         blocks = C.c_int64()

@@ -90,6 +90,29 @@ def build_index(data, M=16, ef_construction=200, distance_fn=cosine_distance_ult
     return UltraGraph(idx, ids, M, ef_construction, distance_fn)
 
 
+def remove_vectors(graph, ids):
+    """The reference has no delete (pure_hnsw.clj:16 is a todo); the rule is the engine's own (hnswgpu_hnsw_remove): ``ids`` are
+    the caller's ids, the form ``graph.ids`` holds; their vectors leave the base and the graph, a neighbour list that loses a
+    member is selected again from its kept members and those of the members that left, and ``graph.ids`` follows.  An unknown
+    id raises KeyError before the device is touched; an id of several rows removes them all.  Empty ``ids`` does nothing.
+    Returns the graph."""
+    ids = list(ids)
+    if not ids:
+        return graph
+    rows_of = {}
+    for row, i in enumerate(graph.ids):
+        rows_of.setdefault(i, []).append(row)
+    rows = []
+    for i in ids:
+        if i not in rows_of:
+            raise KeyError(i)
+        rows.extend(rows_of[i])
+    kept = graph.index.hnsw_remove(np.asarray(rows, np.int32))
+    graph.ids = [graph.ids[i] for i in kept]
+    graph.__dict__.pop("_route", None)       # (routed_to_exact_scan's measurements were of the graph that was)
+    return graph
+
+
 def _format(graph, ids_row, d_row):
     return [{"id": graph.ids[i], "distance": float(d)} for i, d in zip(ids_row, d_row) if i >= 0]
 

@@ -143,6 +143,59 @@ int hnswgpu_hnsw_build_ex(hnswgpu_index *idx, int32_t M, int32_t ef_construction
  * wait); IVF lists must be built / installed AFTER the rows they cover have been added (a handle that holds lists and
  * no graph grows through hnswgpu_ivf_add). */
 int hnswgpu_hnsw_add(hnswgpu_index *idx, const float *rows, int64_t m, int32_t ef_construction, int64_t seed);
+/* Rows leave a LIVE graph.  The reference has no delete (pure_hnsw.clj:16 is a todo): what is restated is the list layout;
+ * the repair rule is this project's own, and tests/hnsw_remove_model.py is its one specification.  `rows` is m row ids of
+ * the handle in host memory, in any order; an id named twice is removed once.  The kept rows are renumbered densely in their
+ * old order: the new id of a kept row r is the number of kept rows below r.  *n_after (may be NULL) gets the rows the handle
+ * holds afterwards.
+ *   - Base rows, norms and the base-order int8 rows with their meta (where the handle has them) are, bit for bit, what
+ *     hnswgpu_create(the kept rows in their old order) + hnswgpu_set_rejection_test(same mode) holds: rows and norms are
+ *     copied, the int8 rows made again over the moved rows.
+ *   - The graph: the kept rows' levels in order, up_off their prefix sum; M, M0 and the builder flags stay.  Every layer's
+ *     list of a kept node that loses no member keeps its members in their order under their new ids, -1 padded.
+ *   - A list that loses at least one member is selected again from the OLD graph alone -- the adjacency as it stood when
+ *     the call began; all lists are repaired from it at once, never from another list's repaired state.  For node u on
+ *     layer lc (width w = M0 on layer 0, M above): the candidates are u's kept old neighbours joined with the kept members
+ *     of the layer-lc lists of u's removed neighbours, without u, each once (one hop through what left, as FreshDiskANN's
+ *     delete consolidation: at most w * w <= 4096 ids); d(u, c) by the traversal's arithmetic on the stored norms;
+ *     ascending by (distance, id); then what the handle's builder does to an over-full list: with
+ *     HNSWGPU_BUILD_HEURISTIC get-neighbors-heuristic without extend-candidates (prune-connections, graph.clj:208-232),
+ *     otherwise -- a graph installed by hnswgpu_set_graph included -- the first min(w, C).  The list is written in
+ *     selection order under the new ids, -1 padded; a list whose candidates are all gone becomes empty, which is legal.
+ *   - What a repair does NOT do: HNSWGPU_BUILD_SYMMETRIC is not applied -- a repair changes only the list it repairs and
+ *     adds no back edge; nothing deeper than one hop is looked at; badly connected nodes are not inserted again.
+ *   - The result DEPENDS on how a removal is split over calls: each call repairs through its own removed rows only, so
+ *     two calls give the rule applied twice, not the rule applied to the union.  (hnswgpu_ivf_remove and
+ *     hnswgpu_lsh_remove are the opposite: their results do not depend on the split.)
+ *   - The entry point: kept -> its new id, max_level unchanged; gone -> the kept row of the highest level, the lowest old
+ *     id among equals, whose level becomes max_level.  No row left: entry -1, max_level 0, and the handle still has its
+ *     (empty) graph with M / M0 / builder flags: searches answer with padding and hnswgpu_hnsw_add grows it again.
+ *   - The per-graph verdict of the mode-1 rejection test (hnswgpu_hnsw_rejection_state) is RESET, as wherever a graph is
+ *     replaced: the next large launch measures the shrunken graph.
+ *   - Everything happens on the device, in one chain on the handle's stream (hnsw_remove_kernels.hpp): only the m ids go
+ *     up, and no destination is decided by the order atomics arrive in.  Between the list pass and the gather the host
+ *     reads two totals (candidates, lists to repair) to size the candidate arrays -- there is no cap to overflow.
+ *   - Failure-atomic, like hnswgpu_hnsw_add: nothing is changed in place, every new array is staged under the handle's
+ *     lock with its streams quiesced, and the handle takes them over only after ONE readback -- the new graph for the host
+ *     mirrors, and three counts: the rank scan's total must be n - (distinct ids), the new up_off[n_after] must be the
+ *     kept rows' levels summed on the host, and the list pass must have seen n_after kept rows (HNSWGPU_EHIP otherwise).
+ *     On any failure the staged arrays are freed and the handle is what it was.  Searches from other threads wait and see
+ *     the old or the new index.
+ *   - Cost and quality, measured on one MI355X (profiles/hnsw_remove.txt: 31,173 x 768 clustered-normalised, heuristic
+ *     graph, M 16, ef_construction 200): removing m = 1 / 1,024 / 8,192
+ *     scattered rows takes 2.09 / 3.52 / 6.34 ms (host clock around the call, median of five) against 110 / 111 / 115 ms for
+ *     hnswgpu_create + hnswgpu_hnsw_build_ex over the kept rows from host memory -- 0.019 / 0.032 / 0.055 of the rebuild.
+ *     recall@10 of 1,000 held-out queries against the exact neighbours among the kept rows, repaired / merely compacted /
+ *     freshly built: after 10 % of the rows left 0.978 / 0.980 / 0.987 at ef 640 and 0.604 / 0.616 / 0.617 at ef 100 (within
+ *     noise of each other); after 40 % left 0.993 / 0.972 / 0.998 at ef 640 and 0.669 / 0.559 / 0.727 at ef 100.  The gap to
+ *     the fresh build is the limit of a one-hop repair without back edges.
+ * Returns, checked in this order: -1 for a null handle (before m == 0 and before any HIP call), for m < 0, and for null
+ * rows with m > 0; 0 for m == 0 (nothing happens, *n_after = n, whatever the handle holds); -3 for a handle without a
+ * graph, for a forest, and for one that also holds IVF lists or LSH tables -- the message names which; -1 for an id outside
+ * [0, n), checked on the host array before anything is enqueued.  The handle is untouched in every one of these cases.
+ * Out of scope: forests, hnswgpu_group_* and sharded.py; handles that hold a graph together with lists or tables; restoring
+ * symmetry after a repair; repair deeper than one hop; reinserting badly connected nodes; tombstones. */
+int hnswgpu_hnsw_remove(hnswgpu_index *idx, const int32_t *rows, int64_t m, int64_t *n_after);
 int hnswgpu_graph_sizes(const hnswgpu_index *idx, int32_t *M, int32_t *M0, int64_t *up_blocks, int32_t *entry,
                         int32_t *max_level);
 int hnswgpu_get_graph(const hnswgpu_index *idx, int32_t *levels, int32_t *l0_adj, int64_t *up_off,
@@ -175,8 +228,8 @@ int hnswgpu_hnsw_search_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, in
  *   stats (optional): [nq][nprobe][2].  All items run in ONE traversal launch (+ the tie repeat pass, per item); the _dev
  *   entry only enqueues on `stream`; the host entry stages one caller's batch (no call combining).
  * On a handle that holds a forest: hnswgpu_get_graph works; hnswgpu_graph_sizes reports entry = -1 and the largest
- *   max_level; hnswgpu_info has_graph = 1; hnswgpu_hnsw_search*, the filtered searches, hnswgpu_hnsw_add and hnswgpu_save
- *   return HNSWGPU_ESTATE; hnswgpu_set_graph / hnswgpu_hnsw_build* replace the forest with a plain graph, and the other way
+ *   max_level; hnswgpu_info has_graph = 1; hnswgpu_hnsw_search*, the filtered searches, hnswgpu_hnsw_add, hnswgpu_hnsw_remove and
+ *   hnswgpu_save return HNSWGPU_ESTATE; hnswgpu_set_graph / hnswgpu_hnsw_build* replace the forest with a plain graph, and the other way
  *   round.
  * Out of scope: the several-CU kernel for forest launches (the single-query latency of the hybrid indexes: a handful of items
  *   run one workgroup each); save / load, add, filtered search and groups on a forest; a device-side forest builder. */
@@ -279,7 +332,7 @@ int hnswgpu_ivf_add(hnswgpu_index *idx, const float *rows, int64_t m);
  * anything is enqueued.  The handle is untouched in every one of these cases.  Removing every row is legal: it leaves the
  * empty handle with lists that hnswgpu_ivf_search answers with padding, and hnswgpu_ivf_add can grow it again.
  * Out of scope: hnswgpu_group_*, sharded.ShardedIVF and shards (rebuild those); handles with both a graph and lists, and
- * forests; removing rows from an HNSW graph; moving centroids or re-clustering after heavy removal.
+ * forests (a plain graph alone shrinks through hnswgpu_hnsw_remove); moving centroids or re-clustering after heavy removal.
  * hnswgpu_lsh_remove still refuses a handle with lists. */
 int hnswgpu_ivf_remove(hnswgpu_index *idx, const int32_t *rows, int64_t m, int64_t *n_after);
 int hnswgpu_set_ivf(hnswgpu_index *idx, const float *centroids, int32_t nlist, const int64_t *list_off,
