@@ -387,6 +387,23 @@ JNIEXPORT jlong JNICALL Java_hnsw_gpu_Native_ivfRemove(JNIEnv *env, jclass c, jl
     return rc != 0 ? (jlong)rc : (jlong)n_after;
 }
 
+/* rows of a live IVF-FLAT index take new values (hnswgpu_ivf_update): `ids` holds m row ids in any order, none named twice; `rows`
+ * holds m x dim floats, row ids[i] takes rows[i]; n, the ids and the centroids stay.  Returns 0, or the negative error code (the
+ * exception is pending).  Unverified like the rest of this file: no JVM where the library is built and tested. */
+JNIEXPORT jint JNICALL Java_hnsw_gpu_Native_ivfUpdate(JNIEnv *env, jclass c, jlong h, jintArray ids, jfloatArray rows, jlong m, jint dim) {
+    if (!ids || !rows) return throw_iae(env, "ivfUpdate: null array");
+    if (m < 0 || m > (jlong)(*env)->GetArrayLength(env, ids)) return throw_iae(env, "ivfUpdate: m outside the id array");
+    if (dim < 1 || m > (jlong)(*env)->GetArrayLength(env, rows) / dim) return throw_iae(env, "ivfUpdate: fewer than m x dim floats");
+    jint *pi = (*env)->GetIntArrayElements(env, ids, NULL);
+    jfloat *pr = pi ? (*env)->GetFloatArrayElements(env, rows, NULL) : NULL;
+    int rc = pi && pr ? hnswgpu_ivf_update((hnswgpu_index *)(intptr_t)h, (const int32_t *)pi, (const float *)pr, (int64_t)m)
+                      : HNSWGPU_ENOMEM; /* OutOfMemoryError is pending */
+    if (pr) (*env)->ReleaseFloatArrayElements(env, rows, pr, JNI_ABORT);
+    if (pi) (*env)->ReleaseIntArrayElements(env, ids, pi, JNI_ABORT);
+    if (rc != 0 && rc != HNSWGPU_ENOMEM) throw_last(env);
+    return rc;
+}
+
 /* rows leave a live HNSW graph (hnswgpu_hnsw_remove): `rows` holds m row ids in any order, repeats count once; the kept rows are
  * renumbered densely in their old order, a neighbour list that loses a member is selected again from the old graph.  Returns the
  * rows the handle holds afterwards, or the negative error code (the exception is pending).  Unverified like the rest of this

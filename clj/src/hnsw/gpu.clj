@@ -20,6 +20,7 @@
      (remove-vectors! index ids)                                     ; ... and leave the graph again: hnswgpu_hnsw_remove
      (add-ivf-vectors! index new-data)                               ; the same for a live IVF-FLAT index: hnswgpu_ivf_add
      (remove-ivf-vectors! index ids)                                 ; ... and leave it: hnswgpu_ivf_remove
+     (update-ivf-vectors! index new-data)                            ; ... and take new values under their ids: hnswgpu_ivf_update
      (build-lsh-index data :metric :cosine)                          ; hnsw.ann.hash.hybrid-lsh/build-lsh-index: (Random. 42), 8 x 12 bits
      (add-lsh-vectors! index new-data)                               ; rows join a live hybrid-LSH index: hnswgpu_lsh_add
      (remove-lsh-vectors! index ids)                                 ; ... and leave it: hnswgpu_lsh_remove
@@ -166,6 +167,31 @@
             (let [kept (vec (remove gone (:ids idx)))]
               (assert (= (count kept) (.getAtIndex n-after L 0)))
               (assoc idx :ids kept))))))))
+
+(def ^:private h-ivfupdate (delay (fn-handle "hnswgpu_ivf_update" (FunctionDescriptor/of I (into-array [P P P L])))))
+
+(defn update-ivf-vectors!
+  "\"Update existing vectors\" (the open item of the reference's to-do list; its IVFFlatIndex is an immutable record) for a live
+   IVF-FLAT GpuIndex: new-data is a seq of [id ^doubles vector]; the vector stored under each id takes the new values and moves to
+   its nearest partition if that is another one (ivf_flat.clj:79-90) -- behind the members that remain there --, and keeps its id;
+   a vector whose partition stays keeps its place in it; the centroids stay (hnswgpu_ivf_update).  An unknown id, an id that names
+   several rows and an id given twice throw before the device is touched.  Returns the index (its ids are unchanged).  One call
+   per batch is the efficient shape: a call copies the rows once, whatever it updates.  Unverified like the rest of this
+   namespace: no JVM where the library is built."
+  [idx new-data]
+  (let [rows-of (reduce (fn [m [i id]] (update m id (fnil conj []) i)) {} (map-indexed vector (:ids idx)))
+        ids (mapv first new-data)]
+    (doseq [id ids]
+      (when-not (contains? rows-of id) (throw (ex-info "update-ivf-vectors!: unknown id" {:id id})))
+      (when (> (count (rows-of id)) 1) (throw (ex-info "update-ivf-vectors!: the id names several rows" {:id id}))))
+    (when-not (or (empty? ids) (apply distinct? ids))
+      (throw (ex-info "update-ivf-vectors!: an id is given twice" {})))
+    (when (seq ids)
+      (with-open [arena (Arena/ofConfined)]
+        (check (.invokeWithArguments ^MethodHandle @h-ivfupdate
+                                     [(:handle idx) (ints-of arena (mapv (comp first rows-of) ids))
+                                      (floats-of arena (mapv second new-data) (:dim idx)) (long (count ids))]))))
+    idx))
 
 (def ^:private h-hnswremove (delay (fn-handle "hnswgpu_hnsw_remove" (FunctionDescriptor/of I (into-array [P P L P])))))
 

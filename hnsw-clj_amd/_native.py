@@ -65,6 +65,7 @@ _SIGS = {
     "hnswgpu_ivf_build": ["p", "i32", "i32", "i64"],
     "hnswgpu_ivf_add": ["p", "p", "i64"],
     "hnswgpu_ivf_remove": ["p", "p", "i64", "p"],
+    "hnswgpu_ivf_update": ["p", "p", "p", "i64"],
     "hnswgpu_set_ivf": ["p", "p", "i32", "p", "p"],
     "hnswgpu_get_ivf": ["p", "p", "p", "p"],
     "hnswgpu_kmeans_assign": ["p", "p", "i32", "p", "p"],

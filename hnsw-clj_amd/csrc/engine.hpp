@@ -74,7 +74,7 @@ struct DevBuf {
     }
 };
 
-enum { PROF_IVF_SCAN = 0, PROF_HNSW = 1, PROF_ASSIGN = 2, PROF_N = 3 };
+enum { PROF_IVF_SCAN = 0, PROF_HNSW = 1, PROF_ASSIGN = 2, PROF_UPDATE = 3, PROF_N = 4 };  // (PROF_UPDATE: the device chain of hnswgpu_ivf_update)
 
 // The form of a filtered call's allow-mask (include/hnswgpu.h), W = (n + 31) / 32 words: one mask shared by the call's queries,
 // or [nq][W], one per query
@@ -245,8 +245,8 @@ struct hnswgpu_index {
     // profiling
     bool prof = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev[hg::PROF_N];
-    double prof_ms[hg::PROF_N] = {0, 0, 0};
-    int64_t prof_cnt[hg::PROF_N] = {0, 0, 0};
+    double prof_ms[hg::PROF_N] = {0, 0, 0, 0};
+    int64_t prof_cnt[hg::PROF_N] = {0, 0, 0, 0};
 };
 
 namespace hg {

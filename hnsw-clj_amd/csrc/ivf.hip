@@ -10,6 +10,8 @@
 #include "stream_kernels.hpp"
 #include "ivf_add_kernels.hpp"
 #include "ivf_remove_kernels.hpp"
+#include "ivf_update_kernels.hpp"
+#include "ivf_update_ids.hpp"
 #include "lsh_remove_ids.hpp"
 #include "javarandom.hpp"
 
@@ -2316,6 +2318,234 @@ int hnswgpu_ivf_remove(hnswgpu_index *idx, const int32_t *rows, int64_t m, int64
     take_list_mirrors(idx, h_off, h_ids, n1);
     old.release();  // (the first-search verdict of a mode-1 handle, ivf_calibrated / ivf_stream_off, stays: not measured again)
     if (n_after) *n_after = n1;
+    return call.close();
+}
+
+// Rows of a live handle take new values under their ids (include/hnswgpu.h).  The reference's IVFFlatIndex is an immutable record
+// and "Update existing vectors" an open item of its to-do list; what is restated is its assignment rule (ivf_flat.clj:79-90) and
+// its list order: the updated handle holds what hnswgpu_create(the base with the new values) + hnswgpu_set_ivf(same centroids,
+// the lists of tests/ivf_update_model.py) holds.  One chain on the handle's stream (ivf_update_kernels.hpp): the call's rows into
+// a staging matrix in slot order (slot s = the s-th smallest id, ivf_update_ids.hpp), their norms (launch_norms) and nearest
+// lists (the GEMV-order scan), the staged base = the old one with the m rows scattered in, one pass over the old list positions
+// (every slot's present list, the movers' bits, leaves and joins per list), the new offsets, the mask's rank / chunk count / chunk
+// scan (remove_kernels.hpp, unchanged), the compaction of the positions that remain, the movers' placement, ids and origins per
+// new position, the splice; the int8 rows, int8 tiles and the half copy are made as for fresh lists; ONE readback holds the
+// counts of the gate, the offsets and the ids for the host mirrors.
+int hnswgpu_ivf_update(hnswgpu_index *idx, const int32_t *ids, const float *rows, int64_t m) {
+    HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
+    HG_REQUIRE(m >= 0, HNSWGPU_EINVAL, "m must be >= 0");
+    HG_REQUIRE(ids || m == 0, HNSWGPU_EINVAL, "ids is null");
+    HG_REQUIRE(rows || m == 0, HNSWGPU_EINVAL, "rows is null");
+    if (m == 0) return 0;  // nothing to update: nothing happens, whatever the handle holds
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_REQUIRE(idx->nlist > 0, HNSWGPU_ESTATE, "index has no IVF lists (call hnswgpu_ivf_build / hnswgpu_set_ivf first)");
+    HG_REQUIRE(idx->nparts == 0, HNSWGPU_ESTATE, "the index holds a forest of HNSW sub-graphs: its edges would stand for the old values of the rows");
+    HG_REQUIRE(!idx->has_graph, HNSWGPU_ESTATE, "the index holds an HNSW graph: its edges would stand for the old values of the rows");
+    HG_REQUIRE(idx->lsh_tables == 0, HNSWGPU_ESTATE, "the index holds LSH tables: they would keep the hash codes of the old values");
+    HG_REQUIRE(idx->d_glistoff == nullptr, HNSWGPU_ESTATE,
+               "a shard of a larger IVF index (hnswgpu_set_ivf_shard) cannot be updated alone: a row may belong into another shard's list");
+    const int64_t n = idx->n;
+    std::vector<int32_t> uid, from;
+    int64_t at = -1, first = -1;
+    int verdict;
+    try {
+        verdict = ivf_update_slots(ids, m, n, uid, from, &at, &first);  // on the host array, before anything is enqueued
+    } catch (const std::bad_alloc &) {  // (its sorted copy of the ids)
+        set_error("host allocation failed");
+        return HNSWGPU_ENOMEM;
+    }
+    HG_REQUIRE(verdict != 1, HNSWGPU_EINVAL, "ids[%lld] = %d is not a row of the index (n = %lld)", (long long)at, ids[at], (long long)n);
+    HG_REQUIRE(verdict != 2, HNSWGPU_EINVAL, "ids[%lld] = %d is named twice (first at ids[%lld]): two values for one row have no winner",
+               (long long)at, ids[at], (long long)first);
+    HG_TRY(call.quiesce());
+    const int64_t ld = idx->ld;
+    const int32_t nlist = idx->nlist;
+    // Failure-atomic, as hnswgpu_ivf_add / hnswgpu_ivf_remove: every array the call makes is STAGED; the handle's fields point at
+    // the staged arrays only for the int8 / half copies (idx->mu is held and the streams are quiesced) and for good behind the one
+    // readback.
+    IvfArrays nw, old;
+    old.of_handle(idx);
+    bool installed = false;
+    std::vector<int64_t> h_off;
+    std::vector<int32_t> h_ids;
+    std::vector<char> g;  // the readback of counts, flags and gate
+    hipEvent_t e0 = nullptr;  // hnswgpu_set_profiling: the start of the chain
+    auto update = [&]() -> int {
+        const size_t nn = static_cast<size_t>(n), mm = static_cast<size_t>(m);
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.base), sizeof(float) * nn * ld));
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.norms), sizeof(float) * nn));
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.listoff), sizeof(int64_t) * (nlist + 1)));
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.listids), sizeof(int32_t) * nn));
+        // scratch.  s_tile: the caller's rows as they came.  s_misc2: the staging matrix and its norms.  s_misc, 16-byte sections:
+        // [counts | flags | gate | keep | leave | join] zeroed, [slot_of | slot_list | new ids' origin] all ones, then word_rank,
+        // chunk_base, src, kept_off, the slots' row ids and call positions
+        IvfUpdateArgs a;
+        memset(&a, 0, sizeof(a));
+        a.r.n0 = a.r.n1 = n;
+        a.r.W = (n + 31) / 32;
+        a.r.ld = ld;
+        a.r.nchunks = (n + kWG - 1) / kWG;
+        a.m = m;
+        a.nlist = nlist;
+        a.dim = idx->dim;
+        auto sect = [](size_t bytes) { return (bytes + 15) / 16 * 16; };
+        const size_t o_flags = sect(sizeof(unsigned long long) * kUpdCounts), o_gate = o_flags + sect(sizeof(uint32_t)),
+                     o_keep = o_gate + sect(sizeof(int64_t) * kLshRemoveGate), o_leave = o_keep + sect(sizeof(uint32_t) * a.r.W),
+                     o_join = o_leave + sect(sizeof(uint32_t) * nlist), o_slot = o_join + sect(sizeof(uint32_t) * nlist),
+                     o_slist = o_slot + sect(sizeof(int32_t) * nn), o_origin = o_slist + sect(sizeof(int32_t) * mm),
+                     o_rank = o_origin + sect(sizeof(uint32_t) * nn), o_chunk = o_rank + sect(sizeof(uint32_t) * a.r.W),
+                     o_src = o_chunk + sect(sizeof(uint32_t) * a.r.nchunks), o_kept = o_src + sect(sizeof(uint32_t) * nn),
+                     o_uid = o_kept + sect(sizeof(int64_t) * (nlist + 1)), o_from = o_uid + sect(sizeof(int32_t) * mm),
+                     bytes = o_from + sect(sizeof(int32_t) * mm);
+        HG_TRY(idx->s_misc.ensure(bytes));
+        HG_TRY(idx->s_misc2.ensure(sect(sizeof(float) * mm * ld) + sizeof(float) * mm));
+        HG_TRY(idx->s_tile.ensure(sizeof(float) * mm * idx->dim));
+        char *s = idx->s_misc.as<char>();
+        HG_HIP(hipMemsetAsync(s, 0, o_slot, st));
+        HG_HIP(hipMemsetAsync(s + o_slot, 0xff, o_rank - o_slot, st));
+        HG_HIP(hipMemsetAsync(nw.listids, 0xff, sizeof(int32_t) * nn, st));
+        HG_HIP(hipMemcpyAsync(s + o_uid, uid.data(), sizeof(int32_t) * mm, hipMemcpyHostToDevice, st));
+        HG_HIP(hipMemcpyAsync(s + o_from, from.data(), sizeof(int32_t) * mm, hipMemcpyHostToDevice, st));
+        HG_HIP(hipMemcpyAsync(idx->s_tile.p, rows, sizeof(float) * mm * idx->dim, hipMemcpyHostToDevice, st));
+        a.counts = reinterpret_cast<unsigned long long *>(s);
+        a.flags = reinterpret_cast<uint32_t *>(s + o_flags);
+        a.r.gate = reinterpret_cast<int64_t *>(s + o_gate);
+        a.r.keep = reinterpret_cast<uint32_t *>(s + o_keep);
+        a.leave = reinterpret_cast<uint32_t *>(s + o_leave);
+        a.join = reinterpret_cast<uint32_t *>(s + o_join);
+        a.slot_of = reinterpret_cast<int32_t *>(s + o_slot);
+        a.slot_list = reinterpret_cast<int32_t *>(s + o_slist);
+        a.origin = reinterpret_cast<uint32_t *>(s + o_origin);
+        a.r.word_rank = reinterpret_cast<uint32_t *>(s + o_rank);
+        a.r.chunk_base = reinterpret_cast<uint32_t *>(s + o_chunk);
+        a.src = reinterpret_cast<uint32_t *>(s + o_src);
+        a.kept_off = reinterpret_cast<int64_t *>(s + o_kept);
+        a.uid = reinterpret_cast<const int32_t *>(s + o_uid);
+        a.from = reinterpret_cast<const int32_t *>(s + o_from);
+        a.raw = idx->s_tile.as<float>();
+        a.stage = idx->s_misc2.as<float>();
+        float *snorms = reinterpret_cast<float *>(idx->s_misc2.as<char>() + sect(sizeof(float) * mm * ld));
+        a.snorms = snorms;
+        a.r.old_ids = old.listids;
+        a.old_off = old.listoff;
+        a.new_off = nw.listoff;
+        a.new_ids = nw.listids;
+        a.old_lrows = old.lrows;
+        a.old_lnorms = old.lnorms;
+        a.new_base = nw.base;
+        a.new_norms = nw.norms;
+        const unsigned slot_wgs = static_cast<unsigned>((m + kNWave - 1) / kNWave), chunks = static_cast<unsigned>(a.r.nchunks),
+                       row_wgs = static_cast<unsigned>((n + kNWave - 1) / kNWave);
+        // ---- 1. the staging matrix in slot order, its norms (the kernel hnswgpu_create uses: the same bits) and the rows' nearest
+        // centroids -> s_ord [m].  Always the GEMV-order scan, as hnswgpu_ivf_add: a row's list must not depend on its batch.
+        prof_begin(idx, PROF_UPDATE, st, &e0);  // (the whole device chain, first launch to last)
+        hipLaunchKernelGGL(ivf_update_stage_kernel, dim3(slot_wgs), dim3(kWG), 0, st, a);
+        HG_HIP(hipGetLastError());
+        HG_TRY(launch_norms(idx->nch, a.stage, ld, m, snorms, st));
+        ScanArgs sa;
+        memset(&sa, 0, sizeof(sa));
+        sa.rows = idx->d_cent;
+        sa.row_norms = idx->d_cnorms;
+        sa.ld = ld;
+        sa.nrows_all = nlist;
+        sa.Q = a.stage;
+        sa.qld = ld;
+        sa.q_norms = snorms;
+        sa.dim = idx->dim;
+        sa.metric = idx->metric;
+        sa.pairs = nullptr;
+        sa.k = 1;
+        sa.role = ROLE_ASSIGN;
+        HG_TRY(scan_topk(idx, sa, static_cast<int32_t>(m), 1, nlist, st, PROF_ASSIGN));
+        a.assign = idx->s_ord.as<uint32_t>();
+        a.adist = idx->s_dist.as<float>();
+        // ---- 2. the staged base: a device copy of the old one with the m rows scattered in
+        HG_HIP(hipMemcpyAsync(nw.base, old.base, sizeof(float) * nn * ld, hipMemcpyDeviceToDevice, st));
+        HG_HIP(hipMemcpyAsync(nw.norms, old.norms, sizeof(float) * nn, hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(ivf_update_base_kernel, dim3(slot_wgs), dim3(kWG), 0, st, a);
+        // ---- 3 - 6. who moves, the new offsets, the positions that remain, the movers behind them, ids and origins
+        hipLaunchKernelGGL(ivf_update_mark_kernel, dim3(chunks), dim3(kWG), 0, st, a);
+        hipLaunchKernelGGL(ivf_update_offsets_kernel, dim3(1), dim3(kWG), 0, st, a);
+        hipLaunchKernelGGL(lsh_remove_rank_kernel, dim3(1), dim3(kWG), 0, st, a.r);
+        hipLaunchKernelGGL(lsh_remove_chunk_count_kernel, dim3(chunks, 1), dim3(kWG), 0, st, a.r);
+        hipLaunchKernelGGL(lsh_remove_chunk_scan_kernel, dim3(1), dim3(kWG), 0, st, a.r);
+        hipLaunchKernelGGL(ivf_update_compact_kernel, dim3(chunks), dim3(kWG), 0, st, a);
+        hipLaunchKernelGGL(ivf_update_place_kernel, dim3(static_cast<unsigned>(nlist)), dim3(kWG), 0, st, a);
+        hipLaunchKernelGGL(ivf_update_ids_kernel, dim3(chunks), dim3(kWG), 0, st, a);
+        HG_HIP(hipGetLastError());
+        if (old.qrows) HG_TRY(quantize_rows(idx, nw.base, n, &nw.qrows, &nw.qmeta, st));  // (as add: one pass over the new base)
+        // ---- 7. splice.  Lists that are the base rows in place stay so while every new position holds the row of its own number
+        // -- one word read back says so (as hnswgpu_ivf_add).
+        uint32_t flags = kUpdNotIdentity;
+        if (old.alias) {
+            HG_HIP(hipMemcpyAsync(&flags, a.flags, sizeof(flags), hipMemcpyDeviceToHost, st));
+            HG_HIP(hipStreamSynchronize(st));
+            HG_REQUIRE(!(flags & kUpdBadAssign), HNSWGPU_EINVAL, "a new row has no nearest centroid (NaN in rows?)");
+        }
+        if (!(flags & kUpdNotIdentity)) {
+            nw.alias = true;
+            nw.lrows = nw.base;
+            nw.lnorms = nw.norms;
+        } else {
+            HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.lrows), sizeof(float) * nn * ld));
+            HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.lnorms), sizeof(float) * nn));
+            a.new_lrows = nw.lrows;
+            a.new_lnorms = nw.lnorms;
+            hipLaunchKernelGGL(ivf_update_splice_kernel, dim3(row_wgs), dim3(kWG), 0, st, a);
+            HG_HIP(hipGetLastError());
+        }
+        // ---- 8. the int8 tile codes and the half copy over the new list rows: made as for a fresh set of lists, by the handle's
+        // rejection mode (ensure_list_codes / ensure_list_half read the handle)
+        nw.to_handle(idx, n);
+        installed = true;
+        HG_TRY(ensure_list_codes(idx, st));
+        HG_TRY(ensure_list_half(idx, st));
+        prof_end(idx, PROF_UPDATE, st, e0);
+        e0 = nullptr;  // (the slot's now)
+        nw.of_handle(idx);
+        // ---- the one readback: counts, flags and gate (adjacent), offsets, ids
+        g.resize(o_keep);
+        h_off.resize(static_cast<size_t>(nlist) + 1);
+        h_ids.resize(nn);
+        HG_HIP(hipMemcpyAsync(g.data(), s, o_keep, hipMemcpyDeviceToHost, st));
+        HG_HIP(hipMemcpyAsync(h_off.data(), nw.listoff, sizeof(int64_t) * (nlist + 1), hipMemcpyDeviceToHost, st));
+        HG_HIP(hipMemcpyAsync(h_ids.data(), nw.listids, sizeof(int32_t) * nn, hipMemcpyDeviceToHost, st));
+        HG_HIP(hipStreamSynchronize(st));
+        unsigned long long counts[kUpdCounts];
+        int64_t gate[kLshRemoveGate];
+        memcpy(counts, g.data(), sizeof(counts));
+        memcpy(&flags, g.data() + o_flags, sizeof(flags));
+        memcpy(gate, g.data() + o_gate, sizeof(gate));
+        HG_REQUIRE(!(flags & kUpdBadAssign), HNSWGPU_EINVAL, "a new row has no nearest centroid (NaN in rows?)");
+        const int64_t movers = static_cast<int64_t>(counts[0]), stayers = static_cast<int64_t>(counts[1]),
+                      joined = static_cast<int64_t>(counts[2]), left = n - gate[kRemoveMaxTables];
+        HG_REQUIRE(h_off[nlist] == n && static_cast<int64_t>(counts[3]) == n, HNSWGPU_EHIP, "the new lists hold %lld rows, not %lld",
+                   (long long)h_off[nlist], (long long)n);
+        HG_REQUIRE(stayers + movers == m, HNSWGPU_EHIP, "%lld stayers and %lld movers for %lld rows", (long long)stayers, (long long)movers,
+                   (long long)m);
+        HG_REQUIRE(left == movers && joined == movers && n - gate[2 * kRemoveMaxTables] == movers, HNSWGPU_EHIP,
+                   "%lld positions left and %lld joined for %lld movers", (long long)left, (long long)joined, (long long)movers);
+        return 0;
+    };
+    int rc;
+    try {
+        rc = update();
+    } catch (const std::bad_alloc &) {
+        set_error("host allocation failed in hnswgpu_ivf_update");
+        rc = HNSWGPU_ENOMEM;
+    }
+    if (rc != 0) {
+        (void)hipStreamSynchronize(st);  // (nothing of the chain is in flight when the staged arrays are freed)
+        if (e0) (void)hipEventDestroy(e0);
+        if (installed) nw.of_handle(idx);  // (whatever the last step made is the staged set's)
+        old.to_handle(idx, n);
+        nw.release();
+        return rc;
+    }
+    take_list_mirrors(idx, h_off, h_ids, n);
+    old.release();  // (the first-search verdict of a mode-1 handle, ivf_calibrated / ivf_stream_off, stays: not measured again)
     return call.close();
 }
 

@@ -11,7 +11,7 @@ from . import _native
 from ._native import COSINE, DOT, L2, check, debug_counter, get_tuning, lib, set_tuning  # noqa: F401
 
 METRICS = {"cosine": COSINE, "l2": L2, "euclidean": L2, "dot": DOT, COSINE: COSINE, L2: L2, DOT: DOT}
-PROF_IVF_SCAN, PROF_HNSW, PROF_ASSIGN = 0, 1, 2
+PROF_IVF_SCAN, PROF_HNSW, PROF_ASSIGN, PROF_UPDATE = 0, 1, 2, 3
 BUILD_SEQUENTIAL, BUILD_HEURISTIC, BUILD_SYMMETRIC, BUILD_EXTEND = 1, 2, 4, 8     # include/hnswgpu.h: HNSWGPU_BUILD_*
 
 
@@ -497,6 +497,16 @@ class Index:
         assert len(kept) == n_after.value, "hnswgpu_ivf_remove left %d rows, the id list %d" % (n_after.value, len(kept))
         self.n = int(n_after.value)
         return kept
+
+    def ivf_update(self, ids, rows):
+        """hnswgpu_ivf_update: row ``ids[i]`` takes the values ``rows[i]`` (row ids in any order, none named twice); n, every
+        row id and the centroids stay.  A row whose nearest centroid is still its list keeps its list position; a row that
+        moves joins its new list behind the members that remain there, ascending by row id among the call's movers."""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        rows = _queries(rows, self.dim)
+        if len(rows) != len(ids):
+            raise ValueError("%d ids for %d rows" % (len(ids), len(rows)))
+        check(lib().hnswgpu_ivf_update(self._h, _p(ids), _p(rows), len(ids)))
 
     def set_ivf(self, centroids, list_off, list_ids):
         cen = _f32(centroids)

@@ -3,7 +3,8 @@
 ``build_index(data, num_partitions=24, distance_fn=..., max_iterations=10)`` runs k-means++ /
 Lloyd on the device; ``search_knn(index, q, k, mode)`` / ``search_ivf_flat(index, q, k, mode=...,
 num_probes=...)`` scan the probed lists with the HIP scan kernel;
-``add_vectors(index, data)`` grows a built index, ``remove_vectors(index, ids)`` shrinks it; ``search_knn_filtered`` / ``search_batch_filtered`` (not in the reference, whose IVF index has no
+``add_vectors(index, data)`` grows a built index, ``remove_vectors(index, ids)`` shrinks it, ``update_vectors(index, data)``
+gives stored vectors new values under their ids; ``search_knn_filtered`` / ``search_batch_filtered`` (not in the reference, whose IVF index has no
 FilterableIndex) scan only the rows of the probed lists that pass a predicate; ``search_batch_filtered_each`` takes one
 predicate per query.
 """
@@ -87,6 +88,32 @@ def remove_vectors(index, ids):
         rows.extend(rows_of[i])
     kept = index.index.ivf_remove(np.asarray(rows, np.int32))
     index.ids = [index.ids[i] for i in kept]
+    return index
+
+
+def update_vectors(index, data):
+    """"Update existing vectors" (the open item of the reference's to-do list; its IVFFlatIndex is an immutable record):
+    ``data`` has the form ``build_index`` takes; the vector stored under each id takes the new values, moves to its nearest
+    partition if that is another one (hnswgpu_ivf_update), and keeps its id: ``index.ids`` is unchanged, the centroids stay.  An
+    unknown id raises KeyError, an id that names several rows or appears twice in ``data`` raises ValueError, both before the
+    device is touched.  Empty ``data`` does nothing.  Returns the index."""
+    ids, rows = _split(data)
+    if not ids:
+        return index
+    rows_of = {}
+    for row, i in enumerate(index.ids):
+        rows_of.setdefault(i, []).append(row)
+    at, seen = [], set()
+    for i in ids:
+        if i not in rows_of:
+            raise KeyError(i)
+        if len(rows_of[i]) > 1:
+            raise ValueError("id %r names %d rows of the index" % (i, len(rows_of[i])))
+        if i in seen:
+            raise ValueError("id %r appears twice: two values for one vector have no winner" % (i,))
+        seen.add(i)
+        at.append(rows_of[i][0])
+    index.index.ivf_update(np.asarray(at, np.int32), rows)
     return index
 
 

@@ -335,6 +335,59 @@ int hnswgpu_ivf_add(hnswgpu_index *idx, const float *rows, int64_t m);
  * forests (a plain graph alone shrinks through hnswgpu_hnsw_remove); moving centroids or re-clustering after heavy removal.
  * hnswgpu_lsh_remove still refuses a handle with lists. */
 int hnswgpu_ivf_remove(hnswgpu_index *idx, const int32_t *rows, int64_t m, int64_t *n_after);
+/* Rows of a LIVE handle with inverted lists take new values under their ids ("Update existing vectors", the open item of the
+ * reference's to-do list, README.md:172-176; its IVFFlatIndex is an immutable record, so what is restated is its assignment
+ * rule and its list order).  `ids` is m row ids of the handle in host memory, in any order; `rows` is m x dim float32 host
+ * memory; row ids[i] takes the values rows[i].  n, every row id and the centroids stay as they are -- unlike
+ * hnswgpu_ivf_remove + hnswgpu_ivf_add, which hand the row a new id and shift every id above it.
+ *   - Assignment.  Each updated row is assigned to its nearest centroid by its NEW values: strict <, lowest list index wins
+ *     ties (assign-to-nearest-centroid, ivf_flat.clj:79-90).  The arithmetic is the one order hnswgpu_ivf_add uses at every m
+ *     -- the GEMV-order scan, never the MFMA tile path -- so a row's list never depends on the batch it was updated in.
+ *   - Stayers.  A row whose nearest centroid is the list it already sits in keeps its list POSITION; only its values, its
+ *     norm and their compact copies change.  Updating rows to the values they already have changes nothing, bit for bit.
+ *   - Movers.  A row whose nearest centroid is another list leaves its old list, which closes up (the remaining members keep
+ *     their order), and joins the new one behind the members that remain there, ascending by row id among the call's movers:
+ *     new list l = (old members of l in their old order, without the movers that left) ++ (the call's movers into l,
+ *     ascending by row id).  A list every member of which leaves stays, with two equal offsets; an empty list may receive its
+ *     first rows.  (tests/ivf_update_model.py states the rule in numpy.)
+ *   - After the call everything a search reads equals, bit for bit, what hnswgpu_create(the base with the new values) +
+ *     hnswgpu_set_rejection_test(same mode) + hnswgpu_set_ivf(same centroids, the lists of the rule) holds: base, norms, the
+ *     base-order int8 rows and their meta where the handle has them, list offsets and ids, rows and norms in list order,
+ *     their int8 tiles and the half copy, the list-length bookkeeping, and what hnswgpu_get_ivf / hnswgpu_save export.  The
+ *     first-search verdict of a mode-1 handle (hnswgpu_ivf_stream_state) is kept, not measured again.  A handle whose lists
+ *     are its base rows in place (identity list_ids) stays so exactly when the new list_ids are again the identity, and gets
+ *     list-order copies of its own otherwise.
+ *   - The result DEPENDS on how an update is split over calls: the movers of a later call stand behind the movers of an
+ *     earlier one, whatever their ids -- two calls give the rule applied twice, not the rule applied to the union
+ *     (hnswgpu_hnsw_remove's caveat, not the independence of hnswgpu_ivf_add).  Within one call the order of `ids` does not
+ *     matter.
+ *   - Everything happens on the device, in one chain on the handle's stream: the m ids (sorted on the host: slot s of the
+ *     call is the s-th smallest id) and the m rows go up once; norms by the kernel hnswgpu_create uses; every destination is
+ *     a function of the old arrays and the call alone (prefix counts of the positions that remain, a mover's stable rank in
+ *     slot order), never of the order atomics arrive in.
+ *   - Failure-atomic, like hnswgpu_ivf_add and hnswgpu_ivf_remove: nothing is changed in place, every new array is staged
+ *     under the handle's lock with its streams quiesced, and the handle takes them over only after ONE readback -- the new
+ *     offsets and ids for the host mirrors, and a gate of counts: the last new offset == n, positions that left == positions
+ *     that joined == movers, stayers + movers == m (HNSWGPU_EHIP otherwise).  On any failure the staged arrays are freed and
+ *     the handle is what it was.  Searches from other threads wait and see the old or the new index.  Peak memory: the old
+ *     plus the new arrays for the length of the call.
+ *   - Cost: one device copy of the base and of the list rows plus their re-quantisation per CALL, whatever m is -- update
+ *     rows in batches.  Measured on one MI355X (profiles/ivf_update.txt: 31,173 x 768, 24 lists, mode 1): 0.99 / 1.23 /
+ *     1.99 ms for m = 1 / 1,024 / 8,192 scattered rows against 2.05 / 2.06 / 2.06 ms for the rebuild over the base with
+ *     the new values from host memory -- faster at every m measured, by less the more rows a call carries (0.48, 0.60, 0.96
+ *     of the rebuild) -- and against 1.95 / 2.24 / 2.72 ms for hnswgpu_ivf_remove + hnswgpu_ivf_add of the same rows, which
+ *     loses the ids; the device chain is 0.19 / 0.21 / 0.35 ms of a call, the rest is the upload of the rows, allocating
+ *     and freeing the staged arrays and the readback.
+ * Returns, checked in this order, the handle untouched in every case: -1 for a null handle (before m == 0 and before any HIP
+ * call), for m < 0, and for null ids or rows with m > 0; 0 for m == 0 (nothing happens); -3 for a handle without lists, for
+ * one that also holds an HNSW graph, a forest or LSH tables (their copies of the row would go stale) and for a shard
+ * (hnswgpu_set_ivf_shard); the message names which; -1 for an id outside [0, n) and for an id named twice (two values for one
+ * row have no defined winner), both checked on the host array before anything is enqueued; -1 for a new row with no nearest
+ * centroid (NaN).
+ * Out of scope: updates of an HNSW graph or of LSH tables, handles with both a graph and lists, forests, hnswgpu_group_*,
+ * sharded.ShardedIVF and shards (rebuild those); a plain handle without lists; moving centroids or re-clustering after heavy
+ * drift; in-place patching that avoids the per-call copy of the base and the list rows. */
+int hnswgpu_ivf_update(hnswgpu_index *idx, const int32_t *ids, const float *rows, int64_t m);
 int hnswgpu_set_ivf(hnswgpu_index *idx, const float *centroids, int32_t nlist, const int64_t *list_off,
                     const int32_t *list_ids);
 int hnswgpu_get_ivf(const hnswgpu_index *idx, float *centroids, int64_t *list_off, int32_t *list_ids);
@@ -616,6 +669,8 @@ int hnswgpu_get_rejection_stats(hnswgpu_index *idx, int64_t *f32_rows, int64_t *
  * costs bytes instead of saving them.  state: 0 = not measured yet, 1 = measured, not yet read, 2 = decided; off: the
  * verdict; frac: f32 rows / neighbours of the measured launch.  Results never depend on it. */
 int hnswgpu_hnsw_rejection_state(hnswgpu_index *idx, int32_t *state, int32_t *off, double *frac);
+/* Device time between events around the timed launches while hnswgpu_set_profiling is on.  which: 0 the IVF / exact scan kernels,
+ * 1 the HNSW traversal, 2 the assignment scan, 3 the device chain of hnswgpu_ivf_update (first launch to last, one per call). */
 int hnswgpu_get_profile(hnswgpu_index *idx, int32_t which, double *total_ms, int64_t *launches, int32_t reset);
 /* Debug read-back of the last ORDERED traversal launch on this handle (HNSWGPU_TUNE_HNSW_ORDER): *nq = its queries (0: none
  * yet), and the first min(cap, *nq) entries of its order[] (the query indices sorted by (key, index)) and of keys[] (per query:
