@@ -2407,7 +2407,9 @@ int hnswgpu_destroy(hnswgpu_index *idx) {
     DevBuf *bufs[] = {&idx->s_q,   &idx->s_partial, &idx->s_ord,   &idx->s_dist, &idx->s_pairs, &idx->s_ids,
                       &idx->s_outd, &idx->s_probes,  &idx->s_stats, &idx->s_misc, &idx->s_misc2, &idx->s_vis, &idx->s_qp, &idx->s_qn, &idx->s_tile, &idx->s_grp, &idx->s_done, &idx->s_pf, &idx->s_solo, &idx->s_bk, &idx->s_heavy, &idx->s_home, &idx->s_dh, &idx->s_hord,
                       &idx->s_fmask, &idx->s_fpass, &idx->s_fblk, &idx->s_fids, &idx->s_fdist, &idx->s_flmask, &idx->s_ffoff, &idx->s_feum, &idx->s_feuw, &idx->s_feqc,
-                      &idx->s_pt_items, &idx->s_pt_ids, &idx->s_pt_dist, &idx->s_pt_stats, &idx->s_pt_probes};
+                      &idx->s_pt_items, &idx->s_pt_ids, &idx->s_pt_dist, &idx->s_pt_stats, &idx->s_pt_probes,
+                      &idx->s_dense.codes, &idx->s_dense.lb, &idx->slots[0].dense.codes, &idx->slots[0].dense.lb, &idx->slots[1].dense.codes,
+                      &idx->slots[1].dense.lb};
     for (DevBuf *b : bufs) b->release();
     for (int s = 0; s < PROF_N; s++)
         for (auto &pr : idx->prof_ev[s]) {

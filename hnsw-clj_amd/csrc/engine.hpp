@@ -74,6 +74,13 @@ struct DevBuf {
     }
 };
 
+// Scratch of one launch with the dense bounds table (dense_kernels.hpp): the query codes + scalars, and the table.  One per
+// place a launch can be enqueued from without waiting for the launch before it: the handle's (every call inside an hg::Call
+// scope -- those are ordered one behind the other, whatever their streams) and one per Slot.  Grown on demand.
+struct DenseScratch {
+    DevBuf codes, lb;
+};
+
 enum { PROF_IVF_SCAN = 0, PROF_HNSW = 1, PROF_ASSIGN = 2, PROF_UPDATE = 3, PROF_N = 4 };  // (PROF_UPDATE: the device chain of hnswgpu_ivf_update)
 
 // The form of a filtered call's allow-mask (include/hnswgpu.h), W = (n + 31) / 32 words: one mask shared by the call's queries,
@@ -161,6 +168,7 @@ struct hnswgpu_index {
         uint32_t *d_done = nullptr;    // workgroups that have finished the current launch
         int32_t *d_order = nullptr;    // [2 x kZcMaxQueries]: order and keys of an ordered launch (order_kernels.hpp)
         uint32_t seq = 0;              // value the flag takes when the current launch has finished
+        hg::DenseScratch dense;        // a slot launch's own bounds table (two slot launches may be in flight)
     };
     Slot slots[2];
     void *h_pin = nullptr;    // pinned host staging of a large combined batch (queries in, results out)
@@ -226,6 +234,12 @@ struct hnswgpu_index {
     // s_hord: order[nq] | keys[nq] of an ordered HNSW launch (order_kernels.hpp); the last such launch's, for hnswgpu_hnsw_last_order
     const int32_t *hnsw_order_last = nullptr;
     int32_t hnsw_order_nq = 0;
+    // The dense bounds table in front of large wave-kernel launches (hnswgpu_set_hnsw_dense_bounds; hnsw_launch_plan holds the
+    // rule): mode 1 = the rule, 0 = never, 2 = every eligible launch; the table of one launch stays within dense_budget bytes.
+    int dense_mode = 1;
+    size_t dense_budget = static_cast<size_t>(2) << 30;
+    int64_t dense_launches = 0;  // launches that used the table
+    hg::DenseScratch s_dense;
     // s_bk: the per-list pair counters of the IVF survivor stream -- zero between searches (the work-list kernel clears
     // them behind its last read); bk_dirty = a search was enqueued past the point that fills them but not past the
     // work-list kernel (an error in between): the next search clears them itself
@@ -318,6 +332,8 @@ struct HnswLaunchPlan {
     size_t mail_bytes, table_bytes, rec_bytes, region;
     int32_t repeat_cap;   // list capacity of the repeat pass behind this launch, beside the SAME visited set (0: no repeat pass)
     bool ordered;         // Wave: the queries dealt to the XCDs in the order of their nearest pivot row (order_kernels.hpp)
+    bool dense;           // Wave: the int8 bounds of the whole batch from a table computed in front of the launch (dense_kernels.hpp),
+    int64_t lb_ld;        // its row stride (floats)
 };
 // Row width -> CALL(NCH, R, RF): f32 rows in flight per wave without / with the int8 rejection test -- the one table of the three
 // traversal kernels.  With the test a hop fetches f32 rows for a handful of neighbours only, half or a quarter of them in flight
@@ -346,6 +362,13 @@ struct HnswLaunchPlan {
 HnswKernelFn hnsw_solo_kernel_for(const HnswLaunchPlan &p, const HnswArgs &a);
 HnswKernelFn hnsw_wave_kernel_for(const HnswLaunchPlan &p, const HnswArgs &a);
 HnswKernelFn hnsw_parts_kernel_for(const HnswLaunchPlan &p, const HnswArgs &a);  // parts.hip: either family with the item table
+// dense.hip: the wave kernel's instantiations that read the bounds table; the table's row stride for n rows; the bytes of a
+// batch's query codes (its QueryScal block follows them); query codes + table, two launches
+HnswKernelFn hnsw_wave_dense_kernel_for(const HnswLaunchPlan &p, const HnswArgs &a);
+int64_t hnsw_dense_ld(int64_t n);
+size_t hnsw_dense_code_bytes(int nch, int32_t nq);
+int launch_hnsw_dense(const hnswgpu_index *idx, const float *d_Q, int64_t qld, int32_t nq, void *codes, float *lb, int64_t lb_ld,
+                      hipStream_t st);
 struct OrderArgs;
 int launch_hnsw_order(int nch, const OrderArgs &a, hipStream_t st);  // wave.hip: key pass + counting sort
 int launch_norms(int nch, const float *rows, int64_t ld, int64_t n, float *out, hipStream_t st);

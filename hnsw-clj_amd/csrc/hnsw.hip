@@ -85,7 +85,9 @@ static HnswKernelFn hnsw_search_kernel_for(const HnswLaunchPlan &p, const HnswAr
 // while a search is being enqueued: a repeat pass is planned from its first pass's plan (`first`) and reads no key at all, so that
 // its list is sized for the visited set it then runs with.  Nothing is allocated, numbered, synchronised or enqueued before this
 // has returned 0: the limits a launch can exceed are found here.
-static int hnsw_launch_plan(const hnswgpu_index *idx, const HnswArgs &a, const HnswLaunchPlan *first, HnswLaunchPlan &p) {
+// plain_search: the first pass of an unfiltered search call (search_enqueue) -- the launches the dense bounds table may serve.
+static int hnsw_launch_plan(const hnswgpu_index *idx, const HnswArgs &a, const HnswLaunchPlan *first, HnswLaunchPlan &p,
+                            bool plain_search = false) {
     memset(&p, 0, sizeof(p));
     const bool build = a.q_rows != nullptr, repeat = a.q_index != nullptr;
     // A forest launch (HnswArgs::items: a.nq counts items, a.nwords covers the largest part): a traversal never leaves its part,
@@ -220,6 +222,23 @@ static int hnsw_launch_plan(const hnswgpu_index *idx, const HnswArgs &a, const H
         p.ordered = p.kernel == HnswKernel::Wave && !build && !parts && idx->d_qrows && idx->d_qmeta &&
                     (order_mode >= 2 || (order_mode == 1 && a.nq >= kOrderMinQueries));
         if (p.ordered) p.grid = 8 * ((a.nq + 7) / 8);  // slots: eight eighths of order[], the ragged end's surplus slots serve nobody
+        // The int8 bounds of the WHOLE batch against ALL rows from the matrix cores, in front of the launch (dense_kernels.hpp): the
+        // traversal then reads 4 bytes per fresh neighbour instead of an int8 row -- the same floats, by the same code_lower_bound.
+        // Eligible: a plain search launch of the wave kernel with the test on whose table (nq x lb_ld floats) is within the handle's
+        // budget (hnswgpu_set_hnsw_dense_bounds: 2 GiB by default -- the 1.25M-row shards are outside it by design).  It pays only
+        // while a query tests a sizeable share of the rows (a query tests about 6.5 ef neighbours) and the chip is full.
+        // 31k x 768 clustered (the bench's index), ms per launch without / with the table, medians of three rounds of ten launches,
+        // the two alternating (tools/hnsw_batch_sweep.py --dense; the rounds of a setting lie within 0.3 % of each other):
+        // ef 640: 2,048 queries 3.523 / 2.996, 4,096: 6.896 / 5.573, 10,000: 12.023 / 10.077; ef 1600: 10,000: 37.353 / 30.598;
+        // ef 100: 4,096: 1.480 / 1.424, 10,000: 2.992 / 3.022.  At the headline the traversal goes from 11.9 to 9.02 ms, the table costs
+        // 0.97 ms (hnsw_dense_bounds_kernel) + 0.015 ms (the query codes): profiles/hnsw_dense_bounds_ab.txt.
+        // On where 6.5 ef is at least 6 % of n (13 % at ef 640, 33 % at ef 1600: faster at every measured batch; 2.1 % at ef 100:
+        // slower at 10,000 queries) from 8 queries per CU, the smallest batch measured.  Nothing was measured between 2.1 % and 13 %.
+        p.lb_ld = hnsw_dense_ld(a.n);
+        const bool dense_rule = a.nq >= 8 * idx->cus && 6.5 * a.ef >= 0.06 * static_cast<double>(a.n);
+        p.dense = plain_search && p.kernel == HnswKernel::Wave && p.rejection && !build && !parts && idx->dense_mode != 0 &&
+                  static_cast<double>(a.nq) * static_cast<double>(p.lb_ld) * sizeof(float) <= static_cast<double>(idx->dense_budget) &&
+                  (idx->dense_mode >= 2 || dense_rule);
     }
     p.nwords = p.vis_global ? 0 : a.nwords;
     if (p.vis_global) {
@@ -253,6 +272,7 @@ static int hnsw_launch_plan(const hnswgpu_index *idx, const HnswArgs &a, const H
     }
     p.fn = parts                          ? hnsw_parts_kernel_for(p, a)
            : p.kernel == HnswKernel::Solo ? hnsw_solo_kernel_for(p, a)
+           : p.dense                      ? hnsw_wave_dense_kernel_for(p, a)
            : p.kernel == HnswKernel::Wave ? hnsw_wave_kernel_for(p, a)
                                           : hnsw_search_kernel_for(p, a);
     HG_REQUIRE(p.fn, HNSWGPU_ELIMIT, "unsupported row length");
@@ -288,8 +308,18 @@ static int hnsw_number_launch(hnswgpu_index *idx, hipStream_t st) {
 }
 
 // Stage 3: everything that touches the handle or a stream before the kernel, and the plan's part of HnswArgs.  Decides nothing.
-static int hnsw_launch_resources(hnswgpu_index *idx, const HnswLaunchPlan &p, HnswArgs &a, hipStream_t st, int32_t *order_mem) {
+static int hnsw_launch_resources(hnswgpu_index *idx, const HnswLaunchPlan &p, HnswArgs &a, hipStream_t st, int32_t *order_mem,
+                                 DenseScratch *dense_mem) {
     a.dbg = g_tile_dbg_buf;  // null outside diagnostic sessions
+    if (p.dense) {  // dense_mem: a slot launch's own scratch (two may be in flight); otherwise the handle's, ordered by the call scope
+        DenseScratch &ds = dense_mem ? *dense_mem : idx->s_dense;
+        HG_TRY(ds.codes.ensure(hnsw_dense_code_bytes(p.nch, a.nq) + sizeof(QueryScal) * static_cast<size_t>(a.nq)));
+        HG_TRY(ds.lb.ensure(sizeof(float) * static_cast<size_t>(a.nq) * static_cast<size_t>(p.lb_ld)));
+        HG_TRY(launch_hnsw_dense(idx, a.Q, a.qld, a.nq, ds.codes.p, ds.lb.as<float>(), p.lb_ld, st));
+        a.lb = ds.lb.as<float>();
+        a.lb_ld = p.lb_ld;
+        idx->dense_launches++;
+    }
     if (p.ordered) {  // order_mem: a slot launch's own [order | keys] (two may be in flight); otherwise the handle's scratch
         if (!order_mem) {
             HG_TRY(idx->s_hord.ensure(sizeof(int32_t) * 2 * static_cast<size_t>(a.nq)));
@@ -381,8 +411,9 @@ static int hnsw_dispatch(const HnswLaunchPlan &p, const HnswArgs &a, hipStream_t
 }
 
 // Stages 3 to 5 of a planned launch; the tail: the launch counters, and a measuring launch sends its counters on their way
-static int hnsw_launch_planned(hnswgpu_index *idx, const HnswLaunchPlan &p, HnswArgs a, hipStream_t st, int32_t *order_mem = nullptr) {
-    HG_TRY(hnsw_launch_resources(idx, p, a, st, order_mem));
+static int hnsw_launch_planned(hnswgpu_index *idx, const HnswLaunchPlan &p, HnswArgs a, hipStream_t st, int32_t *order_mem = nullptr,
+                               DenseScratch *dense_mem = nullptr) {
+    HG_TRY(hnsw_launch_resources(idx, p, a, st, order_mem, dense_mem));
     HG_TRY(hnsw_dispatch(p, a, st));
     if (p.kernel == HnswKernel::Solo) count_launch(HNSWGPU_COUNT_HNSW_SOLO);
     else if (p.kernel == HnswKernel::SearchHelpers) count_launch(HNSWGPU_COUNT_HNSW_HELPERS);
@@ -467,11 +498,12 @@ struct SlotSignal {
     int32_t *host_again;   // device address of the repeat count in the mapped block
     uint32_t flag_val;
     int32_t *order;        // device: [2 x kZcMaxQueries], order and keys of an ordered launch
+    DenseScratch *dense;   // the slot's scratch of a launch with the dense bounds table
 };
 
 static int search_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t ef,
                           int32_t *d_ids, float *d_dist, int64_t *d_stats, hipStream_t st,
-                          const SlotSignal *sig = nullptr, bool repeat_only = false) {
+                          const SlotSignal *sig = nullptr, bool repeat_only = false, bool filtered = false) {
     // under the handle's lock: a forest has no entry point of its own (the one check behind every plain and filtered search)
     HG_REQUIRE(idx->nparts == 0, HNSWGPU_ESTATE,
                "the index holds a forest (hnswgpu_set_graph_parts / hnswgpu_hnsw_build_parts): search it with hnswgpu_hnsw_search_parts");
@@ -490,7 +522,7 @@ static int search_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, int3
     // one plan -- one reading of the tuning table -- per call: the first pass's, which also sizes the repeat pass
     HnswLaunchPlan p;
     if (!repeat_only) hnsw_calibration_absorb(idx);
-    HG_TRY(hnsw_launch_plan(idx, a, nullptr, p));
+    HG_TRY(hnsw_launch_plan(idx, a, nullptr, p, !filtered));
     int32_t *again_cnt, *again;
     if (sig) {
         again_cnt = sig->again;
@@ -514,7 +546,7 @@ static int search_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, int3
         }
         hipEvent_t e0;
         prof_begin(idx, PROF_HNSW, st, &e0);
-        rc = hnsw_launch_planned(idx, p, a, st, sig ? sig->order : nullptr);
+        rc = hnsw_launch_planned(idx, p, a, st, sig ? sig->order : nullptr, sig ? sig->dense : nullptr);
         prof_end(idx, PROF_HNSW, st, e0);
         if (rc || sig) return rc;
         a.done_cnt = nullptr;
@@ -1151,6 +1183,7 @@ static int hnsw_search_batch_slot(hnswgpu_index *idx, const std::vector<hnswgpu_
     sig.host_again = b.again(dp);
     sig.flag_val = ++slot->seq;
     sig.order = slot->d_order;
+    sig.dense = &slot->dense;
     uint64_t gen;
     HG_HIP(hipSetDevice(idx->device));
     {
@@ -1329,6 +1362,54 @@ int hnswgpu_hnsw_last_order(hnswgpu_index *idx, int32_t *order, int32_t *keys, i
     return 0;
 }
 
+// The dense bounds table (dense_kernels.hpp) per handle: the rule's switch and budget, what it has done, and the table itself
+int hnswgpu_set_hnsw_dense_bounds(hnswgpu_index *idx, int32_t mode, int64_t budget_mb) {
+    HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
+    HG_REQUIRE(mode >= 0 && mode <= 2, HNSWGPU_EINVAL, "mode must be 0 (never), 1 (the rule) or 2 (every eligible launch)");
+    HG_REQUIRE(budget_mb < (1LL << 40), HNSWGPU_EINVAL, "budget_mb out of range");
+    std::lock_guard<std::mutex> lk(idx->mu);
+    idx->dense_mode = mode;
+    if (budget_mb >= 0) idx->dense_budget = static_cast<size_t>(budget_mb) << 20;
+    return 0;
+}
+
+int hnswgpu_hnsw_dense_bounds_state(hnswgpu_index *idx, int32_t *mode, int64_t *budget_mb, int64_t *launches, int64_t *bytes) {
+    HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (mode) *mode = idx->dense_mode;
+    if (budget_mb) *budget_mb = static_cast<int64_t>(idx->dense_budget >> 20);
+    if (launches) *launches = idx->dense_launches;
+    if (bytes) {
+        size_t b = idx->s_dense.codes.cap + idx->s_dense.lb.cap;
+        for (auto &sl : idx->slots) b += sl.dense.codes.cap + sl.dense.lb.cap;
+        *bytes = static_cast<int64_t>(b);
+    }
+    return 0;
+}
+
+int hnswgpu_hnsw_dense_bounds(hnswgpu_index *idx, const float *Q, int32_t nq, int64_t qld, float *out) {
+    HG_REQUIRE(idx && Q && out && nq >= 1, HNSWGPU_EINVAL, "null argument");
+    HG_REQUIRE(qld >= idx->dim, HNSWGPU_EINVAL, "qld is smaller than the dimension");
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_REQUIRE(idx->n > 0, HNSWGPU_ESTATE, "empty index");
+    HG_TRY(ensure_qrows(idx, st));
+    HG_REQUIRE(idx->d_qrows, HNSWGPU_EINVAL,
+               "this handle has no int8 rows (hnswgpu_set_rejection_test: mode 0, or mode 1 with dim < 128)");
+    const size_t qfloats = static_cast<size_t>(nq - 1) * static_cast<size_t>(qld) + idx->dim;
+    HG_TRY(idx->s_q.ensure(sizeof(float) * qfloats));
+    HG_HIP(hipMemcpyAsync(idx->s_q.p, Q, sizeof(float) * qfloats, hipMemcpyHostToDevice, st));
+    const int64_t lb_ld = hnsw_dense_ld(idx->n);
+    DenseScratch &ds = idx->s_dense;
+    HG_TRY(ds.codes.ensure(hnsw_dense_code_bytes(idx->nch, nq) + sizeof(QueryScal) * static_cast<size_t>(nq)));
+    HG_TRY(ds.lb.ensure(sizeof(float) * static_cast<size_t>(nq) * static_cast<size_t>(lb_ld)));
+    HG_TRY(launch_hnsw_dense(idx, idx->s_q.as<float>(), qld, nq, ds.codes.p, ds.lb.as<float>(), lb_ld, st));
+    HG_HIP(hipMemcpy2DAsync(out, sizeof(float) * idx->n, ds.lb.p, sizeof(float) * lb_ld, sizeof(float) * idx->n, nq, hipMemcpyDeviceToHost, st));
+    HG_TRY(call.sync());
+    return call.close();
+}
+
 // Filtered search (api/protocol.clj:34-41,97-102): the unfiltered traversal at ef for kk = min(ef, 1024) results per query
 // into s_fids / s_fdist, then the first k passing entries of every list (filter_kernels.hpp: filter_take_kernel).
 // The take reads query q's mask at d_allow + q * W (Each), or the call's one mask (Single).
@@ -1338,7 +1419,7 @@ static int hnsw_filtered_enqueue(hnswgpu_index *idx, MaskForm form, const float 
     const size_t cnt = static_cast<size_t>(nq) * kk;
     HG_TRY(idx->s_fids.ensure(sizeof(int32_t) * cnt));
     HG_TRY(idx->s_fdist.ensure(sizeof(float) * cnt));
-    HG_TRY(search_enqueue(idx, d_Q, nq, kk, ef, idx->s_fids.as<int32_t>(), idx->s_fdist.as<float>(), d_stats, st));
+    HG_TRY(search_enqueue(idx, d_Q, nq, kk, ef, idx->s_fids.as<int32_t>(), idx->s_fdist.as<float>(), d_stats, st, nullptr, false, true));
     return launch_filter_take(idx->s_fids.as<int32_t>(), idx->s_fdist.as<float>(), nq, kk, k, d_allow, idx->n, d_ids, d_dist, st,
                               form == MaskForm::Each ? (idx->n + 31) / 32 : 0);
 }

@@ -1547,6 +1547,11 @@ struct HnswArgs {
     // and hnsw_wave_kernel (parts.hip); null = every work item is a query of the one graph (entry, max_level).
     const int4 *items;
     unsigned long long *dbg;  // -DHG_HNSW_STAMPS diagnostic builds only: per-phase s_memrealtime totals
+    // hnsw_wave_kernel's DENSE instantiations (dense_kernels.hpp): the rejection test's lower bound of query qi against row r
+    // at lb[qi * lb_ld + r], for every query of the launch and every row; null otherwise.  (Behind everything else: the
+    // other kernels' arguments stay where they were.)
+    const float *lb;
+    int64_t lb_ld;
 };
 
 // -DHG_IVF_STAMPS diagnostic builds (tools/build_stamps.sh): absolute wall_clock64 stamps (100 MHz) of the phases of ONE

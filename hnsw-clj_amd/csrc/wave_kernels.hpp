@@ -20,7 +20,8 @@ namespace hg {
 // One wave per query (workgroups of one wave; persistent: workgroup b serves slots b, b + gridDim.x, ...; a slot is a query).  VG = visited set in
 // HBM stamps.  Build launches too (q_rows: the query is a base row, the best entry of every upper level <= the node's level is
 // emitted for the linker, all ef candidates of layer 0 are the result); the repeat pass stays with hnsw_search_kernel.
-template <int NCH, int RB, bool L2, bool VG, bool PARTS = false>
+// DENSE: the int8 bounds of the whole batch are in a table (dense_kernels.hpp; HnswArgs::lb) -- no query code, no int8 rows here.
+template <int NCH, int RB, bool L2, bool VG, bool PARTS = false, bool DENSE = false>
 __global__ __launch_bounds__(kWave) void hnsw_wave_kernel(HnswArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     // LDS: [main: cap x 8] [img: 64 x 8] [cand_id | cand_d: kMaxDeg each] [bits: nwords]
@@ -65,7 +66,7 @@ __global__ __launch_bounds__(kWave) void hnsw_wave_kernel(HnswArgs a) {
         load_query<NCH>(q, qptr, a.dim, lane);
         const float qn = a.metric == METRIC_COS ? query_norm<NCH>(q) : 0.0f;
         Query16<NCH> qc;  // the query's side of the rejection test
-        if (a.qrows != nullptr) encode_query16<NCH>(q, qc);
+        if (!DENSE && a.qrows != nullptr) encode_query16<NCH>(q, qc);
         const int qlevel = a.q_levels ? a.q_levels[qi] : -1;
         int64_t n_eval = 0, n_hop = 0, n_exact = 0;
         int len = 0;
@@ -135,7 +136,15 @@ __global__ __launch_bounds__(kWave) void hnsw_wave_kernel(HnswArgs a) {
                 // ---- rejection test on the int8 rows (kernels.hpp: quantize_rows_kernel): with a full list a neighbour whose
                 //      LOWER BOUND is already >= the worst cannot be admitted (:195-198) -- it gets +inf and no f32 fetch
                 uint64_t needmask = nc >= 64 ? ~0ull : ((1ull << nc) - 1ull);
-                if (a.qrows != nullptr && list_full) {
+                if constexpr (DENSE) {
+                    // ... read from the table, one bound per fresh neighbour: indexed by the QUERY (ordered launches permute slots)
+                    if (list_full) {
+                        const float lb = lane < nc ? a.lb[static_cast<int64_t>(qi) * a.lb_ld + cand_id[lane]] : 0.0f;
+                        const bool need = lane < nc && !(lb >= worst0);  // NaN: needs the exact distance
+                        if (lane < nc) cand_d[lane] = __uint_as_float(0x7f800000u);  // overwritten below if needed
+                        needmask = __builtin_amdgcn_ballot_w64(need);
+                    }
+                } else if (a.qrows != nullptr && list_full) {
                     uint64_t wmask = 0;
                     const int own = wave_sum8_row(lane);  // the row of a step whose total this lane receives
                     for (int j0 = 0; j0 < nc; j0 += 8) {

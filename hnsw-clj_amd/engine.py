@@ -218,6 +218,30 @@ class Index:
         check(lib().hnswgpu_hnsw_last_order(self._h, order.ctypes.data, keys.ctypes.data, nq.value, C.byref(nq)))
         return order, keys
 
+    def set_hnsw_dense_bounds(self, mode, budget_mb=-1):
+        """hnswgpu_set_hnsw_dense_bounds: 1 = the rule (default), 0 = never, 2 = every eligible launch; budget_mb < 0 keeps it."""
+        check(lib().hnswgpu_set_hnsw_dense_bounds(self._h, int(mode), int(budget_mb)))
+
+    def hnsw_dense_bounds_state(self):
+        """hnswgpu_hnsw_dense_bounds_state: (mode, budget_mb, launches that used the table, device bytes of its scratch)."""
+        m, b, l, n = C.c_int32(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        check(lib().hnswgpu_hnsw_dense_bounds_state(self._h, C.byref(m), C.byref(b), C.byref(l), C.byref(n)))
+        return m.value, b.value, l.value, n.value
+
+    def hnsw_dense_bounds(self, Q):
+        """hnswgpu_hnsw_dense_bounds: the rejection test's lower bounds of every query of Q (may be a strided view of rows)
+        against all n rows, (nq, n) float32, by the kernels in front of a launch with the dense bounds table."""
+        Q = np.asarray(Q, np.float32)
+        if Q.ndim != 2 or Q.shape[1] != self.dim:
+            raise ValueError("Q must be (nq, %d)" % self.dim)
+        if Q.strides[1] != 4 or Q.strides[0] % 4 or Q.strides[0] < 4 * self.dim:
+            Q = np.ascontiguousarray(Q)
+        n = C.c_int64()
+        check(lib().hnswgpu_info(self._h, C.byref(n), None, None, None, None))
+        out = np.empty((len(Q), n.value), np.float32)
+        check(lib().hnswgpu_hnsw_dense_bounds(self._h, Q.ctypes.data, len(Q), Q.strides[0] // 4, _p(out)))
+        return out
+
     def hnsw_rejection_state(self):
         """hnswgpu_hnsw_rejection_state: (state, off, frac) -- what rejection mode 1 has measured on this graph."""
         st, off, fr = C.c_int32(0), C.c_int32(0), C.c_double(0.0)

@@ -676,6 +676,24 @@ int hnswgpu_get_profile(hnswgpu_index *idx, int32_t which, double *total_ms, int
  * yet), and the first min(cap, *nq) entries of its order[] (the query indices sorted by (key, index)) and of keys[] (per query:
  * the index of its nearest pivot row).  Either array may be NULL.  Waits for the device. */
 int hnswgpu_hnsw_last_order(hnswgpu_index *idx, int32_t *order, int32_t *keys, int32_t cap, int32_t *nq);
+/* The dense bounds table.  A large batch tests a sizeable share of ALL rows per query (about 6.5 ef neighbours), so a launch
+ * reads every int8 row hundreds of times for one integer dot product each.  Eligible launches -- a plain (unfiltered, no
+ * forest, no build) search on the one-wave-per-query kernel with the rejection test on -- may instead compute the test's
+ * lower bound of every (query, row) pair in front of the traversal, as one int8 GEMM on the matrix cores (query codes x int8
+ * rows, hnsw-clj_amd/csrc/dense_kernels.hpp), into a table of nq x (n rounded up to 128) floats; the traversal then reads 4
+ * bytes per neighbour.  The integer dot product is exact in any order and the bound comes from the same device function:
+ * every entry is the float hnswgpu_hnsw_rejection_bounds reports, bit for bit, NaN where the test abstains -- results,
+ * counters and hnswgpu_get_rejection_stats never depend on it.
+ * mode: 1 = by the rule of hnsw_launch_plan (default), 0 = never, 2 = every eligible launch (tests).  budget_mb: the largest
+ * table of one launch, MiB (default 2048; negative = leave as it is); a launch whose table would be larger runs without.
+ * The table is scratch of the handle, grown on demand (hnswgpu_hnsw_dense_bounds_state: bytes). */
+int hnswgpu_set_hnsw_dense_bounds(hnswgpu_index *idx, int32_t mode, int64_t budget_mb);
+/* mode and budget as set, the launches on this handle that used the table so far, the device bytes its scratch holds now.
+ * Any pointer may be NULL. */
+int hnswgpu_hnsw_dense_bounds_state(hnswgpu_index *idx, int32_t *mode, int64_t *budget_mb, int64_t *launches, int64_t *bytes);
+/* Diagnostic / test entry: the table alone, by the kernels the searches run, for nq host queries (row stride qld >= dim
+ * floats) against all n rows: out[q * n + r], nq x n floats on the host. */
+int hnswgpu_hnsw_dense_bounds(hnswgpu_index *idx, const float *Q, int32_t nq, int64_t qld, float *out);
 
 /* ---- tuning and test switches --------------------------------------------------------------------------------------
  * One process-wide table of 64-bit values.  NONE of them changes what a search returns within the contract of the path

@@ -11,7 +11,43 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-if len(sys.argv) > 1 and sys.argv[1] == "--order":
+if len(sys.argv) > 1 and sys.argv[1] == "--dense":
+    # python tools/hnsw_batch_sweep.py --dense: the dense bounds table (hnswgpu_set_hnsw_dense_bounds 2) against none (0), as --order:
+    # one process, bench.py's own index, the two settings alternating, three rounds of 10 launches; the table the rule in
+    # hnsw_launch_plan is read from.
+    import numpy as np
+    import torch
+
+    import bench
+    from hnsw_clj_amd import engine
+
+    base = bench.make_31k("clustered", 42, 31173)
+    queries = bench.make_31k("clustered", 43, 10000)
+    dev = torch.device("cuda", 0)
+    idx = engine.Index(base, "cosine", 0)
+    idx.hnsw_build(16, 200, 42, **bench.BUILDERS["heuristic"])
+    print("ef    nq      no table ms (3 rounds)     table ms (3 rounds)        table / none (medians)", flush=True)
+    for ef, nq in ((640, 2048), (640, 4096), (640, 10000), (100, 4096), (100, 10000), (1600, 10000)):
+        Q = torch.from_numpy(queries[:nq]).to(dev)
+        out = (torch.empty((nq, 10), dtype=torch.int32, device=dev), torch.empty((nq, 10), dtype=torch.float32, device=dev))
+        ms = {0: [], 2: []}
+        for rnd in range(4):                      # round 0 warms up
+            for mode in (0, 2):
+                idx.set_hnsw_dense_bounds(mode)
+                idx.hnsw_search_dev(Q, 10, ef, out=out)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(10):
+                    idx.hnsw_search_dev(Q, 10, ef, out=out)
+                torch.cuda.synchronize()
+                if rnd:
+                    ms[mode].append((time.perf_counter() - t0) / 10 * 1e3)
+        med = {m: sorted(v)[1] for m, v in ms.items()}
+        print("%-5d %-7d %-26s %-26s %.4f" % (ef, nq, " ".join("%.4f" % v for v in ms[0]), " ".join("%.4f" % v for v in ms[2]),
+                                           med[2] / med[0]), flush=True)
+    idx.set_hnsw_dense_bounds(1)
+    print("state (mode, budget MiB, launches with the table, scratch bytes):", idx.hnsw_dense_bounds_state())
+elif len(sys.argv) > 1 and sys.argv[1] == "--order":
     import numpy as np
     import torch
 
