@@ -34,10 +34,13 @@ Case = collections.namedtuple("Case", "name values signs l0 entry efs roles")
 # the expansion found (all of them while the list is not full); n_evicted_old: entries of `nearest` as the expansion found it
 # that left; n_admitted_then_evicted: neighbours admitted by this expansion and pushed out again by a later one of its own;
 # on_tie: the expanded candidate had LEFT `nearest` and ties its worst (the reference's <=, :175-178); boundary_tie: two or more
-# were admitted and the nearest entry that left ties the worst entry that stayed
+# were admitted and the nearest entry that left ties the worst entry that stayed; worst: the worst of `nearest` AFTER the expansion
+# (None while it is not full); n_tied_out: the entries that have left `nearest` by then and tie that worst, expanded or not -- what a
+# kernel's list has to keep behind its ef entries (the ghosts of kernels.hpp, the run behind `nearest` of hnsw_list.hpp: compact)
 Event = collections.namedtuple(
-    "Event", "node list_full n_fresh n_survivors n_admitted n_evicted_old n_admitted_then_evicted on_tie boundary_tie")
-Trace = collections.namedtuple("Trace", "ids evals hops events stop")   # stop: (node, its distance, the worst) or None
+    "Event", "node list_full n_fresh n_survivors n_admitted n_evicted_old n_admitted_then_evicted on_tie boundary_tie worst n_tied_out")
+# stop: (node, its distance, the worst) or None; visited: every node whose distance the search evaluated
+Trace = collections.namedtuple("Trace", "ids evals hops events stop visited")
 
 
 # ---- embeddings ----------------------------------------------------------------------------------------------------------
@@ -225,6 +228,7 @@ def trace(dist, l0, entry, ef, k=None):
     cand = list(nearest)
     visited = {int(entry)}
     evals, hops, events, stop = 1, 0, [], None
+    left = collections.Counter()                            # distance -> entries that have left `nearest`
     while cand:
         d, _, node = cand.pop(0)
         full = len(nearest) >= ef
@@ -256,10 +260,13 @@ def trace(dist, l0, entry, ef, k=None):
                     evicted.append(nearest.pop())
         n_old = sum(1 for e in evicted if e[2] in before)
         btie = n_adm >= 2 and bool(evicted) and min(e[0] for e in evicted) == nearest[-1][0]
-        events.append(Event(node, full, n_fresh, n_surv, n_adm, n_old, len(evicted) - n_old, on_tie, btie))
+        left.update(e[0] for e in evicted)
+        worst = nearest[-1][0] if len(nearest) >= ef else None
+        events.append(Event(node, full, n_fresh, n_surv, n_adm, n_old, len(evicted) - n_old, on_tie, btie, worst,
+                            left[worst] if worst is not None else 0))
     k = min(ef, len(nearest)) if k is None else k
     ids = [e[2] for e in nearest[:k]] + [-1] * max(0, k - len(nearest))
-    return Trace(np.array(ids, np.int32), evals, hops, events, stop)
+    return Trace(np.array(ids, np.int32), evals, hops, events, stop, frozenset(visited))
 
 
 def is_full_fanout(e):

@@ -364,8 +364,9 @@ def test_hnsw_heuristic_build_connects_clusters(eng, oracle):
 
 @pytest.mark.parametrize("dim", [384, 768, 1536, 3072])
 def test_hnsw_embedding_dims(eng, oracle, dim):
-    """The dimensions the reference's integration test walks (test/hnsw/integration_test.clj:91-118): every row-length
-    instantiation of the traversal kernel (2 .. 12 float4 chunks per lane), build on the device + search, against the
+    """The dimensions the reference's integration test walks (test/hnsw/integration_test.clj:91-118): four row-length
+    instantiations (2, 3, 6 and 12 float4 chunks per lane) of the kernel a small launch takes in this suite, the several-CU one
+    (every traversal kernel at every width: test_hnsw_search_widths_gpu.py), build on the device + search, against the
     oracle on the same graph; results ascending (:134-136), recall against exact kNN >= 0.8 (:138-157)."""
     O = oracle
     # rows on a 12-dimensional manifold (like sentence embeddings; on well-separated clusters the reference's
@@ -900,7 +901,7 @@ def test_ivf_production_boundary(eng, oracle, metric, tune):
             assert_exact(ids, d, oi, od, "production boundary %s nq=%d k=%d rejection mode %d" % (metric, nq, k, mode_rej))
 
 
-@pytest.mark.parametrize("dim", [24, 300, 768, 1024, 1536, 3072])
+@pytest.mark.parametrize("dim", [24, 300, 768, 1024, 1536, 2048, 2050, 3072])
 @pytest.mark.parametrize("metric", ["cosine", "l2", "dot"])
 def test_rejection_bounds_never_exceed_the_distance(eng, metric, dim):
     """The HNSW traversal skips the f32 row of a neighbour whose int8 lower bound is already >= the list's worst

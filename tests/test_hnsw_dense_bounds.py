@@ -105,10 +105,12 @@ def test_table_equals_the_traversals_bounds_at_every_ragged_size(eng, metric, n)
 
 
 @pytest.mark.parametrize("metric", METRICS)
-@pytest.mark.parametrize("dim", [128, 200, 768, 1536, 3072])
+@pytest.mark.parametrize("dim", [128, 200, 768, 1000, 1030, 1536, 2048, 2050, 3072])
 def test_table_at_every_code_range(eng, metric, dim):
     """Every K the kernel loops over: 200 (padded codes), 768, 1536 (A = 11008) and 3072 (A = 5504, where the planes' own products
-    pass 2^31 before they are summed).  Rows of the largest codes in every place (+-127 against +-A) among the gaussian ones."""
+    pass 2^31 before they are summed); 1000 and 2048 (the traversals' loaders of four and eight chunks), 1030 and 2050 (a last
+    loader chunk that is padding from end to end).  Rows of the largest codes in every place (+-127 against +-A) among the gaussian
+    ones."""
     for n, nq in ((2049, 33), (33, 257)):
         base, Q = _rows_and_queries(n, nq, dim, dim + n)
         base[0] = 3.0

@@ -16,10 +16,11 @@ def eng(native_lib):
     return engine
 
 
-@pytest.mark.parametrize("dim", [24, 300, 768, 1024, 1536, 3072])
+@pytest.mark.parametrize("dim", [24, 300, 768, 1024, 1030, 1536, 1538, 2048, 2050, 3072])
 @pytest.mark.parametrize("metric", ["cosine", "l2", "dot"])
 def test_hnsw_rejection_bounds_never_exceed_the_distance(eng, metric, dim):
-    """The rows of test_rejection_bounds_never_exceed_the_distance (every row-loader width, rows of scales e^+-6, a zero
+    """The rows of test_rejection_bounds_never_exceed_the_distance (every row-loader width -- 2048: eight chunks; 1030, 1538, 2050:
+    five, seven and nine chunks in loaders of six, eight and twelve, the last one padding from end to end --, rows of scales e^+-6, a zero
     row, a row with one huge component, a duplicate, non-finite rows) against a gaussian query, duplicates of rows (one
     scaled by 1000, one with the huge component), a zero query, tiny queries (1e-15 times a gaussian, and 1e-25: below the
     size that still gets a code) and non-finite queries: wherever the 16-bit bound is
