@@ -128,6 +128,7 @@ _SIGS = {
     "hnswgpu_set_hnsw_dense_bounds": ["p", "i32", "i64"],
     "hnswgpu_hnsw_dense_bounds_state": ["p", "p", "p", "p", "p"],
     "hnswgpu_hnsw_dense_bounds": ["p", "p", "i32", "i64", "p"],
+    "hnswgpu_hnsw_dense_rows": ["p", "i32", "p", "p"],
     "hnswgpu_set_tuning": ["i32", "i64"],
     "hnswgpu_get_tuning": ["i32", "p", "p"],
     "hnswgpu_group_create": ["p", "i32", "i32", "i32", "p"],

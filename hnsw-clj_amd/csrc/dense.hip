@@ -11,9 +11,11 @@ static HnswKernelFn wave_dense_kernel(const HnswLaunchPlan &p) {
     return p.vis_global ? &hnsw_wave_kernel<N, R, L, true, false, true> : &hnsw_wave_kernel<N, R, L, false, false, true>;
 }
 
-// (the rows in flight of the rejection test's cell: a plan with the table has the test on)
+// (the rows in flight of the rejection test's cell: a plan with the table has the test on.  768-float rows, nch 3: two or four,
+// the plan's choice -- without the query code and the int8 loop four rows fit 128 VGPRs: hnsw_launch_plan, dense_rows)
 HnswKernelFn hnsw_wave_dense_kernel_for(const HnswLaunchPlan &p, const HnswArgs &a) {
     const bool l2 = a.metric == METRIC_L2;
+    if (p.nch == 3 && p.dense_rows == 4) return l2 ? wave_dense_kernel<3, 4, true>(p) : wave_dense_kernel<3, 4, false>(p);
 #define PICK(N, R, RF) return l2 ? wave_dense_kernel<N, RF, true>(p) : wave_dense_kernel<N, RF, false>(p)
     HG_HNSW_ROWS(p.nch, 2, PICK);
 #undef PICK

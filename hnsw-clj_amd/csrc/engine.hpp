@@ -239,6 +239,8 @@ struct hnswgpu_index {
     int dense_mode = 1;
     size_t dense_budget = static_cast<size_t>(2) << 30;
     int64_t dense_launches = 0;  // launches that used the table
+    int dense_rows_mode = 0;     // hnswgpu_hnsw_dense_rows: f32 rows in flight of such launches on 768-float rows, 0 = the rule, 2 / 4
+    int64_t dense_rows4_launches = 0;  // ... and those that kept four
     hg::DenseScratch s_dense;
     // s_bk: the per-list pair counters of the IVF survivor stream -- zero between searches (the work-list kernel clears
     // them behind its last read); bk_dirty = a search was enqueued past the point that fills them but not past the
@@ -334,6 +336,7 @@ struct HnswLaunchPlan {
     bool ordered;         // Wave: the queries dealt to the XCDs in the order of their nearest pivot row (order_kernels.hpp)
     bool dense;           // Wave: the int8 bounds of the whole batch from a table computed in front of the launch (dense_kernels.hpp),
     int64_t lb_ld;        // its row stride (floats)
+    int dense_rows;       // ... and the f32 rows in flight of its nch 3 instances, 2 or 4 (0: every other launch, HG_HNSW_ROWS decides)
 };
 // Row width -> CALL(NCH, R, RF): f32 rows in flight per wave without / with the int8 rejection test -- the one table of the three
 // traversal kernels.  With the test a hop fetches f32 rows for a handful of neighbours only, half or a quarter of them in flight

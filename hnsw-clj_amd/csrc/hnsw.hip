@@ -239,6 +239,25 @@ static int hnsw_launch_plan(const hnswgpu_index *idx, const HnswArgs &a, const H
         p.dense = plain_search && p.kernel == HnswKernel::Wave && p.rejection && !build && !parts && idx->dense_mode != 0 &&
                   static_cast<double>(a.nq) * static_cast<double>(p.lb_ld) * sizeof(float) <= static_cast<double>(idx->dense_budget) &&
                   (idx->dense_mode >= 2 || dense_rule);
+        // f32 rows a wave of such a launch keeps in flight, on 768-float rows (nch 3; every other width: HG_HNSW_ROWS).  Without the
+        // query code and the eight-row int8 loop the instance with FOUR rows holds 102-103 VGPRs (four waves per SIMD, 16 per CU; two
+        // rows: 74-75, six per SIMD), and a hop fetches its rows in half the dependent round trips.  The rule this started from --
+        // four where the LDS admits 16 workgroups per CU at most (10,240 B each), so that they cost no resident wave -- left 2-4 %
+        // behind between ef 320 and 512.  31k x 768 clustered (the bench's index), ms per launch two / four rows, medians of three
+        // rounds of ten launches, the two alternating (tools/hnsw_batch_sweep.py --rows; the rounds of a setting lie within 0.8 %
+        // of each other; LDS per workgroup in brackets):
+        // 10,000 queries: ef 256 (7,244 B) 5.062 / 5.145, ef 288 (7,500) 5.435 / 5.525, ef 304 (7,628) 5.617 / 5.714, ef 320 (7,756)
+        // 6.127 / 5.900, ef 384 (8,268) 6.933 / 6.656, ef 448 (8,780) 7.825 / 7.490, ef 512 (9,292) 8.473 / 8.279, ef 640 (10,316)
+        // 10.028 / 9.657, ef 1600 (17,996) 30.376 / 28.443; ef 640: 2,048 queries 2.991 / 2.819, 4,096: 5.565 / 5.357; 4,096 queries:
+        // ef 320 2.805 / 2.778, ef 448 3.318 / 3.305.
+        // Two rows are 1.7 % faster up to 7,628 B and four 2-6 % from 7,756 B: the TWO-row launch is what changes there (+ 9 % from
+        // ef 304 to 320 for 5 % more list; supposed: a CU hands out LDS in steps, 6 x 1,280 = 7,680, and holds 18 such workgroups
+        // instead of 21), the four-row one holds 16 by its registers on both sides.  Four rows from kDenseRows4Lds; launches whose
+        // visited set is in HBM (less LDS per workgroup) were not measured and follow the same bytes.
+        // hnswgpu_hnsw_dense_rows (per handle, like the table's mode): 0 = this rule, 2 / 4 = forced (A/B, tests).
+        constexpr size_t kDenseRows4Lds = 7680;
+        if (p.dense && p.nch == 3)
+            p.dense_rows = idx->dense_rows_mode != 0 ? idx->dense_rows_mode : (wave_lds_bytes(a.cap, nwords) > kDenseRows4Lds ? 4 : 2);
     }
     p.nwords = p.vis_global ? 0 : a.nwords;
     if (p.vis_global) {
@@ -319,6 +338,7 @@ static int hnsw_launch_resources(hnswgpu_index *idx, const HnswLaunchPlan &p, Hn
         a.lb = ds.lb.as<float>();
         a.lb_ld = p.lb_ld;
         idx->dense_launches++;
+        if (p.dense_rows == 4) idx->dense_rows4_launches++;
     }
     if (p.ordered) {  // order_mem: a slot launch's own [order | keys] (two may be in flight); otherwise the handle's scratch
         if (!order_mem) {
@@ -1384,6 +1404,16 @@ int hnswgpu_hnsw_dense_bounds_state(hnswgpu_index *idx, int32_t *mode, int64_t *
         for (auto &sl : idx->slots) b += sl.dense.codes.cap + sl.dense.lb.cap;
         *bytes = static_cast<int64_t>(b);
     }
+    return 0;
+}
+
+int hnswgpu_hnsw_dense_rows(hnswgpu_index *idx, int32_t rows, int32_t *rows_set, int64_t *launches_four) {
+    HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
+    HG_REQUIRE(rows < 0 || rows == 0 || rows == 2 || rows == 4, HNSWGPU_EINVAL, "rows must be 0 (the rule), 2 or 4 (negative: unchanged)");
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (rows >= 0) idx->dense_rows_mode = rows;
+    if (rows_set) *rows_set = idx->dense_rows_mode;
+    if (launches_four) *launches_four = idx->dense_rows4_launches;
     return 0;
 }
 

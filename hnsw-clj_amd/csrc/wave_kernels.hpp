@@ -7,15 +7,45 @@
 // largest compute phase -- at the headline's ef 640 the merge took 2.9 of the 8.2 us an expansion takes per wave, the same again
 // went into selecting the next candidate from LDS, and the launch ran no faster with the int8 rejection test than without
 // (24 % fewer bytes, same time): THAT kernel is bound by instructions, not by memory.  This one is bound by memory: the
-// headline launch requests 9.8 MB per query, 7.6 TB/s, 28-29 GB/s per CU past L2 -- what a CU's path to memory carries for
-// random ~1 KB rows -- and 4,096 queries already run at the QPS of 10,000, so its time follows the bytes that leave L2
-// (hence the 16-bit query code of the rejection test, kernels.hpp: Query16).  The list is hnsw_list.hpp's, the one the sequencer
-// of solo_kernels.hpp keeps too, here without a mirror: nobody else reads it.  Ids, distance bits and both counters are
-// hnsw_search_kernel's (the parity suite runs both).
+// headline launch (the DENSE instance, four rows in flight) fetches 57.65 GB past L2 in 8.56 ms -- 5.8 MB per query, 1,868 f32 rows
+// of 3 KB of which nine in ten are admitted; 6.74 TB/s, 26.3 GB/s per CU, where a CU's path to memory carries 29-31 GB/s for random
+// rows of an Infinity-Cache-resident table of this size (profiles/hnsw_dense_rows_ab.txt) -- so its time follows the bytes that
+// leave L2 (hence the bounds table of the DENSE instances, and the 16-bit query code of the others' rejection test, kernels.hpp:
+// Query16) and the dependent round trips a hop fetches them in (hence the rows in flight).  The list is hnsw_list.hpp's, the
+// one the sequencer of solo_kernels.hpp keeps too, here without a mirror: nobody else reads it.  Ids, distance bits and both
+// counters are hnsw_search_kernel's (the parity suite runs both).
 #pragma once
 #include "hnsw_list.hpp"
 
 namespace hg {
+
+// One trip of an expansion's gather: the f32 rows of the needed neighbours of ranks t0 .. t0 + R - 1 in flight together, their
+// distances into cand_d (lane b takes the candidate of rank t0 + b and fetches its norm up front).
+template <int NCH, int R, bool L2>
+__device__ __forceinline__ void wave_gather_trip(const float *rows, int64_t ld, const float *row_norms, int metric,
+                                                 const float4 (&q)[NCH], float qn, const int32_t *cand_id, float *cand_d, bool isset,
+                                                 int rank, int t0, int nneed, int nvec, int lane) {
+    float4 r[R][NCH];
+    int myj = -1;
+#pragma unroll
+    for (int b = 0; b < R; b++) {
+        const uint64_t hit = __builtin_amdgcn_ballot_w64(isset && rank == t0 + b);
+        const int jb = hit ? __ffsll(static_cast<unsigned long long>(hit)) - 1 : -1;
+        myj = lane == b ? jb : myj;
+    }
+    const int32_t myid = myj >= 0 ? cand_id[myj] : 0;
+    const float myrn = (metric == METRIC_COS && myj >= 0) ? row_norms[myid] : 0.0f;
+#pragma unroll
+    for (int b = 0; b < R; b++) {
+        const int32_t rid = __builtin_amdgcn_readlane(myid, b);
+        load_row<NCH>(r[b], rows + static_cast<int64_t>(rid) * ld, nvec, lane, t0 + b < nneed);
+    }
+    float s[R];
+#pragma unroll
+    for (int b = 0; b < R; b++) s[b] = lane_partial<NCH, L2>(q, r[b]);
+    const float mine = rows_sum_to_lane<R>(s, lane);  // lane b keeps candidate b's reduced sum
+    if (myj >= 0) cand_d[myj] = finish_dist(metric, mine, qn, myrn) + 0.0f;
+}
 
 // One wave per query (workgroups of one wave; persistent: workgroup b serves slots b, b + gridDim.x, ...; a slot is a query).  VG = visited set in
 // HBM stamps.  Build launches too (q_rows: the query is a base row, the best entry of every upper level <= the node's level is
@@ -179,27 +209,16 @@ __global__ __launch_bounds__(kWave) void hnsw_wave_kernel(HnswArgs a) {
                 n_exact += nneed;
                 const bool isset = (needmask >> lane) & 1ull;
                 const int rank = __popcll(needmask & ((1ull << lane) - 1ull));
+                // (768-float rows with the table and four rows in flight: a last trip of one or two rows is the two-row trip --
+                // nneed is wave-uniform, and a row's distance does not depend on the trip that fetched it)
+                constexpr bool kShortTrip = DENSE && NCH == 3 && RB == 4;
                 for (int t0 = 0; t0 < nneed; t0 += RB) {
-                    float4 r[RB][NCH];
-                    int myj = -1;
-#pragma unroll
-                    for (int b = 0; b < RB; b++) {
-                        const uint64_t hit = __builtin_amdgcn_ballot_w64(isset && rank == t0 + b);
-                        const int jb = hit ? __ffsll(static_cast<unsigned long long>(hit)) - 1 : -1;
-                        myj = lane == b ? jb : myj;
-                    }
-                    const int32_t myid = myj >= 0 ? cand_id[myj] : 0;
-                    const float myrn = (a.metric == METRIC_COS && myj >= 0) ? a.row_norms[myid] : 0.0f;
-#pragma unroll
-                    for (int b = 0; b < RB; b++) {
-                        const int32_t rid = __builtin_amdgcn_readlane(myid, b);
-                        load_row<NCH>(r[b], a.rows + static_cast<int64_t>(rid) * a.ld, nvec, lane, t0 + b < nneed);
-                    }
-                    float s[RB];
-#pragma unroll
-                    for (int b = 0; b < RB; b++) s[b] = lane_partial<NCH, L2>(q, r[b]);
-                    const float mine = rows_sum_to_lane<RB>(s, lane);  // lane b keeps candidate b's reduced sum
-                    if (myj >= 0) cand_d[myj] = finish_dist(a.metric, mine, qn, myrn) + 0.0f;
+                    if (kShortTrip && nneed - t0 <= 2)
+                        wave_gather_trip<NCH, 2, L2>(a.rows, a.ld, a.row_norms, a.metric, q, qn, cand_id, cand_d, isset, rank, t0, nneed,
+                                                     nvec, lane);
+                    else
+                        wave_gather_trip<NCH, RB, L2>(a.rows, a.ld, a.row_norms, a.metric, q, qn, cand_id, cand_d, isset, rank, t0, nneed,
+                                                      nvec, lane);
                 }
                 // ---- admission: lane j = the j-th fresh neighbour
                 const float cdist = lane < nc ? cand_d[lane] : 0.0f;

@@ -228,6 +228,13 @@ class Index:
         check(lib().hnswgpu_hnsw_dense_bounds_state(self._h, C.byref(m), C.byref(b), C.byref(l), C.byref(n)))
         return m.value, b.value, l.value, n.value
 
+    def hnsw_dense_rows(self, rows=-1):
+        """hnswgpu_hnsw_dense_rows: f32 rows in flight behind the table on 768-float rows, 0 = the rule (default), 2 / 4 forced,
+        negative keeps the setting; returns (the setting, launches on this handle that kept four rows in flight)."""
+        r, n = C.c_int32(0), C.c_int64(0)
+        check(lib().hnswgpu_hnsw_dense_rows(self._h, int(rows), C.byref(r), C.byref(n)))
+        return r.value, n.value
+
     def hnsw_dense_bounds(self, Q):
         """hnswgpu_hnsw_dense_bounds: the rejection test's lower bounds of every query of Q (may be a strided view of rows)
         against all n rows, (nq, n) float32, by the kernels in front of a launch with the dense bounds table."""

@@ -691,6 +691,12 @@ int hnswgpu_set_hnsw_dense_bounds(hnswgpu_index *idx, int32_t mode, int64_t budg
 /* mode and budget as set, the launches on this handle that used the table so far, the device bytes its scratch holds now.
  * Any pointer may be NULL. */
 int hnswgpu_hnsw_dense_bounds_state(hnswgpu_index *idx, int32_t *mode, int64_t *budget_mb, int64_t *launches, int64_t *bytes);
+/* f32 rows a wave keeps in flight in launches with the table on 768-float rows (513 to 768 elements; every other width keeps
+ * its fixed count).  rows: 0 = four from 7.5 KiB of LDS per workgroup (ef 320 on a 31k-row index), where fewer workgroups fit a CU
+ * anyway, two below (default; the measured table is beside the rule in hnsw_launch_plan), 2 / 4 = forced (A/B, tests), negative
+ * = leave as it is.  *rows_set: the setting; *launches_four: the launches on this handle that kept four rows in flight so far.
+ * Either pointer may be NULL.  Results, counters and hnswgpu_get_rejection_stats never depend on it. */
+int hnswgpu_hnsw_dense_rows(hnswgpu_index *idx, int32_t rows, int32_t *rows_set, int64_t *launches_four);
 /* Diagnostic / test entry: the table alone, by the kernels the searches run, for nq host queries (row stride qld >= dim
  * floats) against all n rows: out[q * n + r], nq x n floats on the host. */
 int hnswgpu_hnsw_dense_bounds(hnswgpu_index *idx, const float *Q, int32_t nq, int64_t qld, float *out);

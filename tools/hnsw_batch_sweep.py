@@ -3,7 +3,10 @@ waves-per-query setting the launcher can pick.  usage: python tools/hnsw_batch_s
 
 python tools/hnsw_batch_sweep.py --order: the wave kernel's ordered launches (HNSW_ORDER 2) against plain ones (0) in ONE process
 on bench.py's own index (31,173 x 768 clustered, heuristic builder): 2,048 / 4,096 / 10,000 queries at ef 640 and ef 100, the two
-settings alternating, three rounds of 10 launches each; the table hnsw_launch_plan's threshold (kOrderMinQueries) is read from."""
+settings alternating, three rounds of 10 launches each; the table hnsw_launch_plan's threshold (kOrderMinQueries) is read from.
+
+python tools/hnsw_batch_sweep.py --dense / --rows [ef:nq ...]: the same protocol for the dense bounds table (on against off) and
+for the f32 rows in flight behind it (hnswgpu_hnsw_dense_rows 2 against 4): the tables beside the two rules in hnsw_launch_plan."""
 import os
 import subprocess
 import sys
@@ -47,6 +50,46 @@ if len(sys.argv) > 1 and sys.argv[1] == "--dense":
                                            med[2] / med[0]), flush=True)
     idx.set_hnsw_dense_bounds(1)
     print("state (mode, budget MiB, launches with the table, scratch bytes):", idx.hnsw_dense_bounds_state())
+elif len(sys.argv) > 1 and sys.argv[1] == "--rows":
+    # python tools/hnsw_batch_sweep.py --rows: two f32 rows in flight against four in the launches with the dense bounds table
+    # (hnswgpu_hnsw_dense_rows 2 / 4), as --dense: one process, bench.py's own index, the two settings alternating, three rounds of 10
+    # launches; the table the rows-in-flight rule in hnsw_launch_plan is read from.  The table is forced on (mode 2) so that the ef
+    # below the dense rule's threshold are measured too.
+    import numpy as np
+    import torch
+
+    import bench
+    from hnsw_clj_amd import engine
+
+    base = bench.make_31k("clustered", 42, 31173)
+    queries = bench.make_31k("clustered", 43, 10000)
+    dev = torch.device("cuda", 0)
+    idx = engine.Index(base, "cosine", 0)
+    idx.hnsw_build(16, 200, 42, **bench.BUILDERS["heuristic"])
+    idx.set_hnsw_dense_bounds(2)
+    print("ef    nq      two rows ms (3 rounds)     four rows ms (3 rounds)    four / two (medians)", flush=True)
+    shapes = [tuple(int(x) for x in s.split(":")) for s in sys.argv[2:]]      # further shapes: ef:nq ...
+    for ef, nq in shapes or ((640, 2048), (640, 4096), (640, 10000), (1600, 10000), (288, 10000), (320, 10000), (448, 10000)):
+        Q = torch.from_numpy(queries[:nq]).to(dev)
+        out = (torch.empty((nq, 10), dtype=torch.int32, device=dev), torch.empty((nq, 10), dtype=torch.float32, device=dev))
+        ms = {2: [], 4: []}
+        for rnd in range(4):                      # round 0 warms up
+            for rows in (2, 4):
+                idx.hnsw_dense_rows(rows)
+                idx.hnsw_search_dev(Q, 10, ef, out=out)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(10):
+                    idx.hnsw_search_dev(Q, 10, ef, out=out)
+                torch.cuda.synchronize()
+                if rnd:
+                    ms[rows].append((time.perf_counter() - t0) / 10 * 1e3)
+        med = {m: sorted(v)[1] for m, v in ms.items()}
+        print("%-5d %-7d %-26s %-26s %.4f" % (ef, nq, " ".join("%.4f" % v for v in ms[2]), " ".join("%.4f" % v for v in ms[4]),
+                                           med[4] / med[2]), flush=True)
+    idx.set_hnsw_dense_bounds(1)
+    print("launch counter hnsw_wave %d; launches with the table %d, of them with four rows %d" % (
+        engine.debug_counter("hnsw_wave"), idx.hnsw_dense_bounds_state()[2], idx.hnsw_dense_rows(0)[1]))
 elif len(sys.argv) > 1 and sys.argv[1] == "--order":
     import numpy as np
     import torch
