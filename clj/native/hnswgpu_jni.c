@@ -371,6 +371,23 @@ JNIEXPORT jlong JNICALL Java_hnsw_gpu_Native_lshRemove(JNIEnv *env, jclass c, jl
     return rc != 0 ? (jlong)rc : (jlong)n_after;
 }
 
+/* rows of a live hybrid LSH index take new values (hnswgpu_lsh_update): `ids` holds m row ids in any order, none named twice; `rows`
+ * holds m x dim floats, row ids[i] takes rows[i]; n, the ids and the planes stay.  Returns 0, or the negative error code (the
+ * exception is pending).  Unverified like the rest of this file: no JVM where the library is built and tested. */
+JNIEXPORT jint JNICALL Java_hnsw_gpu_Native_lshUpdate(JNIEnv *env, jclass c, jlong h, jintArray ids, jfloatArray rows, jlong m, jint dim) {
+    if (!ids || !rows) return throw_iae(env, "lshUpdate: null array");
+    if (m < 0 || m > (jlong)(*env)->GetArrayLength(env, ids)) return throw_iae(env, "lshUpdate: m outside the id array");
+    if (dim < 1 || m > (jlong)(*env)->GetArrayLength(env, rows) / dim) return throw_iae(env, "lshUpdate: fewer than m x dim floats");
+    jint *pi = (*env)->GetIntArrayElements(env, ids, NULL);
+    jfloat *pr = pi ? (*env)->GetFloatArrayElements(env, rows, NULL) : NULL;
+    int rc = pi && pr ? hnswgpu_lsh_update((hnswgpu_index *)(intptr_t)h, (const int32_t *)pi, (const float *)pr, (int64_t)m)
+                      : HNSWGPU_ENOMEM; /* OutOfMemoryError is pending */
+    if (pr) (*env)->ReleaseFloatArrayElements(env, rows, pr, JNI_ABORT);
+    if (pi) (*env)->ReleaseIntArrayElements(env, ids, pi, JNI_ABORT);
+    if (rc != 0 && rc != HNSWGPU_ENOMEM) throw_last(env);
+    return rc;
+}
+
 /* rows leave a live IVF-FLAT index (hnswgpu_ivf_remove): `rows` holds m row ids in any order, repeats count once; the kept rows are
  * renumbered densely in their old order, every list keeps its kept members in their order.  Returns the rows the handle holds
  * afterwards, or the negative error code (the exception is pending).  Unverified like the rest of this file: no JVM where the

@@ -24,6 +24,7 @@
      (build-lsh-index data :metric :cosine)                          ; hnsw.ann.hash.hybrid-lsh/build-lsh-index: (Random. 42), 8 x 12 bits
      (add-lsh-vectors! index new-data)                               ; rows join a live hybrid-LSH index: hnswgpu_lsh_add
      (remove-lsh-vectors! index ids)                                 ; ... and leave it: hnswgpu_lsh_remove
+     (update-lsh-vectors! index new-data)                            ; ... and take new values under their ids: hnswgpu_lsh_update
      (search-lsh index query-vec k :mode :balanced)                  ; hybrid-lsh/search-knn (search-hybrid-multiprobe)
      (search-lsh-batch index queries k :mode :balanced)
      (search-lsh-filtered index query-vec k filter-fn :mode :balanced) ; the allow-mask through the bucket scan: hnswgpu_lsh_search_filtered
@@ -277,6 +278,31 @@
             (let [kept (vec (remove gone (:ids idx)))]
               (assert (= (count kept) (.getAtIndex n-after L 0)))
               (assoc idx :ids kept))))))))
+
+(def ^:private h-lshupdate (delay (fn-handle "hnswgpu_lsh_update" (FunctionDescriptor/of I (into-array [P P P L])))))
+
+(defn update-lsh-vectors!
+  "\"Update existing vectors\" (the open item of the reference's to-do list; its HybridIndex is an immutable record) for a live
+   hybrid-LSH GpuIndex: new-data is a seq of [id ^doubles vector]; the vector stored under each id takes the new values, is hashed
+   again under the index's hyperplanes and, in every table where its code changed, moves to its new bucket at the place its row
+   gives it (hybrid_lsh.clj:105-129: a bucket lists its rows in row order), and keeps its id (hnswgpu_lsh_update).  An unknown id, an
+   id that names several rows and an id given twice throw before the device is touched.  Returns the index (its ids are
+   unchanged).  One call per batch is the efficient shape: a call copies the rows once, whatever it updates.  Unverified like the
+   rest of this namespace: no JVM where the library is built."
+  [idx new-data]
+  (let [rows-of (reduce (fn [m [i id]] (update m id (fnil conj []) i)) {} (map-indexed vector (:ids idx)))
+        ids (mapv first new-data)]
+    (doseq [id ids]
+      (when-not (contains? rows-of id) (throw (ex-info "update-lsh-vectors!: unknown id" {:id id})))
+      (when (> (count (rows-of id)) 1) (throw (ex-info "update-lsh-vectors!: the id names several rows" {:id id}))))
+    (when-not (or (empty? ids) (apply distinct? ids))
+      (throw (ex-info "update-lsh-vectors!: an id is given twice" {})))
+    (when (seq ids)
+      (with-open [arena (Arena/ofConfined)]
+        (check (.invokeWithArguments ^MethodHandle @h-lshupdate
+                                     [(:handle idx) (ints-of arena (mapv (comp first rows-of) ids))
+                                      (floats-of arena (mapv second new-data) (:dim idx)) (long (count ids))]))))
+    idx))
 
 (def ^:private lsh-modes {:turbo [2 1] :fast [4 1] :balanced [6 2] :accurate [8 3] :precise [8 4]})   ; hybrid_lsh.clj:350-364
 

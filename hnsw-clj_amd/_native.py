@@ -105,6 +105,7 @@ _SIGS = {
     "hnswgpu_lsh_hash": ["p", "p", "i32", "p"],
     "hnswgpu_lsh_add": ["p", "p", "i64"],
     "hnswgpu_lsh_remove": ["p", "p", "i64", "p"],
+    "hnswgpu_lsh_update": ["p", "p", "p", "i64"],
     "hnswgpu_lsh_search": ["p", "p", "i32", "i32", "i32", "i32", "i32", "i32", "p", "p"],
     "hnswgpu_lsh_search_dev": ["p", "p", "i32", "i32", "i32", "i32", "i32", "i32", "p", "p", "p"],
     "hnswgpu_lsh_search_filtered": ["p", "p", "i32", "i32", "i32", "i32", "i32", "i32", "p", "p", "p"],

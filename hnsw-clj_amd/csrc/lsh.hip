@@ -1,17 +1,19 @@
 // lsh.hip -- the hybrid LSH index (src/hnsw/ann/hash/hybrid_lsh.clj): hyperplanes, hash, buckets, multi-probe search
-// (C ABI: include/hnswgpu.h, "Hybrid LSH"; kernels: lsh_kernels.hpp, lsh_add_kernels.hpp for rows that join live tables and
-// lsh_remove_kernels.hpp for rows that leave them).
+// (C ABI: include/hnswgpu.h, "Hybrid LSH"; kernels: lsh_kernels.hpp, lsh_add_kernels.hpp for rows that join live tables,
+// lsh_remove_kernels.hpp for rows that leave them and lsh_update_kernels.hpp for rows that take new values).
 #include <string.h>
 
 #include <new>
 #include <vector>
 
 #include "engine.hpp"
+#include "ivf_update_ids.hpp"
 #include "javarandom.hpp"
 #include "lsh_add_kernels.hpp"
 #include "lsh_kernels.hpp"
 #include "lsh_remove_ids.hpp"
 #include "lsh_remove_kernels.hpp"
+#include "lsh_update_kernels.hpp"
 
 namespace hg {
 
@@ -541,6 +543,156 @@ int hnswgpu_lsh_remove(hnswgpu_index *idx, const int32_t *rows, int64_t m, int64
     }
     nw.swap_into(idx, n1);  // (n1 == 0: no base, norms, codes or ids -- an empty handle with planes and all-zero offsets)
     if (n_after) *n_after = n1;
+    return call.close();
+}
+
+// Rows of a live handle with tables take new values under their ids (include/hnswgpu.h).  The reference's HybridIndex is an
+// immutable record and "Update existing vectors" an open item of its to-do list; what is restated is again its bucket order: the
+// updated handle holds what hnswgpu_create(the base with the new values) + hnswgpu_set_lsh(the same planes) holds.  One chain on
+// the handle's stream (lsh_update_kernels.hpp): the call's rows into a staging matrix in slot order (slot s = the s-th smallest
+// id, ivf_update_ids.hpp), their norms (launch_norms) and codes (lsh_hash_kernel), device copies of base / norms / codes with the
+// m rows scattered in, per table the entries that leave and join every bucket, the new offsets, the movers grouped by the bucket
+// they leave and by the bucket they join, and the placement of the entries that stay and of those that join; the int8 rows are
+// made over the new base as add does; ONE readback of four words per table.
+int hnswgpu_lsh_update(hnswgpu_index *idx, const int32_t *ids, const float *rows, int64_t m) {
+    HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
+    HG_REQUIRE(m >= 0, HNSWGPU_EINVAL, "m must be >= 0");
+    HG_REQUIRE(ids || m == 0, HNSWGPU_EINVAL, "ids is null");
+    HG_REQUIRE(rows || m == 0, HNSWGPU_EINVAL, "rows is null");
+    if (m == 0) return 0;  // nothing to update: nothing happens, whatever the handle holds
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_REQUIRE(idx->lsh_tables > 0, HNSWGPU_ESTATE, "index has no LSH tables (call hnswgpu_lsh_build / hnswgpu_set_lsh first)");
+    HG_REQUIRE(!idx->has_graph || idx->nparts > 0, HNSWGPU_ESTATE,
+               "the index holds an HNSW graph: its edges would stand for the old values of the rows");
+    HG_REQUIRE(idx->nparts == 0, HNSWGPU_ESTATE,
+               "the index holds a forest of HNSW sub-graphs: its edges would stand for the old values of the rows");
+    HG_REQUIRE(idx->nlist == 0 || idx->d_glistoff != nullptr, HNSWGPU_ESTATE,
+               "the index holds IVF lists: they would keep the old values of the rows");
+    HG_REQUIRE(idx->d_glistoff == nullptr, HNSWGPU_ESTATE,
+               "a shard of a larger IVF index (hnswgpu_set_ivf_shard) cannot be updated alone: its lists would keep the old values");
+    const int64_t n = idx->n;
+    std::vector<int32_t> uid, from;
+    int64_t at = -1, first = -1;
+    int verdict;
+    try {
+        verdict = ivf_update_slots(ids, m, n, uid, from, &at, &first);  // on the host array, before anything is enqueued
+    } catch (const std::bad_alloc &) {  // (its sorted copy of the ids)
+        set_error("host allocation failed");
+        return HNSWGPU_ENOMEM;
+    }
+    HG_REQUIRE(verdict != 1, HNSWGPU_EINVAL, "ids[%lld] = %d is not a row of the index (n = %lld)", (long long)at, ids[at], (long long)n);
+    HG_REQUIRE(verdict != 2, HNSWGPU_EINVAL, "ids[%lld] = %d is named twice (first at ids[%lld]): two values for one row have no winner",
+               (long long)at, ids[at], (long long)first);
+    HG_TRY(call.quiesce());
+    const int64_t ld = idx->ld, nb = static_cast<int64_t>(1) << idx->lsh_bits;
+    const int32_t tables = idx->lsh_tables;
+    LshStagedRows nw;  // failure-atomic, as hnswgpu_lsh_add: the handle's fields change only behind the last step
+    auto update = [&]() -> int {
+        const size_t nn = static_cast<size_t>(n), mm = static_cast<size_t>(m), T = static_cast<size_t>(tables);
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.base), sizeof(float) * nn * ld));
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.norms), sizeof(float) * nn));
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.lsh.codes), sizeof(uint16_t) * nn * T));
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.lsh.off), sizeof(int64_t) * T * (nb + 1)));
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.lsh.ids), sizeof(int32_t) * nn * T));
+        // scratch.  s_tile: the caller's rows as they came.  s_misc2: the staging matrix and its norms.  s_misc, 16-byte sections:
+        // [gate | count] zeroed, then seg, grouped, the slots' row ids and call positions, their new and their old codes
+        LshUpdateArgs a;
+        memset(&a, 0, sizeof(a));
+        a.n = n;
+        a.m = m;
+        a.ld = ld;
+        a.dim = idx->dim;
+        a.tables = tables;
+        a.bits = idx->lsh_bits;
+        auto sect = [](size_t bytes) { return (bytes + 15) / 16 * 16; };
+        const size_t o_count = sect(sizeof(unsigned long long) * kLshUpdateGate), o_seg = o_count + sect(sizeof(uint32_t) * 2 * T * nb),
+                     o_grouped = o_seg + sect(sizeof(uint32_t) * 2 * T * (nb + 1)), o_uid = o_grouped + sect(sizeof(int32_t) * 2 * T * mm),
+                     o_from = o_uid + sect(sizeof(int32_t) * mm), o_scodes = o_from + sect(sizeof(int32_t) * mm),
+                     o_ocodes = o_scodes + sect(sizeof(uint16_t) * mm * T), bytes = o_ocodes + sect(sizeof(uint16_t) * mm * T);
+        HG_TRY(idx->s_misc.ensure(bytes));
+        HG_TRY(idx->s_misc2.ensure(sect(sizeof(float) * mm * ld) + sizeof(float) * mm));
+        HG_TRY(idx->s_tile.ensure(sizeof(float) * mm * idx->dim));
+        char *s = idx->s_misc.as<char>();
+        HG_HIP(hipMemsetAsync(s, 0, o_seg, st));
+        HG_HIP(hipMemcpyAsync(s + o_uid, uid.data(), sizeof(int32_t) * mm, hipMemcpyHostToDevice, st));
+        HG_HIP(hipMemcpyAsync(s + o_from, from.data(), sizeof(int32_t) * mm, hipMemcpyHostToDevice, st));
+        HG_HIP(hipMemcpyAsync(idx->s_tile.p, rows, sizeof(float) * mm * idx->dim, hipMemcpyHostToDevice, st));
+        a.gate = reinterpret_cast<unsigned long long *>(s);
+        a.count = reinterpret_cast<uint32_t *>(s + o_count);
+        a.seg = reinterpret_cast<uint32_t *>(s + o_seg);
+        a.grouped = reinterpret_cast<int32_t *>(s + o_grouped);
+        a.uid = reinterpret_cast<const int32_t *>(s + o_uid);
+        a.from = reinterpret_cast<const int32_t *>(s + o_from);
+        uint16_t *scodes = reinterpret_cast<uint16_t *>(s + o_scodes);
+        a.scodes = scodes;
+        a.ocodes = reinterpret_cast<uint16_t *>(s + o_ocodes);
+        a.raw = idx->s_tile.as<float>();
+        a.stage = idx->s_misc2.as<float>();
+        float *snorms = reinterpret_cast<float *>(idx->s_misc2.as<char>() + sect(sizeof(float) * mm * ld));
+        a.snorms = snorms;
+        a.old_codes = idx->d_lsh_codes;
+        a.new_base = nw.base;
+        a.new_norms = nw.norms;
+        a.new_codes = nw.lsh.codes;
+        a.old_off = idx->d_lsh_off;
+        a.new_off = nw.lsh.off;
+        a.old_ids = idx->d_lsh_ids;
+        a.new_ids = nw.lsh.ids;
+        const unsigned slot_wgs = static_cast<unsigned>((m + kNWave - 1) / kNWave), Tu = static_cast<unsigned>(tables);
+        // ---- 1. the staging matrix in slot order, its norms (the kernel hnswgpu_create uses: the same bits) and its codes (the
+        // kernel and the planes that made the old ones)
+        hipLaunchKernelGGL(lsh_update_stage_kernel, dim3(slot_wgs), dim3(kWG), 0, st, a);
+        HG_HIP(hipGetLastError());
+        HG_TRY(launch_norms(idx->nch, a.stage, ld, m, snorms, st));
+        LshHashArgs h;
+        h.planes = idx->d_lsh_planes;
+        h.rows = a.stage;
+        h.ld = ld;
+        h.n = m;
+        h.tables = tables;
+        h.bits = idx->lsh_bits;
+        h.codes = scodes;
+        HG_TRY(launch_lsh_hash(idx->nch, h, st));
+        // ---- 2. the staged base, norms and codes: device copies of the old ones with the m rows scattered in
+        HG_HIP(hipMemcpyAsync(nw.base, idx->d_base, sizeof(float) * nn * ld, hipMemcpyDeviceToDevice, st));
+        HG_HIP(hipMemcpyAsync(nw.norms, idx->d_norms, sizeof(float) * nn, hipMemcpyDeviceToDevice, st));
+        HG_HIP(hipMemcpyAsync(nw.lsh.codes, idx->d_lsh_codes, sizeof(uint16_t) * nn * T, hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(lsh_update_scatter_kernel, dim3(slot_wgs), dim3(kWG), 0, st, a);
+        if (idx->d_qrows) HG_TRY(quantize_rows(idx, nw.base, n, &nw.qrows, &nw.qmeta, st));  // (as add: one pass over the new base)
+        // ---- 3. - 6. count, offsets, group, place: launch boundaries are the only dependences
+        const unsigned count_wgs = static_cast<unsigned>(std::min<int64_t>((m + kWG - 1) / kWG, 256));
+        hipLaunchKernelGGL(lsh_update_count_kernel, dim3(count_wgs, Tu, 2), dim3(kWG), 0, st, a);
+        hipLaunchKernelGGL(lsh_update_offsets_kernel, dim3(Tu), dim3(kWG), 0, st, a);
+        if (nb <= kLshAddLdsBuckets)
+            hipLaunchKernelGGL(lsh_update_group_kernel<true>, dim3(Tu, 2), dim3(kWave), 0, st, a);
+        else
+            hipLaunchKernelGGL(lsh_update_group_kernel<false>, dim3(Tu, 2), dim3(kWave), 0, st, a);
+        hipLaunchKernelGGL(lsh_update_keep_kernel, dim3(static_cast<unsigned>((n + kWG - 1) / kWG), Tu), dim3(kWG), 0, st, a);
+        hipLaunchKernelGGL(lsh_update_join_kernel, dim3(static_cast<unsigned>((m + kWG - 1) / kWG), Tu), dim3(kWG), 0, st, a);
+        HG_HIP(hipGetLastError());
+        // ---- the one readback
+        unsigned long long gate[kLshUpdateGate];
+        HG_HIP(hipMemcpyAsync(gate, a.gate, sizeof(gate), hipMemcpyDeviceToHost, st));
+        HG_HIP(hipStreamSynchronize(st));
+        for (int32_t t = 0; t < tables; t++) {
+            const long long total = static_cast<long long>(gate[LSH_UPD_TOTAL * kLshMaxTables + t]),
+                            left = static_cast<long long>(gate[LSH_UPD_LEFT * kLshMaxTables + t]),
+                            joined = static_cast<long long>(gate[LSH_UPD_JOINED * kLshMaxTables + t]),
+                            placed = static_cast<long long>(gate[LSH_UPD_PLACED * kLshMaxTables + t]);
+            HG_REQUIRE(total == n, HNSWGPU_EHIP, "the new buckets of table %d hold %lld rows, not %lld", t, total, (long long)n);
+            HG_REQUIRE(left == joined, HNSWGPU_EHIP, "%lld entries left the buckets of table %d and %lld joined them", left, t, joined);
+            HG_REQUIRE(placed == n, HNSWGPU_EHIP, "%lld entries of table %d were placed, not %lld", placed, t, (long long)n);
+        }
+        return 0;
+    };
+    const int rc = update();
+    if (rc != 0) {
+        (void)hipStreamSynchronize(st);  // (nothing of the chain is in flight when `nw` frees what it staged)
+        return rc;
+    }
+    nw.swap_into(idx, n);
     return call.close();
 }
 

@@ -702,6 +702,16 @@ class Index:
         self.n = int(n_after.value)
         return kept
 
+    def lsh_update(self, ids, rows):
+        """hnswgpu_lsh_update: row ``ids[i]`` takes the values ``rows[i]`` (row ids in any order, none named twice); n, every
+        row id and the planes stay.  Per table a row whose code is unchanged keeps its bucket; a row whose code changed leaves
+        its bucket and joins the new one at the place its row id gives it: the handle is what a fresh one over the new base is."""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        rows = _queries(rows, self.dim)
+        if len(rows) != len(ids):
+            raise ValueError("%d ids for %d rows" % (len(ids), len(rows)))
+        check(lib().hnswgpu_lsh_update(self._h, _p(ids), _p(rows), len(ids)))
+
     def lsh_search(self, Q, k, num_probes=6, probe_radius=2, take_main=None, take_flip=None, out=None):
         """hnswgpu_lsh_search (numpy queries) / hnswgpu_lsh_search_dev (a torch device tensor, torch's current stream):
         multi-probe search; the takes default to the reference's 2 k and k."""

@@ -6,8 +6,8 @@ of which the first 12 form the bucket id), hashes every row on the device and fi
 one-bit neighbours with the HIP bucket scan (hnswgpu_lsh_search).  Queries may be one vector or a batch.
 ``search_knn_filtered`` / ``search_batch_filtered`` / ``search_batch_filtered_each`` (not in the reference, whose index is served
 by the protocol's post-filter) carry a predicate on the ids into the bucket scan as an allow-mask (hnswgpu_lsh_search_filtered).
-``add_vectors`` / ``remove_vectors`` (not in the reference either) change a live index on the device (hnswgpu_lsh_add /
-hnswgpu_lsh_remove).
+``add_vectors`` / ``remove_vectors`` / ``update_vectors`` (not in the reference either) change a live index on the device
+(hnswgpu_lsh_add / hnswgpu_lsh_remove / hnswgpu_lsh_update).
 
 One difference, on purpose: the reference computes cosine whatever ``:distance-fn`` says (its ``query-norm`` is never nil,
 :157-166); here the index's metric decides, as in every other mirror.
@@ -103,6 +103,33 @@ def remove_vectors(index, ids):
         rows.extend(rows_of[i])
     kept = index.index.lsh_remove(np.asarray(rows, np.int32))
     index.ids = [index.ids[i] for i in kept]
+    return index
+
+
+def update_vectors(index, data):
+    """"Update existing vectors" (the open item of the reference's to-do list; its hybrid-lsh index is an immutable record):
+    ``data`` has the form ``build_index`` takes; the vector stored under each id takes the new values, is hashed again under
+    the index's hyperplanes and, in every table where its code changed, moves to its new bucket at the place its row gives it
+    (hnswgpu_lsh_update).  It keeps its id: ``index.ids`` is unchanged.  An unknown id raises KeyError, an id that names
+    several rows or appears twice in ``data`` raises ValueError, both before the device is touched.  Empty ``data`` does
+    nothing.  Returns the index."""
+    ids, rows = _split(data)
+    if not ids:
+        return index
+    rows_of = {}
+    for row, i in enumerate(index.ids):
+        rows_of.setdefault(i, []).append(row)
+    at, seen = [], set()
+    for i in ids:
+        if i not in rows_of:
+            raise KeyError(i)
+        if len(rows_of[i]) > 1:
+            raise ValueError("id %r names %d rows of the index" % (i, len(rows_of[i])))
+        if i in seen:
+            raise ValueError("id %r appears twice: two values for one vector have no winner" % (i,))
+        seen.add(i)
+        at.append(rows_of[i][0])
+    index.index.lsh_update(np.asarray(at, np.int32), rows)
     return index
 
 

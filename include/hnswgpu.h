@@ -384,7 +384,7 @@ int hnswgpu_ivf_remove(hnswgpu_index *idx, const int32_t *rows, int64_t m, int64
  * (hnswgpu_set_ivf_shard); the message names which; -1 for an id outside [0, n) and for an id named twice (two values for one
  * row have no defined winner), both checked on the host array before anything is enqueued; -1 for a new row with no nearest
  * centroid (NaN).
- * Out of scope: updates of an HNSW graph or of LSH tables, handles with both a graph and lists, forests, hnswgpu_group_*,
+ * Out of scope: updates of an HNSW graph (LSH tables take new values through hnswgpu_lsh_update), handles with both a graph and lists, forests, hnswgpu_group_*,
  * sharded.ShardedIVF and shards (rebuild those); a plain handle without lists; moving centroids or re-clustering after heavy
  * drift; in-place patching that avoids the per-call copy of the base and the list rows. */
 int hnswgpu_ivf_update(hnswgpu_index *idx, const int32_t *ids, const float *rows, int64_t m);
@@ -860,7 +860,56 @@ int hnswgpu_get_tuning(int32_t key, int64_t *value, int32_t *is_set);
  *     tables, and for one that also holds an HNSW graph, a forest, IVF lists or a shard's lists (those structures would keep
  *     the old numbering; the message names which); -1 for an id outside [0, n), checked on the host array before anything is
  *     enqueued.  The handle is untouched in every one of these cases.  Removing every row is legal: it leaves an empty handle
- *     with tables (planes, all-zero offsets), the state hnswgpu_lsh_add accepts, and that handle can be grown again. */
+ *     with tables (planes, all-zero offsets), the state hnswgpu_lsh_add accepts, and that handle can be grown again.
+ *
+ *   hnswgpu_lsh_update: rows of a LIVE handle with tables take new values under their ids ("Update existing vectors", the open
+ *     item of the reference's to-do list, README.md:172-176; its HybridIndex is an immutable record, so what is restated is
+ *     again its bucket order).  `ids` is m row ids of the handle in host memory, in any order; `rows` is m x dim float32 host
+ *     memory; row ids[i] takes the values rows[i].  n, every row id and the planes stay as they are -- unlike
+ *     hnswgpu_lsh_remove + hnswgpu_lsh_add, which hand the row a new id and shift every id above it.
+ *     - Equivalence.  After the call the handle holds, bit for bit, what hnswgpu_create(the base with the new values) +
+ *       hnswgpu_set_rejection_test(same mode) + hnswgpu_set_lsh(the same planes) holds: base and norms, the base-order int8
+ *       rows and their meta where the handle has them, and what hnswgpu_lsh_get exports -- codes [n][tables], per table
+ *       off[2^bits + 1] and ids[n], rows ascending inside a bucket -- hence the ids and distance bits of hnswgpu_lsh_search /
+ *       _dev / _filtered / _filtered_each, hnswgpu_exact_knn, hnswgpu_norms, hnswgpu_batch_distances, hnswgpu_lsh_hash, and the
+ *       bytes hnswgpu_save writes (still without the tables).
+ *     - Hashing.  lsh_hash_kernel hashes the new values under the handle's planes: a row's code does not depend on whether it
+ *       came by build, add or update.  NaN and zero rows are accepted as hnswgpu_lsh_add accepts them and hash as they would
+ *       on a fresh handle (dot >= 0.0 is false for NaN), so the equivalence holds for them.
+ *     - Stayers and movers, per table.  A row whose code in table t is unchanged keeps its bucket there.  A row whose code in
+ *       table t changed leaves its bucket of table t, which closes up, and joins its new bucket at the place its row id gives
+ *       it among the members -- a merge, not an append as in hnswgpu_ivf_update.  A row may move in some tables and stay in
+ *       others.  Updating rows to the values they already have changes nothing, bit for bit.
+ *     - Independence of the split.  An update changes no id and a bucket is ascending by row id, so different rows give the
+ *       same handle whether they are updated in one call, in any split of calls, or in any order of `ids` -- the opposite of
+ *       hnswgpu_ivf_update's caveat, the independence of hnswgpu_lsh_add and hnswgpu_lsh_remove.
+ *     - Everything happens on the device, in one chain on the handle's stream: the m ids (sorted on the host: slot s of the
+ *       call is the s-th smallest id) and the m rows go up once; norms by the kernel hnswgpu_create uses; the int8 rows made as
+ *       hnswgpu_lsh_add makes them, over the new base; no code or bucket id is read back; every destination is a function of
+ *       the old arrays and the call alone -- for row r in its new bucket b of table t,
+ *       new_off[t][b] + #old members of b below r - #leavers of b below r + #joiners of b below r --, never of the order
+ *       atomics arrive in.
+ *     - Failure-atomic, like the other mutations: nothing is changed in place, every new array is staged under the handle's
+ *       lock with its streams quiesced, and the handle takes them over only after ONE small readback of a gate of counts -- per
+ *       table: the last new offset == n, entries that left == entries that joined, entries placed == n (HNSWGPU_EHIP
+ *       otherwise).  On any failure the staged arrays are freed and the handle is what it was.  Searches from other threads
+ *       wait and see the old or the new index.  Peak memory: the old plus the new arrays for the length of the call.
+ *     - Cost: one device copy of the base, the codes and the bucket ids (O(n x tables) entries) per CALL, whatever m is, plus
+ *       O(m x tables x log) searches and about m / 64 dependent steps of one wave per table -- update rows in batches.
+ *       Measured on one MI355X (profiles/lsh_update.txt: 31,173 x 768 cosine, 8 tables x 12 bits): 0.48 / 0.65 / 1.54 ms for
+ *       m = 1 / 1,024 / 8,192 scattered rows against 2.29 / 2.29 / 2.27 ms for the rebuild over the base with the new values
+ *       from host memory -- faster at every m measured, by less the more rows a call carries (0.21, 0.29, 0.68 of the
+ *       rebuild) -- and against 0.88 / 1.03 / 1.76 ms for hnswgpu_lsh_remove + hnswgpu_lsh_add of the same rows, which loses
+ *       the ids.  The kernels and device copies are 0.23 / 0.26 / 0.45 ms of a call (the serial walk that groups the movers
+ *       is 0.005 / 0.024 / 0.19 ms of that, the placement of the entries that stay 0.05 ms at every m); the rest is the
+ *       upload of the rows, allocating and freeing the staged arrays and the readback.
+ *     Returns, checked in this order, the handle untouched in every case: -1 for a null handle (before m == 0 and before any
+ *     HIP call), for m < 0, and for null ids or rows with m > 0; 0 for m == 0 (nothing happens); -3 for a handle without
+ *     tables; -3 for a handle that also holds an HNSW graph, a forest, IVF lists or a shard's lists (their copies of the row
+ *     would go stale; the message names which); -1 for an id outside [0, n) and for an id named twice (two values for one row
+ *     have no defined winner), both checked on the host array before anything is enqueued.
+ *     Out of scope: HNSW updates; handles that hold tables and another structure; groups, shards and forests; the tables in
+ *     the index file; in-place patching that avoids the per-call copy of the base. */
 int hnswgpu_lsh_build(hnswgpu_index *idx, int32_t tables, int32_t bits, int32_t proj_dim, int64_t seed);
 int hnswgpu_set_lsh(hnswgpu_index *idx, const float *planes, int32_t tables, int32_t bits);
 int hnswgpu_lsh_sizes(hnswgpu_index *idx, int32_t *tables, int32_t *bits);
@@ -868,6 +917,7 @@ int hnswgpu_lsh_get(hnswgpu_index *idx, float *planes, uint16_t *codes, int64_t 
 int hnswgpu_lsh_hash(hnswgpu_index *idx, const float *Q, int32_t nq, uint16_t *codes);
 int hnswgpu_lsh_add(hnswgpu_index *idx, const float *rows, int64_t m);
 int hnswgpu_lsh_remove(hnswgpu_index *idx, const int32_t *rows, int64_t m, int64_t *n_after);
+int hnswgpu_lsh_update(hnswgpu_index *idx, const int32_t *ids, const float *rows, int64_t m);
 int hnswgpu_lsh_search(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t num_probes, int32_t probe_radius,
                        int32_t take_main, int32_t take_flip, int32_t *out_ids, float *out_dist);
 int hnswgpu_lsh_search_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t num_probes,
