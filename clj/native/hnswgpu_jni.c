@@ -436,3 +436,23 @@ JNIEXPORT jlong JNICALL Java_hnsw_gpu_Native_hnswRemove(JNIEnv *env, jclass c, j
     if (rc != 0 && rc != HNSWGPU_ENOMEM) throw_last(env);
     return rc != 0 ? (jlong)rc : (jlong)n_after;
 }
+
+/* rows of a live HNSW graph take new values (hnswgpu_hnsw_update): `ids` holds m row ids in any order, none named twice; `rows`
+ * holds m x dim floats, row ids[i] takes rows[i]; n, the ids and every row's level stay: the rows are unlinked as rows that leave
+ * are and inserted again, ascending, as hnswgpu_hnsw_add inserts rows.  Returns 0, or the negative error code (the exception is
+ * pending).  Unverified like the rest of this file: no JVM where the library is built and tested. */
+JNIEXPORT jint JNICALL Java_hnsw_gpu_Native_hnswUpdate(JNIEnv *env, jclass c, jlong h, jintArray ids, jfloatArray rows, jlong m, jint dim,
+                                                       jint efConstruction) {
+    if (!ids || !rows) return throw_iae(env, "hnswUpdate: null array");
+    if (m < 0 || m > (jlong)(*env)->GetArrayLength(env, ids)) return throw_iae(env, "hnswUpdate: m outside the id array");
+    if (dim < 1 || m > (jlong)(*env)->GetArrayLength(env, rows) / dim) return throw_iae(env, "hnswUpdate: fewer than m x dim floats");
+    jint *pi = (*env)->GetIntArrayElements(env, ids, NULL);
+    jfloat *pr = pi ? (*env)->GetFloatArrayElements(env, rows, NULL) : NULL;
+    int rc = pi && pr ? hnswgpu_hnsw_update((hnswgpu_index *)(intptr_t)h, (const int32_t *)pi, (const float *)pr, (int64_t)m,
+                                            (int32_t)efConstruction)
+                      : HNSWGPU_ENOMEM; /* OutOfMemoryError is pending */
+    if (pr) (*env)->ReleaseFloatArrayElements(env, rows, pr, JNI_ABORT);
+    if (pi) (*env)->ReleaseIntArrayElements(env, ids, pi, JNI_ABORT);
+    if (rc != 0 && rc != HNSWGPU_ENOMEM) throw_last(env);
+    return rc;
+}

@@ -18,6 +18,7 @@
      (top-k-distances index query-vec k)                             ; simd-optimized/top-k-distances
      (add-vector! index new-data)                                    ; hnsw.api/add-vector!, insert-single on a live index
      (remove-vectors! index ids)                                     ; ... and leave the graph again: hnswgpu_hnsw_remove
+     (update-vectors! index new-data)                                ; ... and take new values under their ids: hnswgpu_hnsw_update
      (add-ivf-vectors! index new-data)                               ; the same for a live IVF-FLAT index: hnswgpu_ivf_add
      (remove-ivf-vectors! index ids)                                 ; ... and leave it: hnswgpu_ivf_remove
      (update-ivf-vectors! index new-data)                            ; ... and take new values under their ids: hnswgpu_ivf_update
@@ -219,6 +220,32 @@
             (let [kept (vec (remove gone (:ids idx)))]
               (assert (= (count kept) (.getAtIndex n-after L 0)))
               (assoc idx :ids kept))))))))
+
+(def ^:private h-hnswupdate (delay (fn-handle "hnswgpu_hnsw_update" (FunctionDescriptor/of I (into-array [P P P L I])))))
+
+(defn update-vectors!
+  "\"Update existing vectors\" (the open item of the reference's to-do list; the rule is the engine's own, hnswgpu_hnsw_update) for
+   a live HNSW GpuIndex: new-data is a seq of [id ^doubles vector]; the vector stored under each id takes the new values and keeps
+   its id and its level.  It is unlinked as remove-vectors! unlinks a vector that leaves -- nothing is renumbered -- and inserted
+   again as add-vector! inserts one, with :ef-construction (default 200).  The result depends on how an update is split over calls,
+   and a vector updated to the values it has is still linked anew.  An unknown id, an id that names several rows and an id given
+   twice throw before the device is touched.  Returns the index (its ids are unchanged).  One call per batch is the efficient
+   shape: a call copies the rows once, whatever it updates.  Unverified like the rest of this namespace: no JVM where the library
+   is built."
+  [idx new-data & {:keys [ef-construction] :or {ef-construction 200}}]
+  (let [rows-of (reduce (fn [m [i id]] (update m id (fnil conj []) i)) {} (map-indexed vector (:ids idx)))
+        ids (mapv first new-data)]
+    (doseq [id ids]
+      (when-not (contains? rows-of id) (throw (ex-info "update-vectors!: unknown id" {:id id})))
+      (when (> (count (rows-of id)) 1) (throw (ex-info "update-vectors!: the id names several rows" {:id id}))))
+    (when-not (or (empty? ids) (apply distinct? ids))
+      (throw (ex-info "update-vectors!: an id is given twice" {})))
+    (when (seq ids)
+      (with-open [arena (Arena/ofConfined)]
+        (check (.invokeWithArguments ^MethodHandle @h-hnswupdate
+                                     [(:handle idx) (ints-of arena (mapv (comp first rows-of) ids))
+                                      (floats-of arena (mapv second new-data) (:dim idx)) (long (count ids)) (int ef-construction)]))))
+    idx))
 
 ;; ---- hybrid LSH (hnsw.ann.hash.hybrid-lsh): hnswgpu_lsh_build / hnswgpu_lsh_search ----
 (def ^:private h-lshbuild  (delay (fn-handle "hnswgpu_lsh_build" (FunctionDescriptor/of I (into-array [P I I I L])))))

@@ -53,6 +53,7 @@ _SIGS = {
     "hnswgpu_hnsw_build_ex": ["p", "i32", "i32", "i64", "i32"],
     "hnswgpu_hnsw_add": ["p", "p", "i64", "i32", "i64"],
     "hnswgpu_hnsw_remove": ["p", "p", "i64", "p"],
+    "hnswgpu_hnsw_update": ["p", "p", "p", "i64", "i32"],
     "hnswgpu_graph_sizes": ["p", "p", "p", "p", "p", "p"],
     "hnswgpu_get_graph": ["p", "p", "p", "p", "p"],
     "hnswgpu_hnsw_search": ["p", "p", "i32", "i32", "i32", "p", "p", "p"],

@@ -15,6 +15,8 @@
 #include "build_kernels.hpp"
 #include "engine.hpp"
 #include "hnsw_remove_kernels.hpp"  // the graph side of hnswgpu_hnsw_remove
+#include "hnsw_update_kernels.hpp"  // the unlink of hnswgpu_hnsw_update: the same repair, nothing renumbered
+#include "ivf_update_ids.hpp"       // the id check every update shares
 #include "lsh_remove_ids.hpp"       // the id check every removal shares
 #include "javarandom.hpp"
 #include "order_kernels.hpp"  // OrderArgs, for hnsw_launch_resources
@@ -1604,6 +1606,90 @@ static int launch_remove_dist(hnswgpu_index *idx, const HnswRemoveArgs &a, hipSt
     return 0;
 }
 
+// The scratch of a list repair (hnswgpu_hnsw_remove, hnswgpu_hnsw_update) in s_misc, 16-byte sections: [gate | keep | cnt] zeroed,
+// [owner] -1, then word_rank, the call's ids (uploaded from `rows`), the task tables.  a.r.n0 / m / W, a.blocks0 and a.nlists are set.
+static int hnsw_repair_scratch(hnswgpu_index *idx, HnswRemoveArgs &a, const int32_t *rows, hipStream_t st) {
+    auto sect = [](size_t bytes) { return (bytes + 15) / 16 * 16; };
+    const size_t o_keep = sect(sizeof(int64_t) * kLshRemoveGate), o_cnt = o_keep + sect(sizeof(uint32_t) * a.r.W),
+                 o_owner = o_cnt + sect(sizeof(uint32_t) * a.nlists), o_rank = o_owner + sect(sizeof(int32_t) * a.blocks0),
+                 o_ids = o_rank + sect(sizeof(uint32_t) * a.r.W), o_tlist = o_ids + sect(sizeof(int32_t) * a.r.m),
+                 o_tm = o_tlist + sect(sizeof(int32_t) * a.nlists), o_toff = o_tm + sect(sizeof(int32_t) * a.nlists),
+                 bytes = o_toff + sect(sizeof(int64_t) * (a.nlists + 1));
+    HG_TRY(idx->s_misc.ensure(bytes));
+    char *s = idx->s_misc.as<char>();
+    HG_HIP(hipMemsetAsync(s, 0, o_owner, st));
+    if (a.blocks0 > 0) HG_HIP(hipMemsetAsync(s + o_owner, 0xff, sizeof(int32_t) * a.blocks0, st));
+    HG_HIP(hipMemcpyAsync(s + o_ids, rows, sizeof(int32_t) * static_cast<size_t>(a.r.m), hipMemcpyHostToDevice, st));
+    a.r.gate = reinterpret_cast<int64_t *>(s);
+    a.r.keep = reinterpret_cast<uint32_t *>(s + o_keep);
+    a.cnt = reinterpret_cast<uint32_t *>(s + o_cnt);
+    a.owner = reinterpret_cast<int32_t *>(s + o_owner);
+    a.r.word_rank = reinterpret_cast<uint32_t *>(s + o_rank);
+    a.r.rows = reinterpret_cast<const int32_t *>(s + o_ids);
+    a.task_list = reinterpret_cast<int32_t *>(s + o_tlist);
+    a.task_m = reinterpret_cast<int32_t *>(s + o_tm);
+    a.task_off = reinterpret_cast<int64_t *>(s + o_toff);
+    return 0;
+}
+
+// The graph side of a list repair behind the mask and its rank scan: the owners of the upper blocks, the list pass, the scan of
+// the candidate counts -- its two totals are read back to size the candidate arrays (no cap to overflow) -- then gather,
+// distances over the handle's present rows (the candidates are old ids), the per-task sort, the selection of the handle's
+// builder and the scatter.  RENUM: hnsw_remove_kernels.hpp.  a.ntasks / a.ncand are set on return.
+template <bool RENUM>
+static int hnsw_repair_chain(hnswgpu_index *idx, HnswRemoveArgs &a, hipStream_t st) {
+    auto sect = [](size_t bytes) { return (bytes + 15) / 16 * 16; };
+    const int M0 = a.M0;
+    const unsigned list_wgs = static_cast<unsigned>((a.nlists + kNWave - 1) / kNWave);
+    hipLaunchKernelGGL(hnsw_remove_owner_kernel, dim3(static_cast<unsigned>((a.r.n0 + kWG - 1) / kWG)), dim3(kWG), 0, st, a);
+    hipLaunchKernelGGL(hnsw_remove_lists_kernel<RENUM>, dim3(list_wgs), dim3(kWG), 0, st, a);
+    hipLaunchKernelGGL(hnsw_remove_scan_kernel, dim3(1), dim3(kWG), 0, st, a);
+    HG_HIP(hipGetLastError());
+    int64_t totals[2] = {0, 0};
+    HG_HIP(hipMemcpyAsync(totals, a.r.gate + kHnswRemoveGateCand, sizeof(totals), hipMemcpyDeviceToHost, st));
+    HG_HIP(hipStreamSynchronize(st));
+    a.ncand = totals[0];
+    a.ntasks = totals[1];
+    HG_REQUIRE(a.ntasks >= 0 && a.ntasks <= a.nlists && a.ncand >= a.ntasks &&
+                   a.ncand <= a.ntasks * static_cast<int64_t>(kSelMaxCand) && a.ntasks < 2147483647LL,
+               HNSWGPU_EHIP, "the candidate scan counts %lld candidates of %lld lists", (long long)a.ncand, (long long)a.ntasks);
+    if (a.ntasks == 0) return 0;
+    const bool heuristic = (idx->build_flags & HNSWGPU_BUILD_HEURISTIC) != 0;
+    HG_TRY(idx->s_ids.ensure(sizeof(int32_t) * static_cast<size_t>(a.ncand)));
+    HG_TRY(idx->s_outd.ensure(sizeof(float) * static_cast<size_t>(a.ncand)));
+    a.cand_id = idx->s_ids.as<int32_t>();
+    a.cand_d = idx->s_outd.as<float>();
+    const unsigned task_wgs = static_cast<unsigned>((a.ntasks + kNWave - 1) / kNWave);
+    hipLaunchKernelGGL(hnsw_remove_gather_kernel, dim3(task_wgs), dim3(kWG), 0, st, a);
+    HG_HIP(hipGetLastError());
+    HG_TRY(launch_remove_dist(idx, a, st));  // (the handle still holds the old rows: the candidates are old ids)
+    hipLaunchKernelGGL(hnsw_remove_sort_kernel, dim3(static_cast<unsigned>(a.ntasks)), dim3(kWG), 0, st, a);
+    HG_HIP(hipGetLastError());
+    if (heuristic) {
+        const size_t slots = static_cast<size_t>(a.ntasks) * M0;
+        const size_t o_d = sect(sizeof(int32_t) * slots), o_c = o_d + sect(sizeof(float) * slots);
+        HG_TRY(idx->s_misc2.ensure(o_c + sect(sizeof(int32_t) * static_cast<size_t>(a.ntasks))));
+        char *h = idx->s_misc2.as<char>();
+        HeurArgs ha;
+        memset(&ha, 0, sizeof(ha));
+        ha.ntasks = static_cast<int32_t>(a.ntasks);
+        ha.off = a.task_off;
+        ha.cand_id = a.cand_id;
+        ha.cand_d = a.cand_d;
+        ha.m = a.task_m;
+        ha.extend = 0;
+        ha.out_stride = M0;
+        ha.out_id = reinterpret_cast<int32_t *>(h);
+        ha.out_d = reinterpret_cast<float *>(h + o_d);
+        ha.out_cnt = reinterpret_cast<int32_t *>(h + o_c);
+        HG_TRY(launch_heur(idx, ha, st));
+        a.sel = ha.out_id;
+    }
+    hipLaunchKernelGGL(hnsw_remove_scatter_kernel<RENUM>, dim3(task_wgs), dim3(kWG), 0, st, a);
+    HG_HIP(hipGetLastError());
+    return 0;
+}
+
 // A pending reverse edge of graph.clj's builder: `id` wants into the FULL list of `target` on layer `lc`.
 struct PendingEdge {
     int32_t target, lc, id;
@@ -1863,14 +1949,19 @@ struct Pruner {
 // get-neighbors-heuristic (graph.clj:162-198) on the device (heuristic_select_kernel) instead of the m closest, over-full
 // lists re-selected the same way (prune-connections, graph.clj:208-232); SYMMETRIC = a dropped edge leaves both lists
 // (:226-231); EXTEND = extend-candidates? for the new node's own selection (:191-195).
-static int insert_batches(hnswgpu_index *idx, HostGraph &g, int64_t done, int ef, hipStream_t st, int flags) {
+// `ids` (hnswgpu_hnsw_update): the rows to insert are ids[0, count) in that order instead of the range [done, g.n) -- rows of
+// g that no list names and whose own lists are empty; `done` then is the number of rows the graph links when the call begins
+// (the batch size rule reads it) and grows by a batch's rows as before.  Null: the range.
+static int insert_batches(hnswgpu_index *idx, HostGraph &g, int64_t done, int ef, hipStream_t st, int flags, const int32_t *ids = nullptr,
+                          int64_t count = 0) {
     const bool seq = flags & HNSWGPU_BUILD_SEQUENTIAL, heur = flags & HNSWGPU_BUILD_HEURISTIC;
     const bool sym = heur && (flags & HNSWGPU_BUILD_SYMMETRIC), extend = flags & HNSWGPU_BUILD_EXTEND;
-    const int64_t n = g.n;
+    const int64_t first = done, n = ids ? done + count : g.n;  // positions [done, n) of the insertion order
+    auto row_of = [ids, first](int64_t pos) { return ids ? ids[pos - first] : static_cast<int32_t>(pos); };
     const int M0 = g.M0;
-    const int64_t blocks = g.up_off[n];
+    const int64_t blocks = g.up_off[g.n];
     int maxlv = 1;
-    for (int64_t i = done; i < n; i++) maxlv = std::max(maxlv, g.levels[i]);
+    for (int64_t i = done; i < n; i++) maxlv = std::max(maxlv, g.levels[row_of(i)]);
     // scratch sizing; the batch actually used grows with the graph (see below)
     const int64_t maxB = seq ? 1 : std::max<int64_t>(1, std::min<int64_t>(16384, tune(HNSWGPU_TUNE_BUILD_BATCH, 16384)));
     const int kk = heur ? ef : M0;         // layer-0 candidates a search hands back: all of them for the heuristic
@@ -1899,7 +1990,7 @@ static int insert_batches(hnswgpu_index *idx, HostGraph &g, int64_t done, int ef
     }
     std::vector<int32_t> h_ids(maxB * M0), h_up(maxB * maxlv), h_qrows(maxB), h_qlev(maxB);
     std::vector<float> h_d(maxB * M0), h_upd(maxB * maxlv);
-    g.flag0.assign(n, 0);
+    g.flag0.assign(g.n, 0);
     g.flagu.assign(std::max<int64_t>(blocks, 1), 0);
     // linker threads: at most 16 (a GPU box's CPU share per GPU), HNSWGPU_BUILD_THREADS overrides (1 = sequential)
     int nthreads = static_cast<int>(std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency())));
@@ -1923,8 +2014,8 @@ static int insert_batches(hnswgpu_index *idx, HostGraph &g, int64_t done, int ef
         HG_TRY(upload_dirty(idx, g, st, pin, pool));
         if (timing) t_up += now() - tb0;
         for (int64_t b = 0; b < B; b++) {
-            h_qrows[b] = static_cast<int32_t>(done + b);
-            h_qlev[b] = g.levels[done + b];
+            h_qrows[b] = row_of(done + b);
+            h_qlev[b] = g.levels[h_qrows[b]];
         }
         HG_HIP(hipMemcpyAsync(d_qrows, h_qrows.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, st));
         HG_HIP(hipMemcpyAsync(d_qlev, h_qlev.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, st));
@@ -1982,7 +2073,7 @@ static int insert_batches(hnswgpu_index *idx, HostGraph &g, int64_t done, int ef
         const int take = std::min(M0, ef);
         // (A) own lists of node done + b; (B) reverse edges into the lists of nodes owned by thread `me` (of `nt`)
         auto link_own = [&](int64_t b, HostGraph::Dirty &dirty) {
-            const int32_t id = static_cast<int32_t>(done + b);
+            const int32_t id = row_of(done + b);
             const int L = g.levels[id];
             for (int lc = std::min(L, top_at_start); lc >= 1; lc--) {
                 const int32_t nb = h_up[b * maxlv + (lc - 1)];
@@ -2000,7 +2091,7 @@ static int insert_batches(hnswgpu_index *idx, HostGraph &g, int64_t done, int ef
         // the batch's reverse edges are numbered in the sequential loop's order: node by node, layers top down,
         // a layer's links in selection order
         auto link_reverse = [&](int64_t b, int me, int nt, HostGraph::Dirty &dirty, std::vector<PendingEdge> &pq) {
-            const int32_t id = static_cast<int32_t>(done + b);
+            const int32_t id = row_of(done + b);
             const int L = g.levels[id];
             int64_t sq = b * (maxlv + M0);
             auto rev = [&](int32_t nb, int lc, float dist) {
@@ -2055,7 +2146,7 @@ static int insert_batches(hnswgpu_index *idx, HostGraph &g, int64_t done, int ef
             dd.du.clear();
         }
         for (int64_t b = 0; b < B; b++) {  // :271-273
-            const int32_t id = static_cast<int32_t>(done + b);
+            const int32_t id = row_of(done + b);
             if (g.levels[id] > g.top) {
                 g.entry = id;
                 g.top = g.levels[id];
@@ -2075,6 +2166,50 @@ static int insert_batches(hnswgpu_index *idx, HostGraph &g, int64_t done, int ef
                         "removed from the other side)\n",
                 static_cast<long long>(nbatch), t_gpu, t_up, t_link, t_prune, static_cast<long long>(pruner.n_tasks),
                 static_cast<long long>(pruner.n_removed));
+    return 0;
+}
+
+// A graph that stands on the device -- the handle's d_l0 / d_upadj over rows [0, n0), mirrored by h_l0 / h_upadj / h_upoff --
+// becomes the lists of a HostGraph `g` that is sized already (g.n >= n0, the same up_off below n0): the edges, and their
+// distances, which the reference's pruning sorts by (ultra_fast.clj:279-299), recomputed on the device by the traversal's own
+// arithmetic over the handle's base rows.  Step 2 of hnswgpu_hnsw_add and of hnswgpu_hnsw_update.
+static int adopt_graph(hnswgpu_index *idx, HostGraph &g, int64_t n0, const int32_t *h_l0, const int32_t *h_upadj, const int64_t *h_upoff,
+                       hipStream_t st) {
+    const int M = g.M, M0 = g.M0;
+    const int64_t blocks0 = h_upoff[n0];
+    std::vector<float> d0(static_cast<size_t>(n0) * M0), du(static_cast<size_t>(std::max<int64_t>(blocks0, 1)) * M);
+    std::vector<int32_t> owner(static_cast<size_t>(std::max<int64_t>(blocks0, 1)));
+    for (int64_t i = 0; i < n0; i++)
+        for (int64_t b = h_upoff[i]; b < h_upoff[i + 1]; b++) owner[b] = static_cast<int32_t>(i);
+    HG_TRY(idx->s_outd.ensure(sizeof(float) * (d0.size() + du.size())));
+    HG_TRY(idx->s_ids.ensure(sizeof(int32_t) * owner.size()));
+    float *dd0 = idx->s_outd.as<float>(), *ddu = dd0 + d0.size();
+    HG_HIP(hipMemcpyAsync(idx->s_ids.p, owner.data(), sizeof(int32_t) * owner.size(), hipMemcpyHostToDevice, st));
+    HG_TRY(launch_edge_dist(idx, nullptr, idx->d_l0, M0, n0, dd0, st));
+    HG_TRY(launch_edge_dist(idx, idx->s_ids.as<int32_t>(), idx->d_upadj, M, blocks0, ddu, st));
+    if (n0 > 0) HG_HIP(hipMemcpyAsync(d0.data(), dd0, sizeof(float) * d0.size(), hipMemcpyDeviceToHost, st));
+    if (blocks0 > 0) HG_HIP(hipMemcpyAsync(du.data(), ddu, sizeof(float) * static_cast<size_t>(blocks0) * M, hipMemcpyDeviceToHost, st));
+    HG_HIP(hipStreamSynchronize(st));
+    // a full list whose distances ascend IS the pruned order (prune-connections-ultra's stable sort is the identity on
+    // it); any other list is still in insertion order and gets its first sort when it overflows
+    auto adopt = [](const int32_t *src, const float *dsrc, int width, int32_t *dst, float *ddst, int32_t &cnt, uint8_t &srt) {
+        int c = 0;
+        while (c < width && src[c] >= 0) c++;
+        bool asc = true;
+        for (int j = 0; j < c; j++) {
+            dst[j] = src[j];
+            ddst[j] = dsrc[j];
+            if (j > 0 && dsrc[j] < dsrc[j - 1]) asc = false;
+        }
+        cnt = c;
+        srt = (c == width && asc) ? 1 : 0;
+    };
+    for (int64_t i = 0; i < n0; i++)
+        adopt(&h_l0[static_cast<size_t>(i) * M0], &d0[static_cast<size_t>(i) * M0], M0, &g.l0[static_cast<size_t>(i) * (M0 + 1)],
+              &g.l0_d[static_cast<size_t>(i) * (M0 + 1)], g.l0_cnt[i], g.sorted0[i]);
+    for (int64_t b = 0; b < blocks0; b++)
+        adopt(&h_upadj[static_cast<size_t>(b) * M], &du[static_cast<size_t>(b) * M], M, &g.up[static_cast<size_t>(b) * (M + 1)],
+              &g.up_d[static_cast<size_t>(b) * (M + 1)], g.up_cnt[b], g.sortedu[b]);
     return 0;
 }
 
@@ -2324,42 +2459,7 @@ int hnswgpu_hnsw_add(hnswgpu_index *idx, const float *rows, int64_t m, int32_t e
         g.up_cnt.assign(std::max<int64_t>(blocks1, 1), 0);
         g.sorted0.assign(n1, 0);
         g.sortedu.assign(std::max<int64_t>(blocks1, 1), 0);
-        {
-            // edge distances of the installed graph, by the traversal's arithmetic (rows [0, n0) of the old base: still in place)
-            std::vector<float> d0(static_cast<size_t>(n0) * M0), du(static_cast<size_t>(std::max<int64_t>(blocks0, 1)) * M);
-            std::vector<int32_t> owner(static_cast<size_t>(std::max<int64_t>(blocks0, 1)));
-            for (int64_t i = 0; i < n0; i++)
-                for (int64_t b = idx->h_upoff[i]; b < idx->h_upoff[i + 1]; b++) owner[b] = static_cast<int32_t>(i);
-            HG_TRY(idx->s_outd.ensure(sizeof(float) * (d0.size() + du.size())));
-            HG_TRY(idx->s_ids.ensure(sizeof(int32_t) * owner.size()));
-            float *dd0 = idx->s_outd.as<float>(), *ddu = dd0 + d0.size();
-            HG_HIP(hipMemcpyAsync(idx->s_ids.p, owner.data(), sizeof(int32_t) * owner.size(), hipMemcpyHostToDevice, st));
-            HG_TRY(launch_edge_dist(idx, nullptr, idx->d_l0, M0, n0, dd0, st));
-            HG_TRY(launch_edge_dist(idx, idx->s_ids.as<int32_t>(), idx->d_upadj, M, blocks0, ddu, st));
-            if (n0 > 0) HG_HIP(hipMemcpyAsync(d0.data(), dd0, sizeof(float) * d0.size(), hipMemcpyDeviceToHost, st));
-            if (blocks0 > 0) HG_HIP(hipMemcpyAsync(du.data(), ddu, sizeof(float) * static_cast<size_t>(blocks0) * M, hipMemcpyDeviceToHost, st));
-            HG_HIP(hipStreamSynchronize(st));
-            // a full list whose distances ascend IS the pruned order (prune-connections-ultra's stable sort is the identity on
-            // it); any other list is still in insertion order and gets its first sort when it overflows
-            auto adopt = [](const int32_t *src, const float *dsrc, int width, int32_t *dst, float *ddst, int32_t &cnt, uint8_t &srt) {
-                int c = 0;
-                while (c < width && src[c] >= 0) c++;
-                bool asc = true;
-                for (int j = 0; j < c; j++) {
-                    dst[j] = src[j];
-                    ddst[j] = dsrc[j];
-                    if (j > 0 && dsrc[j] < dsrc[j - 1]) asc = false;
-                }
-                cnt = c;
-                srt = (c == width && asc) ? 1 : 0;
-            };
-            for (int64_t i = 0; i < n0; i++)
-                adopt(&idx->h_l0[static_cast<size_t>(i) * M0], &d0[static_cast<size_t>(i) * M0], M0, &g.l0[static_cast<size_t>(i) * (M0 + 1)],
-                      &g.l0_d[static_cast<size_t>(i) * (M0 + 1)], g.l0_cnt[i], g.sorted0[i]);
-            for (int64_t b = 0; b < blocks0; b++)
-                adopt(&idx->h_upadj[static_cast<size_t>(b) * M], &du[static_cast<size_t>(b) * M], M, &g.up[static_cast<size_t>(b) * (M + 1)],
-                      &g.up_d[static_cast<size_t>(b) * (M + 1)], g.up_cnt[b], g.sortedu[b]);
-        }
+        HG_TRY(adopt_graph(idx, g, n0, idx->h_l0.data(), idx->h_upadj.data(), idx->h_upoff.data(), st));  // (the old base: still in place)
         g.entry = idx->entry;
         g.top = idx->max_level;
         // ---- 3. the device graph grows: old rows copied, new rows empty (staged)
@@ -2500,7 +2600,6 @@ int hnswgpu_hnsw_remove(hnswgpu_index *idx, const int32_t *rows, int64_t m, int6
         HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.upadj), sizeof(int32_t) * ub1 * M));
         HG_HIP(hipMemsetAsync(nw.l0, 0xff, sizeof(int32_t) * rows1 * M0, st));
         HG_HIP(hipMemsetAsync(nw.upadj, 0xff, sizeof(int32_t) * ub1 * M, st));
-        // scratch, 16-byte sections: [gate | keep | cnt] zeroed, [owner] -1, then word_rank, the call's ids, the task tables
         HnswRemoveArgs a;
         memset(&a, 0, sizeof(a));
         a.r.n0 = n0;
@@ -2513,26 +2612,7 @@ int hnswgpu_hnsw_remove(hnswgpu_index *idx, const int32_t *rows, int64_t m, int6
         a.blocks0 = blocks0;
         a.blocks1 = blocks1;
         a.nlists = n0 + blocks0;
-        auto sect = [](size_t bytes) { return (bytes + 15) / 16 * 16; };
-        const size_t o_keep = sect(sizeof(int64_t) * kLshRemoveGate), o_cnt = o_keep + sect(sizeof(uint32_t) * a.r.W),
-                     o_owner = o_cnt + sect(sizeof(uint32_t) * a.nlists), o_rank = o_owner + sect(sizeof(int32_t) * blocks0),
-                     o_ids = o_rank + sect(sizeof(uint32_t) * a.r.W), o_tlist = o_ids + sect(sizeof(int32_t) * m),
-                     o_tm = o_tlist + sect(sizeof(int32_t) * a.nlists), o_toff = o_tm + sect(sizeof(int32_t) * a.nlists),
-                     bytes = o_toff + sect(sizeof(int64_t) * (a.nlists + 1));
-        HG_TRY(idx->s_misc.ensure(bytes));
-        char *s = idx->s_misc.as<char>();
-        HG_HIP(hipMemsetAsync(s, 0, o_owner, st));
-        if (blocks0 > 0) HG_HIP(hipMemsetAsync(s + o_owner, 0xff, sizeof(int32_t) * blocks0, st));
-        HG_HIP(hipMemcpyAsync(s + o_ids, rows, sizeof(int32_t) * static_cast<size_t>(m), hipMemcpyHostToDevice, st));
-        a.r.gate = reinterpret_cast<int64_t *>(s);
-        a.r.keep = reinterpret_cast<uint32_t *>(s + o_keep);
-        a.cnt = reinterpret_cast<uint32_t *>(s + o_cnt);
-        a.owner = reinterpret_cast<int32_t *>(s + o_owner);
-        a.r.word_rank = reinterpret_cast<uint32_t *>(s + o_rank);
-        a.r.rows = reinterpret_cast<const int32_t *>(s + o_ids);
-        a.task_list = reinterpret_cast<int32_t *>(s + o_tlist);
-        a.task_m = reinterpret_cast<int32_t *>(s + o_tm);
-        a.task_off = reinterpret_cast<int64_t *>(s + o_toff);
+        HG_TRY(hnsw_repair_scratch(idx, a, rows, st));
         a.r.old_base = old.base;
         a.r.old_norms = old.norms;
         a.r.new_base = nw.base;
@@ -2545,60 +2625,14 @@ int hnswgpu_hnsw_remove(hnswgpu_index *idx, const int32_t *rows, int64_t m, int6
         a.new_l0 = nw.l0;
         a.new_upadj = nw.upadj;
         a.new_upoff = nw.upoff;
-        const unsigned row_wgs = static_cast<unsigned>((n0 + kNWave - 1) / kNWave), list_wgs = static_cast<unsigned>((a.nlists + kNWave - 1) / kNWave);
+        const unsigned row_wgs = static_cast<unsigned>((n0 + kNWave - 1) / kNWave);
         hipLaunchKernelGGL(lsh_remove_mark_kernel, dim3(static_cast<unsigned>((m + kWG - 1) / kWG)), dim3(kWG), 0, st, a.r);
         hipLaunchKernelGGL(lsh_remove_rank_kernel, dim3(1), dim3(kWG), 0, st, a.r);
         if (n1 > 0) hipLaunchKernelGGL(lsh_remove_rows_kernel, dim3(row_wgs), dim3(kWG), 0, st, a.r);
         hipLaunchKernelGGL(hnsw_remove_levels_kernel, dim3(1), dim3(kWG), 0, st, a);
-        hipLaunchKernelGGL(hnsw_remove_owner_kernel, dim3(static_cast<unsigned>((n0 + kWG - 1) / kWG)), dim3(kWG), 0, st, a);
-        hipLaunchKernelGGL(hnsw_remove_lists_kernel, dim3(list_wgs), dim3(kWG), 0, st, a);
-        hipLaunchKernelGGL(hnsw_remove_scan_kernel, dim3(1), dim3(kWG), 0, st, a);
         HG_HIP(hipGetLastError());
         if (old.qrows && n1 > 0) HG_TRY(quantize_rows(idx, nw.base, n1, &nw.qrows, &nw.qmeta, st));  // (as add: one pass over the new base)
-        // the two totals of the scan: what the candidate arrays are sized by (no cap to overflow)
-        int64_t totals[2] = {0, 0};
-        HG_HIP(hipMemcpyAsync(totals, a.r.gate + kHnswRemoveGateCand, sizeof(totals), hipMemcpyDeviceToHost, st));
-        HG_HIP(hipStreamSynchronize(st));
-        a.ncand = totals[0];
-        a.ntasks = totals[1];
-        HG_REQUIRE(a.ntasks >= 0 && a.ntasks <= a.nlists && a.ncand >= a.ntasks &&
-                       a.ncand <= a.ntasks * static_cast<int64_t>(kSelMaxCand) && a.ntasks < 2147483647LL,
-                   HNSWGPU_EHIP, "the candidate scan counts %lld candidates of %lld lists", (long long)a.ncand, (long long)a.ntasks);
-        if (a.ntasks > 0) {
-            const bool heuristic = (idx->build_flags & HNSWGPU_BUILD_HEURISTIC) != 0;
-            HG_TRY(idx->s_ids.ensure(sizeof(int32_t) * static_cast<size_t>(a.ncand)));
-            HG_TRY(idx->s_outd.ensure(sizeof(float) * static_cast<size_t>(a.ncand)));
-            a.cand_id = idx->s_ids.as<int32_t>();
-            a.cand_d = idx->s_outd.as<float>();
-            const unsigned task_wgs = static_cast<unsigned>((a.ntasks + kNWave - 1) / kNWave);
-            hipLaunchKernelGGL(hnsw_remove_gather_kernel, dim3(task_wgs), dim3(kWG), 0, st, a);
-            HG_HIP(hipGetLastError());
-            HG_TRY(launch_remove_dist(idx, a, st));  // (the handle still holds the old rows: the candidates are old ids)
-            hipLaunchKernelGGL(hnsw_remove_sort_kernel, dim3(static_cast<unsigned>(a.ntasks)), dim3(kWG), 0, st, a);
-            HG_HIP(hipGetLastError());
-            if (heuristic) {
-                const size_t slots = static_cast<size_t>(a.ntasks) * M0;
-                const size_t o_d = sect(sizeof(int32_t) * slots), o_c = o_d + sect(sizeof(float) * slots);
-                HG_TRY(idx->s_misc2.ensure(o_c + sect(sizeof(int32_t) * static_cast<size_t>(a.ntasks))));
-                char *h = idx->s_misc2.as<char>();
-                HeurArgs ha;
-                memset(&ha, 0, sizeof(ha));
-                ha.ntasks = static_cast<int32_t>(a.ntasks);
-                ha.off = a.task_off;
-                ha.cand_id = a.cand_id;
-                ha.cand_d = a.cand_d;
-                ha.m = a.task_m;
-                ha.extend = 0;
-                ha.out_stride = M0;
-                ha.out_id = reinterpret_cast<int32_t *>(h);
-                ha.out_d = reinterpret_cast<float *>(h + o_d);
-                ha.out_cnt = reinterpret_cast<int32_t *>(h + o_c);
-                HG_TRY(launch_heur(idx, ha, st));
-                a.sel = ha.out_id;
-            }
-            hipLaunchKernelGGL(hnsw_remove_scatter_kernel, dim3(task_wgs), dim3(kWG), 0, st, a);
-            HG_HIP(hipGetLastError());
-        }
+        HG_TRY(hnsw_repair_chain<true>(idx, a, st));  // owner, list pass, scan, gather, distances, sort, selection, scatter
         // ---- the one readback: gate, levels, up_off, both adjacency arrays
         int64_t gate[kLshRemoveGate];
         h_levels.resize(static_cast<size_t>(n1));
@@ -2659,6 +2693,191 @@ int hnswgpu_hnsw_remove(hnswgpu_index *idx, const int32_t *rows, int64_t m, int6
     idx->hnsw_rej_off = false;
     old.release();
     if (n_after) *n_after = n1;
+    return call.close();
+}
+
+// Rows of a live graph take new values (include/hnswgpu.h).  The reference has no update (its to-do list names it); the rule is
+// this project's own and is its two mutation rules composed under stable ids.  UNLINK: hnswgpu_hnsw_remove's one-hop repair with
+// the call's ids U as the rows that left and nothing renumbered -- one chain on the handle's stream (hnsw_update_kernels.hpp: the
+// mask, the rows and norms scattered into copies, the list pass, the scan, gather, distances, sort, selection, scatter), the
+// int8 rows made again over the new base.  ONE readback brings the gate's three counts and the unlinked graph.  RE-INSERT: the
+// rows of U, ascending, with the levels they have, by hnswgpu_hnsw_add's insertion (insert_batches over an id list) against the
+// staged arrays.  Everything is staged and the handle restored on any failure, as hnswgpu_hnsw_add does.
+int hnswgpu_hnsw_update(hnswgpu_index *idx, const int32_t *ids, const float *rows, int64_t m, int32_t ef_construction) {
+    HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
+    HG_REQUIRE(m >= 0, HNSWGPU_EINVAL, "m must be >= 0");
+    HG_REQUIRE(m == 0 || ids, HNSWGPU_EINVAL, "ids is null");
+    HG_REQUIRE(m == 0 || rows, HNSWGPU_EINVAL, "rows is null");
+    HG_REQUIRE(ef_construction >= 1 && ef_construction <= 4096, HNSWGPU_ELIMIT, "need 1 <= ef_construction <= 4096");
+    if (m == 0) return 0;
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_REQUIRE(idx->has_graph, HNSWGPU_ESTATE, "index has no graph (call hnswgpu_hnsw_build / hnswgpu_set_graph first)");
+    HG_REQUIRE(idx->nparts == 0, HNSWGPU_ESTATE,
+               "the index holds a forest of HNSW sub-graphs: an update would link a row across its part (rebuild the part's graph)");
+    HG_REQUIRE(idx->nlist == 0, HNSWGPU_ESTATE, "the index holds IVF lists: they would keep the rows' old values (hnswgpu_ivf_update)");
+    HG_REQUIRE(idx->lsh_tables == 0, HNSWGPU_ESTATE, "the index holds LSH tables: they would keep the rows' old values (hnswgpu_lsh_update)");
+    HG_REQUIRE(idx->M0 == 2 * idx->M, HNSWGPU_ESTATE, "hnswgpu_hnsw_update needs a graph with M0 = 2 M (as hnswgpu_hnsw_build makes)");
+    const int64_t n = idx->n;
+    std::vector<int32_t> uid, from;  // uid: U ascending, the insertion order
+    int64_t at = -1, first = -1;
+    int verdict;
+    try {
+        verdict = ivf_update_slots(ids, m, n, uid, from, &at, &first);  // on the host array, before anything is enqueued
+    } catch (const std::bad_alloc &) {  // (its sorted copy of the ids)
+        set_error("host allocation failed");
+        return HNSWGPU_ENOMEM;
+    }
+    HG_REQUIRE(verdict != 1, HNSWGPU_EINVAL, "ids[%lld] = %d is not a row of the index (n = %lld)", (long long)at, ids[at], (long long)n);
+    HG_REQUIRE(verdict != 2, HNSWGPU_EINVAL, "ids[%lld] = %d is named twice (first at ids[%lld]): two values for one row have no winner",
+               (long long)at, ids[at], (long long)first);
+    HG_TRY(call.quiesce());
+    const int M = idx->M, M0 = idx->M0;
+    const int64_t ld = idx->ld, blocks = idx->up_blocks;
+    // Failure-atomic, as hnswgpu_hnsw_add: what the call makes is STAGED (levels and up_off are not: no level changes), the
+    // handle's fields point at the staged arrays while the insertion searches run and are put back if any step fails.
+    struct Staged {
+        float *base = nullptr, *norms = nullptr;
+        uint32_t *qrows = nullptr;
+        float4 *qmeta = nullptr;
+        int32_t *l0 = nullptr, *upadj = nullptr;
+        void release() {
+            void *ptrs[] = {base, norms, qrows, qmeta, l0, upadj};
+            for (void *p : ptrs)
+                if (p) (void)hipFree(p);
+            *this = Staged();
+        }
+    } nw, old;
+    old.base = idx->d_base, old.norms = idx->d_norms, old.qrows = idx->d_qrows, old.qmeta = idx->d_qmeta;
+    old.l0 = idx->d_l0, old.upadj = idx->d_upadj;
+    const int old_cal = idx->hnsw_cal_state;
+    const bool old_rej_off = idx->hnsw_rej_off;
+    bool installed = false;
+    HostGraph g;
+    auto update = [&]() -> int {
+        const size_t nn = static_cast<size_t>(n), mm = static_cast<size_t>(m), ub = static_cast<size_t>(std::max<int64_t>(blocks, 1));
+        // what the host knows before the device does: the lists of U (the gate's second count) and the entry the insertion starts at
+        std::vector<uint8_t> in_u(nn, 0);
+        int64_t u_lists = m;
+        for (int64_t s = 0; s < m; s++) {
+            in_u[uid[s]] = 1;
+            u_lists += idx->h_levels[uid[s]];
+        }
+        int32_t entry1 = idx->entry, top1 = idx->max_level;
+        int64_t skip = 0;  // rows of U that stand in the graph before the insertion begins
+        if (m == n) {      // an empty graph: the lowest id is its first row, as hnswgpu_hnsw_add's
+            entry1 = uid[0], top1 = idx->h_levels[uid[0]], skip = 1;
+        } else if (entry1 < 0 || entry1 >= n || in_u[entry1]) {  // hnswgpu_hnsw_remove's rule: the highest level, the lowest id among equals
+            entry1 = -1;
+            for (int64_t r = 0; r < n; r++)
+                if (!in_u[r] && (entry1 < 0 || idx->h_levels[r] > idx->h_levels[entry1])) entry1 = static_cast<int32_t>(r);
+            top1 = idx->h_levels[entry1];
+        }
+        // ---- 1. copies of the base and the norms take the call's rows; the int8 rows are made again
+        OwnedBuf d_stage;
+        HG_TRY(d_stage.ensure(sizeof(float) * mm * (ld + 1)));
+        float *stage = d_stage.as<float>(), *snorms = stage + mm * ld;
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.base), sizeof(float) * nn * ld));
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.norms), sizeof(float) * nn));
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.l0), sizeof(int32_t) * nn * M0));
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&nw.upadj), sizeof(int32_t) * ub * M));
+        HG_HIP(hipMemcpyAsync(nw.base, old.base, sizeof(float) * nn * ld, hipMemcpyDeviceToDevice, st));
+        HG_HIP(hipMemcpyAsync(nw.norms, old.norms, sizeof(float) * nn, hipMemcpyDeviceToDevice, st));
+        HG_HIP(hipMemsetAsync(nw.l0, 0xff, sizeof(int32_t) * nn * M0, st));
+        HG_HIP(hipMemsetAsync(nw.upadj, 0xff, sizeof(int32_t) * ub * M, st));
+        if (ld != idx->dim) HG_HIP(hipMemsetAsync(stage, 0, sizeof(float) * mm * ld, st));
+        HG_HIP(hipMemcpy2DAsync(stage, sizeof(float) * ld, rows, sizeof(float) * idx->dim, sizeof(float) * idx->dim, mm, hipMemcpyHostToDevice, st));
+        HG_TRY(launch_norms(idx->nch, stage, ld, m, snorms, st));
+        // ---- 2. the unlink: the mask of U, then hnswgpu_hnsw_remove's repair at the lists' own places under the old ids
+        HnswRemoveArgs a;
+        memset(&a, 0, sizeof(a));
+        a.r.n0 = a.r.n1 = n;
+        a.r.m = m;
+        a.r.W = (n + 31) / 32;
+        a.r.ld = ld;
+        a.M = M;
+        a.M0 = M0;
+        a.blocks0 = a.blocks1 = blocks;
+        a.nlists = n + blocks;
+        HG_TRY(hnsw_repair_scratch(idx, a, ids, st));
+        a.old_levels = idx->d_levels;
+        a.old_l0 = old.l0;
+        a.old_upadj = old.upadj;
+        a.old_upoff = idx->d_upoff;
+        a.new_levels = idx->d_levels;  // (never written: the levels kernel is hnswgpu_hnsw_remove's alone)
+        a.new_upoff = idx->d_upoff;
+        a.new_l0 = nw.l0;
+        a.new_upadj = nw.upadj;
+        const HnswUpdateRows ur = {n, m, ld, a.r.rows, stage, snorms, nw.base, nw.norms};
+        hipLaunchKernelGGL(lsh_remove_mark_kernel, dim3(static_cast<unsigned>((m + kWG - 1) / kWG)), dim3(kWG), 0, st, a.r);
+        hipLaunchKernelGGL(lsh_remove_rank_kernel, dim3(1), dim3(kWG), 0, st, a.r);
+        hipLaunchKernelGGL(hnsw_update_rows_kernel, dim3(static_cast<unsigned>((m + kNWave - 1) / kNWave)), dim3(kWG), 0, st, ur);
+        HG_HIP(hipGetLastError());
+        if (old.qrows) HG_TRY(quantize_rows(idx, nw.base, n, &nw.qrows, &nw.qmeta, st));  // (as add: one pass over the new base)
+        HG_TRY(hnsw_repair_chain<false>(idx, a, st));  // (distances over the handle's old rows: no row of U takes part in any)
+        // ---- the one readback: the gate and the unlinked graph, for the linker and the host mirrors
+        int64_t gate[kLshRemoveGate];
+        std::vector<int32_t> h_l0(nn * M0), h_upadj(static_cast<size_t>(blocks) * M);
+        HG_HIP(hipMemcpyAsync(gate, a.r.gate, sizeof(gate), hipMemcpyDeviceToHost, st));
+        HG_HIP(hipMemcpyAsync(h_l0.data(), nw.l0, sizeof(int32_t) * nn * M0, hipMemcpyDeviceToHost, st));
+        if (blocks > 0) HG_HIP(hipMemcpyAsync(h_upadj.data(), nw.upadj, sizeof(int32_t) * blocks * M, hipMemcpyDeviceToHost, st));
+        HG_HIP(hipStreamSynchronize(st));
+        HG_REQUIRE(gate[kHnswUpdateGateKept] == n - m, HNSWGPU_EHIP, "the mask marks %lld rows, not %lld", (long long)(n - gate[kHnswUpdateGateKept]),
+                   (long long)m);
+        HG_REQUIRE(gate[kHnswUpdateGateCleared] == u_lists, HNSWGPU_EHIP, "the list pass cleared %lld lists, not %lld",
+                   (long long)gate[kHnswUpdateGateCleared], (long long)u_lists);
+        HG_REQUIRE(gate[kHnswUpdateGateSeen] == n - m, HNSWGPU_EHIP, "the list pass saw %lld rows outside the call, not %lld",
+                   (long long)gate[kHnswUpdateGateSeen], (long long)(n - m));
+        // ---- 3. the insertion searches run against the staged arrays
+        idx->d_base = nw.base, idx->d_norms = nw.norms, idx->d_qrows = nw.qrows, idx->d_qmeta = nw.qmeta;
+        idx->d_l0 = nw.l0, idx->d_upadj = nw.upadj;
+        idx->graph_gen++;
+        idx->hnsw_cal_state = 0;  // as hnswgpu_hnsw_remove: the new graph is measured afresh
+        idx->hnsw_rej_off = false;
+        installed = true;
+        g.n = n;
+        g.M = M;
+        g.M0 = M0;
+        g.levels = idx->h_levels;
+        g.up_off = idx->h_upoff;
+        g.l0.assign(nn * (M0 + 1), -1);
+        g.l0_d.assign(nn * (M0 + 1), 0.f);
+        g.l0_cnt.assign(nn, 0);
+        g.up.assign(ub * (M + 1), -1);
+        g.up_d.assign(ub * (M + 1), 0.f);
+        g.up_cnt.assign(ub, 0);
+        g.sorted0.assign(nn, 0);
+        g.sortedu.assign(ub, 0);
+        HG_TRY(adopt_graph(idx, g, n, h_l0.data(), h_upadj.data(), idx->h_upoff.data(), st));
+        g.entry = entry1;
+        g.top = top1;
+        HG_TRY(insert_batches(idx, g, n - m + skip, ef_construction, st, idx->build_flags & ~HNSWGPU_BUILD_SEQUENTIAL, uid.data() + skip, m - skip));
+        HG_TRY(publish_graph(idx, g, st));  // (host mirrors, entry, max_level: assigned only once the uploads succeeded)
+        idx->hnsw_cal_state = 0;  // (the insertion's own launches are not the measurement of the graph that now stands)
+        idx->hnsw_rej_off = false;
+        return 0;
+    };
+    int rc;
+    try {
+        rc = update();
+    } catch (const std::bad_alloc &) {
+        set_error("host allocation failed in hnswgpu_hnsw_update");
+        rc = HNSWGPU_ENOMEM;
+    }
+    if (rc != 0) {
+        (void)hipStreamSynchronize(st);  // (nothing of the call is in flight when the staged arrays are freed)
+        if (installed) {
+            idx->d_base = old.base, idx->d_norms = old.norms, idx->d_qrows = old.qrows, idx->d_qmeta = old.qmeta;
+            idx->d_l0 = old.l0, idx->d_upadj = old.upadj;
+            idx->graph_gen++;
+            idx->hnsw_cal_state = old_cal;
+            idx->hnsw_rej_off = old_rej_off;
+        }
+        nw.release();
+        return rc;
+    }
+    old.release();
     return call.close();
 }
 

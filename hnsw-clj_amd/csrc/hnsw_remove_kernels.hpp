@@ -8,6 +8,10 @@
 // A wave per adjacency list (kMaxDeg <= kWave: a lane per slot), ballot / popcount for the in-wave compaction, LDS for the sort.
 // No kernel waits for another workgroup; every loop is bounded by n0, w or w * w; every index is checked before its store; the
 // one atomicAdd counts (a commutative sum) and decides no destination.  Included by hnsw.hip only.
+// The list pass and the scatter carry a template parameter RENUM: true is the removal described above; false is the UNLINK of
+// hnswgpu_hnsw_update (hnsw_update_kernels.hpp), the same repair with nothing renumbered -- every list stays at its place (the
+// staged arrays have the old shape: new_upoff = old_upoff, blocks1 = blocks0, n1 = n0), ids are written as they are, and the
+// lists of the marked rows themselves are cleared instead of dropped.
 #pragma once
 #include "build_kernels.hpp"
 #include "remove_kernels.hpp"
@@ -22,6 +26,7 @@ constexpr int kHnswRemoveGateOff = 0;    // the new up_off[n1]
 constexpr int kHnswRemoveGateRows = 1;   // kept layer-0 lists the list pass saw
 constexpr int kHnswRemoveGateCand = 2;   // candidates of all tasks
 constexpr int kHnswRemoveGateTasks = 3;  // lists to select again
+constexpr int kHnswRemoveGateCleared = 4;  // RENUM = false: lists of marked rows the list pass cleared
 
 struct HnswRemoveArgs {
     LshRemoveArgs r;     // n0, n1, m, W, ld, rows, keep, word_rank, old / new base and norms, gate; tables = 0
@@ -69,9 +74,16 @@ __device__ __forceinline__ const int32_t *hnsw_remove_list_of(const HnswRemoveAr
     return a.old_upadj + b * a.M;
 }
 
-// where list (u, lc) of a KEPT node stands in the staged graph, or null (never: the gate would say so)
+// the id a kept row carries in the staged graph: its rank among the kept rows, or (RENUM = false) the id it has
+template <bool RENUM>
+__device__ __forceinline__ int64_t hnsw_remove_id(const HnswRemoveArgs &a, int64_t r) {
+    return RENUM ? lsh_remove_rank(a.r, r) : r;
+}
+
+// where list (u, lc) of a KEPT node stands in the staged graph (RENUM = false: of any node), or null (never: the gate would say so)
+template <bool RENUM>
 __device__ __forceinline__ int32_t *hnsw_remove_dest(const HnswRemoveArgs &a, int64_t u, int lc) {
-    const int64_t to = lsh_remove_rank(a.r, u);
+    const int64_t to = hnsw_remove_id<RENUM>(a, u);
     if (to < 0 || to >= a.r.n1) return nullptr;
     if (lc == 0) return a.new_l0 + to * a.M0;
     const int64_t b = a.new_upoff[to] + lc - 1;
@@ -116,24 +128,31 @@ static __global__ __launch_bounds__(kWG) void hnsw_remove_owner_kernel(HnswRemov
 }
 
 // 2. One wave per old list of a kept node: its kept members in their order under their new ids, -1 padded, to the list's new
-// place; and, if a member left, the number of its candidates
-static __global__ __launch_bounds__(kWG) void hnsw_remove_lists_kernel(HnswRemoveArgs a) {
+// place; and, if a member left, the number of its candidates.  RENUM = false: a list of a marked node is cleared at its place
+template <bool RENUM>
+__global__ __launch_bounds__(kWG) void hnsw_remove_lists_kernel(HnswRemoveArgs a) {
     const int lane = threadIdx.x & (kWave - 1);
     const int64_t t = static_cast<int64_t>(blockIdx.x) * kNWave + (threadIdx.x >> 6);
     int64_t u;
     int lc, w;
     const int32_t *old;
     if (!hnsw_remove_list(a, t, u, lc, w, old)) return;  // (wave-uniform, as every branch on t, u, lc below)
-    if (!lsh_remove_kept(a.r, u)) return;
-    int32_t *dst = hnsw_remove_dest(a, u, lc);
+    const bool u_kept = lsh_remove_kept(a.r, u);
+    if (RENUM && !u_kept) return;
+    int32_t *dst = hnsw_remove_dest<RENUM>(a, u, lc);
     if (!dst) return;
+    if (!RENUM && !u_kept) {
+        if (lane < w) dst[lane] = -1;
+        if (lane == 0) atomicAdd(reinterpret_cast<unsigned long long *>(a.r.gate + kHnswRemoveGateCleared), 1ull);
+        return;
+    }
     const int32_t nb = lane < w ? old[lane] : -1;
     const bool valid = nb >= 0 && nb < a.r.n0;
     const bool kept = valid && lsh_remove_kept(a.r, nb);
     const uint64_t mk = __ballot(kept), ml = __ballot(valid && !kept);
     const uint64_t below = (1ull << lane) - 1ull;
     const int nk = __popcll(mk);
-    if (kept) dst[__popcll(mk & below)] = static_cast<int32_t>(lsh_remove_rank(a.r, nb));
+    if (kept) dst[__popcll(mk & below)] = static_cast<int32_t>(hnsw_remove_id<RENUM>(a, nb));
     if (lane >= nk && lane < w) dst[lane] = -1;
     if (lane == 0 && lc == 0) atomicAdd(reinterpret_cast<unsigned long long *>(a.r.gate + kHnswRemoveGateRows), 1ull);
     if (ml == 0) return;
@@ -305,8 +324,9 @@ static __global__ __launch_bounds__(kWG) void hnsw_remove_sort_kernel(HnswRemove
 }
 
 // 7. One wave per task: the selection -- heuristic_select_kernel's, or the first w of the sorted range -- over the task's list in
-// the staged graph, under the new ids, -1 padded
-static __global__ __launch_bounds__(kWG) void hnsw_remove_scatter_kernel(HnswRemoveArgs a) {
+// the staged graph, under the new ids (RENUM = false: the ids as they are), -1 padded
+template <bool RENUM>
+__global__ __launch_bounds__(kWG) void hnsw_remove_scatter_kernel(HnswRemoveArgs a) {
     const int lane = threadIdx.x & (kWave - 1);
     const int64_t k = static_cast<int64_t>(blockIdx.x) * kNWave + (threadIdx.x >> 6);
     if (k >= a.ntasks) return;
@@ -315,13 +335,13 @@ static __global__ __launch_bounds__(kWG) void hnsw_remove_scatter_kernel(HnswRem
     const int32_t *old;
     if (!hnsw_remove_list(a, a.task_list[k], u, lc, w, old)) return;
     if (!lsh_remove_kept(a.r, u)) return;
-    int32_t *dst = hnsw_remove_dest(a, u, lc);
+    int32_t *dst = hnsw_remove_dest<RENUM>(a, u, lc);
     if (!dst || lane >= w) return;
     const int64_t base = a.task_off[k], end = a.task_off[k + 1];
     int32_t id = -1;
     if (a.sel) id = a.sel[k * a.M0 + lane];
     else if (base >= 0 && base + lane < end && end <= a.ncand) id = a.cand_id[base + lane];
-    dst[lane] = (id >= 0 && lsh_remove_kept(a.r, id)) ? static_cast<int32_t>(lsh_remove_rank(a.r, id)) : -1;
+    dst[lane] = (id >= 0 && lsh_remove_kept(a.r, id)) ? static_cast<int32_t>(hnsw_remove_id<RENUM>(a, id)) : -1;
 }
 
 }  // namespace hg

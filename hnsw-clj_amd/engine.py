@@ -459,6 +459,16 @@ class Index:
         self.n = int(n_after.value)
         return kept
 
+    def hnsw_update(self, ids, rows, ef_construction=200):
+        """hnswgpu_hnsw_update: row ``ids[i]`` takes the values ``rows[i]`` (row ids in any order, none named twice); n, every
+        row id and every row's level stay.  The rows are unlinked as hnswgpu_hnsw_remove unlinks rows that leave -- nothing is
+        renumbered -- and inserted again in ascending id order as hnswgpu_hnsw_add inserts rows (include/hnswgpu.h)."""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        rows = _queries(rows, self.dim)
+        if len(rows) != len(ids):
+            raise ValueError("%d ids for %d rows" % (len(ids), len(rows)))
+        check(lib().hnswgpu_hnsw_update(self._h, _p(ids), _p(rows), len(ids), ef_construction))
+
     def get_graph(self):
         M, M0, ent, mx = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
         blocks = C.c_int64()

@@ -113,6 +113,34 @@ def remove_vectors(graph, ids):
     return graph
 
 
+def update_vectors(graph, data):
+    """"Update existing vectors" (the open item of the reference's to-do list); the rule is the engine's own
+    (hnswgpu_hnsw_update): ``data`` has the form ``build_index`` takes; the vector stored under each id takes the new values and
+    keeps its id and its level -- it is unlinked as a removed vector is and inserted again as an added one, with the graph's
+    ``ef_construction`` -- so ``graph.ids`` is unchanged.  An unknown id raises KeyError, an id that names several rows or
+    appears twice in ``data`` raises ValueError, both before the device is touched.  Empty ``data`` does nothing.  Returns
+    the graph."""
+    ids, rows = _split(data)
+    if not ids:
+        return graph
+    rows_of = {}
+    for row, i in enumerate(graph.ids):
+        rows_of.setdefault(i, []).append(row)
+    at, seen = [], set()
+    for i in ids:
+        if i not in rows_of:
+            raise KeyError(i)
+        if len(rows_of[i]) > 1:
+            raise ValueError("id %r names %d rows of the index" % (i, len(rows_of[i])))
+        if i in seen:
+            raise ValueError("id %r appears twice: two values for one vector have no winner" % (i,))
+        seen.add(i)
+        at.append(rows_of[i][0])
+    graph.index.hnsw_update(np.asarray(at, np.int32), rows, graph.ef_construction)
+    graph.__dict__.pop("_route", None)       # (routed_to_exact_scan's measurements were of the graph that was)
+    return graph
+
+
 def _format(graph, ids_row, d_row):
     return [{"id": graph.ids[i], "distance": float(d)} for i, d in zip(ids_row, d_row) if i >= 0]
 

@@ -196,6 +196,74 @@ int hnswgpu_hnsw_add(hnswgpu_index *idx, const float *rows, int64_t m, int32_t e
  * Out of scope: forests, hnswgpu_group_* and sharded.py; handles that hold a graph together with lists or tables; restoring
  * symmetry after a repair; repair deeper than one hop; reinserting badly connected nodes; tombstones. */
 int hnswgpu_hnsw_remove(hnswgpu_index *idx, const int32_t *rows, int64_t m, int64_t *n_after);
+/* Rows of a LIVE graph take new values.  The reference has no update (its to-do list names "Update existing vectors"); the
+ * rule is this project's own -- the two rules above, composed under stable ids -- and tests/hnsw_update_model.py is its one
+ * specification.  `ids` is m row ids in host memory, in any order; `rows` is m x dim float32 in host memory; row ids[i]
+ * takes the values rows[i].  n, every row id and EVERY ROW'S LEVEL stay as they are: the handle's levels are still the
+ * seed's draws by id, and a later hnswgpu_hnsw_add with the build's seed continues the sequence as before.  Let U be the
+ * ids of the call.
+ *   1. Unlink -- hnswgpu_hnsw_remove's repair with U as the rows that left, but nothing is renumbered.  Every list of a node
+ *      outside U that holds no member of U stays as it is.  A list that holds a member of U is selected again from the OLD
+ *      graph alone -- the adjacency as it stood when the call began; all lists are repaired from it at once.  For node u on
+ *      layer lc (width w = M0 on layer 0, M above): the candidates are u's old neighbours outside U joined with the members
+ *      outside U of the layer-lc lists of u's neighbours in U, without u, each once; d(u, c) by the traversal's arithmetic
+ *      on the stored norms; ascending by (distance, id); then what the handle's builder does to an over-full list: with
+ *      HNSWGPU_BUILD_HEURISTIC get-neighbors-heuristic without extend-candidates, otherwise -- a graph installed by
+ *      hnswgpu_set_graph included -- the first min(w, C).  HNSWGPU_BUILD_SYMMETRIC is not applied: a repair changes only the
+ *      list it repairs and adds no back edge; nothing deeper than one hop is looked at.  No row of U takes part in any of
+ *      these distances: the old and the new base give the same bits.  Every list of every row of U becomes empty: after
+ *      this step no edge leads into U or out of it.
+ *   2. Values -- base rows of U take the new values, padding columns zero; their norms come from the kernel hnswgpu_create
+ *      uses; the base-order int8 rows and meta are made again where the handle has them.  After the call base, norms, int8
+ *      rows and meta equal, bit for bit, what hnswgpu_create(base with the new values) +
+ *      hnswgpu_set_rejection_test(same mode) holds.
+ *   3. The entry point the insertion starts from: outside U -> it stays, with max_level; in U -> hnswgpu_hnsw_remove's rule:
+ *      the row outside U of the highest level, the lowest id among equals, whose level becomes the top; every row in U -> the
+ *      lowest id of U with its own level, and the insertion starts behind it -- hnswgpu_hnsw_add on an empty graph.
+ *   4. Re-insert -- the rows of U in ascending id order AS hnswgpu_hnsw_add INSERTS ROWS: the same search kernel and linker,
+ *      the handle's builder flags without HNSWGPU_BUILD_SEQUENTIAL (a graph from hnswgpu_set_graph links to the m closest),
+ *      the levels the rows already have, against the graph of step 1; batches by the builder's size rule with
+ *      done = (n - |U|) + the rows inserted so far; rows of one batch do not see each other; entry and top move behind a
+ *      batch in which a row's level exceeds the top.  Reverse edges, over-full lists and their pruning as add handles them.
+ *   - Updating the LAST m rows of a handle equals, edge for edge and bit for bit, hnswgpu_hnsw_remove(those rows) followed
+ *     by hnswgpu_hnsw_add(the new values, the same ef_construction, the build's seed).
+ *   - The result DEPENDS on how an update is split over calls: two calls give the rule applied twice.  Within one call the
+ *     order of `ids` does not matter.
+ *   - Updating a row to the values it already has does NOT leave the graph unchanged: the row is unlinked and linked again
+ *     (hnswgpu_ivf_update is the opposite: such a row stays where it is).
+ *   - The per-graph verdict of the mode-1 rejection test (hnswgpu_hnsw_rejection_state) is RESET, as hnswgpu_hnsw_remove
+ *     resets it.
+ *   - The device work of the unlink is one chain on the handle's stream (hnsw_update_kernels.hpp, and hnsw_remove_kernels.hpp
+ *     instantiated without the renumbering): the mark mask of U, the m uploaded rows and their norms scattered into copies of
+ *     base and norms, the pass over all n + up_blocks lists (untouched lists copied, U's lists cleared, candidates counted),
+ *     the scan whose two totals size the candidate arrays (no cap to overflow), gather, distances, the per-task sort, the
+ *     selection, the scatter under the old ids.  No destination is decided by the order atomics arrive in.
+ *   - Failure-atomic, like hnswgpu_hnsw_add: everything is staged under the handle's lock with its streams quiesced.  ONE
+ *     readback brings the unlinked graph down for the linker, with three counts the host knows in advance: rows marked
+ *     == m, lists cleared == m + the levels of U summed, rows outside U seen == n - m (HNSWGPU_EHIP otherwise, the handle
+ *     untouched).  The insertion searches then run against the staged arrays; on any failure the handle is restored to
+ *     exactly what it was.  Searches from other threads wait and see the old or the new index.
+ *   - Cost and quality, measured on one MI355X (profiles/hnsw_update.txt: 31,173 x 768 clustered-normalised, heuristic
+ *     graph, M 16, ef_construction 200; the new values are rows of other clusters): updating m = 1 / 1,024 / 8,192
+ *     scattered rows takes 9.2 / 12.7 / 27.2 ms (host clock around the call, median of five) against 107 / 115 / 114 ms for
+ *     hnswgpu_create + hnswgpu_hnsw_build_ex over the new base from host memory -- 0.09 / 0.11 / 0.24 of the rebuild -- and
+ *     9.4 / 12.1 / 26.8 ms for hnswgpu_hnsw_remove + hnswgpu_hnsw_add of the same rows: the update costs what the pair costs
+ *     and keeps ids and levels.  The update was faster than the rebuild at every m measured; the call copies the base once
+ *     and its insertion grows with m, so larger shares than 8,192 of 31,173 were not timed.  recall@10 of 1,000 held-out
+ *     queries against the exact neighbours in the new base, updated / freshly built / remove + add: after 10 % of the rows
+ *     took new values 0.847 / 0.979 / 0.842 at ef 640 and 0.495 / 0.614 / 0.498 at ef 100; after 40 % 0.937 / 0.991 / 0.937
+ *     at ef 640 and 0.515 / 0.661 / 0.519 at ef 100.  The update equals remove + add within noise and is BELOW a fresh
+ *     build: the rows of a new cluster arrive in few batches whose rows do not see each other (hnswgpu_hnsw_add's batched
+ *     insertion), so where recall matters more than the 4-10x in time, or most rows move to new regions, rebuild.
+ * Returns, checked in this order, the handle untouched in every case: -1 for a null handle (before m == 0 and before any
+ * HIP call); -1 for m < 0; -1 for null ids or rows with m > 0; HNSWGPU_ELIMIT for ef_construction outside [1, 4096], as
+ * hnswgpu_hnsw_add; 0 for m == 0 (nothing happens); -3 for a handle without a graph, for a forest, for one that also holds
+ * IVF lists or LSH tables, and for a graph with M0 != 2 M -- the message names which; -1 for an id outside [0, n); -1 for an
+ * id named twice (the message names both positions) -- both checked on the host array before anything is enqueued.
+ * Out of scope: forests; hnswgpu_group_* and sharded.py; handles that hold a graph together with lists or tables; new level
+ * draws; repair deeper than one hop; restoring symmetry after the unlink; in-place patching that avoids the per-call copy of
+ * the base. */
+int hnswgpu_hnsw_update(hnswgpu_index *idx, const int32_t *ids, const float *rows, int64_t m, int32_t ef_construction);
 int hnswgpu_graph_sizes(const hnswgpu_index *idx, int32_t *M, int32_t *M0, int64_t *up_blocks, int32_t *entry,
                         int32_t *max_level);
 int hnswgpu_get_graph(const hnswgpu_index *idx, int32_t *levels, int32_t *l0_adj, int64_t *up_off,
@@ -384,7 +452,8 @@ int hnswgpu_ivf_remove(hnswgpu_index *idx, const int32_t *rows, int64_t m, int64
  * (hnswgpu_set_ivf_shard); the message names which; -1 for an id outside [0, n) and for an id named twice (two values for one
  * row have no defined winner), both checked on the host array before anything is enqueued; -1 for a new row with no nearest
  * centroid (NaN).
- * Out of scope: updates of an HNSW graph (LSH tables take new values through hnswgpu_lsh_update), handles with both a graph and lists, forests, hnswgpu_group_*,
+ * Out of scope: handles with both a graph and lists (LSH tables take new values through hnswgpu_lsh_update, a plain graph
+ * through hnswgpu_hnsw_update), forests, hnswgpu_group_*,
  * sharded.ShardedIVF and shards (rebuild those); a plain handle without lists; moving centroids or re-clustering after heavy
  * drift; in-place patching that avoids the per-call copy of the base and the list rows. */
 int hnswgpu_ivf_update(hnswgpu_index *idx, const int32_t *ids, const float *rows, int64_t m);
