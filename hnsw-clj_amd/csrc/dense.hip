@@ -25,7 +25,7 @@ size_t hnsw_dense_code_bytes(int nch, int32_t nq) {
     return (sizeof(uint32_t) * 2 * kWave * nch * static_cast<size_t>(nq) + 255) & ~static_cast<size_t>(255);
 }
 
-int64_t hnsw_dense_ld(int64_t n) { return (n + kDenseTR - 1) / kDenseTR * kDenseTR; }
+int64_t hnsw_dense_ld(int64_t n) { return (n + kDenseLd - 1) / kDenseLd * kDenseLd; }
 
 // Query codes, then the table: two launches in front of the traversal.  codes: hnsw_dense_code_bytes + nq QueryScal.
 int launch_hnsw_dense(const hnswgpu_index *idx, const float *d_Q, int64_t qld, int32_t nq, void *codes, float *lb, int64_t lb_ld,
@@ -52,14 +52,28 @@ int launch_hnsw_dense(const hnswgpu_index *idx, const float *d_Q, int64_t qld, i
     d.n = idx->n;
     d.nq = nq;
     d.kbytes = 4 * kWave * idx->nch;
-    d.metric = idx->metric;
-    d.nqt = (nq + kDenseTQ - 1) / kDenseTQ;
-    d.nrt = static_cast<int32_t>((idx->n + kDenseTR - 1) / kDenseTR);
-    d.rp = std::max(1, std::min(kDensePanel, d.nrt / 8));  // (few rows: narrower panels, so that every XCD has one)
-    d.nsp = (d.nrt + d.rp - 1) / d.rp;
-    const int64_t grid = 8LL * ((d.nsp + 7) / 8) * d.nqt * d.rp;
-    HG_REQUIRE(grid < (1LL << 31), HNSWGPU_ELIMIT, "too many tiles for one bounds launch");
-    hipLaunchKernelGGL(hnsw_dense_bounds_kernel, dim3(static_cast<unsigned>(grid)), dim3(kWG), 0, st, d);
+    dense_tiling(d);
+    const int64_t places = dense_walk_places(d);
+    // one persistent workgroup per CU, a multiple of 8 of them: each stays on one XCD of the walk
+    const unsigned grid = static_cast<unsigned>(std::min<int64_t>(places, std::max(8, idx->cus / 8 * 8)));
+    // (a workgroup steps its place by the grid once past the last one: that sum stays an int too)
+    HG_REQUIRE(places < (1LL << 31) - grid, HNSWGPU_ELIMIT, "too many tiles for one bounds launch");
+    d.nvt = static_cast<int32_t>(places);
+    static bool attr_done[3][64] = {};
+#define CALL(M)                                                                                                              \
+    do {                                                                                                                     \
+        if (attr_needed(attr_done[M]))                                                                                       \
+            HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&hnsw_dense_bounds_kernel<M>),                         \
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, kDenseLds));                              \
+        hipLaunchKernelGGL((hnsw_dense_bounds_kernel<M>), dim3(grid), dim3(kDenseWG), kDenseLds, st, d);                     \
+    } while (0)
+    static_assert(METRIC_COS == 0 && METRIC_L2 == 1 && METRIC_DOT == 2, "attr_done");
+    switch (idx->metric) {
+        case METRIC_L2: CALL(METRIC_L2); break;
+        case METRIC_DOT: CALL(METRIC_DOT); break;
+        default: CALL(METRIC_COS); break;
+    }
+#undef CALL
     HG_HIP(hipGetLastError());
     return 0;
 }

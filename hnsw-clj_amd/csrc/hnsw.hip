@@ -230,14 +230,17 @@ static int hnsw_launch_plan(const hnswgpu_index *idx, const HnswArgs &a, const H
         // budget (hnswgpu_set_hnsw_dense_bounds: 2 GiB by default -- the 1.25M-row shards are outside it by design).  It pays only
         // while a query tests a sizeable share of the rows (a query tests about 6.5 ef neighbours) and the chip is full.
         // 31k x 768 clustered (the bench's index), ms per launch without / with the table, medians of three rounds of ten launches,
-        // the two alternating (tools/hnsw_batch_sweep.py --dense; the rounds of a setting lie within 0.3 % of each other):
-        // ef 640: 2,048 queries 3.523 / 2.996, 4,096: 6.896 / 5.573, 10,000: 12.023 / 10.077; ef 1600: 10,000: 37.353 / 30.598;
-        // ef 100: 4,096: 1.480 / 1.424, 10,000: 2.992 / 3.022.  At the headline the traversal goes from 11.9 to 9.02 ms, the table costs
-        // 0.97 ms (hnsw_dense_bounds_kernel) + 0.015 ms (the query codes): profiles/hnsw_dense_bounds_ab.txt.
-        // On where 6.5 ef is at least 6 % of n (13 % at ef 640, 33 % at ef 1600: faster at every measured batch; 2.1 % at ef 100:
-        // slower at 10,000 queries) from 8 queries per CU, the smallest batch measured.  Nothing was measured between 2.1 % and 13 %.
+        // the two alternating (tools/hnsw_batch_sweep.py --dense; the rounds of a setting lie within 0.6 % of each other):
+        // ef 640: 2,048 queries 3.502 / 2.682, 4,096: 6.884 / 5.250, 10,000: 11.912 / 9.300; ef 1600: 10,000: 37.316 / 28.140;
+        // ef 320: 4,096: 3.276 / 2.602, 10,000: 7.033 / 5.587; ef 200: 4,096: 2.326 / 1.906, 10,000: 5.025 / 4.042;
+        // ef 100: 4,096: 1.482 / 1.298, 10,000: 3.004 / 2.687.  At the headline the table costs 0.63 ms (hnsw_dense_bounds_kernel)
+        // + 0.013 ms (the query codes): profiles/hnsw_dense_gemm_ab.txt (with the first kernel, 0.96 ms, ef 100 was 3.8 % faster at
+        // 4,096 queries and 1.0 % slower at 10,000, and the rule stood at 6 % of n: profiles/hnsw_dense_bounds_ab.txt).
+        // On where 6.5 ef is at least 2 % of n (2.1 % at ef 100, 4.2 % at ef 200, 6.7 % at ef 320, 13 % at ef 640, 33 % at ef 1600:
+        // 11 - 25 % faster at every measured batch) from 8 queries per CU, the smallest batch measured.  Nothing was measured below
+        // 2.1 %, nor below 8 queries per CU.
         p.lb_ld = hnsw_dense_ld(a.n);
-        const bool dense_rule = a.nq >= 8 * idx->cus && 6.5 * a.ef >= 0.06 * static_cast<double>(a.n);
+        const bool dense_rule = a.nq >= 8 * idx->cus && 6.5 * a.ef >= 0.02 * static_cast<double>(a.n);
         p.dense = plain_search && p.kernel == HnswKernel::Wave && p.rejection && !build && !parts && idx->dense_mode != 0 &&
                   static_cast<double>(a.nq) * static_cast<double>(p.lb_ld) * sizeof(float) <= static_cast<double>(idx->dense_budget) &&
                   (idx->dense_mode >= 2 || dense_rule);

@@ -15,7 +15,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 if len(sys.argv) > 1 and sys.argv[1] == "--dense":
-    # python tools/hnsw_batch_sweep.py --dense: the dense bounds table (hnswgpu_set_hnsw_dense_bounds 2) against none (0), as --order:
+    # python tools/hnsw_batch_sweep.py --dense [ef:nq ...]: the dense bounds table (hnswgpu_set_hnsw_dense_bounds 2) against none (0), as --order:
     # one process, bench.py's own index, the two settings alternating, three rounds of 10 launches; the table the rule in
     # hnsw_launch_plan is read from.
     import numpy as np
@@ -30,7 +30,9 @@ if len(sys.argv) > 1 and sys.argv[1] == "--dense":
     idx = engine.Index(base, "cosine", 0)
     idx.hnsw_build(16, 200, 42, **bench.BUILDERS["heuristic"])
     print("ef    nq      no table ms (3 rounds)     table ms (3 rounds)        table / none (medians)", flush=True)
-    for ef, nq in ((640, 2048), (640, 4096), (640, 10000), (100, 4096), (100, 10000), (1600, 10000)):
+    shapes = [tuple(int(x) for x in s.split(":")) for s in sys.argv[2:]]      # further shapes: ef:nq ...
+    for ef, nq in shapes or ((640, 2048), (640, 4096), (640, 10000), (100, 4096), (100, 10000), (1600, 10000),
+                             (200, 4096), (200, 10000), (320, 4096), (320, 10000)):
         Q = torch.from_numpy(queries[:nq]).to(dev)
         out = (torch.empty((nq, 10), dtype=torch.int32, device=dev), torch.empty((nq, 10), dtype=torch.float32, device=dev))
         ms = {0: [], 2: []}
