@@ -113,6 +113,13 @@ _SIGS = {
     "hnswgpu_lsh_search_filtered_dev": ["p", "p", "i32", "i32", "i32", "i32", "i32", "i32", "p", "p", "p", "p"],
     "hnswgpu_lsh_search_filtered_each": ["p", "p", "i32", "i32", "i32", "i32", "i32", "i32", "p", "p", "p"],
     "hnswgpu_lsh_search_filtered_each_dev": ["p", "p", "i32", "i32", "i32", "i32", "i32", "i32", "p", "p", "p", "p"],
+    "hnswgpu_pcaf_build": ["p", "i32", "i64"],
+    "hnswgpu_set_pcaf": ["p", "p", "i32"],
+    "hnswgpu_pcaf_sizes": ["p", "p"],
+    "hnswgpu_pcaf_get": ["p", "p", "p"],
+    "hnswgpu_pcaf_project": ["p", "p", "i64", "p"],
+    "hnswgpu_pcaf_search": ["p", "p", "i32", "i32", "i32", "p", "p"],
+    "hnswgpu_pcaf_search_dev": ["p", "p", "i32", "i32", "i32", "p", "p", "p"],
     "hnswgpu_save": ["p", "p"],
     "hnswgpu_load": ["p", "i32", "p"],
     "hnswgpu_set_profiling": ["p", "i32"],

@@ -229,6 +229,14 @@ struct hnswgpu_index {
     int32_t *d_lsh_ids = nullptr;
     std::vector<float> h_lsh_planes;
 
+    // P-HNSW (pcaf.hip, pcaf_kernels.hpp): a random projection to pcaf_T components, or none (pcaf_T == 0).  The projection
+    // [T][ld] zero padded, the projected rows [n][Tp] (Tp = T rounded up to 8, zero padded) and their norms; the caller's
+    // projection [T][dim] for export.  A handle with this state holds no graph, lists, tables or forest and takes no mutation.
+    int pcaf_T = 0, pcaf_Tp = 0;
+    float *d_pcaf_proj = nullptr, *d_pcaf_low = nullptr, *d_pcaf_lnorms = nullptr;
+    std::vector<float> h_pcaf_proj;
+    hg::DevBuf s_pcaf_q, s_pcaf_keys;  // a search's projected queries + norms, and its per-slab candidate keys
+
     // scratch (grown on demand, reused across calls; calls are serialised by `mu`)
     hg::DevBuf s_q, s_partial, s_ord, s_dist, s_pairs, s_ids, s_outd, s_probes, s_stats, s_misc, s_misc2, s_vis, s_qp, s_qn, s_tile, s_grp, s_done, s_pf, s_solo, s_bk, s_heavy, s_home, s_dh, s_hord;
     // s_hord: order[nq] | keys[nq] of an ordered HNSW launch (order_kernels.hpp); the last such launch's, for hnswgpu_hnsw_last_order
@@ -266,6 +274,11 @@ struct hnswgpu_index {
 };
 
 namespace hg {
+
+// First check of every call that installs a graph, lists, tables or a forest, or adds, removes or updates rows: the projected
+// rows of a P-HNSW handle would go stale, and its search reads the base rows alone
+#define HG_REFUSE_PCAF(idx, what) \
+    HG_REQUIRE(!(idx) || (idx)->pcaf_T == 0, HNSWGPU_ESTATE, "index holds P-HNSW state (hnswgpu_pcaf_build / hnswgpu_set_pcaf): %s is refused", what)
 
 inline int64_t ivf_mean_len(const hnswgpu_index *idx) {
     return std::max<int64_t>(1, (idx->ivf_n_global > 0 ? idx->ivf_n_global : idx->n) / std::max(idx->nlist, 1));

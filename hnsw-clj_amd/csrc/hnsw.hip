@@ -1121,6 +1121,7 @@ int hnswgpu_set_graph(hnswgpu_index *idx, const int32_t *levels, const int32_t *
     hipStream_t st = idx->stream;
     Call call;
     HG_TRY(call.open(idx, st));
+    HG_REFUSE_PCAF(idx, "hnswgpu_set_graph");
     HG_TRY(install_graph(idx, call, st, levels, l0_adj, M0, up_off, up_adj, M, entry, max_level, nullptr));
     return call.close();
 }
@@ -1133,6 +1134,7 @@ int hnswgpu_set_graph_parts(hnswgpu_index *idx, const int32_t *levels, const int
     hipStream_t st = idx->stream;
     Call call;
     HG_TRY(call.open(idx, st));
+    HG_REFUSE_PCAF(idx, "hnswgpu_set_graph_parts");
     HG_TRY(install_graph(idx, call, st, levels, l0_adj, M0, up_off, up_adj, M, -1, 0, &pt));
     return call.close();
 }
@@ -2273,6 +2275,7 @@ int hnswgpu_hnsw_build_ex(hnswgpu_index *idx, int32_t M, int32_t ef_construction
     hipStream_t st = idx->stream;
     Call call;
     HG_TRY(call.open(idx, st));
+    HG_REFUSE_PCAF(idx, "hnswgpu_hnsw_build_ex");
     const int64_t n = idx->n;
     const int M0 = 2 * M;
     HostGraph g;
@@ -2335,6 +2338,7 @@ int hnswgpu_hnsw_build_parts(hnswgpu_index *idx, int32_t nparts, const int64_t *
     hipStream_t st = idx->stream;
     Call call;
     HG_TRY(call.open(idx, st));
+    HG_REFUSE_PCAF(idx, "hnswgpu_hnsw_build_parts");
     const int64_t n = idx->n;
     HG_REQUIRE(part_off[0] == 0 && part_off[nparts] == n, HNSWGPU_EINVAL, "part_off must run from 0 to n");
     for (int32_t p = 0; p < nparts; p++)
@@ -2388,6 +2392,7 @@ int hnswgpu_hnsw_add(hnswgpu_index *idx, const float *rows, int64_t m, int32_t e
     hipStream_t st = idx->stream;
     Call call;
     HG_TRY(call.open(idx, st));
+    HG_REFUSE_PCAF(idx, "hnswgpu_hnsw_add");
     HG_REQUIRE(idx->has_graph, HNSWGPU_ESTATE, "index has no graph (call hnswgpu_hnsw_build / hnswgpu_set_graph first)");
     HG_REQUIRE(idx->nparts == 0, HNSWGPU_ESTATE,
                "the index holds a forest: a new row has no part (rebuild with hnswgpu_hnsw_build_parts / hnswgpu_set_graph_parts)");
@@ -2543,6 +2548,7 @@ int hnswgpu_hnsw_remove(hnswgpu_index *idx, const int32_t *rows, int64_t m, int6
     hipStream_t st = idx->stream;
     Call call;
     HG_TRY(call.open(idx, st));
+    HG_REFUSE_PCAF(idx, "hnswgpu_hnsw_remove");
     HG_REQUIRE(idx->has_graph, HNSWGPU_ESTATE, "index has no graph (call hnswgpu_hnsw_build / hnswgpu_set_graph first)");
     HG_REQUIRE(idx->nparts == 0, HNSWGPU_ESTATE,
                "the index holds a forest of HNSW sub-graphs: its part tables would keep the old numbering of the rows");
@@ -2716,6 +2722,7 @@ int hnswgpu_hnsw_update(hnswgpu_index *idx, const int32_t *ids, const float *row
     hipStream_t st = idx->stream;
     Call call;
     HG_TRY(call.open(idx, st));
+    HG_REFUSE_PCAF(idx, "hnswgpu_hnsw_update");
     HG_REQUIRE(idx->has_graph, HNSWGPU_ESTATE, "index has no graph (call hnswgpu_hnsw_build / hnswgpu_set_graph first)");
     HG_REQUIRE(idx->nparts == 0, HNSWGPU_ESTATE,
                "the index holds a forest of HNSW sub-graphs: an update would link a row across its part (rebuild the part's graph)");

@@ -1807,6 +1807,7 @@ static int set_ivf_impl(hnswgpu_index *idx, const float *centroids, int32_t nlis
     hipStream_t st = idx->stream;
     Call call;
     HG_TRY(call.open(idx, st));
+    HG_REFUSE_PCAF(idx, "hnswgpu_set_ivf");
     // every earlier call on this handle is ordered before `st` by the scope (the small HNSW searches on the slot streams
     // are waited for as well: lists that alias the base rows share them with the traversal): nothing can still read the
     // lists about to be freed (no device-wide synchronisation: other handles keep running)
@@ -1938,6 +1939,7 @@ int hnswgpu_ivf_build(hnswgpu_index *idx, int32_t nlist, int32_t max_iter, int64
     hipStream_t st = idx->stream;
     Call call;
     HG_TRY(call.open(idx, st));
+    HG_REFUSE_PCAF(idx, "hnswgpu_ivf_build");
     const int64_t n = idx->n;
     HG_TRY(call.quiesce());  // see set_ivf_impl: retires every earlier call on this handle, and only those
     free_ivf(idx);
@@ -2033,6 +2035,7 @@ int hnswgpu_ivf_add(hnswgpu_index *idx, const float *rows, int64_t m) {
     hipStream_t st = idx->stream;
     Call call;
     HG_TRY(call.open(idx, st));
+    HG_REFUSE_PCAF(idx, "hnswgpu_ivf_add");
     HG_REQUIRE(idx->nlist > 0, HNSWGPU_ESTATE, "index has no IVF lists (call hnswgpu_ivf_build / hnswgpu_set_ivf first)");
     HG_REQUIRE(!idx->has_graph, HNSWGPU_ESTATE,
                "the index holds an HNSW graph: rows added to the IVF lists would be missing from the graph");
@@ -2187,6 +2190,7 @@ int hnswgpu_ivf_remove(hnswgpu_index *idx, const int32_t *rows, int64_t m, int64
     hipStream_t st = idx->stream;
     Call call;
     HG_TRY(call.open(idx, st));
+    HG_REFUSE_PCAF(idx, "hnswgpu_ivf_remove");
     HG_REQUIRE(idx->nlist > 0, HNSWGPU_ESTATE, "index has no IVF lists (call hnswgpu_ivf_build / hnswgpu_set_ivf first)");
     HG_REQUIRE(idx->nparts == 0, HNSWGPU_ESTATE,
                "the index holds a forest of HNSW sub-graphs: its parts would keep the old numbering of the rows");
@@ -2340,6 +2344,7 @@ int hnswgpu_ivf_update(hnswgpu_index *idx, const int32_t *ids, const float *rows
     hipStream_t st = idx->stream;
     Call call;
     HG_TRY(call.open(idx, st));
+    HG_REFUSE_PCAF(idx, "hnswgpu_ivf_update");
     HG_REQUIRE(idx->nlist > 0, HNSWGPU_ESTATE, "index has no IVF lists (call hnswgpu_ivf_build / hnswgpu_set_ivf first)");
     HG_REQUIRE(idx->nparts == 0, HNSWGPU_ESTATE, "the index holds a forest of HNSW sub-graphs: its edges would stand for the old values of the rows");
     HG_REQUIRE(!idx->has_graph, HNSWGPU_ESTATE, "the index holds an HNSW graph: its edges would stand for the old values of the rows");

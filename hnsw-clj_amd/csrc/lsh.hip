@@ -258,6 +258,7 @@ int hnswgpu_lsh_build(hnswgpu_index *idx, int32_t tables, int32_t bits, int32_t 
     hipStream_t st = idx->stream;
     Call call;
     HG_TRY(call.open(idx, st));
+    HG_REFUSE_PCAF(idx, "hnswgpu_lsh_build");
     HG_TRY(lsh_install(idx, call, planes.data(), tables, bits, st));
     HG_TRY(call.sync());
     return call.close();
@@ -269,6 +270,7 @@ int hnswgpu_set_lsh(hnswgpu_index *idx, const float *planes, int32_t tables, int
     hipStream_t st = idx->stream;
     Call call;
     HG_TRY(call.open(idx, st));
+    HG_REFUSE_PCAF(idx, "hnswgpu_set_lsh");
     HG_TRY(lsh_install(idx, call, planes, tables, bits, st));
     HG_TRY(call.sync());
     return call.close();
@@ -337,6 +339,7 @@ int hnswgpu_lsh_add(hnswgpu_index *idx, const float *rows, int64_t m) {
     hipStream_t st = idx->stream;
     Call call;
     HG_TRY(call.open(idx, st));
+    HG_REFUSE_PCAF(idx, "hnswgpu_lsh_add");
     HG_REQUIRE(idx->lsh_tables > 0, HNSWGPU_ESTATE, "index has no LSH tables (call hnswgpu_lsh_build / hnswgpu_set_lsh first)");
     HG_REQUIRE(!idx->has_graph || idx->nparts > 0, HNSWGPU_ESTATE,
                "the index holds an HNSW graph: rows added to the LSH tables would be missing from the graph");
@@ -445,6 +448,7 @@ int hnswgpu_lsh_remove(hnswgpu_index *idx, const int32_t *rows, int64_t m, int64
     hipStream_t st = idx->stream;
     Call call;
     HG_TRY(call.open(idx, st));
+    HG_REFUSE_PCAF(idx, "hnswgpu_lsh_remove");
     HG_REQUIRE(idx->lsh_tables > 0, HNSWGPU_ESTATE, "index has no LSH tables (call hnswgpu_lsh_build / hnswgpu_set_lsh first)");
     HG_REQUIRE(!idx->has_graph || idx->nparts > 0, HNSWGPU_ESTATE,
                "the index holds an HNSW graph: it would keep the old numbering of the rows");
@@ -563,6 +567,7 @@ int hnswgpu_lsh_update(hnswgpu_index *idx, const int32_t *ids, const float *rows
     hipStream_t st = idx->stream;
     Call call;
     HG_TRY(call.open(idx, st));
+    HG_REFUSE_PCAF(idx, "hnswgpu_lsh_update");
     HG_REQUIRE(idx->lsh_tables > 0, HNSWGPU_ESTATE, "index has no LSH tables (call hnswgpu_lsh_build / hnswgpu_set_lsh first)");
     HG_REQUIRE(!idx->has_graph || idx->nparts > 0, HNSWGPU_ESTATE,
                "the index holds an HNSW graph: its edges would stand for the old values of the rows");

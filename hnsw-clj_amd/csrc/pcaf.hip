@@ -1,0 +1,325 @@
+// pcaf.hip -- P-HNSW on one handle (src/hnsw/ann/dimreduct/pcaf.clj): the random projection, the projected rows and their
+// norms as state of an ordinary cosine handle, and search-pcaf-parallel for a batch in three launches (C ABI:
+// include/hnswgpu.h, "P-HNSW"; kernels: pcaf_kernels.hpp).
+#include <string.h>
+
+#include <cmath>
+#include <vector>
+
+#include "engine.hpp"
+#include "javarandom.hpp"
+#include "pcaf_kernels.hpp"
+
+namespace hg {
+
+constexpr size_t kPcafLdsMax = 160 * 1024;   // LDS of a gfx950 workgroup
+constexpr int32_t kPcafSlice = 65536;        // queries (rows of hnswgpu_pcaf_project) per pass over the scratch buffers
+
+static int pcaf_tp(int32_t T) { return (T + 7) & ~7; }
+
+// X [m][dim] (row stride xld, device) -> out [m][Tp], norms [m]
+static int launch_pcaf_project(const hnswgpu_index *idx, const float *P, int32_t T, const float *X, int64_t xld, int64_t m, float *out,
+                               float *norms, hipStream_t st) {
+    if (m <= 0) return 0;
+    PcafProjectArgs a;
+    a.X = X;
+    a.xld = xld;
+    a.m = m;
+    a.dim = idx->dim;
+    a.vec = (xld % 4 == 0 && reinterpret_cast<uintptr_t>(X) % 16 == 0) ? 1 : 0;
+    a.P = P;
+    a.pld = idx->ld;
+    a.T = T;
+    a.Tp = pcaf_tp(T);
+    a.out = out;
+    a.norms = norms;
+    const dim3 grid(static_cast<unsigned>((m + kPcafProjRows - 1) / kPcafProjRows));
+    const int nt = (a.Tp + 31) / 32;
+#define CALL(NT) hipLaunchKernelGGL((pcaf_project_kernel<NT>), grid, dim3(kWG), 0, st, a)
+    if (nt <= 1) CALL(1);
+    else if (nt <= 2) CALL(2);
+    else if (nt <= 4) CALL(4);
+    else CALL(8);
+#undef CALL
+    HG_HIP(hipGetLastError());
+    return 0;
+}
+
+// The shape of a filter launch.  Waves per workgroup: as many of 8, 4, 2, 1 as the LDS holds (a wave's row buffer is
+// 32 (Tp + 4) floats beside the query block and the 2 kf keys per query).  Slabs: whole steps of nw * 32 rows, as many slabs as
+// give every CU a workgroup at the batch's number of query blocks -- at T = 100 a workgroup takes most of a CU's LDS, so more
+// workgroups than CUs would queue, and every slab costs the merge kf more keys per query.
+struct PcafFilterPlan {
+    int nw;
+    size_t lds;
+    int64_t slab_rows;
+    int32_t nslabs;
+};
+static PcafFilterPlan pcaf_filter_plan(const hnswgpu_index *idx, int32_t nq, int32_t kf) {
+    PcafFilterPlan p;
+    p.nw = 8;
+    while (p.nw > 1 && pcaf_filter_lds(idx->pcaf_Tp, kf, p.nw) > kPcafLdsMax) p.nw >>= 1;
+    p.lds = pcaf_filter_lds(idx->pcaf_Tp, kf, p.nw);
+    const int64_t step = p.nw * 32, steps = (idx->n + step - 1) / step, qblocks = (nq + 31) / 32;
+    const int64_t want = std::max<int64_t>(1, (idx->cus + qblocks - 1) / qblocks);
+    p.slab_rows = std::max<int64_t>(1, (steps + want - 1) / want) * step;
+    p.nslabs = static_cast<int32_t>((idx->n + p.slab_rows - 1) / p.slab_rows);
+    return p;
+}
+
+static int launch_pcaf_filter(const PcafFilterArgs &a, const PcafFilterPlan &p, hipStream_t st) {
+    const int nv = a.Tp / 8;
+    const dim3 grid(static_cast<unsigned>(static_cast<int64_t>((a.nq + 31) / 32) * a.nslabs)), block(p.nw * kWave);
+#define CALL(NV)                                                                                                             \
+    do {                                                                                                                     \
+        static bool attr_done[64] = {};                                                                                      \
+        if (attr_needed(attr_done))                                                                                          \
+            HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pcaf_filter_kernel<NV>),                              \
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kPcafLdsMax)));          \
+        hipLaunchKernelGGL((pcaf_filter_kernel<NV>), grid, block, p.lds, st, a);                                             \
+    } while (0)
+    if (nv <= 4) CALL(4);
+    else if (nv <= 8) CALL(8);
+    else if (nv <= 13) CALL(13);
+    else if (nv <= 16) CALL(16);
+    else if (nv <= 24) CALL(24);
+    else CALL(32);
+#undef CALL
+    HG_HIP(hipGetLastError());
+    return 0;
+}
+
+static int launch_pcaf_refine(int nch, const PcafRefineArgs &a, int32_t nq, hipStream_t st) {
+#define CALL(N, R, L) hipLaunchKernelGGL((pcaf_refine_kernel<N>), dim3(nq), dim3(kWG), 0, st, a)
+    HG_DISPATCH(nch, false, CALL);
+#undef CALL
+    HG_HIP(hipGetLastError());
+    return 0;
+}
+
+static const char *pcaf_other_state(const hnswgpu_index *idx) {
+    if (idx->nparts > 0) return "an HNSW forest";
+    if (idx->has_graph) return "an HNSW graph";
+    if (idx->nlist > 0) return "IVF lists";
+    if (idx->lsh_tables > 0) return "LSH tables";
+    return nullptr;
+}
+
+// What a build or an install stages: the handle takes it over only when every step has succeeded.
+struct PcafStaged {
+    float *proj = nullptr, *low = nullptr, *lnorms = nullptr;
+    ~PcafStaged() {
+        void *ptrs[] = {proj, low, lnorms};
+        for (void *p : ptrs)
+            if (p) (void)hipFree(p);
+    }
+};
+
+// P: [T][dim] on the host
+static int pcaf_install(hnswgpu_index *idx, Call &call, const float *P, int32_t T, hipStream_t st) {
+    const char *other = pcaf_other_state(idx);
+    HG_REQUIRE(!other, HNSWGPU_ESTATE, "index holds %s: P-HNSW state goes on a handle that holds rows only", other);
+    const int64_t n = idx->n, ld = idx->ld;
+    const int Tp = pcaf_tp(T);
+    PcafStaged s;
+    HG_HIP(hipMalloc(reinterpret_cast<void **>(&s.proj), sizeof(float) * T * ld));
+    if (ld != idx->dim) HG_HIP(hipMemsetAsync(s.proj, 0, sizeof(float) * T * ld, st));
+    HG_HIP(hipMemcpy2DAsync(s.proj, sizeof(float) * ld, P, sizeof(float) * idx->dim, sizeof(float) * idx->dim, T, hipMemcpyHostToDevice, st));
+    if (n > 0) {
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&s.low), sizeof(float) * n * Tp));
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&s.lnorms), sizeof(float) * n));
+        HG_TRY(launch_pcaf_project(idx, s.proj, T, idx->d_base, ld, n, s.low, s.lnorms, st));
+    }
+    std::vector<float> keep(P, P + static_cast<size_t>(T) * idx->dim);
+    HG_TRY(call.quiesce());  // the upload is done, and no search reads the old state any more
+    std::swap(idx->d_pcaf_proj, s.proj);  // (what the handle had goes with `s`)
+    std::swap(idx->d_pcaf_low, s.low);
+    std::swap(idx->d_pcaf_lnorms, s.lnorms);
+    idx->h_pcaf_proj.swap(keep);
+    idx->pcaf_T = T;
+    idx->pcaf_Tp = Tp;
+    return 0;
+}
+
+static int check_pcaf_shape(const hnswgpu_index *idx, int32_t T) {
+    HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
+    HG_REQUIRE(idx->metric == METRIC_COS, HNSWGPU_EINVAL, "P-HNSW needs a cosine handle (pcaf.clj uses cosine in both phases)");
+    HG_REQUIRE(T >= 1, HNSWGPU_EINVAL, "n_components must be >= 1");
+    HG_REQUIRE(T <= kPcafMaxT, HNSWGPU_ELIMIT, "n_components > %d is not supported", kPcafMaxT);
+    return 0;
+}
+
+#define HG_PCAF_STATE(idx) \
+    HG_REQUIRE((idx)->pcaf_T > 0, HNSWGPU_ESTATE, "index has no P-HNSW state (call hnswgpu_pcaf_build / hnswgpu_set_pcaf first)")
+
+// d_Q [nq][dim] -> d_ids / d_dist [nq][k] on `st`; only enqueues: projection, filter, merge + refine per slice of queries
+static int pcaf_search_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t kf, int32_t *d_ids, float *d_dist,
+                               hipStream_t st) {
+    const int Tp = idx->pcaf_Tp;
+    const int32_t slice = std::min(nq, kPcafSlice);
+    const PcafFilterPlan plan = pcaf_filter_plan(idx, slice, kf);
+    HG_TRY(idx->s_pcaf_q.ensure(sizeof(float) * static_cast<size_t>(slice) * (Tp + 1)));
+    HG_TRY(idx->s_pcaf_keys.ensure(sizeof(uint64_t) * static_cast<size_t>(slice) * plan.nslabs * kf));
+    float *qlow = idx->s_pcaf_q.as<float>(), *qnorms = qlow + static_cast<size_t>(slice) * Tp;
+    for (int32_t q0 = 0; q0 < nq; q0 += slice) {
+        const int32_t m = std::min(slice, nq - q0);
+        const float *Qs = d_Q + static_cast<int64_t>(q0) * idx->dim;
+        HG_TRY(launch_pcaf_project(idx, idx->d_pcaf_proj, idx->pcaf_T, Qs, idx->dim, m, qlow, qnorms, st));
+        PcafFilterArgs f;
+        f.rows = idx->d_pcaf_low;
+        f.row_norms = idx->d_pcaf_lnorms;
+        f.n = idx->n;
+        f.Q = qlow;
+        f.q_norms = qnorms;
+        f.nq = m;
+        f.Tp = Tp;
+        f.kf = kf;
+        f.slab_rows = plan.slab_rows;
+        f.nslabs = plan.nslabs;
+        f.keys = idx->s_pcaf_keys.as<uint64_t>();
+        HG_TRY(launch_pcaf_filter(f, plan, st));
+        PcafRefineArgs r;
+        r.keys = f.keys;
+        r.nslabs = plan.nslabs;
+        r.kf = kf;
+        r.k = k;
+        r.rows = idx->d_base;
+        r.row_norms = idx->d_norms;
+        r.ld = idx->ld;
+        r.Q = Qs;
+        r.qld = idx->dim;
+        r.dim = idx->dim;
+        r.out_ids = d_ids + static_cast<int64_t>(q0) * k;
+        r.out_dist = d_dist + static_cast<int64_t>(q0) * k;
+        HG_TRY(launch_pcaf_refine(idx->nch, r, m, st));
+    }
+    return 0;
+}
+
+// Everything hnswgpu_pcaf_search* checks before the lock; *kf: min(k_filter, 3 k) (pcaf.clj:236), not yet clamped to n
+static int check_pcaf_search(const hnswgpu_index *idx, const void *Q, int32_t nq, int32_t k, int32_t k_filter, const void *ids,
+                             const void *dist, int32_t *kf) {
+    HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
+    HG_REQUIRE(nq >= 0, HNSWGPU_EINVAL, "nq < 0");
+    HG_REQUIRE(k >= 1, HNSWGPU_EINVAL, "k must be >= 1");
+    HG_REQUIRE(k <= 1024, HNSWGPU_ELIMIT, "k > 1024 is not supported");
+    HG_REQUIRE(nq == 0 || (Q && ids && dist), HNSWGPU_EINVAL, "null argument");
+    *kf = static_cast<int32_t>(std::min<int64_t>(k_filter <= 0 ? 32 : k_filter, 3 * static_cast<int64_t>(k)));  // (:122, :236)
+    return 0;
+}
+
+}  // namespace hg
+
+using namespace hg;
+
+extern "C" {
+
+int hnswgpu_pcaf_build(hnswgpu_index *idx, int32_t n_components, int64_t seed) {
+    HG_TRY(check_pcaf_shape(idx, n_components));
+    // (create-random-projection, :33-45: row by row, float(gaussian) * float(1 / sqrt(target-dim)))
+    std::vector<float> P(static_cast<size_t>(n_components) * idx->dim);
+    const float scale = static_cast<float>(1.0 / std::sqrt(static_cast<double>(n_components)));
+    JavaRandom rng(seed);
+    for (float &p : P) p = scale * static_cast<float>(rng.next_gaussian());
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_TRY(pcaf_install(idx, call, P.data(), n_components, st));
+    HG_TRY(call.sync());
+    return call.close();
+}
+
+int hnswgpu_set_pcaf(hnswgpu_index *idx, const float *projection, int32_t n_components) {
+    HG_TRY(check_pcaf_shape(idx, n_components));
+    HG_REQUIRE(projection, HNSWGPU_EINVAL, "null argument");
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_TRY(pcaf_install(idx, call, projection, n_components, st));
+    HG_TRY(call.sync());
+    return call.close();
+}
+
+int hnswgpu_pcaf_sizes(hnswgpu_index *idx, int32_t *n_components) {
+    HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (n_components) *n_components = idx->pcaf_T;
+    return 0;
+}
+
+int hnswgpu_pcaf_get(hnswgpu_index *idx, float *projection, float *low_rows) {
+    HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_PCAF_STATE(idx);
+    if (projection) memcpy(projection, idx->h_pcaf_proj.data(), sizeof(float) * idx->h_pcaf_proj.size());
+    if (low_rows && idx->n > 0)
+        HG_HIP(hipMemcpy2DAsync(low_rows, sizeof(float) * idx->pcaf_T, idx->d_pcaf_low, sizeof(float) * idx->pcaf_Tp,
+                                sizeof(float) * idx->pcaf_T, idx->n, hipMemcpyDeviceToHost, st));
+    HG_TRY(call.sync());
+    return call.close();
+}
+
+int hnswgpu_pcaf_project(hnswgpu_index *idx, const float *X, int64_t m, float *out) {
+    HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
+    HG_REQUIRE(m >= 0, HNSWGPU_EINVAL, "m < 0");
+    HG_REQUIRE(m == 0 || (X && out), HNSWGPU_EINVAL, "null argument");
+    if (m == 0) return 0;
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_PCAF_STATE(idx);
+    const int T = idx->pcaf_T, Tp = idx->pcaf_Tp;
+    const int32_t slice = static_cast<int32_t>(std::min<int64_t>(m, kPcafSlice));
+    HG_TRY(idx->s_pcaf_q.ensure(sizeof(float) * static_cast<size_t>(slice) * (Tp + 1)));
+    float *low = idx->s_pcaf_q.as<float>(), *norms = low + static_cast<size_t>(slice) * Tp;
+    for (int64_t r0 = 0; r0 < m; r0 += slice) {
+        const int32_t c = static_cast<int32_t>(std::min<int64_t>(slice, m - r0));
+        HG_TRY(upload_queries(idx, X + r0 * idx->dim, c, st));
+        HG_TRY(launch_pcaf_project(idx, idx->d_pcaf_proj, T, idx->s_q.as<float>(), idx->dim, c, low, norms, st));
+        HG_HIP(hipMemcpy2DAsync(out + r0 * T, sizeof(float) * T, low, sizeof(float) * Tp, sizeof(float) * T, c, hipMemcpyDeviceToHost, st));
+    }
+    HG_TRY(call.sync());
+    return call.close();
+}
+
+int hnswgpu_pcaf_search_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t k_filter, int32_t *d_out_ids,
+                            float *d_out_dist, void *stream) {
+    int32_t kf;
+    HG_TRY(check_pcaf_search(idx, d_Q, nq, k, k_filter, d_out_ids, d_out_dist, &kf));
+    if (nq == 0) return 0;
+    HG_REQUIRE(idx->n > 0, HNSWGPU_ESTATE, "empty index: use the host entry point");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_PCAF_STATE(idx);
+    kf = static_cast<int32_t>(std::min<int64_t>(kf, idx->n));
+    HG_REQUIRE(kf <= kPcafMaxKf, HNSWGPU_ELIMIT, "min(k_filter, 3 k, n) > %d is not supported", kPcafMaxKf);
+    HG_TRY(pcaf_search_enqueue(idx, d_Q, nq, k, kf, d_out_ids, d_out_dist, st));
+    return call.close();
+}
+
+int hnswgpu_pcaf_search(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t k_filter, int32_t *out_ids,
+                        float *out_dist) {
+    int32_t kf;
+    HG_TRY(check_pcaf_search(idx, Q, nq, k, k_filter, out_ids, out_dist, &kf));
+    if (nq == 0) return 0;
+    const int64_t cnt = static_cast<int64_t>(nq) * k;
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_PCAF_STATE(idx);
+    if (idx->n == 0) {
+        fill_empty(out_ids, out_dist, cnt);
+        return call.close();
+    }
+    kf = static_cast<int32_t>(std::min<int64_t>(kf, idx->n));
+    HG_REQUIRE(kf <= kPcafMaxKf, HNSWGPU_ELIMIT, "min(k_filter, 3 k, n) > %d is not supported", kPcafMaxKf);
+    HG_TRY(call.stage_in(Q, nq, k));
+    HG_TRY(pcaf_search_enqueue(idx, idx->s_q.as<float>(), nq, k, kf, idx->s_ids.as<int32_t>(), idx->s_outd.as<float>(), st));
+    HG_TRY(call.stage_out(out_ids, out_dist, cnt));
+    return call.close();
+}
+
+}  // extern "C"

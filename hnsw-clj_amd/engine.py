@@ -901,6 +901,55 @@ class Index:
         check(lib().hnswgpu_dense_distances_dev(self._h, Q.data_ptr(), Q.shape[0], out.data_ptr(), st))
         return out
 
+    # -- P-HNSW on one handle (include/hnswgpu.h: "P-HNSW")
+    def pcaf_build(self, n_components=100, seed=42):
+        """hnswgpu_pcaf_build: the projection from java.util.Random(seed) as the reference draws it, every row projected."""
+        check(lib().hnswgpu_pcaf_build(self._h, n_components, seed))
+
+    def set_pcaf(self, projection):
+        """hnswgpu_set_pcaf: the caller's projection (n_components, dim)."""
+        projection = _f32(projection)
+        if projection.ndim != 2 or projection.shape[1] != self.dim:
+            raise ValueError("projection must be (n_components, %d), got %s" % (self.dim, projection.shape))
+        check(lib().hnswgpu_set_pcaf(self._h, _p(projection), projection.shape[0]))
+
+    def pcaf_sizes(self):
+        """n_components, 0 on a handle without P-HNSW state."""
+        t = C.c_int32()
+        check(lib().hnswgpu_pcaf_sizes(self._h, C.byref(t)))
+        return t.value
+
+    def pcaf_get(self):
+        """(projection (T, dim), projected rows (n, T))."""
+        t = self.pcaf_sizes()
+        projection = np.empty((t, self.dim), np.float32)
+        low = np.empty((self.n, t), np.float32)
+        check(lib().hnswgpu_pcaf_get(self._h, _p(projection), _p(low)))
+        return projection, low
+
+    def pcaf_project(self, X):
+        """project-vector-simd for every row of X (m, dim) -> (m, T), by the kernel that projected the base rows."""
+        X = _queries(X, self.dim)
+        out = np.empty((len(X), self.pcaf_sizes()), np.float32)
+        check(lib().hnswgpu_pcaf_project(self._h, _p(X), len(X), _p(out)))
+        return out
+
+    def pcaf_search(self, Q, k, k_filter=0):
+        """hnswgpu_pcaf_search: min(k_filter, 3 k, n) candidates by projected cosine (k_filter 0: the reference's 32), their
+        exact cosine distances, the best k; -1 / +inf where fewer are found."""
+        Q = _queries(Q, self.dim)
+        ids = np.empty((len(Q), k), np.int32)
+        d = np.empty((len(Q), k), np.float32)
+        check(lib().hnswgpu_pcaf_search(self._h, _p(Q), len(Q), k, int(k_filter or 0), _p(ids), _p(d)))
+        return ids, d
+
+    def pcaf_search_dev(self, Q, k, k_filter=0, out=None):
+        """hnswgpu_pcaf_search_dev on torch's current stream: enqueues only, nothing is read back."""
+        Q, ids, d, st = self._dev_args(Q, k, out)
+        check(lib().hnswgpu_pcaf_search_dev(self._h, Q.data_ptr(), Q.shape[0], k, int(k_filter or 0), ids.data_ptr(),
+                                            d.data_ptr(), st))
+        return ids, d
+
     # -- measurement
     def set_profiling(self, on=True):
         check(lib().hnswgpu_set_profiling(self._h, 1 if on else 0))

@@ -9,6 +9,10 @@ Device composition over the C ABI:
   * phase 2 is ``hnswgpu_rerank`` on the handle that holds the original rows (:239-253).
 The reference runs both phases in float32 through the Vector API, whose lane-reduction order is hardware
 dependent; the kernels' fixed f32 orders are within the same 1e-7-relative envelope.
+
+``one_handle=True`` keeps the same index on ONE handle instead (include/hnswgpu.h, "P-HNSW"): the projection and the projected
+rows are state of the handle that holds the original rows, and a search is hnswgpu_pcaf_search(_dev) -- three launches, no
+[queries][rows] intermediate.  The composition stays the default.
 """
 import numpy as np
 
@@ -32,7 +36,7 @@ class PCAFIndex:
     def __init__(self, projection, proj_index, low_index, high_index, ids, k_filter):
         self.projection = projection      # float32 [target_dim, original_dim]
         self.proj_index = proj_index      # rows = projection matrix, metric DOT
-        self.low_index = low_index        # projected rows, cosine
+        self.low_index = low_index        # projected rows, cosine (one handle: None, like proj_index -- high_index holds all)
         self.high_index = high_index      # original rows (float32), cosine
         self.ids = ids
         self.k_filter = k_filter
@@ -40,21 +44,30 @@ class PCAFIndex:
 
     def close(self):
         for h in (self.proj_index, self.low_index, self.high_index):
-            h.close()
+            if h is not None:
+                h.close()
 
 
 def project_dev(index_or_proj, X):
     """project-vector-simd (:47-80) for every row of the CUDA tensor X."""
     proj = index_or_proj.proj_index if isinstance(index_or_proj, PCAFIndex) else index_or_proj
+    if proj is None:
+        raise ValueError("a one-handle index projects inside hnswgpu_pcaf_search (Index.pcaf_project for host arrays)")
     return -proj.dense_distances_dev(X)
 
 
-def build_pcaf_index(data, n_components=100, k_filter=32, show_progress=False, num_threads=4, device=0):
+def build_pcaf_index(data, n_components=100, k_filter=32, show_progress=False, num_threads=4, device=0, one_handle=False):
     """pcaf.clj:116-194 (``num_threads`` kept for signature parity)"""
     import torch
 
     ids, base = _split(data)
     dim = base.shape[1]
+    if one_handle:
+        high_index = engine.Index(base, engine.COSINE, device)
+        high_index.pcaf_build(n_components, 42)
+        if show_progress:
+            print("P-HNSW: %d vectors, %d -> %d dims" % (len(ids), dim, n_components))
+        return PCAFIndex(high_index.pcaf_get()[0], None, None, high_index, ids, k_filter)
     P = create_random_projection(dim, n_components)
     proj = engine.Index(P, engine.DOT, device)
     dev = torch.device("cuda", device)
@@ -71,6 +84,8 @@ def build_pcaf_index(data, n_components=100, k_filter=32, show_progress=False, n
 
 def search_batch_dev(index, Q, k, k_filter=None):
     """Q: [nq, dim] float32 CUDA tensor -> (data positions [nq, k] int32, exact cosine distances [nq, k])."""
+    if index.low_index is None:
+        return index.high_index.pcaf_search_dev(Q, int(k), int(k_filter or index.k_filter))
     kf = min(int(k_filter or index.k_filter), 3 * int(k))            # :236
     kf = max(1, min(kf, index.low_index.n))
     cand, _ = index.low_index.exact_knn_dev(project_dev(index, Q), kf)

@@ -1037,6 +1037,46 @@ int hnswgpu_lsh_search_filtered_each_dev(hnswgpu_index *idx, const float *d_Q, i
                                          int32_t probe_radius, int32_t take_main, int32_t take_flip,
                                          const uint32_t *d_allow_each, int32_t *d_out_ids, float *d_out_dist, void *stream);
 
+/* ---- P-HNSW on one handle (hnsw-clj_amd/csrc/pcaf.hip, pcaf_kernels.hpp) --------------------------------------------
+ * src/hnsw/ann/dimreduct/pcaf.clj: a Gaussian random projection to n_components = T dimensions, a brute-force cosine
+ * search among the projected rows for kf candidates, and an exact cosine re-rank of those on the original rows.  The
+ * reference's arithmetic is float32 in both phases, and so is this.  The state -- projection, projected rows, their norms --
+ * lives on an ordinary COSINE handle beside its base rows; a search is one call and three launches (projection of the
+ * queries on the f32 matrix cores; the filter: a block of 32 projected queries against a slab of projected rows per
+ * workgroup, selection inside the kernel; merge of the slabs' candidates + exact distances + top k), and nothing of the
+ * shape [queries][rows] is ever written.
+ *   hnswgpu_pcaf_build: create-random-projection (:33-45) -- Random(seed) gaussians in row-major order, each
+ *     float(g) * float(1 / sqrt(T)); seed 42 is the reference's matrix bit for bit -- then every base row projected on the
+ *     device (project-vector-simd, :47-80) and kept with its norm (build-pcaf-index, :116-194).
+ *   hnswgpu_set_pcaf: the same with the caller's projection [T][dim], row-major.
+ *   hnswgpu_pcaf_sizes: *n_components = T, 0 on a handle without the state.
+ *   hnswgpu_pcaf_get: projection [T][dim] and / or low_rows [n][T] (unpadded); either pointer may be null.
+ *   hnswgpu_pcaf_project: project-vector-simd (:47-80) for m rows X [m][dim] -> out [m][T].
+ *   hnswgpu_pcaf_search / _dev: search-pcaf-parallel (:195-253) for a batch.  kf = min(k_filter, 3 k, n), k_filter <= 0
+ *     means 32 (:122); the kf rows nearest by cosine in the projected space (a zero norm on either side: distance 1.0, as
+ *     in simd.clj) get their exact cosine distance from the f32 base rows with the arithmetic of hnswgpu_rerank -- the same
+ *     bits on the same candidates --, are sorted ascending, and min(k, kf) are returned, -1 / +inf behind them.  Ties in
+ *     either phase go to the lower row id; the reference's order among ties is that of a hash map's iteration, i.e.
+ *     unspecified.  _dev only enqueues on `stream`.
+ *   Errors: -1 a null handle or pointer, a non-cosine handle (the reference uses cosine in both phases), n_components < 1,
+ *     k < 1; -5 n_components > 256, an effective kf > 128 (the reference's largest preset is 64), k > 1024; -3 a search,
+ *     get or project on a handle without the state.  nq == 0 returns 0; n == 0: the host search fills the padding, the
+ *     _dev search returns -3, as hnswgpu_exact_knn / _dev do.
+ *   Other state: hnswgpu_pcaf_build / hnswgpu_set_pcaf return -3 on a handle that holds a graph, a forest, IVF lists or
+ *     LSH tables, and every call that installs one of those or adds, removes or updates rows returns -3 on a handle with
+ *     P-HNSW state (the projected rows would go stale); the message names why; the handle is untouched.
+ *   Out of scope: mutating a P-HNSW handle; filtered P-HNSW search; the index file -- hnswgpu_save writes such a handle
+ *     without the state, as it does LSH tables; groups and shards. */
+int hnswgpu_pcaf_build(hnswgpu_index *idx, int32_t n_components, int64_t seed);
+int hnswgpu_set_pcaf(hnswgpu_index *idx, const float *projection, int32_t n_components);
+int hnswgpu_pcaf_sizes(hnswgpu_index *idx, int32_t *n_components);
+int hnswgpu_pcaf_get(hnswgpu_index *idx, float *projection, float *low_rows);
+int hnswgpu_pcaf_project(hnswgpu_index *idx, const float *X, int64_t m, float *out);
+int hnswgpu_pcaf_search(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t k_filter, int32_t *out_ids,
+                        float *out_dist);
+int hnswgpu_pcaf_search_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t k_filter, int32_t *d_out_ids,
+                            float *d_out_dist, void *stream);
+
 /* ---- ONE index over several GPUs (hnsw-clj_amd/csrc/group.hip) ---------------------------------------------------
  * The reference shards inside one process: search-partitioned scatters a query to its partitions, takes a top-k per
  * partition, concatenates, sorts and takes k (src/hnsw/ann/partition/partitioned_hnsw.clj:149-196).  A group gives the
