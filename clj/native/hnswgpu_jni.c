@@ -356,6 +356,58 @@ JNIEXPORT jint JNICALL Java_hnsw_gpu_Native_lshSearchFilteredEach(JNIEnv *env, j
     return rc;
 }
 
+/* the allow-mask through P-HNSW's low-dimensional filter: the candidates of phase 1 are the nearest passing rows (hnswgpu_pcaf_search_filtered) */
+JNIEXPORT jint JNICALL Java_hnsw_gpu_Native_pcafSearchFiltered(JNIEnv *env, jclass c, jlong h, jfloatArray q, jint nq, jint k, jint k_filter,
+        jintArray allow, jintArray ids, jfloatArray dist) {
+    if (!q || !allow || !ids || !dist) return throw_iae(env, "pcafSearchFiltered: null array");
+    jfloat *pq = (*env)->GetFloatArrayElements(env, q, NULL);
+    jint *pa = (*env)->GetIntArrayElements(env, allow, NULL);
+    jint *pi = (*env)->GetIntArrayElements(env, ids, NULL);
+    jfloat *pd = (*env)->GetFloatArrayElements(env, dist, NULL);
+    int rc = (pq && pa && pi && pd) ? hnswgpu_pcaf_search_filtered((hnswgpu_index *)(intptr_t)h, pq, nq, k, k_filter, (const uint32_t *)pa, (int32_t *)pi, pd)
+                                    : HNSWGPU_ENOMEM; /* OutOfMemoryError is pending */
+    if (pq) (*env)->ReleaseFloatArrayElements(env, q, pq, JNI_ABORT);
+    if (pa) (*env)->ReleaseIntArrayElements(env, allow, pa, JNI_ABORT);
+    if (pi) (*env)->ReleaseIntArrayElements(env, ids, pi, 0);
+    if (pd) (*env)->ReleaseFloatArrayElements(env, dist, pd, 0);
+    if (rc != 0 && rc != HNSWGPU_ENOMEM) throw_last(env);
+    return rc;
+}
+
+/* ... with one mask per query: `allow` holds nq rows of (n + 31) / 32 ints, row q is query q's mask (hnswgpu_pcaf_search_filtered_each) */
+JNIEXPORT jint JNICALL Java_hnsw_gpu_Native_pcafSearchFilteredEach(JNIEnv *env, jclass c, jlong h, jfloatArray q, jint nq, jint k, jint k_filter,
+        jintArray allow, jintArray ids, jfloatArray dist) {
+    if (!q || !allow || !ids || !dist) return throw_iae(env, "pcafSearchFilteredEach: null array");
+    jfloat *pq = (*env)->GetFloatArrayElements(env, q, NULL);
+    jint *pa = (*env)->GetIntArrayElements(env, allow, NULL);
+    jint *pi = (*env)->GetIntArrayElements(env, ids, NULL);
+    jfloat *pd = (*env)->GetFloatArrayElements(env, dist, NULL);
+    int rc = (pq && pa && pi && pd) ? hnswgpu_pcaf_search_filtered_each((hnswgpu_index *)(intptr_t)h, pq, nq, k, k_filter, (const uint32_t *)pa, (int32_t *)pi, pd)
+                                    : HNSWGPU_ENOMEM; /* OutOfMemoryError is pending */
+    if (pq) (*env)->ReleaseFloatArrayElements(env, q, pq, JNI_ABORT);
+    if (pa) (*env)->ReleaseIntArrayElements(env, allow, pa, JNI_ABORT);
+    if (pi) (*env)->ReleaseIntArrayElements(env, ids, pi, 0);
+    if (pd) (*env)->ReleaseFloatArrayElements(env, dist, pd, 0);
+    if (rc != 0 && rc != HNSWGPU_ENOMEM) throw_last(env);
+    return rc;
+}
+
+/* the _dev forms: device addresses and a hipStream_t as longs; they only enqueue on the stream and read nothing back */
+JNIEXPORT jint JNICALL Java_hnsw_gpu_Native_pcafSearchFilteredDev(JNIEnv *env, jclass c, jlong h, jlong d_q, jint nq, jint k, jint k_filter,
+        jlong d_allow, jlong d_ids, jlong d_dist, jlong stream) {
+    int rc = hnswgpu_pcaf_search_filtered_dev((hnswgpu_index *)(intptr_t)h, (const float *)(intptr_t)d_q, nq, k, k_filter, (const uint32_t *)(intptr_t)d_allow,
+        (int32_t *)(intptr_t)d_ids, (float *)(intptr_t)d_dist, (void *)(intptr_t)stream);
+    if (rc != 0) throw_last(env);
+    return rc;
+}
+JNIEXPORT jint JNICALL Java_hnsw_gpu_Native_pcafSearchFilteredEachDev(JNIEnv *env, jclass c, jlong h, jlong d_q, jint nq, jint k, jint k_filter,
+        jlong d_allow, jlong d_ids, jlong d_dist, jlong stream) {
+    int rc = hnswgpu_pcaf_search_filtered_each_dev((hnswgpu_index *)(intptr_t)h, (const float *)(intptr_t)d_q, nq, k, k_filter, (const uint32_t *)(intptr_t)d_allow,
+        (int32_t *)(intptr_t)d_ids, (float *)(intptr_t)d_dist, (void *)(intptr_t)stream);
+    if (rc != 0) throw_last(env);
+    return rc;
+}
+
 /* rows leave a live hybrid LSH index (hnswgpu_lsh_remove): `rows` holds m row ids in any order, repeats count once; the kept rows
  * are renumbered densely in their old order.  Returns the rows the handle holds afterwards, or the negative error code (the
  * exception is pending).  Unverified like the rest of this file: no JVM where the library is built and tested. */

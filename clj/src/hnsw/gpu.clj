@@ -30,6 +30,7 @@
      (search-lsh-batch index queries k :mode :balanced)
      (search-lsh-filtered index query-vec k filter-fn :mode :balanced) ; the allow-mask through the bucket scan: hnswgpu_lsh_search_filtered
      (search-lsh-batch-filtered-each index queries k filter-fns)      ; one predicate per query: hnswgpu_lsh_search_filtered_each
+     (search-pcaf-batch-filtered-each pcaf-index queries k filter-fns) ; P-HNSW, candidates among the passing rows: hnswgpu_pcaf_search_filtered_each
      (from-ultra-graph graph)                                        ; a graph built by the reference's own insert-single
      (from-ivf-flat-index ivf)                                       ; an IVFFlatIndex built by the reference's own k-means
      (save idx path) / (load-index path ids)                         ; helper/index-io save-index / load-index
@@ -433,6 +434,80 @@
               ds (.allocate arena (* 4 nq k) 4)]
           (check (.invokeWithArguments ^MethodHandle @h-lshsearch-filtered-each
                                        [(:handle idx) qa (int nq) (int k) (int p) (int r) (int (* 2 k)) (int k) mask ids ds]))
+          (doseq [[j q] (map-indexed vector qs)]
+            (aset out q (results idx ids ds j k)))))
+      (vec out))))
+
+;; ---- P-HNSW on one handle, filtered: the allow-mask through the low-dimensional filter (hnswgpu_pcaf_search_filtered / _each) ----
+(def ^:private h-pcafbuild (delay (fn-handle "hnswgpu_pcaf_build" (FunctionDescriptor/of I (into-array [P I L])))))
+(def ^:private h-pcafsearch-filtered
+  (delay (fn-handle "hnswgpu_pcaf_search_filtered" (FunctionDescriptor/of I (into-array [P P I I I P P P])))))
+(def ^:private h-pcafsearch-filtered-each
+  (delay (fn-handle "hnswgpu_pcaf_search_filtered_each" (FunctionDescriptor/of I (into-array [P P I I I P P P])))))
+;; the _dev forms take device addresses (queries, mask words, results) and a hipStream_t, and only enqueue: for hosts that keep
+;; their batches in device memory; nothing here allocates such memory
+(def h-pcafsearch-filtered-dev
+  (delay (fn-handle "hnswgpu_pcaf_search_filtered_dev" (FunctionDescriptor/of I (into-array [P P I I I P P P P])))))
+(def h-pcafsearch-filtered-each-dev
+  (delay (fn-handle "hnswgpu_pcaf_search_filtered_each_dev" (FunctionDescriptor/of I (into-array [P P I I I P P P P])))))
+
+(defn build-pcaf-index
+  "hnsw.ann.dimreduct.pcaf/build-pcaf-index (pcaf.clj:116-194) on ONE handle: data = seq of [id ^doubles vector]; the projection
+   is the reference's (Random. 42) matrix, the projected rows live beside the originals (hnswgpu_pcaf_build)."
+  [data & {:keys [n-components seed] :or {n-components 100 seed 42}}]
+  (let [idx (create data :cosine :pcaf)]
+    (check (.invokeWithArguments ^MethodHandle @h-pcafbuild [(:handle idx) (int n-components) (long seed)]))
+    idx))
+
+(defn search-pcaf-batch-filtered
+  "search-knn-filtered* through phase 1 of P-HNSW for a batch with ONE predicate on the caller's ids, evaluated once per row here
+   into the call's allow-mask: the min(k-filter, 3k) candidates are the nearest PASSING rows in the projected space and only those
+   are fetched -- not protocol.clj:97-102's search 3k, drop, keep k, which at a low pass rate returns nothing.  :k-filter 0 is the
+   reference's 32."
+  [idx queries k filter-fn & {:keys [k-filter] :or {k-filter 0}}]
+  (if (or (empty? (:ids idx)) (empty? queries))
+    (mapv (constantly []) queries)
+    (with-open [arena (Arena/ofConfined)]
+      (let [nq (count queries)
+            words (quot (+ (count (:ids idx)) 31) 32)
+            mask (.allocate arena (* 4 words) 4)
+            _ (MemorySegment/copy (MemorySegment/ofArray (lsh-mask-of idx filter-fn words)) 0 mask 0 (* 4 words))
+            q (floats-of arena (vec queries) (:dim idx))
+            ids (.allocate arena (* 4 nq k) 4)
+            ds (.allocate arena (* 4 nq k) 4)]
+        (check (.invokeWithArguments ^MethodHandle @h-pcafsearch-filtered
+                                     [(:handle idx) q (int nq) (int k) (int k-filter) mask ids ds]))
+        (mapv #(results idx ids ds % k) (range nq))))))
+
+(defn search-pcaf-batch-filtered-each
+  "search-pcaf-batch-filtered with one predicate PER QUERY (filter-fns: as many as queries).  An identical predicate is evaluated
+   once; the batch goes through one hnswgpu_pcaf_search_filtered_each call, equal predicates adjacent (a query block fetches the
+   union of its masks), and the caller's order is restored."
+  [idx queries k filter-fns & {:keys [k-filter] :or {k-filter 0}}]
+  (assert (= (count queries) (count filter-fns)) "one filter-fn per query")
+  (cond
+    (empty? queries) []
+    (empty? (:ids idx)) (mapv (constantly []) queries)
+    (every? #(identical? % (first filter-fns)) filter-fns)
+    (search-pcaf-batch-filtered idx queries k (first filter-fns) :k-filter k-filter)
+    :else
+    (let [words (quot (+ (count (:ids idx)) 31) 32)
+          distinct-fns (vec (distinct filter-fns))
+          fn-no (into {} (map-indexed (fn [i f] [f i]) distinct-fns))
+          masks (mapv #(lsh-mask-of idx % words) distinct-fns)
+          qs (vec (sort-by (fn [q] [(fn-no (nth filter-fns q)) q]) (range (count queries))))
+          nq (count qs)
+          out (object-array nq)]
+      (with-open [arena (Arena/ofConfined)]
+        (let [mask (.allocate arena (* 4 words nq) 4)
+              _ (doseq [[j q] (map-indexed vector qs)]
+                  (MemorySegment/copy (MemorySegment/ofArray ^ints (masks (fn-no (nth filter-fns q)))) 0
+                                      mask (* 4 words j) (* 4 words)))
+              qa (floats-of arena (mapv #(nth queries %) qs) (:dim idx))
+              ids (.allocate arena (* 4 nq k) 4)
+              ds (.allocate arena (* 4 nq k) 4)]
+          (check (.invokeWithArguments ^MethodHandle @h-pcafsearch-filtered-each
+                                       [(:handle idx) qa (int nq) (int k) (int k-filter) mask ids ds]))
           (doseq [[j q] (map-indexed vector qs)]
             (aset out q (results idx ids ds j k)))))
       (vec out))))

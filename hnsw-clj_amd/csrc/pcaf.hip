@@ -48,18 +48,20 @@ static int launch_pcaf_project(const hnswgpu_index *idx, const float *P, int32_t
 // The shape of a filter launch.  Waves per workgroup: as many of 8, 4, 2, 1 as the LDS holds (a wave's row buffer is
 // 32 (Tp + 4) floats beside the query block and the 2 kf keys per query).  Slabs: whole steps of nw * 32 rows, as many slabs as
 // give every CU a workgroup at the batch's number of query blocks -- at T = 100 a workgroup takes most of a CU's LDS, so more
-// workgroups than CUs would queue, and every slab costs the merge kf more keys per query.
+// workgroups than CUs would queue, and every slab costs the merge kf more keys per query.  `masked`: the launch is
+// pcaf_filter_masked_kernel's, whose waves keep their id buffers beside the rest (pcaf_filter_masked_lds).
 struct PcafFilterPlan {
     int nw;
     size_t lds;
     int64_t slab_rows;
     int32_t nslabs;
 };
-static PcafFilterPlan pcaf_filter_plan(const hnswgpu_index *idx, int32_t nq, int32_t kf) {
+static PcafFilterPlan pcaf_filter_plan(const hnswgpu_index *idx, int32_t nq, int32_t kf, bool masked) {
+    const auto lds = [&](int nw) { return masked ? pcaf_filter_masked_lds(idx->pcaf_Tp, kf, nw) : pcaf_filter_lds(idx->pcaf_Tp, kf, nw); };
     PcafFilterPlan p;
     p.nw = 8;
-    while (p.nw > 1 && pcaf_filter_lds(idx->pcaf_Tp, kf, p.nw) > kPcafLdsMax) p.nw >>= 1;
-    p.lds = pcaf_filter_lds(idx->pcaf_Tp, kf, p.nw);
+    while (p.nw > 1 && lds(p.nw) > kPcafLdsMax) p.nw >>= 1;
+    p.lds = lds(p.nw);
     const int64_t step = p.nw * 32, steps = (idx->n + step - 1) / step, qblocks = (nq + 31) / 32;
     const int64_t want = std::max<int64_t>(1, (idx->cus + qblocks - 1) / qblocks);
     p.slab_rows = std::max<int64_t>(1, (steps + want - 1) / want) * step;
@@ -85,6 +87,36 @@ static int launch_pcaf_filter(const PcafFilterArgs &a, const PcafFilterPlan &p, 
     else if (nv <= 24) CALL(24);
     else CALL(32);
 #undef CALL
+    HG_HIP(hipGetLastError());
+    return 0;
+}
+
+// the same grid and NV over pcaf_filter_masked_kernel, x the form of the mask (a.allow_stride != 0: one mask per query)
+static int launch_pcaf_filter_masked(const PcafMaskedArgs &a, const PcafFilterPlan &p, hipStream_t st) {
+    const int nv = a.Tp / 8;
+    const bool each = a.allow_stride != 0;
+    const dim3 grid(static_cast<unsigned>(static_cast<int64_t>((a.nq + 31) / 32) * a.nslabs)), block(p.nw * kWave);
+#define CALLE(NV, E)                                                                                                         \
+    do {                                                                                                                     \
+        static bool attr_done[64] = {};                                                                                      \
+        if (attr_needed(attr_done))                                                                                          \
+            HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pcaf_filter_masked_kernel<NV, E>),                    \
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kPcafLdsMax)));          \
+        hipLaunchKernelGGL((pcaf_filter_masked_kernel<NV, E>), grid, block, p.lds, st, a);                                   \
+    } while (0)
+#define CALL(NV)                  \
+    do {                          \
+        if (each) CALLE(NV, true); \
+        else CALLE(NV, false);    \
+    } while (0)
+    if (nv <= 4) CALL(4);
+    else if (nv <= 8) CALL(8);
+    else if (nv <= 13) CALL(13);
+    else if (nv <= 16) CALL(16);
+    else if (nv <= 24) CALL(24);
+    else CALL(32);
+#undef CALL
+#undef CALLE
     HG_HIP(hipGetLastError());
     return 0;
 }
@@ -152,12 +184,14 @@ static int check_pcaf_shape(const hnswgpu_index *idx, int32_t T) {
 #define HG_PCAF_STATE(idx) \
     HG_REQUIRE((idx)->pcaf_T > 0, HNSWGPU_ESTATE, "index has no P-HNSW state (call hnswgpu_pcaf_build / hnswgpu_set_pcaf first)")
 
-// d_Q [nq][dim] -> d_ids / d_dist [nq][k] on `st`; only enqueues: projection, filter, merge + refine per slice of queries
-static int pcaf_search_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t kf, int32_t *d_ids, float *d_dist,
-                               hipStream_t st) {
+// d_Q [nq][dim] -> d_ids / d_dist [nq][k] on `st`; only enqueues: projection, filter, merge + refine per slice of queries.
+// d_allow: null -- the unfiltered search; else the mask of query q is d_allow + q * allow_stride ((n + 31) / 32 words; stride 0:
+// one mask for the call) and the filter is the masked one.  Projection, key scratch and refine are the same either way.
+static int pcaf_search_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t kf, const uint32_t *d_allow,
+                               int64_t allow_stride, int32_t *d_ids, float *d_dist, hipStream_t st) {
     const int Tp = idx->pcaf_Tp;
     const int32_t slice = std::min(nq, kPcafSlice);
-    const PcafFilterPlan plan = pcaf_filter_plan(idx, slice, kf);
+    const PcafFilterPlan plan = pcaf_filter_plan(idx, slice, kf, d_allow != nullptr);
     HG_TRY(idx->s_pcaf_q.ensure(sizeof(float) * static_cast<size_t>(slice) * (Tp + 1)));
     HG_TRY(idx->s_pcaf_keys.ensure(sizeof(uint64_t) * static_cast<size_t>(slice) * plan.nslabs * kf));
     float *qlow = idx->s_pcaf_q.as<float>(), *qnorms = qlow + static_cast<size_t>(slice) * Tp;
@@ -165,7 +199,7 @@ static int pcaf_search_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq,
         const int32_t m = std::min(slice, nq - q0);
         const float *Qs = d_Q + static_cast<int64_t>(q0) * idx->dim;
         HG_TRY(launch_pcaf_project(idx, idx->d_pcaf_proj, idx->pcaf_T, Qs, idx->dim, m, qlow, qnorms, st));
-        PcafFilterArgs f;
+        PcafMaskedArgs f;
         f.rows = idx->d_pcaf_low;
         f.row_norms = idx->d_pcaf_lnorms;
         f.n = idx->n;
@@ -177,7 +211,9 @@ static int pcaf_search_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq,
         f.slab_rows = plan.slab_rows;
         f.nslabs = plan.nslabs;
         f.keys = idx->s_pcaf_keys.as<uint64_t>();
-        HG_TRY(launch_pcaf_filter(f, plan, st));
+        f.allow = d_allow ? d_allow + static_cast<int64_t>(q0) * allow_stride : nullptr;
+        f.allow_stride = allow_stride;
+        HG_TRY(d_allow ? launch_pcaf_filter_masked(f, plan, st) : launch_pcaf_filter(f, plan, st));
         PcafRefineArgs r;
         r.keys = f.keys;
         r.nslabs = plan.nslabs;
@@ -296,7 +332,7 @@ int hnswgpu_pcaf_search_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, in
     HG_PCAF_STATE(idx);
     kf = static_cast<int32_t>(std::min<int64_t>(kf, idx->n));
     HG_REQUIRE(kf <= kPcafMaxKf, HNSWGPU_ELIMIT, "min(k_filter, 3 k, n) > %d is not supported", kPcafMaxKf);
-    HG_TRY(pcaf_search_enqueue(idx, d_Q, nq, k, kf, d_out_ids, d_out_dist, st));
+    HG_TRY(pcaf_search_enqueue(idx, d_Q, nq, k, kf, nullptr, 0, d_out_ids, d_out_dist, st));
     return call.close();
 }
 
@@ -317,9 +353,76 @@ int hnswgpu_pcaf_search(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t 
     kf = static_cast<int32_t>(std::min<int64_t>(kf, idx->n));
     HG_REQUIRE(kf <= kPcafMaxKf, HNSWGPU_ELIMIT, "min(k_filter, 3 k, n) > %d is not supported", kPcafMaxKf);
     HG_TRY(call.stage_in(Q, nq, k));
-    HG_TRY(pcaf_search_enqueue(idx, idx->s_q.as<float>(), nq, k, kf, idx->s_ids.as<int32_t>(), idx->s_outd.as<float>(), st));
+    HG_TRY(pcaf_search_enqueue(idx, idx->s_q.as<float>(), nq, k, kf, nullptr, 0, idx->s_ids.as<int32_t>(), idx->s_outd.as<float>(), st));
     HG_TRY(call.stage_out(out_ids, out_dist, cnt));
     return call.close();
+}
+
+// ---- filtered search: the allow-mask through the low-dimensional filter (pcaf_filter_masked_kernel; the contract:
+// include/hnswgpu.h) ----
+// One body for both forms of the mask: Single is stride 0, Each stride (n + 31) / 32.  Device arrays: enqueues only, reads
+// nothing back -- kf is clamped to n, not to the passing rows, so nothing needs a count.
+static int pcaf_filtered_dev(hnswgpu_index *idx, MaskForm form, const float *d_Q, int32_t nq, int32_t k, int32_t k_filter,
+                             const uint32_t *d_allow, int32_t *d_out_ids, float *d_out_dist, void *stream) {
+    int32_t kf;
+    HG_TRY(check_pcaf_search(idx, d_Q, nq, k, k_filter, d_out_ids, d_out_dist, &kf));
+    if (nq == 0) return 0;
+    HG_REQUIRE(d_allow, HNSWGPU_EINVAL, "allow is null");
+    HG_REQUIRE(idx->n > 0, HNSWGPU_ESTATE, "empty index: use the host entry point");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_PCAF_STATE(idx);
+    kf = static_cast<int32_t>(std::min<int64_t>(kf, idx->n));
+    HG_REQUIRE(kf <= kPcafMaxKf, HNSWGPU_ELIMIT, "min(k_filter, 3 k, n) > %d is not supported", kPcafMaxKf);
+    const int64_t stride = form == MaskForm::Each ? (idx->n + 31) / 32 : 0;
+    HG_TRY(pcaf_search_enqueue(idx, d_Q, nq, k, kf, d_allow, stride, d_out_ids, d_out_dist, st));
+    return call.close();
+}
+
+// Host arrays.  One caller's batch, its mask -- Each: its [nq][W] masks -- staged whole as hnswgpu_lsh_search_filtered_each
+// stages its own: masks differ between callers, so the call takes no part in the call combiner.
+static int pcaf_filtered_host(hnswgpu_index *idx, MaskForm form, const float *Q, int32_t nq, int32_t k, int32_t k_filter,
+                              const uint32_t *allow, int32_t *out_ids, float *out_dist) {
+    int32_t kf;
+    HG_TRY(check_pcaf_search(idx, Q, nq, k, k_filter, out_ids, out_dist, &kf));
+    if (nq == 0) return 0;
+    HG_REQUIRE(allow, HNSWGPU_EINVAL, "allow is null");
+    const int64_t cnt = static_cast<int64_t>(nq) * k;
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_PCAF_STATE(idx);
+    if (idx->n == 0) {  // (an empty index has no mask words)
+        fill_empty(out_ids, out_dist, cnt);
+        return call.close();
+    }
+    kf = static_cast<int32_t>(std::min<int64_t>(kf, idx->n));
+    HG_REQUIRE(kf <= kPcafMaxKf, HNSWGPU_ELIMIT, "min(k_filter, 3 k, n) > %d is not supported", kPcafMaxKf);
+    HG_TRY(call.stage_in(Q, nq, k));
+    HG_TRY(call.stage_mask(allow, form, nq));
+    const int64_t stride = form == MaskForm::Each ? (idx->n + 31) / 32 : 0;
+    HG_TRY(pcaf_search_enqueue(idx, idx->s_q.as<float>(), nq, k, kf, idx->s_fmask.as<uint32_t>(), stride, idx->s_ids.as<int32_t>(),
+                               idx->s_outd.as<float>(), st));
+    HG_TRY(call.stage_out(out_ids, out_dist, cnt));
+    return call.close();
+}
+
+int hnswgpu_pcaf_search_filtered_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t k_filter,
+                                     const uint32_t *d_allow, int32_t *d_out_ids, float *d_out_dist, void *stream) {
+    return pcaf_filtered_dev(idx, MaskForm::Single, d_Q, nq, k, k_filter, d_allow, d_out_ids, d_out_dist, stream);
+}
+int hnswgpu_pcaf_search_filtered(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t k_filter, const uint32_t *allow,
+                                 int32_t *out_ids, float *out_dist) {
+    return pcaf_filtered_host(idx, MaskForm::Single, Q, nq, k, k_filter, allow, out_ids, out_dist);
+}
+int hnswgpu_pcaf_search_filtered_each_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t k_filter,
+                                          const uint32_t *d_allow_each, int32_t *d_out_ids, float *d_out_dist, void *stream) {
+    return pcaf_filtered_dev(idx, MaskForm::Each, d_Q, nq, k, k_filter, d_allow_each, d_out_ids, d_out_dist, stream);
+}
+int hnswgpu_pcaf_search_filtered_each(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t k_filter,
+                                      const uint32_t *allow_each, int32_t *out_ids, float *out_dist) {
+    return pcaf_filtered_host(idx, MaskForm::Each, Q, nq, k, k_filter, allow_each, out_ids, out_dist);
 }
 
 }  // extern "C"

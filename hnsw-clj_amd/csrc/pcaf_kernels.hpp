@@ -295,6 +295,233 @@ __global__ __launch_bounds__(512) void pcaf_filter_kernel(PcafFilterArgs a) {
 }
 #undef HG_PCAF_LOAD
 
+// ---- 2b. filter under an allow-mask -------------------------------------------------------------------------------------
+// hnswgpu_pcaf_search_filtered[_each]: the kf nearest PASSING rows per query and slab.  Grid, query block, key buffer, cut and
+// key output are pcaf_filter_kernel's (so pcaf_refine_kernel serves both); a step is 32 passing rows instead of 32 consecutive
+// ones, and a row that no query of the block may see costs no HBM, no MFMA and no epilogue.
+struct PcafMaskedArgs : PcafFilterArgs {
+    const uint32_t *allow;  // (n + 31) / 32 words per mask, bit r & 31 of word r >> 5: row r passes
+    int64_t allow_stride;   // EACH: words between the masks of two queries (the mask of query q is allow + q * allow_stride)
+};
+
+// pcaf_filter_lds plus two id buffers of 32 rows per wave (the row fetch runs a step ahead of the epilogue that names the rows)
+__host__ __device__ inline size_t pcaf_filter_masked_lds(int Tp, int kf, int nw) {
+    return pcaf_filter_lds(Tp, kf, nw) + sizeof(uint32_t) * 64 * nw;
+}
+
+// Mask word w of this lane: the mask's (shared) or the OR of the block's qcnt masks (EACH); 0 at and behind w_hi (the end of the
+// wave's range, already cut to the mask's length); bits of rows >= n cleared.  One coalesced load per mask and 64 words.
+template <bool EACH>
+__device__ __forceinline__ uint32_t pcaf_mask_word(const PcafMaskedArgs &a, int q0, int qcnt, int64_t w, int64_t w_hi) {
+    if (w >= w_hi) return 0u;
+    uint32_t u = 0u;
+    if (EACH) {
+        const uint32_t *m = a.allow + static_cast<int64_t>(q0) * a.allow_stride + w;
+#pragma unroll 4
+        for (int q = 0; q < qcnt; q++) u |= m[q * a.allow_stride];
+    } else {
+        u = a.allow[w];
+    }
+    if (w == (a.n >> 5)) u &= (1u << (a.n & 31)) - 1u;  // (only the ragged last word has this index)
+    return u;
+}
+
+// The next step of a wave from the 64 words it holds (lane l: word w0 + l, `mw` = its bits not yet taken): the rows of the
+// first 32 set bits in row order go to ids[0 ..), their bits leave mw; returns how many (0: the words are used up).
+__device__ __forceinline__ int pcaf_take_step(uint32_t &mw, int64_t w0, int lane, uint32_t *ids) {
+    const int c = __popc(mw);
+    int incl = c;
+#pragma unroll
+    for (int off = 1; off < kWave; off <<= 1) {
+        const int t = __shfl_up(incl, off, kWave);
+        if (lane >= off) incl += t;
+    }
+    const int tot = __builtin_amdgcn_readlane(incl, kWave - 1);
+    int pos = incl - c;
+    const uint32_t row0 = static_cast<uint32_t>(w0 + lane) << 5;
+    while (mw != 0u && pos < 32) {
+        ids[pos++] = row0 + static_cast<uint32_t>(__ffs(mw) - 1);
+        mw &= mw - 1u;
+    }
+    return tot < 32 ? tot : 32;
+}
+
+// Build the wave's next step in id buffer nb_ and put its rows in flight: float4 number f = 64 v + lane of the step is column
+// f % tv of row ids[f / tv] (pk[v] holds both), a projected row being one run of Tp * 4 bytes.  Words are walked from
+// registers; when the 64 in hand are used up the prefetched 64 take their place and the 64 behind them are requested.
+#define HG_PCAF_NEXT(nb_)                                                                                      \
+    do {                                                                                                       \
+        uint32_t *ids_ = idw + (nb_) * 32;                                                                     \
+        valid_next = 0;                                                                                        \
+        while (wcur < w_hi) {                                                                                  \
+            valid_next = pcaf_take_step(mw, wcur, lane, ids_);                                                 \
+            if (valid_next) break;                                                                             \
+            wcur += kWave;                                                                                     \
+            mw = mw_ahead;                                                                                     \
+            mw_ahead = pcaf_mask_word<EACH>(a, q0, qcnt, wcur + kWave + lane, w_hi);                           \
+        }                                                                                                      \
+        pcaf_wave_sync();                                                                                      \
+        if (valid_next) {                                                                                      \
+            _Pragma("unroll") for (int v = 0; v < NV; v++) if (v < nv) {                                       \
+                const int slot_ = pk[v] >> 16;                                                                 \
+                st[v] = slot_ < valid_next                                                                     \
+                            ? *reinterpret_cast<const float4 *>(a.rows + static_cast<int64_t>(ids_[slot_]) * a.Tp + (pk[v] & 0xffff)) \
+                            : make_float4(0.f, 0.f, 0.f, 0.f);                                                 \
+            }                                                                                                  \
+            rn_next = lane < valid_next ? a.row_norms[ids_[lane]] : 0.0f;                                      \
+        }                                                                                                      \
+    } while (0)
+
+// grid and LDS front as pcaf_filter_kernel; behind them `fin` (waves that have no further step) and per wave two id buffers.
+// Wave w owns the mask words [w_lo, w_hi) of the slab (slab_rows is a multiple of nw * 32: whole words, the same number per
+// wave) and turns them into steps of <= 32 passing rows; a step never spans two 64-word loads, so at most the last step of a
+// load is partial, and words without a set bit make no step.  EACH: the words are the union over the block's queries, and lane
+// li (query li) arms slot i only if its own mask has the row's bit (read from its own mask row: the wave has just read these
+// words for the union).
+// Barriers.  The waves of a workgroup have different numbers of steps, and every pass of the append loop has workgroup
+// barriers, so the loop structure must not depend on a wave's own steps: every wave runs the SAME outer iterations, a wave
+// without a step (valid == 0) skips only its LDS store, its fetch, its MFMAs and its epilogue -- code without a barrier -- and
+// arrives at the append loop with pend == 0.  Inside the append loop the trip count depends on *flag alone, read by all waves
+// between the same two barriers, as in pcaf_filter_kernel.  The outer loop ends on *fin == nw, read between those same two
+// barriers: a wave adds itself to *fin exactly once, in the outer body before the append loop of the iteration in which it
+// first has no next step, i.e. before barrier 1 of that iteration; nobody adds between barrier 1 and barrier 2 of any pass (the
+// only code there is the two reads), and a wave that leaves barrier 2 and adds in the NEXT outer iteration does so after every
+// wave has read.  A wave's next-step state only ever goes from "has one" to "has none", so *fin reaches nw, and the iteration
+// in which it does still appends the last steps before anyone leaves.
+template <int NV, bool EACH>
+__global__ __launch_bounds__(512) void pcaf_filter_masked_kernel(PcafMaskedArgs a) {
+    extern __shared__ __align__(16) unsigned char pcaf_smem[];
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6, half = lane >> 5, li = lane & 31;
+    const int nw = blockDim.x >> 6, S = a.Tp + 4, cap = 2 * a.kf, tv = a.Tp >> 2, nv = a.Tp >> 3;
+    uint64_t *buf = reinterpret_cast<uint64_t *>(pcaf_smem);  // [32][cap]
+    uint64_t *thr = buf + 32 * cap;                           // [32]
+    float *Qs = reinterpret_cast<float *>(thr + 32);          // [32][S]
+    float *Rw = Qs + 32 * S + wave * 32 * S;                  // this wave's [32][S]
+    int32_t *cnt = reinterpret_cast<int32_t *>(Qs + 32 * S * (1 + nw));  // [32]
+    int32_t *flag = cnt + 32, *fin = cnt + 33;
+    uint32_t *idw = reinterpret_cast<uint32_t *>(cnt + 36) + wave * 64;  // this wave's [2][32]
+    const int qb = blockIdx.x / a.nslabs, slab = blockIdx.x % a.nslabs;
+    const int q0 = qb * 32, qcnt = a.nq - q0 < 32 ? a.nq - q0 : 32;
+    const int64_t wpw = a.slab_rows / (32 * nw), w_all = (a.n + 31) >> 5;
+    const int64_t w_lo = slab * (a.slab_rows >> 5) + wave * wpw, w_hi = w_lo + wpw < w_all ? w_lo + wpw : w_all;
+
+    for (int f = tid; f < 32 * tv; f += blockDim.x) {
+        const int q = f / tv, c = f % tv;
+        const float4 v = q < qcnt ? reinterpret_cast<const float4 *>(a.Q + static_cast<int64_t>(q0 + q) * a.Tp)[c]
+                                  : make_float4(0.f, 0.f, 0.f, 0.f);
+        *reinterpret_cast<float4 *>(Qs + q * S + 4 * c) = v;
+    }
+    if (tid < 32) {
+        thr[tid] = ~0ull;
+        cnt[tid] = 0;
+    }
+    if (tid == 0) {
+        *flag = 0;
+        *fin = 0;
+    }
+    const bool qok = li < qcnt;
+    const float qn = qok ? a.q_norms[q0 + li] : 0.0f;
+    const uint32_t *own = a.allow + static_cast<int64_t>(qok ? q0 + li : q0) * a.allow_stride;  // (EACH: this lane's query's mask)
+    int pk[NV];  // slot of the step << 16 | first float of the lane's float4 in the row
+#pragma unroll
+    for (int v = 0; v < NV; v++) {
+        const int f = v * kWave + lane;
+        pk[v] = ((f / tv) << 16) | ((f % tv) * 4);
+    }
+    float4 st[NV];
+    float rn_next = 0.0f;
+    int64_t wcur = w_lo;
+    uint32_t mw = pcaf_mask_word<EACH>(a, q0, qcnt, wcur + lane, w_hi);
+    uint32_t mw_ahead = pcaf_mask_word<EACH>(a, q0, qcnt, wcur + kWave + lane, w_hi);
+    int valid_next, p = 0;
+    bool told = false;
+    HG_PCAF_NEXT(0);
+    __syncthreads();
+
+    for (;;) {
+        const int valid = valid_next;  // (wave-uniform) rows of this wave's step; 0: the wave has run out
+        const uint32_t *ids = idw + p * 32;
+        float d[16];
+        uint32_t pend = 0;
+        if (valid) {
+#pragma unroll
+            for (int v = 0; v < NV; v++)
+                if (v < nv) *reinterpret_cast<float4 *>(Rw + (pk[v] >> 16) * S + (pk[v] & 0xffff)) = st[v];
+            const float rn = rn_next;
+            pcaf_wave_sync();
+            p ^= 1;
+            HG_PCAF_NEXT(p);
+            f32x16 acc;
+#pragma unroll
+            for (int i = 0; i < 16; i++) acc[i] = 0.0f;
+            for (int t = 0; t < nv; t++) {
+                const float4 av = *reinterpret_cast<const float4 *>(Rw + li * S + 8 * t + 4 * half);
+                const float4 bv = *reinterpret_cast<const float4 *>(Qs + li * S + 8 * t + 4 * half);
+                acc = pcaf_mfma4(av, bv, acc);
+            }
+            // D[slot i][query li], i = (reg & 3) + 8 (reg >> 2) + 4 half
+#pragma unroll
+            for (int reg = 0; reg < 16; reg++) {
+                const int i = (reg & 3) + 8 * (reg >> 2) + 4 * half;
+                d[reg] = finish_dist(METRIC_COS, acc[reg], qn, __shfl(rn, i, kWave));
+                if (qok && i < valid) {
+                    const uint32_t r = ids[i];
+                    const bool pass = EACH ? ((own[r >> 5] >> (r & 31)) & 1u) != 0u : true;
+                    if (pass) pend |= 1u << reg;
+                }
+            }
+        }
+        if (!valid_next && !told) {  // before barrier 1 below, once per wave
+            told = true;
+            if (lane == 0) atomicAdd(fin, 1);
+        }
+        int nfin;
+        for (;;) {
+            const uint64_t th = thr[li];
+#pragma unroll
+            for (int reg = 0; reg < 16; reg++) {
+                if (!(pend & (1u << reg))) continue;
+                const uint64_t key = make_key(d[reg], ids[(reg & 3) + 8 * (reg >> 2) + 4 * half]);
+                bool done = true;
+                if (key < th) {
+                    const int pos = atomicAdd(&cnt[li], 1);
+                    if (pos < cap) {
+                        buf[li * cap + pos] = key;
+                    } else {
+                        *flag = 1;
+                        done = false;
+                    }
+                }
+                if (done) pend &= ~(1u << reg);
+            }
+            __syncthreads();
+            const int over = *flag;
+            nfin = *fin;
+            __syncthreads();
+            if (!over) break;
+            for (int q = wave; q < 32; q += nw)
+                if (cnt[q] >= cap) {  // (wave-uniform)
+                    pcaf_wave_cut<(2 * kPcafMaxKf + kWave - 1) / kWave>(buf + q * cap, cap, a.kf, lane);
+                    if (lane == 0) {
+                        cnt[q] = a.kf;
+                        thr[q] = buf[q * cap + a.kf - 1];
+                    }
+                }
+            if (tid == 0) *flag = 0;
+            __syncthreads();
+        }
+        if (nfin == nw) break;
+    }
+    // (behind the last step's barriers nobody appends any more)
+    for (int q = wave; q < qcnt; q += nw) {
+        const int c = cnt[q] < cap ? cnt[q] : cap, have = c < a.kf ? c : a.kf;
+        pcaf_wave_cut<(2 * kPcafMaxKf + kWave - 1) / kWave>(buf + q * cap, c, a.kf, lane);
+        uint64_t *out = a.keys + (static_cast<int64_t>(q0 + q) * a.nslabs + slab) * a.kf;
+        for (int j = lane; j < a.kf; j += kWave) out[j] = j < have ? buf[q * cap + j] : ~0ull;
+    }
+}
+#undef HG_PCAF_NEXT
+
 // ---- 3. merge + refine --------------------------------------------------------------------------------------------------
 struct PcafRefineArgs {
     const uint64_t *keys;  // [nq][nslabs][kf] from the filter

@@ -950,6 +950,42 @@ class Index:
                                             d.data_ptr(), st))
         return ids, d
 
+    def pcaf_search_filtered(self, Q, k, allow, k_filter=0):
+        """hnswgpu_pcaf_search_filtered (pack_mask words): pcaf_search among the rows ``allow`` lets pass -- phase 1 picks the
+        kf nearest PASSING rows, only those are fetched; -1 / +inf where fewer than k pass."""
+        Q = _queries(Q, self.dim)
+        allow = _mask_words(allow, self.n)
+        ids = np.empty((len(Q), k), np.int32)
+        d = np.empty((len(Q), k), np.float32)
+        check(lib().hnswgpu_pcaf_search_filtered(self._h, _p(Q), len(Q), k, int(k_filter or 0), _p(allow), _p(ids), _p(d)))
+        return ids, d
+
+    def pcaf_search_filtered_each(self, Q, k, allow_each, k_filter=0):
+        """hnswgpu_pcaf_search_filtered_each: row q is pcaf_search_filtered(Q[q:q + 1], k, allow_each[q]) -- one mask per query
+        (pack_masks) in the same three launches."""
+        Q = _queries(Q, self.dim)
+        allow_each = _mask_rows(allow_each, self.n, len(Q))
+        ids = np.empty((len(Q), k), np.int32)
+        d = np.empty((len(Q), k), np.float32)
+        check(lib().hnswgpu_pcaf_search_filtered_each(self._h, _p(Q), len(Q), k, int(k_filter or 0), _p(allow_each), _p(ids), _p(d)))
+        return ids, d
+
+    def pcaf_search_filtered_dev(self, Q, k, allow, k_filter=0, out=None):
+        """hnswgpu_pcaf_search_filtered_dev on torch's current stream (device tensors for queries and mask): enqueues only."""
+        Q, ids, d, st = self._dev_args(Q, k, out)
+        allow = self._dev_mask(allow, Q)
+        check(lib().hnswgpu_pcaf_search_filtered_dev(self._h, Q.data_ptr(), Q.shape[0], k, int(k_filter or 0), allow.data_ptr(),
+                                                     ids.data_ptr(), d.data_ptr(), st))
+        return ids, d
+
+    def pcaf_search_filtered_each_dev(self, Q, k, allow_each, k_filter=0, out=None):
+        """hnswgpu_pcaf_search_filtered_each_dev on torch's current stream: enqueues only."""
+        Q, ids, d, st = self._dev_args(Q, k, out)
+        allow_each = self._dev_masks(allow_each, Q)
+        check(lib().hnswgpu_pcaf_search_filtered_each_dev(self._h, Q.data_ptr(), Q.shape[0], k, int(k_filter or 0),
+                                                          allow_each.data_ptr(), ids.data_ptr(), d.data_ptr(), st))
+        return ids, d
+
     # -- measurement
     def set_profiling(self, on=True):
         check(lib().hnswgpu_set_profiling(self._h, 1 if on else 0))

@@ -12,7 +12,9 @@ dependent; the kernels' fixed f32 orders are within the same 1e-7-r
 
 ``one_handle=True`` keeps the same index on ONE handle instead (include/hnswgpu.h, "P-HNSW"): the projection and the projected
 rows are state of the handle that holds the original rows, and a search is hnswgpu_pcaf_search(_dev) -- three launches, no
-[queries][rows] intermediate.  The composition stays the default.
+[queries][rows] intermediate.  The composition stays the default.  Only the one-handle index has the filtered searches
+(search_batch_filtered / _each, search_knn_filtered): a predicate on the ids goes into phase 1 as an allow-mask
+(hnswgpu_pcaf_search_filtered), so the candidates are passing rows -- not the protocol's "search 3k, drop, keep k".
 """
 import numpy as np
 
@@ -121,6 +123,84 @@ def search_knn(index, query_vec, k, mode=None):
     q = np.asarray(query_vec, np.float32).reshape(1, -1)
     res = search_batch(index, q, k, mode)
     return res[0] if res else []
+
+
+def _format(index, ids, d):
+    return [{"id": index.ids[i], "distance": float(x)} for i, x in zip(ids.tolist(), d.tolist()) if i >= 0]
+
+
+def _filtered_args(index, queries, mode):
+    if index.low_index is not None:
+        raise ValueError("filtered P-HNSW search needs an index built with one_handle=True")
+    queries = np.asarray(queries, np.float32)
+    return (queries[None, :] if queries.ndim == 1 else queries), int(MODE_K_FILTER.get(mode) or index.k_filter)
+
+
+def _allow_bits(index, filter_fn):
+    """The predicate on the caller's ids, evaluated once per row on the host (or a ready bool array of length n)."""
+    if callable(filter_fn):
+        return np.fromiter((bool(filter_fn(i)) for i in index.ids), np.bool_, len(index.ids))
+    bits = np.asarray(filter_fn)
+    if bits.dtype != np.bool_ or bits.shape != (index.high_index.n,):
+        raise ValueError("filter_fn must be a predicate on ids or a bool array with one entry per row")
+    return bits
+
+
+def search_batch_filtered(index, queries, k, filter_fn, mode=None):
+    """FilterableIndex/search-knn-filtered* (api/protocol.clj:34-41) through phase 1, one predicate per call: ``filter_fn`` is
+    called once per row with ``index.ids[i]`` (or is a bool array of length n) and packed into one allow-mask; phase 1 picks
+    its min(k-filter, 3k) candidates among the PASSING rows and fetches only those (hnswgpu_pcaf_search_filtered)."""
+    queries, kf = _filtered_args(index, queries, mode)
+    if len(queries) == 0:
+        return []
+    bits = _allow_bits(index, filter_fn)
+    n = index.high_index.n
+    if n == 0:
+        return [[] for _ in range(len(queries))]
+    ids, d = index.high_index.pcaf_search_filtered(queries, int(k), engine.pack_mask(bits, n), kf)
+    return [_format(index, ids[i], d[i]) for i in range(len(queries))]
+
+
+def search_batch_filtered_each(index, queries, k, filter_fns, mode=None):
+    """search_batch_filtered with one predicate (or bool array) PER QUERY: row q equals
+    ``search_knn_filtered(index, queries[q], k, filter_fns[q], mode)``.  The same object, or equal bits, is evaluated and
+    packed once; the batch goes through ONE hnswgpu_pcaf_search_filtered_each call, equal masks adjacent (the union of a query
+    block's masks, which decides what the block fetches, then is small), and the original order is restored.  A batch whose
+    filters are all one mask takes search_batch_filtered's single-mask call."""
+    queries, kf = _filtered_args(index, queries, mode)
+    if len(filter_fns) != len(queries):
+        raise ValueError("one filter per query: %d filters for %d queries" % (len(filter_fns), len(queries)))
+    if len(queries) == 0:
+        return []
+    n = index.high_index.n
+    masks, by_obj, by_bits, which = [], {}, {}, []   # distinct masks: (bits, packed)
+    for f in filter_fns:
+        m = by_obj.get(id(f))
+        if m is None:
+            bits = _allow_bits(index, f)
+            key = bits.tobytes()
+            m = by_bits.get(key)
+            if m is None:
+                m = by_bits[key] = len(masks)
+                masks.append((bits, engine.pack_mask(bits, n)))
+            by_obj[id(f)] = m
+        which.append(m)
+    if len(masks) == 1:
+        return search_batch_filtered(index, queries, k, masks[0][0], mode)
+    if n == 0:
+        return [[] for _ in range(len(queries))]
+    qs = sorted(range(len(queries)), key=lambda q: (which[q], q))   # equal masks adjacent
+    rows = np.stack([masks[which[q]][1] for q in qs])
+    gi, gd = index.high_index.pcaf_search_filtered_each(queries[qs], int(k), rows, kf)
+    ids = np.empty((len(queries), int(k)), np.int32)
+    d = np.empty((len(queries), int(k)), np.float32)
+    ids[qs], d[qs] = gi, gd
+    return [_format(index, ids[i], d[i]) for i in range(len(queries))]
+
+
+def search_knn_filtered(index, query_vec, k, filter_fn, mode=None):
+    """search_batch_filtered for one query: a list of ``{"id", "distance"}`` ascending, fewer than k when fewer pass."""
+    return search_batch_filtered(index, np.asarray(query_vec, np.float32)[None, :], k, filter_fn, mode)[0]
 
 
 def index_info(index):

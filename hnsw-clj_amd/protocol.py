@@ -3,8 +3,9 @@ FilterableIndex and the default helpers (filtered search by post-filtering, :96-
 the two GPU-served index types.  The HNSW index filters on the device (ultra_fast.search_knn_filtered).  GpuIvfFlatIndex is
 the reference's IVF index, which has no FilterableIndex and is served by the default helper; GpuFilterableIvfFlatIndex adds
 the protocol on top of it, filtering inside the list scan (ivf_flat.search_knn_filtered); GpuHybridLshIndex and
-GpuFilterableHybridLshIndex are the same pair for the hybrid LSH index (hybrid_lsh.search_knn_filtered: inside the bucket scan)."""
-from . import hybrid_lsh, index_io, ivf_flat, ultra_fast
+GpuFilterableHybridLshIndex are the same pair for the hybrid LSH index (hybrid_lsh.search_knn_filtered: inside the bucket scan),
+GpuPcafIndex and GpuFilterablePcafIndex for P-HNSW on one handle (pcaf.search_knn_filtered: inside the low-dimensional filter)."""
+from . import hybrid_lsh, index_io, ivf_flat, pcaf, ultra_fast
 
 
 class ANNIndex:
@@ -139,6 +140,36 @@ class GpuFilterableHybridLshIndex(GpuHybridLshIndex, FilterableIndex):
     def search_batch_filtered(self, queries, k, filter_fns, mode=None):
         """search_knn_filtered_star for a batch, one predicate per query, in one chain of launches (not in the reference)."""
         return hybrid_lsh.search_batch_filtered_each(self.index, queries, k, filter_fns, mode)
+
+
+class GpuPcafIndex(ANNIndex, BatchSearchIndex):
+    """hnsw.ann.dimreduct.pcaf behind the protocol (unified.clj's :pcaf); not persistable, as in the reference."""
+
+    def __init__(self, index):
+        self.index = index
+
+    def search_knn_star(self, query, k, mode=None):
+        return pcaf.search_knn(self.index, query, k, mode)
+
+    def search_batch_star(self, queries, k, mode=None):
+        return pcaf.search_batch(self.index, queries, k, mode)
+
+    def index_info_star(self):
+        return pcaf.index_info(self.index)
+
+    def index_type_star(self):
+        return "pcaf"
+
+
+class GpuFilterablePcafIndex(GpuPcafIndex, FilterableIndex):
+    """P-HNSW (one_handle=True) with the allow-mask through its low-dimensional filter: the candidates are PASSING rows."""
+
+    def search_knn_filtered_star(self, query, k, filter_fn, mode=None):
+        return pcaf.search_knn_filtered(self.index, query, k, filter_fn, mode)
+
+    def search_batch_filtered(self, queries, k, filter_fns, mode=None):
+        """search_knn_filtered_star for a batch, one predicate per query, in one chain of launches (not in the reference)."""
+        return pcaf.search_batch_filtered_each(self.index, queries, k, filter_fns, mode)
 
 
 def supports_filtering(index):

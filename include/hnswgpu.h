@@ -1065,8 +1065,28 @@ int hnswgpu_lsh_search_filtered_each_dev(hnswgpu_index *idx, const float *d_Q, i
  *   Other state: hnswgpu_pcaf_build / hnswgpu_set_pcaf return -3 on a handle that holds a graph, a forest, IVF lists or
  *     LSH tables, and every call that installs one of those or adds, removes or updates rows returns -3 on a handle with
  *     P-HNSW state (the projected rows would go stale); the message names why; the handle is untouched.
- *   Out of scope: mutating a P-HNSW handle; filtered P-HNSW search; the index file -- hnswgpu_save writes such a handle
- *     without the state, as it does LSH tables; groups and shards. */
+ *   hnswgpu_pcaf_search_filtered / _each / _dev: the allow-mask through the low-dimensional filter
+ *     (pcaf_filter_masked_kernel).  Post-filtering ("search 3 k, drop what fails, keep k", protocol.clj:97-102) is at its
+ *     worst here: phase 1 keeps only kf <= 3 k candidates, so at a 1 % pass rate nearly all of them fail and the answer is
+ *     empty.  Instead phase 1 itself chooses among the passing rows, and only those are fetched and multiplied.
+ *     kf = min(k_filter <= 0 ? 32 : k_filter, 3 k, n) -- n, not the number of passing rows: nothing is counted first.
+ *     Phase 1: the kf PASSING rows nearest by projected cosine, ties to the lower row id; fewer than kf pass: all of them
+ *     are candidates.  Phase 2 is that of hnswgpu_pcaf_search, unchanged: exact cosine with hnswgpu_rerank's bits, sorted,
+ *     min(k, candidates) entries, -1 / +inf behind them.  A row whose bit is clear is never returned; an all-ones mask
+ *     returns hnswgpu_pcaf_search's ids and distance bits, bit for bit; an all-zero mask returns padding only.
+ *     _each: result row q equals, bit for bit, the single-mask call on query q alone with mask q.
+ *     Mask: exactly that of the other filtered calls ("filtered search" above).  `allow` is (n + 31) / 32 words indexed by
+ *     row id, `allow_each` is [nq][(n + 31) / 32] row-major, bits at positions >= n are ignored, the mask is an argument
+ *     and never handle state.  A null mask is -1; every other check and code is hnswgpu_pcaf_search's (-1, -5 for k > 1024
+ *     or an effective kf > 128, -3 without P-HNSW state); nq == 0 returns 0; n == 0: the host entries fill the padding,
+ *     the _dev entries return -3.  Unlike hnswgpu_exact_knn_filtered_dev, BOTH _dev entries only enqueue: nothing is read
+ *     back and `stream` is never waited on.  The host entries stage one caller's batch, masks included, and take no part
+ *     in the call combiner.
+ *     Known limit: the slabs of phase 1 are sized by rows, not by passing rows, so a mask that passes one contiguous id
+ *     range leaves most workgroups without work; balancing needs a count before the launch, which the _dev contract
+ *     rules out.
+ *   Out of scope: mutating a P-HNSW handle; the index file -- hnswgpu_save writes such a handle without the state, as it
+ *     does LSH tables; groups and shards. */
 int hnswgpu_pcaf_build(hnswgpu_index *idx, int32_t n_components, int64_t seed);
 int hnswgpu_set_pcaf(hnswgpu_index *idx, const float *projection, int32_t n_components);
 int hnswgpu_pcaf_sizes(hnswgpu_index *idx, int32_t *n_components);
@@ -1076,6 +1096,14 @@ int hnswgpu_pcaf_search(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t 
                         float *out_dist);
 int hnswgpu_pcaf_search_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t k_filter, int32_t *d_out_ids,
                             float *d_out_dist, void *stream);
+int hnswgpu_pcaf_search_filtered(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t k_filter,
+                                 const uint32_t *allow, int32_t *out_ids, float *out_dist);
+int hnswgpu_pcaf_search_filtered_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t k_filter,
+                                     const uint32_t *d_allow, int32_t *d_out_ids, float *d_out_dist, void *stream);
+int hnswgpu_pcaf_search_filtered_each(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t k_filter,
+                                      const uint32_t *allow_each, int32_t *out_ids, float *out_dist);
+int hnswgpu_pcaf_search_filtered_each_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t k_filter,
+                                          const uint32_t *d_allow_each, int32_t *d_out_ids, float *d_out_dist, void *stream);
 
 /* ---- ONE index over several GPUs (hnsw-clj_amd/csrc/group.hip) ---------------------------------------------------
  * The reference shards inside one process: search-partitioned scatters a query to its partitions, takes a top-k per
