@@ -408,6 +408,45 @@ JNIEXPORT jint JNICALL Java_hnsw_gpu_Native_pcafSearchFilteredEachDev(JNIEnv *en
     return rc;
 }
 
+/* rows join, leave and take new values on a live P-HNSW handle (hnswgpu_pcaf_add / _remove / _update): the shapes of lshRemove and
+ * lshUpdate below.  pcafAdd: `rows` holds m x dim floats, the rows get ids n .. n + m - 1; returns 0.  pcafRemove: `rows` holds m row
+ * ids in any order, repeats count once; returns the rows the handle holds afterwards.  pcafUpdate: row ids[i] takes rows[i]; returns
+ * 0.  Each returns the negative error code when the call fails (the exception is pending).  Unverified like the rest of this file:
+ * no JVM where the library is built and tested. */
+JNIEXPORT jint JNICALL Java_hnsw_gpu_Native_pcafAdd(JNIEnv *env, jclass c, jlong h, jfloatArray rows, jlong m, jint dim) {
+    if (!rows) return throw_iae(env, "pcafAdd: null array");
+    if (m < 0 || dim < 1 || m > (jlong)(*env)->GetArrayLength(env, rows) / dim) return throw_iae(env, "pcafAdd: fewer than m x dim floats");
+    jfloat *pr = (*env)->GetFloatArrayElements(env, rows, NULL);
+    int rc = pr ? hnswgpu_pcaf_add((hnswgpu_index *)(intptr_t)h, (const float *)pr, (int64_t)m) : HNSWGPU_ENOMEM; /* OutOfMemoryError is pending */
+    if (pr) (*env)->ReleaseFloatArrayElements(env, rows, pr, JNI_ABORT);
+    if (rc != 0 && rc != HNSWGPU_ENOMEM) throw_last(env);
+    return rc;
+}
+JNIEXPORT jlong JNICALL Java_hnsw_gpu_Native_pcafRemove(JNIEnv *env, jclass c, jlong h, jintArray rows, jlong m) {
+    if (!rows) return throw_iae(env, "pcafRemove: null array");
+    if (m < 0 || m > (jlong)(*env)->GetArrayLength(env, rows)) return throw_iae(env, "pcafRemove: m outside the array");
+    jint *pr = (*env)->GetIntArrayElements(env, rows, NULL);
+    int64_t n_after = -1;
+    int rc = pr ? hnswgpu_pcaf_remove((hnswgpu_index *)(intptr_t)h, (const int32_t *)pr, (int64_t)m, &n_after)
+                : HNSWGPU_ENOMEM; /* OutOfMemoryError is pending */
+    if (pr) (*env)->ReleaseIntArrayElements(env, rows, pr, JNI_ABORT);
+    if (rc != 0 && rc != HNSWGPU_ENOMEM) throw_last(env);
+    return rc != 0 ? (jlong)rc : (jlong)n_after;
+}
+JNIEXPORT jint JNICALL Java_hnsw_gpu_Native_pcafUpdate(JNIEnv *env, jclass c, jlong h, jintArray ids, jfloatArray rows, jlong m, jint dim) {
+    if (!ids || !rows) return throw_iae(env, "pcafUpdate: null array");
+    if (m < 0 || m > (jlong)(*env)->GetArrayLength(env, ids)) return throw_iae(env, "pcafUpdate: m outside the id array");
+    if (dim < 1 || m > (jlong)(*env)->GetArrayLength(env, rows) / dim) return throw_iae(env, "pcafUpdate: fewer than m x dim floats");
+    jint *pi = (*env)->GetIntArrayElements(env, ids, NULL);
+    jfloat *pr = pi ? (*env)->GetFloatArrayElements(env, rows, NULL) : NULL;
+    int rc = pi && pr ? hnswgpu_pcaf_update((hnswgpu_index *)(intptr_t)h, (const int32_t *)pi, (const float *)pr, (int64_t)m)
+                      : HNSWGPU_ENOMEM; /* OutOfMemoryError is pending */
+    if (pr) (*env)->ReleaseFloatArrayElements(env, rows, pr, JNI_ABORT);
+    if (pi) (*env)->ReleaseIntArrayElements(env, ids, pi, JNI_ABORT);
+    if (rc != 0 && rc != HNSWGPU_ENOMEM) throw_last(env);
+    return rc;
+}
+
 /* rows leave a live hybrid LSH index (hnswgpu_lsh_remove): `rows` holds m row ids in any order, repeats count once; the kept rows
  * are renumbered densely in their old order.  Returns the rows the handle holds afterwards, or the negative error code (the
  * exception is pending).  Unverified like the rest of this file: no JVM where the library is built and tested. */

@@ -31,6 +31,9 @@
      (search-lsh-filtered index query-vec k filter-fn :mode :balanced) ; the allow-mask through the bucket scan: hnswgpu_lsh_search_filtered
      (search-lsh-batch-filtered-each index queries k filter-fns)      ; one predicate per query: hnswgpu_lsh_search_filtered_each
      (search-pcaf-batch-filtered-each pcaf-index queries k filter-fns) ; P-HNSW, candidates among the passing rows: hnswgpu_pcaf_search_filtered_each
+     (add-pcaf-vectors! pcaf-index new-data)                         ; rows join a live P-HNSW index: hnswgpu_pcaf_add
+     (remove-pcaf-vectors! pcaf-index ids)                           ; ... and leave it: hnswgpu_pcaf_remove
+     (update-pcaf-vectors! pcaf-index new-data)                      ; ... and take new values under their ids: hnswgpu_pcaf_update
      (from-ultra-graph graph)                                        ; a graph built by the reference's own insert-single
      (from-ivf-flat-index ivf)                                       ; an IVFFlatIndex built by the reference's own k-means
      (save idx path) / (load-index path ids)                         ; helper/index-io save-index / load-index
@@ -457,6 +460,61 @@
   [data & {:keys [n-components seed] :or {n-components 100 seed 42}}]
   (let [idx (create data :cosine :pcaf)]
     (check (.invokeWithArguments ^MethodHandle @h-pcafbuild [(:handle idx) (int n-components) (long seed)]))
+    idx))
+
+(def ^:private h-pcafadd (delay (fn-handle "hnswgpu_pcaf_add" (FunctionDescriptor/of I (into-array [P P L])))))
+(def ^:private h-pcafremove (delay (fn-handle "hnswgpu_pcaf_remove" (FunctionDescriptor/of I (into-array [P P L P])))))
+(def ^:private h-pcafupdate (delay (fn-handle "hnswgpu_pcaf_update" (FunctionDescriptor/of I (into-array [P P P L])))))
+
+(defn add-pcaf-vectors!
+  "add-vector! (src/hnsw/api.clj:30-33) for a live P-HNSW GpuIndex (the reference's index has no add): the new [id ^doubles vector]
+   pairs join the original rows and, projected under the index's projection by the kernel that projected the old rows, the
+   projected rows (hnswgpu_pcaf_add).  Returns the index with their ids appended.  One call per batch is the efficient shape: a
+   call copies the rows once, whatever it adds.  Unverified like the rest of this namespace: no JVM where the library is built."
+  [idx new-data]
+  (with-open [arena (Arena/ofConfined)]
+    (check (.invokeWithArguments ^MethodHandle @h-pcafadd
+                                 [(:handle idx) (floats-of arena (mapv second new-data) (:dim idx)) (long (count new-data))])))
+  (update idx :ids into (map first new-data)))
+
+(defn remove-pcaf-vectors!
+  "The inverse of add-pcaf-vectors!: the vectors with the given ids leave the original and the projected rows, and the kept rows
+   are renumbered densely in their old order (hnswgpu_pcaf_remove).  An unknown id throws before the device is touched.  Returns
+   the index with the ids removed.  Unverified like the rest of this namespace: no JVM where the library is built."
+  [idx ids]
+  (let [gone (set ids)
+        known (set (:ids idx))]
+    (when-let [bad (first (remove known gone))]
+      (throw (ex-info "remove-pcaf-vectors!: unknown id" {:id bad})))
+    (if (empty? gone)
+      idx
+      (let [rows (vec (keep-indexed (fn [i id] (when (gone id) i)) (:ids idx)))]
+        (with-open [arena (Arena/ofConfined)]
+          (let [n-after (.allocate arena 8 8)]
+            (check (.invokeWithArguments ^MethodHandle @h-pcafremove
+                                         [(:handle idx) (ints-of arena rows) (long (count rows)) n-after]))
+            (let [kept (vec (remove gone (:ids idx)))]
+              (assert (= (count kept) (.getAtIndex n-after L 0)))
+              (assoc idx :ids kept))))))))
+
+(defn update-pcaf-vectors!
+  "\"Update existing vectors\" (the open item of the reference's to-do list) for a live P-HNSW GpuIndex: new-data is a seq of
+   [id ^doubles vector]; the vector stored under each id takes the new values, is projected again and keeps its id
+   (hnswgpu_pcaf_update).  An unknown id, an id that names several rows and an id given twice throw before the device is touched.
+   Returns the index (its ids are unchanged).  Unverified like the rest of this namespace: no JVM where the library is built."
+  [idx new-data]
+  (let [rows-of (reduce (fn [m [i id]] (update m id (fnil conj []) i)) {} (map-indexed vector (:ids idx)))
+        ids (mapv first new-data)]
+    (doseq [id ids]
+      (when-not (contains? rows-of id) (throw (ex-info "update-pcaf-vectors!: unknown id" {:id id})))
+      (when (> (count (rows-of id)) 1) (throw (ex-info "update-pcaf-vectors!: the id names several rows" {:id id}))))
+    (when-not (or (empty? ids) (apply distinct? ids))
+      (throw (ex-info "update-pcaf-vectors!: an id is given twice" {})))
+    (when (seq ids)
+      (with-open [arena (Arena/ofConfined)]
+        (check (.invokeWithArguments ^MethodHandle @h-pcafupdate
+                                     [(:handle idx) (ints-of arena (mapv (comp first rows-of) ids))
+                                      (floats-of arena (mapv second new-data) (:dim idx)) (long (count ids))]))))
     idx))
 
 (defn search-pcaf-batch-filtered

@@ -118,6 +118,9 @@ _SIGS = {
     "hnswgpu_pcaf_sizes": ["p", "p"],
     "hnswgpu_pcaf_get": ["p", "p", "p"],
     "hnswgpu_pcaf_project": ["p", "p", "i64", "p"],
+    "hnswgpu_pcaf_add": ["p", "p", "i64"],
+    "hnswgpu_pcaf_remove": ["p", "p", "i64", "p"],
+    "hnswgpu_pcaf_update": ["p", "p", "p", "i64"],
     "hnswgpu_pcaf_search": ["p", "p", "i32", "i32", "i32", "p", "p"],
     "hnswgpu_pcaf_search_dev": ["p", "p", "i32", "i32", "i32", "p", "p", "p"],
     "hnswgpu_pcaf_search_filtered": ["p", "p", "i32", "i32", "i32", "p", "p", "p"],

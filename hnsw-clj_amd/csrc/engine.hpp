@@ -231,7 +231,8 @@ struct hnswgpu_index {
 
     // P-HNSW (pcaf.hip, pcaf_kernels.hpp): a random projection to pcaf_T components, or none (pcaf_T == 0).  The projection
     // [T][ld] zero padded, the projected rows [n][Tp] (Tp = T rounded up to 8, zero padded) and their norms; the caller's
-    // projection [T][dim] for export.  A handle with this state holds no graph, lists, tables or forest and takes no mutation.
+    // projection [T][dim] for export.  A handle with this state holds no graph, lists, tables or forest; its rows change through
+    // hnswgpu_pcaf_add / _remove / _update alone (every other family's mutation refuses it: HG_REFUSE_PCAF).
     int pcaf_T = 0, pcaf_Tp = 0;
     float *d_pcaf_proj = nullptr, *d_pcaf_low = nullptr, *d_pcaf_lnorms = nullptr;
     std::vector<float> h_pcaf_proj;

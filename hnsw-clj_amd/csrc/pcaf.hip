@@ -8,7 +8,10 @@
 
 #include "engine.hpp"
 #include "javarandom.hpp"
+#include "ivf_update_ids.hpp"
+#include "lsh_remove_ids.hpp"
 #include "pcaf_kernels.hpp"
+#include "pcaf_mutate_kernels.hpp"
 
 namespace hg {
 
@@ -17,9 +20,10 @@ constexpr int32_t kPcafSlice = 65536;        // queries (rows of hnswgpu_pcaf_pr
 
 static int pcaf_tp(int32_t T) { return (T + 7) & ~7; }
 
-// X [m][dim] (row stride xld, device) -> out [m][Tp], norms [m]
+// X [m][dim] (row stride xld, device) -> out [m][Tp], norms [m]; with `dst` (device, [m]) row r goes to row dst[r] of out / norms,
+// which hold n_dst rows (the MAP form of the kernel: hnswgpu_pcaf_update)
 static int launch_pcaf_project(const hnswgpu_index *idx, const float *P, int32_t T, const float *X, int64_t xld, int64_t m, float *out,
-                               float *norms, hipStream_t st) {
+                               float *norms, hipStream_t st, const int32_t *dst = nullptr, int64_t n_dst = 0) {
     if (m <= 0) return 0;
     PcafProjectArgs a;
     a.X = X;
@@ -33,9 +37,15 @@ static int launch_pcaf_project(const hnswgpu_index *idx, const float *P, int32_t
     a.Tp = pcaf_tp(T);
     a.out = out;
     a.norms = norms;
+    a.dst = dst;
+    a.n_dst = n_dst;
     const dim3 grid(static_cast<unsigned>((m + kPcafProjRows - 1) / kPcafProjRows));
     const int nt = (a.Tp + 31) / 32;
-#define CALL(NT) hipLaunchKernelGGL((pcaf_project_kernel<NT>), grid, dim3(kWG), 0, st, a)
+#define CALL(NT)                                                                                       \
+    do {                                                                                               \
+        if (dst) hipLaunchKernelGGL((pcaf_project_kernel<NT, true>), grid, dim3(kWG), 0, st, a);       \
+        else hipLaunchKernelGGL((pcaf_project_kernel<NT, false>), grid, dim3(kWG), 0, st, a);          \
+    } while (0)
     if (nt <= 1) CALL(1);
     else if (nt <= 2) CALL(2);
     else if (nt <= 4) CALL(4);
@@ -146,6 +156,62 @@ struct PcafStaged {
             if (p) (void)hipFree(p);
     }
 };
+
+// The rows of a handle in all their pieces as hnswgpu_pcaf_add / _remove / _update stage them (the projection stays the
+// handle's): what is left in it when it goes out of scope is freed -- the staged arrays on an early return, the handle's old ones
+// behind the swap.
+struct PcafStagedRows {
+    float *base = nullptr, *norms = nullptr, *low = nullptr, *lnorms = nullptr;
+    uint32_t *qrows = nullptr;
+    float4 *qmeta = nullptr;
+    ~PcafStagedRows() {
+        void *ptrs[] = {base, norms, low, lnorms, qrows, qmeta};
+        for (void *p : ptrs)
+            if (p) (void)hipFree(p);
+    }
+    // room for n rows (none for n == 0: the empty handle pcaf_install leaves has null arrays)
+    int alloc(const hnswgpu_index *idx, int64_t n) {
+        if (n <= 0) return 0;
+        const size_t nn = static_cast<size_t>(n);
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&base), sizeof(float) * nn * idx->ld));
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&norms), sizeof(float) * nn));
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&low), sizeof(float) * nn * idx->pcaf_Tp));
+        HG_HIP(hipMalloc(reinterpret_cast<void **>(&lnorms), sizeof(float) * nn));
+        return 0;
+    }
+    // the first n0 rows' four pieces as the handle has them: copied on the device, never computed again
+    int copy_old(const hnswgpu_index *idx, int64_t n0, hipStream_t st) {
+        if (n0 <= 0) return 0;
+        const size_t nn = static_cast<size_t>(n0);
+        HG_HIP(hipMemcpyAsync(base, idx->d_base, sizeof(float) * nn * idx->ld, hipMemcpyDeviceToDevice, st));
+        HG_HIP(hipMemcpyAsync(norms, idx->d_norms, sizeof(float) * nn, hipMemcpyDeviceToDevice, st));
+        HG_HIP(hipMemcpyAsync(low, idx->d_pcaf_low, sizeof(float) * nn * idx->pcaf_Tp, hipMemcpyDeviceToDevice, st));
+        HG_HIP(hipMemcpyAsync(lnorms, idx->d_pcaf_lnorms, sizeof(float) * nn, hipMemcpyDeviceToDevice, st));
+        return 0;
+    }
+    void swap_into(hnswgpu_index *idx, int64_t n) {
+        std::swap(idx->d_base, base);  // (what the handle had goes with this object)
+        std::swap(idx->d_norms, norms);
+        std::swap(idx->d_qrows, qrows);
+        std::swap(idx->d_qmeta, qmeta);
+        std::swap(idx->d_pcaf_low, low);
+        std::swap(idx->d_pcaf_lnorms, lnorms);
+        idx->n = n;
+    }
+};
+
+// m host rows [m][dim] -> dst [m][ld] on the device, padding zero (what hnswgpu_create does with its base)
+static int pcaf_upload_rows(const hnswgpu_index *idx, const float *rows, int64_t m, float *dst, hipStream_t st) {
+    const size_t mm = static_cast<size_t>(m);
+    if (idx->ld == idx->dim) {  // one run of bytes: a 2-D copy of the same rows from pageable memory took 9 us a row on an MI355X
+        HG_HIP(hipMemcpyAsync(dst, rows, sizeof(float) * mm * idx->dim, hipMemcpyHostToDevice, st));
+        return 0;
+    }
+    HG_HIP(hipMemsetAsync(dst, 0, sizeof(float) * mm * idx->ld, st));
+    HG_HIP(hipMemcpy2DAsync(dst, sizeof(float) * idx->ld, rows, sizeof(float) * idx->dim, sizeof(float) * idx->dim, mm,
+                            hipMemcpyHostToDevice, st));
+    return 0;
+}
 
 // P: [T][dim] on the host
 static int pcaf_install(hnswgpu_index *idx, Call &call, const float *P, int32_t T, hipStream_t st) {
@@ -423,6 +489,197 @@ int hnswgpu_pcaf_search_filtered_each_dev(hnswgpu_index *idx, const float *d_Q, 
 int hnswgpu_pcaf_search_filtered_each(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t k_filter,
                                       const uint32_t *allow_each, int32_t *out_ids, float *out_dist) {
     return pcaf_filtered_host(idx, MaskForm::Each, Q, nq, k, k_filter, allow_each, out_ids, out_dist);
+}
+
+// ---- rows join, leave and take new values on a live handle (pcaf_mutate_kernels.hpp; the contract: include/hnswgpu.h) ----
+// One rule behind all three: afterwards the handle holds, bit for bit, what hnswgpu_create(the rows it should now hold) +
+// hnswgpu_set_pcaf(the same projection) holds.  It can, because a row's projection and norm from pcaf_project_kernel depend on the
+// row's values and the projection alone.  Failure-atomic as the siblings (hnswgpu_lsh_add): every array a call makes is STAGED
+// and goes with `nw` on an early return; the handle's fields change only behind the last step (idx->mu is held and the streams
+// are quiesced: no caller sees a state in between).
+
+// Rows join: ids n .. n + m - 1.  One chain on the handle's stream: base / norms / int8 rows grow as in hnswgpu_lsh_add, the
+// projected rows and their norms grow behind device copies of the old ones -- the plain projection kernel reads the new rows
+// where they sit in the grown base and writes at new_low + n0 * Tp, new_lnorms + n0.
+int hnswgpu_pcaf_add(hnswgpu_index *idx, const float *rows, int64_t m) {
+    HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
+    HG_REQUIRE(m >= 0, HNSWGPU_EINVAL, "m must be >= 0");
+    HG_REQUIRE(rows || m == 0, HNSWGPU_EINVAL, "rows is null");
+    if (m == 0) return 0;
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_PCAF_STATE(idx);
+    const int64_t n0 = idx->n, n1 = n0 + m, ld = idx->ld;
+    HG_REQUIRE(n1 < 2147483647LL, HNSWGPU_ELIMIT, "the index must hold fewer than 2^31 rows");
+    HG_TRY(call.quiesce());
+    PcafStagedRows nw;
+    auto grow = [&]() -> int {
+        HG_TRY(nw.alloc(idx, n1));
+        HG_TRY(nw.copy_old(idx, n0, st));
+        HG_TRY(pcaf_upload_rows(idx, rows, m, nw.base + n0 * ld, st));
+        HG_TRY(launch_norms(idx->nch, nw.base + n0 * ld, ld, m, nw.norms + n0, st));
+        if (idx->d_qrows) HG_TRY(quantize_rows(idx, nw.base, n1, &nw.qrows, &nw.qmeta, st));  // (all rows again: one pass over the base)
+        HG_TRY(launch_pcaf_project(idx, idx->d_pcaf_proj, idx->pcaf_T, nw.base + n0 * ld, ld, m, nw.low + n0 * idx->pcaf_Tp,
+                                   nw.lnorms + n0, st));
+        HG_HIP(hipStreamSynchronize(st));  // (the upload has read `rows`; a failing step shows before the takeover)
+        return 0;
+    };
+    const int rc = grow();
+    if (rc != 0) {
+        (void)hipStreamSynchronize(st);  // (nothing of the chain is in flight when `nw` frees what it staged)
+        return rc;
+    }
+    nw.swap_into(idx, n1);
+    return call.close();
+}
+
+// Rows leave; the kept rows are renumbered densely in their old order.  One chain: mark, rank (remove_kernels.hpp, as
+// hnswgpu_ivf_remove reuses them: tables = 0), then ONE pass that moves a kept row's four pieces to its rank.  Only the m ids go
+// up; ONE readback: the rank scan's total, which gates the takeover.
+int hnswgpu_pcaf_remove(hnswgpu_index *idx, const int32_t *rows, int64_t m, int64_t *n_after) {
+    HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
+    HG_REQUIRE(m >= 0, HNSWGPU_EINVAL, "m must be >= 0");
+    HG_REQUIRE(rows || m == 0, HNSWGPU_EINVAL, "rows is null");
+    if (m == 0) {  // nothing to remove: nothing happens, whatever the handle holds
+        std::lock_guard<std::mutex> lk(idx->mu);
+        if (n_after) *n_after = idx->n;
+        return 0;
+    }
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_PCAF_STATE(idx);
+    const int64_t n0 = idx->n;
+    int64_t distinct = 0, bad = -1;
+    try {
+        bad = lsh_remove_check_ids(rows, m, n0, &distinct);  // on the host array, before anything is enqueued
+    } catch (const std::bad_alloc &) {  // (its sorted copy of the ids)
+        set_error("host allocation failed");
+        return HNSWGPU_ENOMEM;
+    }
+    HG_REQUIRE(bad < 0, HNSWGPU_EINVAL, "rows[%lld] = %d is not a row of the index (n = %lld)", (long long)bad, rows[bad], (long long)n0);
+    const int64_t n1 = n0 - distinct;
+    HG_TRY(call.quiesce());
+    PcafStagedRows nw;
+    auto shrink = [&]() -> int {
+        HG_TRY(nw.alloc(idx, n1));
+        // scratch, 16-byte sections: [gate | keep] zeroed, then word_rank and the call's ids
+        PcafRemoveArgs a;
+        memset(&a, 0, sizeof(a));
+        a.r.n0 = n0;
+        a.r.n1 = n1;
+        a.r.m = m;
+        a.r.W = (n0 + 31) / 32;
+        a.r.ld = idx->ld;
+        auto sect = [](size_t bytes) { return (bytes + 15) / 16 * 16; };
+        const size_t o_keep = sect(sizeof(int64_t) * kLshRemoveGate), o_rank = o_keep + sect(sizeof(uint32_t) * a.r.W),
+                     o_ids = o_rank + sect(sizeof(uint32_t) * a.r.W), bytes = o_ids + sect(sizeof(int32_t) * m);
+        HG_TRY(idx->s_misc.ensure(bytes));
+        char *s = idx->s_misc.as<char>();
+        HG_HIP(hipMemsetAsync(s, 0, o_rank, st));
+        HG_HIP(hipMemcpyAsync(s + o_ids, rows, sizeof(int32_t) * static_cast<size_t>(m), hipMemcpyHostToDevice, st));
+        a.r.gate = reinterpret_cast<int64_t *>(s);
+        a.r.keep = reinterpret_cast<uint32_t *>(s + o_keep);
+        a.r.word_rank = reinterpret_cast<uint32_t *>(s + o_rank);
+        a.r.rows = reinterpret_cast<const int32_t *>(s + o_ids);
+        a.r.old_base = idx->d_base;
+        a.r.old_norms = idx->d_norms;
+        a.r.new_base = nw.base;
+        a.r.new_norms = nw.norms;
+        a.Tp = idx->pcaf_Tp;
+        a.old_low = idx->d_pcaf_low;
+        a.old_lnorms = idx->d_pcaf_lnorms;
+        a.new_low = nw.low;
+        a.new_lnorms = nw.lnorms;
+        hipLaunchKernelGGL(lsh_remove_mark_kernel, dim3(static_cast<unsigned>((m + kWG - 1) / kWG)), dim3(kWG), 0, st, a.r);
+        hipLaunchKernelGGL(lsh_remove_rank_kernel, dim3(1), dim3(kWG), 0, st, a.r);
+        if (n1 > 0) hipLaunchKernelGGL(pcaf_remove_rows_kernel, dim3(static_cast<unsigned>((n0 + kNWave - 1) / kNWave)), dim3(kWG), 0, st, a);
+        HG_HIP(hipGetLastError());
+        if (idx->d_qrows && n1 > 0) HG_TRY(quantize_rows(idx, nw.base, n1, &nw.qrows, &nw.qmeta, st));  // (as add: one pass over the new base)
+        // ---- the one readback
+        int64_t kept = -1;
+        HG_HIP(hipMemcpyAsync(&kept, a.r.gate + 2 * kRemoveMaxTables, sizeof(kept), hipMemcpyDeviceToHost, st));
+        HG_HIP(hipStreamSynchronize(st));
+        HG_REQUIRE(kept == n1, HNSWGPU_EHIP, "the mask keeps %lld rows, not %lld", (long long)kept, (long long)n1);
+        return 0;
+    };
+    const int rc = shrink();
+    if (rc != 0) {
+        (void)hipStreamSynchronize(st);  // (nothing of the chain is in flight when `nw` frees what it staged)
+        return rc;
+    }
+    nw.swap_into(idx, n1);  // (n1 == 0: null arrays -- the empty handle with its projection that hnswgpu_pcaf_add grows again)
+    if (n_after) *n_after = n1;
+    return call.close();
+}
+
+// Rows take new values under their ids.  One chain: the call's ids and rows go up once (the rows into a staging matrix [m][ld],
+// padding zero); their norms by the kernel hnswgpu_create uses; device copies of the four arrays; pcaf_update_place_kernel puts
+// the staged rows and norms where the ids name, and the MAP form of the projection kernel projects the staged rows straight into
+// the copies of the projected rows and their norms.  Every slot writes its own row only: the result does not depend on the order
+// of `ids` or on the split of calls.
+int hnswgpu_pcaf_update(hnswgpu_index *idx, const int32_t *ids, const float *rows, int64_t m) {
+    HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
+    HG_REQUIRE(m >= 0, HNSWGPU_EINVAL, "m must be >= 0");
+    HG_REQUIRE(ids || m == 0, HNSWGPU_EINVAL, "ids is null");
+    HG_REQUIRE(rows || m == 0, HNSWGPU_EINVAL, "rows is null");
+    if (m == 0) return 0;  // nothing to update: nothing happens, whatever the handle holds
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_PCAF_STATE(idx);
+    const int64_t n = idx->n, ld = idx->ld;
+    std::vector<int32_t> uid, from;
+    int64_t at = -1, first = -1;
+    int verdict;
+    try {
+        verdict = ivf_update_slots(ids, m, n, uid, from, &at, &first);  // on the host array, before anything is enqueued
+    } catch (const std::bad_alloc &) {  // (its sorted copy of the ids)
+        set_error("host allocation failed");
+        return HNSWGPU_ENOMEM;
+    }
+    HG_REQUIRE(verdict != 1, HNSWGPU_EINVAL, "ids[%lld] = %d is not a row of the index (n = %lld)", (long long)at, ids[at], (long long)n);
+    HG_REQUIRE(verdict != 2, HNSWGPU_EINVAL, "ids[%lld] = %d is named twice (first at ids[%lld]): two values for one row have no winner",
+               (long long)at, ids[at], (long long)first);
+    HG_TRY(call.quiesce());
+    PcafStagedRows nw;
+    auto update = [&]() -> int {
+        const size_t mm = static_cast<size_t>(m);
+        HG_TRY(nw.alloc(idx, n));
+        // scratch.  s_misc: the call's ids (slot s of the call is its s-th id as it came).  s_misc2: the staging matrix | its norms.
+        auto sect = [](size_t bytes) { return (bytes + 15) / 16 * 16; };
+        HG_TRY(idx->s_misc.ensure(sizeof(int32_t) * mm));
+        HG_TRY(idx->s_misc2.ensure(sect(sizeof(float) * mm * ld) + sizeof(float) * mm));
+        PcafUpdateArgs a;
+        a.n = n;
+        a.m = m;
+        a.ld = ld;
+        a.ids = idx->s_misc.as<int32_t>();
+        float *stage = idx->s_misc2.as<float>();
+        float *snorms = reinterpret_cast<float *>(idx->s_misc2.as<char>() + sect(sizeof(float) * mm * ld));
+        a.stage = stage;
+        a.snorms = snorms;
+        a.new_base = nw.base;
+        a.new_norms = nw.norms;
+        HG_HIP(hipMemcpyAsync(idx->s_misc.p, ids, sizeof(int32_t) * mm, hipMemcpyHostToDevice, st));
+        HG_TRY(pcaf_upload_rows(idx, rows, m, stage, st));
+        HG_TRY(launch_norms(idx->nch, stage, ld, m, snorms, st));
+        HG_TRY(nw.copy_old(idx, n, st));
+        hipLaunchKernelGGL(pcaf_update_place_kernel, dim3(static_cast<unsigned>((m + kNWave - 1) / kNWave)), dim3(kWG), 0, st, a);
+        HG_HIP(hipGetLastError());
+        HG_TRY(launch_pcaf_project(idx, idx->d_pcaf_proj, idx->pcaf_T, stage, ld, m, nw.low, nw.lnorms, st, a.ids, n));
+        if (idx->d_qrows) HG_TRY(quantize_rows(idx, nw.base, n, &nw.qrows, &nw.qmeta, st));  // (as add: one pass over the new base)
+        HG_HIP(hipStreamSynchronize(st));  // (the uploads have read `ids` and `rows`; a failing step shows before the takeover)
+        return 0;
+    };
+    const int rc = update();
+    if (rc != 0) {
+        (void)hipStreamSynchronize(st);  // (nothing of the chain is in flight when `nw` frees what it staged)
+        return rc;
+    }
+    nw.swap_into(idx, n);
+    return call.close();
 }
 
 }  // extern "C"

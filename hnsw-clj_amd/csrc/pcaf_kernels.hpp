@@ -2,7 +2,8 @@
 //
 // Three kernels, one launch each, and nothing of the shape [queries][rows] between them:
 //   1. pcaf_project_kernel: X[m][dim] . P^T -> [m][Tp] on the f32 matrix cores (v_mfma_f32_32x32x2_f32) plus every projected
-//      row's norm in the same pass.  Serves the build (X = the base rows), hnswgpu_pcaf_project and the query side of a search.
+//      row's norm in the same pass.  Serves the build (X = the base rows), hnswgpu_pcaf_project, the query side of a search and
+//      the rows hnswgpu_pcaf_add appends; its MAP form stores every row where a map names (hnswgpu_pcaf_update).
 //   2. pcaf_filter_kernel: a workgroup owns <= 32 projected queries (the B operand, resident in LDS) and streams a contiguous
 //      slab of projected rows past them, 32 rows per wave and step; the 32 x 32 accumulators become cosine distances, each is
 //      tested against its query's running threshold and the survivors are collected per query in LDS; kf keys per query and
@@ -75,13 +76,19 @@ struct PcafProjectArgs {
     int32_t T, Tp;
     float *out;       // [m][Tp]
     float *norms;     // [m]
+    // MAP only (hnswgpu_pcaf_update): row r of X is row dst[r] of out / norms, which hold n_dst rows; distinct per call
+    const int32_t *dst;
+    int64_t n_dst;
 };
 
 // 128 X rows per workgroup, 32 per wave, against all NT * 32 >= Tp components.  Per chunk of 32 floats of dim the workgroup
 // stages the chunk of P (shared by its waves) and of its X rows in LDS, then every wave multiplies its 32 rows with the NT
 // column tiles.  Epilogue: lane (li, half) holds component nt * 32 + li of rows 8 (reg >> 2) + 4 half + (reg & 3): the row
 // goes out in 128-byte runs, and its sum of squares is an fmaf chain over the lane's tiles and a butterfly over the 32 lanes.
-template <int NT>
+// MAP: the same body with a destination map in the epilogue -- row r's components and norm are stored at row dst[r] (checked
+// against n_dst before the store).  A row's bits depend on its values and on P alone, never on r, on its slot in the 128-row block
+// or on where it is stored: each accumulator entry is one row's sum over k, and the norm's butterfly runs over one row's 32 lanes.
+template <int NT, bool MAP = false>
 __global__ __launch_bounds__(kWG) void pcaf_project_kernel(PcafProjectArgs a) {
     __shared__ __align__(16) float Ps[NT * 32 * kPcafProjLd];
     __shared__ __align__(16) float Xs[kPcafProjRows * kPcafProjLd];
@@ -133,16 +140,22 @@ __global__ __launch_bounds__(kWG) void pcaf_project_kernel(PcafProjectArgs a) {
 #pragma unroll
     for (int reg = 0; reg < 16; reg++) {
         const int64_t row = row0 + wave * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * half;
+        bool live = row < a.m;
+        int64_t to = row;
+        if (MAP) {
+            to = live ? a.dst[row] : -1;
+            live = to >= 0 && to < a.n_dst;
+        }
         float s = 0.0f;
 #pragma unroll
         for (int nt = 0; nt < NT; nt++) {
             const float v = acc[nt][reg];  // components >= T are exact zeros (P's rows there are)
             s = __builtin_fmaf(v, v, s);
-            if (row < a.m && nt * 32 + li < a.Tp) a.out[row * a.Tp + nt * 32 + li] = v;
+            if (live && nt * 32 + li < a.Tp) a.out[to * a.Tp + nt * 32 + li] = v;
         }
 #pragma unroll
         for (int off = 1; off < 32; off <<= 1) s = s + __shfl_xor(s, off, kWave);
-        if (row < a.m && li == 0) a.norms[row] = __builtin_sqrtf(s);
+        if (live && li == 0) a.norms[to] = __builtin_sqrtf(s);
     }
 }
 

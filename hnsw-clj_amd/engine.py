@@ -934,6 +934,33 @@ class Index:
         check(lib().hnswgpu_pcaf_project(self._h, _p(X), len(X), _p(out)))
         return out
 
+    def pcaf_add(self, rows):
+        """hnswgpu_pcaf_add: `rows` join the base and, projected by the kernel that projected the old rows, the projected rows;
+        returns the row ids they got."""
+        rows = _queries(rows, self.dim)
+        first = self.n
+        check(lib().hnswgpu_pcaf_add(self._h, _p(rows), len(rows)))
+        self.n += len(rows)
+        return np.arange(first, self.n, dtype=np.int32)
+
+    def pcaf_remove(self, rows):
+        """hnswgpu_pcaf_remove: the rows named by `rows` (row ids, any order, repeats count once) leave the base and the
+        projected rows; the kept rows are renumbered densely in their old order.  Returns n_after, the rows that remain."""
+        rows = np.ascontiguousarray(rows, np.int32).reshape(-1)
+        n_after = C.c_int64(-1)
+        check(lib().hnswgpu_pcaf_remove(self._h, _p(rows), len(rows), C.byref(n_after)))
+        self.n = int(n_after.value)
+        return self.n
+
+    def pcaf_update(self, ids, rows):
+        """hnswgpu_pcaf_update: row ``ids[i]`` takes the values ``rows[i]`` (row ids in any order, none named twice) and is
+        projected again; n, every row id and the projection stay."""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        rows = _queries(rows, self.dim)
+        if len(rows) != len(ids):
+            raise ValueError("%d ids for %d rows" % (len(ids), len(rows)))
+        check(lib().hnswgpu_pcaf_update(self._h, _p(ids), _p(rows), len(ids)))
+
     def pcaf_search(self, Q, k, k_filter=0):
         """hnswgpu_pcaf_search: min(k_filter, 3 k, n) candidates by projected cosine (k_filter 0: the reference's 32), their
         exact cosine distances, the best k; -1 / +inf where fewer are found."""

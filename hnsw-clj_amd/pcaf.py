@@ -15,6 +15,8 @@ rows are state of the handle that holds the original rows, and a search is hnswg
 [queries][rows] intermediate.  The composition stays the default.  Only the one-handle index has the filtered searches
 (search_batch_filtered / _each, search_knn_filtered): a predicate on the ids goes into phase 1 as an allow-mask
 (hnswgpu_pcaf_search_filtered), so the candidates are passing rows -- not the protocol's "search 3k, drop, keep k".
+Only the one-handle index is a live one too: add_vectors / remove_vectors / update_vectors (hnswgpu_pcaf_add / _remove /
+_update) leave the handle what a fresh build over the rows it then holds would be.
 """
 import numpy as np
 
@@ -123,6 +125,78 @@ def search_knn(index, query_vec, k, mode=None):
     q = np.asarray(query_vec, np.float32).reshape(1, -1)
     res = search_batch(index, q, k, mode)
     return res[0] if res else []
+
+
+def _one_handle(index, what):
+    if index.low_index is not None:
+        raise ValueError("%s needs an index built with one_handle=True" % what)
+    return index.high_index
+
+
+def _rows_of(index):
+    rows_of = {}
+    for row, i in enumerate(index.ids):
+        rows_of.setdefault(i, []).append(row)
+    return rows_of
+
+
+def add_vectors(index, data):
+    """The reference's P-HNSW index has no add (build-pcaf-index returns an immutable record); ``data`` has the form
+    ``build_index`` takes; every vector joins the original rows and, projected under the index's projection by the kernel that
+    projected the old rows, the projected rows (hnswgpu_pcaf_add).  Empty ``data`` does nothing.  Returns the index."""
+    handle = _one_handle(index, "add_vectors")
+    ids, rows = _split(data)
+    if len(ids):
+        handle.pcaf_add(rows)
+        index.ids = list(index.ids) + list(ids)
+    return index
+
+
+def remove_vectors(index, ids):
+    """The reference's P-HNSW index has no remove either: ``ids`` are the caller's ids, the form ``index.ids`` holds; their
+    vectors leave the original and the projected rows, the kept rows are renumbered densely in their old order
+    (hnswgpu_pcaf_remove), and ``index.ids`` follows.  An unknown id raises KeyError before the device is touched; an id of
+    several rows removes them all.  Empty ``ids`` does nothing.  Returns the index."""
+    handle = _one_handle(index, "remove_vectors")
+    ids = list(ids)
+    if not ids:
+        return index
+    rows_of = _rows_of(index)
+    rows = []
+    for i in ids:
+        if i not in rows_of:
+            raise KeyError(i)
+        rows.extend(rows_of[i])
+    gone = set(rows)
+    kept = [i for row, i in enumerate(index.ids) if row not in gone]
+    n_after = handle.pcaf_remove(np.asarray(rows, np.int32))
+    assert n_after == len(kept), "hnswgpu_pcaf_remove left %d rows, the id list %d" % (n_after, len(kept))
+    index.ids = kept
+    return index
+
+
+def update_vectors(index, data):
+    """"Update existing vectors" (the open item of the reference's to-do list): ``data`` has the form ``build_index`` takes;
+    the vector stored under each id takes the new values and is projected again (hnswgpu_pcaf_update).  It keeps its id:
+    ``index.ids`` is unchanged.  An unknown id raises KeyError, an id that names several rows or appears twice in ``data``
+    raises ValueError, both before the device is touched.  Empty ``data`` does nothing.  Returns the index."""
+    handle = _one_handle(index, "update_vectors")
+    ids, rows = _split(data)
+    if not len(ids):
+        return index
+    rows_of = _rows_of(index)
+    at, seen = [], set()
+    for i in ids:
+        if i not in rows_of:
+            raise KeyError(i)
+        if len(rows_of[i]) > 1:
+            raise ValueError("id %r names %d rows of the index" % (i, len(rows_of[i])))
+        if i in seen:
+            raise ValueError("id %r appears twice: two values for one vector have no winner" % (i,))
+        seen.add(i)
+        at.append(rows_of[i][0])
+    handle.pcaf_update(np.asarray(at, np.int32), rows)
+    return index
 
 
 def _format(index, ids, d):

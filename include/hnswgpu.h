@@ -1037,7 +1037,7 @@ int hnswgpu_lsh_search_filtered_each_dev(hnswgpu_index *idx, const float *d_Q, i
                                          int32_t probe_radius, int32_t take_main, int32_t take_flip,
                                          const uint32_t *d_allow_each, int32_t *d_out_ids, float *d_out_dist, void *stream);
 
-/* ---- P-HNSW on one handle (hnsw-clj_amd/csrc/pcaf.hip, pcaf_kernels.hpp) --------------------------------------------
+/* ---- P-HNSW on one handle (hnsw-clj_amd/csrc/pcaf.hip, pcaf_kernels.hpp, pcaf_mutate_kernels.hpp) ------------------
  * src/hnsw/ann/dimreduct/pcaf.clj: a Gaussian random projection to n_components = T dimensions, a brute-force cosine
  * search among the projected rows for kf candidates, and an exact cosine re-rank of those on the original rows.  The
  * reference's arithmetic is float32 in both phases, and so is this.  The state -- projection, projected rows, their norms --
@@ -1063,8 +1063,9 @@ int hnswgpu_lsh_search_filtered_each_dev(hnswgpu_index *idx, const float *d_Q, i
  *     get or project on a handle without the state.  nq == 0 returns 0; n == 0: the host search fills the padding, the
  *     _dev search returns -3, as hnswgpu_exact_knn / _dev do.
  *   Other state: hnswgpu_pcaf_build / hnswgpu_set_pcaf return -3 on a handle that holds a graph, a forest, IVF lists or
- *     LSH tables, and every call that installs one of those or adds, removes or updates rows returns -3 on a handle with
- *     P-HNSW state (the projected rows would go stale); the message names why; the handle is untouched.
+ *     LSH tables, and every call of the OTHER families that installs one of those or adds, removes or updates rows returns
+ *     -3 on a handle with P-HNSW state (their code does not know the projected rows, which would go stale); the message
+ *     names why; the handle is untouched.  The rows of such a handle change through the three calls below.
  *   hnswgpu_pcaf_search_filtered / _each / _dev: the allow-mask through the low-dimensional filter
  *     (pcaf_filter_masked_kernel).  Post-filtering ("search 3 k, drop what fails, keep k", protocol.clj:97-102) is at its
  *     worst here: phase 1 keeps only kf <= 3 k candidates, so at a 1 % pass rate nearly all of them fail and the answer is
@@ -1085,13 +1086,62 @@ int hnswgpu_lsh_search_filtered_each_dev(hnswgpu_index *idx, const float *d_Q, i
  *     Known limit: the slabs of phase 1 are sized by rows, not by passing rows, so a mask that passes one contiguous id
  *     range leaves most workgroups without work; balancing needs a count before the launch, which the _dev contract
  *     rules out.
- *   Out of scope: mutating a P-HNSW handle; the index file -- hnswgpu_save writes such a handle without the state, as it
- *     does LSH tables; groups and shards. */
+ *   hnswgpu_pcaf_add / _remove / _update: rows join, leave and take new values on a LIVE handle with P-HNSW state (the
+ *     reference's index is an immutable record; "Update existing vectors" is an open item of its to-do list,
+ *     README.md:172-176).  The one rule behind all three: after the call the handle holds, bit for bit, what
+ *     hnswgpu_create(the rows it should now hold) + hnswgpu_set_rejection_test(same mode) + hnswgpu_set_pcaf(the same
+ *     projection) holds: base and norms, the base-order int8 rows and their meta where the handle has them, the projected
+ *     rows hnswgpu_pcaf_get exports and their norms -- hence the ids and distance bits of hnswgpu_pcaf_search / _filtered /
+ *     _filtered_each and their _dev forms, of hnswgpu_exact_knn, hnswgpu_norms and hnswgpu_pcaf_project.  The rule holds
+ *     because a row's projection and norm from pcaf_project_kernel depend on the row's values and the projection alone, not
+ *     on which slot of which 128-row block the row sits in or where the result is stored: an accumulator entry is one row's
+ *     sum over k in a fixed order, and the norm's butterfly runs over one row's 32 lanes.
+ *     - hnswgpu_pcaf_add: `rows` is m x dim float32 host memory; the rows get ids n .. n + m - 1.  n == 0 is legal: the
+ *       handle hnswgpu_set_pcaf leaves over an empty base, and the one remove-everything leaves.  m rows in one call or in
+ *       any split of calls give the same handle.  The plain projection kernel reads the new rows where they sit in the
+ *       grown base and writes behind device copies of the old projected rows and norms.
+ *     - hnswgpu_pcaf_remove: `rows` is m row ids in host memory, in any order; an id named twice is removed once.  The kept
+ *       rows are renumbered densely in their old order: the new id of a kept row r is the number of kept rows below r.
+ *       *n_after (may be NULL) gets the rows the handle holds afterwards.  Removing every row is legal: it leaves an empty
+ *       handle that still has its projection, and hnswgpu_pcaf_add grows it again.  One pass of a wave per old row
+ *       (pcaf_remove_rows_kernel) moves a kept row's base row, norm, projected row and projected norm to its rank; the
+ *       drop mask and the rank scan are those of hnswgpu_lsh_remove / hnswgpu_ivf_remove.
+ *     - hnswgpu_pcaf_update: `ids` is m row ids in host memory, in any order; `rows` is m x dim float32 host memory; row
+ *       ids[i] takes the values rows[i].  n, every id and the projection stay.  Updating rows to the values they have
+ *       changes nothing, bit for bit.  Every slot of the call writes its own row only, so distinct rows give the same
+ *       handle in one call, in any split of calls, and in any order of `ids`.  Norms by the kernel hnswgpu_create uses, over
+ *       the call's staged rows; the MAP form of the projection kernel projects the staged rows straight into device copies
+ *       of the projected rows and norms, at the rows `ids` names.
+ *     - Everything happens on the device, in one chain on the handle's stream: only the call's ids and rows go up; base
+ *       rows, norms, projected rows and projected norms of untouched rows are copied, never computed again and never read
+ *       back; the int8 rows are made over the new base where the handle has them.  Failure-atomic, like hnswgpu_lsh_add:
+ *       nothing changes in place, every new array is staged under the handle's lock with its streams quiesced, and the
+ *       handle takes the arrays over only after the chain has succeeded -- hnswgpu_pcaf_remove only after ONE small readback
+ *       has shown that the rank scan counts n - (distinct ids) rows (HNSWGPU_EHIP otherwise).  On any failure the staged
+ *       arrays are freed and the handle is what it was.  Searches from other threads wait and see the old or the new index.
+ *       Peak memory: the old plus the new arrays for the length of the call.
+ *     - Cost: one device copy of the base and the projected rows per CALL, whatever m is -- mutate in batches.  Measured
+ *       on one MI355X (profiles/pcaf_mutations.txt: 100,000 x 768 cosine, T = 100; host clock, median of 5): add 0.70 / 0.86 /
+ *       1.52 ms, remove 0.61 / 0.64 / 0.87 ms, update 0.72 / 0.64 / 1.94 ms for m = 1 / 1,024 / 8,192 scattered rows, against
+ *       10.8 - 12.8 ms for the rebuild (hnswgpu_create + hnswgpu_set_pcaf over the rows from host memory): 0.05 - 0.16 of the
+ *       rebuild, faster at every m measured, by less the more rows a call uploads.
+ *     - Returns, checked in this order, the handle untouched in every case: -1 for a null handle (before m == 0 and before
+ *       any HIP call), for m < 0, and for null rows / ids with m > 0; 0 for m == 0 (nothing happens, *n_after = n, whatever
+ *       the handle holds); -3 for a handle without P-HNSW state; -5 from hnswgpu_pcaf_add if n + m >= 2^31 - 1, before `rows`
+ *       is read; -1 for an id outside [0, n) and, for hnswgpu_pcaf_update, an id named twice (two values for one row have no
+ *       defined winner), both checked on the host array before anything is enqueued.
+ *     A handle with P-HNSW state holds no other structure, so there is none to keep in step; hnswgpu_save still writes such
+ *     a handle without the state.
+ *   Out of scope: spare capacity or in-place patching that avoids the per-call copy; the index file -- hnswgpu_save writes
+ *     such a handle without the state, as it does LSH tables; groups and shards; the three-handle composition. */
 int hnswgpu_pcaf_build(hnswgpu_index *idx, int32_t n_components, int64_t seed);
 int hnswgpu_set_pcaf(hnswgpu_index *idx, const float *projection, int32_t n_components);
 int hnswgpu_pcaf_sizes(hnswgpu_index *idx, int32_t *n_components);
 int hnswgpu_pcaf_get(hnswgpu_index *idx, float *projection, float *low_rows);
 int hnswgpu_pcaf_project(hnswgpu_index *idx, const float *X, int64_t m, float *out);
+int hnswgpu_pcaf_add(hnswgpu_index *idx, const float *rows, int64_t m);
+int hnswgpu_pcaf_remove(hnswgpu_index *idx, const int32_t *rows, int64_t m, int64_t *n_after);
+int hnswgpu_pcaf_update(hnswgpu_index *idx, const int32_t *ids, const float *rows, int64_t m);
 int hnswgpu_pcaf_search(hnswgpu_index *idx, const float *Q, int32_t nq, int32_t k, int32_t k_filter, int32_t *out_ids,
                         float *out_dist);
 int hnswgpu_pcaf_search_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t k_filter, int32_t *d_out_ids,
