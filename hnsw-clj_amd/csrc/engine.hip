@@ -1979,6 +1979,18 @@ static int mask_count_scan(hnswgpu_index *idx, const uint32_t *d_allow, int64_t 
     *out = m;
     return 0;
 }
+int group_queries_of(int64_t ld) { return filtered_group_queries(ld); }
+// The same two launches for range.hip, whose hit masks of a slice's queries are G masks of this format (range_kernels.hpp):
+// *blk = [G][*nblk] set bits of mask g below block b, *totals = [G] set bits of mask g, both in s_fblk.
+int mask_counts(hnswgpu_index *idx, const uint32_t *d_masks, int64_t len, int64_t G, hipStream_t st, const uint32_t **blk, int32_t *nblk,
+                const unsigned long long **totals) {
+    MaskArgs m;
+    HG_TRY(mask_count_scan(idx, d_masks, len, G, st, &m));
+    *blk = m.blk;
+    *nblk = m.nblk;
+    *totals = m.total;
+    return 0;
+}
 // ... and the scatter of the masks g0 .. g0 + ng of them: list i at pass_ids + i * stride, at most `cap` entries of it written
 static int mask_scatter(MaskArgs m, int64_t g0, int32_t ng, int32_t *pass_ids, int64_t cap, int64_t stride, hipStream_t st) {
     m.allow += g0 * m.allow_stride;
@@ -2407,7 +2419,7 @@ int hnswgpu_destroy(hnswgpu_index *idx) {
         if (p) (void)hipFree(p);
     DevBuf *bufs[] = {&idx->s_q,   &idx->s_partial, &idx->s_ord,   &idx->s_dist, &idx->s_pairs, &idx->s_ids,
                       &idx->s_outd, &idx->s_probes,  &idx->s_stats, &idx->s_misc, &idx->s_misc2, &idx->s_vis, &idx->s_qp, &idx->s_qn, &idx->s_tile, &idx->s_grp, &idx->s_done, &idx->s_pf, &idx->s_solo, &idx->s_bk, &idx->s_heavy, &idx->s_home, &idx->s_dh, &idx->s_hord,
-                      &idx->s_fmask, &idx->s_fpass, &idx->s_fblk, &idx->s_fids, &idx->s_fdist, &idx->s_flmask, &idx->s_ffoff, &idx->s_feum, &idx->s_feuw, &idx->s_feqc,
+                      &idx->s_fmask, &idx->s_fpass, &idx->s_fblk, &idx->s_fids, &idx->s_fdist, &idx->s_flmask, &idx->s_ffoff, &idx->s_feum, &idx->s_feuw, &idx->s_feqc, &idx->s_rhits, &idx->s_rmeta,
                       &idx->s_pt_items, &idx->s_pt_ids, &idx->s_pt_dist, &idx->s_pt_stats, &idx->s_pt_probes, &idx->s_pcaf_q, &idx->s_pcaf_keys,
                       &idx->s_dense.codes, &idx->s_dense.lb, &idx->slots[0].dense.codes, &idx->slots[0].dense.lb, &idx->slots[1].dense.codes,
                       &idx->slots[1].dense.lb};

@@ -263,6 +263,8 @@ struct hnswgpu_index {
     // ... and for one mask per query: the groups' union masks, the word per union row (who of the group allows it), the
     // selection's per-query candidate counts.  (The lists live in s_fpass, the block counts and totals in s_fblk.)
     hg::DevBuf s_feum, s_feuw, s_feqc;
+    // range search (range_kernels.hpp): a slice's hit words [queries][W]; the call's radii | lims | running total
+    hg::DevBuf s_rhits, s_rmeta;
     uint32_t pf_seq = 0;  // number of the last small launch, helper or several-CU kernel (hnsw.hip: hnsw_number_launch is its one owner)
     size_t s_done_n = 0;  // counters per half of s_done (scan tails | route tails)
     uint32_t vis_gen = 0;  // last generation number handed to an HBM visited slab
@@ -588,6 +590,12 @@ constexpr int64_t kMaskCountDevice = -2;  // ... no readback: the list holds `le
 int mask_compact(hnswgpu_index *idx, const uint32_t *d_allow, int64_t len, int64_t p_host, int64_t *p, hipStream_t st,
                  const unsigned long long **d_total = nullptr);
 int fill_empty_dev(int32_t *d_ids, float *d_dist, int64_t cnt, hipStream_t st);
+// G masks of `len` bits, mask g at d_masks + g * ((len + 31) / 32): per-block prefix counts [G][*nblk] (blocks of 1024 words) and
+// totals [G] in s_fblk, by mask_count_kernel / mask_scan_kernel with mask = blockIdx.y (G <= 65535)
+int mask_counts(hnswgpu_index *idx, const uint32_t *d_masks, int64_t len, int64_t G, hipStream_t st, const uint32_t **blk, int32_t *nblk,
+                const unsigned long long **totals);
+// 32 / 16 / 8 queries per group of the register-row group kernels by row length (filter_kernels.hpp: filtered_group_queries)
+int group_queries_of(int64_t ld);
 // IVF-FLAT filtered search (filter_kernels.hpp; driven by ivf.hip: ivf_filtered_chain)
 int launch_list_mask(hnswgpu_index *idx, const uint32_t *d_allow, uint32_t *d_lmask, hipStream_t st);
 int launch_list_foff(hnswgpu_index *idx, const int32_t *d_pass_pos, const unsigned long long *d_total, int64_t cap, int32_t *d_foff,

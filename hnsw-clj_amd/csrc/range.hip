@@ -1,0 +1,171 @@
+// range.hip -- hnswgpu_range_search / hnswgpu_range_search_dev: every row within a radius of each query, exact, as CSR
+// (lims, ids, distances).  The kernels and the reasons for their shape: range_kernels.hpp.  One body for both entries.
+#include <string.h>
+
+#include "engine.hpp"
+#include "range_kernels.hpp"
+
+namespace hg {
+
+static int launch_range_scan(int nch, const RangeArgs &a, int64_t blocks, hipStream_t st) {
+    HG_REQUIRE(blocks > 0 && blocks < 2147483647LL, HNSWGPU_ELIMIT, "range scan grid too large (%lld blocks)", (long long)blocks);
+    const size_t lds = range_scan_lds_bytes(a.ld, a.tq);
+    const bool l2 = a.metric == METRIC_L2;
+#define CALL(N, R, L)                                                                                          \
+    do {                                                                                                       \
+        static bool rs_attr_done[64] = {};                                                                     \
+        if (attr_needed(rs_attr_done))                                                                         \
+            HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&range_scan_kernel<N, R, L>),           \
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));              \
+        hipLaunchKernelGGL((range_scan_kernel<N, R, L>), dim3(static_cast<unsigned>(blocks)), dim3(kTileThreads), lds, st, a); \
+    } while (0)
+    HG_DISPATCH(nch, l2, CALL);
+#undef CALL
+    HG_HIP(hipGetLastError());
+    return 0;
+}
+
+static int launch_range_fill(int nch, const RangeArgs &a, hipStream_t st) {
+    const bool l2 = a.metric == METRIC_L2;
+    const dim3 grid(static_cast<unsigned>(a.nblk), static_cast<unsigned>(a.nq));
+#define CALL(N, R, L) hipLaunchKernelGGL((range_fill_kernel<N, L>), grid, dim3(kWG), 0, st, a)
+    HG_DISPATCH(nch, l2, CALL);
+#undef CALL
+    HG_HIP(hipGetLastError());
+    return 0;
+}
+
+// Slices of whole query groups: scan into the slice's hit words, counts, lims, and -- unless the call only counts -- fill and
+// sort.  Everything is enqueued on `st`; the running total lives at d_run and nothing is read back.
+static int range_enqueue(hnswgpu_index *idx, const float *d_Q, int32_t nq, const float *d_radius, int32_t flags, int64_t *d_lims,
+                         int32_t *d_ids, float *d_dist, int64_t cap, unsigned long long *d_run, hipStream_t st) {
+    const int64_t n = idx->n, W = (n + 31) / 32;
+    const int tq = group_queries_of(idx->ld);
+    const int64_t G = (static_cast<int64_t>(nq) + tq - 1) / tq;
+    // a slice's hit words stay within the budget (at least one group; at most 65535 queries: a query is a blockIdx.y)
+    const int64_t budget = std::max<int64_t>(0, tune(HNSWGPU_TUNE_FILTER_EACH_MB, 2048)) << 20;
+    const int64_t group_bytes = static_cast<int64_t>(tq) * W * static_cast<int64_t>(sizeof(uint32_t));
+    const int64_t gps = std::max<int64_t>(1, std::min<int64_t>(budget / group_bytes, 65535 / tq));
+    const int64_t slice_q = std::min<int64_t>(gps * tq, nq);
+    HG_TRY(idx->s_rhits.ensure(sizeof(uint32_t) * static_cast<size_t>(slice_q) * static_cast<size_t>(W)));
+    HG_TRY(pad_queries(idx, d_Q, idx->dim, nq, st));
+    for (int64_t g0 = 0; g0 < G; g0 += gps) {
+        const int64_t q0 = g0 * tq;
+        const int32_t nb = static_cast<int32_t>(std::min<int64_t>((g0 + gps) * tq, nq) - q0);
+        const int32_t ng = (nb + tq - 1) / tq;
+        RangeArgs a;
+        memset(&a, 0, sizeof(a));
+        a.rows = idx->d_base;
+        a.row_norms = idx->d_norms;
+        a.ld = idx->ld;
+        a.n = n;
+        a.metric = idx->metric;
+        a.Qp = idx->s_qp.as<float>() + q0 * idx->ld;
+        a.q_norms = idx->s_qn.as<float>() + q0;
+        a.radius = d_radius + q0;
+        a.nq = nb;
+        a.tq = tq;
+        a.ngroups = ng;
+        a.nwords = W;
+        a.hits = idx->s_rhits.as<uint32_t>();
+        // chunks of whole 256-row tiles, about 2048 workgroups in all: a workgroup stages its query group once per chunk
+        const int64_t tiles = (n + kTileRows - 1) / kTileRows;
+        const int64_t want = std::max<int64_t>(1, std::min<int64_t>(tiles, (2048 + ng - 1) / ng));
+        a.chunk_rows = (tiles + want - 1) / want * kTileRows;
+        const int64_t nchunks = (n + a.chunk_rows - 1) / a.chunk_rows;
+        hipEvent_t e0;
+        prof_begin(idx, PROF_IVF_SCAN, st, &e0);
+        HG_TRY(launch_range_scan(idx->nch, a, nchunks * ng, st));
+        prof_end(idx, PROF_IVF_SCAN, st, e0);
+        HG_TRY(mask_counts(idx, a.hits, n, nb, st, &a.blk, &a.nblk, &a.qtot));
+        HG_REQUIRE(a.nblk == (W + kRangeFillWords - 1) / kRangeFillWords, HNSWGPU_EHIP, "the count pass and the fill pass disagree about a block");
+        a.run = d_run;
+        a.first = g0 == 0;
+        a.lims = d_lims + q0;
+        a.out_ids = d_ids;
+        a.out_dist = d_dist;
+        a.cap = cap;
+        hipLaunchKernelGGL(range_lims_kernel, dim3(1), dim3(kRangeSortThreads), 0, st, a);
+        HG_HIP(hipGetLastError());
+        if (!d_ids) continue;  // count only
+        HG_TRY(launch_range_fill(idx->nch, a, st));
+        if (flags & HNSWGPU_RANGE_BY_DISTANCE) {
+            hipLaunchKernelGGL(range_sort_kernel, dim3(static_cast<unsigned>(nb)), dim3(kRangeSortThreads), 0, st, a);
+            HG_HIP(hipGetLastError());
+        }
+    }
+    return 0;
+}
+
+static int check_range_args(const hnswgpu_index *idx, const void *Q, int32_t nq, const void *radius, int32_t flags, const void *lims,
+                            const void *ids, const void *dist, int64_t cap) {
+    HG_REQUIRE(idx, HNSWGPU_EINVAL, "idx is null");
+    HG_REQUIRE(nq >= 0, HNSWGPU_EINVAL, "nq < 0");
+    HG_REQUIRE((flags & ~HNSWGPU_RANGE_BY_DISTANCE) == 0, HNSWGPU_EINVAL, "unknown flag bits: %d", flags);
+    HG_REQUIRE(cap >= 0, HNSWGPU_EINVAL, "cap < 0");
+    HG_REQUIRE((ids == nullptr) == (dist == nullptr), HNSWGPU_EINVAL, "out_ids and out_dist: both or neither");
+    HG_REQUIRE(ids || cap == 0, HNSWGPU_EINVAL, "a count-only call (no output arrays) takes cap == 0");
+    HG_REQUIRE(nq == 0 || (Q && radius && lims), HNSWGPU_EINVAL, "null argument");
+    return 0;
+}
+
+}  // namespace hg
+
+using namespace hg;
+
+int hnswgpu_range_search_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, const float *d_radius, int32_t flags, int64_t *d_lims,
+                             int32_t *d_out_ids, float *d_out_dist, int64_t cap, void *stream) {
+    HG_TRY(check_range_args(idx, d_Q, nq, d_radius, flags, d_lims, d_out_ids, d_out_dist, cap));
+    if (nq == 0) return 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Call call;
+    HG_TRY(call.open(idx, st));
+    if (idx->n == 0) {
+        hipLaunchKernelGGL(range_zero_lims_kernel, dim3((nq + 1 + 255) / 256), dim3(256), 0, st, d_lims, static_cast<int64_t>(nq) + 1);
+        HG_HIP(hipGetLastError());
+        return call.close();
+    }
+    HG_TRY(idx->s_rmeta.ensure(sizeof(unsigned long long)));
+    HG_TRY(range_enqueue(idx, d_Q, nq, d_radius, flags, d_lims, d_out_ids, d_out_dist, cap, idx->s_rmeta.as<unsigned long long>(), st));
+    return call.close();
+}
+
+int hnswgpu_range_search(hnswgpu_index *idx, const float *Q, int32_t nq, const float *radius, int32_t flags, int64_t *lims,
+                         int32_t *out_ids, float *out_dist, int64_t cap) {
+    HG_TRY(check_range_args(idx, Q, nq, radius, flags, lims, out_ids, out_dist, cap));
+    if (nq == 0) {
+        if (lims) lims[0] = 0;
+        return 0;
+    }
+    if (idx->n == 0) {
+        memset(lims, 0, sizeof(int64_t) * (static_cast<size_t>(nq) + 1));
+        return 0;
+    }
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_TRY(upload_queries(idx, Q, nq, st));
+    // s_rmeta: [running total][lims: nq + 1][radii: nq]
+    const size_t lims_bytes = sizeof(int64_t) * (static_cast<size_t>(nq) + 1);
+    HG_TRY(idx->s_rmeta.ensure(sizeof(unsigned long long) + lims_bytes + sizeof(float) * static_cast<size_t>(nq)));
+    unsigned long long *d_run = idx->s_rmeta.as<unsigned long long>();
+    int64_t *d_lims = reinterpret_cast<int64_t *>(d_run + 1);
+    float *d_radius = reinterpret_cast<float *>(d_lims + nq + 1);
+    HG_HIP(hipMemcpyAsync(d_radius, radius, sizeof(float) * static_cast<size_t>(nq), hipMemcpyHostToDevice, st));
+    if (out_ids) {
+        HG_TRY(idx->s_ids.ensure(sizeof(int32_t) * static_cast<size_t>(cap)));
+        HG_TRY(idx->s_outd.ensure(sizeof(float) * static_cast<size_t>(cap)));
+    }
+    HG_TRY(range_enqueue(idx, idx->s_q.as<float>(), nq, d_radius, flags, d_lims, out_ids ? idx->s_ids.as<int32_t>() : nullptr,
+                         out_ids ? idx->s_outd.as<float>() : nullptr, cap, d_run, st));
+    HG_HIP(hipMemcpyAsync(lims, d_lims, lims_bytes, hipMemcpyDeviceToHost, st));
+    HG_TRY(call.sync());
+    const int64_t total = lims[nq];
+    if (out_ids && total > cap) {
+        (void)call.close();
+        set_error("the result holds %lld entries, the arrays %lld: lims is complete, size the arrays by lims[nq]", (long long)total, (long long)cap);
+        return HNSWGPU_ELIMIT;
+    }
+    if (out_ids && total > 0) HG_TRY(call.stage_out(out_ids, out_dist, total));
+    return call.close();
+}

@@ -13,6 +13,7 @@ from ._native import COSINE, DOT, L2, check, debug_counter, get_tuning, lib, set
 METRICS = {"cosine": COSINE, "l2": L2, "euclidean": L2, "dot": DOT, COSINE: COSINE, L2: L2, DOT: DOT}
 PROF_IVF_SCAN, PROF_HNSW, PROF_ASSIGN, PROF_UPDATE = 0, 1, 2, 3
 BUILD_SEQUENTIAL, BUILD_HEURISTIC, BUILD_SYMMETRIC, BUILD_EXTEND = 1, 2, 4, 8     # include/hnswgpu.h: HNSWGPU_BUILD_*
+RANGE_BY_DISTANCE = 1                                                              # HNSWGPU_RANGE_BY_DISTANCE
 
 
 def _p(a):
@@ -344,6 +345,30 @@ class Index:
         d = np.empty((len(Q), k), np.float32)
         check(lib().hnswgpu_exact_knn_filtered_each(self._h, _p(Q), len(Q), k, _p(allow_each), _p(ids), _p(d)))
         return ids, d
+
+    def _radii(self, radius, nq):
+        r = np.asarray(radius, np.float32)
+        r = np.full(nq, r, np.float32) if r.ndim == 0 else np.ascontiguousarray(r)
+        if r.shape != (nq,):
+            raise ValueError("radius must be a scalar or one value per query (%d), got %s" % (nq, r.shape))
+        return r
+
+    def range_search(self, Q, radius, by_distance=False):
+        """hnswgpu_range_search: every row within ``radius`` (a scalar, or one value per query) of each query, exact, as CSR --
+        ``(lims, ids, dist)``: query q's rows are ids[lims[q]:lims[q + 1]], ascending by row id, or by (distance, row id) with
+        ``by_distance``.  Counts first, then allocates, then fills."""
+        Q = _queries(Q, self.dim)
+        nq = len(Q)
+        r = self._radii(radius, nq)
+        flags = RANGE_BY_DISTANCE if by_distance else 0
+        lims = np.zeros(nq + 1, np.int64)
+        check(lib().hnswgpu_range_search(self._h, _p(Q), nq, _p(r), flags, _p(lims), None, None, 0))
+        total = int(lims[nq])
+        ids = np.empty(total, np.int32)
+        d = np.empty(total, np.float32)
+        if total:
+            check(lib().hnswgpu_range_search(self._h, _p(Q), nq, _p(r), flags, _p(lims), _p(ids), _p(d), total))
+        return lims, ids, d
 
     def rerank(self, Q, cand, k):
         """Per query: exact distances to its candidate rows cand[q] (-1 = skip), stable sort, first k."""
@@ -891,6 +916,27 @@ class Index:
         check(lib().hnswgpu_rerank_dev(self._h, Q.data_ptr(), Q.shape[0], cand.data_ptr(), cand.shape[1], k,
                                        ids.data_ptr(), d.data_ptr(), st))
         return ids, d
+
+    def range_search_dev(self, Q, radius, cap, by_distance=False, out=None):
+        """hnswgpu_range_search_dev on torch's current stream: enqueues only and never synchronises.  ``radius``: a float32
+        device tensor of nq values; ``cap``: entries of ids / dist (0 = count only: ids and dist come back as None).  Returns
+        ``(lims, ids, dist)`` tensors; no entry at or past ``cap`` is written, and the caller compares lims[-1] with cap."""
+        import torch
+
+        Q, _, _, st = self._dev_args(Q, 1, out=(None, None))
+        nq, cap = Q.shape[0], int(cap)
+        assert radius.is_cuda and radius.dtype == torch.float32 and radius.numel() == nq
+        radius = radius.contiguous()
+        if out is not None:
+            lims, ids, d = out
+        else:
+            lims = torch.empty(nq + 1, dtype=torch.int64, device=Q.device)
+            ids = torch.empty(cap, dtype=torch.int32, device=Q.device) if cap else None
+            d = torch.empty(cap, dtype=torch.float32, device=Q.device) if cap else None
+        check(lib().hnswgpu_range_search_dev(self._h, Q.data_ptr(), nq, radius.data_ptr(), RANGE_BY_DISTANCE if by_distance else 0,
+                                             lims.data_ptr(), ids.data_ptr() if ids is not None else None,
+                                             d.data_ptr() if d is not None else None, cap, st))
+        return lims, ids, d
 
     def dense_distances_dev(self, Q, out=None):
         import torch

@@ -183,6 +183,28 @@ def search_batch(graph, queries, k, ef=None, route=False):
     return [_format(graph, ids[i], d[i]) for i in range(len(queries))]
 
 
+def search_radius_batch(graph, queries, radius):
+    """Every row within ``radius`` (a scalar or one value per query) of each query -- exact, not in the reference, whose REPL
+    speaks of results as "at least 80 % similar" but can only ask for k of them.  One list per query of ``{"id", "distance"}``
+    with the caller's ids, ascending by distance (hnswgpu_range_search with HNSWGPU_RANGE_BY_DISTANCE: sorted on the device)."""
+    queries = np.asarray(queries, np.float32)
+    if queries.ndim == 1:
+        queries = queries[None, :]
+    if len(queries) == 0:
+        return []
+    if graph.index.n == 0:
+        return [[] for _ in queries]
+    lims, ids, d = graph.index.range_search(queries, radius, by_distance=True)
+    return [_format(graph, ids[lims[q]:lims[q + 1]], d[lims[q]:lims[q + 1]]) for q in range(len(queries))]
+
+
+def search_radius(graph, query_vec, radius):
+    """search_radius_batch for one query."""
+    if graph.index.n == 0:
+        return []
+    return search_radius_batch(graph, np.asarray(query_vec, np.float32)[None, :], radius)[0]
+
+
 def filtered_plan(n, p, k, ef=None):
     """How a filtered search over n rows, p of them passing, is served: ``("scan" | "graph", ef')`` -- a pure function of
     counts the reference and the engine already fix.  The reference over-fetches by 3 (protocol.clj:101), and a result list

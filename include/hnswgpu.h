@@ -649,6 +649,39 @@ int hnswgpu_ivf_search_filtered_each(hnswgpu_index *idx, const float *Q, int32_t
 int hnswgpu_ivf_search_filtered_each_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t k, int32_t nprobe,
                                          const uint32_t *d_allow_each, int32_t *d_out_ids, float *d_out_dist, void *stream);
 
+/* ---- range search -------------------------------------------------------------------------------------------
+ * Every row within a radius of each query, exact, as CSR -- the question behind near-duplicate detection and "every verse at
+ * least 80 % similar", which no top-k call answers (a guessed k truncates or pads) and hnswgpu_dense_distances answers with an
+ * [nq][n] float array for the caller to threshold.
+ *   radius[nq]: one radius per query.  Row i belongs to query q's result iff d(q, i) <= radius[q], where d is the handle's
+ *     metric exactly as hnswgpu_batch_distances returns it, bit for bit (cosine, L2, dot = -dot), at every batch size.  A NaN
+ *     radius matches nothing; +inf matches every row whose distance is not NaN.
+ *   lims[nq + 1]: the CSR offsets.  Query q's results are the entries [lims[q], lims[q + 1]) of out_ids / out_dist;
+ *     lims[0] == 0 and lims[nq] is the size of the whole result.
+ *   Order inside a segment: ascending row id (flags 0) -- the canonical form, the same on every run -- or, with
+ *     HNSWGPU_RANGE_BY_DISTANCE, ascending (distance, row id); a distance of -0 then comes back as +0.
+ *   out_ids == NULL and out_dist == NULL with cap == 0: the count alone -- lims is written and nothing else; this is how a
+ *     caller sizes its arrays.  Exactly one of the two NULL, or both NULL with cap != 0, is an error (-1).
+ *   cap: entries out_ids / out_dist hold.  lims[nq] > cap: lims is complete and correct, the host entry returns
+ *     HNSWGPU_ELIMIT and leaves out_* unspecified.
+ *   hnswgpu_range_search_dev enqueues only and NEVER synchronises: it cannot know the result's size, so it writes no entry at
+ *     a position >= cap, returns 0, and ITS CALLER compares lims[nq] with cap once the stream has passed the call (entries
+ *     below cap are then the head of the result in id order; under HNSWGPU_RANGE_BY_DISTANCE a cut segment is unspecified).
+ *   -1 for a null idx, Q, radius or lims, for unknown flag bits and for cap < 0; nq == 0 returns 0; n == 0 writes all-zero lims.
+ *   Works on any handle, whatever else it holds (graph, lists, tables, forest, P-HNSW state): it reads the base rows and their
+ *     norms alone.  The hit bits of a slice of query groups (nq x (n + 31) / 32 words) are bounded by HNSWGPU_TUNE_FILTER_EACH_MB.
+ *   How (hnsw-clj_amd/csrc/range_kernels.hpp): the group scan of the filtered exact search with the store replaced by a compare
+ *     and a ballot -- a wave owns 32 consecutive rows, one word of every query's hit mask -- then popcounts and scans (no
+ *     atomic anywhere: the result does not depend on scheduling), then a second look at the hits alone, whose distances are
+ *     recomputed one wave per row, and a bitonic sort per query for the distance order.
+ *   Out of scope: an allow-mask; range search through a graph, lists, tables or the low-dimensional filter (all of them would be
+ *     approximate); groups, shards and forests; combining concurrent callers. */
+#define HNSWGPU_RANGE_BY_DISTANCE 1
+int hnswgpu_range_search(hnswgpu_index *idx, const float *Q, int32_t nq, const float *radius, int32_t flags,
+                         int64_t *lims, int32_t *out_ids, float *out_dist, int64_t cap);
+int hnswgpu_range_search_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, const float *d_radius, int32_t flags,
+                             int64_t *d_lims, int32_t *d_out_ids, float *d_out_dist, int64_t cap, void *stream);
+
 /* ---- persistence ------------------------------------------------------------------------------------------
  * One flat binary file (header + plain arrays; layout in hnsw-clj_amd/csrc/persist.hip) with the base
  * vectors, the graph and the IVF lists -- replaces helper/index-io's save-index / load-index, an EDN
@@ -842,7 +875,7 @@ int hnswgpu_hnsw_dense_bounds(hnswgpu_index *idx, const float *Q, int32_t nq, in
 #define HNSWGPU_TUNE_BUILD_KEEP_ROWS 59 /* 0 = the builder's heuristic selection fetches the already selected rows again for every candidate instead of keeping them in registers (A/B; the graph does not depend on it) */
 #define HNSWGPU_TUNE_QUERY_WAVES 60 /* the per-query kernels of large IVF batches (home-list selection) with one WAVE per query, four queries per workgroup, instead of a workgroup per query: -1 from 2048 queries, 0 never, 1 wherever a wave can serve a query (k <= 64) */
 #define HNSWGPU_TUNE_HNSW_ORDER 61 /* launches of the one-wave-per-query kernel serve their queries in the order of their nearest pivot row (min(256, n) base rows at a fixed stride, judged on the int8 rows), dealt so that neighbouring queries run on one XCD at one time -- a hint for the L2s, results never depend on it: 1 = search launches on handles with int8 rows from a batch size (default), 0 = never (A/B), 2 = every such launch (tests) */
-#define HNSWGPU_TUNE_FILTER_EACH_MB 62 /* hnswgpu_exact_knn_filtered_each: bound of the dense distance scratch of one slice of query groups, in MiB (default 2048, the single-mask call's bound; at least one group per slice) */
+#define HNSWGPU_TUNE_FILTER_EACH_MB 62 /* hnswgpu_exact_knn_filtered_each: bound of the dense distance scratch of one slice of query groups, in MiB (default 2048, the single-mask call's bound; at least one group per slice).  hnswgpu_range_search: the same bound for the hit words of one slice of query groups (0 = one group per slice) */
 #define HNSWGPU_TUNE_COUNT 63
 int hnswgpu_set_tuning(int32_t key, int64_t value);
 int hnswgpu_get_tuning(int32_t key, int64_t *value, int32_t *is_set);
