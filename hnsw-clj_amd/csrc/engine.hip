@@ -2276,6 +2276,53 @@ static int filtered_chain(hnswgpu_index *idx, MaskForm form, const float *d_Q, i
     return 0;
 }
 
+// The pass lists of a filtered range search (range.hip), with NOTHING read back: every list holds n entries and its length
+// goes to d_cnt, device memory of the caller's (s_fblk, where the scan leaves it, is the next count pass's).
+//   Single -- d_allow is one mask: its list in s_fpass, its length in d_cnt[0]; *words = null.
+//   Each -- d_allow is [nq][W], the masks of whole query groups of tq: filtered_chain's union chain with capacity n -- group
+//   g's union list at s_fpass + g * n, its length in d_cnt[g], and at s_feuw + g * n the word per union row.
+int mask_lists_dev(hnswgpu_index *idx, MaskForm form, const uint32_t *d_allow, int32_t nq, int tq, hipStream_t st,
+                   unsigned long long *d_cnt, const int32_t **lists, const uint32_t **words) {
+    const int64_t n = idx->n, W = (n + 31) / 32;
+    *words = nullptr;
+    if (form == MaskForm::Single) {
+        int64_t cap = 0;
+        const unsigned long long *d_total = nullptr;
+        HG_TRY(mask_compact(idx, d_allow, n, kMaskCountDevice, &cap, st, &d_total));
+        HG_HIP(hipMemcpyAsync(d_cnt, d_total, sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
+        *lists = idx->s_fpass.as<int32_t>();
+        return 0;
+    }
+    const int64_t G = (static_cast<int64_t>(nq) + tq - 1) / tq;
+    HG_REQUIRE(G <= 65535, HNSWGPU_ELIMIT, "too many query groups for one slice (%lld, at most 65535)", (long long)G);
+    HG_TRY(idx->s_feum.ensure(sizeof(uint32_t) * static_cast<size_t>(G * W)));
+    HG_TRY(idx->s_fpass.ensure(sizeof(int32_t) * static_cast<size_t>(G * n)));
+    HG_TRY(idx->s_feuw.ensure(sizeof(uint32_t) * static_cast<size_t>(G * n)));
+    UnionArgs u;
+    memset(&u, 0, sizeof(u));
+    u.allow_each = d_allow;
+    u.n = n;
+    u.nwords = W;
+    u.nq = nq;
+    u.tq = tq;
+    u.um = idx->s_feum.as<uint32_t>();
+    const unsigned gy = static_cast<unsigned>(G);
+    hipLaunchKernelGGL(mask_union_kernel, dim3(static_cast<unsigned>((W + kMaskThreads - 1) / kMaskThreads), gy), dim3(kMaskThreads), 0, st, u);
+    MaskArgs m;
+    HG_TRY(mask_count_scan(idx, u.um, n, G, st, &m));
+    HG_TRY(mask_scatter(m, 0, static_cast<int32_t>(G), idx->s_fpass.as<int32_t>(), n, n, st));
+    HG_HIP(hipMemcpyAsync(d_cnt, m.total, sizeof(unsigned long long) * static_cast<size_t>(G), hipMemcpyDeviceToDevice, st));
+    u.upass = idx->s_fpass.as<int32_t>();
+    u.up = d_cnt;
+    u.uw = idx->s_feuw.as<uint32_t>();
+    u.pstride = n;
+    hipLaunchKernelGGL(union_words_kernel, dim3(static_cast<unsigned>((n + kMaskThreads - 1) / kMaskThreads), gy), dim3(kMaskThreads), 0, st, u);
+    HG_HIP(hipGetLastError());
+    *lists = u.upass;
+    *words = u.uw;
+    return 0;
+}
+
 int launch_filter_take(const int32_t *ids_in, const float *dist_in, int32_t nq, int32_t kk, int32_t k, const uint32_t *d_allow,
                        int64_t n, int32_t *d_out_ids, float *d_out_dist, hipStream_t st, int64_t allow_stride) {
     if (nq <= 0) return 0;
@@ -2419,7 +2466,7 @@ int hnswgpu_destroy(hnswgpu_index *idx) {
         if (p) (void)hipFree(p);
     DevBuf *bufs[] = {&idx->s_q,   &idx->s_partial, &idx->s_ord,   &idx->s_dist, &idx->s_pairs, &idx->s_ids,
                       &idx->s_outd, &idx->s_probes,  &idx->s_stats, &idx->s_misc, &idx->s_misc2, &idx->s_vis, &idx->s_qp, &idx->s_qn, &idx->s_tile, &idx->s_grp, &idx->s_done, &idx->s_pf, &idx->s_solo, &idx->s_bk, &idx->s_heavy, &idx->s_home, &idx->s_dh, &idx->s_hord,
-                      &idx->s_fmask, &idx->s_fpass, &idx->s_fblk, &idx->s_fids, &idx->s_fdist, &idx->s_flmask, &idx->s_ffoff, &idx->s_feum, &idx->s_feuw, &idx->s_feqc, &idx->s_rhits, &idx->s_rmeta,
+                      &idx->s_fmask, &idx->s_fpass, &idx->s_fblk, &idx->s_fids, &idx->s_fdist, &idx->s_flmask, &idx->s_ffoff, &idx->s_feum, &idx->s_feuw, &idx->s_feqc, &idx->s_rhits, &idx->s_rmeta, &idx->s_rcnt,
                       &idx->s_pt_items, &idx->s_pt_ids, &idx->s_pt_dist, &idx->s_pt_stats, &idx->s_pt_probes, &idx->s_pcaf_q, &idx->s_pcaf_keys,
                       &idx->s_dense.codes, &idx->s_dense.lb, &idx->slots[0].dense.codes, &idx->slots[0].dense.lb, &idx->slots[1].dense.codes,
                       &idx->slots[1].dense.lb};

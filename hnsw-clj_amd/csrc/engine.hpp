@@ -265,6 +265,8 @@ struct hnswgpu_index {
     hg::DevBuf s_feum, s_feuw, s_feqc;
     // range search (range_kernels.hpp): a slice's hit words [queries][W]; the call's radii | lims | running total
     hg::DevBuf s_rhits, s_rmeta;
+    // ... under an allow-mask (range_filtered_kernels.hpp): the lengths of a slice's pass lists, which nobody reads back
+    hg::DevBuf s_rcnt;
     uint32_t pf_seq = 0;  // number of the last small launch, helper or several-CU kernel (hnsw.hip: hnsw_number_launch is its one owner)
     size_t s_done_n = 0;  // counters per half of s_done (scan tails | route tails)
     uint32_t vis_gen = 0;  // last generation number handed to an HBM visited slab
@@ -594,6 +596,10 @@ int fill_empty_dev(int32_t *d_ids, float *d_dist, int64_t cnt, hipStream_t st);
 // totals [G] in s_fblk, by mask_count_kernel / mask_scan_kernel with mask = blockIdx.y (G <= 65535)
 int mask_counts(hnswgpu_index *idx, const uint32_t *d_masks, int64_t len, int64_t G, hipStream_t st, const uint32_t **blk, int32_t *nblk,
                 const unsigned long long **totals);
+// The pass lists of a filtered range search, nothing read back (engine.hip): Single -- the mask's list [n] and d_cnt[0] its
+// length; Each -- per group of tq queries the union list [G][n], d_cnt[G] and the words [G][n] (bit j: query j allows the row)
+int mask_lists_dev(hnswgpu_index *idx, MaskForm form, const uint32_t *d_allow, int32_t nq, int tq, hipStream_t st,
+                   unsigned long long *d_cnt, const int32_t **lists, const uint32_t **words);
 // 32 / 16 / 8 queries per group of the register-row group kernels by row length (filter_kernels.hpp: filtered_group_queries)
 int group_queries_of(int64_t ld);
 // IVF-FLAT filtered search (filter_kernels.hpp; driven by ivf.hip: ivf_filtered_chain)

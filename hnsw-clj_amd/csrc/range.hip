@@ -1,8 +1,11 @@
 // range.hip -- hnswgpu_range_search / hnswgpu_range_search_dev: every row within a radius of each query, exact, as CSR
 // (lims, ids, distances).  The kernels and the reasons for their shape: range_kernels.hpp.  One body for both entries.
+// hnswgpu_range_search_filtered[_each][_dev]: the same under an allow-mask, one per call or one per query, by a gathered scan
+// and a gathered fill over the masks' pass lists (range_filtered_kernels.hpp).  One body for the four entries.
 #include <string.h>
 
 #include "engine.hpp"
+#include "range_filtered_kernels.hpp"
 #include "range_kernels.hpp"
 
 namespace hg {
@@ -109,6 +112,177 @@ static int check_range_args(const hnswgpu_index *idx, const void *Q, int32_t nq,
     return 0;
 }
 
+// ---- under an allow-mask ---------------------------------------------------------------------------------------------------
+static int launch_range_gather_scan(int nch, MaskForm form, const RangeGatherArgs &a, int64_t blocks, hipStream_t st) {
+    HG_REQUIRE(blocks > 0 && blocks < 2147483647LL, HNSWGPU_ELIMIT, "range scan grid too large (%lld blocks)", (long long)blocks);
+    const size_t lds = range_scan_lds_bytes(a.r.ld, a.r.tq);
+    const bool l2 = a.r.metric == METRIC_L2;
+#define CALLE(N, R, L, E)                                                                                                 \
+    do {                                                                                                                  \
+        static bool rg_attr_done[64] = {};                                                                                \
+        if (attr_needed(rg_attr_done))                                                                                    \
+            HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&range_gather_scan_kernel<N, R, L, E>),            \
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                         \
+        hipLaunchKernelGGL((range_gather_scan_kernel<N, R, L, E>), dim3(static_cast<unsigned>(blocks)), dim3(kTileThreads), lds, st, a); \
+    } while (0)
+#define CALL(N, R, L)                                     \
+    do {                                                  \
+        if (form == MaskForm::Each) CALLE(N, R, L, true); \
+        else CALLE(N, R, L, false);                       \
+    } while (0)
+    HG_DISPATCH(nch, l2, CALL);
+#undef CALL
+#undef CALLE
+    HG_HIP(hipGetLastError());
+    return 0;
+}
+
+static int launch_range_fill_gather(int nch, const RangeGatherArgs &a, hipStream_t st) {
+    const bool l2 = a.r.metric == METRIC_L2;
+    const dim3 grid(static_cast<unsigned>(a.r.nblk), static_cast<unsigned>(a.r.nq));
+#define CALL(N, R, L) hipLaunchKernelGGL((range_fill_gather_kernel<N, L>), grid, dim3(kWG), 0, st, a)
+    HG_DISPATCH(nch, l2, CALL);
+#undef CALL
+    HG_HIP(hipGetLastError());
+    return 0;
+}
+
+// range_enqueue over pass lists.  Single: the call's mask is compacted once, before the slices.  Each: d_allow is [nq][W] and
+// every slice compacts the unions of ITS groups; the slice budget covers their lists and words (8 n bytes per group) and their
+// union masks beside the hit words.  Nothing is read back: lists and grids are sized by n, the lists' lengths stay in s_rcnt.
+static int range_filtered_enqueue(hnswgpu_index *idx, MaskForm form, const float *d_Q, int32_t nq, const float *d_radius, int32_t flags,
+                                  const uint32_t *d_allow, int64_t *d_lims, int32_t *d_ids, float *d_dist, int64_t cap,
+                                  unsigned long long *d_run, hipStream_t st) {
+    const bool each = form == MaskForm::Each;
+    const int64_t n = idx->n, W = (n + 31) / 32;
+    const int tq = group_queries_of(idx->ld);
+    const int64_t G = (static_cast<int64_t>(nq) + tq - 1) / tq;
+    const int64_t budget = std::max<int64_t>(0, tune(HNSWGPU_TUNE_FILTER_EACH_MB, 2048)) << 20;
+    const int64_t group_bytes = static_cast<int64_t>(tq) * W * static_cast<int64_t>(sizeof(uint32_t)) + (each ? 8 * n + 4 * W : 0);
+    const int64_t gps = std::max<int64_t>(1, std::min<int64_t>(budget / group_bytes, 65535 / tq));
+    const int64_t slice_q = std::min<int64_t>(gps * tq, nq);
+    HG_TRY(idx->s_rhits.ensure(sizeof(uint32_t) * static_cast<size_t>(slice_q) * static_cast<size_t>(W)));
+    HG_TRY(idx->s_rcnt.ensure(sizeof(unsigned long long) * static_cast<size_t>(each ? (slice_q + tq - 1) / tq : 1)));
+    HG_TRY(pad_queries(idx, d_Q, idx->dim, nq, st));
+    RangeGatherArgs ga;
+    memset(&ga, 0, sizeof(ga));
+    ga.cnt = idx->s_rcnt.as<unsigned long long>();
+    if (!each) HG_TRY(mask_lists_dev(idx, form, d_allow, nq, tq, st, idx->s_rcnt.as<unsigned long long>(), &ga.pass, &ga.uw));
+    for (int64_t g0 = 0; g0 < G; g0 += gps) {
+        const int64_t q0 = g0 * tq;
+        const int32_t nb = static_cast<int32_t>(std::min<int64_t>((g0 + gps) * tq, nq) - q0);
+        const int32_t ng = (nb + tq - 1) / tq;
+        if (each) {
+            HG_TRY(mask_lists_dev(idx, form, d_allow + q0 * W, nb, tq, st, idx->s_rcnt.as<unsigned long long>(), &ga.pass, &ga.uw));
+            ga.lstride = n;
+        }
+        RangeArgs &a = ga.r;
+        memset(&a, 0, sizeof(a));
+        a.rows = idx->d_base;
+        a.row_norms = idx->d_norms;
+        a.ld = idx->ld;
+        a.n = n;
+        a.metric = idx->metric;
+        a.Qp = idx->s_qp.as<float>() + q0 * idx->ld;
+        a.q_norms = idx->s_qn.as<float>() + q0;
+        a.radius = d_radius + q0;
+        a.nq = nb;
+        a.tq = tq;
+        a.ngroups = ng;
+        a.nwords = W;
+        a.hits = idx->s_rhits.as<uint32_t>();
+        // the unfiltered scan's grid: chunks of whole tiles of the n positions a list can hold, about 2048 workgroups in all.  The
+        // kernel cuts its list -- p positions, known on the device alone -- into as many chunks itself.
+        const int64_t tiles = (n + kTileRows - 1) / kTileRows;
+        const int64_t want = std::max<int64_t>(1, std::min<int64_t>(tiles, (2048 + ng - 1) / ng));
+        a.chunk_rows = (tiles + want - 1) / want * kTileRows;
+        ga.nchunks = static_cast<int32_t>((n + a.chunk_rows - 1) / a.chunk_rows);
+        hipEvent_t e0;
+        prof_begin(idx, PROF_IVF_SCAN, st, &e0);
+        HG_TRY(launch_range_gather_scan(idx->nch, form, ga, static_cast<int64_t>(ga.nchunks) * ng, st));
+        prof_end(idx, PROF_IVF_SCAN, st, e0);
+        HG_TRY(mask_counts(idx, a.hits, n, nb, st, &a.blk, &a.nblk, &a.qtot));
+        HG_REQUIRE(a.nblk == (W + kRangeFillWords - 1) / kRangeFillWords, HNSWGPU_EHIP, "the count pass and the fill pass disagree about a block");
+        a.run = d_run;
+        a.first = g0 == 0;
+        a.lims = d_lims + q0;
+        a.out_ids = d_ids;
+        a.out_dist = d_dist;
+        a.cap = cap;
+        hipLaunchKernelGGL(range_lims_kernel, dim3(1), dim3(kRangeSortThreads), 0, st, a);
+        HG_HIP(hipGetLastError());
+        if (!d_ids) continue;  // count only
+        HG_TRY(launch_range_fill_gather(idx->nch, ga, st));
+        if (flags & HNSWGPU_RANGE_BY_DISTANCE) {
+            hipLaunchKernelGGL(range_sort_kernel, dim3(static_cast<unsigned>(nb)), dim3(kRangeSortThreads), 0, st, a);
+            HG_HIP(hipGetLastError());
+        }
+    }
+    return 0;
+}
+
+static int range_filtered_dev(hnswgpu_index *idx, MaskForm form, const float *d_Q, int32_t nq, const float *d_radius, int32_t flags,
+                              const uint32_t *d_allow, int64_t *d_lims, int32_t *d_out_ids, float *d_out_dist, int64_t cap, void *stream) {
+    HG_TRY(check_range_args(idx, d_Q, nq, d_radius, flags, d_lims, d_out_ids, d_out_dist, cap));
+    HG_REQUIRE(d_allow, HNSWGPU_EINVAL, "allow is null");
+    if (nq == 0) return 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Call call;
+    HG_TRY(call.open(idx, st));
+    if (idx->n == 0) {
+        hipLaunchKernelGGL(range_zero_lims_kernel, dim3((nq + 1 + 255) / 256), dim3(256), 0, st, d_lims, static_cast<int64_t>(nq) + 1);
+        HG_HIP(hipGetLastError());
+        return call.close();
+    }
+    HG_TRY(idx->s_rmeta.ensure(sizeof(unsigned long long)));
+    HG_TRY(range_filtered_enqueue(idx, form, d_Q, nq, d_radius, flags, d_allow, d_lims, d_out_ids, d_out_dist, cap,
+                                  idx->s_rmeta.as<unsigned long long>(), st));
+    return call.close();
+}
+
+// Host arrays.  One caller's staged batch, its mask -- Each: its [nq][W] masks -- staged whole: no part in the call combiner.
+static int range_filtered_host(hnswgpu_index *idx, MaskForm form, const float *Q, int32_t nq, const float *radius, int32_t flags,
+                               const uint32_t *allow, int64_t *lims, int32_t *out_ids, float *out_dist, int64_t cap) {
+    HG_TRY(check_range_args(idx, Q, nq, radius, flags, lims, out_ids, out_dist, cap));
+    HG_REQUIRE(allow, HNSWGPU_EINVAL, "allow is null");
+    if (nq == 0) {
+        if (lims) lims[0] = 0;
+        return 0;
+    }
+    if (idx->n == 0) {
+        memset(lims, 0, sizeof(int64_t) * (static_cast<size_t>(nq) + 1));
+        return 0;
+    }
+    hipStream_t st = idx->stream;
+    Call call;
+    HG_TRY(call.open(idx, st));
+    HG_TRY(upload_queries(idx, Q, nq, st));
+    HG_TRY(call.stage_mask(allow, form, nq));
+    // s_rmeta: [running total][lims: nq + 1][radii: nq]
+    const size_t lims_bytes = sizeof(int64_t) * (static_cast<size_t>(nq) + 1);
+    HG_TRY(idx->s_rmeta.ensure(sizeof(unsigned long long) + lims_bytes + sizeof(float) * static_cast<size_t>(nq)));
+    unsigned long long *d_run = idx->s_rmeta.as<unsigned long long>();
+    int64_t *d_lims = reinterpret_cast<int64_t *>(d_run + 1);
+    float *d_radius = reinterpret_cast<float *>(d_lims + nq + 1);
+    HG_HIP(hipMemcpyAsync(d_radius, radius, sizeof(float) * static_cast<size_t>(nq), hipMemcpyHostToDevice, st));
+    if (out_ids) {
+        HG_TRY(idx->s_ids.ensure(sizeof(int32_t) * static_cast<size_t>(cap)));
+        HG_TRY(idx->s_outd.ensure(sizeof(float) * static_cast<size_t>(cap)));
+    }
+    HG_TRY(range_filtered_enqueue(idx, form, idx->s_q.as<float>(), nq, d_radius, flags, idx->s_fmask.as<uint32_t>(), d_lims,
+                                  out_ids ? idx->s_ids.as<int32_t>() : nullptr, out_ids ? idx->s_outd.as<float>() : nullptr, cap, d_run, st));
+    HG_HIP(hipMemcpyAsync(lims, d_lims, lims_bytes, hipMemcpyDeviceToHost, st));
+    HG_TRY(call.sync());
+    const int64_t total = lims[nq];
+    if (out_ids && total > cap) {
+        (void)call.close();
+        set_error("the result holds %lld entries, the arrays %lld: lims is complete, size the arrays by lims[nq]", (long long)total, (long long)cap);
+        return HNSWGPU_ELIMIT;
+    }
+    if (out_ids && total > 0) HG_TRY(call.stage_out(out_ids, out_dist, total));
+    return call.close();
+}
+
 }  // namespace hg
 
 using namespace hg;
@@ -168,4 +342,23 @@ int hnswgpu_range_search(hnswgpu_index *idx, const float *Q, int32_t nq, const f
     }
     if (out_ids && total > 0) HG_TRY(call.stage_out(out_ids, out_dist, total));
     return call.close();
+}
+
+int hnswgpu_range_search_filtered_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, const float *d_radius, int32_t flags,
+                                      const uint32_t *d_allow, int64_t *d_lims, int32_t *d_out_ids, float *d_out_dist, int64_t cap,
+                                      void *stream) {
+    return range_filtered_dev(idx, MaskForm::Single, d_Q, nq, d_radius, flags, d_allow, d_lims, d_out_ids, d_out_dist, cap, stream);
+}
+int hnswgpu_range_search_filtered(hnswgpu_index *idx, const float *Q, int32_t nq, const float *radius, int32_t flags,
+                                  const uint32_t *allow, int64_t *lims, int32_t *out_ids, float *out_dist, int64_t cap) {
+    return range_filtered_host(idx, MaskForm::Single, Q, nq, radius, flags, allow, lims, out_ids, out_dist, cap);
+}
+int hnswgpu_range_search_filtered_each_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, const float *d_radius, int32_t flags,
+                                           const uint32_t *d_allow_each, int64_t *d_lims, int32_t *d_out_ids, float *d_out_dist,
+                                           int64_t cap, void *stream) {
+    return range_filtered_dev(idx, MaskForm::Each, d_Q, nq, d_radius, flags, d_allow_each, d_lims, d_out_ids, d_out_dist, cap, stream);
+}
+int hnswgpu_range_search_filtered_each(hnswgpu_index *idx, const float *Q, int32_t nq, const float *radius, int32_t flags,
+                                       const uint32_t *allow_each, int64_t *lims, int32_t *out_ids, float *out_dist, int64_t cap) {
+    return range_filtered_host(idx, MaskForm::Each, Q, nq, radius, flags, allow_each, lims, out_ids, out_dist, cap);
 }

@@ -370,6 +370,32 @@ class Index:
             check(lib().hnswgpu_range_search(self._h, _p(Q), nq, _p(r), flags, _p(lims), _p(ids), _p(d), total))
         return lims, ids, d
 
+    def _range_filtered(self, fn, Q, radius, mask, by_distance):
+        nq = len(Q)
+        r = self._radii(radius, nq)
+        flags = RANGE_BY_DISTANCE if by_distance else 0
+        lims = np.zeros(nq + 1, np.int64)
+        check(fn(self._h, _p(Q), nq, _p(r), flags, _p(mask), _p(lims), None, None, 0))
+        total = int(lims[nq])
+        ids = np.empty(total, np.int32)
+        d = np.empty(total, np.float32)
+        if total:
+            check(fn(self._h, _p(Q), nq, _p(r), flags, _p(mask), _p(lims), _p(ids), _p(d), total))
+        return lims, ids, d
+
+    def range_search_filtered(self, Q, radius, allow, by_distance=False):
+        """hnswgpu_range_search_filtered: range_search among the rows ``allow`` (pack_mask) lets pass -- the unfiltered result
+        with the failing rows dropped, ids and distance bits alike, at the cost of the passing rows.  Counts first, then
+        allocates (by the filtered count), then fills."""
+        Q = _queries(Q, self.dim)
+        return self._range_filtered(lib().hnswgpu_range_search_filtered, Q, radius, _mask_words(allow, self.n), by_distance)
+
+    def range_search_filtered_each(self, Q, radius, allow_each, by_distance=False):
+        """hnswgpu_range_search_filtered_each: segment q is range_search_filtered(Q[q:q + 1], radius[q], allow_each[q]) -- one
+        mask per query (pack_masks); a group of queries fetches the union of its passing rows once."""
+        Q = _queries(Q, self.dim)
+        return self._range_filtered(lib().hnswgpu_range_search_filtered_each, Q, radius, _mask_rows(allow_each, self.n, len(Q)), by_distance)
+
     def rerank(self, Q, cand, k):
         """Per query: exact distances to its candidate rows cand[q] (-1 = skip), stable sort, first k."""
         Q = _queries(Q, self.dim)
@@ -937,6 +963,34 @@ class Index:
                                              lims.data_ptr(), ids.data_ptr() if ids is not None else None,
                                              d.data_ptr() if d is not None else None, cap, st))
         return lims, ids, d
+
+    def _range_filtered_dev(self, fn, Q, radius, mask, cap, by_distance, out):
+        import torch
+
+        nq, cap = Q.shape[0], int(cap)
+        assert radius.is_cuda and radius.dtype == torch.float32 and radius.numel() == nq
+        radius = radius.contiguous()
+        if out is not None:
+            lims, ids, d = out
+        else:
+            lims = torch.empty(nq + 1, dtype=torch.int64, device=Q.device)
+            ids = torch.empty(cap, dtype=torch.int32, device=Q.device) if cap else None
+            d = torch.empty(cap, dtype=torch.float32, device=Q.device) if cap else None
+        check(fn(self._h, Q.data_ptr(), nq, radius.data_ptr(), RANGE_BY_DISTANCE if by_distance else 0, mask.data_ptr(),
+                 lims.data_ptr(), ids.data_ptr() if ids is not None else None, d.data_ptr() if d is not None else None, cap,
+                 torch.cuda.current_stream(Q.device).cuda_stream))
+        return lims, ids, d
+
+    def range_search_filtered_dev(self, Q, radius, allow, cap, by_distance=False, out=None):
+        """hnswgpu_range_search_filtered_dev on torch's current stream: enqueues only and never synchronises (no passing
+        count is read back).  Arguments and results as range_search_dev; ``allow``: the packed mask on the device."""
+        Q = self._dev_args(Q, 1, out=(None, None))[0]
+        return self._range_filtered_dev(lib().hnswgpu_range_search_filtered_dev, Q, radius, self._dev_mask(allow, Q), cap, by_distance, out)
+
+    def range_search_filtered_each_dev(self, Q, radius, allow_each, cap, by_distance=False, out=None):
+        """hnswgpu_range_search_filtered_each_dev on torch's current stream: enqueues only and never synchronises."""
+        Q = self._dev_args(Q, 1, out=(None, None))[0]
+        return self._range_filtered_dev(lib().hnswgpu_range_search_filtered_each_dev, Q, radius, self._dev_masks(allow_each, Q), cap, by_distance, out)
 
     def dense_distances_dev(self, Q, out=None):
         import torch

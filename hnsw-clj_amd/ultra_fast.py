@@ -183,26 +183,44 @@ def search_batch(graph, queries, k, ef=None, route=False):
     return [_format(graph, ids[i], d[i]) for i in range(len(queries))]
 
 
-def search_radius_batch(graph, queries, radius):
+def search_radius_batch(graph, queries, radius, allow=None, allow_each=None):
     """Every row within ``radius`` (a scalar or one value per query) of each query -- exact, not in the reference, whose REPL
     speaks of results as "at least 80 % similar" but can only ask for k of them.  One list per query of ``{"id", "distance"}``
-    with the caller's ids, ascending by distance (hnswgpu_range_search with HNSWGPU_RANGE_BY_DISTANCE: sorted on the device)."""
+    with the caller's ids, ascending by distance (hnswgpu_range_search with HNSWGPU_RANGE_BY_DISTANCE: sorted on the device).
+    ``allow`` (one packed mask or bool array over the rows) or ``allow_each`` (one per query) keeps the search among the rows
+    that pass (hnswgpu_range_search_filtered[_each]): only those rows are read."""
     queries = np.asarray(queries, np.float32)
     if queries.ndim == 1:
         queries = queries[None, :]
+    if allow is not None and allow_each is not None:
+        raise ValueError("allow and allow_each exclude each other")
     if len(queries) == 0:
         return []
-    if graph.index.n == 0:
+    n = graph.index.n
+    if n == 0:
         return [[] for _ in queries]
-    lims, ids, d = graph.index.range_search(queries, radius, by_distance=True)
+    if allow is not None:
+        allow = np.asarray(allow)
+        lims, ids, d = graph.index.range_search_filtered(queries, radius, allow if allow.dtype == np.uint32 else engine.pack_mask(allow, n),
+                                                         by_distance=True)
+    elif allow_each is not None:
+        if len(allow_each) != len(queries):
+            raise ValueError("allow_each holds %d masks for %d queries" % (len(allow_each), len(queries)))
+        packed = isinstance(allow_each, np.ndarray) and allow_each.dtype == np.uint32
+        lims, ids, d = graph.index.range_search_filtered_each(queries, radius, allow_each if packed else engine.pack_masks(allow_each, n),
+                                                              by_distance=True)
+    else:
+        lims, ids, d = graph.index.range_search(queries, radius, by_distance=True)
     return [_format(graph, ids[lims[q]:lims[q + 1]], d[lims[q]:lims[q + 1]]) for q in range(len(queries))]
 
 
-def search_radius(graph, query_vec, radius):
+def search_radius(graph, query_vec, radius, allow=None):
     """search_radius_batch for one query."""
     if graph.index.n == 0:
         return []
-    return search_radius_batch(graph, np.asarray(query_vec, np.float32)[None, :], radius)[0]
+    if allow is None:
+        return search_radius_batch(graph, np.asarray(query_vec, np.float32)[None, :], radius)[0]
+    return search_radius_batch(graph, np.asarray(query_vec, np.float32)[None, :], radius, allow=allow)[0]
 
 
 def filtered_plan(n, p, k, ef=None):

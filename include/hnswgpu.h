@@ -674,13 +674,47 @@ int hnswgpu_ivf_search_filtered_each_dev(hnswgpu_index *idx, const float *d_Q, i
  *     and a ballot -- a wave owns 32 consecutive rows, one word of every query's hit mask -- then popcounts and scans (no
  *     atomic anywhere: the result does not depend on scheduling), then a second look at the hits alone, whose distances are
  *     recomputed one wave per row, and a bitonic sort per query for the distance order.
- *   Out of scope: an allow-mask; range search through a graph, lists, tables or the low-dimensional filter (all of them would be
- *     approximate); groups, shards and forests; combining concurrent callers. */
+ *   Out of scope: range search through a graph, lists, tables or the low-dimensional filter (all of them would be
+ *     approximate); groups, shards and forests; combining concurrent callers.  (Under an allow-mask: below.) */
 #define HNSWGPU_RANGE_BY_DISTANCE 1
 int hnswgpu_range_search(hnswgpu_index *idx, const float *Q, int32_t nq, const float *radius, int32_t flags,
                          int64_t *lims, int32_t *out_ids, float *out_dist, int64_t cap);
 int hnswgpu_range_search_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, const float *d_radius, int32_t flags,
                              int64_t *d_lims, int32_t *d_out_ids, float *d_out_dist, int64_t cap, void *stream);
+/* hnswgpu_range_search_filtered[_each]: range search under an allow-mask -- "within my own documents", per-user visibility,
+ *   tenant partitions -- at the cost of the passing rows, not of the base.
+ *   allow: the mask of the filtered searches above ((n + 31) / 32 words indexed by row id, bits at positions >= n ignored, an
+ *     argument and never handle state).  allow_each: [nq][W], row q is query q's mask, as for the other _each calls.
+ *   Row i belongs to query q's segment iff its bit is set (for q, in the _each form) AND d(q, i) <= radius[q], with the
+ *     distance bits of hnswgpu_batch_distances at every batch size and for all three metrics.  Everything else is
+ *     hnswgpu_range_search's contract, unchanged: lims and the count-only form, HNSWGPU_ELIMIT from the host entries with lims
+ *     complete, ascending row id or HNSWGPU_RANGE_BY_DISTANCE, a NaN radius, nq == 0, n == 0, any handle.  A null mask is -1.
+ *     So the result is the unfiltered call's with the failing rows dropped, ids and distance bits alike; an all-ones mask
+ *     reproduces hnswgpu_range_search bit for bit, and row q of the _each form is the single-mask call of query q with mask q.
+ *   Both _dev entries enqueue only and NEVER synchronise, as hnswgpu_range_search_dev: no passing count is read back (unlike
+ *     hnswgpu_exact_knn_filtered[_each]_dev, nothing here is sized by it), nothing is written at or past cap, and the caller
+ *     compares lims[nq] with cap.  The host entries stage one caller's batch, masks included, and take no part in the call
+ *     combiner.
+ *   How (hnsw-clj_amd/csrc/range_filtered_kernels.hpp): the mask -- _each: the union of a query group's masks, plus a word per
+ *     union row saying which of the group's queries allow it -- is compacted into the ascending list of passing row ids (counts,
+ *     scan, scatter: no atomic); the scan walks list POSITIONS, a wave owning 32 of them = one word of every query's hit mask in
+ *     pass-list space, with the rows gathered through the list; counts and lims are the unfiltered call's; the fill reads a
+ *     hit's row id through the list.  Only passing rows are fetched, hit words past the list's end are cleared and never
+ *     computed, and results are sized by the filtered count.  Scratch is sized by n, not by the passing count: 4 n bytes for
+ *     the list (_each: 8 n + n / 8 per query group of a slice), and the slice of query groups that HNSWGPU_TUNE_FILTER_EACH_MB
+ *     bounds covers them beside the hit words.  Callers of the _each form that sort a batch by mask (equal masks adjacent)
+ *     pay the single-mask call's cost; a group of unrelated masks fetches their union once.
+ *   Out of scope: forests, groups and shards; a rule that switches to filtering after the unfiltered call for near-full masks. */
+int hnswgpu_range_search_filtered(hnswgpu_index *idx, const float *Q, int32_t nq, const float *radius, int32_t flags,
+                                  const uint32_t *allow, int64_t *lims, int32_t *out_ids, float *out_dist, int64_t cap);
+int hnswgpu_range_search_filtered_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, const float *d_radius, int32_t flags,
+                                      const uint32_t *d_allow, int64_t *d_lims, int32_t *d_out_ids, float *d_out_dist,
+                                      int64_t cap, void *stream);
+int hnswgpu_range_search_filtered_each(hnswgpu_index *idx, const float *Q, int32_t nq, const float *radius, int32_t flags,
+                                       const uint32_t *allow_each, int64_t *lims, int32_t *out_ids, float *out_dist, int64_t cap);
+int hnswgpu_range_search_filtered_each_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, const float *d_radius, int32_t flags,
+                                           const uint32_t *d_allow_each, int64_t *d_lims, int32_t *d_out_ids, float *d_out_dist,
+                                           int64_t cap, void *stream);
 
 /* ---- persistence ------------------------------------------------------------------------------------------
  * One flat binary file (header + plain arrays; layout in hnsw-clj_amd/csrc/persist.hip) with the base
