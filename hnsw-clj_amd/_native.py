@@ -101,6 +101,8 @@ _SIGS = {
     "hnswgpu_range_search_filtered_dev": ["p", "p", "i32", "p", "i32", "p", "p", "p", "p", "i64", "p"],
     "hnswgpu_range_search_filtered_each": ["p", "p", "i32", "p", "i32", "p", "p", "p", "p", "i64"],
     "hnswgpu_range_search_filtered_each_dev": ["p", "p", "i32", "p", "i32", "p", "p", "p", "p", "i64", "p"],
+    "hnswgpu_ivf_range_search": ["p", "p", "i32", "p", "i32", "p", "i32", "p", "p", "p", "i64", "p"],
+    "hnswgpu_ivf_range_search_dev": ["p", "p", "i32", "p", "i32", "p", "i32", "p", "p", "p", "i64", "p", "p"],
     "hnswgpu_ivf_search_filtered": ["p", "p", "i32", "i32", "i32", "p", "p", "p", "p"],
     "hnswgpu_ivf_search_filtered_dev": ["p", "p", "i32", "i32", "i32", "p", "p", "p", "p"],
     "hnswgpu_ivf_search_filtered_each": ["p", "p", "i32", "i32", "i32", "p", "p", "p", "p"],

@@ -267,6 +267,8 @@ struct hnswgpu_index {
     hg::DevBuf s_rhits, s_rmeta;
     // ... under an allow-mask (range_filtered_kernels.hpp): the lengths of a slice's pass lists, which nobody reads back
     hg::DevBuf s_rcnt;
+    // ... through the IVF lists (ivf_range_kernels.hpp): the call's probe table | a slice's woff rows | pair order | work items
+    hg::DevBuf s_ivr;
     uint32_t pf_seq = 0;  // number of the last small launch, helper or several-CU kernel (hnsw.hip: hnsw_number_launch is its one owner)
     size_t s_done_n = 0;  // counters per half of s_done (scan tails | route tails)
     uint32_t vis_gen = 0;  // last generation number handed to an HBM visited slab
@@ -609,6 +611,11 @@ int launch_list_foff(hnswgpu_index *idx, const int32_t *d_pass_pos, const unsign
 int launch_ivf_filtered_scan(int nch, const IvfFilteredArgs &a, hipStream_t st);
 // ... with one mask per query
 int launch_ivf_each_scan(int nch, const IvfEachArgs &a, hipStream_t st);
+// Range search through the lists (ivf_range_kernels.hpp; driven by range.hip), the two steps it shares with the top-k search
+// (ivf.hip): the GEMV-order routing of ivf_filtered_chain as a probe table d_probes [nq][np] (np <= nlist), and
+// pair_order_kernel over a table of npairs entries -- d_order: the entries' indices filed by list, those without a list last
+int ivf_route_table(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t np, int32_t *d_probes, hipStream_t st);
+int launch_pair_order(hnswgpu_index *idx, const int32_t *d_probes, int64_t npairs, int32_t *d_order, hipStream_t st);
 
 // The block of host memory of one combined batch -- a Slot's mapped block and the pinned staging block alike:
 // [64-byte header: flag word, repeat count][queries][stats, 2 x int64 per query, or absent][ids][distances], every section on a

@@ -1782,6 +1782,36 @@ static int ivf_filtered_chain(hnswgpu_index *idx, MaskForm form, const float *d_
     return ivf_decode(idx, p, d_out_ids, d_out_dist, nullptr, st);
 }
 
+// The routing above without a scan behind it (range.hip: hnswgpu_ivf_range_search): the np nearest lists of every query in the
+// GEMV order, as the probe table d_probes [nq][np]
+int ivf_route_table(hnswgpu_index *idx, const float *d_Q, int32_t nq, int32_t np, int32_t *d_probes, hipStream_t st) {
+    IvfSearchPlan p;
+    memset(&p, 0, sizeof(p));
+    p.nq = nq;
+    p.k = 1;
+    p.nprobe = np;
+    p.npairs = static_cast<int64_t>(nq) * np;
+    p.scan = IvfScan::Gemv;
+    p.route = ivf_plain_route(idx, nq);
+    HG_REQUIRE(p.npairs < 2147483647LL, HNSWGPU_ELIMIT, "too many (query, list) pairs (%lld)", (long long)p.npairs);
+    HG_TRY(idx->s_pairs.ensure(sizeof(Pair) * static_cast<size_t>(p.npairs)));
+    HG_TRY(idx->s_ord.ensure(sizeof(uint32_t) * static_cast<size_t>(p.npairs)));
+    HG_TRY(idx->s_dist.ensure(sizeof(float) * static_cast<size_t>(p.npairs)));
+    StreamScratch sc;
+    memset(&sc, 0, sizeof(sc));
+    return ivf_route(idx, p, d_Q, nullptr, d_probes, nullptr, sc, st);
+}
+
+int launch_pair_order(hnswgpu_index *idx, const int32_t *d_probes, int64_t npairs, int32_t *d_order, hipStream_t st) {
+    HG_REQUIRE(npairs < 2147483647LL && idx->nlist <= kOrderMaxLists, HNSWGPU_ELIMIT, "too many (query, list) pairs (%lld) or lists (%d)",
+               (long long)npairs, idx->nlist);
+    size_t olds;
+    HG_TRY(order_lds(false, idx->nlist, &olds));
+    hipLaunchKernelGGL(pair_order_kernel, dim3(1), dim3(1024), olds, st, d_probes, static_cast<int>(npairs), idx->nlist, d_order);
+    HG_HIP(hipGetLastError());
+    return 0;
+}
+
 }  // namespace hg
 
 using namespace hg;

@@ -396,6 +396,32 @@ class Index:
         Q = _queries(Q, self.dim)
         return self._range_filtered(lib().hnswgpu_range_search_filtered_each, Q, radius, _mask_rows(allow_each, self.n, len(Q)), by_distance)
 
+    def ivf_range_search(self, Q, radius, nprobe, probes=None, by_distance=False, want_probes=False):
+        """hnswgpu_ivf_range_search: the rows of each query's probed lists within ``radius`` (a scalar, or one value per query),
+        as CSR ``(lims, ids, dist)`` (``+ (probes,)`` with ``want_probes``).  ``probes`` None: the ``nprobe`` nearest lists, as
+        ivf_search routes; otherwise an [nq, nprobe] table of list ids, -1 = skip.  A segment is in the order of the query's
+        candidate stream -- its probed lists one after the other, each in list order, NOT ascending row id -- or ascending by
+        (distance, row id) with ``by_distance``.  Counts first, then allocates, then fills."""
+        Q = _queries(Q, self.dim)
+        nq = len(Q)
+        r = self._radii(radius, nq)
+        if probes is not None:
+            probes = np.ascontiguousarray(probes, np.int32)
+            if probes.ndim != 2 or probes.shape[0] != nq or probes.shape[1] < 1:
+                raise ValueError("probes must be [nq = %d, nprobe >= 1], got %s" % (nq, probes.shape))
+            nprobe = probes.shape[1]
+        flags = RANGE_BY_DISTANCE if by_distance else 0
+        lims = np.zeros(nq + 1, np.int64)
+        pr = np.empty((nq, nprobe), np.int32) if want_probes else None
+        fn = lib().hnswgpu_ivf_range_search
+        check(fn(self._h, _p(Q), nq, _p(r), nprobe, _p(probes), flags, _p(lims), None, None, 0, _p(pr)))
+        total = int(lims[nq])
+        ids = np.empty(total, np.int32)
+        d = np.empty(total, np.float32)
+        if total:
+            check(fn(self._h, _p(Q), nq, _p(r), nprobe, _p(probes), flags, _p(lims), _p(ids), _p(d), total, None))
+        return (lims, ids, d, pr) if want_probes else (lims, ids, d)
+
     def rerank(self, Q, cand, k):
         """Per query: exact distances to its candidate rows cand[q] (-1 = skip), stable sort, first k."""
         Q = _queries(Q, self.dim)
@@ -963,6 +989,34 @@ class Index:
                                              lims.data_ptr(), ids.data_ptr() if ids is not None else None,
                                              d.data_ptr() if d is not None else None, cap, st))
         return lims, ids, d
+
+    def ivf_range_search_dev(self, Q, radius, nprobe, cap, probes=None, by_distance=False, want_probes=False, out=None):
+        """hnswgpu_ivf_range_search_dev on torch's current stream: enqueues only and never synchronises.  Arguments and results
+        as range_search_dev; ``probes``: None (routed) or an int32 device tensor [nq, nprobe]; with ``want_probes`` the table
+        used comes back as a fourth tensor."""
+        import torch
+
+        Q, _, _, st = self._dev_args(Q, 1, out=(None, None))
+        nq, cap = Q.shape[0], int(cap)
+        assert radius.is_cuda and radius.dtype == torch.float32 and radius.numel() == nq
+        radius = radius.contiguous()
+        if probes is not None:
+            assert probes.is_cuda and probes.dtype == torch.int32 and probes.dim() == 2 and probes.shape[0] == nq
+            probes = probes.contiguous()
+            nprobe = probes.shape[1]
+        if out is not None:
+            lims, ids, d = out
+        else:
+            lims = torch.empty(nq + 1, dtype=torch.int64, device=Q.device)
+            ids = torch.empty(cap, dtype=torch.int32, device=Q.device) if cap else None
+            d = torch.empty(cap, dtype=torch.float32, device=Q.device) if cap else None
+        pr = torch.empty((nq, nprobe), dtype=torch.int32, device=Q.device) if want_probes else None
+        check(lib().hnswgpu_ivf_range_search_dev(self._h, Q.data_ptr(), nq, radius.data_ptr(), nprobe,
+                                                 probes.data_ptr() if probes is not None else None,
+                                                 RANGE_BY_DISTANCE if by_distance else 0, lims.data_ptr(),
+                                                 ids.data_ptr() if ids is not None else None, d.data_ptr() if d is not None else None,
+                                                 cap, pr.data_ptr() if pr is not None else None, st))
+        return (lims, ids, d, pr) if want_probes else (lims, ids, d)
 
     def _range_filtered_dev(self, fn, Q, radius, mask, cap, by_distance, out):
         import torch

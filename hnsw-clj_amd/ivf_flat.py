@@ -117,6 +117,18 @@ def update_vectors(index, data):
     return index
 
 
+def range_search(index, query_vec, radius, nprobe=4, by_distance=False):
+    """Not in the reference (its IVF search is top-k alone): every vector of the ``nprobe`` nearest partitions within ``radius``
+    (a scalar, or one value per query) of each query (hnswgpu_ivf_range_search), as lists of ``{"id", "distance"}`` in the
+    reference's candidate order -- the probed partitions one after the other, each in its own order (ivf_flat.clj:281-288) --
+    or ascending by distance with ``by_distance``.  One query gives one list, a batch a list per query."""
+    q = np.asarray(query_vec, np.float32)
+    single = q.ndim == 1
+    lims, ids, d = index.index.ivf_range_search(q[None, :] if single else q, radius, int(nprobe), by_distance=by_distance)
+    out = [_format(index, ids[lims[i]:lims[i + 1]], d[lims[i]:lims[i + 1]]) for i in range(len(lims) - 1)]
+    return out[0] if single else out
+
+
 def _format(index, ids_row, d_row):
     return [{"id": index.ids[i], "distance": float(d)} for i, d in zip(ids_row, d_row) if i >= 0]
 

@@ -674,8 +674,8 @@ int hnswgpu_ivf_search_filtered_each_dev(hnswgpu_index *idx, const float *d_Q, i
  *     and a ballot -- a wave owns 32 consecutive rows, one word of every query's hit mask -- then popcounts and scans (no
  *     atomic anywhere: the result does not depend on scheduling), then a second look at the hits alone, whose distances are
  *     recomputed one wave per row, and a bitonic sort per query for the distance order.
- *   Out of scope: range search through a graph, lists, tables or the low-dimensional filter (all of them would be
- *     approximate); groups, shards and forests; combining concurrent callers.  (Under an allow-mask: below.) */
+ *   Out of scope: range search through a graph, tables or the low-dimensional filter (all of them would be
+ *     approximate); groups, shards and forests; combining concurrent callers.  (Under an allow-mask, and through the IVF lists: below.) */
 #define HNSWGPU_RANGE_BY_DISTANCE 1
 int hnswgpu_range_search(hnswgpu_index *idx, const float *Q, int32_t nq, const float *radius, int32_t flags,
                          int64_t *lims, int32_t *out_ids, float *out_dist, int64_t cap);
@@ -715,6 +715,37 @@ int hnswgpu_range_search_filtered_each(hnswgpu_index *idx, const float *Q, int32
 int hnswgpu_range_search_filtered_each_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, const float *d_radius, int32_t flags,
                                            const uint32_t *d_allow_each, int64_t *d_lims, int32_t *d_out_ids, float *d_out_dist,
                                            int64_t cap, void *stream);
+/* hnswgpu_ivf_range_search: range search through the IVF lists -- the rows of each query's PROBED lists within its radius, at
+ *   the cost of nprobe / nlist of the base.  Approximate as a set (a row in an unprobed list is missed), exact in what it
+ *   reports: row i of a probed list belongs to query q's segment iff d(q, i) <= radius[q], with the distance bits of
+ *   hnswgpu_batch_distances -- the bits hnswgpu_range_search compares; with every list probed the result is that call's result as
+ *   a set, bit for bit.
+ *   probes == NULL: routed as hnswgpu_ivf_search routes -- nprobe clamped to the number of lists, the nearest centroids in the
+ *     GEMV order.  Otherwise probes is [nq][nprobe] list ids, -1 = skip: hnswgpu_ivf_search_lists' table.  An id outside
+ *     [-1, nlist) is -1 from the host entry and reads as a skip in the _dev entry.
+ *   out_probes, when not NULL: the [nq][nprobe] table actually used (-1 where the index has fewer lists than asked for).
+ *   Order inside a segment (flags 0): the query's CANDIDATE STREAM -- its probed lists in probe-table order, each list in list
+ *     order, the reference's candidate order (ivf_flat.clj:281-288) -- NOT ascending row id.  A list named twice in a row of
+ *     probes appears twice.  HNSWGPU_RANGE_BY_DISTANCE: ascending (distance, row id), as hnswgpu_range_search.
+ *   lims, cap, the count-only form (out_ids == out_dist == NULL, cap == 0), HNSWGPU_ELIMIT from the host entry with lims
+ *     complete ("size the arrays by lims[nq]"), a NaN radius, nq == 0, n == 0: hnswgpu_range_search's contract, unchanged.  The
+ *     _dev entry enqueues only and NEVER synchronises or reads back: nothing is written at or past cap, and its caller compares
+ *     lims[nq] with cap.
+ *   Refused: a handle without lists and a shard (hnswgpu_set_ivf_shard), both -3; nprobe < 1 (-1); nprobe > 1024 or more than
+ *     16384 lists (-5); the argument errors of hnswgpu_range_search.
+ *   How (hnsw-clj_amd/csrc/ivf_range_kernels.hpp): the (query, list) pairs are filed by list and a workgroup scans a chunk of
+ *     ONE list's contiguous rows for a block of the queries that probe it, gathered into LDS: a list is read once per block of
+ *     queries, not once per query.  A list always starts a fresh word of a query's hit mask (which lives in stream space), so a
+ *     wave that owns 32 consecutive list positions owns one whole word of every such query: one writer per word, no atomic.
+ *     Counts, lims and the sort are hnswgpu_range_search's; the fill finds a hit's probe through the query's word offsets.  A
+ *     slice of query groups (hit words: the nprobe largest lists' words per query) is bounded by HNSWGPU_TUNE_FILTER_EACH_MB.
+ *   Out of scope: allow-masks; groups, shards and forests; the call combiner; the int8 / half-precision bounds as a pre-test. */
+int hnswgpu_ivf_range_search(hnswgpu_index *idx, const float *Q, int32_t nq, const float *radius, int32_t nprobe,
+                             const int32_t *probes, int32_t flags, int64_t *lims, int32_t *out_ids, float *out_dist, int64_t cap,
+                             int32_t *out_probes);
+int hnswgpu_ivf_range_search_dev(hnswgpu_index *idx, const float *d_Q, int32_t nq, const float *d_radius, int32_t nprobe,
+                                 const int32_t *d_probes, int32_t flags, int64_t *d_lims, int32_t *d_out_ids, float *d_out_dist,
+                                 int64_t cap, int32_t *d_out_probes, void *stream);
 
 /* ---- persistence ------------------------------------------------------------------------------------------
  * One flat binary file (header + plain arrays; layout in hnsw-clj_amd/csrc/persist.hip) with the base
